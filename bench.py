@@ -10,13 +10,23 @@ N > 1 (config C4): one process per GPU, the frame sharded by screen bands; the e
 words; rccl: b32_gather_bands_rccl; torch: torch.distributed gather) -- checked against the torch-gathered frame before anything is timed,
 with a fallback the line reports (`transport`).
 
-Prints ONE JSON line on rank 0 (see the driver contract), with
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times exactly --steps steps and reports
+metric / value / unit / higher_is_better / dtype / ms_per_step (+ the Mpixels/s of the same steps and the run's configuration).
+With --full the line also holds
+  frame_sha256   the timed frame's SHA-256, checked against tests/golden/hashes.json
   roofline       dominant kernel vs the 8 TB/s HBM peak (HIP events on the kernel's own stream, inside the timed region)
   cpu_baseline   the CPU port of the reference (oracle/, release-profile build, 1 thread) timed on this box's host cores
   cpu_all_cores  the same port threaded (transform split by vertex range, draw split by row band)
   configs        (N = 1) the other BASELINE configs -- C1, C2, C5 -- and C3 with a transparent pass, each with ms/frame, Mtri/s, Mpix/s, frame-level roofline
                  fraction and a framebuffer SHA-256 checked against tests/golden/hashes.json
   protocol       SURVEY 8d extras: median of the per-step times, output-pixel rate, H2D of the scene, D2H of the frame
+  weak_series    (N > 1; also without --full when --weak-series is given) the weak-scaling point of SURVEY 8e
+
+--dump-outputs DIR writes what the last timed step computed, in float32 / float64 .npy files (under 64 MB in all):
+  frame.npy            (H, W, 4) RGBA8 framebuffer as float32, when it fits; otherwise
+  frame_sample.npy     (2^21, 4) float32: the pixels of a fixed seeded sample of pixel indices (sorted), and
+  frame_row_sums.npy   (H, 4) float64: per-row sums of every channel (every pixel of the frame contributes)
+  timings.npy          float64 [triangles_drawn, fragments, tile_pairs] of the RasterTimings the frame returned
 """
 import argparse
 import hashlib
@@ -56,7 +66,7 @@ def main():
                     help="one stream only: no setup kernel of the next frame beside the fill of the current one (b32_set_routes B32_ROUTE_PIPELINE; "
                          "profiling runs that want kernel durations without overlap)")
     ap.add_argument("--weak-series", action="store_true",
-                    help="also time the weak-scaling point of SURVEY 8e (N x 125 k tris on the same frame); always on for N > 1")
+                    help="also time the weak-scaling point of SURVEY 8e (N x 125 k tris on the same frame); always on for N > 1 with --full")
     ap.add_argument("--sync-gather", action="store_true",
                     help="N > 1: gather every frame before the next one starts (default: frames alternate between two framebuffers and the "
                          "gather of one overlaps the rendering of the next, after a run-time self-check against the synchronous frame)")
@@ -70,6 +80,11 @@ def main():
                          "line says so -- when its set-up or its run-time self-check against the torch-gathered frame fails")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default). gloo = debug only: ranks may share one GPU, band rows are staged through the host")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: frame hash, protocol extras, per-kernel passes and roofline, "
+                         "CPU baselines, the other configs, the weak-scaling point at N > 1 (off: the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's framebuffer and RasterTimings to DIR/*.npy (rank 0)")
     args = ap.parse_args()
 
     import numpy as np
@@ -326,7 +341,7 @@ def main():
 
     # ---- N > 1 only: the frame LATENCY beside the pipelined throughput -- K frames, each gathered before the next one starts
     sync_ms = None
-    if pipelined:
+    if pipelined and args.full:
         sync_all()
         s0 = time.perf_counter()
         for _ in range(args.steps):
@@ -376,6 +391,22 @@ def main():
     ctx.set_profiling_stride(1)
     pipelined_frames = ctx.route_counts().get("pipelined", 0) - pipelined_before      # frames of the timed region only
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the framebuffer (the set the last step drew into) and its RasterTimings
+        last_fb = sets[(args.steps - 1) % len(sets)][0] if pipelined else fb
+        px = last_fb.pixels.reshape(H, W, 4)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+
+        def out(name, a):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        if px.size * 4 <= 48 << 20:
+            out("frame", px.astype(np.float32))
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(W * H, size=1 << 21, replace=False))
+            out("frame_sample", px.reshape(W * H, 4)[idx].astype(np.float32))
+        out("frame_row_sums", px.sum(axis=1, dtype=np.float64))
+        out("timings", np.array([tm.triangles_drawn, tm.fragments, tm.tile_pairs], np.float64))
+
     frags = torch.tensor([float(exact_fragments)], dtype=torch.float64, device=rdev)
     if world > 1:
         dist.all_reduce(frags, op=dist.ReduceOp.SUM)
@@ -385,7 +416,7 @@ def main():
 
     # ---- SURVEY 8d protocol extras (untimed region): per-step device times -> median; D2H of the finished frame
     per_step = []
-    if world == 1:
+    if world == 1 and args.full:
         n_med = max(args.steps, 20)
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
         torch.cuda.synchronize(dev)
@@ -397,7 +428,7 @@ def main():
         torch.cuda.synchronize(dev)
         per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
     d0 = time.perf_counter()
-    final_host = fb.pixels if rank == 0 else None               # b32_fb_download: the presenter's copy (game/renderer.rs:179)
+    final_host = fb.pixels if rank == 0 and (args.full or args.check) else None      # b32_fb_download: the presenter's copy (game/renderer.rs:179)
     d2h_ms = (time.perf_counter() - d0) * 1e3
 
     # ---- kernel durations WITHOUT overlap (untimed passes, one stream): in the timed region the next frame's setup kernel runs beside
@@ -406,7 +437,7 @@ def main():
     # path) is what an event pair itself costs.
     cover_ms, cover_samples, phases = None, 0, {}
     shader_clock_ghz, shader_clock_ms = 0.0, 0.0
-    if world == 1:
+    if world == 1 and args.full:
         ctx.set_routes(R.Context.ROUTE_PIPELINE | args.routes_off)
         n_iso = min(max(args.steps, 24), 60)
         ctx.set_profiling(1)
@@ -471,7 +502,7 @@ def main():
     # fixed C3 scene, i.e. strong scaling, as `metric` states); raw times only, the driver derives efficiencies.
     final_frame = final_host if (args.check and rank == 0) else None      # the C3 frame, before the weak series redraws
     weak = None
-    if world > 1 or args.weak_series:
+    if (world > 1 and args.full) or args.weak_series:
         per_gpu = 125000
         wsc = scenegen.make_scene(args.config, n_tris=per_gpu * world)
         wrs = R.ResidentScene(fb, wsc.vertices, wsc.faces, indexed_textures=wsc.indexed_textures)
@@ -535,7 +566,7 @@ def main():
     # ---- the other BASELINE configs on this GPU (N = 1): C1 and C2 (320x240) and C5 (heavy overdraw), same protocol, frames checked
     # against the committed hashes
     side = None
-    if world == 1 and rank == 0 and not args.no_configs and args.config == "C3" and args.tris is None:
+    if args.full and world == 1 and rank == 0 and not args.no_configs and args.config == "C3" and args.tris is None:
         side = {}
         for name in ("C1", "C2", "C5", "C3:blend"):
             # ("C3:blend": the headline scene with 10 % of its faces in the transparent pass -- ordinary content for the reference,
@@ -588,7 +619,7 @@ def main():
         tex_bytes = sum(t.width * t.height * 2 for t in sc.textures)
         alg_frame = 36 * len(sc.vertices) + 20 * NF + 16 * tm.triangles_drawn + 8 * W * H + tex_bytes   # SURVEY 8d B_alg
         roofline = None
-        if cover_ms:
+        if cover_ms and args.full:
             alg_cover = 72 * tm.tile_pairs + 16 * tm.triangles_drawn + 4 * W * (y1 - y0) + tex_bytes
             ach = alg_cover / (cover_ms * 1e-3) / 1e9
             # HBM traffic of the dominant kernel: PMC counters need rocprofv3 around the process, so this is the per-launch figure of
@@ -653,7 +684,7 @@ def main():
                                      "traffic_frac_of_peak": round(s_traffic / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if s_traffic else None}
         cpu = None
         cpu_all = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as O
             ofb = O.Framebuffer(W, H)
             reps, t_cpu = 0, 0.0
@@ -707,8 +738,6 @@ def main():
                 bad = (got.reshape(H, W, 4) != cfb.pixels.reshape(H, W, 4)).any(axis=2)
                 rows = np.nonzero(bad.any(axis=1))[0]
                 print(f"#   {int(bad.sum())} pixels differ, rows {rows.min()}..{rows.max()} ({len(rows)} rows)", file=sys.stderr)
-        sha = hashlib.sha256(final_host).hexdigest()
-        want = HASHES.get(args.config, {}).get("sha256") if args.tris is None else None
         line = {
             "metric": "Mtriangles/s + Mpixels/s, 1M-tri synthetic scene @ 2560x1920",
             "value": round(mtri, 3), "unit": "Mtriangles/s",
@@ -725,29 +754,34 @@ def main():
                            "b32_gather_bands_rccl through the C ABI (grouped ncclSend / ncclRecv on the frame's stream) after every frame" if transport["used"] == "rccl" else
                            "torch.distributed gather " + ("overlapped with the next frame (two framebuffers)" if pipelined else "after every frame"))) if world > 1 else "single GPU"},
             "transport": transport if world > 1 else None,
-            "frame_sha256": sha[:16], "bit_exact_vs_committed_hash": (sha == want) if want else None,
             "build_digest": build_digest, "csrc_digest": csrc_digest(),     # the loaded library's own digest == the source tree's (checked at start)
-            "protocol": {"ms_per_step_median": round(per_step[len(per_step) // 2], 5) if per_step else None,
-                         "ms_per_step_min": round(per_step[0], 5) if per_step else None,
-                         "median_over": len(per_step), "median_note": "HIP events between consecutive steps on the frame's stream (separate pass)",
-                         "h2d_ms": round(h2d_ms, 3), "h2d_bytes": h2d_bytes, "d2h_ms": round(d2h_ms, 3), "d2h_bytes": W * H * 4,
-                         "sync_gather_ms_per_step": round(sync_ms, 5) if sync_ms is not None else None,
-                         "untimed_frames_before_timed_region": SUSTAIN_FRAMES + args.warmup + 1,
-                         "async_depth": 1, "frames_in_flight": 1 if args.no_pipeline else 2, "pipelined_frames_in_timed_region": pipelined_frames,
-                         "async_note": "timed region: b32_set_async_depth(1), frames enqueued back to back; the setup kernel of frame i+1 runs on the "
-                                       "library's second stream beside the fill of frame i (two frame sets); every frame is cleared, set up and drawn in full",
-                         "frame_latency_ms": round(latency_ms, 5) if latency_ms else None,
-                         "ms_per_step_one_stream": round(one_stream_ms, 5) if one_stream_ms else None,
-                         "ms_per_step_safe_mode": round(safe_ms, 5) if safe_ms else None,
-                         "ms_per_step_safe_mode_bound_fb": round(safe_bound_ms, 5) if safe_bound_ms else None,
-                         "safe_mode_frame_identical": (safe_sha == sha) if safe_sha else None,
-                         "safe_mode_note": "b32_set_async_depth(0), the library default.  ms_per_step_safe_mode: the library's own framebuffer (b32_fb_new) -- a clear of the "
-                                           "whole band supersedes the pending frame, no host synchronisation per frame; ..._bound_fb: caller-bound memory (b32_fb_bind_device, "
-                                           "this run's torch tensor) -- every clear settles the pending frame (one host synchronisation): it can be read behind the library's back"},
-            "phases_ms": {k: round(v, 4) for k, v in phases.items()},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            sha = hashlib.sha256(final_host).hexdigest()
+            want = HASHES.get(args.config, {}).get("sha256") if args.tris is None else None
+            line.update({
+                "frame_sha256": sha[:16], "bit_exact_vs_committed_hash": (sha == want) if want else None,
+                "protocol": {"ms_per_step_median": round(per_step[len(per_step) // 2], 5) if per_step else None,
+                             "ms_per_step_min": round(per_step[0], 5) if per_step else None,
+                             "median_over": len(per_step), "median_note": "HIP events between consecutive steps on the frame's stream (separate pass)",
+                             "h2d_ms": round(h2d_ms, 3), "h2d_bytes": h2d_bytes, "d2h_ms": round(d2h_ms, 3), "d2h_bytes": W * H * 4,
+                             "sync_gather_ms_per_step": round(sync_ms, 5) if sync_ms is not None else None,
+                             "untimed_frames_before_timed_region": SUSTAIN_FRAMES + args.warmup + 1,
+                             "async_depth": 1, "frames_in_flight": 1 if args.no_pipeline else 2, "pipelined_frames_in_timed_region": pipelined_frames,
+                             "async_note": "timed region: b32_set_async_depth(1), frames enqueued back to back; the setup kernel of frame i+1 runs on the "
+                                           "library's second stream beside the fill of frame i (two frame sets); every frame is cleared, set up and drawn in full",
+                             "frame_latency_ms": round(latency_ms, 5) if latency_ms else None,
+                             "ms_per_step_one_stream": round(one_stream_ms, 5) if one_stream_ms else None,
+                             "ms_per_step_safe_mode": round(safe_ms, 5) if safe_ms else None,
+                             "ms_per_step_safe_mode_bound_fb": round(safe_bound_ms, 5) if safe_bound_ms else None,
+                             "safe_mode_frame_identical": (safe_sha == sha) if safe_sha else None,
+                             "safe_mode_note": "b32_set_async_depth(0), the library default.  ms_per_step_safe_mode: the library's own framebuffer (b32_fb_new) -- a clear of the "
+                                               "whole band supersedes the pending frame, no host synchronisation per frame; ..._bound_fb: caller-bound memory (b32_fb_bind_device, "
+                                               "this run's torch tensor) -- every clear settles the pending frame (one host synchronisation): it can be read behind the library's back"},
+                "phases_ms": {k: round(v, 4) for k, v in phases.items()},
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+            })
         if side is not None:
             line["configs"] = side
         if weak is not None:

@@ -10,7 +10,8 @@ and tests assert equality on all three sides:
     tests/test_oracle_kats.py::test_oracle_constants_are_the_reference_text   (C oracle tap b32o_constants)
     tests/test_oracle_kats.py::test_np_model_constants_are_the_reference_text (oracle/np_model.py loads the fixture)
     tests/test_gpu_parity.py::test_device_constants_are_the_reference_text    (device tap b32_device_constants, runs on the GPU)
-    tests/test_oracle_kats.py::test_fixture_is_current                        (re-derives the fixture when /root/reference is present)
+    tests/test_oracle_kats.py::test_fixture_is_well_formed                    (shape of the committed fixture)
+    python tests/golden/pin_constants.py --check                              (re-derives the fixture from the reference tree and compares)
 The fixture holds numbers and where they came from -- no reference source text.
 """
 import json
@@ -205,6 +206,10 @@ def main():
     if not os.path.isdir(SRC):
         raise SystemExit(f"{SRC} not found: this script runs in the build container only")
     out = derive()
+    if "--check" in sys.argv[1:]:
+        same = out == json.load(open(OUT))
+        print("ok" if same else f"{OUT} differs from what the reference text gives")
+        return 0 if same else 1
     json.dump(out, open(OUT, "w"), indent=1, sort_keys=True)
     for k in sorted(out):
         if k != "unr.table":

@@ -1261,7 +1261,7 @@ def test_bench_c4_through_the_c_abi(transport):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "6", "--warmup", "2",
-                        "--transport", transport, "--dist-backend", "gloo", "--check"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--transport", transport, "--dist-backend", "gloo", "--check", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert "parity vs oracle: bit-exact" in r.stderr, r.stderr[-3000:]
@@ -1274,6 +1274,28 @@ def test_bench_c4_through_the_c_abi(transport):
     else:
         assert t["used"] == "torch" and t["self_check"] == "failed" and t["fallback_reason"], t
     assert line["weak_series"]["tris"] == 500000
+
+
+def test_bench_dump_outputs_are_the_timed_frame(tmp_path):
+    """bench.py --dump-outputs in a plain run (no --full): exactly --steps timed steps, no side measurement in the line, and the files
+    hold what the last timed step returned -- at C1 the whole framebuffer, which must be the committed frame."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--config", "C1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["unit"] == "Mtriangles/s"
+    assert not {"cpu_baseline", "configs", "roofline", "protocol", "weak_series"} & set(line)
+    frame = np.load(out / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (240, 320, 4)
+    px = frame.astype(np.uint8)
+    assert np.array_equal(px, frame) and hashlib.sha256(px.tobytes()).hexdigest() == HASHES["C1"]["sha256"]
+    assert np.array_equal(np.load(out / "frame_row_sums.npy"), px.sum(axis=1, dtype=np.float64))
+    tm = np.load(out / "timings.npy")
+    assert tm.dtype == np.float64 and tm[0] == HASHES["C1"]["triangles_drawn"]
 
 
 def _console_meshes(n_meshes, seed0, blend_every=4):
