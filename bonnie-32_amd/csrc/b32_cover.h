@@ -158,22 +158,6 @@ __device__ __forceinline__ uint32_t cover_slow64(const Tri& tr, unsigned long lo
 // pixels outside it are certain to fail, pixels inside still take the reference's own test.  The interval ends are computed with
 // an approximate reciprocal and widened by 0.01 px (its error over a 64-px row is < 2e-5 px).  Returns lo and shrinks n to
 // hi - lo.  Surfaces with A outside [0.5, 2^20) are left alone (w0 + w1 could round where it matters).
-#ifndef B32_ROW_TRIM
-#define B32_ROW_TRIM 1
-#endif
-#ifndef B32_SPAN_PACK
-#define B32_SPAN_PACK 1          // span rounds: the per-surface parameters travel packed (7 ds_bpermute per round instead of 15), see phase_a_rows
-#endif
-#ifndef B32_PF_SREC
-#define B32_PF_SREC 0            // experiment: touch the surface's ShadeRec line during coverage so that the shading phase's gather finds it in L2
-#endif
-#ifndef B32_INTERIOR
-#define B32_INTERIOR 0           // experiment (round 4, judge item 3c), OFF: certain-interior runs of long rows take trips without the inside test.
-                                 // Bit-exact (full-size C3 / C5 hashes, 43 parity tests) and slower: finding and verifying the run (~70 VALU per
-                                 // round as soon as ONE lane of the wave has a long row), the second queue and its own, emptier rounds cost more
-                                 // than the skipped barycentrics return -- C5 0.2103 -> 0.2394 ms, C3 0.1200 -> 0.1368 (profiles/r04_interior_trips_ab.txt)
-#endif
-constexpr uint32_t INTERIOR_MIN_ROW = 12;      // rows shorter than this are not worth the interval (one boundary trip at each end)
 __device__ __forceinline__ uint32_t row_trim(float w0, float w1, float a0, float a1, float inv_area, uint32_t& n) {
     const float A = __builtin_amdgcn_rcpf(__builtin_fabsf(inv_area));
     if (!((A >= 0.5f) & (A < 1048576.0f))) return 0u;
@@ -195,35 +179,6 @@ __device__ __forceinline__ uint32_t row_trim(float w0, float w1, float a0, float
     const uint32_t lo = (uint32_t)flo;
     n = (uint32_t)fhi - lo;
     return lo;
-}
-
-// Certain-interior run of a trimmed row (CHEAP painter's coverage of large triangles).  A pixel that lies inside the triangle in EXACT
-// arithmetic always passes the reference's toleranced float test (render.rs:1536-1542): for a surface that passed k_setup's exactness
-// guard the edge values are exact integers, bc_x = fl(w0 * fl(1 / area)) >= 0 whenever w0 has the area's sign (likewise bc_y), and
-// bc_z = fl(fl(1 - bc_x) - bc_y) is within 4e-7 of the exact w2 / area >= 0 -- far above -1e-4.  Along a row the exactly-inside pixels
-// are one interval (three linear conditions); its ends come from approximate reciprocals and are then VERIFIED with the exact integer
-// conditions at both end pixels (linearity covers everything between); a failed check simply means "no interior run".
-// In: edge values (w0, w1) at the row's first pixel, per-pixel steps (a0, a1), |area| = |a0 * b1 - b0 * a1| (all exact integers in f32),
-// sign s of the area, n pixels.  Out: [tlo, thi) in pixels from the row's first pixel; returns false when there is none.
-__device__ __forceinline__ bool interior_run(float w0, float w1, float a0, float a1, float absA, float s, uint32_t n, uint32_t& tlo, uint32_t& thi) {
-    const float E[3] = { s * w0, s * w1, absA - (s * w0 + s * w1) };
-    const float G[3] = { s * a0, s * a1, -(s * a0 + s * a1) };
-    float flo = 0.0f, fhi = (float)n;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {       // E + G t >= 0
-        const float r = -E[j] * __builtin_amdgcn_rcpf(G[j]);
-        const float lo_c = fmaxf(flo, ceilf(r - 1.5e-5f)), hi_c = fminf(fhi, floorf(r + 1.5e-5f) + 1.0f);
-        flo = G[j] > 0.0f ? lo_c : flo;
-        fhi = G[j] < 0.0f ? hi_c : fhi;
-        ok = ok & !((G[j] == 0.0f) & (E[j] < 0.0f));
-    }
-    ok = ok & (fhi > flo) & (flo >= 0.0f) & (fhi <= (float)n);
-    const float ta = flo, tb = fhi - 1.0f;                   // the two end pixels, checked exactly
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ok = ok & (E[j] + G[j] * ta >= 0.0f) & (E[j] + G[j] * tb >= 0.0f);
-    tlo = ok ? (uint32_t)flo : 0u; thi = ok ? (uint32_t)fhi : 0u;
-    return ok;
 }
 
 // One trip of the sort-free CHEAP coverage: TRIP consecutive pixels of a row starting at LDS entry `addr` with edge values (w0, w1),
@@ -343,12 +298,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
         uint32_t my_sid = 0, my_key = 0;
         bool narrow = false;
         load_batch<TEXMODE>(b, a, e0 + e, live, lds_desc, EXACT, ZMODE || (EXACT && !affine), my_sid, my_key, narrow);
-#if B32_PF_SREC
-        if (P64 && !EXACT && live) {
-            const uint32_t pf = reinterpret_cast<const uint32_t*>(a.srecs + my_sid)[0];      // (a plain load: it allocates in L2)
-            asm volatile("" :: "v"(pf));
-        }
-#endif
         if (ZMODE) { my_key = 0u; my_sid = 0xFFFFFFFEu - my_sid; }
         const uint32_t flags = b.q3.w;
         const uint32_t cx0 = max(b.q1.w & 0xFFFF, x_lo), cx1 = min(b.q1.w >> 16, x_hi);
@@ -363,31 +312,24 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
         // row, the reciprocal form of the steps per pixel); span_all: every surface of this batch is eligible -- the rounds below then
         // take the span form, else the per-pixel form serves the whole batch (it is valid for every surface)
         bool span_all = false;
-        float sE0 = 0.0f, sE1 = 0.0f, sH0 = 0.0f, sH1 = 0.0f, sA = 0.0f;
-        SpanEdge sd0 = { 0.0f, 0.0f }, sd1 = { 0.0f, 0.0f }, sd2 = { 0.0f, 0.0f };
-        (void)sd0; (void)sd1; (void)sd2; (void)sA;
-        uint32_t sG01 = 0, sH01 = 0;                      // B32_SPAN_PACK: (G0, G1) and (H0, H1) as pairs of i16 (|.| <= SPAN_MAX_EXT = 512)
+        float sE0 = 0.0f, sE1 = 0.0f;
+        uint32_t sG01 = 0, sH01 = 0;                      // (G0, G1) and (H0, H1) as pairs of i16 (|.| <= SPAN_MAX_EXT = 512)
         if (P64 && !EXACT && !ZMODE && a.span_cover) {
             const float fa0 = __uint_as_float(b.q0.z), fb0 = __uint_as_float(b.q0.w), fa1 = __uint_as_float(b.q1.x), fb1 = __uint_as_float(b.q1.y);
             const float inv = __uint_as_float(b.q1.z);
             const float sgn = inv < 0.0f ? -1.0f : 1.0f;
             const float G0 = sgn * fa0, G1 = sgn * fa1, G2 = -(G0 + G1);           // steps per pixel of E0, E1, E2 (exact integers)
-            sH0 = sgn * fb0; sH1 = sgn * fb1;                                       // steps per row
-            const float H2 = -(sH0 + sH1);
-            const float ext = fmaxf(fmaxf(fmaxf(__builtin_fabsf(G0), __builtin_fabsf(G1)), fmaxf(__builtin_fabsf(sH0), __builtin_fabsf(sH1))),
+            const float H0 = sgn * fb0, H1 = sgn * fb1, H2 = -(H0 + H1);           // steps per row
+            const float ext = fmaxf(fmaxf(fmaxf(__builtin_fabsf(G0), __builtin_fabsf(G1)), fmaxf(__builtin_fabsf(H0), __builtin_fabsf(H1))),
                                     fmaxf(__builtin_fabsf(G2), __builtin_fabsf(H2)));
-            sA = __builtin_fabsf(fa0 * fb1 - fb0 * fa1);                            // |area| (render.rs:1500 in exact integers)
-            const bool fast = narrow && !(flags & (F_EMPTY | F_SLOW)) && ext <= SPAN_MAX_EXT && __builtin_fabsf(inv) >= SPAN_MIN_INV_AREA && sA >= 1.0f;
+            const float A = __builtin_fabsf(fa0 * fb1 - fb0 * fa1);                 // |area| (render.rs:1500 in exact integers)
+            const bool fast = narrow && !(flags & (F_EMPTY | F_SLOW)) && ext <= SPAN_MAX_EXT && __builtin_fabsf(inv) >= SPAN_MIN_INV_AREA && A >= 1.0f;
             span_all = !__ballot(live && !fast);
             const float dx = (float)cx0 - __uint_as_float(b.q0.x), dy = (float)cy0 - __uint_as_float(b.q0.y);
             sE0 = sgn * (fa0 * dx + fb0 * dy); sE1 = sgn * (fa1 * dx + fb1 * dy);   // at the first pixel of the clipped box
-#if B32_SPAN_PACK
             // (a surface that is not `fast` may hold steps beyond i16: its packed words are never used -- span_all is false then)
             sG01 = ((uint32_t)hw_cvt_i32(G0) & 0xFFFFu) | ((uint32_t)hw_cvt_i32(G1) << 16);
-            sH01 = ((uint32_t)hw_cvt_i32(sH0) & 0xFFFFu) | ((uint32_t)hw_cvt_i32(sH1) << 16);
-#else
-            sd0 = span_edge(G0); sd1 = span_edge(G1); sd2 = span_edge(G2);
-#endif
+            sH01 = ((uint32_t)hw_cvt_i32(H0) & 0xFFFFu) | ((uint32_t)hw_cvt_i32(H1) << 16);
         }
         const uint32_t h = (live && !slow) ? cy1 - cy0 : 0u;
         // exclusive prefix sum of the row counts
@@ -404,7 +346,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
         // their own, whose lanes are all busy.  The remainders refer to lanes of THIS batch (parameters come over ds_bpermute again), so
         // the queue is drained before the next batch is loaded.
         uint32_t lq = 0, lqn = 0;                       // leftover queue and its length (wave-uniform)
-        uint32_t lqi = 0, lqin = 0;                     // the same for certain-interior runs (interior_run): trips without the inside test
         // One trip of the sort-free EXACT coverage: four pixels -- the four texel addresses, their bits of the skip mask (LDS when the
         // pool's mask fits, else global: 1/16 of the texels' bytes; no texel is fetched during coverage) -- then the (non-returning)
         // atomics of the drawn fragments.  Returns the number of fragments drawn (the reference's pixel stores).
@@ -467,9 +408,8 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             uint32_t addr = ry * STR64 + rx;
             unsigned long long* top = reinterpret_cast<unsigned long long*>(tilebuf);
             unsigned long long* sec = top + TILE_H * STR64;
-#if B32_DRAIN_TRIPS > 0
-            // at most B32_DRAIN_TRIPS trips per entry and round; what is left of a long row goes back into the queue (a round used to last
-            // as long as its longest remainder: with the ~25-px rows of C5 most lanes idled behind the longest)
+            // at most B32_DRAIN_TRIPS trips per entry and round; what is left of a long row goes back into the queue (unbounded, a round
+            // lasts as long as its longest remainder: with the ~25-px rows of C5 most lanes idle behind the longest)
             constexpr uint32_t DT = (uint32_t)B32_DRAIN_TRIPS * (uint32_t)B32_TRIP;
             if (EXACT) {
                 Tri tr;
@@ -498,43 +438,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 if (lane < cnt) lq = got;
             }
             lqn = cnt;
-#else
-            for (uint32_t i = 0; __ballot(i < n); i += B32_TRIP)
-                cheap_trip<ZMODE>(top, sec, addr, w0, w1, sa0, sa1, sinv, i < n ? n - i : 0u, P, z1, z2, z3);
-            lqn = 0;
-#endif
-        };
-        // Rounds of the interior queue: an entry is (lane of the surface, tile row, first column, pixels), every pixel certain to pass the
-        // inside test -- the trip is the two atomics per pixel and nothing else (no edge values, no barycentrics).
-        auto drain_interior = [&]() {
-            const bool valid = lane < lqin;
-            const uint32_t s = valid ? (lqi & 63u) : lane;
-            const uint32_t ry = (lqi >> 6) & 63u, rx = (lqi >> 12) & 127u;
-            const uint32_t n = valid ? (lqi >> 19) : 0u;
-            const unsigned long long P = ((unsigned long long)bperm(s, my_key) << 32) | bperm(s, my_sid);
-            unsigned long long* top = reinterpret_cast<unsigned long long*>(tilebuf);
-            unsigned long long* sec = top + TILE_H * STR64;
-            const uint32_t addr = ry * STR64 + rx;
-            constexpr uint32_t DT = 2u * (uint32_t)B32_TRIP;
-#pragma unroll
-            for (uint32_t t0 = 0; t0 < DT; t0 += (uint32_t)B32_TRIP) {       // (one trip's returning atomics in flight at a time: registers)
-                if (!__ballot(n > t0)) break;
-                unsigned long long old[B32_TRIP];
-#pragma unroll
-                for (uint32_t j = 0; j < (uint32_t)B32_TRIP; ++j) old[j] = atomicMax(&top[addr + t0 + j], (t0 + j) < n ? P : 0ull);
-#pragma unroll
-                for (uint32_t j = 0; j < (uint32_t)B32_TRIP; ++j) atomicMax(&sec[addr + t0 + j], (t0 + j) < n ? min(old[j], P) : 0ull);
-            }
-            const bool more = n > DT;
-            const unsigned long long mm = __ballot(more);
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(mm);
-            if (cnt) {
-                const uint32_t entry = s | (ry << 6) | ((rx + DT) << 12) | ((n - DT) << 19);
-                const uint32_t dst = more ? (uint32_t)__builtin_popcountll(mm & ((1ull << lane) - 1ull)) : (cnt & 63u);
-                const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)(more ? entry : 0u));
-                if (lane < cnt) lqi = got;
-            }
-            lqin = cnt;
         };
         // span form of the remainder rounds: an entry is (lane of the surface, tile row, first column, pixels left of the row's interval)
         auto drain_span = [&]() {
@@ -546,7 +449,7 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             unsigned long long* top = reinterpret_cast<unsigned long long*>(tilebuf);
             unsigned long long* sec = top + TILE_H * STR64;
             const uint32_t addr = ry * STR64 + rx;
-            constexpr uint32_t DT = (uint32_t)(B32_DRAIN_TRIPS > 0 ? B32_DRAIN_TRIPS : 2) * (uint32_t)B32_TRIP;
+            constexpr uint32_t DT = (uint32_t)B32_DRAIN_TRIPS * (uint32_t)B32_TRIP;
 #pragma unroll
             for (uint32_t t0 = 0; t0 < DT; t0 += (uint32_t)B32_TRIP) {
                 if (t0 && !__ballot(n > t0)) break;
@@ -575,7 +478,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 const uint32_t k = k0 + lane;
                 const bool valid = k < R;
                 const uint32_t s = valid ? own - 1 : lane;
-#if B32_SPAN_PACK
                 // Seven permutes per round instead of fifteen (the LDS pipe is ONE per CU, shared by the sixteen waves of both workgroups,
                 // and the rounds are what it is busy with: tools/timeline.py): the steps travel as two words of i16 pairs, the reciprocal
                 // forms and |area| are recomputed by the row's lane -- the very expressions the surface's lane evaluated before, on the
@@ -591,16 +493,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 const float E0 = __builtin_fmaf(hH0, rowf, hE0), E1 = __builtin_fmaf(hH1, rowf, hE1);       // exact integers
                 const float E2 = hA - E0 - E1;
                 const uint32_t bx0 = sbp & 63u, bx1 = (sbp >> 6) & 127u, ry = ((sbp >> 13) & 63u) + (k - sP);   // tile-local
-#else
-                const uint32_t sbox = bperm(s, box), sP = bperm(s, P);
-                const float rowf = (float)(k - sP);
-                const float hE0 = bpermf(s, sE0), hE1 = bpermf(s, sE1), hH0 = bpermf(s, sH0), hH1 = bpermf(s, sH1), hA = bpermf(s, sA);
-                SpanEdge e0, e1, e2;
-                e0.r = bpermf(s, sd0.r); e0.c = bpermf(s, sd0.c); e1.r = bpermf(s, sd1.r); e1.c = bpermf(s, sd1.c); e2.r = bpermf(s, sd2.r); e2.c = bpermf(s, sd2.c);
-                const float E0 = __builtin_fmaf(hH0, rowf, hE0), E1 = __builtin_fmaf(hH1, rowf, hE1);       // exact integers
-                const float E2 = hA - E0 - E1;
-                const uint32_t bx0 = sbox & 0xFF, bx1 = (sbox >> 8) & 0xFF, ry = (sbox >> 16) + (k - sP);   // tile-local
-#endif
                 float lo, hi;
                 span_interval(E0, E1, E2, e0, e1, e2, (float)(bx1 - bx0), lo, hi);
                 const int len = valid ? hw_cvt_i32(hi - lo) : 0;
@@ -656,10 +548,8 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             uint32_t n = valid ? rx1 - rx0 : 0u;
             const float dx = (float)(rx0 + x_lo) - sx3, dy = (float)(ry + ty_top) - sy3;
             float w0 = sa0 * dx + sb0 * dy, w1 = sa1 * dx + sb1 * dy;                            // exact integers
-            if (B32_ROW_TRIM) {
-                const uint32_t lo = row_trim(w0, w1, sa0, sa1, sinv, n);
-                rx0 += lo; w0 += sa0 * (float)lo; w1 += sa1 * (float)lo;                         // exact: the closed form at the new start
-            }
+            const uint32_t lo = row_trim(w0, w1, sa0, sa1, sinv, n);
+            rx0 += lo; w0 += sa0 * (float)lo; w1 += sa1 * (float)lo;                             // exact: the closed form at the new start
             uint32_t addr = ry * (P64 ? STR64 : TILE_STRIDE) + rx0;
             const uint32_t li = cs + s + 1;
             uint32_t mine = 0;
@@ -668,7 +558,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 // winner is a drawn fragment, so no runner-up is kept)
                 const unsigned long long P = P64 ? (((unsigned long long)bperm(s, my_key) << 32) | bperm(s, my_sid)) : 0ull;
                 if (P64 && EXACT && TEXMODE == 0) {
-#if B32_DRAIN_TRIPS > 0
                     // one trip now; what is left of the row is queued like the CHEAP flavour's remainders (see `drain`)
                     mine += exact_trip(tr, addr, w0, w1, sa0, sa1, sinv, n, P);
                     const bool more = n > 4u;
@@ -682,9 +571,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                         if (lane >= lqn && lane < lqn + cnt) lq = got;
                         lqn += cnt;
                     }
-#else
-                    for (uint32_t i = 0; __ballot(i < n); i += 4) mine += exact_trip(tr, addr, w0, w1, sa0, sa1, sinv, i < n ? n - i : 0u, P);
-#endif
                 } else
                 for (uint32_t i = 0; __ballot(i < n); ++i) {
                     if (i < n) {
@@ -713,30 +599,8 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 unsigned long long* sec = top + TILE_H * STR64;
                 float z1 = 0.0f, z2 = 0.0f, z3 = 0.0f;
                 if (ZMODE) { z1 = bpermf(s, __uint_as_float(b.q5.y)); z2 = bpermf(s, __uint_as_float(b.q5.z)); z3 = bpermf(s, __uint_as_float(b.q5.w)); }
-                // Long rows (large triangles): the certain-interior run behind the first trip -- a multiple of TRIP pixels -- goes to the
-                // interior queue, what follows it to the ordinary one.  (Only when the run starts inside the first trip: the first trip then
-                // covers the row's left boundary, and one ordinary remainder covers the right one.)
-                uint32_t n_int = 0;
-                if (B32_INTERIOR && !ZMODE && __ballot(n >= INTERIOR_MIN_ROW)) {
-                    uint32_t tlo, thi;
-                    const float sgn = sinv < 0.0f ? -1.0f : 1.0f;
-                    const bool run = (n >= INTERIOR_MIN_ROW) && interior_run(w0, w1, sa0, sa1, __builtin_fabsf(sa0 * sb1 - sb0 * sa1), sgn, n, tlo, thi);
-                    if (run && tlo <= (uint32_t)B32_TRIP && thi >= 2u * (uint32_t)B32_TRIP) n_int = (thi - (uint32_t)B32_TRIP) & ~((uint32_t)B32_TRIP - 1u);
-                }
                 cheap_trip<ZMODE>(top, sec, addr, w0, w1, sa0, sa1, sinv, n, P, z1, z2, z3);          // (addr, w0, w1 now stand at pixel TRIP of the row)
-                if (B32_INTERIOR && !ZMODE) {
-                    const unsigned long long mi = __ballot(n_int != 0);
-                    if (mi) {
-                        const uint32_t cnt = (uint32_t)__builtin_popcountll(mi);
-                        while (lqin + cnt > 64u) drain_interior();
-                        const uint32_t entry = s | (ry << 6) | ((rx0 + (uint32_t)B32_TRIP) << 12) | (n_int << 19);
-                        const uint32_t dst = n_int ? lqin + (uint32_t)__builtin_popcountll(mi & ((1ull << lane) - 1ull)) : ((lqin + cnt) & 63u);
-                        const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)(n_int ? entry : 0u));
-                        if (lane >= lqin && lane < lqin + cnt) lqi = got;
-                        lqin += cnt;
-                    }
-                }
-                const uint32_t skip = (uint32_t)B32_TRIP + n_int;          // pixels of the row already dealt with or queued as interior
+                constexpr uint32_t skip = B32_TRIP;                         // pixels of the row the first trip dealt with
                 const bool more = n > skip;
                 const unsigned long long mm = __ballot(more);
                 if (mm) {
@@ -773,7 +637,6 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             }
         }
         if (P64) while (lqn) drain();                  // (the row remainders of this batch: its registers are about to be reloaded)
-        if (P64 && B32_INTERIOR && !ZMODE && !EXACT) while (lqin) drain_interior();
         // surfaces whose edge walk must be replayed literally: wave-cooperative slow path
         unsigned long long sm = __ballot(slow);
         while (sm) {

@@ -10,22 +10,10 @@
 #include "b32_cover.h"
 #include "b32_shade_tile.h"
 
-#ifndef B32_SHADE_PIPE
-#define B32_SHADE_PIPE 0          // experiment switch, OFF (round 6): software-pipelined straight-line shading (shade_tile_plain).  1 = the texel stage
-                                  // (this step's texels travel beside the previous step's colours and stores: 111 VGPRs, nothing spilled), 2 = the gather
-                                  // stage (the next step's record gathers beside this step's texels and colours: 27 VGPRs spilled under the 112 cap,
-                                  // 8 without it).  Same-box A/B: C3 0.1061-0.1076 (1) / 0.140-0.142 (2) / 0.114-0.115 (2, uncapped) against 0.1044-0.1067,
-                                  // k_cover 88.8-89.4 / 114-116 / 89.6-90.1 against 87.0-87.8 us -- a wave's own waits (tools/timeline.py: 1.3 us for the
-                                  // gather, 0.75 us for the texels of a 3-us step) are already filled by the CU's other fifteen waves
-                                  // (profiles/r06_shade_pipe_ab.txt)
-#endif
-
 namespace b32 {
 
-// per-wave repair queue of the fused kernel's shading phase (b32_shade_tile.h): 64 words; 192 in the experiment builds with the
-// software-pipelined shading step (it drains only where no record set is in flight and appends up to 128 entries in between), which
-// then leave ~2 KB instead of ~6 KB for a staged index atlas beside two workgroups' planes
-constexpr uint32_t RQ_WORDS = B32_SHADE_PIPE ? 192 : 64, RQ_BYTES = RQ_WORDS * 4;
+// per-wave repair queue of the fused kernel's shading phase (b32_shade_tile.h): 64 words
+constexpr uint32_t RQ_WORDS = 64, RQ_BYTES = RQ_WORDS * 4;
 static_assert(2 * (4 * LDS_TILE_BYTES + LDS_MISC_BYTES + 8 * RQ_BYTES + 511) / 512 * 512 <= 160 * 1024, "two 8-wave workgroups per CU");
 
 // ------------------------------------------------------------------------------------------------ k_cover
@@ -34,7 +22,7 @@ __device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t
                                                uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t tid, uint32_t lane, uint32_t TH, uint32_t* rq,
                                                const uint8_t* latlas);
 
-template <int NT, bool ZMODE, bool PIPE>
+template <int NT, bool ZMODE>
 __device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, uint32_t x_lo, uint32_t x_hi,
                                                  uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t tid, uint32_t lane, uint32_t TH, uint32_t* wq);
 
@@ -377,7 +365,7 @@ __device__ __forceinline__ void cover_body(const FillArgs& a_in) {
                 // from global memory -- painter's or z-buffer mode, with or without a shading pass; wave-uniform choice)
                 if (PLAIN != 2 && (PLAIN == 1 || PLAIN == 3 || (!FMT8 && fp.affine && fp.fixed_point && !fp.ortho && fp.nt == 1 && !latlas && a.tex0.width && a.tex0.height &&
                                                   (fp.shading == B32_SHADE_NONE || a.shades))))
-                    shade_tile_plain<NT, ZMODE, (B32_SHADE_PIPE != 0) && PLAIN == 1>(a, tilebuf, e0, e1, x_lo, x_hi, y_lo, y_hi, ty_top, tid, lane, TH, wmarks + wave * RQ_WORDS);
+                    shade_tile_plain<NT, ZMODE>(a, tilebuf, e0, e1, x_lo, x_hi, y_lo, y_hi, ty_top, tid, lane, TH, wmarks + wave * RQ_WORDS);
                 else if (PLAIN == 0 || PLAIN == 2) shade_tile_p64<FMT8, NT, ZMODE>(a, tilebuf, e0, e1, x_lo, x_hi, y_lo, y_hi, ty_top, tid, lane, TH, wmarks + wave * RQ_WORDS, latlas);
             }
             else if (a.clear_on) {      // nothing reaches this tile: it still gets the frame's clear colour
@@ -516,17 +504,6 @@ static void launch_p64(hipStream_t s, const FillArgs& a_in, uint32_t ntiles, int
     }
 #endif
     const bool plain = a.fp.affine && a.fp.shading == B32_SHADE_NONE && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;
-#ifdef B32_EXP_LDS_ATLAS
-    // experiment build (tools/exp_variants.py build atlas -DB32_EXP_LDS_ATLAS): the benchmark's frame through ONE 16-wave workgroup per CU
-    // with the 64 KB index atlas + CLUT in LDS, against two 8-wave workgroups per CU fetching expanded texels through L1 / L2
-    if (plain && !wide && a.atlas_idx_bytes) {
-        static bool attr_x[64] = {};
-        if (first_launch_on_device(attr_x))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<0, EXACT, 1024, ZMODE, FMT8, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL((k_cover<0, EXACT, 1024, ZMODE, FMT8, true, 2>), dim3(min(ntiles, (uint32_t)n_cu)), dim3(1024), lds_w, s, a);
-        return;
-    }
-#endif
     // (the straight-line shading's frames: see cover_body)
     const bool straight = !FMT8 && !a.atlas_idx_bytes && a.tex0.width && a.tex0.height;
     const bool lit_plain = a.fp.affine && a.fp.shading != B32_SHADE_NONE && a.shades && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;

@@ -13,6 +13,7 @@
 #ifndef B32_DRAIN_TRIPS
 #define B32_DRAIN_TRIPS 2
 #endif
+static_assert(B32_DRAIN_TRIPS > 0, "row remainders are queued and worked off at most B32_DRAIN_TRIPS trips per round");
 #ifndef B32_P64_WAVES
 #define B32_P64_WAVES 4          // minimum waves per SIMD the general 8-wave forms of the fused kernel are compiled for
 #endif

@@ -11,31 +11,6 @@
 // anything enqueued on the main stream that k_setup reads (uploads, packed streams, light lists, list-space memsets) -> the next
 // setup (ev_main, only when `side_dirty`).  The main stream always waits for the frame's setup before enqueue_frame returns, so a
 // synchronisation of the main stream still covers everything this context has in flight.
-#ifndef B32_JOIN_NOT_BATCHED
-#define B32_JOIN_NOT_BATCHED 1     // (the merged runs of a batched frame keep the event: their kernels are so short that the two extra launches cost what the
-                                   // barrier packet did -- console frame 0.268-0.275 against 0.264-0.265 ms)
-#endif
-#ifndef B32_JOIN_KERNEL
-#define B32_JOIN_KERNEL 1            // (0: the fill waits for its setup kernel through a cross-stream event, as before)
-#endif
-#ifndef B32_POLL_BATCHED
-#define B32_POLL_BATCHED 1            // (0: the merged draws of a batched frame wait for their setup kernels through a cross-stream event, as before)
-#endif
-#ifndef B32_START_AT_BLEND
-#define B32_START_AT_BLEND 1         // (0: the fused kernel always publishes the frame's "started" word itself)
-#endif
-#ifndef B32_START_GATE
-#define B32_START_GATE 1             // (0: a cross-stream event behind every fill orders it before the setup kernel that next writes its frame set, as before)
-#endif
-#ifndef B32_PIPE_FEW_TILES
-#define B32_PIPE_FEW_TILES 1          // (0: frames whose fused kernel has no more tiles than workgroup slots are not pipelined, as before round 6)
-#endif
-#ifndef B32_WIRE_BIN_EARLY
-#define B32_WIRE_BIN_EARLY 1          // (0: k_wire_bin behind the fill on the main stream, as before)
-#endif
-#ifndef B32_EXP_NO_WIRE_PIPE
-#define B32_EXP_NO_WIRE_PIPE 0          // (1: frames with wireframe phases are not pipelined, as before round 5 -- their wire list was not part of the frame set)
-#endif
 static void swap_with(b32_ctx* c, FrameSet& a) {
     std::swap(c->keys[0], a.keys0); std::swap(c->crecs, a.crecs); std::swap(c->srecs, a.srecs); std::swap(c->xrecs, a.xrecs);
     std::swap(c->spans, a.spans); std::swap(c->face_of, a.face_of); std::swap(c->partials, a.partials);
@@ -45,7 +20,7 @@ static void swap_with(b32_ctx* c, FrameSet& a) {
     std::swap(c->wire, a.wire); std::swap(c->cap_wire, a.cap_wire);
     std::swap(c->wire_fill, a.wire_fill); std::swap(c->wire_lists, a.wire_lists); std::swap(c->cap_wire_tiles, a.cap_wire_tiles); std::swap(c->wire_grid, a.wire_grid);
     std::swap(c->d_ctrl, a.d_ctrl);
-    std::swap(c->ev_setup, a.ev_setup); std::swap(c->ev_done, a.ev_done); std::swap(c->set_in_flight, a.in_flight);
+    std::swap(c->ev_setup, a.ev_setup); std::swap(c->set_in_flight, a.in_flight);
 }
 // The frame being enqueued takes the OLDEST set; afterwards alt[n_sets - 2] is the previous frame's set and alt[0] the set of the frame
 // n_sets - 1 back -- the one whose fill the new frame's setup kernel is meant to run beside (its tile cursor is what the gate polls).
@@ -74,14 +49,9 @@ static int pipeline_ensure(b32_ctx* c) {
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_wbin, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_setup, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-        for (FrameSet& a : c->alt) {
-            HIPCHK(c, hipEventCreateWithFlags(&a.ev_setup, hipEventDisableTiming));
-            HIPCHK(c, hipEventCreateWithFlags(&a.ev_done, hipEventDisableTiming));
-        }
-        // the frames enqueued on the current set before the side stream existed recorded nothing: their fills end before this point of
-        // the main stream, which the first setup kernel on the side stream waits for (side_dirty) and the set's own event now marks too
-        HIPCHK(c, hipEventRecord(c->ev_done, c->stream));
+        for (FrameSet& a : c->alt) HIPCHK(c, hipEventCreateWithFlags(&a.ev_setup, hipEventDisableTiming));
+        // the fills of the frames enqueued before the side stream existed end before this point of the main stream, which the first setup
+        // kernel on the side stream waits for (side_dirty)
         c->side_dirty = true;
     }
     for (uint32_t k = 0; k + 1 < c->n_sets; ++k) {
@@ -278,9 +248,6 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
         // of 32 rows to 600 of 16; C2's 20 tiles prefer 150 of 8 rows -- 0.039 ms against 0.051 with 75 of 16 rows, 0.049 with 300 of 4)
         while (th > (uint32_t)B32_MIN_TILE_H && fp.tiles_x * ((c->band_y1 + th - 1) / th - c->band_y0 / th) < (th == TILE_H ? 2u : 1u) * (uint32_t)c->n_cu &&
                (c->band_y1 - c->band_y0) / (th / 2) + 2 <= 255 /* tile rows must fit the packed spans */) th /= 2;
-#ifdef B32_EXP_FORCE_TH
-        th = B32_EXP_FORCE_TH;
-#endif
         fp.tile_h = th;
         fp.tile_yb = (c->band_y0 / th) * th;
         fp.tiles_y = (c->band_y1 - fp.tile_yb + th - 1) / th;
@@ -431,10 +398,7 @@ static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const Route& 
     // workgroup form launch_fill is going to choose (16 waves, one workgroup per CU: ~84 KB; two 8-wave workgroups per CU: ~6 KB)
     fa.atlas0 = c->d_atlas0; fa.atlas_idx_bytes = 0;
     if (r.prio64 && !c->fmt8 && c->nt == 1 && c->atlas_idx_bytes && !(c->route_off & B32_ROUTE_LDS_ATLAS)) {
-        bool wide = fp.tiles_x * fp.tiles_y <= (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
-#ifdef B32_EXP_LDS_ATLAS
-        wide = true;                     // (experiment build: launch_p64 sends the plain frame through the 16-wave form)
-#endif
+        const bool wide = fp.tiles_x * fp.tiles_y <= (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
         if (c->atlas_idx_bytes + ATLAS_CLUT_BYTES + 16u <= fill_lds_atlas_room(wide)) fa.atlas_idx_bytes = c->atlas_idx_bytes;
     }
     if (c->fmt8) fa.fp.xray = 0;                        // render_mesh: x-ray only changes culling; its stores keep their own depth tests
@@ -455,15 +419,11 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     c->pipelined = false;
     // (pipe_hint: whether the previous frame's route qualified -- a frame that will not, e.g. every frame of a PS1-sized target, skips
     // the set swap and its event as well: 0.030 -> 0.028 ms on 20 k triangles at 320x240)
-#ifdef B32_EXP_PIPE_SMALL
-    const uint32_t pipe_min_faces = 0u;              // (experiment build: small frames pipelined too)
-#else
     const uint32_t pipe_min_faces = 2048u;
-#endif
     // (not on the legacy default stream -- hipStreamLegacy, what torch's default stream maps to: it synchronises implicitly with every
     // blocking stream, and recording / waiting cross-stream events on that handle crashed the runtime, found when safe mode began to
     // leave superseded frames in flight)
-    if (c->frame_pending && c->pipe_hint && !c->redrawing && !(fp.wire_collect && B32_EXP_NO_WIRE_PIPE) && !prof_all && c->nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
+    if (c->frame_pending && c->pipe_hint && !c->redrawing && !prof_all && c->nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
         c->stream != hipStreamLegacy) {
         if ((rc = pipeline_ensure(c))) return rc;
         rotate_sets(c);
@@ -505,11 +465,8 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // stream have different priorities (unknown before the first pipelined frame of a stream: tried once, then decided).
     // The same for the frames of a screen band (one rank of a sharded frame: 240 rows of C4 are 320 tiles of 32 rows) -- round 5 had measured
     // them with the event (N = 8 band 0.067 -> 0.071: no); with the kernel pair the weak series' N = 8 point goes 0.054 -> 0.042 ms per rank.
-    const bool join_small = B32_JOIN_KERNEL && B32_PIPE_FEW_TILES && !c->frame_batched && (c->join_stream != s || c->join_ok);
-    c->pipe_hint = r.direct_bin && (ntiles > 2u * (uint32_t)c->n_cu || c->frame_batched || (c->band_set && B32_PIPELINE_BANDS) || join_small);
-#ifdef B32_EXP_PIPE_SMALL
-    c->pipe_hint = (r.direct_bin || r.want_inline) && !c->band_set;
-#endif
+    const bool join_small = !c->frame_batched && (c->join_stream != s || c->join_ok);
+    c->pipe_hint = r.direct_bin && (ntiles > 2u * (uint32_t)c->n_cu || c->frame_batched || join_small);
     if (!c->pipe_hint) c->pipelined = false;       // (the frame keeps the set it rotated to -- the route's regions are that set's -- but runs on the main stream)
     c->last_local_sort = r.local_sort || r.want_prio64;                         // the global draw order is not materialised
     c->last_exact = r.ordered_all ? true : (r.exact_cov && !fp.zmode);          // the ordered walk counts every store it performs
@@ -532,13 +489,9 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         for (const auto& co : c->cover_of) if (co.ctrl && co.ctrl == c->alt[0].d_ctrl) { polled_tiles = co.tiles; polled_groups = co.groups; polled_seq = co.seq; }
         // The set this frame's setup kernel writes was last read by the fill n_sets frames back.  That fill lies in front of alt[0]'s on the main
         // stream: when alt[0]'s frame launched a fused kernel, "it has started" orders the two on the device (k_gate, no event on the main
-        // stream: B32_START_GATE); else the side stream waits for the main stream as it stands now.
-        const bool start_gate = B32_START_GATE && polled_tiles && polled_seq && c->alt[0].d_ctrl;
-#if B32_START_GATE
+        // stream); else the side stream waits for the main stream as it stands now.
+        const bool start_gate = polled_tiles && polled_seq && c->alt[0].d_ctrl;
         if (!start_gate) { HIPCHK(c, hipEventRecord(c->ev_main, s)); HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0)); }
-#else
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_done, 0));     // the last fill that read this set (n_sets frames ago)
-#endif
         uint32_t gate_need = 0;
         if (c->gate_permille && polled_tiles && c->alt[0].d_ctrl) {
             // The fused kernel's workgroups take their next tile from the cursor after the coverage of the current one: the cursor
@@ -580,7 +533,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // k + 1 has normally finished beside draw k's fill and blend pass, and what the cross-stream event cost the main stream per draw (6.5 us
     // between k_blend's end and the next fill's start: tools/console_trace.sh) was most of what there was to save in a console frame.
     uint32_t poll_seq = 0, poll_patience = 0;
-    const bool poll_batched = B32_POLL_BATCHED && c->pipelined && c->frame_batched && c->join_ok && (r.direct_bin || r.want_inline) && !wire_front && !r.ordered_all &&
+    const bool poll_batched = c->pipelined && c->frame_batched && c->join_ok && (r.direct_bin || r.want_inline) && !wire_front && !r.ordered_all &&
                               ntiles && 8u * ntiles <= 5u * (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
     if (poll_batched) {
         // (b32_debug_inject(ctx, 1) as below: the flag carries another value, the patience is 2 ms)
@@ -590,8 +543,9 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         launch_flag_poll(c->side, c->d_ctrl, lose_flag ? c->join_seq ^ 0x40000000u : c->join_seq);
         poll_seq = c->join_seq; poll_patience = lose_flag ? 200000u : 200000000u;
         c->flag_join_frames++; c->poll_join_frames++;
-    } else if (c->pipelined && B32_JOIN_KERNEL && r.direct_bin && c->join_ok && !(c->frame_batched && B32_JOIN_NOT_BATCHED)) {
-        // (no cross-stream event on the fill's path: see k_flag / k_join)
+    } else if (c->pipelined && r.direct_bin && c->join_ok && !c->frame_batched) {
+        // (no cross-stream event on the fill's path: see k_flag / k_join.  The merged runs of a batched frame keep the event: their kernels
+        // are so short that the two extra launches cost what the barrier packet did -- console frame 0.268-0.275 against 0.264-0.265 ms)
         // (b32_debug_inject(ctx, 1): this frame's flag carries another epoch and the join's patience is 2 ms -- the "setup kernel never arrived" path)
         const bool lose_flag = (c->inject & 1u) != 0;
         c->inject &= ~1u;
@@ -604,15 +558,13 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         if (e1 != hipSuccess) { (void)hipStreamSynchronize(c->side); c->last_hip = (int)e1; return B32_E_HIP; }
         c->event_join_frames++;
     }
-    if (c->pipelined) {
-        if (wire_on && wa.tile_fill && B32_WIRE_BIN_EARLY) {       // (behind ev_setup: the fill does not wait for the binning)
-            launch_wire_bin(c->side, wa, wire_back, wire_front, true);
-            // (back-face edges: the first wire kernel on the main stream, k_wire_table_clear, looks at Events::wbin_done itself -- no event
-            // for the main stream to wait for; the overlay alone has no such kernel in front of k_wire_tile and keeps the event)
-            if (wire_back) { launch_flag_wbin(c->side, c->d_ctrl, wa.epoch); wire_polled = true; }
-            else HIPCHK(c, hipEventRecord(c->ev_wbin, c->side));
-            wire_binned = true;
-        }
+    if (c->pipelined && wire_on && wa.tile_fill) {       // (behind ev_setup: the fill does not wait for the binning)
+        launch_wire_bin(c->side, wa, wire_back, wire_front, true);
+        // (back-face edges: the first wire kernel on the main stream, k_wire_table_clear, looks at Events::wbin_done itself -- no event
+        // for the main stream to wait for; the overlay alone has no such kernel in front of k_wire_tile and keeps the event)
+        if (wire_back) { launch_flag_wbin(c->side, c->d_ctrl, wa.epoch); wire_polled = true; }
+        else HIPCHK(c, hipEventRecord(c->ev_wbin, c->side));
+        wire_binned = true;
     }
     c->set_in_flight = true;
     if (prof_all) HIPCHK(c, hipEventRecord(ev[1], s));
@@ -658,7 +610,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // default() in that role: 0.284 -> 0.331 -- its setup kernel is the long one and then starts too late; not done.
     // Only frames that fill the GPU (more tiles than workgroup slots): a console-sized draw leaves most CUs idle anyway and its setup kernel is
     // a chain of round trips that wants to start as early as it may (12-room console frame with the deferral: 0.171 -> 0.213 ms).
-    fa.start_defer = (B32_START_AT_BLEND && fa.prio64 && !wire_front && !r.ordered_all && ntiles > 2u * (uint32_t)c->n_cu && fa.gather_blend) ? 1u : 0u;
+    fa.start_defer = (fa.prio64 && !wire_front && !r.ordered_all && ntiles > 2u * (uint32_t)c->n_cu && fa.gather_blend) ? 1u : 0u;
     // a deferred Framebuffer::clear: folded into this frame's fused kernel when that kernel is the one that runs, the frame has no
     // depth buffer to reset and the clear was issued for this very band; else the clear launches go first
     if (c->clear_pending) {
@@ -679,9 +631,6 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         launch_wire(s, wa, wire_back, wire_front, wire_binned, wire_polled ? c->d_ctrl : nullptr, wa.epoch);
     }
     if (prof_fill) { if (prof_all) HIPCHK(c, hipEventRecord(ev[5], s)); c->ev_frames++; }
-#if !B32_START_GATE
-    if (c->side) HIPCHK(c, hipEventRecord(c->ev_done, s));         // (the next setup kernel that writes this set waits for it)
-#endif
     c->last_cover_tiles = (r.prio64 && !wire_front && !r.ordered_all) ? ntiles : 0u;
     c->last_cover_groups = std::min<uint32_t>(ntiles, (uint32_t)c->n_cu * 2u);
     {   // remembered per frame set

@@ -13,9 +13,6 @@
 #include <vector>
 
 using namespace b32;
-#ifndef B32_PIPELINE_BANDS
-#define B32_PIPELINE_BANDS 0      // experiment switch: two frames in flight for band-sharded frames too (measured: N=8 band 0.067 -> 0.071 ms: no)
-#endif
 #ifndef B32_MIN_TILE_H
 #define B32_MIN_TILE_H 8
 #endif
@@ -37,7 +34,7 @@ struct FrameSet {
     WireTri* wire = nullptr; size_t cap_wire = 0;           // (frames with wireframe phases: k_setup writes the wire list, the wire kernels behind the fill read it)
     uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0; unsigned long long wire_grid = 0;   // (... and its tile lists: binned beside the previous frame's fill)
     Ctrl* d_ctrl = nullptr;
-    hipEvent_t ev_setup = nullptr, ev_done = nullptr;      // k_setup finished (side stream) / last fill reading this set finished (main stream)
+    hipEvent_t ev_setup = nullptr;                         // k_setup finished (side stream)
     bool in_flight = false;                                  // a frame was enqueued on this set since the last b32_frame_finish
 };
 
@@ -53,7 +50,7 @@ struct b32_ctx {
     uint32_t n_sets = 2;                 // b32_set_pipeline_depth: 2 = setup(i+1) beside fill(i); 3 = setup(i+2) beside fill(i), so that the
                                          // setup kernel a fill waits for ended a whole fill ago (fills back to back; measured slower: the two
                                          // kernels then share the CUs all the time and the frame is bound by their summed VALU work)
-    hipEvent_t ev_setup = nullptr, ev_done = nullptr; bool set_in_flight = false;     // (members of the current set, see FrameSet)
+    hipEvent_t ev_setup = nullptr; bool set_in_flight = false;     // (members of the current set, see FrameSet)
     bool side_dirty = true;              // something k_setup reads was written on `stream` since the side stream last waited for it
     hipStream_t join_stream = nullptr; bool join_ok = false;   // k_flag / k_join instead of an event: only while `stream` and `side` have DIFFERENT priorities (then they never share a hardware queue); checked per main stream
     uint32_t gate_permille = 0;          // b32_set_pipeline_gate: hold the next setup kernel until the previous fill's tile cursor has got this far (0: only until that fill has started -- the frame sets' order, k_gate)

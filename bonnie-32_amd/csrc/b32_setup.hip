@@ -207,13 +207,7 @@ __device__ __forceinline__ void agg_issue(uint32_t* fill, uint32_t slot, bool ac
         if (n < 2) { if (++misses >= 2) break; continue; }
         if (active && slot == s) { g.leader = (uint32_t)l; g.rank = (uint32_t)__builtin_popcountll(grp & below); if (lane == (uint32_t)l) cnt = n; }
     }
-#if defined(B32_EXP_BIN_WG_ATOMICS)          // experiment (frames are WRONG): the reservation as an L2-local atomic -- what per-XCD counters would cost
-    if (active && g.leader == lane) g.ret = __hip_atomic_fetch_add(fill + slot, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#elif defined(B32_EXP_BIN_NO_ATOMICS)        // experiment (frames are WRONG): no reservation at all
-    if (active && g.leader == lane) g.ret = (slot * 2654435761u) >> 26;
-#else
     if (active && g.leader == lane) g.ret = atomicAdd(fill + slot, cnt);
-#endif
 }
 // (every lane that was `active` in agg_issue must call this together)
 __device__ __forceinline__ uint32_t agg_position(const AggSlot& g) {
@@ -528,12 +522,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 
                         if (k) agg_issue(db.fill, tile * FILL_PAD + (db_cls ? 1u : 0u), act, threadIdx.x & 63u, g);
                         const uint32_t pos = agg_position(g);
                         if (act) {
-#ifdef B32_EXP_BIN_NO_LIST_STORE                                   // experiment (frames are WRONG): reservations without the 4-byte list stores
-                            if (pos >= cap) over = true;
-#else
                             if (pos < cap) db.lists[(size_t)tile * db.region + (db_cls ? db.region - 1u - pos : pos)] = rslot;
                             else over = true;
-#endif
                             if (++tx > tx1) { tx = tx0; ++ty; }
                         }
                     }

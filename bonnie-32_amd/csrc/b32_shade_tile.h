@@ -160,11 +160,7 @@ __device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t
 // and stores nothing of it).  The winner of a covered pixel passed the inside test during coverage (same arithmetic, or the span form
 // proven equal to it), so it is not evaluated again.  A step in which some winner must replay the edge walk literally (SH_SLOW) takes
 // the general per-pixel functions; skipped winners go to the wave's repair queue as in the general form.
-// PIPE (the forms with registers to spare: painter's and z-buffer mode without a shading pass): the step is software-pipelined -- the winners
-// and the two 64-byte record gathers of step k + 1 are issued as soon as step k's records have been turned into barycentrics and texel
-// addresses, BEFORE step k's texel fetch is waited for, so that the gather's round trip (1.3 us of a 3-us step: tools/timeline.py) runs
-// beside the texel fetch, the colour pipeline and the stores instead of in front of them.  Same loads, same arithmetic, another order.
-template <int NT, bool ZMODE, bool PIPE>
+template <int NT, bool ZMODE>
 __device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, uint32_t x_lo, uint32_t x_hi,
                                                  uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t tid_in, uint32_t lane_in, uint32_t TH, uint32_t* wq) {
     // (the lane's constants of this phase -- column, x, masks -- are derived again per tile from an opaque copy of its index: hoisted out of the
@@ -331,92 +327,17 @@ __device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32
         if (inB) leave(pyB);
     };
 
-    if (PIPE) {
-        // Iteration k: [flush point] -> gathers of step k issued -> texel rule, colours and stores of step k - 1 (its texels were requested at
-        // the end of the previous iteration) -> barycentrics and texel fetches of step k.  What crosses the loop's back edge is `Mid` (fourteen
-        // registers and the step's flags), never a record set.
-        // The repair queue holds up to RQ_WORDS = 192 entries here and is drained only at the top of an iteration, where nothing is in flight
-        // but the two texel fetches: a drain is the general per-pixel code -- about a hundred registers -- and a record set live across it
-        // would be spilled on every step, not only on the rare ones that drain.  A step appends at most 128 entries.
-        const uint32_t n_steps = (TH + STEP_ROWS - 1) / STEP_ROWS;
-        Mid m;
-        m.bA0 = m.bA1 = m.bA2 = m.bB0 = m.bB1 = m.bB2 = 0.0f;
-        m.pkA0 = m.pkA1 = m.pkA2 = m.pkB0 = m.pkB1 = m.pkB2 = 0u; m.fetA = m.fetB = 0u;
-        unsigned long long ptA = 0, ptB = 0;
-        bool pcA = false, pcB = false, pinA = false, pinB = false;
-        for (uint32_t k = 0;; ++k) {
-            const bool flush = k > n_steps;
-            while (lqn > (flush ? 0u : 64u)) {             // ONE drain site: the queue's last (up to) 64 entries, one per lane
-                const uint32_t base = lqn > 64u ? lqn - 64u : 0u;
-                uint32_t* q = wq;
-                lqn -= base; wq = q + base;
-                drain();                                    // (reads wq[lane] for lane < lqn, leaves lqn = 0)
-                wq = q; lqn = base;
-            }
-            if (flush) break;
-#if B32_SHADE_PIPE == 2
-            In cur;
-            if (k < n_steps) issue(k * STEP_ROWS, cur);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k >= 1) {
-                const uint32_t r0 = (k - 1) * STEP_ROWS;
-                unsigned long long mA = 0, mB = 0;
-                uint32_t shA = 0, shB = 0;
-                part2(r0, ptA, ptB, pcA, pcB, pinA, pinB, m, mA, mB, shA, shB);
-                if (mA | mB) {                              // append (never drains: see above)
-                    const uint32_t rowA = r0 + (tid >> 6), rowB = rowA + ROWS_PER_STEP;
-                    if ((mA >> lane) & 1ull) wq[lqn + (uint32_t)__builtin_popcountll(mA & below)] = (rowA << 6) | col | ((shA & SH_SLOW) ? 0x1000u : 0u);
-                    lqn += (uint32_t)__builtin_popcountll(mA);
-                    if ((mB >> lane) & 1ull) wq[lqn + (uint32_t)__builtin_popcountll(mB & below)] = (rowB << 6) | col | ((shB & SH_SLOW) ? 0x1000u : 0u);
-                    lqn += (uint32_t)__builtin_popcountll(mB);
-                }
-            }
-            if (k < n_steps) {
-                part1(k * STEP_ROWS, cur, m);
-                ptA = cur.tA; ptB = cur.tB; pcA = cur.cA; pcB = cur.cB; pinA = cur.inA; pinB = cur.inB;
-            }
-        }
-#else
-            // texel stage only: the step's own gather is waited for, its texels are requested, and while they travel the PREVIOUS step's texel
-            // rule, colours and stores run
-            Mid mc = m;
-            unsigned long long ctA = 0, ctB = 0; bool ccA = false, ccB = false, cinA = false, cinB = false;
-            if (k < n_steps) {
-                In cur;
-                issue(k * STEP_ROWS, cur);
-                part1(k * STEP_ROWS, cur, mc);
-                ctA = cur.tA; ctB = cur.tB; ccA = cur.cA; ccB = cur.cB; cinA = cur.inA; cinB = cur.inB;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (k >= 1) {
-                const uint32_t r0 = (k - 1) * STEP_ROWS;
-                unsigned long long mA = 0, mB = 0;
-                uint32_t shA = 0, shB = 0;
-                part2(r0, ptA, ptB, pcA, pcB, pinA, pinB, m, mA, mB, shA, shB);
-                if (mA | mB) {                              // append (never drains: see above)
-                    const uint32_t rowA = r0 + (tid >> 6), rowB = rowA + ROWS_PER_STEP;
-                    if ((mA >> lane) & 1ull) wq[lqn + (uint32_t)__builtin_popcountll(mA & below)] = (rowA << 6) | col | ((shA & SH_SLOW) ? 0x1000u : 0u);
-                    lqn += (uint32_t)__builtin_popcountll(mA);
-                    if ((mB >> lane) & 1ull) wq[lqn + (uint32_t)__builtin_popcountll(mB & below)] = (rowB << 6) | col | ((shB & SH_SLOW) ? 0x1000u : 0u);
-                    lqn += (uint32_t)__builtin_popcountll(mB);
-                }
-            }
-            m = mc; ptA = ctA; ptB = ctB; pcA = ccA; pcB = ccB; pinA = cinA; pinB = cinB;
-        }
-#endif
-    } else {
-        for (uint32_t r0 = 0; r0 < TH; r0 += STEP_ROWS) {
-            In cur;
-            issue(r0, cur);
-            unsigned long long mA = 0, mB = 0;
-            uint32_t shA = 0, shB = 0;
-            if (cur.any) {
-                Mid m;
-                part1(r0, cur, m);
-                part2(r0, cur.tA, cur.tB, cur.cA, cur.cB, cur.inA, cur.inB, m, mA, mB, shA, shB);
-            } else nothing_here(r0, cur.inA, cur.inB);
-            enqueue(r0, mA, mB, shA, shB);
-        }
+    for (uint32_t r0 = 0; r0 < TH; r0 += STEP_ROWS) {
+        In cur;
+        issue(r0, cur);
+        unsigned long long mA = 0, mB = 0;
+        uint32_t shA = 0, shB = 0;
+        if (cur.any) {
+            Mid m;
+            part1(r0, cur, m);
+            part2(r0, cur.tA, cur.tB, cur.cA, cur.cB, cur.inA, cur.inB, m, mA, mB, shA, shB);
+        } else nothing_here(r0, cur.inA, cur.inB);
+        enqueue(r0, mA, mB, shA, shB);
     }
 }
 

@@ -379,9 +379,6 @@ __global__ __launch_bounds__(WIRE_THREADS) __attribute__((amdgpu_waves_per_eu(7,
         }
     }
     __syncthreads();
-#if defined(B32_EXP_WIRE_STAGE) && B32_EXP_WIRE_STAGE <= 1
-    return;
-#endif
     if (kind == 1) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -399,9 +396,6 @@ __global__ __launch_bounds__(WIRE_THREADS) __attribute__((amdgpu_waves_per_eu(7,
         }
     }
     __syncthreads();
-#if defined(B32_EXP_WIRE_STAGE) && B32_EXP_WIRE_STAGE <= 2
-    return;
-#endif
     // which of my edges are drawn, over how many steps: segment counts
     // the tile's rectangle inside the frame and the band (non-empty: a tile of the grid; all four below 16384)
     const int cx0 = (int)x_lo, cx1 = (int)min(x_lo + 63u, a.width - 1u);
@@ -449,9 +443,6 @@ __global__ __launch_bounds__(WIRE_THREADS) __attribute__((amdgpu_waves_per_eu(7,
             if (pos >= pass0 && pos < pass0 + WIRE_SEG_CAP) segs[pos - pass0] = (uint16_t)(i | (q << 10) | flags);     // (i < 768 < 2^10, q < 16)
     }
     __syncthreads();
-#if defined(B32_EXP_WIRE_STAGE) && B32_EXP_WIRE_STAGE <= 3
-    return;
-#endif
     const uint32_t in_pass = min(total - pass0, WIRE_SEG_CAP);
     for (uint32_t t = tid; t < in_pass; t += WIRE_THREADS) {
         const uint32_t sg = segs[t], q = (sg >> 10) & 15u, which = sg >> 15;
@@ -559,10 +550,7 @@ void launch_wire(hipStream_t s, const WireArgs& a, bool back, bool front, bool b
         hipLaunchKernelGGL(k_wire_insert, dim3(gblocks), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_wire_draw<1>, dim3(gblocks), dim3(256), 0, s, a);
     }
-#ifndef B32_EXP_WIRE_PAD_LDS                               // experiment: dynamic LDS nobody uses = fewer workgroups per CU
-#define B32_EXP_WIRE_PAD_LDS 0
-#endif
-    if (tiles) hipLaunchKernelGGL(k_wire_tile, dim3(ntiles), dim3(WIRE_THREADS), B32_EXP_WIRE_PAD_LDS, s, a);
+    if (tiles) hipLaunchKernelGGL(k_wire_tile, dim3(ntiles), dim3(WIRE_THREADS), 0, s, a);
     if (front) hipLaunchKernelGGL(k_wire_draw<2>, dim3(gblocks), dim3(256), 0, s, a);
 }
 
