@@ -39,6 +39,12 @@ class B32Texture(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("blend_mode", C.c_uint32), ("_pad", C.c_uint32), ("pixels", C.c_void_p)]
 
 
+# B32Line (Framebuffer line family, b32_draw_lines): kinds B32_LINE_*
+LINE_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("z0", "<f4"), ("z1", "<f4"),
+                       ("r", "u1"), ("g", "u1"), ("b", "u1"), ("blend", "u1"), ("kind", "u1"), ("alpha", "u1"), ("_pad", "u1", 2)])
+assert LINE_DTYPE.itemsize == 32
+LINE_2D, LINE_2D_ALPHA, LINE_3D, LINE_3D_OVERLAY, LINE_3D_ALPHA = range(5)
+
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -130,6 +136,7 @@ SYMBOLS = [
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     ("b32_draw_star_diamonds", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_float]),
     ("b32_present_nearest", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_draw_lines", C.c_int, [_P, _P, C.c_uint32]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

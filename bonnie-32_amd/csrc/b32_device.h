@@ -464,6 +464,21 @@ __device__ __forceinline__ float wire_t_fast(float kf, float Nf, float rN) {
 }
 void launch_wire(hipStream_t s, const WireArgs& a, bool back, bool front, bool binned = false, Ctrl* wait_ctrl = nullptr, uint32_t wait_epoch = 0);   // wait_ctrl: see k_wire_table_clear
 void launch_wire_bin(hipStream_t s, const WireArgs& a, bool back, bool front, bool early);
+// Framebuffer line pass (b32_draw_lines, b32_lines.hip): 64 x LINE_TH tiles over the band, first tile row at band_y0.
+constexpr uint32_t LINE_TH = 16;
+constexpr uint32_t LINE_SMALL = 64;            // batches of at most this many lines travel in the kernel argument (LineBatch): no copy
+constexpr uint32_t LINE_TILE_CAP = 1024;       // entries per tile list of the tile route
+constexpr uint32_t LINE_LONG_CAP = 1024;       // lines whose box covers more than LINE_BIG_TILES tiles share one list
+struct LineArgs {
+    const B32Line* lines; uint32_t n;          // lines == nullptr: the batch is the kernel argument
+    uint32_t* fb; const float* zbuf;           // zbuf == nullptr: every depth is f32::MAX
+    uint32_t width, band_y0, band_y1, tiles_x, tiles_y;
+    // tile route (nullptr: every tile scans the whole batch in order): FILL_PAD words per counter -- the two long-list counters (one per
+    // parity: a batch's tile kernel zeroes the other one for the next binned batch), then one per tile --, lists of LINE_TILE_CAP ids per tile
+    uint32_t* counters; uint32_t* lists; uint32_t* long_list; uint32_t parity;
+};
+struct LineBatch { B32Line l[LINE_SMALL]; };
+void launch_lines(hipStream_t s, const LineArgs& a, const B32Line* small);   // small != nullptr: n <= LINE_SMALL lines passed by value
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

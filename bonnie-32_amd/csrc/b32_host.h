@@ -153,6 +153,12 @@ struct b32_ctx {
     uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0;     // tile route of the wireframe phases (WireArgs)
     unsigned long long wire_grid = 0;                                                       // tile grid the (self-resetting) counters belong to
     unsigned long long wire_tile_frames = 0;
+    // line pass (b32_draw_lines): batches of more than LINE_SMALL lines are copied into a pinned ring slot, then to d_lines on the stream
+    static constexpr uint32_t LINE_RING = 4;
+    B32Line* h_lines[LINE_RING] = {}; size_t cap_h_lines[LINE_RING] = {}; hipEvent_t ev_lines[LINE_RING] = {}; uint32_t line_slot = 0;
+    B32Line* d_lines = nullptr; size_t cap_lines = 0;
+    uint32_t *line_counters = nullptr, *line_lists = nullptr, *line_long = nullptr; size_t cap_line_tiles = 0; uint32_t line_parity = 0;
+    unsigned long long line_tile_batches = 0, line_scan_batches = 0;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl* d_ctrl = nullptr; uint32_t* d_consts = nullptr; Ctrl h_ctrl{}; Stamps h_stamps{};   // (d_ctrl: Ctrl followed by Stamps)

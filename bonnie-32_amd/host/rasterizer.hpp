@@ -114,8 +114,19 @@ public:
     void clear(Color c) { check(b32_fb_clear(ctx_, c.r, c.g, c.b, (uint8_t)c.blend), "Framebuffer::clear"); }
     std::vector<uint8_t> pixels() const { std::vector<uint8_t> p(width * height * 4); check(b32_fb_download(ctx_, p.data()), "fb.pixels"); return p; }
     void set_pixels(const std::vector<uint8_t>& p) { if (p.size() != width * height * 4) throw Error(B32_E_ARG, "set_pixels"); check(b32_fb_upload(ctx_, p.data()), "fb.pixels="); }
+    // the line family, render.rs:684-872 (enqueued, no host synchronisation; several lines at once: draw_lines, in array order)
+    void draw_line(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { draw_one(B32_LINE_2D, x0, y0, 0.0f, x1, y1, 0.0f, c, 255); }
+    void draw_line_alpha(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, uint8_t alpha) { draw_one(B32_LINE_2D_ALPHA, x0, y0, 0.0f, x1, y1, 0.0f, c, alpha); }
+    void draw_line_3d(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c) { draw_one(B32_LINE_3D, x0, y0, z0, x1, y1, z1, c, 255); }
+    void draw_line_3d_overlay(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c) { draw_one(B32_LINE_3D_OVERLAY, x0, y0, z0, x1, y1, z1, c, 255); }
+    void draw_line_3d_alpha(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) { draw_one(B32_LINE_3D_ALPHA, x0, y0, z0, x1, y1, z1, c, alpha); }
+    void draw_lines(const std::vector<B32Line>& lines) { check(b32_draw_lines(ctx_, lines.data(), (uint32_t)lines.size()), "draw_lines"); }
     b32_ctx* ctx() const { return ctx_; }
 private:
+    void draw_one(uint8_t kind, int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) {
+        const B32Line l = { x0, y0, x1, y1, z0, z1, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, { 0, 0 } };
+        check(b32_draw_lines(ctx_, &l, 1), "draw_line");
+    }
     b32_ctx* ctx_ = nullptr;
 };
 

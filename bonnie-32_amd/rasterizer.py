@@ -73,9 +73,9 @@ class Context:
         _chk(self.lib.b32_set_async_depth(self.h, int(deep)), "b32_set_async_depth")
 
     ROUTES = ("direct_bin", "inline_bin", "counting_sort", "keyed", "redraw_region", "redraw_global_sort", "redraw_pairs", "pipelined", "lds_atlas", "wire_tiles", "span_cover",
-              "flag_join", "event_join", "poll_join")
+              "flag_join", "event_join", "poll_join", "line_tiles", "line_scan")
 
-    ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096
+    ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER, ROUTE_LINE_TILES = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
 
     # ---- a frame of several meshes (scene.rs:112-261): b32_frame_begin / _add_scene / _end
     def frame_begin(self, camera, settings):
@@ -371,6 +371,39 @@ class Framebuffer:
         cx = np.ascontiguousarray(cx, np.int32); cy = np.ascontiguousarray(cy, np.int32)
         rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
         _chk(self.ctx.lib.b32_draw_star_diamonds(self.ctx.h, cx.ctypes.data, cy.ctypes.data, rgb.ctypes.data, len(cx), float(size)), "draw_star_diamonds")
+
+    # ---- the line family (render.rs:684-872): each call is a batch of one; draw_lines takes a whole abi.LINE_DTYPE array in order
+    def draw_lines(self, lines):
+        """b32_draw_lines: every line of `lines` (abi.LINE_DTYPE) as the reference calls in array order; enqueued, no host synchronisation."""
+        arr = np.ascontiguousarray(lines, dtype=abi.LINE_DTYPE).reshape(-1)
+        _chk(self.ctx.lib.b32_draw_lines(self.ctx.h, arr.ctypes.data if len(arr) else None, len(arr)), "draw_lines")
+
+    @staticmethod
+    def _line(kind, x0, y0, x1, y1, z0, z1, color: T.Color, alpha):
+        l = np.zeros(1, abi.LINE_DTYPE)
+        l["x0"], l["y0"], l["x1"], l["y1"], l["z0"], l["z1"] = x0, y0, x1, y1, z0, z1
+        l["r"], l["g"], l["b"], l["blend"], l["kind"], l["alpha"] = color.r, color.g, color.b, color.blend, kind, alpha
+        return l
+
+    def draw_line(self, x0, y0, x1, y1, color: T.Color):
+        """Framebuffer::draw_line (render.rs:715-755)"""
+        self.draw_lines(self._line(abi.LINE_2D, x0, y0, x1, y1, 0.0, 0.0, color, 255))
+
+    def draw_line_alpha(self, x0, y0, x1, y1, color: T.Color, alpha):
+        """Framebuffer::draw_line_alpha (render.rs:684-711)"""
+        self.draw_lines(self._line(abi.LINE_2D_ALPHA, x0, y0, x1, y1, 0.0, 0.0, color, alpha))
+
+    def draw_line_3d(self, x0, y0, z0, x1, y1, z1, color: T.Color):
+        """Framebuffer::draw_line_3d (render.rs:757-762): z < zbuffer"""
+        self.draw_lines(self._line(abi.LINE_3D, x0, y0, x1, y1, z0, z1, color, 255))
+
+    def draw_line_3d_overlay(self, x0, y0, z0, x1, y1, z1, color: T.Color):
+        """Framebuffer::draw_line_3d_overlay (render.rs:764-766): z <= zbuffer"""
+        self.draw_lines(self._line(abi.LINE_3D_OVERLAY, x0, y0, x1, y1, z0, z1, color, 255))
+
+    def draw_line_3d_alpha(self, x0, y0, z0, x1, y1, z1, color: T.Color, alpha):
+        """Framebuffer::draw_line_3d_alpha (render.rs:822-872): depths * 0.995, z <= zbuffer, set_pixel_alpha"""
+        self.draw_lines(self._line(abi.LINE_3D_ALPHA, x0, y0, x1, y1, z0, z1, color, alpha))
 
     def present_nearest(self, dst_w, dst_h):
         """The presenter's nearest-neighbour upscale (game/renderer.rs:179-214) -> uint8 [dst_h, dst_w, 4]."""

@@ -250,7 +250,8 @@ int b32_frame_finish(b32_ctx* ctx, B32Timings* out /* nullable */);
  * far more of the mesh lands in one screen tile than the mean) or need the global depth sort; it then draws nothing and must be
  * redrawn by the host.
  *   deep = 0 (default): safe.  Enqueueing another frame, or any call that reads, writes or rebinds the framebuffer (b32_fb_download,
- *            b32_zbuffer_download, b32_fb_upload, b32_fb_clear*, b32_render_skybox_mesh, b32_draw_star_diamonds, b32_fb_bind_device,
+ *            b32_zbuffer_download, b32_fb_upload, b32_fb_clear*, b32_render_skybox_mesh, b32_draw_star_diamonds, b32_draw_lines,
+ *            b32_fb_bind_device,
  *            b32_set_stream, b32_present_nearest, b32_scene_upload*, b32_scene_swap, b32_set_band), first settles the pending frame (one host synchronisation, redraw if needed): no
  *            frame is ever lost, and none is redrawn on top of a later clear.  One exception that cannot be observed (round 5): a
  *            b32_fb_clear of the whole band behind a pending frame overwrites every pixel and depth that frame can have drawn, so the
@@ -277,7 +278,8 @@ int b32_set_async_depth(b32_ctx* ctx, int deep);
  * 9 frames whose wireframe phases went through the tile route (B32_ROUTE_WIRE_TILES), 10 frames whose opaque coverage was decided by
  * exact row intervals (B32_ROUTE_SPAN_COVER), 11 pipelined frames whose setup kernel was handed over to the fill by the flag / join kernel
  * pair, 12 by a cross-stream event (main and side stream of one priority), 13 those of 11 whose fused kernel polled the flag itself (the merged
- * draws of a batched frame: no launch and no event in front of the fill).
+ * draws of a batched frame: no launch and no event in front of the fill), 14 b32_draw_lines batches binned to tiles (B32_ROUTE_LINE_TILES),
+ * 15 b32_draw_lines batches in which every tile scanned the whole batch in order (small batches, or the route switched off).
  * Unknown `which` or null ctx: 0. */
 unsigned long long b32_route_count(const b32_ctx* ctx, int which);
 /* Switch internal routes OFF for the frames enqueued from now on (no reference counterpart: the results are identical on every route;
@@ -300,6 +302,8 @@ unsigned long long b32_route_count(const b32_ctx* ctx, int which);
                                     * interval with integer-quotient ends -- no per-pixel test; other surfaces keep the per-pixel form -> per-pixel form for all */
 #define B32_ROUTE_STAGGER     4096u /* fused kernel, frames with more tiles than workgroup slots: the second workgroup of every CU starts 4 us late (the two then
                                     * run coverage against shading instead of in step) -> all workgroups start together */
+#define B32_ROUTE_LINE_TILES  8192u /* b32_draw_lines, batches of more than 64 lines: line ids binned to 64x16 tiles, each tile's list put in order in LDS
+                                    * (a tile whose list overflows scans the whole batch) -> every tile scans the whole batch in order */
 #define B32_ROUTE_PIPELINE    64u  /* setup kernel of the next frame on a second stream beside the fill of the current one -> one stream */
 int b32_set_routes(b32_ctx* ctx, uint32_t off_mask);
 /* CHEAP coverage (inside test only, texel rule applied to the winner) is used while every texture has at most 1/den skippable texels
@@ -383,6 +387,29 @@ int b32_render_skybox_mesh(b32_ctx* ctx, const B32SkyVertex* vertices, uint32_t 
                            const B32Camera* camera);
 /* draw_star_diamond, render.rs:199-240, for n stars in order: centre (cx, cy) = (screen.x as i32, screen.y as i32), colour rgb[3*i..]. */
 int b32_draw_star_diamonds(b32_ctx* ctx, const int32_t* cx, const int32_t* cy, const uint8_t* rgb, uint32_t n, float size);
+/* The Framebuffer's line family (render.rs:684-872), drawn after the meshes by every caller (the player's cylinder, the editor's
+ * outlines and gizmos, the modeler's edge overlay).  Lines never write the z-buffer; they read it (f32::MAX everywhere while it is not
+ * valid, as in painter's mode).  Colour = Color{r, g, b, blend} (blend: BlendMode, B32_BLEND_ERASE -> alpha byte 0 in set_pixel,
+ * types.rs:829-832); the *_ALPHA kinds blend rgb with `alpha` through set_pixel_alpha (render.rs:646-667) and ignore `blend`. */
+typedef struct B32Line {
+    int32_t x0, y0, x1, y1;
+    float   z0, z1;             /* ignored by the 2-D kinds */
+    uint8_t r, g, b, blend;
+    uint8_t kind;               /* B32_LINE_* */
+    uint8_t alpha;              /* the *_ALPHA kinds */
+    uint8_t _pad[2];
+} B32Line;                      /* 32 bytes */
+#define B32_LINE_2D          0u /* draw_line            render.rs:715-755 (draw_line_blended, Opaque -> set_pixel)  */
+#define B32_LINE_2D_ALPHA    1u /* draw_line_alpha      render.rs:684-711 (set_pixel_alpha)                          */
+#define B32_LINE_3D          2u /* draw_line_3d         render.rs:757-817, z <  zbuffer                               */
+#define B32_LINE_3D_OVERLAY  3u /* draw_line_3d_overlay render.rs:764-766, z <= zbuffer                               */
+#define B32_LINE_3D_ALPHA    4u /* draw_line_3d_alpha   render.rs:822-872, z * 0.995 both ends, <=, set_pixel_alpha    */
+/* Draws lines[0..n) as the reference methods called one after another in array order on the current framebuffer: every pixel and
+ * byte equal, only rows of the band written.  Asynchronous: enqueued on the context's stream behind everything enqueued before (a
+ * deferred b32_fb_clear is flushed first) and ahead of everything after it; `lines` may be reused as soon as the call returns (the
+ * batch is copied).  The whole batch is checked first and nothing is drawn if a line is rejected: an unknown kind -> B32_E_ARG; an
+ * extent |x1-x0| or |y1-y0| >= 2^30 (2*err overflows i32 in the reference) -> B32_E_UNSUPPORTED.  n == 0: no-op. */
+int b32_draw_lines(b32_ctx* ctx, const B32Line* lines, uint32_t n);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
