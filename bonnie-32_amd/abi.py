@@ -45,6 +45,12 @@ LINE_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"
 assert LINE_DTYPE.itemsize == 32
 LINE_2D, LINE_2D_ALPHA, LINE_3D, LINE_3D_OVERLAY, LINE_3D_ALPHA = range(5)
 
+# B32Prim (the rest of the Framebuffer drawing methods, b32_draw_prims): kinds 0..4 = LINE_*, then B32_PRIM_*
+PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("z0", "<f4"), ("z1", "<f4"), ("size", "<i4"),
+                       ("r", "u1"), ("g", "u1"), ("b", "u1"), ("blend", "u1"), ("kind", "u1"), ("alpha", "u1"), ("mode", "u1"), ("_pad", "u1", 5)])
+assert PRIM_DTYPE.itemsize == 40
+PRIM_LINE_BLENDED, PRIM_CIRCLE, PRIM_CIRCLE_ALPHA, PRIM_THICK_LINE, PRIM_RECT, PRIM_FILLED_RECT = range(5, 11)
+
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -137,6 +143,7 @@ SYMBOLS = [
     ("b32_draw_star_diamonds", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_float]),
     ("b32_present_nearest", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     ("b32_draw_lines", C.c_int, [_P, _P, C.c_uint32]),
+    ("b32_draw_prims", C.c_int, [_P, _P, C.c_uint32]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

@@ -48,7 +48,7 @@ void b32_destroy(b32_ctx* c) {
                      c->shades, c->counts, c->block_sums, c->pkeys[0], c->pkeys[1], c->pvals[0], c->pvals[1], c->block_hist, c->ranges,
                      c->d_ctrl, c->d_consts, c->d_lights, c->digit_total, c->partials, c->vis, c->spans, c->tile_mid, c->zbuf,
                      c->wire, c->wire_owner, c->wire_first, c->wire_fill, c->wire_lists, c->d_texels32, c->inline_lists, c->d_texmask, c->direct_lists, c->tile_fill, c->d_pos12, c->face_of, c->d_atlas0,
-                     c->d_lines, c->line_counters, c->line_lists, c->line_long };
+                     c->d_lines, c->line_counters, c->line_lists, c->line_long, c->d_prims, c->prim_counters, c->prim_lists, c->prim_long };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto& r : c->merged_runs) if (r.merged) { void* mp[] = { r.merged->d_verts, r.merged->d_faces, r.merged->d_texels, r.merged->d_texels32, r.merged->d_tex,
@@ -59,6 +59,7 @@ void b32_destroy(b32_ctx* c) {
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
     for (uint32_t k = 0; k < b32_ctx::LINE_RING; ++k) { if (c->ev_lines[k]) (void)hipEventDestroy(c->ev_lines[k]); if (c->h_lines[k]) (void)hipHostFree(c->h_lines[k]); }
+    for (uint32_t k = 0; k < b32_ctx::LINE_RING; ++k) { if (c->ev_prims[k]) (void)hipEventDestroy(c->ev_prims[k]); if (c->h_prims[k]) (void)hipHostFree(c->h_prims[k]); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
@@ -318,6 +319,77 @@ int b32_draw_lines(b32_ctx* c, const B32Line* lines, uint32_t n) {
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
+// The rest of Framebuffer's drawing methods (render.rs:631-971) and the line family, in array order, on the stream (b32_prims.hip).  The
+// same staging as b32_draw_lines: a batch of at most PRIM_SMALL travels in the kernel argument, a larger one through a pinned ring slot.
+int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
+    if (!c || !c->fb || (n && !prims)) return B32_E_ARG;
+    for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is drawn
+        const B32Prim& p = prims[i];
+        if (p.kind > B32_PRIM_FILLED_RECT || (p.kind == B32_PRIM_LINE_BLENDED && p.mode > B32_BLEND_ERASE)) return B32_E_ARG;
+        if (p.kind == B32_PRIM_CIRCLE || p.kind == B32_PRIM_CIRCLE_ALPHA) {
+            // r * r, dx * dx + dy * dy and cy +- radius stay inside i32 (render.rs:632-637)
+            if (std::llabs((long long)p.size) > 32767 || std::llabs((long long)p.x0) >= (1ll << 30) || std::llabs((long long)p.y0) >= (1ll << 30))
+                return B32_E_UNSUPPORTED;
+        } else if (p.kind != B32_PRIM_FILLED_RECT) {
+            const long long adx = std::llabs((long long)p.x1 - p.x0), ady = std::llabs((long long)p.y1 - p.y0);
+            if (adx >= (1ll << 30) || ady >= (1ll << 30)) return B32_E_UNSUPPORTED;     // 2 * err overflows i32 (render.rs:735, 800)
+        }
+    }
+    if (!n) return B32_OK;
+    (void)hipSetDevice(c->device);
+    { const int rcs = settle_before_write(c); if (rcs) return rcs; }
+    { const int rcf = flush_clear(c); if (rcf) return rcf; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    PrimArgs a{};
+    a.n = n; a.fb = c->fb;
+    a.zbuf = (c->zbuf && c->zbuf_valid && (size_t)c->width * c->height <= c->cap_zbuf) ? c->zbuf : nullptr;
+    a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
+    a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
+    if (n <= PRIM_SMALL) {
+        launch_prims(c->stream, a, prims);
+        HIPCHK(c, hipGetLastError());
+        ++c->prim_scan_batches;
+        return B32_OK;
+    }
+    const uint32_t k = c->prim_slot;
+    c->prim_slot = (k + 1) % b32_ctx::LINE_RING;
+    if (c->ev_prims[k]) HIPCHK(c, hipEventSynchronize(c->ev_prims[k]));
+    else HIPCHK(c, hipEventCreateWithFlags(&c->ev_prims[k], hipEventDisableTiming));
+    if (c->cap_h_prims[k] < n) {
+        if (c->h_prims[k]) HIPCHK(c, hipHostFree(c->h_prims[k]));
+        c->h_prims[k] = nullptr; c->cap_h_prims[k] = 0;
+        const size_t cap = (size_t)n + n / 4 + 64;
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_prims[k]), cap * sizeof(B32Prim), hipHostMallocDefault));
+        c->cap_h_prims[k] = cap;
+    }
+    std::memcpy(c->h_prims[k], prims, (size_t)n * sizeof(B32Prim));
+    int rc;
+    if ((rc = ensure(c, c->d_prims, c->cap_prims, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_prims, c->h_prims[k], (size_t)n * sizeof(B32Prim), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_prims[k], c->stream));
+    a.prims = c->d_prims;
+    const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
+    if (!(c->route_off & B32_ROUTE_PRIM_TILES)) {
+        if (ntiles > c->cap_prim_tiles || !c->prim_counters) {             // (zero between batches: every tile kernel zeroes its own counter)
+            const size_t cap = ntiles + ntiles / 4 + 16;
+            if (c->prim_counters) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->prim_counters)); HIPCHK(c, hipFree(c->prim_lists)); }
+            c->prim_counters = c->prim_lists = nullptr; c->cap_prim_tiles = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_counters), (cap + 2) * FILL_PAD * sizeof(uint32_t)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_lists), cap * LINE_TILE_CAP * sizeof(uint32_t)));
+            HIPCHK(c, hipMemsetAsync(c->prim_counters, 0, (cap + 2) * FILL_PAD * sizeof(uint32_t), c->stream));
+            c->cap_prim_tiles = cap;
+        }
+        if (!c->prim_long) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_long), LINE_LONG_CAP * sizeof(uint32_t)));
+        a.counters = c->prim_counters; a.lists = c->prim_lists; a.long_list = c->prim_long; a.parity = c->prim_parity;
+        c->prim_parity ^= 1u;
+        ++c->prim_tile_batches;
+    } else {
+        ++c->prim_scan_batches;
+    }
+    launch_prims(c->stream, a, nullptr);
+    HIPCHK(c, hipGetLastError());
+    return B32_OK;
+}
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
     if (!c || !c->fb || !out || !dw || !dh || dw > 32768 || dh > 32768) return B32_E_ARG;
     (void)hipSetDevice(c->device);
@@ -562,6 +634,8 @@ extern "C" unsigned long long b32_route_count(const b32_ctx* c, int which) {
     if (c && which == 13) return c->poll_join_frames;
     if (c && which == 14) return c->line_tile_batches;
     if (c && which == 15) return c->line_scan_batches;
+    if (c && which == 16) return c->prim_tile_batches;
+    if (c && which == 17) return c->prim_scan_batches;
     return (c && which >= 0 && which < 8) ? c->routes[which] : 0ull;
 }
 extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {

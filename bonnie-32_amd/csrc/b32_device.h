@@ -479,6 +479,16 @@ struct LineArgs {
 };
 struct LineBatch { B32Line l[LINE_SMALL]; };
 void launch_lines(hipStream_t s, const LineArgs& a, const B32Line* small);   // small != nullptr: n <= LINE_SMALL lines passed by value
+// Framebuffer primitive pass (b32_draw_prims, b32_prims.hip): the line pass's tiles, caps and tile route for B32Prim batches.
+constexpr uint32_t PRIM_SMALL = 48;            // batches of at most this many primitives travel in the kernel argument (PrimBatch, 1920 bytes)
+struct PrimArgs {
+    const B32Prim* prims; uint32_t n;          // prims == nullptr: the batch is the kernel argument
+    uint32_t* fb; const float* zbuf;           // zbuf == nullptr: every depth is f32::MAX
+    uint32_t width, band_y0, band_y1, tiles_x, tiles_y;
+    uint32_t* counters; uint32_t* lists; uint32_t* long_list; uint32_t parity;   // as in LineArgs
+};
+struct PrimBatch { B32Prim p[PRIM_SMALL]; };
+void launch_prims(hipStream_t s, const PrimArgs& a, const B32Prim* small);   // small != nullptr: n <= PRIM_SMALL primitives passed by value
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

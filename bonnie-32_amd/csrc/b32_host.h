@@ -159,6 +159,11 @@ struct b32_ctx {
     B32Line* d_lines = nullptr; size_t cap_lines = 0;
     uint32_t *line_counters = nullptr, *line_lists = nullptr, *line_long = nullptr; size_t cap_line_tiles = 0; uint32_t line_parity = 0;
     unsigned long long line_tile_batches = 0, line_scan_batches = 0;
+    // primitive pass (b32_draw_prims): the same ring and tile route for batches of more than PRIM_SMALL primitives
+    B32Prim* h_prims[LINE_RING] = {}; size_t cap_h_prims[LINE_RING] = {}; hipEvent_t ev_prims[LINE_RING] = {}; uint32_t prim_slot = 0;
+    B32Prim* d_prims = nullptr; size_t cap_prims = 0;
+    uint32_t *prim_counters = nullptr, *prim_lists = nullptr, *prim_long = nullptr; size_t cap_prim_tiles = 0; uint32_t prim_parity = 0;
+    unsigned long long prim_tile_batches = 0, prim_scan_batches = 0;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl* d_ctrl = nullptr; uint32_t* d_consts = nullptr; Ctrl h_ctrl{}; Stamps h_stamps{};   // (d_ctrl: Ctrl followed by Stamps)

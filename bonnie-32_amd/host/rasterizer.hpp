@@ -121,13 +121,56 @@ public:
     void draw_line_3d_overlay(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c) { draw_one(B32_LINE_3D_OVERLAY, x0, y0, z0, x1, y1, z1, c, 255); }
     void draw_line_3d_alpha(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) { draw_one(B32_LINE_3D_ALPHA, x0, y0, z0, x1, y1, z1, c, alpha); }
     void draw_lines(const std::vector<B32Line>& lines) { check(b32_draw_lines(ctx_, lines.data(), (uint32_t)lines.size()), "draw_lines"); }
+    // the other drawing methods, render.rs:631-971 (enqueued; several at once, mixed with lines: draw_prims / PrimBatch, in array order)
+    void draw_line_blended(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, BlendMode mode) { draw_prim(prim(B32_PRIM_LINE_BLENDED, x0, y0, x1, y1, c, 0, 255, mode)); }
+    void draw_circle(int32_t cx, int32_t cy, int32_t radius, Color c) { draw_prim(prim(B32_PRIM_CIRCLE, cx, cy, 0, 0, c, radius)); }
+    void draw_circle_alpha(int32_t cx, int32_t cy, int32_t radius, Color c, uint8_t alpha) { draw_prim(prim(B32_PRIM_CIRCLE_ALPHA, cx, cy, 0, 0, c, radius, alpha)); }
+    void draw_thick_line(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t thickness, Color c) { draw_prim(prim(B32_PRIM_THICK_LINE, x0, y0, x1, y1, c, thickness)); }
+    void draw_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { draw_prim(prim(B32_PRIM_RECT, x0, y0, x1, y1, c)); }
+    void draw_filled_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { draw_prim(prim(B32_PRIM_FILLED_RECT, x0, y0, x1, y1, c)); }
+    void draw_prims(const std::vector<B32Prim>& prims) { check(b32_draw_prims(ctx_, prims.data(), (uint32_t)prims.size()), "draw_prims"); }
+    // one B32Prim record (kinds B32_LINE_* / B32_PRIM_*; z0 / z1 only for the 3-D line kinds)
+    static B32Prim prim(uint8_t kind, int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, int32_t size = 0, uint8_t alpha = 255,
+                        BlendMode mode = BlendMode::Opaque, float z0 = 0.0f, float z1 = 0.0f) {
+        return B32Prim{ x0, y0, x1, y1, z0, z1, size, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, (uint8_t)mode, { 0, 0, 0, 0, 0 } };
+    }
     b32_ctx* ctx() const { return ctx_; }
 private:
+    void draw_prim(const B32Prim& p) { check(b32_draw_prims(ctx_, &p, 1), "draw_prims"); }
     void draw_one(uint8_t kind, int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) {
         const B32Line l = { x0, y0, x1, y1, z0, z1, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, { 0, 0 } };
         check(b32_draw_lines(ctx_, &l, 1), "draw_line");
     }
     b32_ctx* ctx_ = nullptr;
+};
+
+// Framebuffer's drawing methods recorded in call order; flush() draws them with ONE b32_draw_prims call (a dot per vertex costs one launch
+// per frame, not one per circle).  set_pixel / set_pixel_alpha / set_pixel_blended: a 1x1 FILLED_RECT, a one-point LINE_2D_ALPHA, a
+// one-point LINE_BLENDED.
+class PrimBatch {
+public:
+    explicit PrimBatch(Framebuffer& fb) : fb_(fb) {}
+    void draw_line(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { add(B32_LINE_2D, x0, y0, x1, y1, c); }
+    void draw_line_alpha(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, uint8_t alpha) { add(B32_LINE_2D_ALPHA, x0, y0, x1, y1, c, 0, alpha); }
+    void draw_line_3d(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c) { add(B32_LINE_3D, x0, y0, x1, y1, c, 0, 255, BlendMode::Opaque, z0, z1); }
+    void draw_line_3d_overlay(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c) { add(B32_LINE_3D_OVERLAY, x0, y0, x1, y1, c, 0, 255, BlendMode::Opaque, z0, z1); }
+    void draw_line_3d_alpha(int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) { add(B32_LINE_3D_ALPHA, x0, y0, x1, y1, c, 0, alpha, BlendMode::Opaque, z0, z1); }
+    void draw_line_blended(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, BlendMode mode) { add(B32_PRIM_LINE_BLENDED, x0, y0, x1, y1, c, 0, 255, mode); }
+    void draw_circle(int32_t cx, int32_t cy, int32_t radius, Color c) { add(B32_PRIM_CIRCLE, cx, cy, 0, 0, c, radius); }
+    void draw_circle_alpha(int32_t cx, int32_t cy, int32_t radius, Color c, uint8_t alpha) { add(B32_PRIM_CIRCLE_ALPHA, cx, cy, 0, 0, c, radius, alpha); }
+    void draw_thick_line(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t thickness, Color c) { add(B32_PRIM_THICK_LINE, x0, y0, x1, y1, c, thickness); }
+    void draw_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { add(B32_PRIM_RECT, x0, y0, x1, y1, c); }
+    void draw_filled_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { add(B32_PRIM_FILLED_RECT, x0, y0, x1, y1, c); }
+    void set_pixel(int32_t x, int32_t y, Color c) { add(B32_PRIM_FILLED_RECT, x, y, x, y, c); }
+    void set_pixel_alpha(int32_t x, int32_t y, Color c, uint8_t alpha) { add(B32_LINE_2D_ALPHA, x, y, x, y, c, 0, alpha); }
+    void set_pixel_blended(int32_t x, int32_t y, Color c, BlendMode mode) { add(B32_PRIM_LINE_BLENDED, x, y, x, y, c, 0, 255, mode); }
+    size_t size() const { return recs_.size(); }
+    void flush() { fb_.draw_prims(recs_); recs_.clear(); }
+private:
+    template <typename... A>
+    void add(uint8_t kind, A... args) { recs_.push_back(Framebuffer::prim(kind, args...)); }
+    Framebuffer& fb_;
+    std::vector<B32Prim> recs_;
 };
 
 namespace detail {

@@ -73,9 +73,9 @@ class Context:
         _chk(self.lib.b32_set_async_depth(self.h, int(deep)), "b32_set_async_depth")
 
     ROUTES = ("direct_bin", "inline_bin", "counting_sort", "keyed", "redraw_region", "redraw_global_sort", "redraw_pairs", "pipelined", "lds_atlas", "wire_tiles", "span_cover",
-              "flag_join", "event_join", "poll_join", "line_tiles", "line_scan")
+              "flag_join", "event_join", "poll_join", "line_tiles", "line_scan", "prim_tiles", "prim_scan")
 
-    ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER, ROUTE_LINE_TILES = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192
+    ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER, ROUTE_LINE_TILES, ROUTE_PRIM_TILES = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384
 
     # ---- a frame of several meshes (scene.rs:112-261): b32_frame_begin / _add_scene / _end
     def frame_begin(self, camera, settings):
@@ -405,6 +405,40 @@ class Framebuffer:
         """Framebuffer::draw_line_3d_alpha (render.rs:822-872): depths * 0.995, z <= zbuffer, set_pixel_alpha"""
         self.draw_lines(self._line(abi.LINE_3D_ALPHA, x0, y0, x1, y1, z0, z1, color, alpha))
 
+    # ---- the other drawing methods (render.rs:631-971), in one ordered batch with the line family: b32_draw_prims
+    def draw_prims(self, prims):
+        """b32_draw_prims: every record of `prims` (abi.PRIM_DTYPE) as the reference calls in array order; enqueued, no host synchronisation."""
+        arr = np.ascontiguousarray(prims, dtype=abi.PRIM_DTYPE).reshape(-1)
+        _chk(self.ctx.lib.b32_draw_prims(self.ctx.h, arr.ctypes.data if len(arr) else None, len(arr)), "draw_prims")
+
+    def prim_batch(self):
+        """A PrimBatch on this framebuffer: the same drawing methods, recorded; flush() draws them all with one b32_draw_prims call."""
+        return PrimBatch(self)
+
+    def draw_line_blended(self, x0, y0, x1, y1, color: T.Color, mode):
+        """Framebuffer::draw_line_blended (render.rs:720-755): Opaque -> set_pixel, else set_pixel_blended"""
+        self.draw_prims(prim(abi.PRIM_LINE_BLENDED, x0, y0, x1, y1, color, mode=mode))
+
+    def draw_circle(self, cx, cy, radius, color: T.Color):
+        """Framebuffer::draw_circle (render.rs:631-642)"""
+        self.draw_prims(prim(abi.PRIM_CIRCLE, cx, cy, 0, 0, color, size=radius))
+
+    def draw_circle_alpha(self, cx, cy, radius, color: T.Color, alpha):
+        """Framebuffer::draw_circle_alpha (render.rs:670-681)"""
+        self.draw_prims(prim(abi.PRIM_CIRCLE_ALPHA, cx, cy, 0, 0, color, size=radius, alpha=alpha))
+
+    def draw_thick_line(self, x0, y0, x1, y1, thickness, color: T.Color):
+        """Framebuffer::draw_thick_line (render.rs:875-938)"""
+        self.draw_prims(prim(abi.PRIM_THICK_LINE, x0, y0, x1, y1, color, size=thickness))
+
+    def draw_rect(self, x0, y0, x1, y1, color: T.Color):
+        """Framebuffer::draw_rect (render.rs:941-951)"""
+        self.draw_prims(prim(abi.PRIM_RECT, x0, y0, x1, y1, color))
+
+    def draw_filled_rect(self, x0, y0, x1, y1, color: T.Color):
+        """Framebuffer::draw_filled_rect (render.rs:954-971)"""
+        self.draw_prims(prim(abi.PRIM_FILLED_RECT, x0, y0, x1, y1, color))
+
     def present_nearest(self, dst_w, dst_h):
         """The presenter's nearest-neighbour upscale (game/renderer.rs:179-214) -> uint8 [dst_h, dst_w, 4]."""
         out = np.empty((dst_h, dst_w, 4), np.uint8)
@@ -473,6 +507,81 @@ def render_mesh(fb: Framebuffer, vertices, faces, textures, camera: T.Camera, se
 
 # aliases named in BASELINE.json's north_star (the reference's real entry point is render_mesh_15)
 draw_mesh = render_mesh_15
+
+
+def prim(kind, x0, y0, x1, y1, color: T.Color, z0=0.0, z1=0.0, size=0, alpha=255, mode=0):
+    """One abi.PRIM_DTYPE record."""
+    p = np.zeros(1, abi.PRIM_DTYPE)
+    p["x0"], p["y0"], p["x1"], p["y1"], p["z0"], p["z1"], p["size"] = x0, y0, x1, y1, z0, z1, size
+    p["r"], p["g"], p["b"], p["blend"], p["kind"], p["alpha"], p["mode"] = color.r, color.g, color.b, color.blend, kind, alpha, mode
+    return p
+
+
+class PrimBatch:
+    """Framebuffer's drawing methods, recorded in call order; flush() draws them with ONE b32_draw_prims call (callers that draw a dot per
+    vertex pay one launch per frame, not one per circle).  set_pixel / set_pixel_alpha / set_pixel_blended map to a 1x1 FILLED_RECT, a
+    one-point LINE_2D_ALPHA and a one-point LINE_BLENDED."""
+
+    def __init__(self, fb: "Framebuffer"):
+        self.fb = fb
+        self._recs = []
+
+    def __len__(self):
+        return len(self._recs)
+
+    def _add(self, *args, **kw):
+        self._recs.append(prim(*args, **kw))
+
+    def draw_line(self, x0, y0, x1, y1, color: T.Color):
+        self._add(abi.LINE_2D, x0, y0, x1, y1, color)
+
+    def draw_line_alpha(self, x0, y0, x1, y1, color: T.Color, alpha):
+        self._add(abi.LINE_2D_ALPHA, x0, y0, x1, y1, color, alpha=alpha)
+
+    def draw_line_3d(self, x0, y0, z0, x1, y1, z1, color: T.Color):
+        self._add(abi.LINE_3D, x0, y0, x1, y1, color, z0=z0, z1=z1)
+
+    def draw_line_3d_overlay(self, x0, y0, z0, x1, y1, z1, color: T.Color):
+        self._add(abi.LINE_3D_OVERLAY, x0, y0, x1, y1, color, z0=z0, z1=z1)
+
+    def draw_line_3d_alpha(self, x0, y0, z0, x1, y1, z1, color: T.Color, alpha):
+        self._add(abi.LINE_3D_ALPHA, x0, y0, x1, y1, color, z0=z0, z1=z1, alpha=alpha)
+
+    def draw_line_blended(self, x0, y0, x1, y1, color: T.Color, mode):
+        self._add(abi.PRIM_LINE_BLENDED, x0, y0, x1, y1, color, mode=mode)
+
+    def draw_circle(self, cx, cy, radius, color: T.Color):
+        self._add(abi.PRIM_CIRCLE, cx, cy, 0, 0, color, size=radius)
+
+    def draw_circle_alpha(self, cx, cy, radius, color: T.Color, alpha):
+        self._add(abi.PRIM_CIRCLE_ALPHA, cx, cy, 0, 0, color, size=radius, alpha=alpha)
+
+    def draw_thick_line(self, x0, y0, x1, y1, thickness, color: T.Color):
+        self._add(abi.PRIM_THICK_LINE, x0, y0, x1, y1, color, size=thickness)
+
+    def draw_rect(self, x0, y0, x1, y1, color: T.Color):
+        self._add(abi.PRIM_RECT, x0, y0, x1, y1, color)
+
+    def draw_filled_rect(self, x0, y0, x1, y1, color: T.Color):
+        self._add(abi.PRIM_FILLED_RECT, x0, y0, x1, y1, color)
+
+    def set_pixel(self, x, y, color: T.Color):
+        self._add(abi.PRIM_FILLED_RECT, x, y, x, y, color)
+
+    def set_pixel_alpha(self, x, y, color: T.Color, alpha):
+        self._add(abi.LINE_2D_ALPHA, x, y, x, y, color, alpha=alpha)
+
+    def set_pixel_blended(self, x, y, color: T.Color, mode):
+        self._add(abi.PRIM_LINE_BLENDED, x, y, x, y, color, mode=mode)
+
+    def records(self):
+        """The recorded batch (abi.PRIM_DTYPE, call order)."""
+        return np.concatenate(self._recs) if self._recs else np.zeros(0, abi.PRIM_DTYPE)
+
+    def flush(self):
+        """Draws everything recorded (one b32_draw_prims call) and starts an empty batch."""
+        recs, self._recs = self.records(), []
+        self.fb.draw_prims(recs)
 
 
 class ResidentScene:

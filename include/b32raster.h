@@ -251,7 +251,7 @@ int b32_frame_finish(b32_ctx* ctx, B32Timings* out /* nullable */);
  * redrawn by the host.
  *   deep = 0 (default): safe.  Enqueueing another frame, or any call that reads, writes or rebinds the framebuffer (b32_fb_download,
  *            b32_zbuffer_download, b32_fb_upload, b32_fb_clear*, b32_render_skybox_mesh, b32_draw_star_diamonds, b32_draw_lines,
- *            b32_fb_bind_device,
+ *            b32_draw_prims, b32_fb_bind_device,
  *            b32_set_stream, b32_present_nearest, b32_scene_upload*, b32_scene_swap, b32_set_band), first settles the pending frame (one host synchronisation, redraw if needed): no
  *            frame is ever lost, and none is redrawn on top of a later clear.  One exception that cannot be observed (round 5): a
  *            b32_fb_clear of the whole band behind a pending frame overwrites every pixel and depth that frame can have drawn, so the
@@ -279,7 +279,8 @@ int b32_set_async_depth(b32_ctx* ctx, int deep);
  * exact row intervals (B32_ROUTE_SPAN_COVER), 11 pipelined frames whose setup kernel was handed over to the fill by the flag / join kernel
  * pair, 12 by a cross-stream event (main and side stream of one priority), 13 those of 11 whose fused kernel polled the flag itself (the merged
  * draws of a batched frame: no launch and no event in front of the fill), 14 b32_draw_lines batches binned to tiles (B32_ROUTE_LINE_TILES),
- * 15 b32_draw_lines batches in which every tile scanned the whole batch in order (small batches, or the route switched off).
+ * 15 b32_draw_lines batches in which every tile scanned the whole batch in order (small batches, or the route switched off), 16 b32_draw_prims
+ * batches binned to tiles (B32_ROUTE_PRIM_TILES), 17 b32_draw_prims batches in which every tile scanned the whole batch in order.
  * Unknown `which` or null ctx: 0. */
 unsigned long long b32_route_count(const b32_ctx* ctx, int which);
 /* Switch internal routes OFF for the frames enqueued from now on (no reference counterpart: the results are identical on every route;
@@ -304,6 +305,8 @@ unsigned long long b32_route_count(const b32_ctx* ctx, int which);
                                     * run coverage against shading instead of in step) -> all workgroups start together */
 #define B32_ROUTE_LINE_TILES  8192u /* b32_draw_lines, batches of more than 64 lines: line ids binned to 64x16 tiles, each tile's list put in order in LDS
                                     * (a tile whose list overflows scans the whole batch) -> every tile scans the whole batch in order */
+#define B32_ROUTE_PRIM_TILES 16384u /* b32_draw_prims, batches of more than 48 primitives: the same tile route as B32_ROUTE_LINE_TILES, binned by a conservative
+                                    * box per kind -> every tile scans the whole batch in order */
 #define B32_ROUTE_PIPELINE    64u  /* setup kernel of the next frame on a second stream beside the fill of the current one -> one stream */
 int b32_set_routes(b32_ctx* ctx, uint32_t off_mask);
 /* CHEAP coverage (inside test only, texel rule applied to the winner) is used while every texture has at most 1/den skippable texels
@@ -410,6 +413,36 @@ typedef struct B32Line {
  * batch is copied).  The whole batch is checked first and nothing is drawn if a line is rejected: an unknown kind -> B32_E_ARG; an
  * extent |x1-x0| or |y1-y0| >= 2^30 (2*err overflows i32 in the reference) -> B32_E_UNSUPPORTED.  n == 0: no-op. */
 int b32_draw_lines(b32_ctx* ctx, const B32Line* lines, uint32_t n);
+/* The rest of the Framebuffer's drawing methods (render.rs:631-971), in one ordered batch with the line family: circles, thick lines,
+ * rectangles and the PS1-blended line.  Colour = Color{r, g, b, blend} as in B32Line.  Single pixels need no kind of their own:
+ * set_pixel is a 1x1 B32_PRIM_FILLED_RECT, set_pixel_alpha a one-point B32_LINE_2D_ALPHA (x0 == x1, y0 == y1), set_pixel_blended a
+ * one-point B32_PRIM_LINE_BLENDED. */
+typedef struct B32Prim {
+    int32_t x0, y0, x1, y1;     /* lines, thick line, rects: end points / corners; circles: (x0, y0) = centre */
+    float   z0, z1;             /* the 3-D line kinds only */
+    int32_t size;               /* circles: radius; thick line: thickness; ignored by the other kinds */
+    uint8_t r, g, b, blend;     /* Color{r, g, b, blend}, as in B32Line */
+    uint8_t kind;               /* B32_PRIM_* */
+    uint8_t alpha;              /* the *_ALPHA kinds */
+    uint8_t mode;               /* B32_PRIM_LINE_BLENDED: the BlendMode argument of draw_line_blended */
+    uint8_t _pad[5];
+} B32Prim;                      /* 40 bytes */
+/* kinds 0..4 mean exactly what B32_LINE_2D .. B32_LINE_3D_ALPHA mean */
+#define B32_PRIM_LINE_BLENDED  5u /* draw_line_blended  render.rs:720-755 (mode Opaque -> set_pixel, else set_pixel_blended :313-334, which ignores
+                                   * the colour's own blend and gives Color::TRANSPARENT for Erase) */
+#define B32_PRIM_CIRCLE        6u /* draw_circle        render.rs:631-642 (set_pixel where dx*dx + dy*dy <= r*r; radius < 0: nothing)   */
+#define B32_PRIM_CIRCLE_ALPHA  7u /* draw_circle_alpha  render.rs:670-681 (the same pixels, set_pixel_alpha)                          */
+#define B32_PRIM_THICK_LINE    8u /* draw_thick_line    render.rs:875-938 (thickness <= 1: draw_line; else the f32 quad, set_pixel)   */
+#define B32_PRIM_RECT          9u /* draw_rect          render.rs:941-951 (four draw_line edges of the normalised corners)          */
+#define B32_PRIM_FILLED_RECT  10u /* draw_filled_rect   render.rs:954-971 (normalised, clamped, set_pixel: opaque)                  */
+/* Draws prims[0..n) as the reference methods called one after another in array order, with b32_draw_lines's contract: every pixel and
+ * byte equal, only rows of the band written, the z-buffer read (f32::MAX while it is not valid) and never written, enqueued on the
+ * context's stream with no host synchronisation (a deferred clear is flushed first), `prims` reusable as soon as the call returns.
+ * The whole batch is checked first and nothing is drawn if a primitive is rejected: an unknown kind, or B32_PRIM_LINE_BLENDED with
+ * mode > B32_BLEND_ERASE -> B32_E_ARG; for kinds 0..5, B32_PRIM_THICK_LINE and B32_PRIM_RECT an extent |x1-x0| or |y1-y0| >= 2^30
+ * -> B32_E_UNSUPPORTED; for circles |radius| > 32767 or |x0|, |y0| >= 2^30 (r*r, dx*dx + dy*dy or cy +- r overflow i32 in the
+ * reference) -> B32_E_UNSUPPORTED.  B32_PRIM_FILLED_RECT takes any i32.  n == 0: no-op. */
+int b32_draw_prims(b32_ctx* ctx, const B32Prim* prims, uint32_t n);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
