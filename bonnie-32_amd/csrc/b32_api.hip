@@ -47,8 +47,7 @@ void b32_destroy(b32_ctx* c) {
     void* ptrs[] = { c->fb_own, c->d_verts, c->d_faces, c->d_texels, c->d_tex, c->keys[0], c->keys[1], c->vals[0], c->vals[1], c->crecs, c->srecs, c->xrecs,
                      c->shades, c->counts, c->block_sums, c->pkeys[0], c->pkeys[1], c->pvals[0], c->pvals[1], c->block_hist, c->ranges,
                      c->d_ctrl, c->d_consts, c->d_lights, c->digit_total, c->partials, c->vis, c->spans, c->tile_mid, c->zbuf,
-                     c->wire, c->wire_owner, c->wire_first, c->wire_fill, c->wire_lists, c->d_texels32, c->inline_lists, c->d_texmask, c->direct_lists, c->tile_fill, c->d_pos12, c->face_of, c->d_atlas0,
-                     c->d_lines, c->line_counters, c->line_lists, c->line_long, c->d_prims, c->prim_counters, c->prim_lists, c->prim_long };
+                     c->wire, c->wire_owner, c->wire_first, c->wire_fill, c->wire_lists, c->d_texels32, c->inline_lists, c->d_texmask, c->direct_lists, c->tile_fill, c->d_pos12, c->face_of, c->d_atlas0 };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (auto& r : c->merged_runs) if (r.merged) { void* mp[] = { r.merged->d_verts, r.merged->d_faces, r.merged->d_texels, r.merged->d_texels32, r.merged->d_tex,
@@ -58,8 +57,7 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : { c->ev_main, c->ev_wbin, c->ev_setup, c->alt[0].ev_setup, c->alt[1].ev_setup }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    for (uint32_t k = 0; k < b32_ctx::LINE_RING; ++k) { if (c->ev_lines[k]) (void)hipEventDestroy(c->ev_lines[k]); if (c->h_lines[k]) (void)hipHostFree(c->h_lines[k]); }
-    for (uint32_t k = 0; k < b32_ctx::LINE_RING; ++k) { if (c->ev_prims[k]) (void)hipEventDestroy(c->ev_prims[k]); if (c->h_prims[k]) (void)hipHostFree(c->h_prims[k]); }
+    c->lines.release(); c->prims.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
@@ -253,9 +251,72 @@ int b32_draw_star_diamonds(b32_ctx* c, const int32_t* cx, const int32_t* cy, con
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return B32_OK;
 }
-// The line family of Framebuffer (render.rs:684-872), in array order, on the stream (b32_lines.hip).  A batch of at most LINE_SMALL lines
-// travels in the kernel argument; a larger one is copied into a pinned ring slot (the caller may reuse `lines` at once) and from there to
-// the device on the stream.  A slot is written again LINE_RING batches later, after its copy has left (normally long ago).
+}  // extern "C"
+
+// A validated batch through the ordered tile pass (b32_draw_pass.h), in array order, on the stream.  A batch of at most `small_n` records
+// travels in the kernel argument; a larger one is copied into a pinned ring slot of `ps` and from there to the device on the stream,
+// and takes the tile route unless `route` is switched off.
+template <class Rec>
+static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n, uint32_t small_n, uint32_t route) {
+    if (!n) return B32_OK;
+    (void)hipSetDevice(c->device);
+    { const int rcs = settle_before_write(c); if (rcs) return rcs; }
+    { const int rcf = flush_clear(c); if (rcf) return rcf; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    DrawArgs<Rec> a{};
+    a.n = n; a.fb = c->fb;
+    a.zbuf = (c->zbuf && c->zbuf_valid && (size_t)c->width * c->height <= c->cap_zbuf) ? c->zbuf : nullptr;
+    a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
+    a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
+    if (n <= small_n) {
+        launch_draw(c->stream, a, recs);
+        HIPCHK(c, hipGetLastError());
+        ++ps.scan_batches;
+        return B32_OK;
+    }
+    const uint32_t k = ps.slot;
+    ps.slot = (k + 1) % LINE_RING;
+    if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));
+    else HIPCHK(c, hipEventCreateWithFlags(&ps.ev[k], hipEventDisableTiming));
+    if (ps.cap_host[k] < n) {
+        if (ps.host[k]) HIPCHK(c, hipHostFree(ps.host[k]));
+        ps.host[k] = nullptr; ps.cap_host[k] = 0;
+        const size_t cap = (size_t)n + n / 4 + 64;
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&ps.host[k]), cap * sizeof(Rec), hipHostMallocDefault));
+        ps.cap_host[k] = cap;
+    }
+    std::memcpy(ps.host[k], recs, (size_t)n * sizeof(Rec));
+    int rc;
+    if ((rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(ps.ev[k], c->stream));
+    a.recs = ps.dev;
+    const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
+    if (!(c->route_off & route)) {
+        if (ntiles > ps.cap_tiles || !ps.counters) {                       // (zero between batches: every tile kernel zeroes its own counter)
+            const size_t cap = ntiles + ntiles / 4 + 16;
+            if (ps.counters) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(ps.counters)); HIPCHK(c, hipFree(ps.lists)); }
+            ps.counters = ps.lists = nullptr; ps.cap_tiles = 0;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&ps.counters), (cap + 2) * FILL_PAD * sizeof(uint32_t)));
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&ps.lists), cap * LINE_TILE_CAP * sizeof(uint32_t)));
+            HIPCHK(c, hipMemsetAsync(ps.counters, 0, (cap + 2) * FILL_PAD * sizeof(uint32_t), c->stream));
+            ps.cap_tiles = cap;
+        }
+        if (!ps.long_list) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&ps.long_list), LINE_LONG_CAP * sizeof(uint32_t)));
+        a.counters = ps.counters; a.lists = ps.lists; a.long_list = ps.long_list; a.parity = ps.parity;
+        ps.parity ^= 1u;
+        ++ps.tile_batches;
+    } else {
+        ++ps.scan_batches;
+    }
+    launch_draw(c->stream, a, nullptr);
+    HIPCHK(c, hipGetLastError());
+    return B32_OK;
+}
+
+extern "C" {
+
+// The line family of Framebuffer (render.rs:684-872), b32_lines.hip.
 int b32_draw_lines(b32_ctx* c, const B32Line* lines, uint32_t n) {
     if (!c || !c->fb || (n && !lines)) return B32_E_ARG;
     for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is drawn
@@ -264,63 +325,9 @@ int b32_draw_lines(b32_ctx* c, const B32Line* lines, uint32_t n) {
         const long long adx = std::llabs((long long)l.x1 - l.x0), ady = std::llabs((long long)l.y1 - l.y0);
         if (adx >= (1ll << 30) || ady >= (1ll << 30)) return B32_E_UNSUPPORTED;     // 2 * err overflows i32 (render.rs:735, 800)
     }
-    if (!n) return B32_OK;
-    (void)hipSetDevice(c->device);
-    { const int rcs = settle_before_write(c); if (rcs) return rcs; }
-    { const int rcf = flush_clear(c); if (rcf) return rcf; }
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    LineArgs a{};
-    a.n = n; a.fb = c->fb;
-    a.zbuf = (c->zbuf && c->zbuf_valid && (size_t)c->width * c->height <= c->cap_zbuf) ? c->zbuf : nullptr;
-    a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
-    a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
-    if (n <= LINE_SMALL) {
-        launch_lines(c->stream, a, lines);
-        HIPCHK(c, hipGetLastError());
-        ++c->line_scan_batches;
-        return B32_OK;
-    }
-    const uint32_t k = c->line_slot;
-    c->line_slot = (k + 1) % b32_ctx::LINE_RING;
-    if (c->ev_lines[k]) HIPCHK(c, hipEventSynchronize(c->ev_lines[k]));
-    else HIPCHK(c, hipEventCreateWithFlags(&c->ev_lines[k], hipEventDisableTiming));
-    if (c->cap_h_lines[k] < n) {
-        if (c->h_lines[k]) HIPCHK(c, hipHostFree(c->h_lines[k]));
-        c->h_lines[k] = nullptr; c->cap_h_lines[k] = 0;
-        const size_t cap = (size_t)n + n / 4 + 64;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_lines[k]), cap * sizeof(B32Line), hipHostMallocDefault));
-        c->cap_h_lines[k] = cap;
-    }
-    std::memcpy(c->h_lines[k], lines, (size_t)n * sizeof(B32Line));
-    int rc;
-    if ((rc = ensure(c, c->d_lines, c->cap_lines, (size_t)n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_lines, c->h_lines[k], (size_t)n * sizeof(B32Line), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_lines[k], c->stream));
-    a.lines = c->d_lines;
-    const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
-    if (!(c->route_off & B32_ROUTE_LINE_TILES)) {
-        if (ntiles > c->cap_line_tiles || !c->line_counters) {             // (zero between batches: every tile kernel zeroes its own counter)
-            const size_t cap = ntiles + ntiles / 4 + 16;
-            if (c->line_counters) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->line_counters)); HIPCHK(c, hipFree(c->line_lists)); }
-            c->line_counters = c->line_lists = nullptr; c->cap_line_tiles = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->line_counters), (cap + 2) * FILL_PAD * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->line_lists), cap * LINE_TILE_CAP * sizeof(uint32_t)));
-            HIPCHK(c, hipMemsetAsync(c->line_counters, 0, (cap + 2) * FILL_PAD * sizeof(uint32_t), c->stream));
-            c->cap_line_tiles = cap;
-        }
-        if (!c->line_long) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->line_long), LINE_LONG_CAP * sizeof(uint32_t)));
-        a.counters = c->line_counters; a.lists = c->line_lists; a.long_list = c->line_long; a.parity = c->line_parity;
-        c->line_parity ^= 1u;
-        ++c->line_tile_batches;
-    } else {
-        ++c->line_scan_batches;
-    }
-    launch_lines(c->stream, a, nullptr);
-    HIPCHK(c, hipGetLastError());
-    return B32_OK;
+    return draw_pass(c, c->lines, lines, n, LINE_SMALL, B32_ROUTE_LINE_TILES);
 }
-// The rest of Framebuffer's drawing methods (render.rs:631-971) and the line family, in array order, on the stream (b32_prims.hip).  The
-// same staging as b32_draw_lines: a batch of at most PRIM_SMALL travels in the kernel argument, a larger one through a pinned ring slot.
+// The rest of Framebuffer's drawing methods (render.rs:631-971) and the line family, b32_prims.hip.
 int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
     if (!c || !c->fb || (n && !prims)) return B32_E_ARG;
     for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is drawn
@@ -335,60 +342,7 @@ int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
             if (adx >= (1ll << 30) || ady >= (1ll << 30)) return B32_E_UNSUPPORTED;     // 2 * err overflows i32 (render.rs:735, 800)
         }
     }
-    if (!n) return B32_OK;
-    (void)hipSetDevice(c->device);
-    { const int rcs = settle_before_write(c); if (rcs) return rcs; }
-    { const int rcf = flush_clear(c); if (rcf) return rcf; }
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    PrimArgs a{};
-    a.n = n; a.fb = c->fb;
-    a.zbuf = (c->zbuf && c->zbuf_valid && (size_t)c->width * c->height <= c->cap_zbuf) ? c->zbuf : nullptr;
-    a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
-    a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
-    if (n <= PRIM_SMALL) {
-        launch_prims(c->stream, a, prims);
-        HIPCHK(c, hipGetLastError());
-        ++c->prim_scan_batches;
-        return B32_OK;
-    }
-    const uint32_t k = c->prim_slot;
-    c->prim_slot = (k + 1) % b32_ctx::LINE_RING;
-    if (c->ev_prims[k]) HIPCHK(c, hipEventSynchronize(c->ev_prims[k]));
-    else HIPCHK(c, hipEventCreateWithFlags(&c->ev_prims[k], hipEventDisableTiming));
-    if (c->cap_h_prims[k] < n) {
-        if (c->h_prims[k]) HIPCHK(c, hipHostFree(c->h_prims[k]));
-        c->h_prims[k] = nullptr; c->cap_h_prims[k] = 0;
-        const size_t cap = (size_t)n + n / 4 + 64;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_prims[k]), cap * sizeof(B32Prim), hipHostMallocDefault));
-        c->cap_h_prims[k] = cap;
-    }
-    std::memcpy(c->h_prims[k], prims, (size_t)n * sizeof(B32Prim));
-    int rc;
-    if ((rc = ensure(c, c->d_prims, c->cap_prims, (size_t)n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_prims, c->h_prims[k], (size_t)n * sizeof(B32Prim), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_prims[k], c->stream));
-    a.prims = c->d_prims;
-    const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
-    if (!(c->route_off & B32_ROUTE_PRIM_TILES)) {
-        if (ntiles > c->cap_prim_tiles || !c->prim_counters) {             // (zero between batches: every tile kernel zeroes its own counter)
-            const size_t cap = ntiles + ntiles / 4 + 16;
-            if (c->prim_counters) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->prim_counters)); HIPCHK(c, hipFree(c->prim_lists)); }
-            c->prim_counters = c->prim_lists = nullptr; c->cap_prim_tiles = 0;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_counters), (cap + 2) * FILL_PAD * sizeof(uint32_t)));
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_lists), cap * LINE_TILE_CAP * sizeof(uint32_t)));
-            HIPCHK(c, hipMemsetAsync(c->prim_counters, 0, (cap + 2) * FILL_PAD * sizeof(uint32_t), c->stream));
-            c->cap_prim_tiles = cap;
-        }
-        if (!c->prim_long) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->prim_long), LINE_LONG_CAP * sizeof(uint32_t)));
-        a.counters = c->prim_counters; a.lists = c->prim_lists; a.long_list = c->prim_long; a.parity = c->prim_parity;
-        c->prim_parity ^= 1u;
-        ++c->prim_tile_batches;
-    } else {
-        ++c->prim_scan_batches;
-    }
-    launch_prims(c->stream, a, nullptr);
-    HIPCHK(c, hipGetLastError());
-    return B32_OK;
+    return draw_pass(c, c->prims, prims, n, PRIM_SMALL, B32_ROUTE_PRIM_TILES);
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
     if (!c || !c->fb || !out || !dw || !dh || dw > 32768 || dh > 32768) return B32_E_ARG;
@@ -632,10 +586,10 @@ extern "C" unsigned long long b32_route_count(const b32_ctx* c, int which) {
     if (c && which == 11) return c->flag_join_frames;
     if (c && which == 12) return c->event_join_frames;
     if (c && which == 13) return c->poll_join_frames;
-    if (c && which == 14) return c->line_tile_batches;
-    if (c && which == 15) return c->line_scan_batches;
-    if (c && which == 16) return c->prim_tile_batches;
-    if (c && which == 17) return c->prim_scan_batches;
+    if (c && which == 14) return c->lines.tile_batches;
+    if (c && which == 15) return c->lines.scan_batches;
+    if (c && which == 16) return c->prims.tile_batches;
+    if (c && which == 17) return c->prims.scan_batches;
     return (c && which >= 0 && which < 8) ? c->routes[which] : 0ull;
 }
 extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {

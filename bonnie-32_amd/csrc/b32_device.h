@@ -464,31 +464,25 @@ __device__ __forceinline__ float wire_t_fast(float kf, float Nf, float rN) {
 }
 void launch_wire(hipStream_t s, const WireArgs& a, bool back, bool front, bool binned = false, Ctrl* wait_ctrl = nullptr, uint32_t wait_epoch = 0);   // wait_ctrl: see k_wire_table_clear
 void launch_wire_bin(hipStream_t s, const WireArgs& a, bool back, bool front, bool early);
-// Framebuffer line pass (b32_draw_lines, b32_lines.hip): 64 x LINE_TH tiles over the band, first tile row at band_y0.
+// The ordered tile pass of the Framebuffer drawing calls (b32_draw_pass.h): 64 x LINE_TH tiles over the band, first tile row at band_y0.
+// Two record types share it: B32Line (b32_draw_lines, b32_lines.hip) and B32Prim (b32_draw_prims, b32_prims.hip).
 constexpr uint32_t LINE_TH = 16;
-constexpr uint32_t LINE_SMALL = 64;            // batches of at most this many lines travel in the kernel argument (LineBatch): no copy
+constexpr uint32_t LINE_SMALL = 64;            // batches of at most this many lines travel in the kernel argument (DrawBatch): no copy
+constexpr uint32_t PRIM_SMALL = 48;            // ... and of at most this many primitives (1920 bytes)
 constexpr uint32_t LINE_TILE_CAP = 1024;       // entries per tile list of the tile route
-constexpr uint32_t LINE_LONG_CAP = 1024;       // lines whose box covers more than LINE_BIG_TILES tiles share one list
-struct LineArgs {
-    const B32Line* lines; uint32_t n;          // lines == nullptr: the batch is the kernel argument
+constexpr uint32_t LINE_LONG_CAP = 1024;       // records whose box covers more than DRAW_BIG_TILES tiles share one list
+template <class Rec>
+struct DrawArgs {
+    const Rec* recs; uint32_t n;               // recs == nullptr: the batch is the kernel argument
     uint32_t* fb; const float* zbuf;           // zbuf == nullptr: every depth is f32::MAX
     uint32_t width, band_y0, band_y1, tiles_x, tiles_y;
     // tile route (nullptr: every tile scans the whole batch in order): FILL_PAD words per counter -- the two long-list counters (one per
     // parity: a batch's tile kernel zeroes the other one for the next binned batch), then one per tile --, lists of LINE_TILE_CAP ids per tile
     uint32_t* counters; uint32_t* lists; uint32_t* long_list; uint32_t parity;
 };
-struct LineBatch { B32Line l[LINE_SMALL]; };
-void launch_lines(hipStream_t s, const LineArgs& a, const B32Line* small);   // small != nullptr: n <= LINE_SMALL lines passed by value
-// Framebuffer primitive pass (b32_draw_prims, b32_prims.hip): the line pass's tiles, caps and tile route for B32Prim batches.
-constexpr uint32_t PRIM_SMALL = 48;            // batches of at most this many primitives travel in the kernel argument (PrimBatch, 1920 bytes)
-struct PrimArgs {
-    const B32Prim* prims; uint32_t n;          // prims == nullptr: the batch is the kernel argument
-    uint32_t* fb; const float* zbuf;           // zbuf == nullptr: every depth is f32::MAX
-    uint32_t width, band_y0, band_y1, tiles_x, tiles_y;
-    uint32_t* counters; uint32_t* lists; uint32_t* long_list; uint32_t parity;   // as in LineArgs
-};
-struct PrimBatch { B32Prim p[PRIM_SMALL]; };
-void launch_prims(hipStream_t s, const PrimArgs& a, const B32Prim* small);   // small != nullptr: n <= PRIM_SMALL primitives passed by value
+template <class Rec, uint32_t N> struct DrawBatch { Rec r[N]; };
+void launch_draw(hipStream_t s, const DrawArgs<B32Line>& a, const B32Line* small);   // small != nullptr: n <= LINE_SMALL lines passed by value
+void launch_draw(hipStream_t s, const DrawArgs<B32Prim>& a, const B32Prim* small);   // small != nullptr: n <= PRIM_SMALL primitives passed by value
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

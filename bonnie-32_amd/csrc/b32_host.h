@@ -38,6 +38,22 @@ struct FrameSet {
     bool in_flight = false;                                  // a frame was enqueued on this set since the last b32_frame_finish
 };
 
+// What one ordered tile pass (b32_draw_pass.h) keeps in the context.  A batch too large for the kernel argument is copied into a pinned
+// ring slot (the caller may reuse its array at once) and from there to `dev` on the stream; a slot is written again LINE_RING batches
+// later, after its copy has left (normally long ago).  counters / lists / long_list: the tile route (DrawArgs).
+constexpr uint32_t LINE_RING = 4;
+template <class Rec>
+struct DrawPassState {
+    Rec* host[LINE_RING] = {}; size_t cap_host[LINE_RING] = {}; hipEvent_t ev[LINE_RING] = {}; uint32_t slot = 0;
+    Rec* dev = nullptr; size_t cap_dev = 0;
+    uint32_t *counters = nullptr, *lists = nullptr, *long_list = nullptr; size_t cap_tiles = 0; uint32_t parity = 0;
+    unsigned long long tile_batches = 0, scan_batches = 0;
+    void release() {
+        for (uint32_t k = 0; k < LINE_RING; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (host[k]) (void)hipHostFree(host[k]); }
+        for (void* p : { (void*)dev, (void*)counters, (void*)lists, (void*)long_list }) if (p) (void)hipFree(p);
+    }
+};
+
 struct b32_ctx {
     int device = 0;
     int n_cu = 256;
@@ -153,17 +169,8 @@ struct b32_ctx {
     uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0;     // tile route of the wireframe phases (WireArgs)
     unsigned long long wire_grid = 0;                                                       // tile grid the (self-resetting) counters belong to
     unsigned long long wire_tile_frames = 0;
-    // line pass (b32_draw_lines): batches of more than LINE_SMALL lines are copied into a pinned ring slot, then to d_lines on the stream
-    static constexpr uint32_t LINE_RING = 4;
-    B32Line* h_lines[LINE_RING] = {}; size_t cap_h_lines[LINE_RING] = {}; hipEvent_t ev_lines[LINE_RING] = {}; uint32_t line_slot = 0;
-    B32Line* d_lines = nullptr; size_t cap_lines = 0;
-    uint32_t *line_counters = nullptr, *line_lists = nullptr, *line_long = nullptr; size_t cap_line_tiles = 0; uint32_t line_parity = 0;
-    unsigned long long line_tile_batches = 0, line_scan_batches = 0;
-    // primitive pass (b32_draw_prims): the same ring and tile route for batches of more than PRIM_SMALL primitives
-    B32Prim* h_prims[LINE_RING] = {}; size_t cap_h_prims[LINE_RING] = {}; hipEvent_t ev_prims[LINE_RING] = {}; uint32_t prim_slot = 0;
-    B32Prim* d_prims = nullptr; size_t cap_prims = 0;
-    uint32_t *prim_counters = nullptr, *prim_lists = nullptr, *prim_long = nullptr; size_t cap_prim_tiles = 0; uint32_t prim_parity = 0;
-    unsigned long long prim_tile_batches = 0, prim_scan_batches = 0;
+    DrawPassState<B32Line> lines;                                 // b32_draw_lines
+    DrawPassState<B32Prim> prims;                                 // b32_draw_prims
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl* d_ctrl = nullptr; uint32_t* d_consts = nullptr; Ctrl h_ctrl{}; Stamps h_stamps{};   // (d_ctrl: Ctrl followed by Stamps)
