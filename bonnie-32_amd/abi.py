@@ -51,6 +51,12 @@ PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"
 assert PRIM_DTYPE.itemsize == 40
 PRIM_LINE_BLENDED, PRIM_CIRCLE, PRIM_CIRCLE_ALPHA, PRIM_THICK_LINE, PRIM_RECT, PRIM_FILLED_RECT = range(5, 11)
 
+# B32WorldItem (world-space overlay items, b32_draw_world): kind = LINE_* / PRIM_* 0..8, flags = WORLD_CLIP_NEAR
+WORLD_ITEM_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("size", "<i4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("blend", "u1"),
+                             ("kind", "u1"), ("alpha", "u1"), ("mode", "u1"), ("flags", "u1"), ("_pad", "u1", 4)])
+assert WORLD_ITEM_DTYPE.itemsize == 40
+WORLD_CLIP_NEAR = 1
+
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -62,6 +68,10 @@ class B32IndexedTexture(C.Structure):
 class B32Camera(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("basis_x", C.c_float * 3), ("basis_y", C.c_float * 3),
                 ("basis_z", C.c_float * 3)]
+
+
+class B32Ortho(C.Structure):
+    _fields_ = [("zoom", C.c_float), ("center_x", C.c_float), ("center_y", C.c_float)]
 
 
 class B32Light(C.Structure):
@@ -144,6 +154,11 @@ SYMBOLS = [
     ("b32_present_nearest", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     ("b32_draw_lines", C.c_int, [_P, _P, C.c_uint32]),
     ("b32_draw_prims", C.c_int, [_P, _P, C.c_uint32]),
+    ("b32_draw_world", C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    ("b32_draw_floor_grid", C.c_int, [_P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    ("b32_floor_grid_items", C.c_int, [C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_world_project_batch", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    ("b32_world_counts", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

@@ -57,7 +57,9 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : { c->ev_main, c->ev_wbin, c->ev_setup, c->alt[0].ev_setup, c->alt[1].ev_setup }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    c->lines.release(); c->prims.release();
+    c->lines.release(); c->prims.release(); c->world.release();
+    if (c->world_counts) (void)hipFree(c->world_counts);
+    for (hipEvent_t e : c->world_ev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
@@ -253,27 +255,29 @@ int b32_draw_star_diamonds(b32_ctx* c, const int32_t* cx, const int32_t* cy, con
 }
 }  // extern "C"
 
-// A validated batch through the ordered tile pass (b32_draw_pass.h), in array order, on the stream.  A batch of at most `small_n` records
-// travels in the kernel argument; a larger one is copied into a pinned ring slot of `ps` and from there to the device on the stream,
-// and takes the tile route unless `route` is switched off.
-template <class Rec>
-static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n, uint32_t small_n, uint32_t route) {
-    if (!n) return B32_OK;
+// The ordered tile pass (b32_draw_pass.h) on the stream, in three steps that b32_draw_lines / b32_draw_prims (records from the host) and
+// b32_draw_world (records a kernel wrote on the device) put together.
+
+// Before a pass: a pending frame settled (safe mode), a deferred clear flushed.
+static int draw_enter(b32_ctx* c) {
     (void)hipSetDevice(c->device);
     { const int rcs = settle_before_write(c); if (rcs) return rcs; }
-    { const int rcf = flush_clear(c); if (rcf) return rcf; }
-    if (c->band_y1 <= c->band_y0) return B32_OK;
+    return flush_clear(c);
+}
+// What every launch of a pass over the (non-empty) band needs.
+template <class Rec>
+static DrawArgs<Rec> draw_args(b32_ctx* c, uint32_t n) {
     DrawArgs<Rec> a{};
     a.n = n; a.fb = c->fb;
     a.zbuf = (c->zbuf && c->zbuf_valid && (size_t)c->width * c->height <= c->cap_zbuf) ? c->zbuf : nullptr;
     a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
     a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
-    if (n <= small_n) {
-        launch_draw(c->stream, a, recs);
-        HIPCHK(c, hipGetLastError());
-        ++ps.scan_batches;
-        return B32_OK;
-    }
+    return a;
+}
+// Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there to ps.dev
+// on the stream.
+template <class Rec>
+static int stage_records(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n) {
     const uint32_t k = ps.slot;
     ps.slot = (k + 1) % LINE_RING;
     if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));
@@ -290,9 +294,16 @@ static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32
     if ((rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
     HIPCHK(c, hipMemcpyAsync(ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(ps.ev[k], c->stream));
-    a.recs = ps.dev;
+    return B32_OK;
+}
+// Bin and draw records that are already on the device (a.recs, behind whatever wrote them on the stream): the tile route if `tiles` and
+// `route` is not switched off, else every tile scans the whole batch.  *tiled (nullable): which of the two it was.
+template <class Rec>
+static int draw_resident(b32_ctx* c, DrawPassState<Rec>& ps, DrawArgs<Rec>& a, bool tiles, uint32_t route, bool* tiled = nullptr) {
     const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
-    if (!(c->route_off & route)) {
+    const bool binned = tiles && !(c->route_off & route);
+    if (tiled) *tiled = binned;
+    if (binned) {
         if (ntiles > ps.cap_tiles || !ps.counters) {                       // (zero between batches: every tile kernel zeroes its own counter)
             const size_t cap = ntiles + ntiles / 4 + 16;
             if (ps.counters) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(ps.counters)); HIPCHK(c, hipFree(ps.lists)); }
@@ -311,6 +322,50 @@ static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32
     }
     launch_draw(c->stream, a, nullptr);
     HIPCHK(c, hipGetLastError());
+    return B32_OK;
+}
+
+// A validated batch of host records through the pass, in array order.  A batch of at most `small_n` records travels in the kernel
+// argument; a larger one is staged, and takes the tile route unless `route` is switched off.
+template <class Rec>
+static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n, uint32_t small_n, uint32_t route) {
+    if (!n) return B32_OK;
+    { const int rc = draw_enter(c); if (rc) return rc; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    DrawArgs<Rec> a = draw_args<Rec>(c, n);
+    if (n <= small_n) {
+        launch_draw(c->stream, a, recs);
+        HIPCHK(c, hipGetLastError());
+        ++ps.scan_batches;
+        return B32_OK;
+    }
+    { const int rc = stage_records(c, ps, recs, n); if (rc) return rc; }
+    a.recs = ps.dev;
+    return draw_resident(c, ps, a, true, route);
+}
+
+// ------------------------------------------------------------------ world-space items (b32_world.hip)
+static int world_check(const B32WorldItem* items, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is enqueued
+        const B32WorldItem& it = items[i];
+        const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
+        if (it.kind > B32_PRIM_THICK_LINE || (it.flags & ~B32_WORLD_CLIP_NEAR) || (circle && it.flags) ||
+            (it.kind == B32_PRIM_LINE_BLENDED && it.mode > B32_BLEND_ERASE)) return B32_E_ARG;
+        if (circle && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;      // r * r (render.rs:632)
+    }
+    return B32_OK;
+}
+static int world_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, WorldArgs& wa) {
+    if (!c->world_counts) {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->world_counts), 3 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->world_counts, 0, 3 * sizeof(unsigned long long), c->stream));
+    }
+    wa = WorldArgs{};
+    wa.n = n; wa.counts = c->world_counts;
+    for (int k = 0; k < 3; ++k) { wa.pos[k] = cam->position[k]; wa.bx[k] = cam->basis_x[k]; wa.by[k] = cam->basis_y[k]; wa.bz[k] = cam->basis_z[k]; }
+    wa.vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f;                        // math.rs:524-525
+    wa.half_w = (float)w / 2.0f; wa.half_h = (float)h / 2.0f;
+    if (ortho) { wa.has_ortho = 1u; wa.zoom = ortho->zoom; wa.center_x = ortho->center_x; wa.center_y = ortho->center_y; }
     return B32_OK;
 }
 
@@ -343,6 +398,77 @@ int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
         }
     }
     return draw_pass(c, c->prims, prims, n, PRIM_SMALL, B32_ROUTE_PRIM_TILES);
+}
+// World-space items (draw.rs:12-67, math.rs:503-652): projected by k_world_project into the primitive pass's device record buffer, then
+// binned and drawn from there like any other primitive batch.  The records never visit the host.
+int b32_draw_world(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32WorldItem* items, uint32_t n) {
+    if (!c || !c->fb || !cam || (n && !items)) return B32_E_ARG;
+    { const int rc = world_check(items, n); if (rc) return rc; }
+    if (!n) return B32_OK;
+    { const int rc = draw_enter(c); if (rc) return rc; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    WorldArgs wa;
+    int rc;
+    if ((rc = world_args(c, cam, ortho, c->width, c->height, n, wa))) return rc;
+    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)n))) return rc;
+    wa.out = c->prims.dev;
+    if (n > WORLD_SMALL) {
+        if ((rc = stage_records(c, c->world, items, n))) return rc;
+        wa.items = c->world.dev;
+    }
+    const bool timed = c->profile_level >= 1;
+    if (timed) {
+        for (hipEvent_t& e : c->world_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+        HIPCHK(c, hipEventRecord(c->world_ev[0], c->stream));
+    }
+    launch_world_project(c->stream, wa, n > WORLD_SMALL ? nullptr : items);
+    HIPCHK(c, hipGetLastError());
+    if (timed) { HIPCHK(c, hipEventRecord(c->world_ev[1], c->stream)); c->world_timed = true; }
+    DrawArgs<B32Prim> a = draw_args<B32Prim>(c, n);
+    a.recs = c->prims.dev;
+    bool tiled = false;
+    if ((rc = draw_resident(c, c->prims, a, n > PRIM_SMALL, B32_ROUTE_PRIM_TILES, &tiled))) return rc;
+    ++(tiled ? c->world_tile_batches : c->world_scan_batches);
+    return B32_OK;
+}
+int b32_draw_floor_grid(b32_ctx* c, const B32Camera* cam, float y, float spacing, float extent,
+                        const uint8_t grid_rgbb[4], const uint8_t x_axis_rgbb[4], const uint8_t z_axis_rgbb[4]) {
+    if (!c || !c->fb || !cam) return B32_E_ARG;
+    uint32_t n = 0;
+    int rc;
+    if ((rc = b32_floor_grid_items(y, spacing, extent, grid_rgbb, x_axis_rgbb, z_axis_rgbb, nullptr, 0, &n))) return rc;
+    std::vector<B32WorldItem> items(n);
+    if ((rc = b32_floor_grid_items(y, spacing, extent, grid_rgbb, x_axis_rgbb, z_axis_rgbb, items.data(), n, &n))) return rc;
+    return b32_draw_world(c, cam, nullptr, items.data(), n);
+}
+int b32_world_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32WorldItem* items, uint32_t n,
+                            uint32_t w, uint32_t h, B32Prim* out) {
+    if (!c || !cam || (n && (!items || !out)) || w == 0 || h == 0 || w > 16384 || h > 16384) return B32_E_ARG;
+    { const int rc = world_check(items, n); if (rc) return rc; }
+    if (!n) return B32_OK;
+    (void)hipSetDevice(c->device);
+    WorldArgs wa;
+    int rc;
+    if ((rc = world_args(c, cam, ortho, w, h, n, wa))) return rc;
+    B32WorldItem* d_items = nullptr; B32Prim* d_out = nullptr;
+    Scratch tmp(c);
+    if ((rc = tmp.upload(items, (size_t)n, &d_items))) return rc;
+    if ((rc = tmp.alloc(&d_out, (size_t)n))) return rc;
+    wa.items = d_items; wa.out = d_out;
+    launch_world_project(c->stream, wa, nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
+}
+int b32_world_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected) {
+    if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    unsigned long long h[3] = { 0, 0, 0 };
+    if (c->world_counts) HIPCHK(c, hipMemcpyAsync(h, c->world_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
+    return B32_OK;
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
     if (!c || !c->fb || !out || !dw || !dh || dw > 32768 || dh > 32768) return B32_E_ARG;
@@ -561,11 +687,16 @@ int b32_device_constants(b32_ctx* c, const char** names, uint32_t* bits, uint8_t
 int b32_last_kernel_times(b32_ctx* c, const char** names, float* ms, uint32_t cap) {
     if (!c || !names || !ms) return 0;
     static const char* const kNames[5] = { "setup", "sort", "bin", "cover", "shade" };
-    if (!c->phase_frames) return 0;
     uint32_t k = 0;
-    for (int p = 0; p < 5 && k < cap; ++p) {
+    for (int p = 0; c->phase_frames && p < 5 && k < cap; ++p) {
         if (p != 3 && c->phase_level < 2) continue;
         names[k] = kNames[p]; ms[k] = c->phase_ms[p]; ++k;
+    }
+    // the projection kernel of the last b32_draw_world enqueued while profiling was on (waits for it)
+    float world_ms = 0.0f;
+    if (c->world_timed && k < cap && hipEventSynchronize(c->world_ev[1]) == hipSuccess &&
+        hipEventElapsedTime(&world_ms, c->world_ev[0], c->world_ev[1]) == hipSuccess) {
+        names[k] = "world_project"; ms[k] = world_ms; ++k;
     }
     return (int)k;
 }
@@ -590,6 +721,8 @@ extern "C" unsigned long long b32_route_count(const b32_ctx* c, int which) {
     if (c && which == 15) return c->lines.scan_batches;
     if (c && which == 16) return c->prims.tile_batches;
     if (c && which == 17) return c->prims.scan_batches;
+    if (c && which == 18) return c->world_tile_batches;
+    if (c && which == 19) return c->world_scan_batches;
     return (c && which >= 0 && which < 8) ? c->routes[which] : 0ull;
 }
 extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {
@@ -601,6 +734,7 @@ extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {
 extern "C" int b32_set_profiling(b32_ctx* c, int level) {
     if (!c) return B32_E_ARG;
     c->profile_level = level < 0 ? 0 : (level > 2 ? 2 : level);
+    if (!c->profile_level) c->world_timed = false;      // (b32_last_kernel_times no longer reports "world_project")
     c->prof_seq = 0;
     if (c->profile_level >= 1 && !c->ev_created) {      // (here, not in the first profiled frame: 384 hipEventCreate calls are ~0.2 ms of host time)
         (void)hipSetDevice(c->device);

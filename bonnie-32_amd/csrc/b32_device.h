@@ -483,6 +483,17 @@ struct DrawArgs {
 template <class Rec, uint32_t N> struct DrawBatch { Rec r[N]; };
 void launch_draw(hipStream_t s, const DrawArgs<B32Line>& a, const B32Line* small);   // small != nullptr: n <= LINE_SMALL lines passed by value
 void launch_draw(hipStream_t s, const DrawArgs<B32Prim>& a, const B32Prim* small);   // small != nullptr: n <= PRIM_SMALL primitives passed by value
+// World-space items projected into B32Prim records on the device (b32_draw_world, b32_world.hip): one lane per item, record i of `out`
+// from item i.  counts: items drawn, dropped (the reference draws nothing), rejected (b32_draw_prims's extent / centre rules) -- added to.
+constexpr uint32_t WORLD_SMALL = 48;           // batches of at most this many items travel in the kernel argument (1920 bytes)
+struct WorldArgs {
+    const B32WorldItem* items; uint32_t n;     // items == nullptr: the batch is the kernel argument
+    B32Prim* out; unsigned long long* counts;
+    float pos[3], bx[3], by[3], bz[3];         // Camera
+    float vs, half_w, half_h;                  // (min(w, h) as f32 / 2.0) * 0.75, w as f32 / 2.0, h as f32 / 2.0 (math.rs:524-531)
+    float zoom, center_x, center_y; uint32_t has_ortho;
+};
+void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);   // small != nullptr: n <= WORLD_SMALL items passed by value
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

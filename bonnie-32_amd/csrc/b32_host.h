@@ -171,6 +171,13 @@ struct b32_ctx {
     unsigned long long wire_tile_frames = 0;
     DrawPassState<B32Line> lines;                                 // b32_draw_lines
     DrawPassState<B32Prim> prims;                                 // b32_draw_prims
+    // b32_draw_world: the items' pinned ring and device copy (of DrawPassState only the staging half is used -- the projected records are
+    // written into prims.dev and drawn as a primitive batch); drawn / dropped / rejected on the device; HIP events around the last
+    // projection kernel enqueued while profiling was on (b32_last_kernel_times "world_project")
+    DrawPassState<B32WorldItem> world;
+    unsigned long long* world_counts = nullptr;
+    unsigned long long world_tile_batches = 0, world_scan_batches = 0;
+    hipEvent_t world_ev[2] = {}; bool world_timed = false;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl* d_ctrl = nullptr; uint32_t* d_consts = nullptr; Ctrl h_ctrl{}; Stamps h_stamps{};   // (d_ctrl: Ctrl followed by Stamps)

@@ -1,0 +1,168 @@
+// b32_world.hip -- world-space overlay items projected into B32Prim records on the device (b32_draw_world), and the floor grid's segments.
+//
+// Reference: every overlay starts from world positions.  draw_3d_line_clipped (rasterizer/draw.rs:12-67) clips a segment against the near
+// plane in world space, projects both ends with world_to_screen (math.rs:503-534), casts with `as i32` and calls fb.draw_line; the modeler
+// projects with world_to_screen_with_ortho[_depth] (math.rs:538-617) and calls draw_line_3d[_alpha] / draw_circle[_alpha].  Whether a
+// clipped segment is drawn at all can hang on the last bit of p0 + (p1 - p0) * t: the clipped end is projected again and answers None when
+// its camera z comes out <= 0.1.
+//
+// GPU form: one lane per item, the reference's expressions in the reference's order (f32, no contraction, Vec3::dot = (x*ox + y*oy) + z*oz,
+// f2i32_sat = `as i32`).  Record i is written from item i, so the array order is the reference's call order; an item that draws nothing
+// becomes a circle of radius -1, which the tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of
+// b32_prims.hip reads them where this kernel wrote them.
+#include "b32_device.h"
+#include <cmath>
+
+namespace b32 {
+
+struct WorldBatch { B32WorldItem r[WORLD_SMALL]; };
+static_assert(sizeof(B32WorldItem) == 40 && sizeof(WorldBatch) + sizeof(WorldArgs) <= 2048, "B32WorldItem layout / kernel argument size");
+
+constexpr float WORLD_NEAR = 0.1f;                  // NEAR_PLANE, math.rs:155; the `cam_z <= 0.1` of math.rs:516, 560, 602, 634
+
+// Vec3::dot, math.rs:23-25
+__device__ __forceinline__ float world_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// world_to_screen[_with_depth] (ortho == false) and world_to_screen_with_ortho[_depth], math.rs:503-652: false = None
+__device__ __forceinline__ bool world_point(const WorldArgs& a, const float* p, bool ortho, float& sx, float& sy, float& z) {
+    const float rel[3] = { p[0] - a.pos[0], p[1] - a.pos[1], p[2] - a.pos[2] };
+    const float cam_x = world_dot(rel, a.bx), cam_y = world_dot(rel, a.by), cam_z = world_dot(rel, a.bz);
+    z = cam_z;
+    if (ortho) {
+        sx = (cam_x - a.center_x) * a.zoom + a.half_w;
+        sy = -(cam_y - a.center_y) * a.zoom + a.half_h;
+        return true;
+    }
+    if (cam_z <= WORLD_NEAR) return false;
+    const float denom = cam_z + 5.0f;               // ud = 5.0, us = ud - 1.0
+    sx = (cam_x * 4.0f / denom) * a.vs + a.half_w;
+    sy = (cam_y * 4.0f / denom) * a.vs + a.half_h;
+    return true;
+}
+
+// item i of the batch (`live`: i < a.n; the other lanes only take part in the counting)
+__device__ __forceinline__ void world_project(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live) {
+    __shared__ uint32_t tally[3];                               // the workgroup's drawn / dropped / rejected
+    if (threadIdx.x < 3u) tally[threadIdx.x] = 0u;
+    __syncthreads();
+    const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
+    const bool depth = it.kind >= B32_LINE_3D && it.kind <= B32_LINE_3D_ALPHA;
+    float p0[3] = { it.p0[0], it.p0[1], it.p0[2] }, p1[3] = { it.p1[0], it.p1[1], it.p1[2] };
+    bool ortho = a.has_ortho != 0u, some = true;
+    if (!circle && (it.flags & B32_WORLD_CLIP_NEAR)) {          // draw_3d_line_clipped, draw.rs:19-42 (the projection after it takes no ortho)
+        ortho = false;
+        const float rel0[3] = { p0[0] - a.pos[0], p0[1] - a.pos[1], p0[2] - a.pos[2] };
+        const float rel1[3] = { p1[0] - a.pos[0], p1[1] - a.pos[1], p1[2] - a.pos[2] };
+        const float z0 = world_dot(rel0, a.bz), z1 = world_dot(rel1, a.bz);
+        if (z0 <= WORLD_NEAR && z1 <= WORLD_NEAR) {
+            some = false;
+        } else if (z0 <= WORLD_NEAR || z1 <= WORLD_NEAR) {
+            const float t = (WORLD_NEAR - z0) / (z1 - z0);
+            float q[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) q[k] = p0[k] + (p1[k] - p0[k]) * t;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { if (z0 <= WORLD_NEAR) p0[k] = q[k]; else p1[k] = q[k]; }
+        }
+    }
+    float sx0 = 0.0f, sy0 = 0.0f, cz0 = 0.0f, sx1 = 0.0f, sy1 = 0.0f, cz1 = 0.0f;
+    if (some) some = world_point(a, p0, ortho, sx0, sy0, cz0);
+    if (some && !circle) some = world_point(a, p1, ortho, sx1, sy1, cz1);
+
+    B32Prim o{};
+    o.kind = B32_PRIM_CIRCLE; o.size = -1;                      // draws nothing
+    uint32_t which = 1u;                                        // dropped: the reference draws nothing
+    if (some) {
+        const int32_t x0 = f2i32_sat(sx0), y0 = f2i32_sat(sy0);
+        const int32_t x1 = circle ? 0 : f2i32_sat(sx1), y1 = circle ? 0 : f2i32_sat(sy1);
+        constexpr long long LIM = 1ll << 30;                    // what b32_draw_prims answers B32_E_UNSUPPORTED for
+        const bool bad = circle ? (llabs((long long)x0) >= LIM || llabs((long long)y0) >= LIM)
+                                : (llabs((long long)x1 - x0) >= LIM || llabs((long long)y1 - y0) >= LIM);
+        which = bad ? 2u : 0u;
+        if (!bad) {
+            o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
+            // (a NaN depth as one fixed quiet NaN: payloads are unspecified, and every NaN fails every depth test alike)
+            o.z0 = !depth ? 0.0f : (cz0 != cz0 ? __uint_as_float(0x7FC00000u) : cz0);
+            o.z1 = !depth ? 0.0f : (cz1 != cz1 ? __uint_as_float(0x7FC00000u) : cz1);
+            o.size = it.size;
+            o.r = it.r; o.g = it.g; o.b = it.b; o.blend = it.blend;
+            o.kind = it.kind; o.alpha = it.alpha; o.mode = it.mode;
+        }
+    }
+    if (live) a.out[i] = o;
+    // One add per wave into LDS, one per workgroup and counter into memory: 100 000 single adds to one address take a millisecond.
+    // (integer sums: the totals do not depend on the order of the adds)
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k) {
+        const unsigned long long m = __ballot(live && which == k);
+        if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&tally[k], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < 3u && tally[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+}
+
+// a.n <= WORLD_SMALL items out of the kernel argument: one workgroup
+__global__ __launch_bounds__(256) void k_world_project_small(WorldArgs a, WorldBatch batch) {
+    const uint32_t i = threadIdx.x;
+    const bool live = i < a.n;
+    world_project(a, live ? batch.r[i] : B32WorldItem{}, i, live);
+}
+__global__ __launch_bounds__(256) void k_world_project(WorldArgs a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < a.n;
+    world_project(a, live ? a.items[i] : B32WorldItem{}, i, live);
+}
+
+void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small) {
+    if (!a.n) return;
+    if (small) {
+        WorldBatch batch{};
+        for (uint32_t i = 0; i < a.n && i < WORLD_SMALL; ++i) batch.r[i] = small[i];
+        hipLaunchKernelGGL(k_world_project_small, dim3(1), dim3(256), 0, s, a, batch);
+        return;
+    }
+    hipLaunchKernelGGL(k_world_project, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+}
+
+}  // namespace b32
+
+// draw_floor_grid's two while loops (draw.rs:81-135) as items, in call order.  An accumulation that does not advance is the reference's
+// endless loop: found here, never by looping.
+extern "C" int b32_floor_grid_items(float y, float spacing, float extent, const uint8_t grid_rgbb[4], const uint8_t x_axis_rgbb[4],
+                                    const uint8_t z_axis_rgbb[4], B32WorldItem* out, uint32_t cap, uint32_t* n) {
+    if (!n || !grid_rgbb || !x_axis_rgbb || !z_axis_rgbb) return B32_E_ARG;
+    *n = 0;
+    if (!std::isfinite(y) || !std::isfinite(spacing) || !std::isfinite(extent) || !(spacing > 0.0f)) return B32_E_ARG;
+    constexpr uint32_t MAX_SEGMENTS = 1u << 20;
+    const float segment_length = spacing;
+    uint32_t count = 0;
+    for (int pass = 0; pass < 2; ++pass) {                      // 0: X-parallel lines (fixed Z), 1: Z-parallel lines (fixed X)
+        float u = -extent;                                      // the fixed coordinate
+        while (u <= extent) {
+            const bool axis = std::fabs(u) < 0.001f;
+            const uint8_t* col = axis ? (pass == 0 ? z_axis_rgbb : x_axis_rgbb) : grid_rgbb;
+            float v = -extent;
+            while (v < extent) {
+                const float v_end = std::fmin(v + segment_length, extent);
+                if (count >= MAX_SEGMENTS) return B32_E_UNSUPPORTED;
+                if (out && count < cap) {
+                    B32WorldItem it{};
+                    it.p0[0] = pass == 0 ? v : u; it.p0[1] = y; it.p0[2] = pass == 0 ? u : v;
+                    it.p1[0] = pass == 0 ? v_end : u; it.p1[1] = y; it.p1[2] = pass == 0 ? u : v_end;
+                    it.r = col[0]; it.g = col[1]; it.b = col[2]; it.blend = col[3];
+                    it.kind = B32_LINE_2D; it.alpha = 255; it.flags = B32_WORLD_CLIP_NEAR;
+                    out[count] = it;
+                }
+                ++count;
+                const float next = v + segment_length;
+                if (!(next > v)) return B32_E_ARG;
+                v = next;
+            }
+            const float next = u + spacing;
+            if (!(next > u)) return B32_E_ARG;
+            u = next;
+        }
+    }
+    *n = count;
+    return B32_OK;
+}

@@ -134,8 +134,33 @@ public:
                         BlendMode mode = BlendMode::Opaque, float z0 = 0.0f, float z1 = 0.0f) {
         return B32Prim{ x0, y0, x1, y1, z0, z1, size, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, (uint8_t)mode, { 0, 0, 0, 0, 0 } };
     }
+    // world-space overlays, rasterizer/draw.rs:12-135 and math.rs:503-652: projected on the device (enqueued; several at once: draw_world /
+    // WorldBatch, in array order).  ortho: OrthoProjection as (zoom, center_x, center_y).
+    void draw_world(const std::vector<B32WorldItem>& items, const Camera& cam, const std::optional<Vec3>& ortho = std::nullopt) {
+        const B32Camera c = camera_of(cam);
+        const B32Ortho o = ortho ? B32Ortho{ ortho->x, ortho->y, ortho->z } : B32Ortho{ 0, 0, 0 };
+        check(b32_draw_world(ctx_, &c, ortho ? &o : nullptr, items.data(), (uint32_t)items.size()), "draw_world");
+    }
+    void draw_3d_line_clipped(const Camera& cam, Vec3 p0, Vec3 p1, Color c) { draw_world({ world_item(B32_LINE_2D, p0, p1, c, 0, 255, BlendMode::Opaque, B32_WORLD_CLIP_NEAR) }, cam); }
+    void draw_floor_grid(const Camera& cam, float y, float spacing, float extent, Color grid, Color x_axis, Color z_axis) {
+        const B32Camera c = camera_of(cam);
+        const uint8_t g[4] = { grid.r, grid.g, grid.b, (uint8_t)grid.blend }, xa[4] = { x_axis.r, x_axis.g, x_axis.b, (uint8_t)x_axis.blend },
+                      za[4] = { z_axis.r, z_axis.g, z_axis.b, (uint8_t)z_axis.blend };
+        check(b32_draw_floor_grid(ctx_, &c, y, spacing, extent, g, xa, za), "draw_floor_grid");
+    }
+    struct WorldCounts { uint64_t drawn = 0, dropped = 0, rejected = 0; };
+    WorldCounts world_counts() const { WorldCounts w; check(b32_world_counts(ctx_, &w.drawn, &w.dropped, &w.rejected), "world_counts"); return w; }
+    // one B32WorldItem (kinds B32_LINE_* / B32_PRIM_* 0..8; the circle kinds use p0 only)
+    static B32WorldItem world_item(uint8_t kind, Vec3 p0, Vec3 p1, Color c, int32_t size = 0, uint8_t alpha = 255, BlendMode mode = BlendMode::Opaque,
+                                   uint8_t flags = 0) {
+        return B32WorldItem{ { p0.x, p0.y, p0.z }, { p1.x, p1.y, p1.z }, size, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, (uint8_t)mode, flags, { 0, 0, 0, 0 } };
+    }
     b32_ctx* ctx() const { return ctx_; }
 private:
+    static B32Camera camera_of(const Camera& c) {
+        return { { c.position.x, c.position.y, c.position.z }, { c.basis_x.x, c.basis_x.y, c.basis_x.z }, { c.basis_y.x, c.basis_y.y, c.basis_y.z },
+                 { c.basis_z.x, c.basis_z.y, c.basis_z.z } };
+    }
     void draw_prim(const B32Prim& p) { check(b32_draw_prims(ctx_, &p, 1), "draw_prims"); }
     void draw_one(uint8_t kind, int32_t x0, int32_t y0, float z0, int32_t x1, int32_t y1, float z1, Color c, uint8_t alpha) {
         const B32Line l = { x0, y0, x1, y1, z0, z1, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, { 0, 0 } };
@@ -171,6 +196,30 @@ private:
     void add(uint8_t kind, A... args) { recs_.push_back(Framebuffer::prim(kind, args...)); }
     Framebuffer& fb_;
     std::vector<B32Prim> recs_;
+};
+
+// World-space overlay calls recorded in call order; flush(camera, ortho) projects and draws them with ONE b32_draw_world call.
+class WorldBatch {
+public:
+    explicit WorldBatch(Framebuffer& fb) : fb_(fb) {}
+    void line_clipped(Vec3 p0, Vec3 p1, Color c) { add(B32_LINE_2D, p0, p1, c, 0, 255, BlendMode::Opaque, B32_WORLD_CLIP_NEAR); }       // draw_3d_line_clipped
+    void line_clipped_3d(Vec3 p0, Vec3 p1, Color c) { add(B32_LINE_3D, p0, p1, c, 0, 255, BlendMode::Opaque, B32_WORLD_CLIP_NEAR); }    // editor/viewport_3d.rs:5783-5840
+    void line(Vec3 p0, Vec3 p1, Color c) { add(B32_LINE_2D, p0, p1, c); }
+    void line_alpha(Vec3 p0, Vec3 p1, Color c, uint8_t alpha) { add(B32_LINE_2D_ALPHA, p0, p1, c, 0, alpha); }
+    void line_3d(Vec3 p0, Vec3 p1, Color c) { add(B32_LINE_3D, p0, p1, c); }
+    void line_3d_overlay(Vec3 p0, Vec3 p1, Color c) { add(B32_LINE_3D_OVERLAY, p0, p1, c); }
+    void line_3d_alpha(Vec3 p0, Vec3 p1, Color c, uint8_t alpha) { add(B32_LINE_3D_ALPHA, p0, p1, c, 0, alpha); }
+    void line_blended(Vec3 p0, Vec3 p1, Color c, BlendMode mode) { add(B32_PRIM_LINE_BLENDED, p0, p1, c, 0, 255, mode); }
+    void thick_line(Vec3 p0, Vec3 p1, int32_t thickness, Color c) { add(B32_PRIM_THICK_LINE, p0, p1, c, thickness); }
+    void circle(Vec3 p, int32_t radius, Color c) { add(B32_PRIM_CIRCLE, p, Vec3{ 0, 0, 0 }, c, radius); }
+    void circle_alpha(Vec3 p, int32_t radius, Color c, uint8_t alpha) { add(B32_PRIM_CIRCLE_ALPHA, p, Vec3{ 0, 0, 0 }, c, radius, alpha); }
+    size_t size() const { return items_.size(); }
+    void flush(const Camera& cam, const std::optional<Vec3>& ortho = std::nullopt) { fb_.draw_world(items_, cam, ortho); items_.clear(); }
+private:
+    template <typename... A>
+    void add(uint8_t kind, A... args) { items_.push_back(Framebuffer::world_item(kind, args...)); }
+    Framebuffer& fb_;
+    std::vector<B32WorldItem> items_;
 };
 
 namespace detail {

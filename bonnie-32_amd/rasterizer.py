@@ -74,6 +74,7 @@ class Context:
 
     ROUTES = ("direct_bin", "inline_bin", "counting_sort", "keyed", "redraw_region", "redraw_global_sort", "redraw_pairs", "pipelined", "lds_atlas", "wire_tiles", "span_cover",
               "flag_join", "event_join", "poll_join", "line_tiles", "line_scan", "prim_tiles", "prim_scan")
+    WORLD_ROUTES = ("world_tiles", "world_scan")      # b32_route_count 18, 19: b32_draw_world batches (they count under prim_tiles / prim_scan too)
 
     ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER, ROUTE_LINE_TILES, ROUTE_PRIM_TILES = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384
 
@@ -190,7 +191,7 @@ class Context:
 
     def route_counts(self):
         """b32_route_count: how many frames of this context took each internal route (tests assert the targeted one ran)."""
-        return {n: int(self.lib.b32_route_count(self.h, i)) for i, n in enumerate(self.ROUTES)}
+        return {n: int(self.lib.b32_route_count(self.h, i)) for i, n in enumerate(self.ROUTES + self.WORLD_ROUTES)}
 
     def debug_inject(self, what):
         """b32_debug_inject: fault injection (1 = the next flag / join hand-over loses its flag; 2 = the next fused kernel does not publish its start)."""
@@ -439,6 +440,47 @@ class Framebuffer:
         """Framebuffer::draw_filled_rect (render.rs:954-971)"""
         self.draw_prims(prim(abi.PRIM_FILLED_RECT, x0, y0, x1, y1, color))
 
+    # ---- world-space overlays (rasterizer/draw.rs:12-135, math.rs:503-652): projected on the device, b32_draw_world
+    def draw_world(self, items, camera: T.Camera, ortho=None):
+        """b32_draw_world: every item of `items` (abi.WORLD_ITEM_DTYPE) projected on the device and drawn as the reference's calls in array
+        order; enqueued, no host synchronisation.  ortho: None (perspective) or (zoom, center_x, center_y)."""
+        arr = np.ascontiguousarray(items, dtype=abi.WORLD_ITEM_DTYPE).reshape(-1)
+        cam = camera.pack()
+        o = _pack_ortho(ortho)
+        _chk(self.ctx.lib.b32_draw_world(self.ctx.h, C.byref(cam), C.byref(o) if o is not None else None,
+                                         arr.ctypes.data if len(arr) else None, len(arr)), "draw_world")
+
+    def world_batch(self):
+        """A WorldBatch on this framebuffer: world-space calls recorded; flush(camera, ortho) draws them with one b32_draw_world call."""
+        return WorldBatch(self)
+
+    def draw_3d_line_clipped(self, camera: T.Camera, p0, p1, color: T.Color):
+        """draw_3d_line_clipped (draw.rs:12-67)"""
+        self.draw_world(world_item(abi.LINE_2D, p0, p1, color, flags=abi.WORLD_CLIP_NEAR), camera)
+
+    def draw_floor_grid(self, camera: T.Camera, y, spacing, extent, grid_color: T.Color, x_axis_color: T.Color, z_axis_color: T.Color):
+        """draw_floor_grid (draw.rs:81-135)"""
+        cam = camera.pack()
+        cols = [(C.c_uint8 * 4)(c.r, c.g, c.b, c.blend) for c in (grid_color, x_axis_color, z_axis_color)]
+        _chk(self.ctx.lib.b32_draw_floor_grid(self.ctx.h, C.byref(cam), float(y), float(spacing), float(extent), *cols), "draw_floor_grid")
+
+    def world_counts(self):
+        """b32_world_counts: (drawn, dropped, rejected) items this context has projected so far; synchronises."""
+        v = [C.c_uint64() for _ in range(3)]
+        _chk(self.ctx.lib.b32_world_counts(self.ctx.h, *[C.byref(x) for x in v]), "world_counts")
+        return tuple(int(x.value) for x in v)
+
+    def world_project_batch(self, items, camera: T.Camera, ortho=None, width=None, height=None):
+        """b32_world_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_world hands to the tile pass."""
+        arr = np.ascontiguousarray(items, dtype=abi.WORLD_ITEM_DTYPE).reshape(-1)
+        out = np.zeros(len(arr), abi.PRIM_DTYPE)
+        cam = camera.pack()
+        o = _pack_ortho(ortho)
+        _chk(self.ctx.lib.b32_world_project_batch(self.ctx.h, C.byref(cam), C.byref(o) if o is not None else None,
+                                                  arr.ctypes.data if len(arr) else None, len(arr), width or self.width, height or self.height,
+                                                  out.ctypes.data if len(arr) else None), "world_project_batch")
+        return out
+
     def present_nearest(self, dst_w, dst_h):
         """The presenter's nearest-neighbour upscale (game/renderer.rs:179-214) -> uint8 [dst_h, dst_w, 4]."""
         out = np.empty((dst_h, dst_w, 4), np.uint8)
@@ -515,6 +557,121 @@ def prim(kind, x0, y0, x1, y1, color: T.Color, z0=0.0, z1=0.0, size=0, alpha=255
     p["x0"], p["y0"], p["x1"], p["y1"], p["z0"], p["z1"], p["size"] = x0, y0, x1, y1, z0, z1, size
     p["r"], p["g"], p["b"], p["blend"], p["kind"], p["alpha"], p["mode"] = color.r, color.g, color.b, color.blend, kind, alpha, mode
     return p
+
+
+def _pack_ortho(ortho):
+    if ortho is None:
+        return None
+    zoom, cx, cy = ortho
+    return abi.B32Ortho(float(zoom), float(cx), float(cy))
+
+
+def world_item(kind, p0, p1, color: T.Color, size=0, alpha=255, mode=0, flags=0):
+    """One abi.WORLD_ITEM_DTYPE record."""
+    it = np.zeros(1, abi.WORLD_ITEM_DTYPE)
+    it["p0"], it["p1"], it["size"] = np.asarray(p0, np.float32), np.asarray(p1, np.float32), size
+    it["r"], it["g"], it["b"], it["blend"] = color.r, color.g, color.b, color.blend
+    it["kind"], it["alpha"], it["mode"], it["flags"] = kind, alpha, mode, flags
+    return it
+
+
+def floor_grid_items(y, spacing, extent, grid_color: T.Color, x_axis_color: T.Color, z_axis_color: T.Color):
+    """The segments of draw_floor_grid (draw.rs:81-135) in call order, as LINE_2D items with WORLD_CLIP_NEAR: what b32_floor_grid_items
+    builds in the library.  ValueError where the reference would not terminate; more than 2^20 segments: OverflowError."""
+    f32 = np.float32
+    y, spacing, extent = f32(y), f32(spacing), f32(extent)
+    if not (np.isfinite(y) and np.isfinite(spacing) and np.isfinite(extent) and spacing > 0):
+        raise ValueError("draw_floor_grid does not terminate for these arguments")
+    rows = []
+    for pas in (0, 1):                                            # 0: X-parallel lines (fixed Z), 1: Z-parallel lines (fixed X)
+        u = -extent
+        while u <= extent:
+            col = ((z_axis_color if pas == 0 else x_axis_color) if abs(u) < f32(0.001) else grid_color)
+            v = -extent
+            while v < extent:
+                v_end = min(f32(v + spacing), extent)
+                if len(rows) >= 1 << 20:
+                    raise OverflowError("more than 2^20 floor grid segments")
+                rows.append(((v, y, u), (v_end, y, u), col) if pas == 0 else ((u, y, v), (u, y, v_end), col))
+                nxt = f32(v + spacing)
+                if not nxt > v:
+                    raise ValueError("draw_floor_grid does not terminate: x + spacing == x")
+                v = nxt
+            nxt = f32(u + spacing)
+            if not nxt > u:
+                raise ValueError("draw_floor_grid does not terminate: z + spacing == z")
+            u = nxt
+    items = np.zeros(len(rows), abi.WORLD_ITEM_DTYPE)
+    if rows:
+        items["p0"] = np.array([r[0] for r in rows], f32); items["p1"] = np.array([r[1] for r in rows], f32)
+        for f in ("r", "g", "b", "blend"):
+            items[f] = [getattr(r[2], f) for r in rows]
+    items["kind"], items["alpha"], items["flags"] = abi.LINE_2D, 255, abi.WORLD_CLIP_NEAR
+    return items
+
+
+class WorldBatch:
+    """World-space overlay calls recorded in call order (the modeler's frame: hierarchy lines, depth-tested edges, a dot per vertex);
+    flush(camera, ortho) projects and draws them with ONE b32_draw_world call.  Positions are (x, y, z) in world space."""
+
+    def __init__(self, fb: "Framebuffer"):
+        self.fb = fb
+        self._items = []                                          # one tuple per call; the array is built once, in items()
+
+    def __len__(self):
+        return len(self._items)
+
+    def _add(self, kind, p0, p1, color: T.Color, size=0, alpha=255, mode=0, flags=0):
+        self._items.append((tuple(p0), tuple(p1), size, color.r, color.g, color.b, color.blend, kind, alpha, mode, flags, (0, 0, 0, 0)))
+
+    def line_clipped(self, p0, p1, color: T.Color):
+        """draw_3d_line_clipped (draw.rs:12-67)"""
+        self._add(abi.LINE_2D, p0, p1, color, flags=abi.WORLD_CLIP_NEAR)
+
+    def line_clipped_3d(self, p0, p1, color: T.Color):
+        """the same clip with depth (editor/viewport_3d.rs:5783-5840): world_to_screen_with_depth, draw_line_3d"""
+        self._add(abi.LINE_3D, p0, p1, color, flags=abi.WORLD_CLIP_NEAR)
+
+    def line(self, p0, p1, color: T.Color):
+        """world_to_screen_with_ortho on each end, draw_line"""
+        self._add(abi.LINE_2D, p0, p1, color)
+
+    def line_alpha(self, p0, p1, color: T.Color, alpha):
+        self._add(abi.LINE_2D_ALPHA, p0, p1, color, alpha=alpha)
+
+    def line_3d(self, p0, p1, color: T.Color):
+        """world_to_screen_with_ortho_depth on each end, draw_line_3d"""
+        self._add(abi.LINE_3D, p0, p1, color)
+
+    def line_3d_overlay(self, p0, p1, color: T.Color):
+        self._add(abi.LINE_3D_OVERLAY, p0, p1, color)
+
+    def line_3d_alpha(self, p0, p1, color: T.Color, alpha):
+        """... draw_line_3d_alpha (modeler/viewport.rs:1927-1951)"""
+        self._add(abi.LINE_3D_ALPHA, p0, p1, color, alpha=alpha)
+
+    def line_blended(self, p0, p1, color: T.Color, mode):
+        self._add(abi.PRIM_LINE_BLENDED, p0, p1, color, mode=mode)
+
+    def thick_line(self, p0, p1, thickness, color: T.Color):
+        self._add(abi.PRIM_THICK_LINE, p0, p1, color, size=thickness)
+
+    def circle(self, p, radius, color: T.Color):
+        """world_to_screen_with_ortho, draw_circle"""
+        self._add(abi.PRIM_CIRCLE, p, (0.0, 0.0, 0.0), color, size=radius)
+
+    def circle_alpha(self, p, radius, color: T.Color, alpha):
+        """world_to_screen_with_ortho, draw_circle_alpha (modeler/viewport.rs:1876-1880)"""
+        self._add(abi.PRIM_CIRCLE_ALPHA, p, (0.0, 0.0, 0.0), color, size=radius, alpha=alpha)
+
+    def items(self):
+        """The recorded batch (abi.WORLD_ITEM_DTYPE, call order)."""
+        return np.array(self._items, abi.WORLD_ITEM_DTYPE)
+
+    def flush(self, camera: T.Camera, ortho=None):
+        """Draws everything recorded (one b32_draw_world call) and starts an empty batch."""
+        items, self._items = self.items(), []
+        self.fb.draw_world(items, camera, ortho)
 
 
 class PrimBatch:

@@ -280,7 +280,9 @@ int b32_set_async_depth(b32_ctx* ctx, int deep);
  * pair, 12 by a cross-stream event (main and side stream of one priority), 13 those of 11 whose fused kernel polled the flag itself (the merged
  * draws of a batched frame: no launch and no event in front of the fill), 14 b32_draw_lines batches binned to tiles (B32_ROUTE_LINE_TILES),
  * 15 b32_draw_lines batches in which every tile scanned the whole batch in order (small batches, or the route switched off), 16 b32_draw_prims
- * batches binned to tiles (B32_ROUTE_PRIM_TILES), 17 b32_draw_prims batches in which every tile scanned the whole batch in order.
+ * batches binned to tiles (B32_ROUTE_PRIM_TILES), 17 b32_draw_prims batches in which every tile scanned the whole batch in order
+ * (b32_draw_world batches count under 16 / 17 too: they are primitive batches), 18 b32_draw_world batches binned to tiles, 19 b32_draw_world
+ * batches in which every tile scanned the whole batch.
  * Unknown `which` or null ctx: 0. */
 unsigned long long b32_route_count(const b32_ctx* ctx, int which);
 /* Switch internal routes OFF for the frames enqueued from now on (no reference counterpart: the results are identical on every route;
@@ -443,6 +445,57 @@ typedef struct B32Prim {
  * -> B32_E_UNSUPPORTED; for circles |radius| > 32767 or |x0|, |y0| >= 2^30 (r*r, dx*dx + dy*dy or cy +- r overflow i32 in the
  * reference) -> B32_E_UNSUPPORTED.  B32_PRIM_FILLED_RECT takes any i32.  n == 0: no-op. */
 int b32_draw_prims(b32_ctx* ctx, const B32Prim* prims, uint32_t n);
+
+/* World-space overlays (rasterizer/draw.rs:12-135, math.rs:503-652).  Every caller of the drawing methods above starts from world positions:
+ * it projects both ends with one of the world_to_screen functions, casts with `as i32` and calls fb.draw_*.  An item is one such call:
+ * it is projected ON THE DEVICE into the B32Prim of its kind, in array order, and the records go through the ordered tile pass of
+ * b32_draw_prims without visiting the host.  The arithmetic is the reference's, operation for operation (f32, no contraction,
+ * Vec3::dot = (x*ox + y*oy) + z*oz, Rust's saturating `as i32`).
+ *   line kinds (0..5, B32_PRIM_THICK_LINE), no flag: each end through world_to_screen_with_ortho (2-D kinds 0, 1, 5, 8; math.rs:538-575)
+ *     or world_to_screen_with_ortho_depth (3-D kinds 2, 3, 4; :580-617, z = camera z); nothing is drawn if either end is None.
+ *   line kinds with B32_WORLD_CLIP_NEAR: draw_3d_line_clipped's near-plane clip first (draw.rs:19-42), then world_to_screen (:503-534) or
+ *     world_to_screen_with_depth (:621-652); `ortho` is ignored, as the reference's clipped callers ignore it.  A clipped end can come
+ *     out at camera z <= 0.1 after rounding, and then the segment is not drawn -- as in the reference.
+ *   B32_PRIM_CIRCLE, B32_PRIM_CIRCLE_ALPHA: p0 through world_to_screen_with_ortho, radius `size`.
+ * ortho == NULL: the perspective branch (camera z <= 0.1 is None); else the orthographic one, which never answers None.
+ * One departure from the reference's bits, visible through the stage tap: a NaN depth (z0 / z1 of the 3-D kinds) is stored as the one
+ * quiet NaN 0x7FC00000.  NaN payloads are specified neither by Rust nor by IEEE 754, and every NaN fails every depth test alike. */
+typedef struct B32WorldItem {
+    float   p0[3], p1[3];       /* world positions; the circle kinds use p0 only */
+    int32_t size;               /* circles: radius; B32_PRIM_THICK_LINE: thickness */
+    uint8_t r, g, b, blend;     /* Color{r, g, b, blend}, as in B32Prim */
+    uint8_t kind;               /* what is drawn with the projected ends: B32_PRIM_* 0..8 (no rectangles) */
+    uint8_t alpha, mode;        /* as in B32Prim */
+    uint8_t flags;              /* B32_WORLD_CLIP_NEAR */
+    uint8_t _pad[4];
+} B32WorldItem;                 /* 40 bytes */
+#define B32_WORLD_CLIP_NEAR 1u
+typedef struct B32Ortho { float zoom, center_x, center_y; } B32Ortho;     /* OrthoProjection, types.rs:1432-1438 */
+/* Draws items[0..n) as the reference's calls one after another in array order, with b32_draw_prims's contract: enqueued on the
+ * context's stream behind everything enqueued before and ahead of everything after, a deferred clear flushed first, only rows of the
+ * band written, the z-buffer read and never written, `items` reusable as soon as the call returns, n == 0 a no-op, no host
+ * synchronisation.  An item that draws nothing becomes a record that draws nothing in its place (a circle of radius -1).
+ * The whole batch is checked first: kind > B32_PRIM_THICK_LINE, an unknown flag, the clip flag on a circle, B32_PRIM_LINE_BLENDED with
+ * mode > B32_BLEND_ERASE -> B32_E_ARG; a circle with |radius| > 32767 -> B32_E_UNSUPPORTED.  What else b32_draw_prims refuses (an extent
+ * or a circle centre >= 2^30) is only known after projection: such a record is turned into a no-op on the device and counted as
+ * `rejected`. */
+int b32_draw_world(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable */, const B32WorldItem* items, uint32_t n);
+/* draw_floor_grid (draw.rs:81-135): b32_floor_grid_items drawn with b32_draw_world. */
+int b32_draw_floor_grid(b32_ctx* ctx, const B32Camera* camera, float y, float spacing, float extent,
+                        const uint8_t grid_rgbb[4], const uint8_t x_axis_rgbb[4], const uint8_t z_axis_rgbb[4]);
+/* The segments of draw_floor_grid in the reference's call order, as B32_PRIM_LINE_2D items with B32_WORLD_CLIP_NEAR (host only, no
+ * context): the two while loops with their f32 accumulation (x += spacing, .min(extent)); a line with |z| < 0.001 takes z_axis_rgbb, one
+ * with |x| < 0.001 x_axis_rgbb (Color as r, g, b, blend).  *n = the number of segments; at most `cap` are written (out may be NULL).
+ * The reference does not terminate for spacing <= 0, a non-finite argument or a spacing so small that x + spacing == x: B32_E_ARG.
+ * More than 2^20 segments: B32_E_UNSUPPORTED. */
+int b32_floor_grid_items(float y, float spacing, float extent, const uint8_t grid_rgbb[4], const uint8_t x_axis_rgbb[4],
+                         const uint8_t z_axis_rgbb[4], B32WorldItem* out, uint32_t cap, uint32_t* n);
+/* Stage tap: the records b32_draw_world would hand to the tile pass for a width x height framebuffer, copied back (synchronous). */
+int b32_world_project_batch(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable */, const B32WorldItem* items,
+                            uint32_t n, uint32_t width, uint32_t height, B32Prim* out);
+/* Items projected by this context so far (b32_draw_world, b32_draw_floor_grid and the stage tap): drawn, dropped (the reference itself
+ * draws nothing: behind the camera, None) and rejected (see b32_draw_world).  Synchronises the stream. */
+int b32_world_counts(b32_ctx* ctx, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
@@ -474,7 +527,9 @@ int b32_device_constants(b32_ctx* ctx, const char** names, uint32_t* bits, uint8
                          uint8_t* unr_table257, int32_t* dither16);
 
 /* Per-kernel device time of the last finished frame (HIP events on the ctx stream), for bench.py.
- * names[i] points at static strings; returns the number of entries written (<= cap). */
+ * names[i] points at static strings; returns the number of entries written (<= cap).  While profiling is on (b32_set_profiling >= 1) the
+ * projection kernel of the last b32_draw_world is timed too and reported as a further entry "world_project" (the call waits for it);
+ * b32_set_profiling(ctx, 0) ends that. */
 int b32_last_kernel_times(b32_ctx* ctx, const char** names, float* ms, uint32_t cap);
 /* HIP-event instrumentation of the frames enqueued from now on: 0 = none (default for the async path),
  * 1 = events around the coverage kernel (the dominant one), 2 = events around every phase
