@@ -99,6 +99,13 @@ class B32MeshParams(C.Structure):
                 ("_pad", C.c_uint8), ("fog", B32Fog)]
 
 
+class B32Placement(C.Structure):
+    _fields_ = [("cos_f", C.c_float), ("sin_f", C.c_float), ("world_pos", C.c_float * 3)]
+
+
+assert C.sizeof(B32Placement) == 20
+
+
 class B32Timings(C.Structure):
     _fields_ = [("transform_ms", C.c_float), ("fog_ms", C.c_float), ("cull_ms", C.c_float), ("sort_ms", C.c_float),
                 ("draw_ms", C.c_float), ("wireframe_ms", C.c_float), ("triangles_drawn", C.c_uint32),
@@ -147,6 +154,9 @@ SYMBOLS = [
     ("b32_frame_end", C.c_int, [_P]),
     ("b32_frame_submit", C.c_int, [_P, _P, _P, C.POINTER(_P), _P, C.c_uint32]),
     ("b32_batch_count", C.c_ulonglong, [_P, C.c_int]),
+    ("b32_frame_add_scene_placed", C.c_int, [_P, _P, _P, _P]),
+    ("b32_frame_submit_placed", C.c_int, [_P, _P, _P, C.POINTER(_P), _P, _P, _P, C.c_uint32]),
+    ("b32_render_scene_15_placed_async", C.c_int, [_P, _P, _P, _P, _P]),
     ("b32_fb_clear_gradient", C.c_int, [_P] + [C.c_uint8] * 8),
     ("b32_fb_clear_transparent", C.c_int, [_P]),
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),

@@ -91,15 +91,21 @@ int b32_frame_begin(b32_ctx* c, const B32Camera* cam, const B32Settings* st) {
     c->batch_open = true;
     return B32_OK;
 }
-int b32_frame_add_scene(b32_ctx* c, b32_scene* sl, const B32MeshParams* p) {
+int b32_frame_add_scene(b32_ctx* c, b32_scene* sl, const B32MeshParams* p) { return b32_frame_add_scene_placed(c, sl, p, nullptr); }
+// ... with the placement of this draw (render_asset_parts, scene.rs:112-171).  It travels beside the mesh's row and never enters the merged
+// mesh, whose vertices stay in local space: the cache key (member slots and their generations) does not see it, and a slot added twenty times
+// is twenty members of the run, each with a row and a placement of its own.
+int b32_frame_add_scene_placed(b32_ctx* c, b32_scene* sl, const B32MeshParams* p, const B32Placement* place) {
     if (!c || !sl || !c->batch_open) return B32_E_ARG;
     b32_ctx::BatchEntry e{};
     e.slot = sl;
     e.row.ambient = p ? p->ambient : c->batch_st.ambient;
     const bool cull = p ? p->backface_cull != 0 : c->batch_st.backface_cull != 0;
     const bool fogged = p && p->has_fog;
-    e.row.flags = (cull ? 1u : 0u) | (fogged ? 2u : 0u);
+    e.row.flags = (cull ? ROW_CULL : 0u) | (fogged ? ROW_FOG : 0u) | (place ? ROW_PLACED : 0u);
     if (fogged) e.row.fog = p->fog;
+    e.placed = place != nullptr;
+    if (place) e.place = *place;
     e.wire = (p ? p->backface_wireframe != 0 : c->batch_st.backface_wireframe != 0) && cull;       // render.rs:2577
     c->batch.push_back(e);
     return B32_OK;
@@ -118,12 +124,12 @@ int b32_frame_end(b32_ctx* c) {
     int rc = B32_OK;
     auto draw_one = [&](const b32_ctx::BatchEntry& e) -> int {      // the mesh on its own, exactly like a b32_render_scene_15_async call
         B32Settings st = base;
-        st.ambient = e.row.ambient; st.backface_cull = (e.row.flags & 1u) ? 1 : 0; st.backface_wireframe = e.wire ? 1 : 0;
+        st.ambient = e.row.ambient; st.backface_cull = (e.row.flags & ROW_CULL) ? 1 : 0; st.backface_wireframe = e.wire ? 1 : 0;
         int r = b32_scene_swap(c, e.slot);
         if (r) return r;
         if (!c->have_scene) r = B32_E_ARG;
-        else if (c->fmt8) { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, nullptr); }
-        else { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, (e.row.flags & 2u) ? &e.row.fog : nullptr); }
+        else if (c->fmt8) { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, nullptr, e.placed ? &e.place : nullptr); }
+        else { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, (e.row.flags & ROW_FOG) ? &e.row.fog : nullptr, e.placed ? &e.place : nullptr); }
         const int r2 = b32_scene_swap(c, e.slot);
         c->batch_stats[1]++;
         return r ? r : r2;
@@ -146,13 +152,16 @@ int b32_frame_end(b32_ctx* c) {
         if ((rc = b32_scene_swap(c, m))) break;
         rc = ensure_work(c, c->nf);
         if (rc == B32_OK) {
-            bool any_fog = false;
-            for (size_t j = i; j < k; ++j) { c->frame_table.m[j - i] = c->batch[j].row; any_fog |= (c->batch[j].row.flags & 2u) != 0; }
-            c->frame_batched = true;
+            bool any_fog = false, any_placed = false;
+            for (size_t j = i; j < k; ++j) {
+                c->frame_table.m[j - i] = c->batch[j].row; any_fog |= (c->batch[j].row.flags & ROW_FOG) != 0;
+                if (c->batch[j].placed) { c->frame_places.p[j - i] = c->batch[j].place; any_placed = true; }
+            }
+            c->frame_batched = true; c->frame_placed = any_placed;
             B32Fog f0{};                                    // (fp.has_fog switches the fog code on; the rows decide per mesh)
             B32Settings mst = base;                         // (members of a run never have a wireframe phase: see the run split above;
             mst.backface_wireframe = 0;                     //  the base's flag must not give the merged mesh one -- found by the soak)
-            rc = render_scene_async_any(c, &c->batch_cam, &mst, any_fog ? &f0 : nullptr);
+            rc = render_scene_async_any(c, &c->batch_cam, &mst, any_fog ? &f0 : nullptr, nullptr);
             c->batch_stats[0]++;
         }
         const int r2 = b32_scene_swap(c, m);
@@ -167,6 +176,15 @@ int b32_frame_submit(b32_ctx* c, const B32Camera* cam, const B32Settings* st, b3
     if (!c || (n && !slots)) return B32_E_ARG;
     int rc = b32_frame_begin(c, cam, st);
     for (uint32_t i = 0; i < n && !rc; ++i) rc = b32_frame_add_scene(c, slots[i], params ? &params[i] : nullptr);
+    if (rc) { c->batch_open = false; c->batch.clear(); return rc; }
+    return b32_frame_end(c);
+}
+int b32_frame_submit_placed(b32_ctx* c, const B32Camera* cam, const B32Settings* st, b32_scene* const* slots, const B32MeshParams* params,
+                            const B32Placement* places, const uint8_t* has_place, uint32_t n) {
+    if (!c || (n && !slots)) return B32_E_ARG;
+    int rc = b32_frame_begin(c, cam, st);
+    for (uint32_t i = 0; i < n && !rc; ++i)
+        rc = b32_frame_add_scene_placed(c, slots[i], params ? &params[i] : nullptr, (places && has_place && has_place[i]) ? &places[i] : nullptr);
     if (rc) { c->batch_open = false; c->batch.clear(); return rc; }
     return b32_frame_end(c);
 }

@@ -239,7 +239,10 @@ struct FrameParams {
     float ortho_zoom, ortho_cx, ortho_cy;      // OrthoProjection (types.rs), math.rs:140-148
     B32Fog fog;
     CamFx camfx;
+    uint8_t placed, _pad_placed[3];        // placed: some mesh of this draw carries a B32Placement (PlaceTable, k_setup only).  At the END of the struct, in
+                                           // the four bytes that padded it to the pointer behind it in every kernel-argument block: no other member moves
 };
+static_assert(sizeof(FrameParams) == 208, "FrameParams layout (FillArgs and the kernel-argument blocks embed it)");
 
 // Triangle of the wireframe phases (render.rs:2445-2449, 2509-2511, 2574-2635): screen coordinates `as i32`, depth as is.
 struct WireTri { int32_t x[3], y[3]; float z[3]; uint32_t kind; };   // kind: 0 none, 1 back-face, 2 front-face
@@ -378,8 +381,14 @@ struct LightSet { B32Light l[LIGHTS_INLINE]; };
 // this table, indexed by the mesh number k_merge_mesh left in the spare byte of every merged face; everything else (camera, lights,
 // the other settings) is the frame's.
 constexpr uint32_t BATCH_MESHES = 32;
-struct MeshRow { float ambient; uint32_t flags; B32Fog fog; };       // flags: bit 0 backface_cull, bit 1 fog is Some
+struct MeshRow { float ambient; uint32_t flags; B32Fog fog; };       // flags: bit 0 backface_cull, bit 1 fog is Some, bit 2 placed (PlaceTable row of the same number)
 struct MeshTable { MeshRow m[BATCH_MESHES]; };
+constexpr uint32_t ROW_CULL = 1u, ROW_FOG = 2u, ROW_PLACED = 4u;
+// Placements (render_asset_parts, scene.rs:140-156), a table parallel to MeshTable and passed to k_setup only, by value like it: the setup
+// kernel of frame n can never see frame n + 1's.  A draw on its own (not batched) uses row 0; a merged run the rows whose MeshRow has
+// ROW_PLACED.  Read only when FrameParams::placed is set.  (k_setup's argument block: 1488 -> 2128 bytes of the 4096 a launch may carry.)
+struct PlaceTable { B32Placement p[BATCH_MESHES]; };
+static_assert(sizeof(B32Placement) == 20 && sizeof(PlaceTable) == 640, "B32Placement layout");
 struct RecArrays { CovRec* cov; ShadeRec* shade; AuxRec* aux; };
 // Direct binning (sort-free path, meshes too large for the in-kernel collection): k_setup itself appends every surviving face to the
 // lists of the tiles its span touches -- one returning atomic per (tile, face) pair on the tile's fill counter, whose latency passes
@@ -402,7 +411,7 @@ void launch_merge_mesh(hipStream_t s, const B32Vertex* sv, uint32_t nv, const B3
                        uint32_t vbase, uint32_t tbase, uint32_t mesh);
 void launch_offset_tex(hipStream_t s, const TexDesc* src, uint32_t nt, TexDesc* dst, uint32_t texel_base);
 void launch_setup(hipStream_t s, const FrameParams& fp, const B32Vertex* verts, const B32Face* faces, const TexDesc* tex,
-                  const B32Light* lights, const LightSet& inline_lights, const MeshTable& mesh_table, RecArrays recs, const DirectBin& direct, float* shades, uint32_t* keys, uint32_t* spans,
+                  const B32Light* lights, const LightSet& inline_lights, const MeshTable& mesh_table, const PlaceTable& place_table, RecArrays recs, const DirectBin& direct, float* shades, uint32_t* keys, uint32_t* spans,
                   uint32_t* partials, Ctrl* ctrl, WireTri* wire, int n_cu, const float* pos12, const float* attr12, uint32_t* face_of);
 void launch_gate(hipStream_t s, Ctrl* prev, uint32_t need, uint32_t patience_ticks, uint32_t start_seq, Ctrl* mine, uint32_t start_patience_ticks = 200000000u);
 void launch_flag(hipStream_t s, Ctrl* ctrl, uint32_t epoch);

@@ -131,6 +131,7 @@ static FrameParams frame_params(const b32_ctx* c, const B32Camera* cam, const B3
     fp.redraw = c->redrawing ? 1 : 0;
     fp.tex_blend_any = c->tex_blend_any ? 1 : 0;
     fp.batched = c->frame_batched ? 1 : 0;
+    fp.placed = c->frame_placed ? 1 : 0;
     return fp;
 }
 
@@ -526,7 +527,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         }
     }
     if (prof_all) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_setup(ss, fp, c->d_verts, c->d_faces, c->d_tex, c->d_lights, lset, c->frame_table, RecArrays{ c->crecs, c->srecs, c->xrecs }, r.db, c->shades, c->keys[0],
+    launch_setup(ss, fp, c->d_verts, c->d_faces, c->d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->crecs, c->srecs, c->xrecs }, r.db, c->shades, c->keys[0],
                  r.direct_bin ? nullptr : c->spans /* (direct binning: nobody reads the spans) */, c->partials, c->d_ctrl, c->wire, c->n_cu, pos12, attr12, c->face_of);
     // The merged draws of a batched frame: the hand-over polled by the fused kernel itself (FillArgs::join_seq) -- their fills are few 16-wave
     // workgroups (at most 5 / 8 of the CUs: the setup kernel they may have to spin for keeps the rest of the GPU), the setup kernel of draw
@@ -645,14 +646,20 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
 int b32_render_scene_15_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog) {
     if (!c || c->fmt8) return B32_E_ARG;                 // the resident scene holds Texture (8-bit) texels: use b32_render_scene
     c->frame_batched = false;
-    return render_scene_async_any(c, cam, st, fog);
+    return render_scene_async_any(c, cam, st, fog, nullptr);
 }
 int b32_render_scene_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st) {
     if (!c || !c->fmt8) return B32_E_ARG;
     c->frame_batched = false;
-    return render_scene_async_any(c, cam, st, nullptr);
+    return render_scene_async_any(c, cam, st, nullptr, nullptr);
 }
-int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog) {
+// the resident scene on its own, placed: render_asset_parts' two branches (scene.rs:163-169) behind one entry
+int b32_render_scene_15_placed_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place) {
+    if (!c) return B32_E_ARG;
+    c->frame_batched = false;
+    return render_scene_async_any(c, cam, st, c->fmt8 ? nullptr : fog, place);      // (render_mesh takes no fog)
+}
+int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place) {
     if (!c || !cam || !st || !c->fb || !c->have_scene) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     int rc = validate_settings(st);
@@ -662,6 +669,8 @@ int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* 
     // (... unless a clear of the whole band has superseded it: b32_fb_clear)
     if (!c->deep_async && !(c->pending_superseded && c->clear_pending) && (rc = settle_pending(c))) return rc;
     c->pending_superseded = false;
+    // (behind the settle: a redraw of the pending frame above used the placement THAT frame was enqueued with)
+    if (!c->frame_batched) { c->frame_placed = place != nullptr; if (place) c->frame_places.p[0] = *place; }
     c->last_cam = *cam; c->last_settings = *st; c->last_has_fog = fog != nullptr;
     if (fog) c->last_fog = *fog;
     c->keep_lights.assign(st->lights, st->lights + (st->lights ? st->n_lights : 0));

@@ -192,7 +192,8 @@ struct b32_ctx {
     // batched frame (b32_frame_begin / _add_scene / _end): per-mesh rows of the frame being enqueued (kept for a redraw), the recording
     // between begin and end, and the merged meshes built so far (reused while their members' contents stay the same)
     bool frame_batched = false; MeshTable frame_table{};
-    struct BatchEntry { b32_scene* slot; MeshRow row; bool wire; };
+    bool frame_placed = false; PlaceTable frame_places{};      // placements of the frame being enqueued (row 0: a draw on its own), kept for a redraw like the rows
+    struct BatchEntry { b32_scene* slot; MeshRow row; bool wire; bool placed; B32Placement place; };
     struct MergedRun { std::vector<b32_scene*> members; std::vector<unsigned long long> gens; b32_scene* merged = nullptr; unsigned long long used = 0; };
     bool batch_open = false; B32Camera batch_cam{}; B32Settings batch_st{}; std::vector<B32Light> batch_lights; std::vector<BatchEntry> batch;
     std::vector<MergedRun> merged_runs; unsigned long long batch_clock = 0, gen_counter = 0;
@@ -320,5 +321,6 @@ B32_INTERNAL bool stage_ensure(b32_ctx* c);                                     
 B32_INTERNAL int ensure_work(b32_ctx* c, uint32_t nf);                            // b32_scene.hip
 B32_INTERNAL int validate_settings(const B32Settings* st);                        // b32_frame.hip
 B32_INTERNAL int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog);            // b32_frame.hip
-B32_INTERNAL int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog);   // b32_frame.hip
+// (place: the placement of a draw on its own, or NULL; a merged run -- frame_batched -- has set frame_placed / frame_places itself)
+B32_INTERNAL int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place);   // b32_frame.hip
 }

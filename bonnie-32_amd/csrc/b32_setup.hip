@@ -230,13 +230,13 @@ __device__ __forceinline__ uint32_t agg_position(const AggSlot& g) {
 #endif
 template <int SETUP_FPT, int PLAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 4), PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 5)))) void k_setup(FrameParams fp_in, const B32Vertex* __restrict__ verts, const B32Face* __restrict__ faces,
-                                               const TexDesc* __restrict__ tex, const B32Light* __restrict__ lights_mem, LightSet lset, MeshTable mtab,
+                                               const TexDesc* __restrict__ tex, const B32Light* __restrict__ lights_mem, LightSet lset, MeshTable mtab, PlaceTable ptab,
                                                RecArrays recs, DirectBin db, float* __restrict__ shades, uint32_t* __restrict__ keys,
                                                uint32_t* __restrict__ spans, uint32_t* __restrict__ partials, Ctrl* __restrict__ ctrl,
                                                WireTri* __restrict__ wire, const float* __restrict__ pos12, const float* __restrict__ attr12,
                                                uint32_t* __restrict__ face_of) {
     FrameParams fp_plain = fp_in;                 // (dead code unless PLAIN)
-    if (PLAIN) { fp_plain.ortho = 0; fp_plain.fixed_point = 1; fp_plain.has_fog = 0; fp_plain.wire_collect = 0; fp_plain.xray = 0; fp_plain.batched = 0; }   // (fmt8 stays a run-time flag: one scalar test)
+    if (PLAIN) { fp_plain.ortho = 0; fp_plain.fixed_point = 1; fp_plain.has_fog = 0; fp_plain.wire_collect = 0; fp_plain.xray = 0; fp_plain.batched = 0; fp_plain.placed = 0; }   // (fmt8 stays a run-time flag: one scalar test)
     if (PLAIN == 1) { fp_plain.shading = B32_SHADE_NONE; fp_plain.n_lights = 0; }
     const FrameParams& fp = PLAIN ? fp_plain : fp_in;
     __shared__ uint32_t wpart[4][6];
@@ -306,7 +306,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 
         float m_ambient = fp.ambient; bool m_cull = fp.backface_cull != 0, m_has_fog = fp.has_fog != 0; B32Fog m_fog = fp.fog;
         if (fp.batched) {
             const MeshRow& mr = mtab.m[(fb4 >> 24) & (BATCH_MESHES - 1u)];
-            m_ambient = mr.ambient; m_cull = (mr.flags & 1u) != 0; m_has_fog = (mr.flags & 2u) != 0; m_fog = mr.fog;
+            m_ambient = mr.ambient; m_cull = (mr.flags & ROW_CULL) != 0; m_has_fog = (mr.flags & ROW_FOG) != 0; m_fog = mr.fog;
+        }
+        // placement of this face's mesh (render_asset_parts, scene.rs:123-159): row 0 for a draw on its own, the mesh's row in a merged run.
+        // Not placed = the reference's untransformed branch (scene.rs:157-159): the local vertices as they are, NOT times 1 plus 0
+        bool m_placed = false; float pl_cos = 1.0f, pl_sin = 0.0f; V3 pl_w = { 0.0f, 0.0f, 0.0f };
+        if (fp.placed) {
+            const uint32_t mesh = fp.batched ? ((fb4 >> 24) & (BATCH_MESHES - 1u)) : 0u;
+            m_placed = !fp.batched || (mtab.m[mesh].flags & ROW_PLACED) != 0;
+            const B32Placement& pl = ptab.p[mesh];
+            pl_cos = pl.cos_f; pl_sin = pl.sin_f; pl_w = ld3(pl.world_pos);
         }
         if (in.bad) {
             bad_index = true;
@@ -317,6 +326,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 V3 pos = { in.v[j][0], in.v[j][1], in.v[j][2] };
+                if (fp.placed && m_placed) {             // scene.rs:143-146: the placed position IS the vertex from here on
+                    const float rx = pos.x * pl_cos - pos.z * pl_sin;
+                    const float rz = pos.x * pl_sin + pos.z * pl_cos;
+                    pos = { rx + pl_w.x, pos.y + pl_w.y, rz + pl_w.z };
+                }
                 uvx[j] = in.v[j][3]; uvy[j] = in.v[j][4];
                 col[j] = in.col[j];
                 wpos[j] = pos;
@@ -419,6 +433,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 
                         const float* np = reinterpret_cast<const float*>(verts) + (size_t)vi[j] * 9 + 5;
                         wn[j] = { np[0], np[1], np[2] };
                     }
+                }
+                if (fp.placed && m_placed && fp.shading != B32_SHADE_NONE) {       // scene.rs:148-152: rotated with the mesh, not renormalised
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) wn[j] = { wn[j].x * pl_cos - wn[j].z * pl_sin, wn[j].y, wn[j].x * pl_sin + wn[j].z * pl_cos };
                 }
                 if (fp.has_fog && m_has_fog) {
                     const uint32_t fogc = m_fog.r | (m_fog.g << 8) | (m_fog.b << 16) | ((uint32_t)m_fog.blend << 24);
@@ -584,18 +602,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 
 }
 
 void launch_setup(hipStream_t s, const FrameParams& fp, const B32Vertex* verts, const B32Face* faces, const TexDesc* tex,
-                  const B32Light* lights, const LightSet& ls, const MeshTable& mt, RecArrays recs, const DirectBin& db, float* shades, uint32_t* keys, uint32_t* spans, uint32_t* partials,
+                  const B32Light* lights, const LightSet& ls, const MeshTable& mt, const PlaceTable& pt, RecArrays recs, const DirectBin& db, float* shades, uint32_t* keys, uint32_t* spans, uint32_t* partials,
                   Ctrl* ctrl, WireTri* wire, int n_cu, const float* pos12, const float* attr12, uint32_t* face_of) {
     (void)n_cu;
     if (fp.nf == 0) return;
-    const bool plain = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading == B32_SHADE_NONE && !fp.xray && !fp.batched;
+    // (a placed draw takes the general form: the specialised ones compile the placement out, like fog and the mesh table)
+    const bool plain = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading == B32_SHADE_NONE && !fp.xray && !fp.batched && !fp.placed;
     // one face per thread: 52 VGPRs in the plain form = 8 waves per SIMD (two faces per thread with their loads issued up front: 73 VGPRs,
     // 43 us instead of 39 at 1 M faces; three: 49 us)
     const dim3 g1((fp.nf + 255) / 256);
-    const bool lit = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading != B32_SHADE_NONE && !fp.xray && !fp.batched;
-    if (lit) hipLaunchKernelGGL((k_setup<1, 2>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
-    else if (plain) hipLaunchKernelGGL((k_setup<1, 1>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
-    else hipLaunchKernelGGL((k_setup<1, 0>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
+    const bool lit = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading != B32_SHADE_NONE && !fp.xray && !fp.batched && !fp.placed;
+    if (lit) hipLaunchKernelGGL((k_setup<1, 2>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
+    else if (plain) hipLaunchKernelGGL((k_setup<1, 1>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
+    else hipLaunchKernelGGL((k_setup<1, 0>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
 }
 
 // ---------------------------------------------------------------- merged mesh of a batched frame

@@ -352,7 +352,49 @@ private:
 
 // One frame of scene::render_scene (scene.rs:158-261): one camera, base settings and light list; per mesh the room's ambient and fog and
 // the part's backface culling.  The meshes are drawn as merged runs where their draws commute (b32_frame_begin / _add_scene / _end).
-struct MeshParams { float ambient; bool backface_cull, backface_wireframe; Fog fog; };
+// Placement: facing and world offset of one placed object (render_asset_parts, scene.rs:112-159).  from_facing takes cos / sin on the host
+// and decides has_transform as scene.rs:125 does; without a transform the reference draws the local vertices as they are, so the draw gets
+// no placement at all.  A mesh may appear in a frame any number of times, each time with its own placement.
+struct Placement {
+    float cos_f = 1.0f, sin_f = 0.0f; Vec3 world_pos; bool has_transform = true;
+    static Placement from_facing(float facing, Vec3 world_pos) {
+        Placement p;
+        p.cos_f = std::cos(facing); p.sin_f = std::sin(facing); p.world_pos = world_pos;
+        p.has_transform = std::fabs(facing) > 0.0001f || std::fabs(world_pos.x) > 0.0001f || std::fabs(world_pos.y) > 0.0001f || std::fabs(world_pos.z) > 0.0001f;
+        return p;
+    }
+};
+// the host restatement of the same arithmetic (scene.rs:140-156): separately rounded f32 operations in the reference's order
+// (compile with -ffp-contract=off where the compiler would fuse)
+inline Vertex place_vertex(const Vertex& v, const Placement& p) {
+    if (!p.has_transform) return v;
+    Vertex o = v;
+    const float rx = v.pos.x * p.cos_f - v.pos.z * p.sin_f, rz = v.pos.x * p.sin_f + v.pos.z * p.cos_f;
+    o.pos = { rx + p.world_pos.x, v.pos.y + p.world_pos.y, rz + p.world_pos.z };
+    o.normal = { v.normal.x * p.cos_f - v.normal.z * p.sin_f, v.normal.y, v.normal.x * p.sin_f + v.normal.z * p.cos_f };
+    return o;
+}
+struct MeshParams { float ambient; bool backface_cull, backface_wireframe; Fog fog; std::optional<Placement> placement = std::nullopt; };
+namespace detail {
+inline bool pack(const std::optional<Placement>& p, B32Placement& out) {
+    if (!p || !p->has_transform) return false;
+    out = { p->cos_f, p->sin_f, { p->world_pos.x, p->world_pos.y, p->world_pos.z } };
+    return true;
+}
+}  // namespace detail
+// One resident mesh on its own, placed (b32_render_scene_15_placed_async): enqueued only; errors and counters by b32_frame_finish.
+inline void render_placed_async(Framebuffer& fb, const ResidentMesh& mesh, const Camera& camera, const RasterSettings& settings, const Fog& fog,
+                                const std::optional<Placement>& placement) {
+    const std::vector<B32Light> l = detail::pack(settings.lights);
+    const B32Camera c = detail::pack(camera);
+    const B32Settings s = detail::pack(settings, l);
+    B32Fog f{}; const bool has_fog = detail::pack(fog, f);
+    B32Placement pl{}; const bool placed = detail::pack(placement, pl);
+    check(b32_scene_swap(fb.ctx(), mesh.slot()), "scene_swap");
+    const int rc = b32_render_scene_15_placed_async(fb.ctx(), &c, &s, has_fog ? &f : nullptr, placed ? &pl : nullptr);
+    check(b32_scene_swap(fb.ctx(), mesh.slot()), "scene_swap");
+    check(rc, "render_scene_15_placed_async");
+}
 inline RasterTimings render_frame(Framebuffer& fb, const std::vector<std::pair<const ResidentMesh*, MeshParams>>& meshes, const Camera& camera,
                                   const RasterSettings& base) {
     const std::vector<B32Light> l = detail::pack(base.lights);
@@ -363,7 +405,8 @@ inline RasterTimings render_frame(Framebuffer& fb, const std::vector<std::pair<c
         B32MeshParams p{};
         p.ambient = m.second.ambient; p.backface_cull = m.second.backface_cull; p.backface_wireframe = m.second.backface_wireframe;
         p.has_fog = detail::pack(m.second.fog, p.fog) ? 1 : 0;
-        check(b32_frame_add_scene(fb.ctx(), m.first->slot(), &p), "frame_add_scene");
+        B32Placement pl{};
+        check(b32_frame_add_scene_placed(fb.ctx(), m.first->slot(), &p, detail::pack(m.second.placement, pl) ? &pl : nullptr), "frame_add_scene_placed");
     }
     check(b32_frame_end(fb.ctx()), "frame_end");
     B32Timings tm{};
@@ -388,15 +431,17 @@ public:
         const std::vector<B32Light> l = detail::pack(base.lights);
         const B32Camera c = detail::pack(camera);
         const B32Settings s = detail::pack(base, l);
-        std::vector<b32_scene*> slots; std::vector<B32MeshParams> params;
+        std::vector<b32_scene*> slots; std::vector<B32MeshParams> params; std::vector<B32Placement> places; std::vector<uint8_t> has_place;
         for (const auto& m : meshes) {
             B32MeshParams p{};
             p.ambient = m.second.ambient; p.backface_cull = m.second.backface_cull; p.backface_wireframe = m.second.backface_wireframe;
             p.has_fog = detail::pack(m.second.fog, p.fog) ? 1 : 0;
             slots.push_back(m.first->slot()); params.push_back(p);
+            B32Placement pl{};
+            has_place.push_back(detail::pack(m.second.placement, pl) ? 1 : 0); places.push_back(pl);
         }
         fb_.clear(clear);
-        check(b32_frame_submit(fb_.ctx(), &c, &s, slots.data(), params.data(), (uint32_t)slots.size()), "frame_submit");
+        check(b32_frame_submit_placed(fb_.ctx(), &c, &s, slots.data(), params.data(), places.data(), has_place.data(), (uint32_t)slots.size()), "frame_submit_placed");
         const size_t k = n_++ & 1;
         check(b32_fb_download_async(fb_.ctx(), buf_[k], &ticket_[k]), "fb_download_async");
         return ticket_[k];

@@ -27,6 +27,65 @@ def _chk(rc, where=""):
         raise B32Error(rc, where)
 
 
+def place_vertices(vertices, cos_f, sin_f, world_pos):
+    """The per-vertex arithmetic of render_asset_parts (scene.rs:140-156) in numpy float32: rotate about Y by (cos_f, sin_f), then
+    translate by world_pos; normals are rotated and not renormalised; uv and colour are unchanged.  Every operation is one separately
+    rounded f32 operation in the reference's order (numpy does not fuse).  This is what a caller without a GPU does per object and per
+    frame, and what the tests hand to the oracle; on the device the same arithmetic runs inside the setup kernel (B32Placement)."""
+    v = np.array(vertices, dtype=abi.VERTEX_DTYPE, copy=True)
+    c, s = np.float32(cos_f), np.float32(sin_f)
+    w = np.asarray(world_pos, np.float32).reshape(3)
+    with np.errstate(all="ignore"):
+        x, y, z = v["pos"][:, 0].copy(), v["pos"][:, 1].copy(), v["pos"][:, 2].copy()
+        rx = x * c - z * s
+        rz = x * s + z * c
+        v["pos"][:, 0] = rx + w[0]; v["pos"][:, 1] = y + w[1]; v["pos"][:, 2] = rz + w[2]
+        nx, nz = v["normal"][:, 0].copy(), v["normal"][:, 2].copy()
+        v["normal"][:, 0] = nx * c - nz * s
+        v["normal"][:, 2] = nx * s + nz * c
+    return v
+
+
+class Placement:
+    """facing + world offset of one placed object (render_asset_parts, scene.rs:112-159).  Placement(facing=..., world_pos=...) takes
+    cos / sin in f32 on the host and decides `has_transform` as scene.rs:125 does (|facing| or any |world_pos| component above 0.0001,
+    compared in f32); without a transform the reference draws the local vertices as they are, so pack() is None -- "draw exactly as
+    without a placement".  Placement(cos_f=..., sin_f=..., world_pos=...) takes the caller's own cos / sin (Rust's f32::cos is the
+    target's libm and may differ from numpy's in the last bit) and always transforms unless has_transform says otherwise."""
+
+    def __init__(self, facing=None, world_pos=(0.0, 0.0, 0.0), cos_f=None, sin_f=None, has_transform=None):
+        f32 = np.float32
+        self.world_pos = tuple(f32(x) for x in world_pos)
+        if (cos_f is None) != (sin_f is None) or (facing is None and cos_f is None):
+            raise ValueError("Placement needs facing, or cos_f and sin_f")
+        if cos_f is None:
+            self.cos_f, self.sin_f = f32(np.cos(f32(facing))), f32(np.sin(f32(facing)))
+        else:
+            self.cos_f, self.sin_f = f32(cos_f), f32(sin_f)
+        if has_transform is None:
+            eps = f32(0.0001)
+            has_transform = True if facing is None else bool(abs(f32(facing)) > eps or any(abs(x) > eps for x in self.world_pos))
+        self.has_transform = bool(has_transform)
+
+    def pack(self):
+        """abi.B32Placement, or None when the reference takes its untransformed branch."""
+        if not self.has_transform:
+            return None
+        return abi.B32Placement(float(self.cos_f), float(self.sin_f), (C.c_float * 3)(*[float(x) for x in self.world_pos]))
+
+    def apply(self, vertices):
+        """The vertices render_asset_parts hands to render_mesh_15 / render_mesh for this placement (host restatement)."""
+        if not self.has_transform:
+            return np.array(vertices, dtype=abi.VERTEX_DTYPE, copy=True)
+        return place_vertices(vertices, self.cos_f, self.sin_f, self.world_pos)
+
+
+def _pack_placement(placement):
+    if placement is None or isinstance(placement, abi.B32Placement):
+        return placement
+    return placement.pack()
+
+
 class Context:
     """One b32_ctx: one GPU, one stream, one device-resident framebuffer and scene."""
 
@@ -86,8 +145,9 @@ class Context:
         self._frame_keep = (cam, st, keep)
         _chk(self.lib.b32_frame_begin(self.h, C.byref(cam), C.byref(st)), "b32_frame_begin")
 
-    def frame_add(self, scene, ambient=None, backface_cull=None, backface_wireframe=None, fog=None):
-        """Append a detached ResidentScene with its per-mesh parameters (None: the base settings' value; fog None: no fog)."""
+    def frame_add(self, scene, ambient=None, backface_cull=None, backface_wireframe=None, fog=None, placement=None):
+        """Append a detached ResidentScene with its per-mesh parameters (None: the base settings' value; fog None: no fog).
+        placement: a Placement (or abi.B32Placement) for this draw of the slot -- the same slot may be added any number of times."""
         st = self._frame_keep[1]
         p = abi.B32MeshParams()
         p.ambient = float(st.ambient if ambient is None else ambient)
@@ -98,6 +158,10 @@ class Context:
         if fg is not None:
             p.fog = fg
         scene.detach()
+        if placement is not None:
+            pl = _pack_placement(placement)
+            _chk(self.lib.b32_frame_add_scene_placed(self.h, scene._slot, C.byref(p), C.byref(pl) if pl is not None else None), "b32_frame_add_scene_placed")
+            return
         _chk(self.lib.b32_frame_add_scene(self.h, scene._slot, C.byref(p)), "b32_frame_add_scene")
 
     def frame_end(self):
@@ -105,12 +169,29 @@ class Context:
 
     def frame_submit(self, table):
         """b32_frame_submit: the frame recorded by make_frame_table, in one call."""
+        if len(table) == 8:                               # a placed table: b32_frame_submit_placed
+            cam, st, _keep, slots, params, n, places, has_place = table
+            _chk(self.lib.b32_frame_submit_placed(self.h, C.byref(cam), C.byref(st), slots, C.cast(params, C.c_void_p), C.cast(places, C.c_void_p),
+                                                  C.cast(has_place, C.c_void_p), n), "b32_frame_submit_placed")
+            return
         cam, st, _keep, slots, params, n = table
         _chk(self.lib.b32_frame_submit(self.h, C.byref(cam), C.byref(st), slots, C.cast(params, C.c_void_p), n), "b32_frame_submit")
 
     @staticmethod
-    def make_frame_table(camera, settings, scenes, fogs=None, ambients=None):
-        """Packs camera, base settings and a list of detached ResidentScenes (+ per-mesh fog / ambient) once, for frame_submit."""
+    def set_table_placements(table, placements):
+        """Rewrites the placements of a placed frame table in place (objects that move every frame: nothing else is packed again)."""
+        places, has_place = table[6], table[7]
+        for i, pl in enumerate(placements):
+            p = _pack_placement(pl)
+            has_place[i] = 0 if p is None else 1
+            if p is not None:
+                places[i] = p
+
+    @staticmethod
+    def make_frame_table(camera, settings, scenes, fogs=None, ambients=None, placements=None, backface_culls=None):
+        """Packs camera, base settings and a list of detached ResidentScenes (+ per-mesh fog / ambient) once, for frame_submit.
+        placements: one Placement (or None) per entry -- the table then goes through b32_frame_submit_placed, and the same scene may
+        appear any number of times; backface_culls: per-entry culling (per part: double_sided, scene.rs:133-137)."""
         cam = camera.pack()
         st, keep = settings.pack()
         n = len(scenes)
@@ -125,7 +206,14 @@ class Context:
             params[i].has_fog = 0 if fg is None else 1
             if fg is not None:
                 params[i].fog = fg
-        return cam, st, keep, slots, params, n
+            if backface_culls is not None and backface_culls[i] is not None:
+                params[i].backface_cull = int(bool(backface_culls[i]))
+                params[i].backface_wireframe = int(st.backface_wireframe and bool(backface_culls[i]))
+        if placements is None:
+            return cam, st, keep, slots, params, n
+        table = (cam, st, keep, slots, params, n, (abi.B32Placement * n)(), (C.c_uint8 * n)())
+        Context.set_table_placements(table, placements)
+        return table
 
     # ---- the presenter's copy without a host round trip per frame (b32_fb_download_async + tickets)
     def host_alloc(self, nbytes):
@@ -796,6 +884,17 @@ class ResidentScene:
         self._packed = (cam, st, kl, fg)
         return self._packed
 
+    def render_placed_async(self, placement):
+        """b32_render_scene_15_placed_async with the last packed camera / settings / fog: RGB555 and 8-bit-colour scenes alike."""
+        cam, st, _kl, fg = self._packed
+        pl = _pack_placement(placement)
+        self._swap()
+        try:
+            _chk(self.ctx.lib.b32_render_scene_15_placed_async(self.ctx.h, C.byref(cam), C.byref(st), C.byref(fg) if fg is not None else None,
+                                                               C.byref(pl) if pl is not None else None), "render_scene_15_placed_async")
+        finally:
+            self._swap()
+
     def render(self, camera, settings, fog=None) -> T.RasterTimings:
         cam, st, _kl, fg = self._pack(camera, settings, fog)
         tm = abi.B32Timings()
@@ -810,10 +909,13 @@ class ResidentScene:
             self._swap()
         return T.RasterTimings.from_c(tm)
 
-    def render_async(self, camera=None, settings=None, fog=None):
-        """Enqueue only. With no arguments, re-enqueues the last packed camera/settings (no Python packing cost)."""
+    def render_async(self, camera=None, settings=None, fog=None, placement=None):
+        """Enqueue only. With no arguments, re-enqueues the last packed camera/settings (no Python packing cost).
+        placement: a Placement (or abi.B32Placement) -- the resident mesh is drawn rotated and moved, nothing is uploaded."""
         if camera is not None:
             self._pack(camera, settings, fog)
+        if placement is not None:
+            return self.render_placed_async(placement)
         cam, st, _kl, fg = self._packed
         self._swap()
         try:

@@ -359,6 +359,43 @@ int b32_frame_submit(b32_ctx* ctx, const B32Camera* camera, const B32Settings* b
 /* which: 0 merged draws, 1 mesh-by-mesh draws, 2 merged meshes built, 3 frames ended -- since the context was created (tests). */
 unsigned long long b32_batch_count(const b32_ctx* ctx, int which);
 
+/* ---- placed draws: facing and world offset per draw (render_asset_parts, scene.rs:112-171) ----------------------------------------
+ * The reference never draws a placed object from world-space vertices: per part, per object and per frame it rotates the asset's LOCAL
+ * vertices about Y by the object's facing, translates them by its world position (scene.rs:140-156) and only then calls render_mesh_15 /
+ * render_mesh.  A B32Placement carries exactly that to the setup kernel, which applies it to the three vertices a lane has loaded, so a
+ * resident mesh can move, turn and be drawn any number of times per frame without an upload:
+ *     rx = x * cos_f - z * sin_f        rz = x * sin_f + z * cos_f
+ *     pos    = (rx + wx, y + wy, rz + wz)
+ *     normal = (nx * cos_f - nz * sin_f, ny, nx * sin_f + nz * cos_f)      (not renormalised; uv and colour unchanged)
+ * every operation a separately rounded f32 operation in this order, no fused multiply-add.  The placed position is "the vertex" for
+ * everything downstream (fixed-point snap, camera space, near test, fog, painter's key, light positions), the placed normal is what
+ * flat and Gouraud lighting see.  cos_f / sin_f come from the caller (libm stays on the host, like the camera basis).  The reference
+ * skips the transform altogether when neither facing nor position exceeds 0.0001 (has_transform, scene.rs:125) and then uses the local
+ * vertices as they are -- it does not multiply by 1 and add 0: pass place = NULL for that case; NULL means "draw exactly as the
+ * entry without a placement".  Nothing is validated about the numbers: a placement that produces a NaN sort key is reported as
+ * B32_E_NAN_KEY by b32_frame_finish, like the reference's panic.
+ *   b32_frame_add_scene_placed   b32_frame_add_scene with a placement for this draw.  The same slot may be added any number of times
+ *                                in one frame, each time with its own placement (one upload, twenty crates).  The merged mesh of a run
+ *                                does not depend on the placements: frames that differ only in them reuse it (b32_batch_count(ctx, 2)
+ *                                stays constant).  Run splitting, the 32-mesh limit, the error semantics of merged runs and the
+ *                                asynchronous modes are those of b32_frame_add_scene; a frame that has to be redrawn (grown buffers)
+ *                                is redrawn with the placements it had.
+ *   b32_frame_submit_placed      the whole table in one call: places[i] is read only where has_place[i] != 0; places == NULL or
+ *                                has_place == NULL: no mesh is placed (b32_frame_submit).
+ *   b32_render_scene_15_placed_async   the context's resident scene on its own, placed: RGB555 scenes like b32_render_scene_15_async,
+ *                                8-bit-colour scenes (b32_scene_upload_rgba) like b32_render_scene_async (fog is ignored there: render_mesh
+ *                                has none). */
+typedef struct B32Placement {
+    float cos_f, sin_f;          /* facing.cos(), facing.sin(), scene.rs:123-124 */
+    float world_pos[3];          /* obj.world_position(room), scene.rs:248 */
+} B32Placement;                  /* 20 bytes */
+int b32_frame_add_scene_placed(b32_ctx* ctx, b32_scene* slot, const B32MeshParams* params /* nullable */, const B32Placement* place /* nullable */);
+int b32_frame_submit_placed(b32_ctx* ctx, const B32Camera* camera, const B32Settings* base_settings, b32_scene* const* slots,
+                            const B32MeshParams* params /* nullable */, const B32Placement* places /* nullable: n entries */,
+                            const uint8_t* has_place /* nullable: n bytes */, uint32_t n);
+int b32_render_scene_15_placed_async(b32_ctx* ctx, const B32Camera* camera, const B32Settings* settings, const B32Fog* fog /* nullable */,
+                                     const B32Placement* place /* nullable */);
+
 /* ---- the 8-bit-colour path: render_mesh (render.rs:1971-2264) + rasterize_triangle (render.rs:1202-1433) ----
  * What every caller of the reference runs when settings.use_rgb555 is false (scene.rs:163-169).  Same pipeline and settings
  * as render_mesh_15 except: Texture texels are Color values with a per-texel blend mode, no fog, no opaque/transparent
