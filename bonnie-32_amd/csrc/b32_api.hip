@@ -31,10 +31,10 @@ int b32_create(int device, b32_ctx** out) {
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return B32_E_HIP; }
     c->stream = c->own_stream;
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_ctrl), sizeof(Ctrl) + sizeof(Stamps) + sizeof(Events)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_consts), 16 * sizeof(uint32_t)) != hipSuccess ||
+    if (hipMalloc(reinterpret_cast<void**>(&c->cur.d_ctrl), sizeof(Ctrl) + sizeof(Stamps) + sizeof(Events)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&c->scene.d_consts), 16 * sizeof(uint32_t)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&c->digit_total), 4096 * sizeof(uint32_t)) != hipSuccess) { delete c; return B32_E_HIP; }
-    if (hipMemset(c->d_ctrl, 0, sizeof(Ctrl) + sizeof(Stamps) + sizeof(Events)) != hipSuccess) { delete c; return B32_E_HIP; }     // (`sticky` is never reset by a frame)
+    if (hipMemset(c->cur.d_ctrl, 0, sizeof(Ctrl) + sizeof(Stamps) + sizeof(Events)) != hipSuccess) { delete c; return B32_E_HIP; }     // (`sticky` is never reset by a frame)
     *out = c;
     return B32_OK;
 }
@@ -44,17 +44,20 @@ void b32_destroy(b32_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     band_close_any(c);
-    void* ptrs[] = { c->fb_own, c->d_verts, c->d_faces, c->d_texels, c->d_tex, c->keys[0], c->keys[1], c->vals[0], c->vals[1], c->crecs, c->srecs, c->xrecs,
-                     c->shades, c->counts, c->block_sums, c->pkeys[0], c->pkeys[1], c->pvals[0], c->pvals[1], c->block_hist, c->ranges,
-                     c->d_ctrl, c->d_consts, c->d_lights, c->digit_total, c->partials, c->vis, c->spans, c->tile_mid, c->zbuf,
-                     c->wire, c->wire_owner, c->wire_first, c->wire_fill, c->wire_lists, c->d_texels32, c->inline_lists, c->d_texmask, c->direct_lists, c->tile_fill, c->d_pos12, c->face_of, c->d_atlas0 };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->side) (void)hipStreamSynchronize(c->side);
-    for (auto& r : c->merged_runs) if (r.merged) { void* mp[] = { r.merged->d_verts, r.merged->d_faces, r.merged->d_texels, r.merged->d_texels32, r.merged->d_tex,
-                                                                    r.merged->d_consts, r.merged->d_texmask, r.merged->d_pos12, r.merged->d_atlas0 };
-                                                   for (void* q : mp) if (q) (void)hipFree(q); delete r.merged; }
-    for (FrameSet& a : c->alt) { free_alt(c, a); if (a.d_ctrl) (void)hipFree(a.d_ctrl); }
-    for (hipEvent_t e : { c->ev_main, c->ev_wbin, c->ev_setup, c->alt[0].ev_setup, c->alt[1].ev_setup }) if (e) (void)hipEventDestroy(e);
+    c->scene.release();
+    for (auto& r : c->merged_runs) if (r.merged) { r.merged->release(); delete r.merged; }
+    for (FrameSet* a : { &c->cur, &c->alt[0], &c->alt[1] }) {
+        a->release();
+        if (a->d_ctrl) (void)hipFree(a->d_ctrl);
+        if (a->ev_setup) (void)hipEventDestroy(a->ev_setup);
+    }
+    // the context's own buffers: what all frame sets and scenes share
+    for (void* p : { (void*)c->fb_own, (void*)c->zbuf, (void*)c->keys1, (void*)c->vals[0], (void*)c->vals[1], (void*)c->counts, (void*)c->block_sums,
+                     (void*)c->pkeys[0], (void*)c->pkeys[1], (void*)c->pvals[0], (void*)c->pvals[1], (void*)c->block_hist, (void*)c->digit_total,
+                     (void*)c->ranges, (void*)c->vis, (void*)c->tile_mid, (void*)c->inline_lists, (void*)c->wire_owner, (void*)c->wire_first,
+                     (void*)c->d_lights }) if (p) (void)hipFree(p);
+    for (hipEvent_t e : { c->ev_main, c->ev_wbin }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
     c->lines.release(); c->prims.release(); c->world.release();
@@ -615,20 +618,20 @@ int b32_last_draw_order(b32_ctx* c, uint32_t* face_idx, uint32_t cap, uint32_t* 
     if (c->last_local_sort && cnt) {     // the fast path never builds the global order: sort k_setup's keys now (tap only)
         const SortScratch sc{ c->block_hist, c->hist_blocks, c->digit_total };
         hipStream_t s = c->stream;
-        launch_radix_pass(s, c->keys[0], nullptr, c->keys[1], c->vals[1], c->d_consts, c->nf, 0, 8, sc);
-        launch_radix_pass(s, c->keys[1], c->vals[1], c->keys[0], c->vals[0], &c->d_ctrl->n_visible, c->nf, 8, 8, sc);
-        launch_radix_pass(s, c->keys[0], c->vals[0], c->keys[1], c->vals[1], &c->d_ctrl->n_visible, c->nf, 16, 8, sc);
-        launch_radix_pass(s, c->keys[1], c->vals[1], c->keys[0], c->vals[0], &c->d_ctrl->n_visible, c->nf, 24, 8, sc);
+        launch_radix_pass(s, c->cur.keys0, nullptr, c->keys1, c->vals[1], c->scene.d_consts, c->scene.nf, 0, 8, sc);
+        launch_radix_pass(s, c->keys1, c->vals[1], c->cur.keys0, c->vals[0], &c->cur.d_ctrl->n_visible, c->scene.nf, 8, 8, sc);
+        launch_radix_pass(s, c->cur.keys0, c->vals[0], c->keys1, c->vals[1], &c->cur.d_ctrl->n_visible, c->scene.nf, 16, 8, sc);
+        launch_radix_pass(s, c->keys1, c->vals[1], c->cur.keys0, c->vals[0], &c->cur.d_ctrl->n_visible, c->scene.nf, 24, 8, sc);
         c->last_local_sort = false;
     }
     const uint32_t m = cnt < cap ? cnt : cap;
     if (m && face_idx) {
         // the device works on record slots (k_setup packs each wave's survivors to the front of its 64 slots): back to face ids
-        std::vector<uint32_t> fo(c->nf);
+        std::vector<uint32_t> fo(c->scene.nf);
         HIPCHK(c, hipMemcpyAsync(face_idx, c->vals[0], (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(fo.data(), c->face_of, (size_t)c->nf * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(fo.data(), c->cur.face_of, (size_t)c->scene.nf * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (uint32_t i = 0; i < m; ++i) face_idx[i] = face_idx[i] < c->nf ? fo[face_idx[i]] : 0xFFFFFFFFu;
+        for (uint32_t i = 0; i < m; ++i) face_idx[i] = face_idx[i] < c->scene.nf ? fo[face_idx[i]] : 0xFFFFFFFFu;
     }
     return B32_OK;
 }
@@ -753,7 +756,7 @@ extern "C" int b32_set_routes(b32_ctx* c, uint32_t off_mask) {
 extern "C" int b32_set_cheap_threshold(b32_ctx* c, uint32_t den) {
     if (!c || den == 0) return B32_E_ARG;
     c->cheap_den = den;          // (applies to the textures uploaded from now on:
-    c->tex_sig_valid = false;    //  the next upload re-counts the skippable texels even if the pool already holds the same textures)
+    c->scene.tex_sig_valid = false;    //  the next upload re-counts the skippable texels even if the pool already holds the same textures)
     return B32_OK;
 }
 extern "C" int b32_set_pipeline_gate(b32_ctx* c, uint32_t permille) {
@@ -773,7 +776,7 @@ extern "C" int b32_last_shader_clock(const b32_ctx* c, float* ghz, float* fill_m
 }
 extern "C" int b32_transparent_counts(const b32_ctx* c, uint32_t* host_bound, uint32_t* device_last) {
     if (!c || !host_bound || !device_last) return B32_E_ARG;
-    *host_bound = c->blend_faces; *device_last = c->h_ctrl.n_transparent;
+    *host_bound = c->scene.blend_faces; *device_last = c->h_ctrl.n_transparent;
     return B32_OK;
 }
 // The depth the library picks itself (b32_set_pipeline_depth(ctx, 0), the default): two frame sets, three for a NARROW band -- at most a sixth

@@ -16,10 +16,6 @@ extern "C" {
 //   * painter's mode, the 8-bit-colour path, x-ray, orthographic views and the wireframe phases are drawn mesh by mesh as before.
 // The merged mesh (vertices, faces with the member number in their spare byte, texel pool, texture descriptors) is built on the device
 // from the slots and kept while the members' contents stay the same.
-static void release_scene_buffers(b32_scene* sl) {
-    void* ptrs[] = { sl->d_verts, sl->d_faces, sl->d_texels, sl->d_texels32, sl->d_tex, sl->d_consts, sl->d_texmask, sl->d_pos12, sl->d_atlas0 };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-}
 static int build_merged(b32_ctx* c, const b32_ctx::BatchEntry* e, uint32_t n, b32_scene* m) {
     uint64_t nv = 0, nf = 0, nt = 0, pool = 0;
     for (uint32_t j = 0; j < n; ++j) { const b32_scene* sl = e[j].slot; nv += sl->nv; nf += sl->nf; nt += sl->nt; pool += sl->pool_texels; }
@@ -127,8 +123,8 @@ int b32_frame_end(b32_ctx* c) {
         st.ambient = e.row.ambient; st.backface_cull = (e.row.flags & ROW_CULL) ? 1 : 0; st.backface_wireframe = e.wire ? 1 : 0;
         int r = b32_scene_swap(c, e.slot);
         if (r) return r;
-        if (!c->have_scene) r = B32_E_ARG;
-        else if (c->fmt8) { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, nullptr, e.placed ? &e.place : nullptr); }
+        if (!c->scene.have_scene) r = B32_E_ARG;
+        else if (c->scene.fmt8) { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, nullptr, e.placed ? &e.place : nullptr); }
         else { c->frame_batched = false; r = render_scene_async_any(c, &c->batch_cam, &st, (e.row.flags & ROW_FOG) ? &e.row.fog : nullptr, e.placed ? &e.place : nullptr); }
         const int r2 = b32_scene_swap(c, e.slot);
         c->batch_stats[1]++;
@@ -150,7 +146,7 @@ int b32_frame_end(b32_ctx* c) {
         b32_scene* m = nullptr;
         if ((rc = merged_for(c, &c->batch[i], (uint32_t)(k - i), &m))) break;
         if ((rc = b32_scene_swap(c, m))) break;
-        rc = ensure_work(c, c->nf);
+        rc = ensure_work(c, c->scene.nf);
         if (rc == B32_OK) {
             bool any_fog = false, any_placed = false;
             for (size_t j = i; j < k; ++j) {

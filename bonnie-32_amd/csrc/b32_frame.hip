@@ -11,17 +11,7 @@
 // anything enqueued on the main stream that k_setup reads (uploads, packed streams, light lists, list-space memsets) -> the next
 // setup (ev_main, only when `side_dirty`).  The main stream always waits for the frame's setup before enqueue_frame returns, so a
 // synchronisation of the main stream still covers everything this context has in flight.
-static void swap_with(b32_ctx* c, FrameSet& a) {
-    std::swap(c->keys[0], a.keys0); std::swap(c->crecs, a.crecs); std::swap(c->srecs, a.srecs); std::swap(c->xrecs, a.xrecs);
-    std::swap(c->spans, a.spans); std::swap(c->face_of, a.face_of); std::swap(c->partials, a.partials);
-    std::swap(c->shades, a.shades); std::swap(c->cap_shades, a.cap_shades);
-    std::swap(c->direct_lists, a.direct_lists); std::swap(c->cap_direct, a.cap_direct);
-    std::swap(c->tile_fill, a.tile_fill); std::swap(c->cap_tile_fill, a.cap_tile_fill);
-    std::swap(c->wire, a.wire); std::swap(c->cap_wire, a.cap_wire);
-    std::swap(c->wire_fill, a.wire_fill); std::swap(c->wire_lists, a.wire_lists); std::swap(c->cap_wire_tiles, a.cap_wire_tiles); std::swap(c->wire_grid, a.wire_grid);
-    std::swap(c->d_ctrl, a.d_ctrl);
-    std::swap(c->ev_setup, a.ev_setup); std::swap(c->set_in_flight, a.in_flight);
-}
+static void swap_with(b32_ctx* c, FrameSet& a) { std::swap(c->cur, a); }
 // The frame being enqueued takes the OLDEST set; afterwards alt[n_sets - 2] is the previous frame's set and alt[0] the set of the frame
 // n_sets - 1 back -- the one whose fill the new frame's setup kernel is meant to run beside (its tile cursor is what the gate polls).
 static void rotate_sets(b32_ctx* c) {
@@ -32,13 +22,6 @@ static void unrotate_sets(b32_ctx* c) {      // (an enqueue that failed between 
     if (c->n_sets == 3) std::swap(c->alt[0], c->alt[1]);
     swap_with(c, c->alt[0]);
 }
-extern "C" void free_alt(b32_ctx* c, FrameSet& a) {          // (the caller has drained both streams)
-    void* ptrs[] = { a.keys0, a.crecs, a.srecs, a.xrecs, a.spans, a.face_of, a.partials, a.shades, a.direct_lists, a.tile_fill, a.wire, a.wire_fill, a.wire_lists };
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    a.keys0 = nullptr; a.crecs = nullptr; a.srecs = nullptr; a.xrecs = nullptr; a.spans = nullptr; a.face_of = nullptr; a.partials = nullptr;
-    a.shades = nullptr; a.cap_shades = 0; a.direct_lists = nullptr; a.cap_direct = 0; a.tile_fill = nullptr; a.cap_tile_fill = 0; a.cap_work = 0;
-    a.wire = nullptr; a.cap_wire = 0; a.wire_fill = nullptr; a.wire_lists = nullptr; a.cap_wire_tiles = 0; a.wire_grid = 0;
-}
 // side stream, events and the other sets' per-face buffers (sized like the current set's)
 static int pipeline_ensure(b32_ctx* c) {
     if (!c->side) {
@@ -48,7 +31,7 @@ static int pipeline_ensure(b32_ctx* c) {
         HIPCHK(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, prio_least));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_wbin, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_setup, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->cur.ev_setup, hipEventDisableTiming));
         for (FrameSet& a : c->alt) HIPCHK(c, hipEventCreateWithFlags(&a.ev_setup, hipEventDisableTiming));
         // the fills of the frames enqueued before the side stream existed end before this point of the main stream, which the first setup
         // kernel on the side stream waits for (side_dirty)
@@ -63,7 +46,7 @@ static int pipeline_ensure(b32_ctx* c) {
         }
         if (a.cap_work < c->cap_work || !a.crecs) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            free_alt(c, a);
+            a.release();
             const size_t n = c->cap_work;
             int rc;
             if ((rc = ensure_plain(c, a.keys0, n))) return rc;
@@ -116,20 +99,20 @@ static FrameParams frame_params(const b32_ctx* c, const B32Camera* cam, const B3
     fp.tile_h = TILE_H;
     fp.tile_yb = (c->band_y0 / TILE_H) * TILE_H;
     fp.tiles_y = c->band_y1 > c->band_y0 ? (c->band_y1 - fp.tile_yb + TILE_H - 1) / TILE_H : 0;
-    fp.nv = c->nv; fp.nf = c->nf; fp.nt = c->nt;
+    fp.nv = c->scene.nv; fp.nf = c->scene.nf; fp.nt = c->scene.nt;
     fp.n_lights = st->shading != B32_SHADE_NONE ? st->n_lights : 0;
     fp.ambient = st->ambient;
     fp.affine = st->affine_textures; fp.shading = st->shading; fp.backface_cull = st->backface_cull;
     fp.dithering = st->dithering; fp.fixed_point = st->use_fixed_point; fp.has_fog = fog ? 1 : 0; fp.zmode = st->use_zbuffer ? 1 : 0;
     if (fog) fp.fog = *fog;
     fp.camfx = make_camfx_any(*cam, c->width, c->height);
-    fp.fmt8 = c->fmt8 ? 1 : 0;
+    fp.fmt8 = c->scene.fmt8 ? 1 : 0;
     fp.ortho = st->has_ortho ? 1 : 0; fp.xray = st->xray_mode ? 1 : 0;
     fp.ortho_zoom = st->ortho_zoom; fp.ortho_cx = st->ortho_center_x; fp.ortho_cy = st->ortho_center_y;
     fp.wire_collect = wire_any ? 1 : 0;
     fp.band_only = 0;
     fp.redraw = c->redrawing ? 1 : 0;
-    fp.tex_blend_any = c->tex_blend_any ? 1 : 0;
+    fp.tex_blend_any = c->scene.tex_blend_any ? 1 : 0;
     fp.batched = c->frame_batched ? 1 : 0;
     fp.placed = c->frame_placed ? 1 : 0;
     return fp;
@@ -153,10 +136,10 @@ static int frame_lights(b32_ctx* c, const B32Settings* st, FrameParams& fp, Ligh
             c->h_lights.assign(st->lights, st->lights + fp.n_lights);
         }
     }
-    if (fp.shading != B32_SHADE_NONE && (!c->shades || c->cap_shades < c->cap_work)) {
-        if (c->shades) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->shades)); c->shades = nullptr; }
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->shades), c->cap_work * 9 * sizeof(float)));
-        c->cap_shades = c->cap_work;
+    if (fp.shading != B32_SHADE_NONE && (!c->cur.shades || c->cur.cap_shades < c->cap_work)) {
+        if (c->cur.shades) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->cur.shades)); c->cur.shades = nullptr; }
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->cur.shades), c->cap_work * 9 * sizeof(float)));
+        c->cur.cap_shades = c->cap_work;
     }
     return B32_OK;
 }
@@ -169,7 +152,7 @@ static int frame_buffers(b32_ctx* c, const FrameParams& fp, bool wire_back) {
     int rc;
     // pair buffers: start at 2 pairs per face + one per tile; b32_frame_finish grows them on overflow
     if (c->cap_pairs == 0 || !c->pkeys[0]) {
-        const size_t n = (size_t)c->nf * 2 + ntiles + 1024;
+        const size_t n = (size_t)c->scene.nf * 2 + ntiles + 1024;
         for (int i = 0; i < 2; ++i) { if ((rc = ensure_plain(c, c->pkeys[i], n))) return rc; if ((rc = ensure_plain(c, c->pvals[i], n))) return rc; }
         c->cap_pairs = n;
     }
@@ -188,9 +171,9 @@ static int frame_buffers(b32_ctx* c, const FrameParams& fp, bool wire_back) {
         if ((rc = ensure_plain(c, c->tile_mid, need_ranges + 64))) return rc;
         c->cap_tile_mid = need_ranges + 64;
     }
-    if (c->mask_dirty && c->pool_texels) {      // (after the drop-in call's staged copy kernel on the same stream: the texels are there)
-        launch_build_mask(s, c->fmt8 ? nullptr : c->d_texels, c->fmt8 ? c->d_texels32 : nullptr, c->pool_texels, c->d_texmask);
-        c->mask_dirty = false;
+    if (c->scene.mask_dirty && c->scene.pool_texels) {      // (after the drop-in call's staged copy kernel on the same stream: the texels are there)
+        launch_build_mask(s, c->scene.fmt8 ? nullptr : c->scene.d_texels, c->scene.fmt8 ? c->scene.d_texels32 : nullptr, c->scene.pool_texels, c->scene.d_texmask);
+        c->scene.mask_dirty = false;
     }
     if (fp.zmode) {          // Framebuffer::zbuffer (render.rs:12): allocated on first use, f32::MAX until drawn into
         const size_t px = (size_t)c->width * c->height;
@@ -201,10 +184,10 @@ static int frame_buffers(b32_ctx* c, const FrameParams& fp, bool wire_back) {
         if ((rc = ensure_plain(c, c->vis, (size_t)c->width * c->height * 2 + 64))) return rc;    // two words per pixel (prio64 coverage)
         c->cap_vis = (size_t)c->width * c->height;
     }
-    if (fp.wire_collect && c->nf) {
-        if ((size_t)c->nf > c->cap_wire || !c->wire) { if ((rc = ensure_plain(c, c->wire, (size_t)c->nf + 16))) return rc; c->cap_wire = c->nf; }
+    if (fp.wire_collect && c->scene.nf) {
+        if ((size_t)c->scene.nf > c->cur.cap_wire || !c->cur.wire) { if ((rc = ensure_plain(c, c->cur.wire, (size_t)c->scene.nf + 16))) return rc; c->cur.cap_wire = c->scene.nf; }
         size_t slots = 1024;
-        while (slots < (size_t)c->nf * 6) slots <<= 1;                        // load factor <= 0.5 with all 3*nf edges distinct
+        while (slots < (size_t)c->scene.nf * 6) slots <<= 1;                        // load factor <= 0.5 with all 3*nf edges distinct
         if (wire_back && (slots > c->cap_wire_table || !c->wire_owner)) {
             if ((rc = ensure_plain(c, c->wire_owner, slots))) return rc;
             if ((rc = ensure_plain(c, c->wire_first, slots))) return rc;
@@ -213,17 +196,17 @@ static int frame_buffers(b32_ctx* c, const FrameParams& fp, bool wire_back) {
         // tile route: one counter and one list region per 64 x 16 wire tile (WIRE_TH rows) of the band (+ the overflow flag and the big-edge count)
         if (!(c->route_off & B32_ROUTE_WIRE_TILES) && c->band_y1 > c->band_y0) {
             const size_t wt = (size_t)fp.tiles_x * ((c->band_y1 - (c->band_y0 / WIRE_TH) * WIRE_TH + WIRE_TH - 1) / WIRE_TH);
-            if (wt > c->cap_wire_tiles || !c->wire_fill) {
-                if ((rc = ensure_plain(c, c->wire_fill, (wt + 2) * FILL_PAD + 64))) return rc;
-                if ((rc = ensure_plain(c, c->wire_lists, wt * WIRE_TILE_CAP + 64))) return rc;
-                c->cap_wire_tiles = wt; c->wire_grid = 0;
+            if (wt > c->cur.cap_wire_tiles || !c->cur.wire_fill) {
+                if ((rc = ensure_plain(c, c->cur.wire_fill, (wt + 2) * FILL_PAD + 64))) return rc;
+                if ((rc = ensure_plain(c, c->cur.wire_lists, wt * WIRE_TILE_CAP + 64))) return rc;
+                c->cur.cap_wire_tiles = wt; c->cur.wire_grid = 0;
             }
             // (the counters are zero between frames: k_wire_tile re-zeroes what k_wire_bin counted; a new allocation or another tile grid
             // -- resize, band change -- starts from a cleared array)
             const unsigned long long grid = ((unsigned long long)c->width << 40) ^ ((unsigned long long)c->band_y0 << 20) ^ c->band_y1;
-            if (grid != c->wire_grid) {
-                HIPCHK(c, hipMemsetAsync(c->wire_fill, 0, ((c->cap_wire_tiles + 2) * FILL_PAD + 64) * sizeof(uint32_t), s));
-                c->wire_grid = grid; c->side_dirty = true;          // (a pipelined frame bins on the side stream: behind this memset)
+            if (grid != c->cur.wire_grid) {
+                HIPCHK(c, hipMemsetAsync(c->cur.wire_fill, 0, ((c->cur.cap_wire_tiles + 2) * FILL_PAD + 64) * sizeof(uint32_t), s));
+                c->cur.wire_grid = grid; c->side_dirty = true;          // (a pipelined frame bins on the side stream: behind this memset)
             }
         }
     }
@@ -236,9 +219,9 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
     // z-buffer frames without a transparent pass take the sort-free fused path too (depth is the priority); otherwise z-buffer
     // mode applies depth + skip rule per fragment (EXACT coverage)
     // (a transparent pass rides along: its entries are split off at binning time and sorted per tile by k_blend)
-    r.with_class = c->may_blend && !c->fmt8;
-    const bool spans_ok = !(c->route_off & B32_ROUTE_SORT_FREE) && c->local_sort_ok && bin_spans_applicable(fp, sc, r.with_class);
-    r.ordered_all = c->fmt8 ? c->blend8 : (fp.xray != 0);
+    r.with_class = c->scene.may_blend && !c->scene.fmt8;
+    const bool spans_ok = !(c->route_off & B32_ROUTE_SORT_FREE) && c->scene.local_sort_ok && bin_spans_applicable(fp, sc, r.with_class);
+    r.ordered_all = c->scene.fmt8 ? c->scene.blend8 : (fp.xray != 0);
     // sort-free path: painter's or z-buffer mode (orthographic keys use all 32 bits -> class pass -> general path)
     r.want_prio64 = spans_ok && !fp.ortho && !r.ordered_all;
     // too few 64x64 tiles to fill the GPU (narrow multi-GPU band, PS1-sized frame): tiles of 32 or 16 rows multiply the parallelism
@@ -256,46 +239,46 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
     const uint32_t ntiles = fp.tiles_x * fp.tiles_y;
     // EXACT coverage = texel rule per fragment: exact store counting, textures with many skippable texels; the keyed z-buffer kernel
     // is EXACT by construction
-    r.exact_cov = c->count_fragments || !c->cheap_ok || (fp.zmode && !r.want_prio64);
+    r.exact_cov = c->count_fragments || !c->scene.cheap_ok || (fp.zmode && !r.want_prio64);
     // the sorted fast path reads the class from bit 31 of the depth key and has no ordered opaque walk: not for ortho / x-ray frames
-    r.local_sort = !r.exact_cov && c->local_sort_ok && !fp.ortho && !r.ordered_all && !fp.zmode;
+    r.local_sort = !r.exact_cov && c->scene.local_sort_ok && !fp.ortho && !r.ordered_all && !fp.zmode;
     fp.band_only = (r.want_prio64 && c->band_set) ? 1 : 0;   // other ranks own the other rows: their surfaces' records are never read here
     // small mesh (what the reference's callers submit per room / asset part): no binning launch, the
     // fused kernel's workgroups collect their own tile lists from the spans (needs one list region of nf entries per tile)
     // (with a transparent pass only up to 2048 faces: no tile's transparent list can then exceed what k_blend sorts in LDS)
-    r.list_stride = (c->nf + 31u) & ~31u;
-    r.want_inline = r.want_prio64 && !wire_front && c->nf <= (r.with_class ? 2048u : 8192u) && (size_t)ntiles * r.list_stride <= ((size_t)4 << 20) &&
+    r.list_stride = (c->scene.nf + 31u) & ~31u;
+    r.want_inline = r.want_prio64 && !wire_front && c->scene.nf <= (r.with_class ? 2048u : 8192u) && (size_t)ntiles * r.list_stride <= ((size_t)4 << 20) &&
                     !(c->route_off & B32_ROUTE_INLINE_BIN);
     // larger meshes: no binning launch either -- k_setup appends every surviving face to fixed-size tile regions (DirectBin)
-    if (c->direct_ntiles != ntiles) { c->direct_ntiles = ntiles; c->direct_cap_opaque = 0; c->direct_ok = true; }   // another tile grid (resize, band)
-    if (r.want_prio64 && !r.want_inline && !wire_front && c->direct_ok && !(c->route_off & B32_ROUTE_DIRECT_BIN) && ntiles) {
+    if (c->scene.direct_ntiles != ntiles) { c->scene.direct_ntiles = ntiles; c->scene.direct_cap_opaque = 0; c->scene.direct_ok = true; }   // another tile grid (resize, band)
+    if (r.want_prio64 && !r.want_inline && !wire_front && c->scene.direct_ok && !(c->route_off & B32_ROUTE_DIRECT_BIN) && ntiles) {
         // first guess: three times the mean list of a mesh whose every face is drawn and touches one tile; a frame that overflows
         // reports its longest list and is redrawn with regions a quarter above it (b32_frame_finish)
-        if (!c->direct_cap_opaque) c->direct_cap_opaque = std::max<uint32_t>(512u, (uint32_t)std::min<uint64_t>((uint64_t)3 * c->nf / ntiles + 64, 1u << 24));
+        if (!c->scene.direct_cap_opaque) c->scene.direct_cap_opaque = std::max<uint32_t>(512u, (uint32_t)std::min<uint64_t>((uint64_t)3 * c->scene.nf / ntiles + 64, 1u << 24));
         // a mesh of moderate size gets regions that hold ALL its faces (at most 32 MB of list space): such a frame can never overflow a
         // region, needs no redraw, and may stay in flight across scene swaps and further frames like a small mesh's
-        if (c->nf <= 65536u && (uint64_t)ntiles * (c->nf + (r.with_class ? BLEND_SORT_CAP : 0u)) <= (8u << 20)) c->direct_cap_opaque = std::max(c->direct_cap_opaque, c->nf);
-        const uint32_t cap_o = (c->direct_cap_opaque + 31u) & ~31u;
+        if (c->scene.nf <= 65536u && (uint64_t)ntiles * (c->scene.nf + (r.with_class ? BLEND_SORT_CAP : 0u)) <= (8u << 20)) c->scene.direct_cap_opaque = std::max(c->scene.direct_cap_opaque, c->scene.nf);
+        const uint32_t cap_o = (c->scene.direct_cap_opaque + 31u) & ~31u;
         const uint32_t region = cap_o + (r.with_class ? BLEND_SORT_CAP : 0u);
         const size_t need = (size_t)ntiles * region + 64;
         if (need <= ((size_t)1 << 28)) {                            // 1 GB of list space at most; beyond that the compact counting sort
-            if (need > c->cap_direct || !c->direct_lists) {
-                if ((rc = ensure_plain(c, c->direct_lists, need + need / 8))) return rc;
-                c->cap_direct = need + need / 8;
+            if (need > c->cur.cap_direct || !c->cur.direct_lists) {
+                if ((rc = ensure_plain(c, c->cur.direct_lists, need + need / 8))) return rc;
+                c->cur.cap_direct = need + need / 8;
             }
             const size_t need_fill = (size_t)ntiles * FILL_PAD + 64;
-            if (need_fill > c->cap_tile_fill || !c->tile_fill) {
-                if ((rc = ensure_plain(c, c->tile_fill, need_fill * 2))) return rc;
-                c->cap_tile_fill = need_fill * 2;
-                HIPCHK(c, hipMemsetAsync(c->tile_fill, 0, c->cap_tile_fill * sizeof(uint32_t), c->stream));   // zero from here on: k_cover re-zeroes what k_setup counted
+            if (need_fill > c->cur.cap_tile_fill || !c->cur.tile_fill) {
+                if ((rc = ensure_plain(c, c->cur.tile_fill, need_fill * 2))) return rc;
+                c->cur.cap_tile_fill = need_fill * 2;
+                HIPCHK(c, hipMemsetAsync(c->cur.tile_fill, 0, c->cur.cap_tile_fill * sizeof(uint32_t), c->stream));   // zero from here on: k_cover re-zeroes what k_setup counted
                 c->side_dirty = true;
             }
             if (++c->epoch == 0) c->epoch = 1;
-            r.db.fill = c->tile_fill; r.db.lists = c->direct_lists; r.db.region = region; r.db.cap_opaque = cap_o;
+            r.db.fill = c->cur.tile_fill; r.db.lists = c->cur.direct_lists; r.db.region = region; r.db.cap_opaque = cap_o;
             r.db.cap_transparent = r.with_class ? BLEND_SORT_CAP : 0u; r.db.with_class = r.with_class ? 1u : 0u; r.db.epoch = c->epoch;
             r.direct_bin = true;
             r.list_stride = region;
-        } else c->direct_ok = false;
+        } else c->scene.direct_ok = false;
     }
     return B32_OK;
 }
@@ -305,22 +288,22 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
 static int frame_positions(b32_ctx* c, const FrameParams& fp, const float*& pos12, const float*& attr12) {
     int rc;
     pos12 = attr12 = nullptr;
-    if (c->nv && c->nf > 8192u && !(c->route_off & B32_ROUTE_PACKED_STREAMS)) {
+    if (c->scene.nv && c->scene.nf > 8192u && !(c->route_off & B32_ROUTE_PACKED_STREAMS)) {
         // streams per vertex, one behind the other: 12 B positions, 12 B (u, v, rgba) and -- only once the mesh has been drawn with a
         // shading pass -- 24 B (u, v, rgba, normal) for lit frames (floats: 3 + 3 [+ 6] per vertex)
         const bool want_lit = fp.shading != B32_SHADE_NONE;
-        if ((!c->pos_valid || (want_lit && !c->lit_valid)) && c->band_frames >= 1) {
-            const bool with_lit = want_lit || c->lit_valid;
-            const size_t need = (size_t)c->nv * (with_lit ? 12 : 6);
-            if (need > c->cap_pos12 || !c->d_pos12) {
-                if ((rc = ensure_plain(c, c->d_pos12, need + 16))) return rc;
-                c->cap_pos12 = need;
+        if ((!c->scene.pos_valid || (want_lit && !c->scene.lit_valid)) && c->scene.band_frames >= 1) {
+            const bool with_lit = want_lit || c->scene.lit_valid;
+            const size_t need = (size_t)c->scene.nv * (with_lit ? 12 : 6);
+            if (need > c->scene.cap_pos12 || !c->scene.d_pos12) {
+                if ((rc = ensure_plain(c, c->scene.d_pos12, need + 16))) return rc;
+                c->scene.cap_pos12 = need;
             }
-            launch_pack_streams(c->stream, c->d_verts, c->nv, c->d_pos12, c->d_pos12 + (size_t)c->nv * 3, with_lit);
-            c->pos_valid = true; c->lit_valid = with_lit; c->side_dirty = true;
+            launch_pack_streams(c->stream, c->scene.d_verts, c->scene.nv, c->scene.d_pos12, c->scene.d_pos12 + (size_t)c->scene.nv * 3, with_lit);
+            c->scene.pos_valid = true; c->scene.lit_valid = with_lit; c->side_dirty = true;
         }
-        c->band_frames++;
-        if (c->pos_valid && (!want_lit || c->lit_valid)) { pos12 = c->d_pos12; attr12 = c->d_pos12 + (size_t)c->nv * 3; }
+        c->scene.band_frames++;
+        if (c->scene.pos_valid && (!want_lit || c->scene.lit_valid)) { pos12 = c->scene.d_pos12; attr12 = c->scene.d_pos12 + (size_t)c->scene.nv * 3; }
     }
     return B32_OK;
 }
@@ -335,34 +318,34 @@ static int bin_keyed(b32_ctx* c, const FrameParams& fp, const Route& r, const So
         // fast path: no global depth sort.  Pairs are emitted in face order from k_setup's spans; k_cover sorts every tile
         // list by depth key in LDS (stable, so ties keep face order).
         if (ev_bin) HIPCHK(c, hipEventRecord(ev_bin, s));
-        launch_bin_faces(s, fp, c->spans, c->keys[0], c->partials, c->d_ctrl, c->pkeys[0], c->pvals[0], (uint32_t)c->cap_pairs, 0);
+        launch_bin_faces(s, fp, c->cur.spans, c->cur.keys0, c->cur.partials, c->cur.d_ctrl, c->pkeys[0], c->pvals[0], (uint32_t)c->cap_pairs, 0);
     } else {
         // painter's order: 4 stable passes over the 32-bit key; pass 1 also compacts away culled faces and its scan kernel
         // reduces k_setup's counters into Ctrl (n_visible feeds the later passes).
-        RadixExtra ex1; ex1.post_ctrl = c->d_ctrl; ex1.partials = c->partials; ex1.npart = (c->nf + 255) / 256;
-        launch_radix_pass(s, c->keys[0], nullptr, c->keys[1], c->vals[1], c->d_consts, c->nf, 0, 8, sc, ex1);
-        launch_radix_pass(s, c->keys[1], c->vals[1], c->keys[0], c->vals[0], &c->d_ctrl->n_visible, c->nf, 8, 8, sc);
-        launch_radix_pass(s, c->keys[0], c->vals[0], c->keys[1], c->vals[1], &c->d_ctrl->n_visible, c->nf, 16, 8, sc);
-        launch_radix_pass(s, c->keys[1], c->vals[1], c->keys[0], c->vals[0], &c->d_ctrl->n_visible, c->nf, 24, 8, sc);
+        RadixExtra ex1; ex1.post_ctrl = c->cur.d_ctrl; ex1.partials = c->cur.partials; ex1.npart = (c->scene.nf + 255) / 256;
+        launch_radix_pass(s, c->cur.keys0, nullptr, c->keys1, c->vals[1], c->scene.d_consts, c->scene.nf, 0, 8, sc, ex1);
+        launch_radix_pass(s, c->keys1, c->vals[1], c->cur.keys0, c->vals[0], &c->cur.d_ctrl->n_visible, c->scene.nf, 8, 8, sc);
+        launch_radix_pass(s, c->cur.keys0, c->vals[0], c->keys1, c->vals[1], &c->cur.d_ctrl->n_visible, c->scene.nf, 16, 8, sc);
+        launch_radix_pass(s, c->keys1, c->vals[1], c->cur.keys0, c->vals[0], &c->cur.d_ctrl->n_visible, c->scene.nf, 24, 8, sc);
         if (fp.ortho) {      // 32-bit depth keys: the opaque/transparent partition is a fifth stable pass on the class
-            launch_class_keys(s, c->crecs, c->vals[0], &c->d_ctrl->n_visible, c->nf, c->keys[0]);
-            launch_radix_pass(s, c->keys[0], c->vals[0], c->keys[1], c->vals[1], &c->d_ctrl->n_visible, c->nf, 0, 8, sc);
-            HIPCHK(c, hipMemcpyAsync(c->vals[0], c->vals[1], (size_t)c->nf * 4, hipMemcpyDeviceToDevice, s));
+            launch_class_keys(s, c->cur.crecs, c->vals[0], &c->cur.d_ctrl->n_visible, c->scene.nf, c->cur.keys0);
+            launch_radix_pass(s, c->cur.keys0, c->vals[0], c->keys1, c->vals[1], &c->cur.d_ctrl->n_visible, c->scene.nf, 0, 8, sc);
+            HIPCHK(c, hipMemcpyAsync(c->vals[0], c->vals[1], (size_t)c->scene.nf * 4, hipMemcpyDeviceToDevice, s));
         }
         if (ev_bin) HIPCHK(c, hipEventRecord(ev_bin, s));
-        launch_bin(s, fp, c->spans, c->vals[0], c->d_ctrl, c->counts, c->block_sums, c->bin_blocks, c->pkeys[0], c->pvals[0], (uint32_t)c->cap_pairs);
+        launch_bin(s, fp, c->cur.spans, c->vals[0], c->cur.d_ctrl, c->counts, c->block_sums, c->bin_blocks, c->pkeys[0], c->pvals[0], (uint32_t)c->cap_pairs);
     }
     const uint32_t n_sort_keys = r.local_sort ? ntiles : 2 * ntiles;          // the fast path groups by tile only
     const uint32_t kb = bits_for(n_sort_keys ? n_sort_keys : 1);
     if (kb <= 8 || kb > 12) {
         for (uint32_t shift = 0; shift < kb; shift += 8) {
-            launch_radix_pass(s, c->pkeys[cur], c->pvals[cur], c->pkeys[cur ^ 1], c->pvals[cur ^ 1], &c->d_ctrl->n_pairs, (uint32_t)c->cap_pairs, (int)shift, 8, sc);
+            launch_radix_pass(s, c->pkeys[cur], c->pvals[cur], c->pkeys[cur ^ 1], c->pvals[cur ^ 1], &c->cur.d_ctrl->n_pairs, (uint32_t)c->cap_pairs, (int)shift, 8, sc);
             cur ^= 1;
         }
-        launch_tile_ranges(s, c->pkeys[cur], c->d_ctrl, (uint32_t)c->cap_pairs, c->ranges, n_sort_keys);
+        launch_tile_ranges(s, c->pkeys[cur], c->cur.d_ctrl, (uint32_t)c->cap_pairs, c->ranges, n_sort_keys);
     } else {    // up to 2048 tiles: one pass groups every (tile, class) list and its digit bases are the list ranges
         RadixExtra exr; exr.ranges_out = c->ranges; exr.n_ranges = n_sort_keys + 1;
-        launch_radix_pass(s, c->pkeys[cur], c->pvals[cur], c->pkeys[cur ^ 1], c->pvals[cur ^ 1], &c->d_ctrl->n_pairs, (uint32_t)c->cap_pairs, 0, kb <= 11 ? 11 : 12, sc, exr);
+        launch_radix_pass(s, c->pkeys[cur], c->pvals[cur], c->pkeys[cur ^ 1], c->pvals[cur ^ 1], &c->cur.d_ctrl->n_pairs, (uint32_t)c->cap_pairs, 0, kb <= 11 ? 11 : 12, sc, exr);
         cur ^= 1;
     }
     return B32_OK;
@@ -370,39 +353,39 @@ static int bin_keyed(b32_ctx* c, const FrameParams& fp, const Route& r, const So
 
 static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const Route& r, int cur, bool wire_front) {
     FillArgs fa{};
-    fa.fp = fp; fa.crecs = c->crecs; fa.srecs = c->srecs; fa.xrecs = c->xrecs; fa.shades = c->shades; fa.pair_vals = c->pvals[cur]; fa.ranges = c->ranges;
-    fa.keys = c->keys[0]; fa.local_sort = r.local_sort ? 1u : 0u; fa.tile_keys_only = (r.local_sort || r.prio64) ? 1u : 0u; fa.tile_mid = c->tile_mid;
-    fa.tex = c->d_tex; fa.texels = c->d_texels; fa.fb = c->fb; fa.vis = c->vis; fa.zbuf = c->zbuf; fa.ctrl = c->d_ctrl;
-    fa.tex0 = c->nt ? c->h_tex[0] : TexDesc{ 0, 0, 0, 0 };
+    fa.fp = fp; fa.crecs = c->cur.crecs; fa.srecs = c->cur.srecs; fa.xrecs = c->cur.xrecs; fa.shades = c->cur.shades; fa.pair_vals = c->pvals[cur]; fa.ranges = c->ranges;
+    fa.keys = c->cur.keys0; fa.local_sort = r.local_sort ? 1u : 0u; fa.tile_keys_only = (r.local_sort || r.prio64) ? 1u : 0u; fa.tile_mid = c->tile_mid;
+    fa.tex = c->scene.d_tex; fa.texels = c->scene.d_texels; fa.fb = c->fb; fa.vis = c->vis; fa.zbuf = c->zbuf; fa.ctrl = c->cur.d_ctrl;
+    fa.tex0 = c->scene.nt ? c->scene.h_tex[0] : TexDesc{ 0, 0, 0, 0 };
     fa.lds_tex_texels = 0;
-    if (c->nt == 1 && r.exact_cov) {                     // (CHEAP coverage: one texel fetch per output pixel, served by L1/L2)
-        const size_t n = (size_t)c->h_tex[0].width * c->h_tex[0].height;
+    if (c->scene.nt == 1 && r.exact_cov) {                     // (CHEAP coverage: one texel fetch per output pixel, served by L1/L2)
+        const size_t n = (size_t)c->scene.h_tex[0].width * c->scene.h_tex[0].height;
         if (n > 0 && n * 2 <= fill_lds_tex_budget()) fa.lds_tex_texels = (uint32_t)n;
     }
     fa.exact_coverage = r.exact_cov ? 1u : 0u;
-    fa.may_blend = c->may_blend ? 1u : 0u;
+    fa.may_blend = c->scene.may_blend ? 1u : 0u;
     fa.skip_solid = wire_front ? 1u : 0u;
-    fa.texels32 = c->d_texels32;
+    fa.texels32 = c->scene.d_texels32;
     fa.ordered_all = r.ordered_all ? 1u : 0u;
     fa.prio64 = r.prio64 ? 1u : 0u;
     fa.narrow_only = (c->route_off & B32_ROUTE_WIDE_GROUPS) ? 1u : 0u;
-    fa.texmask = c->d_texmask;
-    { const uint32_t words = c->pool_texels / 32 + 2; fa.mask_lds_words = (c->pool_texels && words <= MASK_LDS_MAX_WORDS) ? words : 0u; }
-    fa.inline_bin = r.inline_bin ? 1u : 0u; fa.list_stride = r.list_stride; fa.spans = c->spans; fa.partials = c->partials;
+    fa.texmask = c->scene.d_texmask;
+    { const uint32_t words = c->scene.pool_texels / 32 + 2; fa.mask_lds_words = (c->scene.pool_texels && words <= MASK_LDS_MAX_WORDS) ? words : 0u; }
+    fa.inline_bin = r.inline_bin ? 1u : 0u; fa.list_stride = r.list_stride; fa.spans = c->cur.spans; fa.partials = c->cur.partials;
     if (r.inline_bin) fa.pair_vals = c->inline_lists;
-    fa.direct_bin = r.direct_bin ? 1u : 0u; fa.tile_fill = c->tile_fill; fa.epoch = c->epoch;
-    if (r.direct_bin) fa.pair_vals = c->direct_lists;
+    fa.direct_bin = r.direct_bin ? 1u : 0u; fa.tile_fill = c->cur.tile_fill; fa.epoch = c->epoch;
+    if (r.direct_bin) fa.pair_vals = c->cur.direct_lists;
     fa.gather_blend = (r.prio64 && r.with_class) ? 1u : 0u;
     fa.stagger = (c->route_off & B32_ROUTE_STAGGER) ? 0u : 1u;       // (launch_fill decides whether the frame qualifies)
     fa.span_cover = (r.prio64 && !r.exact_cov && !fp.zmode && !(c->route_off & B32_ROUTE_SPAN_COVER)) ? 1u : 0u;
     // index atlas + CLUT sampled from LDS: the fused kernel with one indexed texture, when they fit beside the tile planes of the
     // workgroup form launch_fill is going to choose (16 waves, one workgroup per CU: ~84 KB; two 8-wave workgroups per CU: ~6 KB)
-    fa.atlas0 = c->d_atlas0; fa.atlas_idx_bytes = 0;
-    if (r.prio64 && !c->fmt8 && c->nt == 1 && c->atlas_idx_bytes && !(c->route_off & B32_ROUTE_LDS_ATLAS)) {
+    fa.atlas0 = c->scene.d_atlas0; fa.atlas_idx_bytes = 0;
+    if (r.prio64 && !c->scene.fmt8 && c->scene.nt == 1 && c->scene.atlas_idx_bytes && !(c->route_off & B32_ROUTE_LDS_ATLAS)) {
         const bool wide = fp.tiles_x * fp.tiles_y <= (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
-        if (c->atlas_idx_bytes + ATLAS_CLUT_BYTES + 16u <= fill_lds_atlas_room(wide)) fa.atlas_idx_bytes = c->atlas_idx_bytes;
+        if (c->scene.atlas_idx_bytes + ATLAS_CLUT_BYTES + 16u <= fill_lds_atlas_room(wide)) fa.atlas_idx_bytes = c->scene.atlas_idx_bytes;
     }
-    if (c->fmt8) fa.fp.xray = 0;                        // render_mesh: x-ray only changes culling; its stores keep their own depth tests
+    if (c->scene.fmt8) fa.fp.xray = 0;                        // render_mesh: x-ray only changes culling; its stores keep their own depth tests
     return fa;
 }
 
@@ -424,7 +407,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // (not on the legacy default stream -- hipStreamLegacy, what torch's default stream maps to: it synchronises implicitly with every
     // blocking stream, and recording / waiting cross-stream events on that handle crashed the runtime, found when safe mode began to
     // leave superseded frames in flight)
-    if (c->frame_pending && c->pipe_hint && !c->redrawing && !prof_all && c->nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
+    if (c->frame_pending && c->pipe_hint && !c->redrawing && !prof_all && c->scene.nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
         c->stream != hipStreamLegacy) {
         if ((rc = pipeline_ensure(c))) return rc;
         rotate_sets(c);
@@ -472,10 +455,10 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     c->last_local_sort = r.local_sort || r.want_prio64;                         // the global draw order is not materialised
     c->last_exact = r.ordered_all ? true : (r.exact_cov && !fp.zmode);          // the ordered walk counts every store it performs
     c->last_direct = r.direct_bin;
-    if (c->nf == 0) {                                                             // otherwise k_setup resets it (all but `sticky`)
-        HIPCHK(c, hipMemsetAsync(c->d_ctrl, 0, offsetof(Ctrl, sticky), s));
-        HIPCHK(c, hipMemsetAsync(&c->d_ctrl->fragments, 0, sizeof(unsigned long long), s));
-        HIPCHK(c, hipMemsetAsync(c->d_ctrl + 1, 0, sizeof(Stamps), s));          // (and the phase clock: b32_last_shader_clock of an empty frame is 0, not the frame before's)
+    if (c->scene.nf == 0) {                                                             // otherwise k_setup resets it (all but `sticky`)
+        HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl, 0, offsetof(Ctrl, sticky), s));
+        HIPCHK(c, hipMemsetAsync(&c->cur.d_ctrl->fragments, 0, sizeof(unsigned long long), s));
+        HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl + 1, 0, sizeof(Stamps), s));          // (and the phase clock: b32_last_shader_clock of an empty frame is 0, not the frame before's)
     }
     const float *pos12 = nullptr, *attr12 = nullptr;
     if ((rc = frame_positions(c, fp, pos12, attr12))) return fail(rc);
@@ -507,28 +490,28 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         // (b32_debug_inject(ctx, 2): the fill in front did not publish its start -- this gate's patience is 2 ms, then the error)
         const uint32_t start_patience = c->start_lost ? 200000u : 200000000u;
         c->start_lost = false;                               // (one gate only, whichever way this frame is ordered)
-        if (gate_need || start_gate) launch_gate(ss, c->alt[0].d_ctrl, gate_need, 30000u /* 300 us */, start_gate ? polled_seq : 0u, c->d_ctrl, start_patience);      // alt[0]: the frame n_sets - 1 back (rotate_sets)
+        if (gate_need || start_gate) launch_gate(ss, c->alt[0].d_ctrl, gate_need, 30000u /* 300 us */, start_gate ? polled_seq : 0u, c->cur.d_ctrl, start_patience);      // alt[0]: the frame n_sets - 1 back (rotate_sets)
     }
     // (the wire kernels' arguments: known before the setup kernel is launched -- a pipelined frame bins its wire list on the side stream)
-    const bool wire_on = fp.wire_collect && c->nf;
+    const bool wire_on = fp.wire_collect && c->scene.nf;
     bool wire_binned = false, wire_polled = false;
     WireArgs wa{};
     if (wire_on) {
-        wa.tris = c->wire; wa.nf = c->nf; wa.table_owner = c->wire_owner; wa.table_first = c->wire_first;
+        wa.tris = c->cur.wire; wa.nf = c->scene.nf; wa.table_owner = c->wire_owner; wa.table_first = c->wire_first;
         wa.table_mask = c->cap_wire_table ? (uint32_t)(c->cap_wire_table - 1) : 0;
         wa.fb = c->fb; wa.zbuf = (c->zbuf && c->zbuf_valid) ? c->zbuf : nullptr;
-        wa.width = c->width; wa.height = c->height; wa.band_y0 = c->band_y0; wa.band_y1 = c->band_y1; wa.ctrl = c->d_ctrl;
+        wa.width = c->width; wa.height = c->height; wa.band_y0 = c->band_y0; wa.band_y1 = c->band_y1; wa.ctrl = c->cur.d_ctrl;
         if (++c->wire_seq == 0) c->wire_seq = 1;
         wa.epoch = c->wire_seq;
-        if (!(c->route_off & B32_ROUTE_WIRE_TILES) && c->wire_fill && c->band_y1 > c->band_y0) {
+        if (!(c->route_off & B32_ROUTE_WIRE_TILES) && c->cur.wire_fill && c->band_y1 > c->band_y0) {
             wa.tile_yb = (c->band_y0 / WIRE_TH) * WIRE_TH; wa.tiles_x = (c->width + TILE_W - 1) / TILE_W;
             wa.tiles_y = (c->band_y1 - wa.tile_yb + WIRE_TH - 1) / WIRE_TH;
-            if ((size_t)wa.tiles_x * wa.tiles_y <= c->cap_wire_tiles) { wa.tile_fill = c->wire_fill; wa.tile_lists = c->wire_lists; c->wire_tile_frames++; }
+            if ((size_t)wa.tiles_x * wa.tiles_y <= c->cur.cap_wire_tiles) { wa.tile_fill = c->cur.wire_fill; wa.tile_lists = c->cur.wire_lists; c->wire_tile_frames++; }
         }
     }
     if (prof_all) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_setup(ss, fp, c->d_verts, c->d_faces, c->d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->crecs, c->srecs, c->xrecs }, r.db, c->shades, c->keys[0],
-                 r.direct_bin ? nullptr : c->spans /* (direct binning: nobody reads the spans) */, c->partials, c->d_ctrl, c->wire, c->n_cu, pos12, attr12, c->face_of);
+    launch_setup(ss, fp, c->scene.d_verts, c->scene.d_faces, c->scene.d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->cur.crecs, c->cur.srecs, c->cur.xrecs }, r.db, c->cur.shades, c->cur.keys0,
+                 r.direct_bin ? nullptr : c->cur.spans /* (direct binning: nobody reads the spans) */, c->cur.partials, c->cur.d_ctrl, c->cur.wire, c->n_cu, pos12, attr12, c->cur.face_of);
     // The merged draws of a batched frame: the hand-over polled by the fused kernel itself (FillArgs::join_seq) -- their fills are few 16-wave
     // workgroups (at most 5 / 8 of the CUs: the setup kernel they may have to spin for keeps the rest of the GPU), the setup kernel of draw
     // k + 1 has normally finished beside draw k's fill and blend pass, and what the cross-stream event cost the main stream per draw (6.5 us
@@ -541,7 +524,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         const bool lose_flag = (c->inject & 1u) != 0;
         c->inject &= ~1u;
         if (++c->join_seq == 0) c->join_seq = 1;
-        launch_flag_poll(c->side, c->d_ctrl, lose_flag ? c->join_seq ^ 0x40000000u : c->join_seq);
+        launch_flag_poll(c->side, c->cur.d_ctrl, lose_flag ? c->join_seq ^ 0x40000000u : c->join_seq);
         poll_seq = c->join_seq; poll_patience = lose_flag ? 200000u : 200000000u;
         c->flag_join_frames++; c->poll_join_frames++;
     } else if (c->pipelined && r.direct_bin && c->join_ok && !c->frame_batched) {
@@ -550,12 +533,12 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         // (b32_debug_inject(ctx, 1): this frame's flag carries another epoch and the join's patience is 2 ms -- the "setup kernel never arrived" path)
         const bool lose_flag = (c->inject & 1u) != 0;
         c->inject &= ~1u;
-        launch_flag(c->side, c->d_ctrl, lose_flag ? c->epoch ^ 0x40000000u : c->epoch);
-        launch_join(s, c->d_ctrl, c->epoch, lose_flag ? 200000u : 200000000u /* 2 s: a last resort -- queues of an oversubscribed GPU are time-sliced in milliseconds */);
+        launch_flag(c->side, c->cur.d_ctrl, lose_flag ? c->epoch ^ 0x40000000u : c->epoch);
+        launch_join(s, c->cur.d_ctrl, c->epoch, lose_flag ? 200000u : 200000000u /* 2 s: a last resort -- queues of an oversubscribed GPU are time-sliced in milliseconds */);
         c->flag_join_frames++;
     } else if (c->pipelined) {
-        hipError_t e1 = hipEventRecord(c->ev_setup, c->side);
-        if (e1 == hipSuccess) e1 = hipStreamWaitEvent(s, c->ev_setup, 0);
+        hipError_t e1 = hipEventRecord(c->cur.ev_setup, c->side);
+        if (e1 == hipSuccess) e1 = hipStreamWaitEvent(s, c->cur.ev_setup, 0);
         if (e1 != hipSuccess) { (void)hipStreamSynchronize(c->side); c->last_hip = (int)e1; return B32_E_HIP; }
         c->event_join_frames++;
     }
@@ -563,11 +546,11 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         launch_wire_bin(c->side, wa, wire_back, wire_front, true);
         // (back-face edges: the first wire kernel on the main stream, k_wire_table_clear, looks at Events::wbin_done itself -- no event
         // for the main stream to wait for; the overlay alone has no such kernel in front of k_wire_tile and keeps the event)
-        if (wire_back) { launch_flag_wbin(c->side, c->d_ctrl, wa.epoch); wire_polled = true; }
+        if (wire_back) { launch_flag_wbin(c->side, c->cur.d_ctrl, wa.epoch); wire_polled = true; }
         else HIPCHK(c, hipEventRecord(c->ev_wbin, c->side));
         wire_binned = true;
     }
-    c->set_in_flight = true;
+    c->cur.in_flight = true;
     if (prof_all) HIPCHK(c, hipEventRecord(ev[1], s));
 
     // ---- tile lists
@@ -585,15 +568,14 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         r.prio64 = r.inline_bin = true;
     } else if (r.want_prio64) {
         if (prof_all) HIPCHK(c, hipEventRecord(ev[2], s));
-        r.prio64 = launch_bin_spans(s, fp, c->spans, r.with_class ? c->keys[0] : nullptr, c->partials, c->d_ctrl, sc, (uint32_t)c->cap_pairs, c->ranges,
+        r.prio64 = launch_bin_spans(s, fp, c->cur.spans, r.with_class ? c->cur.keys0 : nullptr, c->cur.partials, c->cur.d_ctrl, sc, (uint32_t)c->cap_pairs, c->ranges,
                                     c->tile_mid, BLEND_SORT_CAP, c->pvals[0]);
     }
     if (!r.prio64 && (rc = bin_keyed(c, fp, r, sc, prof_all ? ev[2] : nullptr, cur))) return rc;
-    c->last_pair_buf = cur;
     c->routes[r.direct_bin ? 0 : r.inline_bin ? 1 : r.prio64 ? 2 : 3]++;
     // (direct binning with regions that hold the whole mesh, and no more faces that can be transparent than k_blend sorts per tile:
     // nothing can overflow)
-    const bool direct_safe = r.direct_bin && r.db.cap_opaque >= c->nf && (!r.with_class || c->blend_faces <= BLEND_SORT_CAP);
+    const bool direct_safe = r.direct_bin && r.db.cap_opaque >= c->scene.nf && (!r.with_class || c->scene.blend_faces <= BLEND_SORT_CAP);
     c->pending_may_redraw = !(r.inline_bin || direct_safe);
     if (prof_fill) HIPCHK(c, hipEventRecord(ev[3], s));
 
@@ -618,7 +600,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
         // (a frame with a depth buffer to reset: only in z-buffer mode, where the fused kernel owns the depth buffer too -- it seeds its
         // winners with f32::MAX instead of reading the buffer and writes f32::MAX where nothing is drawn)
         const bool has_z = c->zbuf && c->zbuf_valid;
-        if (r.prio64 && !wire_front && !r.ordered_all && (!has_z || fp.zmode) && c->nf && ntiles && c->clear_y0 == c->band_y0 && c->clear_y1 == c->band_y1) {
+        if (r.prio64 && !wire_front && !r.ordered_all && (!has_z || fp.zmode) && c->scene.nf && ntiles && c->clear_y0 == c->band_y0 && c->clear_y1 == c->band_y1) {
             fa.clear_on = 1; fa.clear_rgba = c->clear_rgba; fa.clear_depth = (has_z && fp.zmode) ? 1u : 0u; c->clear_pending = false;
         } else if ((rc = flush_clear(c))) return rc;
     }
@@ -629,27 +611,27 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // ---- wireframe phases
     if (wire_on) {
         if (wire_binned && !wire_polled) HIPCHK(c, hipStreamWaitEvent(s, c->ev_wbin, 0));
-        launch_wire(s, wa, wire_back, wire_front, wire_binned, wire_polled ? c->d_ctrl : nullptr, wa.epoch);
+        launch_wire(s, wa, wire_back, wire_front, wire_binned, wire_polled ? c->cur.d_ctrl : nullptr, wa.epoch);
     }
     if (prof_fill) { if (prof_all) HIPCHK(c, hipEventRecord(ev[5], s)); c->ev_frames++; }
     c->last_cover_tiles = (r.prio64 && !wire_front && !r.ordered_all) ? ntiles : 0u;
     c->last_cover_groups = std::min<uint32_t>(ntiles, (uint32_t)c->n_cu * 2u);
     {   // remembered per frame set
         b32_ctx::CoverOf* slot = &c->cover_of[0];
-        for (auto& co : c->cover_of) { if (co.ctrl == c->d_ctrl) { slot = &co; break; } if (!co.ctrl) slot = &co; }
-        *slot = { c->d_ctrl, c->last_cover_tiles, c->last_cover_groups, c->last_cover_tiles ? start_seq_meant : 0u };
+        for (auto& co : c->cover_of) { if (co.ctrl == c->cur.d_ctrl) { slot = &co; break; } if (!co.ctrl) slot = &co; }
+        *slot = { c->cur.d_ctrl, c->last_cover_tiles, c->last_cover_groups, c->last_cover_tiles ? start_seq_meant : 0u };
     }
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
 
 int b32_render_scene_15_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog) {
-    if (!c || c->fmt8) return B32_E_ARG;                 // the resident scene holds Texture (8-bit) texels: use b32_render_scene
+    if (!c || c->scene.fmt8) return B32_E_ARG;                 // the resident scene holds Texture (8-bit) texels: use b32_render_scene
     c->frame_batched = false;
     return render_scene_async_any(c, cam, st, fog, nullptr);
 }
 int b32_render_scene_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st) {
-    if (!c || !c->fmt8) return B32_E_ARG;
+    if (!c || !c->scene.fmt8) return B32_E_ARG;
     c->frame_batched = false;
     return render_scene_async_any(c, cam, st, nullptr, nullptr);
 }
@@ -657,10 +639,10 @@ int b32_render_scene_async(b32_ctx* c, const B32Camera* cam, const B32Settings* 
 int b32_render_scene_15_placed_async(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place) {
     if (!c) return B32_E_ARG;
     c->frame_batched = false;
-    return render_scene_async_any(c, cam, st, c->fmt8 ? nullptr : fog, place);      // (render_mesh takes no fog)
+    return render_scene_async_any(c, cam, st, c->scene.fmt8 ? nullptr : fog, place);      // (render_mesh takes no fog)
 }
 int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place) {
-    if (!c || !cam || !st || !c->fb || !c->have_scene) return B32_E_ARG;
+    if (!c || !cam || !st || !c->fb || !c->scene.have_scene) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     int rc = validate_settings(st);
     if (rc) return rc;
@@ -726,13 +708,13 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
         // the frame's counters come back through the pinned arena (one small kernel writing host memory) rather than an SDMA copy:
         // ~5 us of stream time less per synchronous frame
         if (stage_ensure(c)) {
-            launch_ctrl_out(c->stream, c->d_ctrl, static_cast<unsigned char*>(c->stage_dev) + STAGE_CTRL_OFF);
+            launch_ctrl_out(c->stream, c->cur.d_ctrl, static_cast<unsigned char*>(c->stage_dev) + STAGE_CTRL_OFF);
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::memcpy(&c->h_ctrl, c->stage_host + STAGE_CTRL_OFF, sizeof(Ctrl));
             std::memcpy(&c->h_stamps, c->stage_host + STAGE_CTRL_OFF + sizeof(Ctrl), sizeof(Stamps));
         } else {
             unsigned char tmp[sizeof(Ctrl) + sizeof(Stamps)];
-            HIPCHK(c, hipMemcpyAsync(tmp, c->d_ctrl, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(tmp, c->cur.d_ctrl, sizeof(tmp), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::memcpy(&c->h_ctrl, tmp, sizeof(Ctrl)); std::memcpy(&c->h_stamps, tmp + sizeof(Ctrl), sizeof(Stamps));
             c->h_stamps.t[ST_END] = 0;
@@ -740,7 +722,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
         if ((c->h_ctrl.need_global_sort & 2u) && c->last_direct) {
             // direct binning: a tile region was too small and nothing was drawn; redraw this frame with regions a quarter above the
             // longest list it reported (enqueue_frame falls back to the compact counting sort if those would not fit)
-            c->direct_cap_opaque = c->h_ctrl.list_demand + c->h_ctrl.list_demand / 4 + 64;
+            c->scene.direct_cap_opaque = c->h_ctrl.list_demand + c->h_ctrl.list_demand / 4 + 64;
             if (no_redraw) break;
             c->routes[4]++;
             c->ev_frames = 0;
@@ -750,10 +732,10 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
             if (rc) return rc;
             continue;
         }
-        if ((c->h_ctrl.need_global_sort & 1u) && c->local_sort_ok) {
+        if ((c->h_ctrl.need_global_sort & 1u) && c->scene.local_sort_ok) {
             // a tile list was longer than the LDS sort handles: nothing was drawn; redraw this frame (and the following ones of
             // this scene) with the global depth sort
-            c->local_sort_ok = false;
+            c->scene.local_sort_ok = false;
             if (no_redraw) break;
             c->routes[5]++;
             c->ev_frames = 0;
@@ -779,10 +761,10 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
     }
     c->frame_pending = false;
     c->pending_superseded = false;
-    c->set_in_flight = false;
+    c->cur.in_flight = false;
     collect_events(c);
     uint32_t sticky = c->h_ctrl.sticky;                        // errors of every frame enqueued since the last finish
-    if (sticky) HIPCHK(c, hipMemsetAsync(&c->d_ctrl->sticky, 0, sizeof(uint32_t), c->stream));
+    if (sticky) HIPCHK(c, hipMemsetAsync(&c->cur.d_ctrl->sticky, 0, sizeof(uint32_t), c->stream));
     if (sticky) c->side_dirty = true;                           // (the next setup kernel on the side stream reads that word: after the memset)
     for (FrameSet& o : c->alt) if (o.in_flight && o.d_ctrl) {
         // several frames in flight: the frames of the other sets since the last finish -- their sticky errors, and each set's last frame,
@@ -814,7 +796,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
         // frames that follow bin into empty lists again)
         if (c->side) HIPCHK(c, hipStreamSynchronize(c->side));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->tile_fill) HIPCHK(c, hipMemsetAsync(c->tile_fill, 0, c->cap_tile_fill * sizeof(uint32_t), c->stream));
+        if (c->cur.tile_fill) HIPCHK(c, hipMemsetAsync(c->cur.tile_fill, 0, c->cur.cap_tile_fill * sizeof(uint32_t), c->stream));
         for (FrameSet& o : c->alt) if (o.tile_fill) HIPCHK(c, hipMemsetAsync(o.tile_fill, 0, o.cap_tile_fill * sizeof(uint32_t), c->stream));
         c->side_dirty = true;
         return B32_E_HIP;
@@ -831,7 +813,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
         // the finished batch of frames take their place.
         const unsigned long long* t = c->h_stamps.t;
         const unsigned long long t_end = t[ST_END] ? t[ST_END] : 0ull;
-        if (c->nf && t[ST_SETUP] && t[ST_FILL] >= t[ST_SETUP]) {
+        if (c->scene.nf && t[ST_SETUP] && t[ST_FILL] >= t[ST_SETUP]) {
             const unsigned long long t_bin = t[ST_BIN] ? t[ST_BIN] : t[ST_FILL];
             const unsigned long long t_fill_end = t[ST_WIRE] ? t[ST_WIRE] : t_end;
             out->cull_ms = (float)(t_bin - t[ST_SETUP]) * 1e-5f;

@@ -174,7 +174,7 @@ int b32_band_wait(b32_ctx* c, uint32_t rank, uint32_t frame_no, uint32_t timeout
     if (!c || !c->band_sync_own || rank == 0 || rank >= BAND_RANKS) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     hipLaunchKernelGGL(k_band_wait, dim3(1), dim3(1), 0, c->stream, c->band_sync_own + (size_t)rank * BAND_STRIDE, frame_no,
-                       (unsigned long long)timeout_us * 100ull, c->band_sync_own + BAND_TIMEOUT_WORD, c->d_ctrl);
+                       (unsigned long long)timeout_us * 100ull, c->band_sync_own + BAND_TIMEOUT_WORD, c->cur.d_ctrl);
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
@@ -185,7 +185,7 @@ int b32_band_wait_all(b32_ctx* c, uint32_t nranks, uint32_t frame_no, uint32_t t
     if (release_after) { const int rc = flush_clear(c); if (rc) return rc; }      // (as b32_band_release)
     if (nranks == 1 && !release_after) return B32_OK;
     hipLaunchKernelGGL(k_band_wait_all, dim3(1), dim3(64), 0, c->stream, c->band_sync_own, nranks, frame_no, (unsigned long long)timeout_us * 100ull,
-                       release_after ? 1u : 0u, c->d_ctrl);
+                       release_after ? 1u : 0u, c->cur.d_ctrl);
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
@@ -203,7 +203,7 @@ int b32_band_acquire(b32_ctx* c, uint32_t frame_no, uint32_t timeout_us) {
     if (!c || !c->band_sync || c->band_rank == 0) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     hipLaunchKernelGGL(k_band_wait, dim3(1), dim3(1), 0, c->stream, c->band_sync + BAND_ROOT_WORD, frame_no, (unsigned long long)timeout_us * 100ull,
-                       c->band_sync + BAND_TIMEOUT_WORD, c->d_ctrl);
+                       c->band_sync + BAND_TIMEOUT_WORD, c->cur.d_ctrl);
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }

@@ -1,5 +1,7 @@
-// b32_host.h -- what the translation units of the C ABI share: the context (b32_ctx), a scene slot (b32_scene), a frame set, the
-// allocation helpers, and the handful of functions one unit calls in another.  Internal: nothing here is part of include/b32raster.h.
+// b32_host.h -- what the translation units of the C ABI share: an uploaded scene (b32_scene), a frame set (FrameSet), the context that
+// holds one resident scene and up to three frame sets as members of those types (b32_ctx), the allocation helpers, and the handful of
+// functions one unit calls in another.  A buffer of a scene or of a frame set is named in ONE free list, the struct's release().
+// Internal: nothing here is part of include/b32raster.h.
 //   b32_api.hip    context, stream, framebuffer calls, test taps and switches
 //   b32_scene.hip  uploads (drop-in and resident), scene slots, the synchronous drop-in calls
 //   b32_frame.hip  one frame: route, enqueue, two / three frames in flight, b32_frame_finish
@@ -22,20 +24,34 @@ constexpr int EV_RING = 64;     // frames of per-phase events kept between two b
 constexpr int EV_PER_FRAME = 6; // start | setup | sort | bin | cover | shade+blend
 }
 
-// Everything k_setup WRITES for one frame and the fill kernels read: a context owns two of these so that the setup kernel of frame
-// i + 1 can run on a second stream beside the fill of frame i (see pipeline_begin).  The context's own members of the same names are
-// the set of the frame being enqueued; `alt` holds the other ones, oldest first (rotate_sets).
+// Everything k_setup WRITES for one frame and the fill kernels read: a context owns two or three of these so that the setup kernel of
+// frame i + 1 can run on a second stream beside the fill of frame i (see pipeline_begin).  b32_ctx::cur is the set of the frame being
+// enqueued; b32_ctx::alt holds the other ones, oldest first (rotate_sets exchanges whole structs).
+// cap_work is the element count the per-face buffers of THIS set were allocated for and travels with them.  b32_ctx::cap_work is what
+// the mesh needs (it also sizes the per-face buffers all sets share): ensure_work brings `cur` to it, pipeline_ensure -- which runs before
+// every rotate_sets -- brings each `alt` in use to it, so the set a frame is enqueued on always has cap_work == b32_ctx::cap_work.
 struct FrameSet {
-    uint32_t* keys0 = nullptr; CovRec* crecs = nullptr; ShadeRec* srecs = nullptr; AuxRec* xrecs = nullptr;
-    uint32_t* spans = nullptr; uint32_t* face_of = nullptr; uint32_t* partials = nullptr; size_t cap_work = 0;
+    uint32_t* keys0 = nullptr; CovRec* crecs = nullptr; ShadeRec* srecs = nullptr; AuxRec* xrecs = nullptr;     // painter's keys, per-face records (b32_device.h)
+    uint32_t* spans = nullptr; uint32_t* partials = nullptr; size_t cap_work = 0;
+    uint32_t* face_of = nullptr;        // record slot -> face id (k_setup packs each wave's survivors to the front of its 64 slots)
     float* shades = nullptr; size_t cap_shades = 0;
+    // direct binning (DirectBin, b32_device.h): k_setup appends to fixed tile regions; the regions grow when a frame overflowed one
     uint32_t* direct_lists = nullptr; size_t cap_direct = 0;
-    uint32_t* tile_fill = nullptr; size_t cap_tile_fill = 0;
+    uint32_t* tile_fill = nullptr; size_t cap_tile_fill = 0;      // FILL_PAD words per tile, zero between frames
     WireTri* wire = nullptr; size_t cap_wire = 0;           // (frames with wireframe phases: k_setup writes the wire list, the wire kernels behind the fill read it)
-    uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0; unsigned long long wire_grid = 0;   // (... and its tile lists: binned beside the previous frame's fill)
+    uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0;   // (... and its tile lists, WireArgs: binned beside the previous frame's fill)
+    unsigned long long wire_grid = 0;                                                   // tile grid the (self-resetting) counters belong to
     Ctrl* d_ctrl = nullptr;
     hipEvent_t ev_setup = nullptr;                         // k_setup finished (side stream)
     bool in_flight = false;                                  // a frame was enqueued on this set since the last b32_frame_finish
+    // Frees the buffers and leaves the set empty (the caller has drained both streams).  The control block, the event and in_flight
+    // survive: pipeline_ensure re-sizes a set that stays in use; b32_destroy releases those two for all three sets.
+    void release() {
+        for (void* p : { (void*)keys0, (void*)crecs, (void*)srecs, (void*)xrecs, (void*)spans, (void*)face_of, (void*)partials, (void*)shades,
+                         (void*)direct_lists, (void*)tile_fill, (void*)wire, (void*)wire_fill, (void*)wire_lists }) if (p) (void)hipFree(p);
+        FrameSet e; e.d_ctrl = d_ctrl; e.ev_setup = ev_setup; e.in_flight = in_flight;
+        *this = e;
+    }
 };
 
 // What one ordered tile pass (b32_draw_pass.h) keeps in the context.  A batch too large for the kernel argument is copied into a pinned
@@ -54,6 +70,52 @@ struct DrawPassState {
     }
 };
 
+// Texture cache of the drop-in calls ("texture upload may be cached by (ptr,len,hash) but must be semantically per-call"):
+// what the texel pool currently holds -- per texture the caller's pointer, its dimensions, blend mode and a 64-bit hash of its
+// content.  A call that passes the same set again (the reference's callers pass the same Texture15 slice every frame) skips the
+// texel copies and the skippable-texel count; any change of pointer, size or content re-uploads.
+struct TexSig { const void* ptr; uint32_t w, h, blend; uint64_t hash; };
+
+// Everything that belongs to ONE uploaded scene: b32_ctx::scene is the resident one, a slot of b32_scene_swap (or a merged mesh of a
+// batched frame) another; b32_scene_swap exchanges whole structs.  What is per context (the routes' switches, h_consts, last_direct,
+// epoch, the frame sets) is not here.
+struct b32_scene {
+    B32Vertex* d_verts = nullptr; size_t cap_verts = 0;
+    B32Face* d_faces = nullptr; size_t cap_faces = 0;
+    uint16_t* d_texels = nullptr; size_t cap_texels = 0;
+    uint32_t* d_texels32 = nullptr; size_t cap_texels32 = 0;   // 8-bit-colour path: Color texels
+    TexDesc* d_tex = nullptr; size_t cap_tex = 0;
+    std::vector<TexDesc> h_tex;
+    uint32_t* d_consts = nullptr;       // (h_consts on the device: the face count the first radix pass reads)
+    uint8_t* d_atlas0 = nullptr; size_t cap_atlas0 = 0; uint32_t atlas_idx_bytes = 0;   // indexed upload of ONE texture: CLUT (512 B) + index bytes, kept for the LDS route
+    uint32_t* d_texmask = nullptr; size_t cap_texmask = 0;       // skip mask of the texel pool (FillArgs.texmask), rebuilt when the pool changes
+    uint32_t pool_texels = 0; bool mask_dirty = true;
+    uint32_t nv = 0, nf = 0, nt = 0;
+    bool have_scene = false;
+    unsigned long long gen = 0;         // identity of the scene's content (every upload gets a new number)
+    bool fmt8 = false;                  // uploaded by b32_scene_upload_rgba (render_mesh path)
+    bool blend8 = false;                // 8-bit path: some texel blends or some face has editor_alpha < 255 -> ordered walk
+    bool may_blend = true;              // some face / texture can produce a transparent-pass surface (render.rs:2403-2415)
+    bool cheap_ok = false;              // every texture has few skippable texels: CHEAP coverage + repair is profitable
+    bool tex_blend_any = false;         // some texture has a blend mode other than Opaque
+    uint32_t blend_faces = 0;           // faces that their own blend mode / editor alpha or their texture's blend mode puts in the transparent pass
+    bool local_sort_ok = true;          // no tile list of this scene has exceeded the LDS sort capacity so far
+    // direct binning (DirectBin, b32_device.h): what the scene's frames taught about its tile regions
+    uint32_t direct_cap_opaque = 0;     // opaque entries per tile region (0: sized from the mesh on first use)
+    uint32_t direct_ntiles = 0;         // the tile grid that size belongs to (another grid: sized again)
+    bool direct_ok = true;              // false: the regions would not fit (one tile's list too long) -> counting sort
+    // packed vertex streams of a resident mesh (k_pack_streams: nv positions of 12 B, then nv (u, v, rgba) of 12 B): built on the second
+    // frame of an uploaded mesh too large for the in-kernel list collection
+    float* d_pos12 = nullptr; size_t cap_pos12 = 0; bool pos_valid = false; uint32_t band_frames = 0;
+    bool lit_valid = false;             // ... and the 24-byte lit stream behind them (packed on the first frame with a shading pass)
+    std::vector<TexSig> tex_sig; bool tex_sig_valid = false;
+    // The only list of a scene's device buffers (the caller has drained the streams that use them).
+    void release() {
+        for (void* p : { (void*)d_verts, (void*)d_faces, (void*)d_texels, (void*)d_texels32, (void*)d_tex, (void*)d_consts, (void*)d_texmask,
+                         (void*)d_pos12, (void*)d_atlas0 }) if (p) (void)hipFree(p);
+    }
+};
+
 struct b32_ctx {
     int device = 0;
     int n_cu = 256;
@@ -61,12 +123,12 @@ struct b32_ctx {
     hipStream_t own_stream = nullptr, stream = nullptr;
     // two frames in flight: the setup kernel of the next frame on `side` beside the fill of the current one on `stream`
     hipStream_t side = nullptr; hipEvent_t ev_main = nullptr, ev_wbin = nullptr;     // (ev_wbin: a pipelined frame's k_wire_bin finished on the side stream)
+    FrameSet cur;                        // the frame set of the frame being enqueued
     FrameSet alt[2];                     // the other frame sets, oldest first (allocated on first use; alt[1] only with three sets)
     uint32_t n_sets_user = 0;            // what b32_set_pipeline_depth asked for (0: the library's own choice, see auto_depth in b32_api.hip)
     uint32_t n_sets = 2;                 // b32_set_pipeline_depth: 2 = setup(i+1) beside fill(i); 3 = setup(i+2) beside fill(i), so that the
                                          // setup kernel a fill waits for ended a whole fill ago (fills back to back; measured slower: the two
                                          // kernels then share the CUs all the time and the frame is bound by their summed VALU work)
-    hipEvent_t ev_setup = nullptr; bool set_in_flight = false;     // (members of the current set, see FrameSet)
     bool side_dirty = true;              // something k_setup reads was written on `stream` since the side stream last waited for it
     hipStream_t join_stream = nullptr; bool join_ok = false;   // k_flag / k_join instead of an event: only while `stream` and `side` have DIFFERENT priorities (then they never share a hardware queue); checked per main stream
     uint32_t gate_permille = 0;          // b32_set_pipeline_gate: hold the next setup kernel until the previous fill's tile cursor has got this far (0: only until that fill has started -- the frame sets' order, k_gate)
@@ -94,63 +156,23 @@ struct b32_ctx {
     void* band_fb_ipc = nullptr; uint32_t* band_sync_own = nullptr; uint32_t* band_sync = nullptr;      // (band_sync_own: inside fb_own's tail)
     uint32_t band_rank = 0; bool band_attached = false;
 
-    // resident scene
-    B32Vertex* d_verts = nullptr; size_t cap_verts = 0;
-    B32Face* d_faces = nullptr; size_t cap_faces = 0;
-    uint16_t* d_texels = nullptr; size_t cap_texels = 0;
-    uint32_t* d_texels32 = nullptr; size_t cap_texels32 = 0;   // 8-bit-colour path: Color texels
-    bool fmt8 = false;                  // the resident scene was uploaded by b32_scene_upload_rgba (render_mesh path)
-    bool blend8 = false;                // 8-bit path: some texel blends or some face has editor_alpha < 255 -> ordered walk
-    TexDesc* d_tex = nullptr; size_t cap_tex = 0;
-    std::vector<TexDesc> h_tex;
-    uint8_t* d_atlas0 = nullptr; size_t cap_atlas0 = 0; uint32_t atlas_idx_bytes = 0;   // indexed upload of ONE texture: CLUT (512 B) + index bytes, kept for the LDS route
-    uint32_t* d_texmask = nullptr; size_t cap_texmask = 0;       // skip mask of the texel pool (FillArgs.texmask), rebuilt when the pool changes
-    uint32_t pool_texels = 0; bool mask_dirty = true;
-    uint32_t nv = 0, nf = 0, nt = 0;
-    bool have_scene = false;
-    unsigned long long gen = 0;         // identity of the resident scene's content (every upload gets a new number; swapped with the slots)
-    bool may_blend = true;              // some face / texture can produce a transparent-pass surface (render.rs:2403-2415)
-    bool cheap_ok = false;              // every texture has few skippable texels: CHEAP coverage + repair is profitable
-    bool tex_blend_any = false;         // some texture of the resident scene has a blend mode other than Opaque
-    uint32_t blend_faces = 0;           // faces that their own blend mode / editor alpha or their texture's blend mode puts in the transparent pass
-    // Texture cache of the drop-in calls ("texture upload may be cached by (ptr,len,hash) but must be semantically per-call"):
-    // what the texel pool currently holds -- per texture the caller's pointer, its dimensions, blend mode and a 64-bit hash of its
-    // content.  A call that passes the same set again (the reference's callers pass the same Texture15 slice every frame) skips the
-    // texel copies and the skippable-texel count; any change of pointer, size or content re-uploads.
-    struct TexSig { const void* ptr; uint32_t w, h, blend; uint64_t hash; };
-    std::vector<TexSig> tex_sig; bool tex_sig_valid = false;
+    b32_scene scene;                    // the resident scene (b32_scene_swap exchanges it with a slot)
     int count_fragments = 0;            // 1: exact fragment-store count every frame (EXACT coverage); instrumentation, off by default
     bool last_exact = false;            // the last frame ran EXACT coverage in painter's mode (B32Timings.fragments is exact)
 
-    // per-face work buffers
-    size_t cap_work = 0;
-    uint32_t *keys[2] = { nullptr, nullptr }, *vals[2] = { nullptr, nullptr };
-    CovRec* crecs = nullptr; ShadeRec* srecs = nullptr; AuxRec* xrecs = nullptr;      // per-face records (b32_device.h)
-    float* shades = nullptr; size_t cap_shades = 0;
+    // per-face work buffers shared by all frame sets (the keyed routes' sort and binning: launches on the main stream only)
+    size_t cap_work = 0;                // elements the resident mesh needs: these buffers' size and every frame set's in use (see FrameSet)
+    uint32_t *keys1 = nullptr, *vals[2] = { nullptr, nullptr };   // (keys1: the radix passes' second key buffer beside cur.keys0)
     uint32_t* counts = nullptr; uint32_t* block_sums = nullptr; uint32_t bin_blocks = 0;
-    uint32_t* spans = nullptr;
-    uint32_t* face_of = nullptr;        // record slot -> face id (k_setup packs each wave's survivors to the front of its 64 slots)
     uint32_t* tile_mid = nullptr; size_t cap_tile_mid = 0;
-    bool local_sort_ok = true;          // no tile list of this scene has exceeded the LDS sort capacity so far
     bool last_local_sort = false;       // the last frame took the fast path (draw order not materialised)
     uint32_t route_off = 0;             // b32_set_routes: B32_ROUTE_* bits switched off (tests keep the older pipelines covered with it)
     uint32_t cheap_den = 64;            // b32_set_cheap_threshold
     // pairs
     size_t cap_pairs = 0;
     uint32_t* inline_lists = nullptr; size_t cap_inline = 0;      // small meshes: one list region per tile, filled inside k_cover
-    // direct binning (DirectBin, b32_device.h): k_setup appends to fixed tile regions; the regions grow when a frame overflowed one
-    uint32_t* direct_lists = nullptr; size_t cap_direct = 0;
-    uint32_t* tile_fill = nullptr; size_t cap_tile_fill = 0;      // FILL_PAD words per tile, zero between frames
-    // packed vertex streams of a resident mesh (k_pack_streams: nv positions of 12 B, then nv (u, v, rgba) of 12 B): built on the second
-    // frame of an uploaded mesh too large for the in-kernel list collection
-    float* d_pos12 = nullptr; size_t cap_pos12 = 0; bool pos_valid = false; uint32_t band_frames = 0;
-    bool lit_valid = false;             // ... and the 24-byte lit stream behind them (packed on the first frame with a shading pass)
-    // (per scene, swapped with the scene slots:)
-    uint32_t direct_cap_opaque = 0;                               // opaque entries per tile region (0: sized from the mesh on first use)
-    uint32_t direct_ntiles = 0;                                   // the tile grid that size belongs to (another grid: sized again)
-    bool direct_ok = true;                                        // false: the regions would not fit (one tile's list too long) -> counting sort
-    bool last_direct = false;
-    uint32_t epoch = 0;
+    bool last_direct = false;           // the last frame took the direct-binning route
+    uint32_t epoch = 0;                 // DirectBin / FillArgs::epoch of the last direct-binned frame (never 0).  Both per context: not part of a scene slot
     // Framebuffer::clear deferred (b32_fb_clear): applied by the next frame's fused kernel when that frame takes the sort-free path in
     // painter's mode on the same band, else by a clear launch before whatever touches the framebuffer next (flush_clear)
     bool clear_pending = false; uint32_t clear_rgba = 0, clear_y0 = 0, clear_y1 = 0;
@@ -159,15 +181,12 @@ struct b32_ctx {
     uint32_t *pkeys[2] = { nullptr, nullptr }, *pvals[2] = { nullptr, nullptr };
     // sort scratch
     uint32_t* block_hist = nullptr; uint32_t hist_blocks = 0; uint32_t* digit_total = nullptr;
-    uint32_t* partials = nullptr; uint32_t partial_blocks = 0;
+    uint32_t partial_blocks = 0;
     // tiles
     uint32_t* ranges = nullptr; size_t cap_ranges = 0;
     uint32_t* vis = nullptr; size_t cap_vis = 0;
-    // wireframe phases (allocated on first use)
-    WireTri* wire = nullptr; size_t cap_wire = 0;
+    // wireframe phases (allocated on first use; the wire list and its tile lists belong to the frame set)
     uint32_t *wire_owner = nullptr, *wire_first = nullptr; size_t cap_wire_table = 0;
-    uint32_t *wire_fill = nullptr, *wire_lists = nullptr; size_t cap_wire_tiles = 0;     // tile route of the wireframe phases (WireArgs)
-    unsigned long long wire_grid = 0;                                                       // tile grid the (self-resetting) counters belong to
     unsigned long long wire_tile_frames = 0;
     DrawPassState<B32Line> lines;                                 // b32_draw_lines
     DrawPassState<B32Prim> prims;                                 // b32_draw_prims
@@ -180,8 +199,8 @@ struct b32_ctx {
     hipEvent_t world_ev[2] = {}; bool world_timed = false;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
-    Ctrl* d_ctrl = nullptr; uint32_t* d_consts = nullptr; Ctrl h_ctrl{}; Stamps h_stamps{};   // (d_ctrl: Ctrl followed by Stamps)
-    uint32_t h_consts[4] = { 0, 0, 0, 0 };   // staging for d_consts (outlives the async copy)
+    Ctrl h_ctrl{}; Stamps h_stamps{};          // host copies of the frame set's control block (FrameSet::d_ctrl: Ctrl followed by Stamps)
+    uint32_t h_consts[4] = { 0, 0, 0, 0 };   // staging for scene.d_consts (outlives the async copy)
     bool defer_upload_sync = false;            // drop-in calls: the frame's own synchronisation covers the uploads
     // staged upload of the drop-in calls (see UploadSegs): the caller's slices are packed into a pinned arena on the host and one
     // kernel moves them; active only inside b32_render_mesh[_15], which always synchronise before they return
@@ -207,7 +226,6 @@ struct b32_ctx {
     bool redrawing = false;             // enqueue_frame is repeating the pending frame (k_setup must not count it as lost)
     int deferred_rc = 0;                // error of a frame that b32_scene_swap had to settle: reported by the next b32_frame_finish
     B32Camera last_cam{}; B32Settings last_settings{}; B32Fog last_fog{}; bool last_has_fog = false;
-    int last_pair_buf = 0;
 
     // asynchronous framebuffer downloads (b32_fb_download_async): ticket t completes with event dl_ev[t % DL_RING]
     static constexpr uint32_t DL_RING = 8;
@@ -225,26 +243,6 @@ struct b32_ctx {
     uint32_t phase_frames = 0;
     int phase_level = 0;                // profiling level those averages were taken at
     std::vector<B32Light> keep_lights;  // private copy of the last frame's lights (redraw after overflow)
-};
-
-// A slot of b32_scene_swap: everything of b32_ctx that belongs to ONE uploaded scene.
-struct b32_scene {
-    B32Vertex* d_verts = nullptr; size_t cap_verts = 0;
-    B32Face* d_faces = nullptr; size_t cap_faces = 0;
-    uint16_t* d_texels = nullptr; size_t cap_texels = 0;
-    uint32_t* d_texels32 = nullptr; size_t cap_texels32 = 0;
-    TexDesc* d_tex = nullptr; size_t cap_tex = 0;
-    uint32_t* d_consts = nullptr;
-    uint32_t* d_texmask = nullptr; size_t cap_texmask = 0; uint32_t pool_texels = 0; bool mask_dirty = true;
-    uint8_t* d_atlas0 = nullptr; size_t cap_atlas0 = 0; uint32_t atlas_idx_bytes = 0;
-    std::vector<TexDesc> h_tex;
-    uint32_t nv = 0, nf = 0, nt = 0;
-    unsigned long long gen = 0;
-    uint32_t blend_faces = 0;
-    bool fmt8 = false, blend8 = false, have_scene = false, may_blend = true, cheap_ok = false, local_sort_ok = true, tex_blend_any = false;
-    uint32_t direct_cap_opaque = 0, direct_ntiles = 0; bool direct_ok = true;
-    float* d_pos12 = nullptr; size_t cap_pos12 = 0; bool pos_valid = false; uint32_t band_frames = 0; bool lit_valid = false;
-    std::vector<b32_ctx::TexSig> tex_sig; bool tex_sig_valid = false;
 };
 
 #define HIPCHK(ctx, expr)                                                 \
@@ -315,7 +313,6 @@ B32_INTERNAL int flush_clear(b32_ctx* c);                                       
 B32_INTERNAL int apply_depth_auto(b32_ctx* c);                                    // b32_api.hip (b32_set_pipeline_depth(ctx, 0): the depth the library picks)
 constexpr size_t FB_TAIL_BYTES = 8192;      // behind the pixels of a library-owned framebuffer: the epoch words of the band exchange (b32_gather.hip)
 B32_INTERNAL void band_close_any(b32_ctx* c);                                    // b32_gather.hip
-B32_INTERNAL void free_alt(b32_ctx* c, FrameSet& a);                              // b32_frame.hip
 B32_INTERNAL int h2d(b32_ctx* c, void* dst, const void* src, size_t bytes);       // b32_scene.hip
 B32_INTERNAL bool stage_ensure(b32_ctx* c);                                       // b32_scene.hip
 B32_INTERNAL int ensure_work(b32_ctx* c, uint32_t nf);                            // b32_scene.hip

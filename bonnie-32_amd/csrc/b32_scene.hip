@@ -51,21 +51,24 @@ static void stage_flush(b32_ctx* c) {        // enqueue the one copy kernel (ord
 // per-face work buffers of the current frame set for a mesh of nf faces
 int ensure_work(b32_ctx* c, uint32_t nf) {
     int rc;
-    if ((size_t)nf + 1 > c->cap_work || !c->crecs) {
+    if ((size_t)nf + 1 > c->cap_work || !c->cur.crecs) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const size_t n = (size_t)nf + nf / 4 + 16;
-        for (int i = 0; i < 2; ++i) { if ((rc = ensure_plain(c, c->keys[i], n))) return rc; if ((rc = ensure_plain(c, c->vals[i], n))) return rc; }
-        if ((rc = ensure_plain(c, c->crecs, n))) return rc;
-        if ((rc = ensure_plain(c, c->srecs, n))) return rc;
-        if ((rc = ensure_plain(c, c->xrecs, n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.keys0, n))) return rc;
+        if ((rc = ensure_plain(c, c->vals[0], n))) return rc;
+        if ((rc = ensure_plain(c, c->keys1, n))) return rc;
+        if ((rc = ensure_plain(c, c->vals[1], n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.crecs, n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.srecs, n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.xrecs, n))) return rc;
         if ((rc = ensure_plain(c, c->counts, n))) return rc;
-        if ((rc = ensure_plain(c, c->spans, n))) return rc;
-        if ((rc = ensure_plain(c, c->face_of, n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.spans, n))) return rc;
+        if ((rc = ensure_plain(c, c->cur.face_of, n))) return rc;
         c->bin_blocks = (uint32_t)((n + 4095) / 4096);
         c->partial_blocks = (uint32_t)((n + 255) / 256);
-        if ((rc = ensure_plain(c, c->partials, (size_t)c->partial_blocks * 8 + 8))) return rc;
+        if ((rc = ensure_plain(c, c->cur.partials, (size_t)c->partial_blocks * 8 + 8))) return rc;
         if ((rc = ensure_plain(c, c->block_sums, (size_t)c->bin_blocks + 1))) return rc;
-        c->cap_work = n;
+        c->cap_work = c->cur.cap_work = n;
     }
     return B32_OK;
 }
@@ -73,8 +76,8 @@ int ensure_work(b32_ctx* c, uint32_t nf) {
 static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf) {
     if ((nv && !v) || (nf && !f)) return B32_E_ARG;
     int rc;
-    if ((rc = ensure(c, c->d_verts, c->cap_verts, (size_t)nv + 1))) return rc;
-    if ((rc = ensure(c, c->d_faces, c->cap_faces, (size_t)nf + 1))) return rc;
+    if ((rc = ensure(c, c->scene.d_verts, c->scene.cap_verts, (size_t)nv + 1))) return rc;
+    if ((rc = ensure(c, c->scene.d_faces, c->scene.cap_faces, (size_t)nf + 1))) return rc;
     {   // can any face end up in the transparent pass? (face blend mode / editor alpha; texture blend modes are added by the callers)
         uint32_t nb = 0;
         uint32_t nbt = 0;                    // ... counting the faces a texture's blend mode puts there too (render.rs:2403-2415)
@@ -82,23 +85,23 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
             const bool own = f[i].blend_mode != B32_BLEND_OPAQUE || f[i].editor_alpha < 255;
             const uint32_t t = f[i].texture_id;
             nb += own ? 1u : 0u;
-            nbt += (own || (t != B32_NO_TEXTURE && t < c->nt && t < c->h_tex.size() && c->h_tex[t].blend_mode != B32_BLEND_OPAQUE)) ? 1u : 0u;
+            nbt += (own || (t != B32_NO_TEXTURE && t < c->scene.nt && t < c->scene.h_tex.size() && c->scene.h_tex[t].blend_mode != B32_BLEND_OPAQUE)) ? 1u : 0u;
         }
-        c->may_blend = nb != 0; c->blend_faces = nbt;
+        c->scene.may_blend = nb != 0; c->scene.blend_faces = nbt;
     }
-    if ((rc = h2d(c, c->d_verts, v, (size_t)nv * sizeof(B32Vertex)))) return rc;
-    if ((rc = h2d(c, c->d_faces, f, (size_t)nf * sizeof(B32Face)))) return rc;
+    if ((rc = h2d(c, c->scene.d_verts, v, (size_t)nv * sizeof(B32Vertex)))) return rc;
+    if ((rc = h2d(c, c->scene.d_faces, f, (size_t)nf * sizeof(B32Face)))) return rc;
     // a mesh of another size: tile regions sized afresh (the per-frame drop-in call uploads the same mesh again and again: what an
     // overflowing frame taught the context stays)
-    if (c->nf != nf) { c->direct_cap_opaque = 0; c->direct_ntiles = 0; c->direct_ok = true; }
-    c->nv = nv; c->nf = nf;
-    c->local_sort_ok = true;
-    c->pos_valid = false; c->lit_valid = false; c->band_frames = 0;
+    if (c->scene.nf != nf) { c->scene.direct_cap_opaque = 0; c->scene.direct_ntiles = 0; c->scene.direct_ok = true; }
+    c->scene.nv = nv; c->scene.nf = nf;
+    c->scene.local_sort_ok = true;
+    c->scene.pos_valid = false; c->scene.lit_valid = false; c->scene.band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;
-    c->gen = ++c->gen_counter;
+    c->scene.gen = ++c->gen_counter;
     c->h_consts[0] = nf;
-    if (!c->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_consts), 16 * sizeof(uint32_t)));   // (swapped away with a scene)
-    if ((rc = h2d(c, c->d_consts, c->h_consts, sizeof(c->h_consts)))) return rc;
+    if (!c->scene.d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->scene.d_consts), 16 * sizeof(uint32_t)));   // (swapped away with a scene)
+    if ((rc = h2d(c, c->scene.d_consts, c->h_consts, sizeof(c->h_consts)))) return rc;
     // the caller may reuse its host buffers as soon as an upload call returns; the drop-in render calls return only after
     // b32_frame_finish has synchronised the stream, so they skip this extra round trip
     if (!c->defer_upload_sync) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -111,26 +114,26 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
 
 static int layout_textures(b32_ctx* c, uint32_t nt, const uint32_t* w, const uint32_t* h, const uint32_t* blend, size_t* total, bool rgba = false) {
     if (nt > 65534) return B32_E_UNSUPPORTED;        // the surface record holds the texture slot in 16 bits
-    c->h_tex.resize(nt);
-    c->tex_blend_any = false;
-    c->atlas_idx_bytes = 0;                         // (only b32_scene_upload_indexed with one texture keeps the index atlas)
+    c->scene.h_tex.resize(nt);
+    c->scene.tex_blend_any = false;
+    c->scene.atlas_idx_bytes = 0;                         // (only b32_scene_upload_indexed with one texture keeps the index atlas)
     size_t off = 0;
     for (uint32_t i = 0; i < nt; ++i) {
         if (w[i] > 65535 || h[i] > 65535) return B32_E_ARG;
-        if (blend[i] != B32_BLEND_OPAQUE) c->tex_blend_any = true;
-        c->h_tex[i] = { w[i], h[i], blend[i], (uint32_t)off };
+        if (blend[i] != B32_BLEND_OPAQUE) c->scene.tex_blend_any = true;
+        c->scene.h_tex[i] = { w[i], h[i], blend[i], (uint32_t)off };
         off += ((size_t)w[i] * h[i] + 7) & ~(size_t)7;
         if (off > 0x7FFFFFFFull) return B32_E_ARG;
     }
     *total = off + 8;
-    c->pool_texels = (uint32_t)off; c->mask_dirty = true;
+    c->scene.pool_texels = (uint32_t)off; c->scene.mask_dirty = true;
     int rc;
-    if ((rc = ensure(c, c->d_texmask, c->cap_texmask, off / 32 + 4))) return rc;
-    if (rgba) { if ((rc = ensure(c, c->d_texels32, c->cap_texels32, *total))) return rc; }
-    else if ((rc = ensure(c, c->d_texels, c->cap_texels, *total))) return rc;
-    if ((rc = ensure(c, c->d_tex, c->cap_tex, (size_t)nt + 1))) return rc;
-    if ((rc = h2d(c, c->d_tex, c->h_tex.data(), nt * sizeof(TexDesc)))) return rc;
-    c->nt = nt;
+    if ((rc = ensure(c, c->scene.d_texmask, c->scene.cap_texmask, off / 32 + 4))) return rc;
+    if (rgba) { if ((rc = ensure(c, c->scene.d_texels32, c->scene.cap_texels32, *total))) return rc; }
+    else if ((rc = ensure(c, c->scene.d_texels, c->scene.cap_texels, *total))) return rc;
+    if ((rc = ensure(c, c->scene.d_tex, c->scene.cap_tex, (size_t)nt + 1))) return rc;
+    if ((rc = h2d(c, c->scene.d_tex, c->scene.h_tex.data(), nt * sizeof(TexDesc)))) return rc;
+    c->scene.nt = nt;
     return B32_OK;
 }
 
@@ -159,41 +162,41 @@ int b32_scene_upload(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face*
     // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
     // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
     { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    c->have_scene = false;
+    c->scene.have_scene = false;
     std::vector<uint32_t> w(nt), h(nt), bl(nt);
     for (uint32_t i = 0; i < nt; ++i) {
         w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
         if (!tex[i].pixels) w[i] = h[i] = 0;                                // pixels.is_empty() -> sample() returns TRANSPARENT
     }
     // texture cache: the same set as the pool holds (pointer, size, blend mode, content hash of every texture)?
-    std::vector<b32_ctx::TexSig> sig(nt);
+    std::vector<TexSig> sig(nt);
     for (uint32_t i = 0; i < nt; ++i) sig[i] = { tex[i].pixels, w[i], h[i], bl[i], hash_bytes(tex[i].pixels, (size_t)w[i] * h[i] * 2) };
-    bool hit = c->tex_sig_valid && !(c->route_off & B32_ROUTE_TEX_CACHE) && c->tex_sig.size() == nt && c->nt == nt && c->d_texels && c->d_tex;
+    bool hit = c->scene.tex_sig_valid && !(c->route_off & B32_ROUTE_TEX_CACHE) && c->scene.tex_sig.size() == nt && c->scene.nt == nt && c->scene.d_texels && c->scene.d_tex;
     for (uint32_t i = 0; hit && i < nt; ++i) {
-        const b32_ctx::TexSig& o = c->tex_sig[i];
+        const TexSig& o = c->scene.tex_sig[i];
         hit = o.ptr == sig[i].ptr && o.w == sig[i].w && o.h == sig[i].h && o.blend == sig[i].blend && o.hash == sig[i].hash;
     }
     int rc;
     if (!hit) {
-        c->tex_sig_valid = false;
+        c->scene.tex_sig_valid = false;
         size_t total = 0;
         rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total);
         if (rc) return rc;
-        c->cheap_ok = true;
+        c->scene.cheap_ok = true;
         for (uint32_t i = 0; i < nt; ++i) {
             const size_t n = (size_t)w[i] * h[i];
-            if ((rc = h2d(c, c->d_texels + c->h_tex[i].offset, tex[i].pixels, n * 2))) return rc;
+            if ((rc = h2d(c, c->scene.d_texels + c->scene.h_tex[i].offset, tex[i].pixels, n * 2))) return rc;
             size_t skippable = 0;                                               // texels the black_transparent rule can skip
             const uint16_t* px = tex[i].pixels;
             for (size_t k = 0; k < n; ++k) skippable += (px[k] & 0x7FFF) == 0;
-            if (n == 0 || skippable * c->cheap_den > n) c->cheap_ok = false;
+            if (n == 0 || skippable * c->cheap_den > n) c->scene.cheap_ok = false;
         }
-        c->tex_sig.swap(sig); c->tex_sig_valid = true;
+        c->scene.tex_sig.swap(sig); c->scene.tex_sig_valid = true;
     }
     if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
-    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->may_blend = true;
-    c->fmt8 = false;
-    c->have_scene = true;
+    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->scene.may_blend = true;
+    c->scene.fmt8 = false;
+    c->scene.have_scene = true;
     return B32_OK;
 }
 
@@ -203,36 +206,36 @@ int b32_scene_upload_rgba(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32
     // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
     // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
     { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    c->have_scene = false;
+    c->scene.have_scene = false;
     std::vector<uint32_t> w(nt), h(nt), bl(nt);
     for (uint32_t i = 0; i < nt; ++i) {
         w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
         if (!tex[i].pixels) w[i] = h[i] = 0;                                // pixels.is_empty() -> Color::TRANSPARENT
     }
     size_t total = 0;
-    c->tex_sig_valid = false;                                               // (the pool is rewritten below)
+    c->scene.tex_sig_valid = false;                                               // (the pool is rewritten below)
     int rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total, true);
     if (rc) return rc;
-    c->cheap_ok = true;
+    c->scene.cheap_ok = true;
     bool blend_texels = false;
     for (uint32_t i = 0; i < nt; ++i) {
         const size_t n = (size_t)w[i] * h[i];
-        if ((rc = h2d(c, c->d_texels32 + c->h_tex[i].offset, tex[i].pixels, n * 4))) return rc;
+        if ((rc = h2d(c, c->scene.d_texels32 + c->scene.h_tex[i].offset, tex[i].pixels, n * 4))) return rc;
         size_t skippable = 0;                                               // Erase texels: the fragment is skipped (render.rs:1348)
         for (size_t k = 0; k < n; ++k) {
             const uint8_t b = tex[i].pixels[k * 4 + 3];
             skippable += b == B32_BLEND_ERASE;
             blend_texels |= b != B32_BLEND_OPAQUE && b != B32_BLEND_ERASE;
         }
-        if (n == 0 || skippable * c->cheap_den > n) c->cheap_ok = false;
+        if (n == 0 || skippable * c->cheap_den > n) c->scene.cheap_ok = false;
     }
     if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
     bool alpha_faces = false;
     for (uint32_t i = 0; i < nf && !alpha_faces; ++i) alpha_faces = f[i].editor_alpha < 255;
-    c->blend8 = blend_texels || alpha_faces;
-    c->may_blend = false;
-    c->fmt8 = true;
-    c->have_scene = true;
+    c->scene.blend8 = blend_texels || alpha_faces;
+    c->scene.may_blend = false;
+    c->scene.fmt8 = true;
+    c->scene.have_scene = true;
     return B32_OK;
 }
 
@@ -242,20 +245,20 @@ int b32_scene_upload_indexed(b32_ctx* c, const B32Vertex* v, uint32_t nv, const 
     // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
     // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
     { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    c->have_scene = false;
+    c->scene.have_scene = false;
     std::vector<uint32_t> w(nt), h(nt), bl(nt);
     for (uint32_t i = 0; i < nt; ++i) {
         w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
         if (!tex[i].indices || !tex[i].clut) w[i] = h[i] = 0;
     }
     size_t total = 0;
-    c->tex_sig_valid = false;                                               // (the pool is rewritten below)
+    c->scene.tex_sig_valid = false;                                               // (the pool is rewritten below)
     int rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total);
     if (rc) return rc;
-    c->cheap_ok = true;
+    c->scene.cheap_ok = true;
     for (uint32_t i = 0; i < nt; ++i) {
         const size_t n = (size_t)w[i] * h[i];
-        if (!n) { c->cheap_ok = false; continue; }
+        if (!n) { c->scene.cheap_ok = false; continue; }
         // the expansion kernel also counts the texels the black_transparent rule can skip (no walk over the texels on the host)
         uint8_t* d_idx = nullptr; uint16_t* d_clut = nullptr; uint32_t* d_cnt = nullptr;
         Scratch tmp(c);
@@ -264,29 +267,29 @@ int b32_scene_upload_indexed(b32_ctx* c, const B32Vertex* v, uint32_t nv, const 
         // the fused kernel can stage them in LDS (B32_ROUTE_LDS_ATLAS); the expansion below reads the same copies
         const bool keep = nt == 1 && tex[i].clut_len <= 256u && n <= (160u << 10);
         if (keep) {
-            if ((rc = ensure(c, c->d_atlas0, c->cap_atlas0, (size_t)ATLAS_CLUT_BYTES + n + 32))) return rc;
-            HIPCHK(c, hipMemsetAsync(c->d_atlas0, 0, ATLAS_CLUT_BYTES, c->stream));
-            if ((rc = h2d(c, c->d_atlas0, tex[i].clut, (size_t)tex[i].clut_len * 2))) return rc;
-            if ((rc = h2d(c, c->d_atlas0 + ATLAS_CLUT_BYTES, tex[i].indices, n))) return rc;
-            HIPCHK(c, hipMemsetAsync(c->d_atlas0 + ATLAS_CLUT_BYTES + n, 0, 32, c->stream));      // (the staging copy reads whole 16-byte quads)
-            d_clut = reinterpret_cast<uint16_t*>(c->d_atlas0); d_idx = c->d_atlas0 + ATLAS_CLUT_BYTES;
-            c->atlas_idx_bytes = (uint32_t)n;
+            if ((rc = ensure(c, c->scene.d_atlas0, c->scene.cap_atlas0, (size_t)ATLAS_CLUT_BYTES + n + 32))) return rc;
+            HIPCHK(c, hipMemsetAsync(c->scene.d_atlas0, 0, ATLAS_CLUT_BYTES, c->stream));
+            if ((rc = h2d(c, c->scene.d_atlas0, tex[i].clut, (size_t)tex[i].clut_len * 2))) return rc;
+            if ((rc = h2d(c, c->scene.d_atlas0 + ATLAS_CLUT_BYTES, tex[i].indices, n))) return rc;
+            HIPCHK(c, hipMemsetAsync(c->scene.d_atlas0 + ATLAS_CLUT_BYTES + n, 0, 32, c->stream));      // (the staging copy reads whole 16-byte quads)
+            d_clut = reinterpret_cast<uint16_t*>(c->scene.d_atlas0); d_idx = c->scene.d_atlas0 + ATLAS_CLUT_BYTES;
+            c->scene.atlas_idx_bytes = (uint32_t)n;
         } else {
             if ((rc = tmp.upload(tex[i].indices, n, &d_idx))) return rc;
             if ((rc = tmp.upload(tex[i].clut, (size_t)tex[i].clut_len, &d_clut))) return rc;
         }
         if ((rc = tmp.alloc(&d_cnt, 1))) return rc;
         HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4, c->stream));
-        launch_expand_indexed(c->stream, d_idx, (uint32_t)n, d_clut, tex[i].clut_len, c->d_texels + c->h_tex[i].offset, d_cnt);
+        launch_expand_indexed(c->stream, d_idx, (uint32_t)n, d_clut, tex[i].clut_len, c->scene.d_texels + c->scene.h_tex[i].offset, d_cnt);
         uint32_t skippable = 0;
         HIPCHK(c, hipMemcpyAsync(&skippable, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((size_t)skippable * c->cheap_den > n) c->cheap_ok = false;
+        if ((size_t)skippable * c->cheap_den > n) c->scene.cheap_ok = false;
     }
     if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
-    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->may_blend = true;
-    c->fmt8 = false;
-    c->have_scene = true;
+    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->scene.may_blend = true;
+    c->scene.fmt8 = false;
+    c->scene.have_scene = true;
     return B32_OK;
 }
 
@@ -300,8 +303,7 @@ void b32_scene_destroy(b32_ctx* c, b32_scene* sl) {
     if (!c || !sl) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = { sl->d_verts, sl->d_faces, sl->d_texels, sl->d_texels32, sl->d_tex, sl->d_consts, sl->d_texmask, sl->d_pos12, sl->d_atlas0 };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    sl->release();
     delete sl;
 }
 int b32_scene_swap(b32_ctx* c, b32_scene* sl) {
@@ -310,23 +312,7 @@ int b32_scene_swap(b32_ctx* c, b32_scene* sl) {
     // the redraw needs that scene.  Frames of small meshes never redraw and stay in flight.
     // Its error, if any, is the frame's error: kept for the b32_frame_finish that ends the frame (the exchange itself goes ahead).
     { const int rc = settle_pending(c); if (rc) return rc; }
-    std::swap(c->d_verts, sl->d_verts); std::swap(c->cap_verts, sl->cap_verts);
-    std::swap(c->d_faces, sl->d_faces); std::swap(c->cap_faces, sl->cap_faces);
-    std::swap(c->d_texels, sl->d_texels); std::swap(c->cap_texels, sl->cap_texels);
-    std::swap(c->d_texels32, sl->d_texels32); std::swap(c->cap_texels32, sl->cap_texels32);
-    std::swap(c->d_tex, sl->d_tex); std::swap(c->cap_tex, sl->cap_tex);
-    std::swap(c->d_consts, sl->d_consts);
-    std::swap(c->d_texmask, sl->d_texmask); std::swap(c->cap_texmask, sl->cap_texmask); std::swap(c->pool_texels, sl->pool_texels);
-    std::swap(c->mask_dirty, sl->mask_dirty);
-    std::swap(c->d_atlas0, sl->d_atlas0); std::swap(c->cap_atlas0, sl->cap_atlas0); std::swap(c->atlas_idx_bytes, sl->atlas_idx_bytes);
-    c->h_tex.swap(sl->h_tex);
-    std::swap(c->nv, sl->nv); std::swap(c->nf, sl->nf); std::swap(c->nt, sl->nt);
-    std::swap(c->fmt8, sl->fmt8); std::swap(c->blend8, sl->blend8); std::swap(c->have_scene, sl->have_scene); std::swap(c->gen, sl->gen); std::swap(c->blend_faces, sl->blend_faces);
-    std::swap(c->may_blend, sl->may_blend); std::swap(c->cheap_ok, sl->cheap_ok); std::swap(c->local_sort_ok, sl->local_sort_ok);
-    std::swap(c->tex_blend_any, sl->tex_blend_any);
-    std::swap(c->direct_cap_opaque, sl->direct_cap_opaque); std::swap(c->direct_ntiles, sl->direct_ntiles); std::swap(c->direct_ok, sl->direct_ok);
-    std::swap(c->d_pos12, sl->d_pos12); std::swap(c->cap_pos12, sl->cap_pos12); std::swap(c->pos_valid, sl->pos_valid); std::swap(c->band_frames, sl->band_frames); std::swap(c->lit_valid, sl->lit_valid);
-    c->tex_sig.swap(sl->tex_sig); std::swap(c->tex_sig_valid, sl->tex_sig_valid);
+    std::swap(c->scene, *sl);
     return B32_OK;
 }
 

@@ -8,7 +8,9 @@ host-placed vertices before it is timed, host time included on every side:
   (c) the 12 rooms alone, no placement anywhere: this build and (--parent-lib PATH) the parent commit's library, alternately, each repetition a
       process of its own.  The placement is compiled out of the kernels this frame uses, so the two must lie within each other's spread.
 usage: python tools/placed_frame.py [--parent-lib PATH] [--out profiles/placed_frame.json] [--reps 3] [--alternations 3]
-Writes the JSON with the build digest; prints a one-line summary."""
+Writes the JSON with the build digest; prints a one-line summary.
+--host-ab (with --parent-lib): only the host-bound comparison of two builds -- (c), and (d) the same 12 rooms drawn through their scene slots,
+one b32_scene_swap pair and one b32_render_scene_15_async per room -- for a change that touches host code alone."""
 import argparse
 import ctypes as C
 import json
@@ -117,6 +119,16 @@ def child(mode, lib_path, reps):
         drain(49)
         res["exact"] = bool(np.array_equal(bufs[49 & 1][0], oracle_frame(0, False)))
         res["ms"] = windows(frame, 2000, reps, drain)
+    elif mode == "slots":                                 # (d)
+        def frame(i):
+            fb.clear(clear)
+            for rs in room_slots:
+                rs.render_async(cam, st, fog) if i == 0 else rs.render_async()
+            deliver(i)
+        for i in range(50): frame(i)
+        drain(49)
+        res["exact"] = bool(np.array_equal(bufs[49 & 1][0], oracle_frame(0, False)))
+        res["ms"] = windows(lambda i: frame(i + 1), 2000, reps, drain)
     elif mode == "placed":                                # (a)
         part_slots = [R.ResidentScene(fb, p.vertices, p.faces, p.textures).detach() for p in parts]
         table = ctx.make_frame_table(cam, st, room_slots + part_slots * 8, fogs=[fog] * 36, placements=[None] * 36)
@@ -169,7 +181,7 @@ def child(mode, lib_path, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child"); ap.add_argument("--lib"); ap.add_argument("--parent-lib"); ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--alternations", type=int, default=3)
+    ap.add_argument("--alternations", type=int, default=3); ap.add_argument("--host-ab", action="store_true")
     ap.add_argument("--out", default=os.path.join("profiles", "placed_frame.json"))
     a = ap.parse_args()
     if a.child:
@@ -183,17 +195,26 @@ def main():
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
     out = {"tool": "tools/placed_frame.py", "frame": "320x240, 12 resident rooms + 24 placed instances of 3 resident parts, every instance moving every frame, "
            "every frame delivered to page-locked host memory; ms per frame, host time included; windows of 2000 / 1000 / 150 frames"}
+    if a.host_ab:
+        return host_ab(a, run, out)
     placed, uploaded = run("placed"), run("uploaded")
     out["digest"] = placed["digest"]
     out["a_frame_submit_placed"] = dict(spread(placed["ms"]), exact=placed["exact"], merged_built_constant=placed["merged_built_constant"],
                                         merged_draws_per_frame=placed["merged_draws_per_frame"])
     out["b_host_place_and_upload_per_instance"] = dict(spread(uploaded["ms"]), exact=uploaded["exact"])
     out["b_over_a"] = round(out["b_host_place_and_upload_per_instance"]["median_ms"] / out["a_frame_submit_placed"]["median_ms"], 2)
+    out["c_rooms_only_no_placement"] = alternate(a, run, "rooms")
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(out, open(a.out, "w"), indent=1)
+    print(json.dumps(out))
+
+
+def alternate(a, run, mode):
     runs = {"this": [], "parent": []}
     for _ in range(a.alternations):                       # alternately: parent, this, parent, this, ...
         if a.parent_lib:
-            runs["parent"].append(run("rooms", os.path.abspath(a.parent_lib)))
-        runs["this"].append(run("rooms"))
+            runs["parent"].append(run(mode, os.path.abspath(a.parent_lib)))
+        runs["this"].append(run(mode))
     c = {}
     for who, rs in runs.items():
         if rs:
@@ -204,7 +225,17 @@ def main():
         lo, hi = min(c["parent"]["run_medians_ms"]), max(c["parent"]["run_medians_ms"])
         c["parent_spread_ms"] = [lo, hi]
         c["this_within_parent_spread"] = all(lo <= x <= hi for x in c["this"]["run_medians_ms"])
-    out["c_rooms_only_no_placement"] = c
+        mid = sorted(c["this"]["all_windows"]["windows"])[len(c["this"]["all_windows"]["windows"]) // 2]
+        c["this_median_of_windows_ms"] = mid
+        c["this_median_at_most_parent_spread_above_parent_range"] = bool(mid <= hi + (hi - lo))
+    return c
+
+
+def host_ab(a, run, out):
+    out["frame"] = "320x240, 12 resident rooms, every frame delivered to page-locked host memory; ms per frame, host time included; windows of 2000 frames"
+    out["command"] = "python tools/placed_frame.py --host-ab --parent-lib <the parent commit's libb32raster.so> --out " + a.out
+    out["c_frame_submit"] = alternate(a, run, "rooms")
+    out["d_scene_slots_one_swap_pair_per_room"] = alternate(a, run, "slots")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(out, open(a.out, "w"), indent=1)
     print(json.dumps(out))
