@@ -110,11 +110,8 @@ __global__ __launch_bounds__(NT, 5) void k_blend(FillArgs a) {        // 5 waves
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const int shading = fp.shading;
     const bool affine = fp.affine != 0;
-    const uint32_t txi = tile % fp.tiles_x;
-    const uint32_t x_lo = txi * TILE_W, x_hi = min(x_lo + TILE_W, fp.width);
-    uint32_t TH, ty_top;                            // 64, or fewer rows when the sort-free path runs on cut tiles (LDS layout unchanged)
-    tile_row_geom(fp, tile / fp.tiles_x, ty_top, TH);
-    const uint32_t y_lo = max(ty_top, fp.band_y0), y_hi = min(ty_top + TH, fp.band_y1);
+    const TileRect rect = tile_rect(fp, tile);      // 64 rows, or fewer when the sort-free path runs on cut tiles (LDS layout unchanged)
+    const uint32_t x_lo = rect.x_lo, x_hi = rect.x_hi, y_lo = rect.y_lo, y_hi = rect.y_hi, ty_top = rect.ty_top, TH = rect.th;
     // the tile's pixels (and depths) are REQUESTED before the sort prelude below and stored to LDS behind it: their latency passes behind
     // the prelude's own chain of dependent global accesses (list -> keys -> sorted list)
     constexpr int TILE_ITERS = TILE_W * TILE_H / NT;
@@ -123,7 +120,7 @@ __global__ __launch_bounds__(NT, 5) void k_blend(FillArgs a) {        // 5 waves
     for (int it = 0; it < TILE_ITERS; ++it) {
         const uint32_t p = tid + (uint32_t)it * NT, row = p >> 6, col = p & 63;
         const uint32_t px = x_lo + col, py = ty_top + row;
-        const bool inb = row < TH && px < x_hi && py >= y_lo && py < y_hi;
+        const bool inb = row < TH && px < x_hi && py >= y_lo && py < y_hi;    // (written out: behind `row < TH &&`, TileRect::inside compiles to a branch per pixel)
         tpx[it] = inb ? a.fb[(size_t)py * fp.width + px] : 0u;
         tpz[it] = (DEPTH_TILE && zmode && inb) ? a.zbuf[(size_t)py * fp.width + px] : 0.0f;
     }
@@ -299,7 +296,7 @@ __global__ __launch_bounds__(NT, 5) void k_blend(FillArgs a) {        // 5 waves
     for (uint32_t p = tid; p < TILE_W * TH; p += NT) {      // finished tile back, one 256-B row segment per wave instruction
         const uint32_t row = p >> 6, col = p & 63;
         const uint32_t px = x_lo + col, py = ty_top + row;
-        if (px < x_hi && py >= y_lo && py < y_hi) {
+        if (rect.inside(px, py)) {
             a.fb[(size_t)py * fp.width + px] = tilebuf[row * BT_STRIDE + col];
             if (FMT8 && zmode) a.zbuf[(size_t)py * fp.width + px] = tilez[row * BT_STRIDE + col];
         }

@@ -93,23 +93,21 @@ __device__ __forceinline__ uint32_t cover_surface(const Tri& tr, uint32_t cx0, u
 
 // Phase A, EXACT coverage, wave-cooperative form (one wave per surface): used for F_SLOW surfaces and as reference path.
 template <int TEXMODE, bool EXACT, bool ZMODE, bool FMT8>
-__device__ __forceinline__ uint32_t cover_one(const Batch& b, int t, uint32_t li, uint32_t* tilebuf, uint32_t x_lo, uint32_t x_hi,
-                                              uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t lane,
+__device__ __forceinline__ uint32_t cover_one(const Batch& b, int t, uint32_t li, uint32_t* tilebuf, const TileRect& rect, uint32_t lane,
                                               const uint16_t* __restrict__ gtex, const uint16_t* ltex, bool affine) {
     const Tri tr = tri_from_batch(b, t, EXACT);
-    const uint32_t cx0 = max(tr.min_x, x_lo), cx1 = min(tr.max_x, x_hi);
-    const uint32_t cy0 = max(tr.min_y, y_lo), cy1 = min(tr.max_y, y_hi);
+    const uint32_t cx0 = max(tr.min_x, rect.x_lo), cx1 = min(tr.max_x, rect.x_hi);
+    const uint32_t cy0 = max(tr.min_y, rect.y_lo), cy1 = min(tr.max_y, rect.y_hi);
     if (cx0 >= cx1 || cy0 >= cy1) return 0;
-    return cover_surface<TEXMODE, EXACT, ZMODE, FMT8>(tr, cx0, cx1, cy0, cy1, li, tilebuf, x_lo, ty_top, lane, gtex, ltex, affine);
+    return cover_surface<TEXMODE, EXACT, ZMODE, FMT8>(tr, cx0, cx1, cy0, cy1, li, tilebuf, rect.x_lo, rect.ty_top, lane, gtex, ltex, affine);
 }
 
 // P64 coverage of a surface whose edge walk must be replayed literally (F_SLOW): one lane per row.
 template <bool ZMODE, bool EXACT, bool FMT8>
-__device__ __forceinline__ uint32_t cover_slow64(const Tri& tr, unsigned long long P, uint32_t* tilebuf, uint32_t x_lo, uint32_t x_hi,
-                                                 uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t lane,
+__device__ __forceinline__ uint32_t cover_slow64(const Tri& tr, unsigned long long P, uint32_t* tilebuf, const TileRect& rect, uint32_t lane,
                                                  const uint16_t* __restrict__ gtex, bool affine) {
-    const uint32_t cx0 = max(tr.min_x, x_lo), cx1 = min(tr.max_x, x_hi);
-    const uint32_t cy0 = max(tr.min_y, y_lo), cy1 = min(tr.max_y, y_hi);
+    const uint32_t cx0 = max(tr.min_x, rect.x_lo), cx1 = min(tr.max_x, rect.x_hi);
+    const uint32_t cy0 = max(tr.min_y, rect.y_lo), cy1 = min(tr.max_y, rect.y_hi);
     if (cx0 >= cx1 || cy0 >= cy1) return 0;
     uint32_t count = 0;
     unsigned long long* top = reinterpret_cast<unsigned long long*>(tilebuf);
@@ -122,7 +120,7 @@ __device__ __forceinline__ uint32_t cover_slow64(const Tri& tr, unsigned long lo
             for (uint32_t px = cx0; px < cx1; ++px) {
                 float bcx, bcy, bcz;
                 if (inside_bc(tr, w0, w1, bcx, bcy, bcz)) {
-                    const uint32_t addr = (py - ty_top) * STR64 + (px - x_lo);
+                    const uint32_t addr = (py - rect.ty_top) * STR64 + (px - rect.x_lo);
                     unsigned long long Pf = P;
                     bool ok = true;
                     if (ZMODE) { uint32_t zkey; ok = frag_zkey(tr, bcx, bcy, bcz, zkey); Pf = ((unsigned long long)(~zkey) << 32) | (uint32_t)P; }
@@ -273,8 +271,8 @@ __device__ __forceinline__ void span_trip(unsigned long long* top, unsigned long
 template <int TEXMODE, bool EXACT, int NW, bool ZMODE, bool FMT8, bool P64 = false>
 __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, uint32_t e0, uint32_t n_op, uint32_t lane, uint32_t wave,
                                                            uint32_t* cursor, uint32_t* wmark, const TexDesc& lds_desc,
-                                                           uint32_t* tilebuf, uint32_t x_lo, uint32_t x_hi, uint32_t y_lo, uint32_t y_hi,
-                                                           uint32_t ty_top, const uint16_t* ltex) {
+                                                           uint32_t* tilebuf, const TileRect& rect, const uint16_t* ltex) {
+    const uint32_t x_lo = rect.x_lo, x_hi = rect.x_hi, y_lo = rect.y_lo, y_hi = rect.y_hi, ty_top = rect.ty_top;
     const uint16_t* __restrict__ gtex = FMT8 ? reinterpret_cast<const uint16_t*>(a.texels32) : a.texels;
     unsigned long long frags = 0;
     const float ERR = K::ERR;
@@ -644,11 +642,11 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             sm &= sm - 1;
             if (P64) {
                 const unsigned long long P = ((unsigned long long)bcu(my_key, t) << 32) | bcu(my_sid, t);
-                const uint32_t cnt64 = cover_slow64<ZMODE, EXACT, FMT8>(tri_from_batch(b, t, ZMODE || EXACT), P, tilebuf, x_lo, x_hi, y_lo, y_hi, ty_top, lane, gtex, affine);
+                const uint32_t cnt64 = cover_slow64<ZMODE, EXACT, FMT8>(tri_from_batch(b, t, ZMODE || EXACT), P, tilebuf, rect, lane, gtex, affine);
                 if (EXACT) frags += cnt64;
                 continue;
             }
-            frags += cover_one<TEXMODE, EXACT, ZMODE, FMT8>(b, t, cs + (uint32_t)t + 1, tilebuf, x_lo, x_hi, y_lo, y_hi, ty_top, lane, gtex, ltex, affine);
+            frags += cover_one<TEXMODE, EXACT, ZMODE, FMT8>(b, t, cs + (uint32_t)t + 1, tilebuf, rect, lane, gtex, ltex, affine);
         }
     }
     (void)wave; (void)wmark;        // (the row starts travel by ds_permute now; the per-wave mark area holds the shading phase's repair queues)

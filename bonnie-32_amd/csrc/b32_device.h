@@ -337,6 +337,20 @@ __host__ __device__ __forceinline__ uint32_t tile_row_of(const FrameParams& fp, 
 __host__ __device__ __forceinline__ void tile_row_geom(const FrameParams& fp, uint32_t row, uint32_t& top, uint32_t& th) {
     th = fp.tile_h; top = fp.tile_yb + row * th;
 }
+// The part of the frame and of this rank's band that tile `tile` covers: columns [x_lo, x_hi), rows [y_lo, y_hi).  The tile itself starts at
+// screen row ty_top and has th rows in use (64, or fewer when the sort-free path runs on cut tiles: too few 64x64 tiles to fill the GPU);
+// the LDS planes keep their full-tile layout whatever th is, entry (py - ty_top, px - x_lo).
+struct TileRect {
+    uint32_t x_lo, x_hi, y_lo, y_hi, ty_top, th;
+    __device__ __forceinline__ bool inside(uint32_t px, uint32_t py) const { return (px < x_hi) & ((py >= y_lo) & (py < y_hi)); }   // (no short circuit: three compares and two mask ANDs, no branch)
+};
+__device__ __forceinline__ TileRect tile_rect(const FrameParams& fp, uint32_t tile) {
+    TileRect r;
+    r.x_lo = (tile % fp.tiles_x) * TILE_W; r.x_hi = min(r.x_lo + TILE_W, fp.width);
+    tile_row_geom(fp, tile / fp.tiles_x, r.ty_top, r.th);
+    r.y_lo = max(r.ty_top, fp.band_y0); r.y_hi = min(r.ty_top + r.th, fp.band_y1);
+    return r;
+}
 // Tile span of a surface's (band-clipped) bounding box, packed tx0 | tx1<<8 | ty0<<16 | ty1<<24 with band-relative tile rows
 // (<= 256 tiles per axis: 16384 px); 0xFFFFFFFF = touches no tile of this band.
 __device__ __forceinline__ uint32_t pack_tile_span(uint32_t bbx, uint32_t bby, uint32_t flags, const FrameParams& fp, uint32_t& count) {

@@ -59,9 +59,9 @@ __device__ __forceinline__ void repair_pixel(const FillArgs& a, const unsigned l
 // are found -- one lane of the wave shading a whole runner-up, behind a record gather and a texel fetch of its own, in two steps out
 // of five on the benchmark scene -- but collected and repaired together: when 64 have gathered, and behind the tile's last row.
 template <bool FMT8, int NT, bool ZMODE>
-__device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, uint32_t x_lo, uint32_t x_hi,
-                                               uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t tid_in, uint32_t lane_in, uint32_t TH, uint32_t* wq,
-                                               const uint8_t* latlas) {
+__device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, const TileRect& rect,
+                                               uint32_t tid_in, uint32_t lane_in, uint32_t* wq, const uint8_t* latlas) {
+    const uint32_t x_lo = rect.x_lo, x_hi = rect.x_hi, y_lo = rect.y_lo, y_hi = rect.y_hi, ty_top = rect.ty_top, TH = rect.th;
     uint32_t tid = tid_in, lane = lane_in;              // (opaque copies: see shade_tile_plain)
     asm volatile("" : "+v"(tid), "+v"(lane));
     const FrameParams& fp = a.fp;
@@ -161,8 +161,9 @@ __device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t
 // proven equal to it), so it is not evaluated again.  A step in which some winner must replay the edge walk literally (SH_SLOW) takes
 // the general per-pixel functions; skipped winners go to the wave's repair queue as in the general form.
 template <int NT, bool ZMODE>
-__device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, uint32_t x_lo, uint32_t x_hi,
-                                                 uint32_t y_lo, uint32_t y_hi, uint32_t ty_top, uint32_t tid_in, uint32_t lane_in, uint32_t TH, uint32_t* wq) {
+__device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32_t* tilebuf, uint32_t e0, uint32_t e1, const TileRect& rect,
+                                                 uint32_t tid_in, uint32_t lane_in, uint32_t* wq) {
+    const uint32_t x_lo = rect.x_lo, x_hi = rect.x_hi, y_lo = rect.y_lo, y_hi = rect.y_hi, ty_top = rect.ty_top, TH = rect.th;
     // (the lane's constants of this phase -- column, x, masks -- are derived again per tile from an opaque copy of its index: hoisted out of the
     // tile loop they would stay live through the coverage phase, which is the one that sets the kernel's register count)
     uint32_t tid = tid_in, lane = lane_in;
