@@ -57,6 +57,12 @@ WORLD_ITEM_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("size", "<i4")
 assert WORLD_ITEM_DTYPE.itemsize == 40
 WORLD_CLIP_NEAR = 1
 
+# B32PickHit (b32_pick_meshes): hit == 0 -> tri = 0xFFFFFFFF, depth = 0
+PICK_HIT_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("depth", "<f4"), ("_pad", "<u4")])
+assert PICK_HIT_DTYPE.itemsize == 16
+PICK_CULL_BACKFACES = 1
+PICK_HEADER_BYTES = 16              # b32_pick_meshes_async's result: {int32 best; uint32 n; 8 bytes of padding}, then n B32PickHit
+PICK_NO_TRI = 0xFFFFFFFF
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -157,6 +163,8 @@ SYMBOLS = [
     ("b32_frame_add_scene_placed", C.c_int, [_P, _P, _P, _P]),
     ("b32_frame_submit_placed", C.c_int, [_P, _P, _P, C.POINTER(_P), _P, _P, _P, C.c_uint32]),
     ("b32_render_scene_15_placed_async", C.c_int, [_P, _P, _P, _P, _P]),
+    ("b32_pick_meshes", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(_P), _P, C.c_uint32, _P, C.POINTER(C.c_int32)]),
+    ("b32_pick_meshes_async", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(_P), _P, C.c_uint32, _P, C.POINTER(C.c_uint64)]),
     ("b32_fb_clear_gradient", C.c_int, [_P] + [C.c_uint8] * 8),
     ("b32_fb_clear_transparent", C.c_int, [_P]),
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),

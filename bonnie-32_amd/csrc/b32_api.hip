@@ -63,12 +63,20 @@ void b32_destroy(b32_ctx* c) {
     c->lines.release(); c->prims.release(); c->world.release();
     if (c->world_counts) (void)hipFree(c->world_counts);
     for (hipEvent_t e : c->world_ev) if (e) (void)hipEventDestroy(e);
+    c->pick_tab.release();
+    if (c->pick_words) (void)hipFree(c->pick_words);
+    if (c->pick_host) (void)hipHostFree(c->pick_host);
+    for (hipEvent_t e : c->pick_tev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
     if (c->dl_stream) { (void)hipStreamSynchronize(c->dl_stream); (void)hipStreamDestroy(c->dl_stream); }
     for (hipEvent_t e : c->dl_snap) if (e) (void)hipEventDestroy(e);
     for (uint32_t* q : c->dl_stage) if (q) (void)hipFree(q);
+    for (uint32_t k = 0; k < b32_ctx::PICK_RING; ++k) {                     // (behind dl_stream's last transfer)
+        if (c->pick_res[k]) (void)hipFree(c->pick_res[k]);
+        for (hipEvent_t e : { c->pick_done[k], c->pick_left[k] }) if (e) (void)hipEventDestroy(e);
+    }
     delete c;
 }
 
@@ -276,28 +284,6 @@ static DrawArgs<Rec> draw_args(b32_ctx* c, uint32_t n) {
     a.width = c->width; a.band_y0 = c->band_y0; a.band_y1 = c->band_y1;
     a.tiles_x = (c->width + 63u) / 64u; a.tiles_y = (c->band_y1 - c->band_y0 + LINE_TH - 1u) / LINE_TH;
     return a;
-}
-// Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there to ps.dev
-// on the stream.
-template <class Rec>
-static int stage_records(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n) {
-    const uint32_t k = ps.slot;
-    ps.slot = (k + 1) % LINE_RING;
-    if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));
-    else HIPCHK(c, hipEventCreateWithFlags(&ps.ev[k], hipEventDisableTiming));
-    if (ps.cap_host[k] < n) {
-        if (ps.host[k]) HIPCHK(c, hipHostFree(ps.host[k]));
-        ps.host[k] = nullptr; ps.cap_host[k] = 0;
-        const size_t cap = (size_t)n + n / 4 + 64;
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&ps.host[k]), cap * sizeof(Rec), hipHostMallocDefault));
-        ps.cap_host[k] = cap;
-    }
-    std::memcpy(ps.host[k], recs, (size_t)n * sizeof(Rec));
-    int rc;
-    if ((rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(ps.ev[k], c->stream));
-    return B32_OK;
 }
 // Bin and draw records that are already on the device (a.recs, behind whatever wrote them on the stream): the tile route if `tiles` and
 // `route` is not switched off, else every tile scans the whole batch.  *tiled (nullable): which of the two it was.
@@ -539,6 +525,17 @@ void* b32_host_alloc(size_t bytes) {
     return p;
 }
 void b32_host_free(void* p) { if (p) (void)hipHostFree(p); }
+int ticket_open(b32_ctx* c, unsigned long long& t, hipEvent_t*& ev) {
+    t = c->dl_seq + 1;
+    ev = &c->dl_ev[t % b32_ctx::DL_RING];
+    if (!*ev) HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    else if (t > b32_ctx::DL_RING) HIPCHK(c, hipEventSynchronize(*ev));      // (the ticket that used this event, DL_RING tickets ago)
+    if (!c->dl_stream) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->dl_stream, hipStreamNonBlocking));
+        for (hipEvent_t& e : c->dl_snap) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    return B32_OK;
+}
 int b32_fb_download_async(b32_ctx* c, uint8_t* rgba, uint64_t* ticket) {
     if (!c || !c->fb || !rgba || !ticket) return B32_E_ARG;
     (void)hipSetDevice(c->device);
@@ -546,24 +543,20 @@ int b32_fb_download_async(b32_ctx* c, uint8_t* rgba, uint64_t* ticket) {
     // a console frame is made of, never are; deep mode never blocks the host: a dropped frame is reported by b32_frame_finish)
     if (!c->deep_async) { const int rc = settle_pending(c); if (rc) return rc; }
     { const int rcf = flush_clear(c); if (rcf) return rcf; }
-    const unsigned long long t = c->dl_seq + 1;
-    hipEvent_t& ev = c->dl_ev[t % b32_ctx::DL_RING];
-    if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else if (t > b32_ctx::DL_RING) HIPCHK(c, hipEventSynchronize(ev));       // (the ticket that used this event, DL_RING downloads ago)
+    unsigned long long t = 0; hipEvent_t* tev = nullptr;
+    { const int rct = ticket_open(c, t, tev); if (rct) return rct; }
+    hipEvent_t& ev = *tev;
     const size_t px = (size_t)c->width * c->height;
     // a snapshot on the device first (two staging buffers, alternating): the frames that follow overwrite the framebuffer while the
     // snapshot crosses PCIe on a stream of its own
-    if (!c->dl_stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->dl_stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : c->dl_snap) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
     if (px > c->dl_stage_px) {
         HIPCHK(c, hipStreamSynchronize(c->dl_stream));
         for (uint32_t*& q : c->dl_stage) { if (q) HIPCHK(c, hipFree(q)); q = nullptr; HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&q), px * 4)); }
         c->dl_stage_px = px;
     }
     const int k = (int)(t & 1u);
-    // (the staging buffer's previous reader -- ticket t - 2's transfer -- must have left: the main stream waits for it, normally long done)
+    // (the staging buffer's previous reader -- a download with a ticket of this parity, so t - 2 or earlier -- must have left: the main stream
+    // waits for ticket t - 2, a download or a pick, behind which dl_stream has nothing older; normally long done)
     if (t > 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->dl_ev[(t - 2) % b32_ctx::DL_RING], 0));
     HIPCHK(c, hipMemcpyAsync(c->dl_stage[k], c->fb, px * 4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->dl_snap[k], c->stream));
@@ -700,6 +693,12 @@ int b32_last_kernel_times(b32_ctx* c, const char** names, float* ms, uint32_t ca
     if (c->world_timed && k < cap && hipEventSynchronize(c->world_ev[1]) == hipSuccess &&
         hipEventElapsedTime(&world_ms, c->world_ev[0], c->world_ev[1]) == hipSuccess) {
         names[k] = "world_project"; ms[k] = world_ms; ++k;
+    }
+    // the pick and resolve kernels of the last b32_pick_meshes[_async] enqueued while profiling was on (waits for them)
+    float pick_ms = 0.0f;
+    if (c->pick_timed && k < cap && hipEventSynchronize(c->pick_tev[1]) == hipSuccess &&
+        hipEventElapsedTime(&pick_ms, c->pick_tev[0], c->pick_tev[1]) == hipSuccess) {
+        names[k] = "pick"; ms[k] = pick_ms; ++k;
     }
     return (int)k;
 }

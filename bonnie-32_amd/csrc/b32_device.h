@@ -516,7 +516,15 @@ struct WorldArgs {
     float vs, half_w, half_h;                  // (min(w, h) as f32 / 2.0) * 0.75, w as f32 / 2.0, h as f32 / 2.0 (math.rs:524-531)
     float zoom, center_x, center_y; uint32_t has_ortho;
 };
-void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);   // small != nullptr: n <= WORLD_SMALL items passed by value
+void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);
+// One row of a pick's table (b32_pick.hip): an item's mesh on the device, its placement and the first of its workgroups.
+struct PickItem {
+    const B32Vertex* verts; const float* pos12;  // pos12 != nullptr: the slot's packed positions (12 B per vertex) instead of the 36-B vertices
+    const B32Face* faces;
+    uint32_t nv, nf;
+    float cos_f, sin_f, wpos[3];
+    uint32_t first_wg, _pad;                    // the item's workgroups are [first_wg, first_wg + ceil(nf / PICK_CHUNK))
+};   // small != nullptr: n <= WORLD_SMALL items passed by value
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

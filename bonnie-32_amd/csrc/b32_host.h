@@ -233,6 +233,16 @@ struct b32_ctx {
     // ... through a device-side snapshot: the frame is copied to dl_stage[t % 2] on the context's stream (microseconds) and leaves for the host
     // from there on dl_stream, so that the NEXT frame's kernels do not wait for the PCIe transfer
     hipStream_t dl_stream = nullptr; hipEvent_t dl_snap[2] = {}; uint32_t* dl_stage[2] = {}; size_t dl_stage_px = 0;
+    // b32_pick_meshes[_async] (b32_pick.hip): the three minima per item (all ones between two picks), the table of a pick too large for
+    // the kernel argument, PICK_RING device result buffers in turn (pick_done: the resolve kernel wrote it, main stream; pick_left: its
+    // transfer has left, dl_stream), the blocking form's page-locked landing buffer, HIP events around the last pick enqueued while
+    // profiling was on (b32_last_kernel_times "pick")
+    static constexpr uint32_t PICK_RING = 4;
+    void* pick_words = nullptr; size_t pick_cap_words = 0;
+    DrawPassState<PickItem> pick_tab;
+    void* pick_res[PICK_RING] = {}; size_t pick_cap_res[PICK_RING] = {}; hipEvent_t pick_done[PICK_RING] = {}, pick_left[PICK_RING] = {}; uint32_t pick_slot = 0;
+    void* pick_host = nullptr; size_t pick_cap_host = 0;
+    hipEvent_t pick_tev[2] = {}; bool pick_timed = false;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only
@@ -269,7 +279,28 @@ static int ensure_plain(b32_ctx* c, T*& p, size_t count) {   // exact-size (re)a
     return B32_OK;
 }
 
-
+// Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there to ps.dev
+// on the stream.
+template <class Rec>
+static int stage_records(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n) {
+    const uint32_t k = ps.slot;
+    ps.slot = (k + 1) % LINE_RING;
+    if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));
+    else HIPCHK(c, hipEventCreateWithFlags(&ps.ev[k], hipEventDisableTiming));
+    if (ps.cap_host[k] < n) {
+        if (ps.host[k]) HIPCHK(c, hipHostFree(ps.host[k]));
+        ps.host[k] = nullptr; ps.cap_host[k] = 0;
+        const size_t cap = (size_t)n + n / 4 + 64;
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&ps.host[k]), cap * sizeof(Rec), hipHostMallocDefault));
+        ps.cap_host[k] = cap;
+    }
+    std::memcpy(ps.host[k], recs, (size_t)n * sizeof(Rec));
+    int rc;
+    if ((rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(ps.ev[k], c->stream));
+    return B32_OK;
+}
 
 // Scratch device allocations of ONE API call (sky / stars / present / taps): released on every exit path, error returns included,
 // after the stream has drained.
@@ -310,6 +341,10 @@ constexpr size_t STAGE_BYTES = (size_t)1 << 20, STAGE_CTRL_OFF = STAGE_BYTES - 1
 extern "C" {
 B32_INTERNAL int settle_pending(b32_ctx* c);                                      // b32_api.hip
 B32_INTERNAL int flush_clear(b32_ctx* c);                                         // b32_api.hip
+// The next ticket (b32_fb_download_async, b32_pick_meshes_async): its number and its event, created on first use, else waited for when
+// it still belongs to the ticket DL_RING tickets ago; the transfer stream exists afterwards.  The caller records *ev on dl_stream and
+// then sets dl_seq = t.
+B32_INTERNAL int ticket_open(b32_ctx* c, unsigned long long& t, hipEvent_t*& ev); // b32_api.hip
 B32_INTERNAL int apply_depth_auto(b32_ctx* c);                                    // b32_api.hip (b32_set_pipeline_depth(ctx, 0): the depth the library picks)
 constexpr size_t FB_TAIL_BYTES = 8192;      // behind the pixels of a library-owned framebuffer: the epoch words of the band exchange (b32_gather.hip)
 B32_INTERNAL void band_close_any(b32_ctx* c);                                    // b32_gather.hip

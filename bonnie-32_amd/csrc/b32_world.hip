@@ -10,35 +10,13 @@
 // f2i32_sat = `as i32`).  Record i is written from item i, so the array order is the reference's call order; an item that draws nothing
 // becomes a circle of radius -1, which the tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of
 // b32_prims.hip reads them where this kernel wrote them.
-#include "b32_device.h"
+#include "b32_world_point.h"
 #include <cmath>
 
 namespace b32 {
 
 struct WorldBatch { B32WorldItem r[WORLD_SMALL]; };
 static_assert(sizeof(B32WorldItem) == 40 && sizeof(WorldBatch) + sizeof(WorldArgs) <= 2048, "B32WorldItem layout / kernel argument size");
-
-constexpr float WORLD_NEAR = 0.1f;                  // NEAR_PLANE, math.rs:155; the `cam_z <= 0.1` of math.rs:516, 560, 602, 634
-
-// Vec3::dot, math.rs:23-25
-__device__ __forceinline__ float world_dot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-// world_to_screen[_with_depth] (ortho == false) and world_to_screen_with_ortho[_depth], math.rs:503-652: false = None
-__device__ __forceinline__ bool world_point(const WorldArgs& a, const float* p, bool ortho, float& sx, float& sy, float& z) {
-    const float rel[3] = { p[0] - a.pos[0], p[1] - a.pos[1], p[2] - a.pos[2] };
-    const float cam_x = world_dot(rel, a.bx), cam_y = world_dot(rel, a.by), cam_z = world_dot(rel, a.bz);
-    z = cam_z;
-    if (ortho) {
-        sx = (cam_x - a.center_x) * a.zoom + a.half_w;
-        sy = -(cam_y - a.center_y) * a.zoom + a.half_h;
-        return true;
-    }
-    if (cam_z <= WORLD_NEAR) return false;
-    const float denom = cam_z + 5.0f;               // ud = 5.0, us = ud - 1.0
-    sx = (cam_x * 4.0f / denom) * a.vs + a.half_w;
-    sy = (cam_y * 4.0f / denom) * a.vs + a.half_h;
-    return true;
-}
 
 // item i of the batch (`live`: i < a.n; the other lanes only take part in the counting)
 __device__ __forceinline__ void world_project(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live) {

@@ -15,6 +15,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -375,6 +376,106 @@ inline Vertex place_vertex(const Vertex& v, const Placement& p) {
     return o;
 }
 struct MeshParams { float ambient; bool backface_cull, backface_wireframe; Fog fog; std::optional<Placement> placement = std::nullopt; };
+
+// Picking: which placed resident mesh, and which of its triangles, lies under the cursor -- check_mesh_hit (editor/viewport_3d.rs:7700-7756)
+// for every (mesh, placement) of the object loop (:7344-7377) and the face branch of the modeler's find_hovered_element
+// (modeler/viewport.rs:2544-2594), on the device (b32_pick_meshes).  The placement is ALWAYS applied here (has_transform is not consulted:
+// check_mesh_hit has no such shortcut).  ortho: OrthoProjection as (zoom, center_x, center_y).
+struct PickItem { const ResidentMesh* mesh; Placement placement; };
+struct PickResult { int32_t best = -1; std::vector<B32PickHit> hits; };          // best: index into the items, -1 when nothing is hit
+namespace detail {
+struct PickCall {                                                              // the packed arguments of one pick
+    B32Camera cam; B32Ortho ortho; bool has_ortho; std::vector<b32_scene*> slots; std::vector<B32Placement> places;
+    PickCall(const std::vector<PickItem>& items, const Camera& camera, const std::optional<Vec3>& o) : cam(pack(camera)), has_ortho((bool)o) {
+        ortho = o ? B32Ortho{ o->x, o->y, o->z } : B32Ortho{ 0, 0, 0 };
+        for (const auto& it : items) {
+            slots.push_back(it.mesh ? it.mesh->slot() : nullptr);
+            places.push_back({ it.placement.cos_f, it.placement.sin_f, { it.placement.world_pos.x, it.placement.world_pos.y, it.placement.world_pos.z } });
+        }
+    }
+};
+}  // namespace detail
+inline PickResult pick_meshes(Framebuffer& fb, const std::vector<PickItem>& items, const Camera& camera, float mx, float my,
+                              const std::optional<Vec3>& ortho = std::nullopt, bool cull_backfaces = false) {
+    const detail::PickCall c(items, camera, ortho);
+    PickResult r; r.hits.resize(items.size());
+    check(b32_pick_meshes(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mx, my, cull_backfaces ? B32_PICK_CULL_BACKFACES : 0u, c.slots.data(),
+                          c.places.data(), (uint32_t)items.size(), r.hits.data(), &r.best), "pick_meshes");
+    return r;
+}
+// The asynchronous form: `out` (16 + 16 * items.size() bytes, preferably from b32_host_alloc) holds {int32 best; uint32 n; 8 bytes}, then the
+// hits, once the returned ticket is done (b32_ticket_poll / _wait); no host synchronisation.
+inline uint64_t pick_meshes_async(Framebuffer& fb, const std::vector<PickItem>& items, const Camera& camera, float mx, float my, void* out,
+                                  const std::optional<Vec3>& ortho = std::nullopt, bool cull_backfaces = false) {
+    const detail::PickCall c(items, camera, ortho);
+    uint64_t ticket = 0;
+    check(b32_pick_meshes_async(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mx, my, cull_backfaces ? B32_PICK_CULL_BACKFACES : 0u, c.slots.data(),
+                                c.places.data(), (uint32_t)items.size(), out, &ticket), "pick_meshes_async");
+    return ticket;
+}
+inline PickResult pick_result(const void* out) {                                // what pick_meshes_async delivered, once its ticket is done
+    const unsigned char* p = static_cast<const unsigned char*>(out);
+    PickResult r; uint32_t n = 0;
+    std::memcpy(&r.best, p, 4); std::memcpy(&n, p + 4, 4);
+    r.hits.resize(n);
+    if (n) std::memcpy(r.hits.data(), p + 16, (size_t)n * sizeof(B32PickHit));
+    return r;
+}
+// The host restatement of one item (what a host without the library walks per mouse move): separately rounded f32 operations in the
+// reference's order (compile with -ffp-contract=off where the compiler would fuse).  A NaN depth is reported as the quiet NaN 0x7FC00000.
+inline B32PickHit pick_mesh(const std::vector<Vertex>& vertices, const std::vector<Face>& faces, const Placement& p, const Camera& cam, size_t w, size_t h,
+                            float mx, float my, const std::optional<Vec3>& ortho = std::nullopt, bool cull_backfaces = false) {
+    struct Screen { bool some; float x, y, d; };
+    const auto dot = [](Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };   // Vec3::dot, math.rs:23-25
+    std::vector<Screen> sv; sv.reserve(vertices.size());
+    for (const auto& v : vertices) {                                            // viewport_3d.rs:7714-7728
+        const float rx = v.pos.x * p.cos_f - v.pos.z * p.sin_f, rz = v.pos.x * p.sin_f + v.pos.z * p.cos_f;
+        const Vec3 rel{ rx + p.world_pos.x - cam.position.x, v.pos.y + p.world_pos.y - cam.position.y, rz + p.world_pos.z - cam.position.z };
+        const float cx = dot(rel, cam.basis_x), cy = dot(rel, cam.basis_y), cz = dot(rel, cam.basis_z);
+        Screen s{ true, 0, 0, cz };
+        if (ortho) {                                                            // math.rs:595-599
+            s.x = (cx - ortho->y) * ortho->x + ((float)w / 2.0f);
+            s.y = -(cy - ortho->z) * ortho->x + ((float)h / 2.0f);
+        } else if (cz <= 0.1f) {                                                // math.rs:634
+            s.some = false;
+        } else {
+            const float vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f, denom = cz + 5.0f;
+            s.x = (cx * 4.0f / denom) * vs + ((float)w / 2.0f);
+            s.y = (cy * 4.0f / denom) * vs + ((float)h / 2.0f);
+        }
+        sv.push_back(s);
+    }
+    bool any = false; uint32_t tri = 0; float closest = 0.0f;
+    for (size_t t = 0; t < faces.size(); ++t) {
+        const Face& f = faces[t];
+        if (f.v0 >= sv.size() || f.v1 >= sv.size() || f.v2 >= sv.size()) continue;
+        const Screen &a = sv[f.v0], &b = sv[f.v1], &c = sv[f.v2];
+        if (!a.some || !b.some || !c.some) continue;
+        const float area = (b.x - a.x) * (c.y - a.y) - (c.x - a.x) * (b.y - a.y);
+        if (cull_backfaces && area <= 0.0f) continue;                           // modeler/viewport.rs:2571-2574
+        const auto sign = [&](const Screen& u, const Screen& v) { return (mx - v.x) * (u.y - v.y) - (u.x - v.x) * (my - v.y); };
+        const float d1 = sign(a, b), d2 = sign(b, c), d3 = sign(c, a);          // point_in_triangle_2d, math.rs:687-706
+        if (((d1 < 0.0f) || (d2 < 0.0f) || (d3 < 0.0f)) && ((d1 > 0.0f) || (d2 > 0.0f) || (d3 > 0.0f))) continue;
+        float depth;                                                            // interpolate_depth_in_triangle, viewport_3d.rs:7485-7508
+        if (std::fabs(area) < 0.0001f) depth = ((a.d + b.d) + c.d) / 3.0f;
+        else {
+            const float w0 = ((b.x - mx) * (c.y - my) - (c.x - mx) * (b.y - my)) / area;
+            const float w1 = ((c.x - mx) * (a.y - my) - (a.x - mx) * (c.y - my)) / area;
+            const float w2 = (1.0f - w0) - w1;
+            depth = (w0 * a.d + w1 * b.d) + w2 * c.d;
+        }
+        if (!any || depth < closest) { any = true; closest = depth; tri = (uint32_t)t; }
+    }
+    if (!any) return B32PickHit{ 0u, 0xFFFFFFFFu, 0.0f, 0u };
+    if (closest != closest) { const uint32_t q = 0x7FC00000u; std::memcpy(&closest, &q, 4); }
+    return B32PickHit{ 1u, tri, closest, 0u };
+}
+// the loop over the items, viewport_3d.rs:7370
+inline int32_t pick_best(const std::vector<B32PickHit>& hits) {
+    int32_t best = -1;
+    for (size_t i = 0; i < hits.size(); ++i) if (hits[i].hit && (best < 0 || hits[i].depth < hits[(size_t)best].depth)) best = (int32_t)i;
+    return best;
+}
 namespace detail {
 inline bool pack(const std::optional<Placement>& p, B32Placement& out) {
     if (!p || !p->has_transform) return false;
@@ -418,16 +519,19 @@ inline RasterTimings render_frame(Framebuffer& fb, const std::vector<std::pair<c
 // memory (game/renderer.rs:179-214) -- without a host round trip per frame: submit() enqueues Framebuffer::clear, the frame's draws
 // (b32_frame_submit: the mesh table in one call) and the copy of the finished frame into page-locked memory (b32_fb_download_async), and
 // returns a ticket; wait(ticket) blocks until THAT frame's pixels are in the returned buffer.  Two buffers alternate, so the presenter reads
-// frame i while frame i + 1 is drawn: keep at most two tickets outstanding.
+// frame i while frame i + 1 is drawn: keep at most two tickets outstanding.  A frame may carry one pick (submit's `pick`): it is enqueued
+// behind the frame's draws, delivered into page-locked memory of its own and waited for one frame behind like the pixels (wait_pick).
+struct FramePick { std::vector<PickItem> items; float mx = 0, my = 0; std::optional<Vec3> ortho = std::nullopt; bool cull_backfaces = false; };
 class FrameLoop {
 public:
     explicit FrameLoop(Framebuffer& fb) : fb_(fb) {
         for (auto& b : buf_) { b = static_cast<uint8_t*>(b32_host_alloc(fb.width * fb.height * 4)); if (!b) throw Error(B32_E_HIP, "b32_host_alloc"); }
     }
-    ~FrameLoop() { b32_synchronize(fb_.ctx()); for (auto b : buf_) b32_host_free(b); }
+    ~FrameLoop() { b32_synchronize(fb_.ctx()); for (auto b : buf_) b32_host_free(b); for (auto b : pick_buf_) b32_host_free(b); }
     FrameLoop(const FrameLoop&) = delete;
     FrameLoop& operator=(const FrameLoop&) = delete;
-    uint64_t submit(Color clear, const std::vector<std::pair<const ResidentMesh*, MeshParams>>& meshes, const Camera& camera, const RasterSettings& base) {
+    uint64_t submit(Color clear, const std::vector<std::pair<const ResidentMesh*, MeshParams>>& meshes, const Camera& camera, const RasterSettings& base,
+                    const FramePick* pick = nullptr) {
         const std::vector<B32Light> l = detail::pack(base.lights);
         const B32Camera c = detail::pack(camera);
         const B32Settings s = detail::pack(base, l);
@@ -443,8 +547,26 @@ public:
         fb_.clear(clear);
         check(b32_frame_submit_placed(fb_.ctx(), &c, &s, slots.data(), params.data(), places.data(), has_place.data(), (uint32_t)slots.size()), "frame_submit_placed");
         const size_t k = n_++ & 1;
+        pick_ticket_[k] = 0;
+        if (pick) {
+            const size_t need = 16 + 16 * pick->items.size();
+            if (need > pick_cap_[k]) {                              // (its previous pick was waited for, or is by now: two frames back)
+                if (pick_buf_[k]) { check(b32_synchronize(fb_.ctx()), "synchronize"); b32_host_free(pick_buf_[k]); }
+                pick_buf_[k] = b32_host_alloc(need + 1024); pick_cap_[k] = pick_buf_[k] ? need + 1024 : 0;
+                if (!pick_buf_[k]) throw Error(B32_E_HIP, "b32_host_alloc");
+            }
+            pick_ticket_[k] = pick_meshes_async(fb_, pick->items, camera, pick->mx, pick->my, pick_buf_[k], pick->ortho, pick->cull_backfaces);
+        }
         check(b32_fb_download_async(fb_.ctx(), buf_[k], &ticket_[k]), "fb_download_async");
         return ticket_[k];
+    }
+    // the pick that travelled with the frame of `ticket` (submit's `pick`), once it has landed
+    PickResult wait_pick(uint64_t ticket) {
+        for (size_t k = 0; k < 2; ++k) if (ticket_[k] == ticket && pick_ticket_[k]) {
+            check(b32_ticket_wait(fb_.ctx(), pick_ticket_[k]), "ticket_wait");
+            return pick_result(pick_buf_[k]);
+        }
+        throw Error(B32_E_ARG, "FrameLoop::wait_pick: no pick travelled with this ticket, or its buffer has been reused");
     }
     // the frame of `ticket`, once it has landed (valid until the submit after next)
     const uint8_t* wait(uint64_t ticket) {
@@ -458,6 +580,7 @@ private:
     Framebuffer& fb_;
     uint8_t* buf_[2] = { nullptr, nullptr };
     uint64_t ticket_[2] = { 0, 0 };
+    void* pick_buf_[2] = { nullptr, nullptr }; size_t pick_cap_[2] = { 0, 0 }; uint64_t pick_ticket_[2] = { 0, 0 };
     size_t n_ = 0;
 };
 

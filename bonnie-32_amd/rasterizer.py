@@ -80,6 +80,133 @@ class Placement:
         return place_vertices(vertices, self.cos_f, self.sin_f, self.world_pos)
 
 
+def _placement_triple(placement):
+    """(cos_f, sin_f, world_pos) as f32 of a Placement, an abi.B32Placement or such a triple.  Picking always applies the placement
+    (viewport_3d.rs:7716-7718 has no has_transform shortcut), so Placement.has_transform is not consulted."""
+    f32 = np.float32
+    if isinstance(placement, (Placement, abi.B32Placement)):
+        c, s, w = placement.cos_f, placement.sin_f, tuple(placement.world_pos)
+    else:
+        c, s, w = placement
+    return f32(c), f32(s), tuple(f32(x) for x in w)
+
+
+class PickMirror:
+    """check_mesh_hit (editor/viewport_3d.rs:7700-7756) and the face branch of find_hovered_element (modeler/viewport.rs:2544-2594) for one
+    placed mesh in numpy float32: what b32_pick_meshes computes per item, and what a host without this library walks per mouse move.
+    The constructor does what the reference does once per mesh and frame (place and project every vertex: screen_verts); pick() is the
+    triangle loop for one cursor.  Every operation is one separately rounded f32 operation in the reference's order."""
+
+    def __init__(self, vertices, faces, placement, camera, w, h, ortho=None):
+        f32 = np.float32
+        pos = np.ascontiguousarray(vertices["pos"] if getattr(vertices, "dtype", None) is not None and vertices.dtype.names else vertices, f32).reshape(-1, 3)
+        fv = np.ascontiguousarray(faces["v"] if getattr(faces, "dtype", None) is not None and faces.dtype.names else faces).reshape(-1, 3).astype(np.int64)
+        c, s, wp = _placement_triple(placement)
+        cp, bx, by, bz = (tuple(f32(x) for x in getattr(camera, n)) for n in ("position", "basis_x", "basis_y", "basis_z"))
+        with np.errstate(all="ignore"):
+            x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+            rx = x * c - z * s
+            rz = x * s + z * c
+            rel = (rx + wp[0] - cp[0], y + wp[1] - cp[1], rz + wp[2] - cp[2])
+            cam_x, cam_y, cam_z = ((rel[0] * b[0] + rel[1] * b[1]) + rel[2] * b[2] for b in (bx, by, bz))
+            hw, hh = f32(w) / f32(2.0), f32(h) / f32(2.0)
+            if ortho is not None:                                  # world_to_screen_with_ortho_depth, math.rs:595-599: never None
+                zoom, ocx, ocy = (f32(v) for v in ortho)
+                sx = (cam_x - ocx) * zoom + hw
+                sy = -(cam_y - ocy) * zoom + hh
+                some = np.ones(len(pos), bool)
+            else:                                                  # world_to_screen_with_depth, math.rs:621-652
+                vs = (f32(min(w, h)) / f32(2.0)) * f32(0.75)
+                denom = cam_z + f32(5.0)
+                sx = (cam_x * f32(4.0) / denom) * vs + hw
+                sy = (cam_y * f32(4.0) / denom) * vs + hh
+                some = ~(cam_z <= f32(0.1))
+            inside = (fv >= 0).all(1) & (fv < len(pos)).all(1)     # screen_verts.get(..): an index out of range skips the triangle
+            i = np.where(inside[:, None], fv, 0) if len(pos) else np.zeros_like(fv)
+            if not len(pos):
+                sx = sy = cam_z = np.zeros(1, f32); some = np.zeros(1, bool)
+            self.ok = inside & some[i[:, 0]] & some[i[:, 1]] & some[i[:, 2]]
+            self.x = [sx[i[:, k]] for k in range(3)]; self.y = [sy[i[:, k]] for k in range(3)]; self.d = [cam_z[i[:, k]] for k in range(3)]
+            x0, x1, x2 = self.x; y0, y1, y2 = self.y
+            self.area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)
+            self.front = ~(self.area <= f32(0.0))                  # modeler/viewport.rs:2571-2574 (a NaN area is not culled)
+
+    def candidates(self, mx, my, cull_backfaces=False):
+        """(triangle indices in face order, their depths) of every triangle the cursor hits."""
+        f32 = np.float32
+        px, py = f32(mx), f32(my)
+        x0, x1, x2 = self.x; y0, y1, y2 = self.y
+        with np.errstate(all="ignore"):
+            d1 = (px - x1) * (y0 - y1) - (x0 - x1) * (py - y1)     # point_in_triangle_2d, math.rs:687-706
+            d2 = (px - x2) * (y1 - y2) - (x1 - x2) * (py - y2)
+            d3 = (px - x0) * (y2 - y0) - (x2 - x0) * (py - y0)
+            has_neg = (d1 < 0) | (d2 < 0) | (d3 < 0)
+            has_pos = (d1 > 0) | (d2 > 0) | (d3 > 0)
+            hit = self.ok & ~(has_neg & has_pos)
+            if cull_backfaces:
+                hit &= self.front
+            t = np.nonzero(hit)[0]
+            x0, x1, x2 = (v[t] for v in self.x); y0, y1, y2 = (v[t] for v in self.y); e0, e1, e2 = (v[t] for v in self.d)
+            area = self.area[t]                                    # interpolate_depth_in_triangle, viewport_3d.rs:7485-7508
+            w0 = ((x1 - px) * (y2 - py) - (x2 - px) * (y1 - py)) / area
+            w1 = ((x2 - px) * (y0 - py) - (x0 - px) * (y2 - py)) / area
+            w2 = f32(1.0) - w0 - w1
+            depth = np.where(np.abs(area) < f32(0.0001), (e0 + e1 + e2) / f32(3.0), w0 * e0 + w1 * e1 + w2 * e2).astype(f32)
+        return t, depth
+
+    def pick(self, mx, my, cull_backfaces=False):
+        """(hit, tri, depth): the closest hit by the reference's strict `<` in face order -- the first of equal depths, a NaN depth only when
+        it is the first hit (reported as the quiet NaN 0x7FC00000); no hit: (False, 0xFFFFFFFF, 0.0)."""
+        t, depth = self.candidates(mx, my, cull_backfaces)
+        return _closest_in_order(t, depth)
+
+
+def _closest_in_order(ids, depth):
+    """`closest = None; for (id, depth): if closest is None or depth < closest.depth: closest = (depth, id)` without the loop."""
+    f32 = np.float32
+    if not len(ids):
+        return False, abi.PICK_NO_TRI, f32(0.0)
+    if np.isnan(depth[0]):
+        return True, int(ids[0]), np.array([0x7FC00000], np.uint32).view(f32)[0]
+    num = ~np.isnan(depth)
+    j = int(np.nonzero(num & (depth == depth[num].min()))[0][0])
+    return True, int(ids[j]), depth[j]
+
+
+def pick_mesh(vertices, faces, placement, camera, w, h, mx, my, ortho=None, cull_backfaces=False):
+    """Host mirror of one item of b32_pick_meshes (see PickMirror): (hit, tri, depth)."""
+    return PickMirror(vertices, faces, placement, camera, w, h, ortho).pick(mx, my, cull_backfaces)
+
+
+def pick_best(hits):
+    """The loop over the items (viewport_3d.rs:7370) on a PICK_HIT_DTYPE array: the index of the closest hit item, or -1."""
+    hits = np.asarray(hits, abi.PICK_HIT_DTYPE)
+    i = np.nonzero(hits["hit"])[0]
+    hit, best, _ = _closest_in_order(i, hits["depth"][i])
+    return best if hit else -1
+
+
+class PickResult:
+    """What b32_pick_meshes_async delivers into `buf` (16 + 16 * n bytes) once its ticket is done."""
+
+    def __init__(self, buf, n, owner=None):
+        self.buf, self.n, self._owner = buf, n, owner
+
+    @property
+    def best(self):
+        return int(self.buf[:4].view(np.int32)[0])
+
+    @property
+    def hits(self):
+        return self.buf[abi.PICK_HEADER_BYTES:abi.PICK_HEADER_BYTES + 16 * self.n].view(abi.PICK_HIT_DTYPE).copy()
+
+    def close(self):
+        if self._owner is not None:
+            ctx, p = self._owner
+            ctx.host_free(p)
+            self._owner = None
+
+
 def _pack_placement(placement):
     if placement is None or isinstance(placement, abi.B32Placement):
         return placement
@@ -239,6 +366,57 @@ class Context:
         d = C.c_int()
         _chk(self.lib.b32_ticket_poll(self.h, int(ticket), C.byref(d)), "b32_ticket_poll")
         return bool(d.value)
+
+    # ---- picking (b32_pick_meshes): which placed resident mesh, and which of its triangles, is under the cursor
+    @staticmethod
+    def make_pick_table(items):
+        """Packs [(detached ResidentScene, placement)] once; set_pick_placements rewrites the placements in place."""
+        n = len(items)
+        slots = (C.c_void_p * max(n, 1))()
+        places = (abi.B32Placement * max(n, 1))()
+        for i, (sc, _) in enumerate(items):
+            slots[i] = sc._slot if sc is not None else None
+        table = (slots, places, n)
+        Context.set_pick_placements(table, [pl for _, pl in items])
+        return table
+
+    @staticmethod
+    def set_pick_placements(table, placements):
+        for i, pl in enumerate(placements):
+            c, s, w = _placement_triple(pl)
+            table[1][i] = abi.B32Placement(float(c), float(s), (C.c_float * 3)(*[float(x) for x in w]))
+
+    def _pick_args(self, items, camera, mouse, ortho, cull_backfaces):
+        slots, places, n = items if isinstance(items, tuple) else self.make_pick_table(items)
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        o = _pack_ortho(ortho)
+        return (self.h, C.byref(cam), C.byref(o) if o is not None else None, float(mouse[0]), float(mouse[1]),
+                abi.PICK_CULL_BACKFACES if cull_backfaces else 0, slots, C.cast(places, C.c_void_p), n), n
+
+    def pick_meshes(self, items, camera, mouse, ortho=None, cull_backfaces=False):
+        """b32_pick_meshes: items = [(detached ResidentScene, Placement)] or a make_pick_table table -> (best, hits); best = -1 when
+        nothing is hit, hits = one abi.PICK_HIT_DTYPE record per item."""
+        args, n = self._pick_args(items, camera, mouse, ortho, cull_backfaces)
+        hits = np.zeros(n, abi.PICK_HIT_DTYPE)
+        best = C.c_int32(-1)
+        _chk(self.lib.b32_pick_meshes(*args, hits.ctypes.data if n else None, C.byref(best)), "b32_pick_meshes")
+        return int(best.value), hits
+
+    def pick_meshes_async(self, items, camera, mouse, ortho=None, cull_backfaces=False, out=None):
+        """b32_pick_meshes_async -> (ticket, PickResult).  out: an (array, pointer) pair from host_alloc of at least 16 + 16 * n bytes to
+        deliver into (reused from frame to frame); None: page-locked memory of the result's own, released by PickResult.close()."""
+        args, n = self._pick_args(items, camera, mouse, ortho, cull_backfaces)
+        need = abi.PICK_HEADER_BYTES + 16 * n
+        own = out is None
+        arr, ptr = self.host_alloc(need) if own else out
+        if len(arr) < need:
+            raise ValueError("pick_meshes_async: the result buffer is too small")
+        t = C.c_uint64()
+        rc = self.lib.b32_pick_meshes_async(*args, ptr, C.byref(t))
+        if rc != abi.B32_OK and own:
+            self.host_free(ptr)
+        _chk(rc, "b32_pick_meshes_async")
+        return int(t.value), PickResult(arr, n, (self, ptr) if own else None)
 
     def finish(self) -> T.RasterTimings:
         """b32_frame_finish of whatever this context has in flight."""

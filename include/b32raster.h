@@ -396,6 +396,46 @@ int b32_frame_submit_placed(b32_ctx* ctx, const B32Camera* camera, const B32Sett
 int b32_render_scene_15_placed_async(b32_ctx* ctx, const B32Camera* camera, const B32Settings* settings, const B32Fog* fog /* nullable */,
                                      const B32Placement* place /* nullable */);
 
+/* ---- picking: which placed resident mesh, and which of its triangles, lies under the cursor ----------------------------------------------
+ * check_mesh_hit (editor/viewport_3d.rs:7700-7756; called per visible part of every enabled object, :7344-7400) and the face branch of the
+ * modeler's find_hovered_element (modeler/viewport.rs:2544-2594) walk every triangle of meshes this library already holds.  An item is one
+ * (slot, placement) pair; for the cursor (mx, my) in framebuffer coordinates the device runs, per item,
+ *     closest = None
+ *     for t in 0..nf, in face order:
+ *         a vertex index >= nv                          -> skip (screen_verts.get(..) is None: no error)
+ *         P_k = (x*cos_f - z*sin_f + wx, y + wy, x*sin_f + z*cos_f + wz)      the placement is ALWAYS applied (no has_transform shortcut)
+ *         (sx_k, sy_k, d_k) = world_to_screen_with_depth(P_k) (ortho == NULL, math.rs:621-652) or
+ *                             world_to_screen_with_ortho_depth(P_k, ortho) (math.rs:580-617); any None -> skip
+ *         area = (sx1 - sx0)*(sy2 - sy0) - (sx2 - sx0)*(sy1 - sy0);  B32_PICK_CULL_BACKFACES and area <= 0.0 -> skip (a NaN area is kept)
+ *         !point_in_triangle_2d(mx, my, ...) (math.rs:687-706) -> skip
+ *         depth = interpolate_depth_in_triangle(...) (viewport_3d.rs:7485-7508)
+ *         if closest is None or depth < closest.depth: closest = (depth, t)
+ * and then, over the items in array order (viewport_3d.rs:7370),
+ *         if closest_i is Some and (best is None or closest_i.depth < best.depth): best = i
+ * with every expression an f32 operation in the reference's order (no contraction, Vec3::dot = (x*ox + y*oy) + z*oz).  The strict `<`
+ * decides everything and its consequences are reproduced: among equal depths (-0.0 == +0.0) the first in loop order wins and its own
+ * depth bits are reported; a hit with a NaN depth is taken when it is the first hit and then never replaced, and ignored after a number
+ * (a face (i, i, i) is hit from every cursor; a face with a NaN vertex passes the near test and is "inside" for every cursor).  One
+ * departure, as in b32_draw_world: a NaN depth is reported as the one quiet NaN 0x7FC00000.
+ * The framebuffer size is the context's (b32_fb_size); a band (b32_set_band) is ignored.  Slots must HOLD their scene, as for
+ * b32_frame_add_scene; the same slot may appear any number of times.  A NULL or empty slot, NULL places with n > 0, an unknown flag or a
+ * zero-size framebuffer -> B32_E_ARG; n > 65535 -> B32_E_UNSUPPORTED; n == 0 -> *best = -1.  Nothing about the numbers is validated.
+ * The work is enqueued on the context's stream behind the uploads into the slots.  It neither reads nor writes the framebuffer or the
+ * z-buffer, flushes no deferred clear, settles or supersedes no pending frame and changes no b32_batch_count.
+ * b32_pick_meshes_async performs no host synchronisation: it delivers 16 + 16 * n bytes -- {int32 best; uint32 n; 8 bytes of padding},
+ * then n B32PickHit -- into the caller's memory (preferably from b32_host_alloc) and completes through the tickets of
+ * b32_fb_download_async (b32_ticket_poll / _wait; the same limit of 8 outstanding).  b32_pick_meshes is the asynchronous form followed
+ * by a wait on its own ticket only. */
+typedef struct B32PickHit { uint32_t hit; uint32_t tri; float depth; uint32_t _pad; } B32PickHit;   /* 16 bytes; hit == 0: tri = 0xFFFFFFFF, depth = 0 */
+#define B32_PICK_CULL_BACKFACES 1u
+struct B32Ortho;                 /* OrthoProjection: defined with the world-space overlays below */
+int b32_pick_meshes(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, float mx, float my, uint32_t flags,
+                    b32_scene* const* slots, const B32Placement* places /* n entries, required */, uint32_t n,
+                    B32PickHit* hits /* n entries, nullable */, int32_t* best /* -1: nothing hit */);
+int b32_pick_meshes_async(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, float mx, float my, uint32_t flags,
+                          b32_scene* const* slots, const B32Placement* places /* n entries, required */, uint32_t n,
+                          void* out /* 16 + 16 * n bytes */, uint64_t* ticket);
+
 /* ---- the 8-bit-colour path: render_mesh (render.rs:1971-2264) + rasterize_triangle (render.rs:1202-1433) ----
  * What every caller of the reference runs when settings.use_rgb555 is false (scene.rs:163-169).  Same pipeline and settings
  * as render_mesh_15 except: Texture texels are Color values with a per-texel blend mode, no fog, no opaque/transparent
@@ -565,8 +605,8 @@ int b32_device_constants(b32_ctx* ctx, const char** names, uint32_t* bits, uint8
 
 /* Per-kernel device time of the last finished frame (HIP events on the ctx stream), for bench.py.
  * names[i] points at static strings; returns the number of entries written (<= cap).  While profiling is on (b32_set_profiling >= 1) the
- * projection kernel of the last b32_draw_world is timed too and reported as a further entry "world_project" (the call waits for it);
- * b32_set_profiling(ctx, 0) ends that. */
+ * projection kernel of the last b32_draw_world is timed too and reported as a further entry "world_project" (the call waits for it), and so
+ * are the two kernels of the last b32_pick_meshes[_async], as "pick"; b32_set_profiling(ctx, 0) ends that. */
 int b32_last_kernel_times(b32_ctx* ctx, const char** names, float* ms, uint32_t cap);
 /* HIP-event instrumentation of the frames enqueued from now on: 0 = none (default for the async path),
  * 1 = events around the coverage kernel (the dominant one), 2 = events around every phase
