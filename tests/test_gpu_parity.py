@@ -1385,8 +1385,10 @@ def test_batched_frame_equals_sequential_calls(oracle, zbuffer, counting, wire):
 def test_deferred_clear_is_never_observable(fast_ctx, oracle):
     """b32_fb_clear defers itself so that the frame that follows can fold it into its fused kernel (no clear launch).  Whatever else
     touches the framebuffer first must see the cleared frame: a download with no draw in between, a second clear with another
-    colour, a band change, a sky pass, a z-buffer frame (depth reset too), a frame that draws nothing (empty mesh), tiles no
-    surface reaches, and a bound device tensor read after b32_synchronize."""
+    colour, a band change, a z-buffer frame (depth reset too), a frame that draws nothing (empty mesh), tiles no surface reaches,
+    and a bound device tensor read after b32_synchronize.  A sky pass, the star sprites, a clear_gradient and the presenter after a
+    deferred clear are in test_sky_present.py: test_gpu_deferred_clear_before_sky_stars_gradient and
+    test_gpu_present_sees_a_deferred_clear_and_a_pending_frame."""
     import torch
     from bonnie32_amd import rasterizer as R
     sc = scenegen.make_scene("C3", n_tris=20_000, width=640, height=480, bbox_px=200.0, seed=12)
