@@ -63,6 +63,18 @@ assert PICK_HIT_DTYPE.itemsize == 16
 PICK_CULL_BACKFACES = 1
 PICK_HEADER_BYTES = 16              # b32_pick_meshes_async's result: {int32 best; uint32 n; 8 bytes of padding}, then n B32PickHit
 PICK_NO_TRI = 0xFFFFFFFF
+# B32HoverParams / B32HoverResult (b32_hover_mesh) and B32BoxParams (b32_box_select)
+HOVER_PARAMS_DTYPE = np.dtype([("mx", "<f4"), ("my", "<f4"), ("vertex_threshold", "<f4"), ("edge_threshold", "<f4"), ("flags", "<u4"),
+                               ("mirror_axis", "<u4"), ("mirror_threshold", "<f4"), ("_pad", "<u4")])
+HOVER_RESULT_DTYPE = np.dtype([("vertex", "<u4"), ("vertex_dist", "<f4"), ("edge_v0", "<u4"), ("edge_v1", "<u4"), ("edge_dist", "<f4"),
+                               ("face", "<u4"), ("face_depth", "<f4"), ("_pad", "<u4")])
+BOX_PARAMS_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("mode", "<u4"), ("_pad", "<u4", 3)])
+assert HOVER_PARAMS_DTYPE.itemsize == 32 and HOVER_RESULT_DTYPE.itemsize == 32 and BOX_PARAMS_DTYPE.itemsize == 32
+HOVER_SEE_THROUGH = 1
+HOVER_NONE = 0xFFFFFFFF
+HOVER_VERTEX_THRESHOLD, HOVER_EDGE_THRESHOLD = 6.0, 4.0      # viewport.rs:2428-2429
+BOX_VERTICES, BOX_POLYGONS = 0, 1
+BOX_HEADER_BYTES = 16               # b32_box_select_async's result: {uint32 n_elements; uint32 n_selected; 8 bytes of padding}, then the words
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -165,6 +177,12 @@ SYMBOLS = [
     ("b32_render_scene_15_placed_async", C.c_int, [_P, _P, _P, _P, _P]),
     ("b32_pick_meshes", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(_P), _P, C.c_uint32, _P, C.POINTER(C.c_int32)]),
     ("b32_pick_meshes_async", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_uint32, C.POINTER(_P), _P, C.c_uint32, _P, C.POINTER(C.c_uint64)]),
+    ("b32_topology_create", C.c_int, [_P, _P, C.c_uint32, _P, C.POINTER(_P)]),
+    ("b32_topology_destroy", None, [_P, _P]),
+    ("b32_hover_mesh", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("b32_hover_mesh_async", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("b32_box_select", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    ("b32_box_select_async", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("b32_fb_clear_gradient", C.c_int, [_P] + [C.c_uint8] * 8),
     ("b32_fb_clear_transparent", C.c_int, [_P]),
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),

@@ -67,6 +67,9 @@ void b32_destroy(b32_ctx* c) {
     if (c->pick_words) (void)hipFree(c->pick_words);
     if (c->pick_host) (void)hipHostFree(c->pick_host);
     for (hipEvent_t e : c->pick_tev) if (e) (void)hipEventDestroy(e);
+    if (c->hover_bits) (void)hipFree(c->hover_bits);
+    if (c->hover_words) (void)hipFree(c->hover_words);
+    for (hipEvent_t e : c->hover_tev) if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
@@ -700,6 +703,12 @@ int b32_last_kernel_times(b32_ctx* c, const char** names, float* ms, uint32_t ca
         hipEventElapsedTime(&pick_ms, c->pick_tev[0], c->pick_tev[1]) == hipSuccess) {
         names[k] = "pick"; ms[k] = pick_ms; ++k;
     }
+    // ... and the kernels of the last b32_hover_mesh[_async]
+    float hover_ms = 0.0f;
+    if (c->hover_timed && k < cap && hipEventSynchronize(c->hover_tev[1]) == hipSuccess &&
+        hipEventElapsedTime(&hover_ms, c->hover_tev[0], c->hover_tev[1]) == hipSuccess) {
+        names[k] = "hover"; ms[k] = hover_ms; ++k;
+    }
     return (int)k;
 }
 
@@ -736,6 +745,7 @@ extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {
 extern "C" int b32_set_profiling(b32_ctx* c, int level) {
     if (!c) return B32_E_ARG;
     c->profile_level = level < 0 ? 0 : (level > 2 ? 2 : level);
+    if (!c->profile_level) c->hover_timed = false;
     if (!c->profile_level) c->world_timed = false;      // (b32_last_kernel_times no longer reports "world_project")
     c->prof_seq = 0;
     if (c->profile_level >= 1 && !c->ev_created) {      // (here, not in the first profiled frame: 384 hipEventCreate calls are ~0.2 ms of host time)

@@ -243,6 +243,12 @@ struct b32_ctx {
     void* pick_res[PICK_RING] = {}; size_t pick_cap_res[PICK_RING] = {}; hipEvent_t pick_done[PICK_RING] = {}, pick_left[PICK_RING] = {}; uint32_t pick_slot = 0;
     void* pick_host = nullptr; size_t pick_cap_host = 0;
     hipEvent_t pick_tev[2] = {}; bool pick_timed = false;
+    // b32_hover_mesh / b32_box_select[_async] (b32_hover.hip): the front pass's vertex bitmap and, behind it, its edge bitmap (all zero
+    // between two calls), the minima of a hover (HoverWords, all ones between two calls), HIP events around the last hover enqueued while
+    // profiling was on (b32_last_kernel_times "hover").  Results leave through the pick's ring of result buffers.
+    uint32_t* hover_bits = nullptr; size_t hover_cap_bits = 0;
+    void* hover_words = nullptr;
+    hipEvent_t hover_tev[2] = {}; bool hover_timed = false;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only
@@ -341,7 +347,7 @@ constexpr size_t STAGE_BYTES = (size_t)1 << 20, STAGE_CTRL_OFF = STAGE_BYTES - 1
 extern "C" {
 B32_INTERNAL int settle_pending(b32_ctx* c);                                      // b32_api.hip
 B32_INTERNAL int flush_clear(b32_ctx* c);                                         // b32_api.hip
-// The next ticket (b32_fb_download_async, b32_pick_meshes_async): its number and its event, created on first use, else waited for when
+// The next ticket (b32_fb_download_async, b32_pick_meshes_async, b32_hover_mesh_async, b32_box_select_async): its number and its event, created on first use, else waited for when
 // it still belongs to the ticket DL_RING tickets ago; the transfer stream exists afterwards.  The caller records *ev on dl_stream and
 // then sets dl_seq = t.
 B32_INTERNAL int ticket_open(b32_ctx* c, unsigned long long& t, hipEvent_t*& ev); // b32_api.hip

@@ -13,6 +13,7 @@
 //
 // The Rust shim a maintainer would add to the reference is shown in INTEGRATION.md; it binds the same C symbols.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -476,6 +477,209 @@ inline int32_t pick_best(const std::vector<B32PickHit>& hits) {
     for (size_t i = 0; i < hits.size(); ++i) if (hits[i].hit && (best < 0 || hits[i].depth < hits[(size_t)best].depth)) best = (int32_t)i;
     return best;
 }
+// Hover and box selection: the modeler's find_hovered_element (modeler/viewport.rs:2379-2601) and apply_box_selection
+// (modeler/viewport.rs:1624-1779) for ONE resident mesh, on the device (b32_hover_mesh, b32_box_select).  A Topology holds the modeler's
+// polygons over the mesh's vertices (to_render_data_textured keeps the vertices 1:1, mesh_editor.rs:1623-1653).  Without a placement the
+// vertices are used as they are; a placement is always applied.  ortho: OrthoProjection as (zoom, center_x, center_y).
+class Topology {
+public:
+    Topology(Framebuffer& fb, const std::vector<uint32_t>& poly_start, const std::vector<uint32_t>& poly_verts) : ctx_(fb.ctx()), np_(poly_start.empty() ? 0 : (uint32_t)poly_start.size() - 1) {
+        if (np_ && poly_start.back() != poly_verts.size()) throw Error(B32_E_ARG, "Topology: poly_start must end at poly_verts.size()");
+        check(b32_topology_create(ctx_, poly_start.data(), np_, poly_verts.data(), &t_), "topology_create");
+    }
+    // the trivial topology of a triangle list: poly_start = 0, 3, 6, ...
+    static Topology triangles(Framebuffer& fb, const std::vector<Face>& faces) {
+        std::vector<uint32_t> start(faces.size() + 1), verts; verts.reserve(faces.size() * 3);
+        for (size_t i = 0; i <= faces.size(); ++i) start[i] = (uint32_t)(3 * i);
+        for (const auto& f : faces) { verts.push_back((uint32_t)f.v0); verts.push_back((uint32_t)f.v1); verts.push_back((uint32_t)f.v2); }
+        return Topology(fb, start, verts);
+    }
+    ~Topology() { if (t_) b32_topology_destroy(ctx_, t_); }
+    Topology(Topology&& o) noexcept : ctx_(o.ctx_), t_(o.t_), np_(o.np_) { o.t_ = nullptr; }
+    Topology(const Topology&) = delete;
+    Topology& operator=(const Topology&) = delete;
+    b32_topology* handle() const { return t_; }
+    uint32_t polygons() const { return np_; }
+private:
+    b32_ctx* ctx_ = nullptr; b32_topology* t_ = nullptr; uint32_t np_ = 0;
+};
+inline B32HoverParams hover_params(float mx, float my, bool see_through = false, uint32_t mirror_axis = 0, float mirror_threshold = 1.0f) {
+    return B32HoverParams{ mx, my, 6.0f, 4.0f, see_through ? B32_HOVER_SEE_THROUGH : 0u, mirror_axis, mirror_threshold, 0u };   // viewport.rs:2428-2429
+}
+namespace detail {
+struct MeshCall {                                                              // the packed arguments of one hover / box selection
+    B32Camera cam; B32Ortho ortho; bool has_ortho; B32Placement place; bool placed;
+    MeshCall(const Camera& camera, const std::optional<Vec3>& o, const std::optional<Placement>& p) : cam(pack(camera)), has_ortho((bool)o), placed((bool)p) {
+        ortho = o ? B32Ortho{ o->x, o->y, o->z } : B32Ortho{ 0, 0, 0 };
+        place = p ? B32Placement{ p->cos_f, p->sin_f, { p->world_pos.x, p->world_pos.y, p->world_pos.z } } : B32Placement{ 1.0f, 0.0f, { 0, 0, 0 } };
+    }
+};
+}  // namespace detail
+inline B32HoverResult hover_mesh(Framebuffer& fb, const ResidentMesh& mesh, const Topology& top, const Camera& camera, const B32HoverParams& params,
+                                 const std::optional<Vec3>& ortho = std::nullopt, const std::optional<Placement>& placement = std::nullopt) {
+    const detail::MeshCall c(camera, ortho, placement);
+    B32HoverResult r{};
+    check(b32_hover_mesh(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mesh.slot(), top.handle(), c.placed ? &c.place : nullptr, &params, &r), "hover_mesh");
+    return r;
+}
+// The asynchronous form: `out` (32 bytes, preferably from b32_host_alloc) holds a B32HoverResult once the returned ticket is done.
+inline uint64_t hover_mesh_async(Framebuffer& fb, const ResidentMesh& mesh, const Topology& top, const Camera& camera, const B32HoverParams& params, void* out,
+                                 const std::optional<Vec3>& ortho = std::nullopt, const std::optional<Placement>& placement = std::nullopt) {
+    const detail::MeshCall c(camera, ortho, placement);
+    uint64_t ticket = 0;
+    check(b32_hover_mesh_async(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mesh.slot(), top.handle(), c.placed ? &c.place : nullptr, &params, out, &ticket),
+          "hover_mesh_async");
+    return ticket;
+}
+// find_hovered_element's return tuple (viewport.rs:2596-2600): the vertex; the edge only without a vertex; the face only without either
+struct HoveredElement { std::optional<uint32_t> vertex; std::optional<std::pair<uint32_t, uint32_t>> edge; std::optional<uint32_t> face; };
+inline HoveredElement hovered_element(const B32HoverResult& r) {
+    HoveredElement e;
+    if (r.vertex != 0xFFFFFFFFu) e.vertex = r.vertex;
+    else if (r.edge_v0 != 0xFFFFFFFFu) e.edge = std::make_pair(r.edge_v0, r.edge_v1);
+    else if (r.face != 0xFFFFFFFFu) e.face = r.face;
+    return e;
+}
+struct BoxSelection { uint32_t n_selected = 0; std::vector<uint32_t> words; bool test(size_t i) const { return (words[i >> 5] >> (i & 31)) & 1u; } };
+// mode B32_BOX_VERTICES: n_elements = the mesh's vertex count, top may be NULL; B32_BOX_POLYGONS: n_elements = top->polygons()
+inline BoxSelection box_select(Framebuffer& fb, const ResidentMesh& mesh, const Topology* top, const Camera& camera, float x0, float y0, float x1, float y1,
+                               uint32_t mode, size_t n_elements, const std::optional<Vec3>& ortho = std::nullopt,
+                               const std::optional<Placement>& placement = std::nullopt) {
+    const detail::MeshCall c(camera, ortho, placement);
+    const B32BoxParams prm{ x0, y0, x1, y1, mode, { 0, 0, 0 } };
+    BoxSelection r; r.words.assign((n_elements + 31) / 32, 0u);
+    check(b32_box_select(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mesh.slot(), top ? top->handle() : nullptr, c.placed ? &c.place : nullptr, &prm,
+                         r.words.data(), &r.n_selected), "box_select");
+    return r;
+}
+// The host restatements (what a host without the library walks per mouse move): separately rounded f32 operations in the reference's order
+// (compile with -ffp-contract=off where the compiler would fuse).
+namespace detail {
+struct HoverScreen { bool some; float x, y, d; };
+inline Vec3 hover_world(const Vec3& v, const std::optional<Placement>& p) {
+    if (!p) return v;
+    const float rx = v.x * p->cos_f - v.z * p->sin_f, rz = v.x * p->sin_f + v.z * p->cos_f;
+    return { rx + p->world_pos.x, v.y + p->world_pos.y, rz + p->world_pos.z };
+}
+inline HoverScreen hover_project(const Vec3& world, const Camera& cam, size_t w, size_t h, const std::optional<Vec3>& ortho) {   // math.rs:538-575
+    const auto dot = [](Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
+    const Vec3 rel{ world.x - cam.position.x, world.y - cam.position.y, world.z - cam.position.z };
+    const float cx = dot(rel, cam.basis_x), cy = dot(rel, cam.basis_y), cz = dot(rel, cam.basis_z);
+    HoverScreen s{ true, 0, 0, cz };
+    if (ortho) { s.x = (cx - ortho->y) * ortho->x + ((float)w / 2.0f); s.y = -(cy - ortho->z) * ortho->x + ((float)h / 2.0f); }
+    else if (cz <= 0.1f) s.some = false;
+    else {
+        const float vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f, denom = cz + 5.0f;
+        s.x = (cx * 4.0f / denom) * vs + ((float)w / 2.0f); s.y = (cy * 4.0f / denom) * vs + ((float)h / 2.0f);
+    }
+    return s;
+}
+inline float hover_dist(float px, float py, float x, float y) { const float dx = px - x, dy = py - y; return std::sqrt(dx * dx + dy * dy); }
+inline float point_to_line_distance(float px, float py, float x0, float y0, float x1, float y1) {   // viewport.rs:2604-2622
+    const float dx = x1 - x0, dy = y1 - y0, len_sq = dx * dx + dy * dy;
+    if (len_sq < 0.001f) return hover_dist(px, py, x0, y0);
+    float t = ((px - x0) * dx + (py - y0) * dy) / len_sq;
+    if (t < 0.0f) t = 0.0f;
+    if (t > 1.0f) t = 1.0f;
+    return hover_dist(px, py, x0 + t * dx, y0 + t * dy);
+}
+}  // namespace detail
+inline B32HoverResult hover_mesh(const std::vector<Vertex>& vertices, const std::vector<uint32_t>& poly_start, const std::vector<uint32_t>& poly_verts,
+                                 const std::optional<Placement>& placement, const Camera& cam, size_t w, size_t h, const B32HoverParams& prm,
+                                 const std::optional<Vec3>& ortho = std::nullopt) {
+    const size_t nv = vertices.size(), np = poly_start.empty() ? 0 : poly_start.size() - 1;
+    const bool cull = !(prm.flags & B32_HOVER_SEE_THROUGH);
+    std::vector<detail::HoverScreen> sv; sv.reserve(nv);
+    for (const auto& v : vertices) sv.push_back(detail::hover_project(detail::hover_world(v.pos, placement), cam, w, h, ortho));
+    const auto editable = [&](size_t i) {                                        // state.rs:797-806
+        const Vec3& p = vertices[i].pos;
+        return prm.mirror_axis == 0 || (prm.mirror_axis == 1 ? p.x : prm.mirror_axis == 2 ? p.y : p.z) >= -prm.mirror_threshold;
+    };
+    const auto norm = [](uint32_t a, uint32_t b) { return ((uint64_t)(a < b ? a : b) << 32) | (a < b ? b : a); };
+    std::vector<bool> vfront(nv, false); std::vector<uint64_t> efront;
+    if (cull) {                                                                 // viewport.rs:2435-2473
+        for (size_t p = 0; p < np; ++p) {
+            const uint32_t s = poly_start[p], n = poly_start[p + 1] - s;
+            if (n < 3) continue;
+            const uint32_t i0 = poly_verts[s], i1 = poly_verts[s + 1], i2 = poly_verts[s + 2];
+            if (i0 >= nv || i1 >= nv || i2 >= nv || !sv[i0].some || !sv[i1].some || !sv[i2].some) continue;
+            const float area = (sv[i1].x - sv[i0].x) * (sv[i2].y - sv[i0].y) - (sv[i2].x - sv[i0].x) * (sv[i1].y - sv[i0].y);
+            if (!(area > 0.0f)) continue;
+            for (uint32_t k = 0; k < n; ++k) {
+                const uint32_t a = poly_verts[s + k], b = poly_verts[s + (k + 1) % n];
+                if (a < nv) vfront[a] = true;
+                efront.push_back(norm(a, b));
+            }
+        }
+        std::sort(efront.begin(), efront.end());
+    }
+    B32HoverResult r{ 0xFFFFFFFFu, 0.0f, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0xFFFFFFFFu, 0.0f, 0u };
+    for (size_t i = 0; i < nv; ++i) {                                           // viewport.rs:2475-2505
+        if ((cull && !vfront[i]) || !editable(i) || !sv[i].some) continue;
+        const float dist = detail::hover_dist(prm.mx, prm.my, sv[i].x, sv[i].y);
+        if (dist < prm.vertex_threshold && (r.vertex == 0xFFFFFFFFu || dist < r.vertex_dist)) { r.vertex = (uint32_t)i; r.vertex_dist = dist; }
+    }
+    for (size_t p = 0; p < np; ++p) {                                           // viewport.rs:2507-2542
+        const uint32_t s = poly_start[p], n = poly_start[p + 1] - s;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t a = poly_verts[s + k], b = poly_verts[s + (k + 1) % n];
+            if (cull && !std::binary_search(efront.begin(), efront.end(), norm(a, b))) continue;
+            if (a >= nv || b >= nv || !editable(a) || !editable(b) || !sv[a].some || !sv[b].some) continue;
+            const float dist = detail::point_to_line_distance(prm.mx, prm.my, sv[a].x, sv[a].y, sv[b].x, sv[b].y);
+            if (dist < prm.edge_threshold && (r.edge_v0 == 0xFFFFFFFFu || dist < r.edge_dist)) { r.edge_v0 = a < b ? a : b; r.edge_v1 = a < b ? b : a; r.edge_dist = dist; }
+        }
+    }
+    bool any = false; float closest = 0.0f;
+    for (size_t p = 0; p < np; ++p) {                                           // viewport.rs:2544-2594
+        const uint32_t s = poly_start[p], n = poly_start[p + 1] - s;
+        bool ok = true;
+        for (uint32_t k = 0; k < n && ok; ++k) ok = poly_verts[s + k] < nv && editable(poly_verts[s + k]);
+        if (!ok) continue;
+        for (uint32_t k = 1; k + 1 < n; ++k) {
+            const detail::HoverScreen &a = sv[poly_verts[s]], &b = sv[poly_verts[s + k]], &c = sv[poly_verts[s + k + 1]];
+            if (!a.some || !b.some || !c.some) continue;
+            const float mx = prm.mx, my = prm.my;
+            const float area = (b.x - a.x) * (c.y - a.y) - (c.x - a.x) * (b.y - a.y);
+            if (cull && area <= 0.0f) continue;
+            const auto sign = [&](const detail::HoverScreen& u, const detail::HoverScreen& v) { return (mx - v.x) * (u.y - v.y) - (u.x - v.x) * (my - v.y); };
+            const float d1 = sign(a, b), d2 = sign(b, c), d3 = sign(c, a);
+            if (((d1 < 0.0f) || (d2 < 0.0f) || (d3 < 0.0f)) && ((d1 > 0.0f) || (d2 > 0.0f) || (d3 > 0.0f))) continue;
+            float depth;
+            if (std::fabs(area) < 0.0001f) depth = ((a.d + b.d) + c.d) / 3.0f;
+            else {
+                const float w0 = ((b.x - mx) * (c.y - my) - (c.x - mx) * (b.y - my)) / area;
+                const float w1 = ((c.x - mx) * (a.y - my) - (a.x - mx) * (c.y - my)) / area;
+                const float w2 = (1.0f - w0) - w1;
+                depth = (w0 * a.d + w1 * b.d) + w2 * c.d;
+            }
+            if (!any || depth < closest) { any = true; closest = depth; r.face = (uint32_t)p; }
+        }
+    }
+    if (any) { if (closest != closest) { const uint32_t q = 0x7FC00000u; std::memcpy(&closest, &q, 4); } r.face_depth = closest; }
+    return r;
+}
+inline BoxSelection box_select(const std::vector<Vertex>& vertices, const std::vector<uint32_t>& poly_start, const std::vector<uint32_t>& poly_verts,
+                               const std::optional<Placement>& placement, const Camera& cam, size_t w, size_t h, float x0, float y0, float x1, float y1,
+                               uint32_t mode, const std::optional<Vec3>& ortho = std::nullopt) {
+    const size_t nv = vertices.size(), np = poly_start.empty() ? 0 : poly_start.size() - 1, n = mode == B32_BOX_POLYGONS ? np : nv;
+    BoxSelection r; r.words.assign((n + 31) / 32, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        Vec3 world;
+        if (mode == B32_BOX_POLYGONS) {                                         // viewport.rs:1743-1766
+            Vec3 acc{ 0, 0, 0 }; size_t cnt = 0;
+            for (uint32_t j = poly_start[i]; j < poly_start[i + 1]; ++j) if (poly_verts[j] < nv) {
+                const Vec3 p = detail::hover_world(vertices[poly_verts[j]].pos, placement);
+                acc = { acc.x + p.x, acc.y + p.y, acc.z + p.z }; ++cnt;
+            }
+            if (!cnt) continue;
+            const float inv = 1.0f / (float)cnt;
+            world = { acc.x * inv, acc.y * inv, acc.z * inv };
+        } else world = detail::hover_world(vertices[i].pos, placement);          // viewport.rs:1708-1726
+        const detail::HoverScreen s = detail::hover_project(world, cam, w, h, ortho);
+        if (s.some && s.x >= x0 && s.x <= x1 && s.y >= y0 && s.y <= y1) { r.words[i >> 5] |= 1u << (i & 31); ++r.n_selected; }
+    }
+    return r;
+}
 namespace detail {
 inline bool pack(const std::optional<Placement>& p, B32Placement& out) {
     if (!p || !p->has_transform) return false;
@@ -520,18 +724,21 @@ inline RasterTimings render_frame(Framebuffer& fb, const std::vector<std::pair<c
 // (b32_frame_submit: the mesh table in one call) and the copy of the finished frame into page-locked memory (b32_fb_download_async), and
 // returns a ticket; wait(ticket) blocks until THAT frame's pixels are in the returned buffer.  Two buffers alternate, so the presenter reads
 // frame i while frame i + 1 is drawn: keep at most two tickets outstanding.  A frame may carry one pick (submit's `pick`): it is enqueued
-// behind the frame's draws, delivered into page-locked memory of its own and waited for one frame behind like the pixels (wait_pick).
+// behind the frame's draws, delivered into page-locked memory of its own and waited for one frame behind like the pixels (wait_pick); and,
+// beside it, one hover of one of its meshes (submit's `hover`, wait_hover).
+struct FrameHover { const ResidentMesh* mesh; const Topology* topology; B32HoverParams params; std::optional<Vec3> ortho = std::nullopt; std::optional<Placement> placement = std::nullopt; };
 struct FramePick { std::vector<PickItem> items; float mx = 0, my = 0; std::optional<Vec3> ortho = std::nullopt; bool cull_backfaces = false; };
 class FrameLoop {
 public:
     explicit FrameLoop(Framebuffer& fb) : fb_(fb) {
         for (auto& b : buf_) { b = static_cast<uint8_t*>(b32_host_alloc(fb.width * fb.height * 4)); if (!b) throw Error(B32_E_HIP, "b32_host_alloc"); }
+        hover_buf_ = static_cast<B32HoverResult*>(b32_host_alloc(2 * sizeof(B32HoverResult))); if (!hover_buf_) throw Error(B32_E_HIP, "b32_host_alloc");
     }
-    ~FrameLoop() { b32_synchronize(fb_.ctx()); for (auto b : buf_) b32_host_free(b); for (auto b : pick_buf_) b32_host_free(b); }
+    ~FrameLoop() { b32_synchronize(fb_.ctx()); for (auto b : buf_) b32_host_free(b); for (auto b : pick_buf_) b32_host_free(b); b32_host_free(hover_buf_); }
     FrameLoop(const FrameLoop&) = delete;
     FrameLoop& operator=(const FrameLoop&) = delete;
     uint64_t submit(Color clear, const std::vector<std::pair<const ResidentMesh*, MeshParams>>& meshes, const Camera& camera, const RasterSettings& base,
-                    const FramePick* pick = nullptr) {
+                    const FramePick* pick = nullptr, const FrameHover* hover = nullptr) {
         const std::vector<B32Light> l = detail::pack(base.lights);
         const B32Camera c = detail::pack(camera);
         const B32Settings s = detail::pack(base, l);
@@ -557,8 +764,18 @@ public:
             }
             pick_ticket_[k] = pick_meshes_async(fb_, pick->items, camera, pick->mx, pick->my, pick_buf_[k], pick->ortho, pick->cull_backfaces);
         }
+        hover_ticket_[k] = 0;
+        if (hover) hover_ticket_[k] = hover_mesh_async(fb_, *hover->mesh, *hover->topology, camera, hover->params, hover_buf_ + k, hover->ortho, hover->placement);
         check(b32_fb_download_async(fb_.ctx(), buf_[k], &ticket_[k]), "fb_download_async");
         return ticket_[k];
+    }
+    // the hover that travelled with the frame of `ticket` (submit's `hover`), once it has landed
+    B32HoverResult wait_hover(uint64_t ticket) {
+        for (size_t k = 0; k < 2; ++k) if (ticket_[k] == ticket && hover_ticket_[k]) {
+            check(b32_ticket_wait(fb_.ctx(), hover_ticket_[k]), "ticket_wait");
+            return hover_buf_[k];
+        }
+        throw Error(B32_E_ARG, "FrameLoop::wait_hover: no hover travelled with this ticket, or its buffer has been reused");
     }
     // the pick that travelled with the frame of `ticket` (submit's `pick`), once it has landed
     PickResult wait_pick(uint64_t ticket) {
@@ -581,6 +798,7 @@ private:
     uint8_t* buf_[2] = { nullptr, nullptr };
     uint64_t ticket_[2] = { 0, 0 };
     void* pick_buf_[2] = { nullptr, nullptr }; size_t pick_cap_[2] = { 0, 0 }; uint64_t pick_ticket_[2] = { 0, 0 };
+    B32HoverResult* hover_buf_ = nullptr; uint64_t hover_ticket_[2] = { 0, 0 };
     size_t n_ = 0;
 };
 

@@ -207,6 +207,302 @@ class PickResult:
             self._owner = None
 
 
+# ---- hover and box selection (b32_hover_mesh, b32_box_select): the modeler's find_hovered_element / apply_box_selection for one mesh
+def _project_f32(x, y, z, camera, w, h, ortho):
+    """world_to_screen_with_ortho (math.rs:538-575) on f32 arrays: (sx, sy, cam_z, some)."""
+    f32 = np.float32
+    cp, bx, by, bz = (tuple(f32(v) for v in getattr(camera, n)) for n in ("position", "basis_x", "basis_y", "basis_z"))
+    rel = (x - cp[0], y - cp[1], z - cp[2])
+    cam_x, cam_y, cam_z = ((rel[0] * b[0] + rel[1] * b[1]) + rel[2] * b[2] for b in (bx, by, bz))
+    hw, hh = f32(w) / f32(2.0), f32(h) / f32(2.0)
+    if ortho is not None:
+        zoom, ocx, ocy = (f32(v) for v in ortho)
+        return (cam_x - ocx) * zoom + hw, -(cam_y - ocy) * zoom + hh, cam_z, np.ones(len(x), bool)
+    vs = (f32(min(w, h)) / f32(2.0)) * f32(0.75)
+    denom = cam_z + f32(5.0)
+    return (cam_x * f32(4.0) / denom) * vs + hw, (cam_y * f32(4.0) / denom) * vs + hh, cam_z, ~(cam_z <= f32(0.1))
+
+
+def _world_f32(pos, placement):
+    """The positions the modeler's loops project: as they are (placement None) or placed as in PickMirror."""
+    x, y, z = pos[:, 0], pos[:, 1], pos[:, 2]
+    if placement is None:
+        return x, y, z
+    c, s, wp = _placement_triple(placement)
+    return (x * c - z * s) + wp[0], y + wp[1], (x * s + z * c) + wp[2]
+
+
+def _positions(vertices):
+    return np.ascontiguousarray(vertices["pos"] if getattr(vertices, "dtype", None) is not None and vertices.dtype.names else vertices, np.float32).reshape(-1, 3)
+
+
+class Topology:
+    """The modeler's polygons over a slot's vertices (b32_topology): poly_start (np + 1, non-decreasing, [0] == 0) into poly_verts.  The
+    constructor derives what b32_topology_create derives: the half-edges (v[k], v[(k + 1) % n]) in loop order (Face::edges,
+    mesh_editor.rs:92-95) with the id of their normalised edge, and the fan triangles in loop order (Face::triangulate,
+    mesh_editor.rs:99-112) with their polygon.  handle(ctx) is the device object (created on first use, released by close())."""
+
+    def __init__(self, poly_start, poly_verts):
+        self.poly_start = np.ascontiguousarray(poly_start, np.uint32).reshape(-1)
+        self.poly_verts = np.ascontiguousarray(poly_verts, np.uint32).reshape(-1)
+        if len(self.poly_start) < 1 or self.poly_start[0] != 0 or (np.diff(self.poly_start.astype(np.int64)) < 0).any() or int(self.poly_start[-1]) != len(self.poly_verts):
+            raise ValueError("Topology: poly_start must start at 0, not decrease and end at len(poly_verts)")
+        self.np = len(self.poly_start) - 1
+        st = self.poly_start.astype(np.int64)
+        self.count = np.diff(st)
+        self.poly_of = np.repeat(np.arange(self.np, dtype=np.int64), self.count)       # polygon of every position of poly_verts
+        k = np.arange(len(self.poly_verts), dtype=np.int64) - st[:-1][self.poly_of]
+        pv = self.poly_verts.astype(np.int64)
+        self.he_v0 = pv
+        self.he_v1 = pv[st[:-1][self.poly_of] + (k + 1) % np.maximum(self.count[self.poly_of], 1)] if len(pv) else pv
+        key = (np.minimum(self.he_v0, self.he_v1) << 32) | np.maximum(self.he_v0, self.he_v1)
+        uniq, self.he_edge = np.unique(key, return_inverse=True) if len(pv) else (key, np.zeros(0, np.int64))
+        self.ne = len(uniq)
+        fan_poly = np.repeat(np.arange(self.np, dtype=np.int64), np.maximum(self.count - 2, 0))
+        j = np.arange(len(fan_poly), dtype=np.int64) - np.concatenate([[0], np.cumsum(np.maximum(self.count - 2, 0))])[:-1][fan_poly] + 1
+        base = st[:-1][fan_poly]
+        self.fan = np.stack([pv[base], pv[base + j], pv[base + j + 1]], 1) if len(fan_poly) else np.zeros((0, 3), np.int64)
+        self.fan_poly = fan_poly
+        self._handles = []
+
+    @classmethod
+    def from_polygons(cls, polygons):
+        """polygons: a list of vertex-index lists."""
+        start = np.concatenate([[0], np.cumsum([len(p) for p in polygons])]).astype(np.uint32)
+        verts = np.array([i for p in polygons for i in p], np.uint32)
+        return cls(start, verts)
+
+    @classmethod
+    def triangles(cls, faces):
+        """The trivial topology of a triangle list (FACE_DTYPE faces or an (n, 3) index array): poly_start = 0, 3, 6, ..."""
+        fv = np.ascontiguousarray(faces["v"] if getattr(faces, "dtype", None) is not None and faces.dtype.names else faces, np.uint32).reshape(-1, 3)
+        return cls(np.arange(len(fv) + 1, dtype=np.uint32) * 3, fv.reshape(-1))
+
+    def handle(self, ctx):
+        for c, h in self._handles:
+            if c is ctx:
+                return h
+        h = C.c_void_p()
+        _chk(ctx.lib.b32_topology_create(ctx.h, abi.ptr(self.poly_start), self.np, abi.ptr(self.poly_verts) if len(self.poly_verts) else None, C.byref(h)),
+             "b32_topology_create")
+        self._handles.append((ctx, h))
+        return h
+
+    def close(self):
+        for c, h in self._handles:
+            if getattr(c, "h", None):
+                c.lib.b32_topology_destroy(c.h, h)
+        self._handles = []
+
+
+class _FanMirror(PickMirror):
+    """PickMirror's triangle loop over already projected vertices (the fan triangles of a Topology)."""
+
+    def __init__(self, sx, sy, cam_z, some, fv):
+        f32 = np.float32
+        n = len(sx)
+        inside = (fv >= 0).all(1) & (fv < n).all(1)
+        i = np.where(inside[:, None], fv, 0) if n else np.zeros_like(fv)
+        if not n:
+            sx = sy = cam_z = np.zeros(1, f32); some = np.zeros(1, bool)
+        with np.errstate(all="ignore"):
+            self.ok = inside & some[i[:, 0]] & some[i[:, 1]] & some[i[:, 2]]
+            self.x = [sx[i[:, k]] for k in range(3)]; self.y = [sy[i[:, k]] for k in range(3)]; self.d = [cam_z[i[:, k]] for k in range(3)]
+            x0, x1, x2 = self.x; y0, y1, y2 = self.y
+            self.area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)
+            self.front = ~(self.area <= f32(0.0))
+
+
+class HoverMirror:
+    """find_hovered_element (modeler/viewport.rs:2379-2601) for one mesh in numpy float32: what b32_hover_mesh computes, and what a host
+    without this library walks per mouse move.  The constructor does what the reference does once per mesh and frame (project every
+    vertex, the front pass of viewport.rs:2435-2473); hover() answers one cursor with vectorised f32 operations, each separately rounded in
+    the reference's order.  placement None: the vertices as they are; else it is always applied (as in PickMirror)."""
+
+    def __init__(self, vertices, topology, placement, camera, w, h, ortho=None):
+        f32 = np.float32
+        self.pos = _positions(vertices)
+        self.top = t = topology
+        nv = self.nv = len(self.pos)
+        with np.errstate(all="ignore"):
+            self.sx, self.sy, self.cz, self.some = _project_f32(*_world_f32(self.pos, placement), camera, w, h, ortho)
+            sx, sy, some = self.sx, self.sy, self.some
+            # the front pass: polygons with n >= 3 whose first three vertices exist and project, signed area > 0.0
+            st = t.poly_start.astype(np.int64)
+            big = np.nonzero(t.count >= 3)[0]
+            pv = t.poly_verts.astype(np.int64)
+            i3 = np.stack([pv[st[big] + k] for k in range(3)], 1) if len(big) else np.zeros((0, 3), np.int64)
+            ok3 = (i3 < nv).all(1)
+            j3 = np.where(ok3[:, None], i3, 0)
+            if nv:
+                ok3 &= some[j3].all(1)
+                x, y = sx[j3], sy[j3]
+                area = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0])
+                ok3 &= area > f32(0.0)
+            else:
+                ok3[:] = False
+        front_poly = np.zeros(t.np, bool)
+        front_poly[big[ok3]] = True
+        on_front = front_poly[t.poly_of]                                        # per position of poly_verts == per half-edge
+        self.vfront = np.zeros(nv, bool)
+        self.vfront[pv[on_front & (pv < nv)]] = True
+        efront = np.zeros(t.ne, bool)
+        efront[t.he_edge[on_front]] = True
+        self.he_front = efront[t.he_edge] if t.ne else np.zeros(0, bool)
+        self.he_in = (t.he_v0 < nv) & (t.he_v1 < nv)
+        self.he_a = np.where(self.he_in, t.he_v0, 0); self.he_b = np.where(self.he_in, t.he_v1, 0)
+        self.faces = _FanMirror(sx, sy, self.cz, some, t.fan)
+
+    def _editable(self, axis, threshold):
+        if not axis:
+            return np.ones(self.nv, bool)
+        with np.errstate(all="ignore"):
+            return self.pos[:, axis - 1] >= -np.float32(threshold)             # state.rs:797-806 (a NaN fails)
+
+    def hover(self, mx, my, see_through=False, mirror_axis=0, mirror_threshold=1.0, vertex_threshold=abi.HOVER_VERTEX_THRESHOLD,
+              edge_threshold=abi.HOVER_EDGE_THRESHOLD):
+        """One abi.HOVER_RESULT_DTYPE record: all three branches, raw (hovered_element() masks them)."""
+        f32 = np.float32
+        px, py = f32(mx), f32(my)
+        t = self.top
+        r = np.zeros((), abi.HOVER_RESULT_DTYPE)
+        r["vertex"] = r["edge_v0"] = r["edge_v1"] = r["face"] = abi.HOVER_NONE
+        edit = self._editable(mirror_axis, mirror_threshold)
+        with np.errstate(all="ignore"):
+            # vertices, viewport.rs:2475-2505
+            ok = self.some & edit
+            if not see_through:
+                ok = ok & self.vfront
+            dx, dy = px - self.sx, py - self.sy
+            dist = np.sqrt(dx * dx + dy * dy)
+            c = np.nonzero(ok & (dist < f32(vertex_threshold)))[0]
+            if len(c):
+                j = c[np.argmin(dist[c])]
+                r["vertex"] = j; r["vertex_dist"] = dist[j]
+            # half-edges, viewport.rs:2507-2542
+            if self.nv and len(self.he_in):
+                a, b = self.he_a, self.he_b
+                ok = self.he_in & edit[a] & edit[b] & self.some[a] & self.some[b]
+                if not see_through:
+                    ok = ok & self.he_front
+                x0, y0, x1, y1 = self.sx[a], self.sy[a], self.sx[b], self.sy[b]
+                ex, ey = x1 - x0, y1 - y0
+                len_sq = ex * ex + ey * ey
+                tt = ((px - x0) * ex + (py - y0) * ey) / len_sq
+                tt = np.where(tt < f32(0.0), f32(0.0), tt)                      # f32::clamp: a NaN and -0.0 stay
+                tt = np.where(tt > f32(1.0), f32(1.0), tt)
+                qx, qy = px - (x0 + tt * ex), py - (y0 + tt * ey)
+                p0x, p0y = px - x0, py - y0
+                dist = np.where(len_sq < f32(0.001), np.sqrt(p0x * p0x + p0y * p0y), np.sqrt(qx * qx + qy * qy)).astype(f32)
+                c = np.nonzero(ok & (dist < f32(edge_threshold)))[0]
+                if len(c):
+                    j = c[np.argmin(dist[c])]
+                    r["edge_v0"] = min(t.he_v0[j], t.he_v1[j]); r["edge_v1"] = max(t.he_v0[j], t.he_v1[j]); r["edge_dist"] = dist[j]
+            # faces, viewport.rs:2544-2594
+            if len(t.fan):
+                pv = t.poly_verts.astype(np.int64)
+                bad = pv >= self.nv
+                bad[~bad] = ~edit[pv[~bad]]
+                bad_poly = np.zeros(t.np, bool)
+                bad_poly[t.poly_of[bad]] = True
+                tri, depth = self.faces.candidates(px, py, not see_through)
+                keep = ~bad_poly[t.fan_poly[tri]]
+                hit, j, d = _closest_in_order(tri[keep], depth[keep])
+                if hit:
+                    r["face"] = t.fan_poly[j]; r["face_depth"] = d
+        return r
+
+
+def hover_mesh(vertices, topology, placement, camera, w, h, mx, my, ortho=None, **params):
+    """Host mirror of b32_hover_mesh (see HoverMirror): one abi.HOVER_RESULT_DTYPE record."""
+    return HoverMirror(vertices, topology, placement, camera, w, h, ortho).hover(mx, my, **params)
+
+
+def hovered_element(result):
+    """find_hovered_element's return tuple (viewport.rs:2596-2600) of a hover result: the vertex; the edge only without a vertex; the face
+    only without either.  (vertex | None, (v0, v1) | None, polygon | None)."""
+    v = int(result["vertex"]); e = (int(result["edge_v0"]), int(result["edge_v1"])); f = int(result["face"])
+    v = None if v == abi.HOVER_NONE else v
+    e = None if v is not None or e[0] == abi.HOVER_NONE else e
+    f = None if v is not None or e is not None or f == abi.HOVER_NONE else f
+    return v, e, f
+
+
+def box_select_mesh(vertices, topology, placement, camera, w, h, rect, mode=abi.BOX_VERTICES, ortho=None):
+    """Host mirror of b32_box_select -- apply_box_selection (modeler/viewport.rs:1624-1779) for one rectangle (x0, y0, x1, y1):
+    (words, n_selected), bit i of word i // 32 set iff element i is selected.  mode BOX_VERTICES: every vertex that projects into the
+    rectangle (inclusive); BOX_POLYGONS: every polygon whose centre (viewport.rs:1749) does."""
+    f32 = np.float32
+    pos = _positions(vertices)
+    x0, y0, x1, y1 = (f32(v) for v in rect)
+    with np.errstate(all="ignore"):
+        wx, wy, wz = _world_f32(pos, placement)
+        some = None
+        if mode == abi.BOX_POLYGONS:
+            t = topology
+            st = t.poly_start.astype(np.int64); pv = t.poly_verts.astype(np.int64)
+            acc = [np.zeros(t.np, f32) for _ in range(3)]
+            cnt = np.zeros(t.np, np.int64)
+            for k in range(int(t.count.max()) if t.np else 0):                  # fold(Vec3::ZERO, acc + p) in order
+                m = np.nonzero(t.count > k)[0]
+                i = pv[st[m] + k]
+                m = m[i < len(pos)]; i = i[i < len(pos)]
+                for a, wc in zip(acc, (wx, wy, wz)):
+                    a[m] = a[m] + wc[i]
+                cnt[m] += 1
+            inv = f32(1.0) / np.maximum(cnt, 1).astype(f32)
+            wx, wy, wz = acc[0] * inv, acc[1] * inv, acc[2] * inv
+            some = cnt > 0
+        sx, sy, _, ok = _project_f32(wx, wy, wz, camera, w, h, ortho)
+        sel = ok & (sx >= x0) & (sx <= x1) & (sy >= y0) & (sy <= y1)
+        if some is not None:
+            sel &= some
+    n = len(sel)
+    bits = np.zeros(((n + 31) // 32) * 32, np.uint8)
+    bits[:n] = sel
+    words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+    return words, int(sel.sum())
+
+
+class HoverResult:
+    """What b32_hover_mesh_async delivers into `buf` (32 bytes) once its ticket is done."""
+
+    def __init__(self, buf, owner=None):
+        self.buf, self._owner = buf, owner
+
+    @property
+    def record(self):
+        return self.buf[:32].view(abi.HOVER_RESULT_DTYPE)[0].copy()
+
+    def close(self):
+        if self._owner is not None:
+            ctx, p = self._owner
+            ctx.host_free(p)
+            self._owner = None
+
+
+class BoxResult:
+    """What b32_box_select_async delivers into `buf` once its ticket is done: n_elements, n_selected and the words."""
+
+    def __init__(self, buf, owner=None):
+        self.buf, self._owner = buf, owner
+
+    @property
+    def n_elements(self):
+        return int(self.buf[:4].view(np.uint32)[0])
+
+    @property
+    def n_selected(self):
+        return int(self.buf[4:8].view(np.uint32)[0])
+
+    @property
+    def words(self):
+        nw = (self.n_elements + 31) // 32
+        return self.buf[abi.BOX_HEADER_BYTES:abi.BOX_HEADER_BYTES + 4 * nw].view(np.uint32).copy()
+
+    close = HoverResult.close
+
+
 def _pack_placement(placement):
     if placement is None or isinstance(placement, abi.B32Placement):
         return placement
@@ -417,6 +713,86 @@ class Context:
             self.host_free(ptr)
         _chk(rc, "b32_pick_meshes_async")
         return int(t.value), PickResult(arr, n, (self, ptr) if own else None)
+
+    # ---- hover and box selection (b32_hover_mesh, b32_box_select): one detached ResidentScene and a Topology
+    def _hover_args(self, scene, topology, camera, mouse, ortho, placement, see_through, mirror_axis, mirror_threshold, vertex_threshold, edge_threshold):
+        prm = np.zeros(1, abi.HOVER_PARAMS_DTYPE)
+        prm["mx"], prm["my"] = mouse
+        prm["vertex_threshold"], prm["edge_threshold"] = vertex_threshold, edge_threshold
+        prm["flags"] = abi.HOVER_SEE_THROUGH if see_through else 0
+        prm["mirror_axis"], prm["mirror_threshold"] = mirror_axis, mirror_threshold
+        return self._mesh_args(scene, topology, camera, ortho, placement) + (prm,)
+
+    def _mesh_args(self, scene, topology, camera, ortho, placement):
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        o = _pack_ortho(ortho)
+        pl = None
+        if placement is not None:
+            c, s, w = _placement_triple(placement)
+            pl = abi.B32Placement(float(c), float(s), (C.c_float * 3)(*[float(x) for x in w]))
+        top = topology.handle(self) if topology is not None else None
+        return (self.h, C.byref(cam), C.byref(o) if o is not None else None, scene._slot, top, C.byref(pl) if pl is not None else None), (cam, o, pl)
+
+    def hover_mesh(self, scene, topology, camera, mouse, ortho=None, placement=None, see_through=False, mirror_axis=0, mirror_threshold=1.0,
+                   vertex_threshold=abi.HOVER_VERTEX_THRESHOLD, edge_threshold=abi.HOVER_EDGE_THRESHOLD):
+        """b32_hover_mesh: one abi.HOVER_RESULT_DTYPE record (all three branches, raw; hovered_element() masks them)."""
+        args, _keep, prm = self._hover_args(scene, topology, camera, mouse, ortho, placement, see_through, mirror_axis, mirror_threshold,
+                                            vertex_threshold, edge_threshold)
+        out = np.zeros(1, abi.HOVER_RESULT_DTYPE)
+        _chk(self.lib.b32_hover_mesh(*args, prm.ctypes.data, out.ctypes.data), "b32_hover_mesh")
+        return out[0]
+
+    def hover_mesh_async(self, scene, topology, camera, mouse, ortho=None, placement=None, out=None, **params):
+        """b32_hover_mesh_async -> (ticket, HoverResult).  out: an (array, pointer) pair from host_alloc of at least 32 bytes; None:
+        page-locked memory of the result's own, released by HoverResult.close()."""
+        p = dict(see_through=False, mirror_axis=0, mirror_threshold=1.0, vertex_threshold=abi.HOVER_VERTEX_THRESHOLD, edge_threshold=abi.HOVER_EDGE_THRESHOLD)
+        p.update(params)
+        args, _keep, prm = self._hover_args(scene, topology, camera, mouse, ortho, placement, **p)
+        own = out is None
+        arr, ptr = self.host_alloc(32) if own else out
+        if len(arr) < 32:
+            raise ValueError("hover_mesh_async: the result buffer is too small")
+        t = C.c_uint64()
+        rc = self.lib.b32_hover_mesh_async(*args, prm.ctypes.data, ptr, C.byref(t))
+        if rc != abi.B32_OK and own:
+            self.host_free(ptr)
+        _chk(rc, "b32_hover_mesh_async")
+        return int(t.value), HoverResult(arr, (self, ptr) if own else None)
+
+    @staticmethod
+    def _box_params(rect, mode):
+        prm = np.zeros(1, abi.BOX_PARAMS_DTYPE)
+        prm["x0"], prm["y0"], prm["x1"], prm["y1"] = rect
+        prm["mode"] = mode
+        return prm
+
+    def box_select(self, scene, topology, camera, rect, mode=abi.BOX_VERTICES, ortho=None, placement=None, n_elements=None):
+        """b32_box_select: (words, n_selected) for the rectangle (x0, y0, x1, y1).  n_elements: the slot's vertex count in mode BOX_VERTICES
+        (default: the uploaded scene's), the topology's polygon count in mode BOX_POLYGONS."""
+        args, _keep = self._mesh_args(scene, topology, camera, ortho, placement)
+        prm = self._box_params(rect, mode)
+        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_vertices) if n_elements is None else n_elements
+        words = np.zeros((n + 31) // 32, np.uint32)
+        cnt = C.c_uint32()
+        _chk(self.lib.b32_box_select(*args, prm.ctypes.data, words.ctypes.data if len(words) else None, C.byref(cnt)), "b32_box_select")
+        return words, int(cnt.value)
+
+    def box_select_async(self, scene, topology, camera, rect, mode=abi.BOX_VERTICES, ortho=None, placement=None, out=None, n_elements=None):
+        """b32_box_select_async -> (ticket, BoxResult); out as for hover_mesh_async, of at least 16 + 4 * ceil(n_elements / 32) bytes."""
+        args, _keep = self._mesh_args(scene, topology, camera, ortho, placement)
+        prm = self._box_params(rect, mode)
+        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_vertices) if n_elements is None else n_elements
+        need = abi.BOX_HEADER_BYTES + 4 * ((n + 31) // 32)
+        own = out is None
+        arr, ptr = self.host_alloc(need) if own else out
+        if len(arr) < need:
+            raise ValueError("box_select_async: the result buffer is too small")
+        t = C.c_uint64()
+        rc = self.lib.b32_box_select_async(*args, prm.ctypes.data, ptr, C.byref(t))
+        if rc != abi.B32_OK and own:
+            self.host_free(ptr)
+        _chk(rc, "b32_box_select_async")
+        return int(t.value), BoxResult(arr, (self, ptr) if own else None)
 
     def finish(self) -> T.RasterTimings:
         """b32_frame_finish of whatever this context has in flight."""
@@ -1033,6 +1409,7 @@ class ResidentScene:
                                                C.cast(arr, C.c_void_p), len(textures))
         _chk(rc, "scene_upload")
         self.n_faces = len(f)
+        self.n_vertices = len(v)
         self._packed = None
         self._slot = None
 

@@ -436,6 +436,80 @@ int b32_pick_meshes_async(b32_ctx* ctx, const B32Camera* camera, const struct B3
                           b32_scene* const* slots, const B32Placement* places /* n entries, required */, uint32_t n,
                           void* out /* 16 + 16 * n bytes */, uint64_t* ticket);
 
+/* ---- hover and box selection: which vertex, else edge, else face of ONE resident mesh lies under the cursor ------------------------------
+ * find_hovered_element (modeler/viewport.rs:2379-2601) and apply_box_selection (modeler/viewport.rs:1624-1779) walk the modeler's n-gons;
+ * to_render_data_textured (modeler/mesh_editor.rs:1623-1653) keeps the vertices 1:1 and fan-triangulates the faces, so a slot's vertex
+ * indices are the modeler's, but its triangles do not give the polygon edges back.  A b32_topology holds the polygons: poly_start[p] ..
+ * poly_start[p + 1] index poly_verts, whose entries index a slot's vertices.  It belongs to no slot (the slot's nv is applied per call) and
+ * nothing about the indices is validated: an index >= nv behaves as mesh.vertices.get(..) == None does in each loop.  Creation derives,
+ * once, the half-edges (v[k], v[(k + 1) % n]) in loop order (Face::edges, mesh_editor.rs:92-95; also for n = 0, 1, 2) with the id of their
+ * normalised edge (min, max), and the fan triangles (v[0], v[k], v[k + 1]) in loop order (Face::triangulate, mesh_editor.rs:99-112; none
+ * for n < 3) with their polygon.  A NULL array with np > 0 (poly_verts only when there are indices to read: polygons that are all
+ * empty may come with NULL), a poly_start that decreases or poly_start[0] != 0 -> B32_E_ARG.
+ *
+ * b32_hover_mesh evaluates ALL THREE branches of find_hovered_element for the cursor (mx, my) and reports each as its own loop finds it;
+ * the reference's answer is vertex, edge only without a vertex, face only without either (the loops do not read one another, so masking
+ * afterwards is the same function).  Positions: place == NULL uses the slot's vertices as they are (the modeler without bones), else the
+ * placement is always applied as in b32_pick_meshes; projection is world_to_screen_with_ortho (math.rs:538-575); the framebuffer size is
+ * the context's, a band is ignored.  Every expression is a separately rounded f32 operation in the reference's order.
+ *   front pass (viewport.rs:2435-2473; not with B32_HOVER_SEE_THROUGH): a polygon with n >= 3 whose first three indices are < nv and
+ *       project, with (sx1-sx0)*(sy2-sy0) - (sx2-sx0)*(sy1-sy0) > 0.0 (a NaN area is not front), marks its vertices < nv and all its
+ *       normalised edges.
+ *   vertices (viewport.rs:2475-2505), in index order: skipped when culling and unmarked; when the mirror is on and not
+ *       local_pos[axis] >= -mirror_threshold (state.rs:797-806; a NaN fails); when it does not project;
+ *       dist = sqrt((mx-sx)*(mx-sx) + (my-sy)*(my-sy)); candidate when dist < vertex_threshold; kept with a strict `<`.
+ *   half-edges (viewport.rs:2507-2542), in loop order: skipped when culling and their normalised edge is unmarked; when an index is >= nv;
+ *       unless both local positions pass the mirror test and both ends project; dist = point_to_line_distance (viewport.rs:2604-2622) in
+ *       the half-edge's OWN orientation (len_sq < 0.001 -> the distance to the first end; t.clamp(0.0, 1.0) keeps a NaN and -0.0);
+ *       candidate when dist < edge_threshold; kept with a strict `<`; reported as the normalised pair.
+ *   faces (viewport.rs:2544-2594), polygons in order: a polygon is skipped whole unless EVERY index is < nv and passes the mirror test;
+ *       its fan triangles go through the body of b32_pick_meshes' loop (culling = not SEE_THROUGH); closest by a strict `<` (the first of
+ *       equal depths; a NaN depth only when it comes first, reported as 0x7FC00000); reported as the POLYGON index.
+ * NULL context, camera, slot, topology or params, a slot that does not hold its scene, a zero-size framebuffer, an unknown flag or
+ * mirror_axis > 3 -> B32_E_ARG; nv == 0 or np == 0 -> "none" in the branches that have nothing to walk.  Like a pick, the work is enqueued
+ * on the context's stream behind the uploads into the slot, touches neither framebuffer nor z-buffer, flushes no clear and settles no
+ * frame; the asynchronous form performs no host synchronisation and delivers 32 bytes through the tickets of b32_fb_download_async.
+ *
+ * b32_box_select is apply_box_selection for one rectangle.  B32_BOX_VERTICES (viewport.rs:1708-1726): bit i is set iff vertex i projects
+ * and sx >= x0 && sx <= x1 && sy >= y0 && sy <= y1 (inclusive; any NaN gives false; no culling, no mirror).  B32_BOX_POLYGONS
+ * (viewport.rs:1743-1766; needs a topology): the centre fold(Vec3::ZERO, acc + p) * (1.0 / count as f32) over the polygon's vertices with
+ * index < nv, in order (a polygon with none is skipped), projected and tested the same way.  The result is {uint32 n_elements; uint32
+ * n_selected; 8 bytes of padding}, then ceil(n_elements / 32) words, bit i of word i / 32: the reference pushes in ascending index
+ * order, so the bitmap is the selection ("add to selection" stays with the caller).  The blocking form copies the words into `words`
+ * (nullable); the asynchronous form delivers 16 + 4 * ceil(n_elements / 32) bytes by ticket.  mode > 1, B32_BOX_POLYGONS without a
+ * topology, and what b32_hover_mesh rejects -> B32_E_ARG. */
+typedef struct b32_topology b32_topology;
+int  b32_topology_create(b32_ctx* ctx, const uint32_t* poly_start /* np + 1, non-decreasing, [0] == 0 */, uint32_t np,
+                         const uint32_t* poly_verts /* poly_start[np] indices into a slot's vertices; may be NULL when that is 0 */, b32_topology** out);
+void b32_topology_destroy(b32_ctx* ctx, b32_topology* topology);
+typedef struct B32HoverParams {
+    float mx, my;                             /* cursor, framebuffer coordinates */
+    float vertex_threshold, edge_threshold;   /* the reference's constants: 6.0, 4.0 (viewport.rs:2428-2429) */
+    uint32_t flags;                           /* B32_HOVER_SEE_THROUGH: xray_mode || double_sided */
+    uint32_t mirror_axis;                     /* 0 off, 1 X, 2 Y, 3 Z (MirrorSettings, modeler/state.rs:777-806) */
+    float mirror_threshold; uint32_t _pad;
+} B32HoverParams;                             /* 32 bytes */
+typedef struct B32HoverResult {
+    uint32_t vertex; float vertex_dist;       /* none: 0xFFFFFFFF, 0 */
+    uint32_t edge_v0, edge_v1; float edge_dist;   /* normalised (min, max) of the winning half-edge; none: both 0xFFFFFFFF, 0 */
+    uint32_t face; float face_depth;          /* POLYGON index; none: 0xFFFFFFFF, 0; a NaN depth is reported as 0x7FC00000 */
+    uint32_t _pad;
+} B32HoverResult;                             /* 32 bytes */
+#define B32_HOVER_SEE_THROUGH 1u
+int b32_hover_mesh(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, b32_scene* slot, b32_topology* topology,
+                   const B32Placement* place /* nullable */, const B32HoverParams* params, B32HoverResult* out);
+int b32_hover_mesh_async(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, b32_scene* slot, b32_topology* topology,
+                         const B32Placement* place /* nullable */, const B32HoverParams* params, void* out /* 32 bytes */, uint64_t* ticket);
+typedef struct B32BoxParams { float x0, y0, x1, y1; uint32_t mode; uint32_t _pad[3]; } B32BoxParams;   /* 32 bytes */
+#define B32_BOX_VERTICES 0u
+#define B32_BOX_POLYGONS 1u
+int b32_box_select(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, b32_scene* slot,
+                   b32_topology* topology /* nullable for B32_BOX_VERTICES */, const B32Placement* place /* nullable */, const B32BoxParams* params,
+                   uint32_t* words /* ceil(n_elements / 32), nullable */, uint32_t* n_selected);
+int b32_box_select_async(b32_ctx* ctx, const B32Camera* camera, const struct B32Ortho* ortho /* nullable */, b32_scene* slot,
+                         b32_topology* topology /* nullable for B32_BOX_VERTICES */, const B32Placement* place /* nullable */,
+                         const B32BoxParams* params, void* out /* 16 + 4 * ceil(n_elements / 32) bytes */, uint64_t* ticket);
+
 /* ---- the 8-bit-colour path: render_mesh (render.rs:1971-2264) + rasterize_triangle (render.rs:1202-1433) ----
  * What every caller of the reference runs when settings.use_rgb555 is false (scene.rs:163-169).  Same pipeline and settings
  * as render_mesh_15 except: Texture texels are Color values with a per-texel blend mode, no fog, no opaque/transparent
@@ -606,7 +680,8 @@ int b32_device_constants(b32_ctx* ctx, const char** names, uint32_t* bits, uint8
 /* Per-kernel device time of the last finished frame (HIP events on the ctx stream), for bench.py.
  * names[i] points at static strings; returns the number of entries written (<= cap).  While profiling is on (b32_set_profiling >= 1) the
  * projection kernel of the last b32_draw_world is timed too and reported as a further entry "world_project" (the call waits for it), and so
- * are the two kernels of the last b32_pick_meshes[_async], as "pick"; b32_set_profiling(ctx, 0) ends that. */
+ * are the two kernels of the last b32_pick_meshes[_async], as "pick", and the kernels of the last b32_hover_mesh[_async], as "hover";
+ * b32_set_profiling(ctx, 0) ends that. */
 int b32_last_kernel_times(b32_ctx* ctx, const char** names, float* ms, uint32_t cap);
 /* HIP-event instrumentation of the frames enqueued from now on: 0 = none (default for the async path),
  * 1 = events around the coverage kernel (the dominant one), 2 = events around every phase
