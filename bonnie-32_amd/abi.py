@@ -57,6 +57,16 @@ WORLD_ITEM_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("size", "<i4")
 assert WORLD_ITEM_DTYPE.itemsize == 40
 WORLD_CLIP_NEAR = 1
 
+# B32GizmoItem (the world editor's clipped lines and filled gizmos, b32_draw_gizmos): kind = GIZMO_*
+GIZMO_ITEM_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("size", "<i4"), ("r", "u1"), ("g", "u1"), ("b", "u1"),
+                             ("blend", "u1"), ("kind", "u1"), ("_pad", "u1", 3)])
+assert GIZMO_ITEM_DTYPE.itemsize == 48
+GIZMO_LINE, GIZMO_LINE_DEPTH, GIZMO_THICK_LINE_DEPTH, GIZMO_POINT, GIZMO_TRIANGLE, GIZMO_TRIANGLE_VIEW = range(6)
+GIZMO_MAX_THICKNESS = 16
+# the record kind of a filled triangle in the stage tap's output (library-internal: no drawing entry accepts it from the host);
+# the third point's x and y are the bit patterns of z0 and z1
+PRIM_TRIANGLE_INTERNAL = 11
+
 # B32PickHit (b32_pick_meshes): hit == 0 -> tri = 0xFFFFFFFF, depth = 0
 PICK_HIT_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("depth", "<f4"), ("_pad", "<u4")])
 assert PICK_HIT_DTYPE.itemsize == 16
@@ -195,6 +205,10 @@ SYMBOLS = [
     ("b32_floor_grid_items", C.c_int, [C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_world_project_batch", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     ("b32_world_counts", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("b32_draw_gizmos", C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    ("b32_gizmo_project_batch", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_gizmo_counts", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("b32_octahedron_items", C.c_int, [_P, C.c_float, _P, _P]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

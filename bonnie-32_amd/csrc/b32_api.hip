@@ -60,8 +60,9 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : { c->ev_main, c->ev_wbin }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    c->lines.release(); c->prims.release(); c->world.release();
+    c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release();
     if (c->world_counts) (void)hipFree(c->world_counts);
+    if (c->gizmo_counts) (void)hipFree(c->gizmo_counts);
     for (hipEvent_t e : c->world_ev) if (e) (void)hipEventDestroy(e);
     c->pick_tab.release();
     if (c->pick_words) (void)hipFree(c->pick_words);
@@ -291,7 +292,8 @@ static DrawArgs<Rec> draw_args(b32_ctx* c, uint32_t n) {
 // Bin and draw records that are already on the device (a.recs, behind whatever wrote them on the stream): the tile route if `tiles` and
 // `route` is not switched off, else every tile scans the whole batch.  *tiled (nullable): which of the two it was.
 template <class Rec>
-static int draw_resident(b32_ctx* c, DrawPassState<Rec>& ps, DrawArgs<Rec>& a, bool tiles, uint32_t route, bool* tiled = nullptr) {
+static int draw_resident(b32_ctx* c, DrawPassState<Rec>& ps, DrawArgs<Rec>& a, bool tiles, uint32_t route, bool* tiled = nullptr,
+                         void (*launch)(hipStream_t, const DrawArgs<Rec>&, const Rec*) = nullptr) {
     const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
     const bool binned = tiles && !(c->route_off & route);
     if (tiled) *tiled = binned;
@@ -312,7 +314,8 @@ static int draw_resident(b32_ctx* c, DrawPassState<Rec>& ps, DrawArgs<Rec>& a, b
     } else {
         ++ps.scan_batches;
     }
-    launch_draw(c->stream, a, nullptr);
+    if (launch) launch(c->stream, a, nullptr);                             // (the pass's kernels for other record kinds: GizmoPass)
+    else launch_draw(c->stream, a, nullptr);
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
@@ -359,6 +362,33 @@ static int world_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, u
     wa.half_w = (float)w / 2.0f; wa.half_h = (float)h / 2.0f;
     if (ortho) { wa.has_ortho = 1u; wa.zoom = ortho->zoom; wa.center_x = ortho->center_x; wa.center_y = ortho->center_y; }
     return B32_OK;
+}
+
+// ------------------------------------------------------------------ the editor's overlay helpers (b32_gizmo.hip)
+// The whole batch, before anything is enqueued; rows (nullable): the items with the index of their first record.  *n_records: how many
+// records the batch becomes.
+static int gizmo_check(const B32GizmoItem* items, uint32_t n, GizmoRow* rows, uint64_t* n_records) {
+    uint64_t first = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const B32GizmoItem& it = items[i];
+        if (it.kind > B32_GIZMO_TRIANGLE_VIEW || it._pad[0] || it._pad[1] || it._pad[2] ||
+            (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > B32_GIZMO_MAX_THICKNESS)) return B32_E_ARG;
+        if (it.kind == B32_GIZMO_POINT && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;    // r * r (render.rs:632)
+        if (rows) { rows[i].it = it; rows[i].first = (uint32_t)first; }
+        first += (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > 1) ? (uint32_t)it.size : 1u;
+    }
+    *n_records = first;
+    return B32_OK;
+}
+static int gizmo_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, GizmoArgs& ga) {
+    if (!c->gizmo_counts) {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->gizmo_counts), 3 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->gizmo_counts, 0, 3 * sizeof(unsigned long long), c->stream));
+    }
+    ga = GizmoArgs{};
+    const int rc = world_args(c, cam, ortho, w, h, n, ga.w);
+    ga.w.counts = c->gizmo_counts;
+    return rc;
 }
 
 extern "C" {
@@ -458,6 +488,67 @@ int b32_world_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* r
     (void)hipSetDevice(c->device);
     unsigned long long h[3] = { 0, 0, 0 };
     if (c->world_counts) HIPCHK(c, hipMemcpyAsync(h, c->world_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
+    return B32_OK;
+}
+// The editor's overlay helpers (viewport_3d.rs:5687-6357): projected by k_gizmo_project into the primitive pass's device record buffer, then
+// binned and drawn from there by the pass's GizmoPass kernels.  The records never visit the host.
+int b32_draw_gizmos(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32GizmoItem* items, uint32_t n) {
+    if (!c || !c->fb || !cam || (n && !items)) return B32_E_ARG;
+    uint64_t n_rec = 0;
+    GizmoRow small[GIZMO_SMALL];
+    GizmoRow* rows = small;
+    if (n > GIZMO_SMALL) { c->gizmo_rows.resize(n); rows = c->gizmo_rows.data(); }
+    { const int rc = gizmo_check(items, n, rows, &n_rec); if (rc) return rc; }
+    if (!n) return B32_OK;
+    if (n_rec > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+    { const int rc = draw_enter(c); if (rc) return rc; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    GizmoArgs ga;
+    int rc;
+    if ((rc = gizmo_args(c, cam, ortho, c->width, c->height, n, ga))) return rc;
+    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)n_rec))) return rc;
+    ga.w.out = c->prims.dev;
+    if (n > GIZMO_SMALL) {
+        if ((rc = stage_records(c, c->gizmo, rows, n))) return rc;
+        ga.rows = c->gizmo.dev;
+    }
+    launch_gizmo_project(c->stream, ga, n > GIZMO_SMALL ? nullptr : rows);
+    HIPCHK(c, hipGetLastError());
+    DrawArgs<B32Prim> a = draw_args<B32Prim>(c, (uint32_t)n_rec);
+    a.recs = c->prims.dev;
+    return draw_resident(c, c->prims, a, n_rec > PRIM_SMALL, B32_ROUTE_PRIM_TILES, nullptr, launch_draw_gizmo);
+}
+int b32_gizmo_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32GizmoItem* items, uint32_t n,
+                            uint32_t w, uint32_t h, B32Prim* out, uint32_t cap, uint32_t* n_records) {
+    if (!c || !cam || !n_records || (n && !items) || w == 0 || h == 0 || w > 16384 || h > 16384) return B32_E_ARG;
+    std::vector<GizmoRow> rows(n);
+    uint64_t n_rec = 0;
+    { const int rc = gizmo_check(items, n, rows.data(), &n_rec); if (rc) return rc; }
+    if (n_rec > cap || (n_rec && !out)) return B32_E_ARG;
+    *n_records = (uint32_t)n_rec;
+    if (!n) return B32_OK;
+    (void)hipSetDevice(c->device);
+    GizmoArgs ga;
+    int rc;
+    if ((rc = gizmo_args(c, cam, ortho, w, h, n, ga))) return rc;
+    GizmoRow* d_rows = nullptr; B32Prim* d_out = nullptr;
+    Scratch tmp(c);
+    if ((rc = tmp.upload(rows.data(), (size_t)n, &d_rows))) return rc;
+    if ((rc = tmp.alloc(&d_out, (size_t)n_rec))) return rc;
+    ga.rows = d_rows; ga.w.out = d_out;
+    launch_gizmo_project(c->stream, ga, nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_rec * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
+}
+int b32_gizmo_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected) {
+    if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    unsigned long long h[3] = { 0, 0, 0 };
+    if (c->gizmo_counts) HIPCHK(c, hipMemcpyAsync(h, c->gizmo_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
     return B32_OK;

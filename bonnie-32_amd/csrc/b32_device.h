@@ -517,6 +517,14 @@ struct WorldArgs {
     float zoom, center_x, center_y; uint32_t has_ortho;
 };
 void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);
+// The world editor's overlay helpers projected into B32Prim records on the device (b32_draw_gizmos, b32_gizmo.hip): one lane per row, the
+// item's records at out[first ...] (`first`: the records of the rows before it, added up by the host).  w.items is unused, w.n the rows,
+// w.counts the gizmo entry's own drawn / dropped / rejected.  The records go through the pass's GizmoPass kernels (b32_prims.hip).
+constexpr uint32_t GIZMO_SMALL = 48;           // batches of at most this many items travel in the kernel argument (2496 bytes)
+struct GizmoRow { B32GizmoItem it; uint32_t first; };
+struct GizmoArgs { WorldArgs w; const GizmoRow* rows; };   // rows == nullptr: the batch is the kernel argument
+void launch_gizmo_project(hipStream_t s, const GizmoArgs& a, const GizmoRow* small);   // small != nullptr: n <= GIZMO_SMALL rows passed by value
+void launch_draw_gizmo(hipStream_t s, const DrawArgs<B32Prim>& a, const B32Prim* unused);
 // One row of a pick's table (b32_pick.hip): an item's mesh on the device, its placement and the first of its workgroups.
 struct PickItem {
     const B32Vertex* verts; const float* pos12;  // pos12 != nullptr: the slot's packed positions (12 B per vertex) instead of the 36-B vertices

@@ -197,6 +197,9 @@ struct b32_ctx {
     unsigned long long* world_counts = nullptr;
     unsigned long long world_tile_batches = 0, world_scan_batches = 0;
     hipEvent_t world_ev[2] = {}; bool world_timed = false;
+    // b32_draw_gizmos: the rows' pinned ring and device copy (as `world`), the rows of the batch being validated, the entry's own counts
+    DrawPassState<GizmoRow> gizmo; std::vector<GizmoRow> gizmo_rows;
+    unsigned long long* gizmo_counts = nullptr;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl h_ctrl{}; Stamps h_stamps{};          // host copies of the frame set's control block (FrameSet::d_ctrl: Ctrl followed by Stamps)

@@ -15,6 +15,7 @@
 // Binning and the scan's tile test use a conservative box per kind (PrimPass::bounds); the exact box decides only the pixels.
 #include "b32_draw_pass.h"
 #include "b32_fill_common.h"
+#include "b32_gizmo_body.h"
 
 namespace b32 {
 
@@ -141,6 +142,87 @@ __global__ __launch_bounds__(DRAW_THREADS) __attribute__((amdgpu_waves_per_eu(4)
 
 void launch_draw(hipStream_t s, const DrawArgs<B32Prim>& a, const B32Prim* small) {
     draw_launch(s, a, small, k_prims_bin, k_prims_tile<true>, k_prims_tile<false>);
+}
+
+// ---------------------------------------------------------------- the records of b32_draw_gizmos (b32_gizmo.hip)
+// The same pass over the four record kinds k_gizmo_project writes -- B32_LINE_2D, B32_LINE_3D_OVERLAY (walked), B32_PRIM_CIRCLE and the
+// library-internal filled triangle (areas) -- as kernels of its own: k_prims_tile sits right under its register bound and does not learn
+// the triangle.  A triangle's row span depends on y alone (draw_filled_triangle_3d, viewport_3d.rs:6314-6345), so it is an area kind:
+// every lane computes the span of each of its four rows (a wave's lanes share the row) and tests its column.  An area entry is the six
+// sorted integers of a triangle or a circle's centre and r * r: 44 bytes against PrimArea's 84, which a triangle would not fit anyway.
+struct GizmoArea { int bx0, bx1, by0, by1; int v[6]; uint32_t kind; };
+
+struct GizmoPass : PrimPass {
+    struct Areas { GizmoArea ca[DRAW_CHUNK]; uint32_t careas; };
+    // The box of a triangle for binning and the scan's tile test: min and max of its three points, padded where f32 cannot hold the
+    // coordinates -- ax = x0 as f32 + (x2 - x0) as f32 * alpha rounds three times, each by at most half an ulp of a magnitude below 2^31
+    // (64), so beyond 2^24 a span can leave the integer box by up to 192 columns: the margin is ((largest |x|) >> 22) + 2.  Rows are exact.
+    __device__ static __forceinline__ bool bounds(const B32Prim& p, long long& x0, long long& x1, long long& y0, long long& y1) {
+        if (p.kind != PRIM_TRIANGLE) return PrimPass::bounds(p, x0, x1, y0, y1);
+        const int x2 = gizmo_f32_bits(p.z0), y2 = gizmo_f32_bits(p.z1);
+        x0 = min(min(p.x0, p.x1), x2); x1 = max(max(p.x0, p.x1), x2); y0 = min(min(p.y0, p.y1), y2); y1 = max(max(p.y0, p.y1), y2);
+        const long long pad = (max(llabs(x0), llabs(x1)) >> 22) + 2;
+        x0 -= pad; x1 += pad;
+        return true;
+    }
+    template <class S>
+    __device__ static __forceinline__ bool entry(const B32Prim& p, uint32_t i, const DrawTile& t, S& sh) {
+        if (p.kind <= B32_LINE_3D_ALPHA) {
+            draw_line_entry(p, sh.ce[i], sh.cop[i], sh.ccol[i]);
+            return false;
+        }
+        GizmoArea A{};
+        A.kind = p.kind;
+        uint32_t abyte = p.blend != B32_BLEND_ERASE ? 255u : 0u;                      // Color::to_bytes, types.rs:829-832
+        if (p.kind == PRIM_TRIANGLE) {                                                  // viewport_3d.rs:6302-6314
+            int x[3] = { p.x0, p.x1, gizmo_f32_bits(p.z0) }, y[3] = { p.y0, p.y1, gizmo_f32_bits(p.z1) };
+            gizmo_tri_sort(x, y);
+            A.v[0] = x[0]; A.v[1] = y[0]; A.v[2] = x[1]; A.v[3] = y[1]; A.v[4] = x[2]; A.v[5] = y[2];
+            A.bx0 = t.cx0; A.bx1 = t.cx1; A.by0 = max(y[0], t.cy0); A.by1 = min(y[2], t.cy1);
+            if (y[2] == y[0]) { A.bx0 = 1; A.bx1 = 0; }
+            abyte = 255u;                                                               // pixels[idx + 3] = 255, :6353
+        } else {                                                                        // B32_PRIM_CIRCLE, render.rs:631-642
+            A.bx0 = max(p.x0 - p.size, t.cx0); A.bx1 = min(p.x0 + p.size, t.cx1); A.by0 = max(p.y0 - p.size, t.cy0); A.by1 = min(p.y0 + p.size, t.cy1);
+            A.v[0] = p.x0; A.v[1] = p.y0; A.v[2] = p.size * p.size;
+        }
+        sh.ca[i] = A;
+        sh.cop[i] = 0u;
+        sh.ccol[i] = (uint32_t)p.r | ((uint32_t)p.g << 8) | ((uint32_t)p.b << 16) | (abyte << 24);
+        return true;
+    }
+    template <class S>
+    __device__ static __forceinline__ void area_bits(const S& sh, uint32_t areas, int x, int y0, uint32_t* abits) {
+        for (uint32_t am = areas; am; am &= am - 1u) {
+            const uint32_t k = (uint32_t)__builtin_ctz(am);
+            const GizmoArea& A = sh.ca[k];
+            if (x < A.bx0 || x > A.bx1) continue;
+#pragma unroll
+            for (uint32_t r = 0; r < DRAW_ROWS; ++r) {
+                const int y = y0 + 4 * (int)r;
+                if (y < A.by0 || y > A.by1) continue;
+                bool hit;
+                if (A.kind == PRIM_TRIANGLE) {
+                    int xa, xb;                                                        // (x is inside the frame: .max(0) / .min(w - 1) change nothing)
+                    hit = gizmo_tri_row(A.v[0], A.v[1], A.v[2], A.v[3], A.v[4], A.v[5], y, xa, xb) && x >= xa && x <= xb;
+                } else {
+                    const int dx = x - A.v[0], dy = y - A.v[1];
+                    hit = dx * dx + dy * dy <= A.v[2];
+                }
+                if (hit) abits[r] |= 1u << k;
+            }
+        }
+    }
+};
+
+__global__ void k_gizmo_bin(DrawArgs<B32Prim> a) { draw_bin<GizmoPass>(a); }
+__global__ __launch_bounds__(DRAW_THREADS) void k_gizmo_tile(DrawArgs<B32Prim> a, PrimBatch batch) { draw_tile<GizmoPass, false>(a, batch); }
+
+// (the records are always on the device: k_gizmo_project wrote them)
+void launch_draw_gizmo(hipStream_t s, const DrawArgs<B32Prim>& a, const B32Prim*) {
+    const uint32_t ntiles = a.tiles_x * a.tiles_y;
+    if (!a.n || !ntiles) return;
+    if (a.counters) hipLaunchKernelGGL(k_gizmo_bin, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_gizmo_tile, dim3(ntiles), dim3(DRAW_THREADS), 0, s, a, PrimBatch{});
 }
 
 }  // namespace b32

@@ -157,6 +157,18 @@ public:
                                    uint8_t flags = 0) {
         return B32WorldItem{ { p0.x, p0.y, p0.z }, { p1.x, p1.y, p1.z }, size, c.r, c.g, c.b, (uint8_t)c.blend, kind, alpha, (uint8_t)mode, flags, { 0, 0, 0, 0 } };
     }
+    // the world editor's overlay helpers, editor/viewport_3d.rs:5687-6357: projected on the device (enqueued; several at once: draw_gizmos /
+    // GizmoBatch, in array order).  ortho is read by B32_GIZMO_TRIANGLE_VIEW only.
+    void draw_gizmos(const std::vector<B32GizmoItem>& items, const Camera& cam, const std::optional<Vec3>& ortho = std::nullopt) {
+        const B32Camera c = camera_of(cam);
+        const B32Ortho o = ortho ? B32Ortho{ ortho->x, ortho->y, ortho->z } : B32Ortho{ 0, 0, 0 };
+        check(b32_draw_gizmos(ctx_, &c, ortho ? &o : nullptr, items.data(), (uint32_t)items.size()), "draw_gizmos");
+    }
+    WorldCounts gizmo_counts() const { WorldCounts w; check(b32_gizmo_counts(ctx_, &w.drawn, &w.dropped, &w.rejected), "gizmo_counts"); return w; }
+    // one B32GizmoItem (kinds B32_GIZMO_*)
+    static B32GizmoItem gizmo_item(uint8_t kind, Vec3 p0, Vec3 p1, Vec3 p2, Color c, int32_t size = 0) {
+        return B32GizmoItem{ { p0.x, p0.y, p0.z }, { p1.x, p1.y, p1.z }, { p2.x, p2.y, p2.z }, size, c.r, c.g, c.b, (uint8_t)c.blend, kind, { 0, 0, 0 } };
+    }
     b32_ctx* ctx() const { return ctx_; }
 private:
     static B32Camera camera_of(const Camera& c) {
@@ -223,6 +235,36 @@ private:
     Framebuffer& fb_;
     std::vector<B32WorldItem> items_;
 };
+
+// The editor's overlay helpers recorded in call order; flush(camera, ortho) projects and draws them with ONE b32_draw_gizmos call.
+class GizmoBatch {
+public:
+    explicit GizmoBatch(Framebuffer& fb) : fb_(fb) {}
+    void line(Vec3 p0, Vec3 p1, Color c) { add(B32_GIZMO_LINE, p0, p1, Vec3{ 0, 0, 0 }, c); }                                        // draw_3d_line
+    void line_depth(Vec3 p0, Vec3 p1, Color c) { add(B32_GIZMO_LINE_DEPTH, p0, p1, Vec3{ 0, 0, 0 }, c); }                            // draw_3d_line_depth
+    void thick_line_depth(Vec3 p0, Vec3 p1, Color c, int32_t thickness) { add(B32_GIZMO_THICK_LINE_DEPTH, p0, p1, Vec3{ 0, 0, 0 }, c, thickness); }
+    void point(Vec3 p, int32_t radius, Color c) { add(B32_GIZMO_POINT, p, Vec3{ 0, 0, 0 }, Vec3{ 0, 0, 0 }, c, radius); }           // draw_3d_point
+    void triangle(Vec3 p0, Vec3 p1, Vec3 p2, Color c) { add(B32_GIZMO_TRIANGLE, p0, p1, p2, c); }                                    // the editor's project_vertex + fill
+    void triangle_view(Vec3 p0, Vec3 p1, Vec3 p2, Color c) { add(B32_GIZMO_TRIANGLE_VIEW, p0, p1, p2, c); }                          // the modeler's
+    void octahedron(Vec3 center, float size, Color c) {                                                                              // draw_filled_octahedron
+        const float ctr[3] = { center.x, center.y, center.z };
+        const uint8_t rgbb[4] = { c.r, c.g, c.b, (uint8_t)c.blend };
+        B32GizmoItem out[20];
+        check(b32_octahedron_items(ctr, size, rgbb, out), "octahedron_items");
+        items_.insert(items_.end(), out, out + 20);
+    }
+    size_t size() const { return items_.size(); }
+    const std::vector<B32GizmoItem>& items() const { return items_; }
+    void flush(const Camera& cam, const std::optional<Vec3>& ortho = std::nullopt) { fb_.draw_gizmos(items_, cam, ortho); items_.clear(); }
+private:
+    template <typename... A>
+    void add(uint8_t kind, A... args) { items_.push_back(Framebuffer::gizmo_item(kind, args...)); }
+    Framebuffer& fb_;
+    std::vector<B32GizmoItem> items_;
+};
+inline void draw_gizmos(Framebuffer& fb, const std::vector<B32GizmoItem>& items, const Camera& cam, const std::optional<Vec3>& ortho = std::nullopt) {
+    fb.draw_gizmos(items, cam, ortho);
+}
 
 namespace detail {
 inline B32Vertex pack(const Vertex& v) {

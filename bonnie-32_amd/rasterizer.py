@@ -823,6 +823,21 @@ class Context:
         """b32_set_pipeline_depth: 2 or 3 frame sets -- the setup kernel one or two frames ahead of the fill (include/b32raster.h)."""
         _chk(self.lib.b32_set_pipeline_depth(self.h, int(sets)), "b32_set_pipeline_depth")
 
+    def gizmo_project_batch(self, items, camera: T.Camera, ortho, width, height):
+        """b32_gizmo_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_gizmos hands to the tile pass for a width x height
+        framebuffer -- one per item, `size` of them for a thick line of thickness > 1 -- in item order; synchronous."""
+        arr = np.ascontiguousarray(items, dtype=abi.GIZMO_ITEM_DTYPE).reshape(-1)
+        # (a thickness beyond the cap is refused before anything is written)
+        cap = int(sum(gizmo_record_count(int(k), min(int(s), abi.GIZMO_MAX_THICKNESS)) for k, s in zip(arr["kind"], arr["size"])))
+        out = np.zeros(cap, abi.PRIM_DTYPE)
+        cam = camera.pack()
+        o = _pack_ortho(ortho)
+        n = C.c_uint32()
+        _chk(self.lib.b32_gizmo_project_batch(self.h, C.byref(cam), C.byref(o) if o is not None else None, arr.ctypes.data if len(arr) else None,
+                                              len(arr), int(width), int(height), out.ctypes.data if cap else None, cap, C.byref(n)),
+             "gizmo_project_batch")
+        return out[:int(n.value)]
+
     def set_routes(self, off_mask):
         """b32_set_routes: switch internal routes off (ROUTE_* bits); results are identical on every route."""
         _chk(self.lib.b32_set_routes(self.h, int(off_mask)), "b32_set_routes")
@@ -1123,6 +1138,26 @@ class Framebuffer:
                                                   out.ctypes.data if len(arr) else None), "world_project_batch")
         return out
 
+    # ---- the world editor's clipped lines and filled gizmos (editor/viewport_3d.rs:5687-6357): projected on the device, b32_draw_gizmos
+    def draw_gizmos(self, items, camera: T.Camera, ortho=None):
+        """b32_draw_gizmos: every item of `items` (abi.GIZMO_ITEM_DTYPE) drawn as the editor's helper calls in array order; enqueued, no
+        host synchronisation.  ortho: None or (zoom, center_x, center_y), read by GIZMO_TRIANGLE_VIEW only."""
+        arr = np.ascontiguousarray(items, dtype=abi.GIZMO_ITEM_DTYPE).reshape(-1)
+        cam = camera.pack()
+        o = _pack_ortho(ortho)
+        _chk(self.ctx.lib.b32_draw_gizmos(self.ctx.h, C.byref(cam), C.byref(o) if o is not None else None,
+                                          arr.ctypes.data if len(arr) else None, len(arr)), "draw_gizmos")
+
+    def gizmo_batch(self):
+        """A GizmoBatch on this framebuffer: the editor's helper calls recorded; flush(camera, ortho) draws them with one b32_draw_gizmos call."""
+        return GizmoBatch(self)
+
+    def gizmo_counts(self):
+        """b32_gizmo_counts: (drawn, dropped, rejected) gizmo items this context has projected so far; synchronises."""
+        v = [C.c_uint64() for _ in range(3)]
+        _chk(self.ctx.lib.b32_gizmo_counts(self.ctx.h, *[C.byref(x) for x in v]), "gizmo_counts")
+        return tuple(int(x.value) for x in v)
+
     def present_nearest(self, dst_w, dst_h):
         """The presenter's nearest-neighbour upscale (game/renderer.rs:179-214) -> uint8 [dst_h, dst_w, 4]."""
         out = np.empty((dst_h, dst_w, 4), np.uint8)
@@ -1314,6 +1349,86 @@ class WorldBatch:
         """Draws everything recorded (one b32_draw_world call) and starts an empty batch."""
         items, self._items = self.items(), []
         self.fb.draw_world(items, camera, ortho)
+
+
+def gizmo_record_count(kind, size):
+    """Records an item becomes in the tile pass: `size` parallel lines for a thick line of thickness > 1, else one."""
+    return size if (kind == abi.GIZMO_THICK_LINE_DEPTH and size > 1) else 1
+
+
+def gizmo_item(kind, p0, p1=(0.0, 0.0, 0.0), p2=(0.0, 0.0, 0.0), color: T.Color = None, size=0):
+    """One abi.GIZMO_ITEM_DTYPE record."""
+    it = np.zeros(1, abi.GIZMO_ITEM_DTYPE)
+    it["p0"], it["p1"], it["p2"], it["size"] = np.asarray(p0, np.float32), np.asarray(p1, np.float32), np.asarray(p2, np.float32), size
+    it["r"], it["g"], it["b"], it["blend"] = color.r, color.g, color.b, color.blend
+    it["kind"] = kind
+    return it
+
+
+def octahedron_items(center, size, color: T.Color):
+    """b32_octahedron_items: the editor's draw_filled_octahedron (viewport_3d.rs:6223-6292) as 20 items in call order -- the eight faces
+    as GIZMO_TRIANGLE, then the twelve edges as GIZMO_LINE in the darker edge colour.  Host only."""
+    out = np.zeros(20, abi.GIZMO_ITEM_DTYPE)
+    ctr = (C.c_float * 3)(*[float(v) for v in center])
+    col = (C.c_uint8 * 4)(color.r, color.g, color.b, color.blend)
+    _chk(abi.load_library().b32_octahedron_items(ctr, float(size), col, out.ctypes.data), "octahedron_items")
+    return out
+
+
+class GizmoBatch:
+    """The world editor's overlay helpers (editor/viewport_3d.rs:5687-6357) recorded in call order; flush(camera, ortho) projects and
+    draws them with ONE b32_draw_gizmos call.  Positions are (x, y, z) in world space."""
+
+    def __init__(self, fb: "Framebuffer" = None):
+        self.fb = fb
+        self._items = []
+
+    def __len__(self):
+        return len(self._items)
+
+    def _add(self, kind, p0, p1, p2, color: T.Color, size=0):
+        self._items.append((tuple(p0), tuple(p1), tuple(p2), size, color.r, color.g, color.b, color.blend, kind, (0, 0, 0)))
+
+    def line(self, p0, p1, color: T.Color):
+        """draw_3d_line (viewport_3d.rs:5687-5695): near clip, world_to_screen, the Cohen-Sutherland clip to the frame, Bresenham"""
+        self._add(abi.GIZMO_LINE, p0, p1, _ZERO3, color)
+
+    def line_depth(self, p0, p1, color: T.Color):
+        """draw_3d_line_depth (:5698-5706)"""
+        self._add(abi.GIZMO_LINE_DEPTH, p0, p1, _ZERO3, color)
+
+    def thick_line_depth(self, p0, p1, color: T.Color, thickness):
+        """draw_3d_thick_line_depth (:5709-5781)"""
+        self._add(abi.GIZMO_THICK_LINE_DEPTH, p0, p1, _ZERO3, color, size=thickness)
+
+    def point(self, p, radius, color: T.Color):
+        """draw_3d_point (:5958-5976)"""
+        self._add(abi.GIZMO_POINT, p, _ZERO3, _ZERO3, color, size=radius)
+
+    def triangle(self, p0, p1, p2, color: T.Color):
+        """the editor's project_vertex three times, then draw_filled_triangle_3d (:6239-6245, :6295-6357)"""
+        self._add(abi.GIZMO_TRIANGLE, p0, p1, p2, color)
+
+    def triangle_view(self, p0, p1, p2, color: T.Color):
+        """the modeler's project_vertex three times (modeler/viewport.rs:4592-4607: takes the flush's ortho), then its fill"""
+        self._add(abi.GIZMO_TRIANGLE_VIEW, p0, p1, p2, color)
+
+    def octahedron(self, center, size, color: T.Color):
+        """draw_filled_octahedron (viewport_3d.rs:6223-6292): eight faces, twelve edges"""
+        for it in octahedron_items(center, size, color):
+            self._items.append(tuple(tuple(v) if isinstance(v, np.ndarray) else v for v in it.tolist()))
+
+    def items(self):
+        """The recorded batch (abi.GIZMO_ITEM_DTYPE, call order)."""
+        return np.array(self._items, abi.GIZMO_ITEM_DTYPE)
+
+    def flush(self, camera: T.Camera, ortho=None):
+        """Draws everything recorded (one b32_draw_gizmos call) and starts an empty batch."""
+        items, self._items = self.items(), []
+        self.fb.draw_gizmos(items, camera, ortho)
+
+
+_ZERO3 = (0.0, 0.0, 0.0)
 
 
 class PrimBatch:

@@ -647,6 +647,74 @@ int b32_world_project_batch(b32_ctx* ctx, const B32Camera* camera, const B32Orth
 /* Items projected by this context so far (b32_draw_world, b32_draw_floor_grid and the stage tap): drawn, dropped (the reference itself
  * draws nothing: behind the camera, None) and rejected (see b32_draw_world).  Synchronises the stream. */
 int b32_world_counts(b32_ctx* ctx, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected);
+/* The world editor's overlay helpers (editor/viewport_3d.rs:5687-6357).  The editor's viewport does not draw its overlay through
+ * rasterizer/draw.rs but through a private family of helpers; three of them draw pixels nothing above can reproduce:
+ *   draw_3d_line (:5687-5695 -> draw_3d_line_impl(use_depth = false), :5783-5882) clips the projected f32 segment to the framebuffer with
+ *     a 16-round Cohen-Sutherland loop (clip_line_to_rect, :5886-5955) BEFORE the `as i32` casts, so a line that crosses the frame edge
+ *     starts its Bresenham error term at the clipped end -- other pixels than draw_3d_line_clipped + fb.draw_line (B32_WORLD_CLIP_NEAR);
+ *   draw_3d_thick_line_depth (:5709-5781) draws `thickness` parallel draw_line_3d_overlay lines whose integer offsets come from f32
+ *     arithmetic on the cast end points;
+ *   draw_filled_triangle_3d (:6295-6357), the body of draw_filled_octahedron (:6223-6292): a scan-line fill with no depth test that writes
+ *     [r, g, b, 255] whatever the colour's blend.  The modeler's twin (modeler/viewport.rs:4663-4722) was read against it line by line: the
+ *     two fill bodies are the same text (only comments differ), so B32_GIZMO_TRIANGLE and B32_GIZMO_TRIANGLE_VIEW differ in the projection
+ *     alone (`cam.z < 0.1` and math.rs project against `cam_z <= 0.1` / the ortho branch of world_to_screen_with_ortho_depth).
+ * An item is one such call.  It is projected ON THE DEVICE, in array order, into records of the ordered tile pass of b32_draw_prims; the
+ * arithmetic is the reference's, operation for operation, as in b32_draw_world (NaN depths are stored as 0x7FC00000 there too):
+ *   B32_GIZMO_LINE: the near-plane clip (:5794-5816, draw.rs:19-42 verbatim), world_to_screen on both ends, then
+ *     clip_line_to_rect(x0f, y0f, x1f, y1f, 0.0, 0.0, w as f32, h as f32) literally (outcodes with `<` / `>=`, the first end preferred,
+ *     BOTTOM, TOP, RIGHT, LEFT, ymax - 1.0 / xmax - 1.0, at most 16 rounds then None, a NaN coordinate has outcode 0), `as i32`, and one
+ *     B32_LINE_2D record (the loop at :5861-5880 is draw_line's; set_pixel honours `blend`).
+ *   B32_GIZMO_LINE_DEPTH: the record b32_draw_world makes for B32_LINE_3D_OVERLAY with B32_WORLD_CLIP_NEAR.
+ *   B32_GIZMO_THICK_LINE_DEPTH: size <= 1 is B32_GIZMO_LINE_DEPTH; else :5750-5780 -- `size` B32_LINE_3D_OVERLAY records
+ *     (x0 + ox, y0 + oy, depth0, x1 + ox, y1 + oy, depth1), i = 0 .. size - 1 in that order; len < 0.001: nothing.
+ *   B32_GIZMO_POINT: world_to_screen, `as i32`, one B32_PRIM_CIRCLE record of radius `size`.
+ *   B32_GIZMO_TRIANGLE / _VIEW: three projections (any None: nothing), then one record of a library-internal kind (11: the third point's
+ *     x and y travel as the bit patterns of z0 and z1; visible through the stage tap only -- b32_draw_prims and b32_draw_world keep
+ *     answering B32_E_ARG for kind 11).  Pixels per :6302-6356: a STABLE sort of the three points by y, y2 == y0 nothing, rows
+ *     y0.max(0) ..= y2.min(h - 1), second_half = y > y1 || y1 == y0, a row whose segment height is 0.0 skipped, columns
+ *     (ax as i32).max(0) ..= (bx as i32).min(w - 1) after the swap, [r, g, b, 255], no depth test, no z write. */
+typedef struct B32GizmoItem {
+    float   p0[3], p1[3], p2[3];    /* world positions; lines use p0, p1; the point uses p0; triangles all three */
+    int32_t size;                   /* THICK_LINE_DEPTH: thickness; POINT: radius; ignored otherwise */
+    uint8_t r, g, b, blend;         /* Color{r, g, b, blend} */
+    uint8_t kind;                   /* B32_GIZMO_* */
+    uint8_t _pad[3];                /* must be 0 */
+} B32GizmoItem;                     /* 48 bytes */
+#define B32_GIZMO_LINE              0u  /* draw_3d_line             viewport_3d.rs:5687-5695, 5783-5882 (use_depth = false) */
+#define B32_GIZMO_LINE_DEPTH        1u  /* draw_3d_line_depth       :5698-5706 (use_depth = true)                           */
+#define B32_GIZMO_THICK_LINE_DEPTH  2u  /* draw_3d_thick_line_depth :5709-5781                                              */
+#define B32_GIZMO_POINT             3u  /* draw_3d_point            :5958-5976                                              */
+#define B32_GIZMO_TRIANGLE          4u  /* project_vertex :6239-6245 three times (cam.z < 0.1 -> None; math.rs project :117-136;
+                                           `as i32`), then draw_filled_triangle_3d :6295-6357                                */
+#define B32_GIZMO_TRIANGLE_VIEW     5u  /* the modeler's: project_vertex modeler/viewport.rs:4592-4607
+                                           (world_to_screen_with_ortho_depth, takes `ortho`), then its fill :4663-4722        */
+#define B32_GIZMO_MAX_THICKNESS    16   /* the reference only ever passes 3 */
+/* Draws items[0..n) as the reference's calls one after another in array order, with b32_draw_world's contract: every pixel and byte
+ * equal, enqueued on the context's stream with no host synchronisation, a deferred clear flushed first, only rows of the band written,
+ * the z-buffer read (f32::MAX while it is not valid) and never written, `items` reusable on return, n == 0 a no-op.  `ortho` is read
+ * by B32_GIZMO_TRIANGLE_VIEW only.
+ * The whole batch is checked before anything is enqueued: an unknown kind, non-zero padding or B32_GIZMO_THICK_LINE_DEPTH with
+ * size > B32_GIZMO_MAX_THICKNESS -> B32_E_ARG; a point with |size| > 32767 -> B32_E_UNSUPPORTED.  What the reference's i32 arithmetic
+ * cannot carry is known only after projection; the item's record(s) become no-ops on the device and the item is counted `rejected`:
+ * a line extent |x1-x0| or |y1-y0| >= 2^30; for kinds 2, 4 and 5 any cast coordinate of magnitude >= 2^30 (x0 + ox, y2 - y0, x2 - x0
+ * overflow); a point whose centre reaches 2^30 (b32_draw_prims's circle rule).  An item for which the reference draws nothing -- both
+ * ends behind the near plane, a None projection, a segment Cohen-Sutherland rejects or fails to converge on, len < 0.001, y2 == y0 -- is
+ * counted `dropped`; every other item `drawn`. */
+int b32_draw_gizmos(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable; read by kind 5 only */,
+                    const B32GizmoItem* items, uint32_t n);
+/* Stage tap: the records b32_draw_gizmos would hand to the tile pass for a width x height framebuffer, in item order (one per item,
+ * `size` for a thick line of thickness > 1; an item that draws nothing: a circle of radius -1), copied back (synchronous).
+ * *n_records = how many there are; more than `cap`: B32_E_ARG and nothing is written. */
+int b32_gizmo_project_batch(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable */, const B32GizmoItem* items,
+                            uint32_t n, uint32_t width, uint32_t height, B32Prim* out, uint32_t cap, uint32_t* n_records);
+/* Gizmo items projected by this context so far (b32_draw_gizmos and the stage tap): drawn, dropped, rejected.  Synchronises the stream. */
+int b32_gizmo_counts(b32_ctx* ctx, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected);
+/* The editor's draw_filled_octahedron (viewport_3d.rs:6223-6292) as 20 items in call order (host only, no context): the six corners
+ * as f32 centre +- size (:6231-6236), the eight faces of :6257-6266 as B32_GIZMO_TRIANGLE, then the twelve edges of :6280-6291 as
+ * B32_GIZMO_LINE in the edge colour (c as u16 * 3 / 4) as u8 (:6275-6279; RasterColor::new: blend Opaque).  The modeler's octahedron
+ * (modeler/viewport.rs:4575-4660) is the same faces as B32_GIZMO_TRIANGLE_VIEW followed by its edges as B32_LINE_3D items of
+ * b32_draw_world. */
+int b32_octahedron_items(const float center[3], float size, const uint8_t rgbb[4], B32GizmoItem out[20]);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
