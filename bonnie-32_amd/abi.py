@@ -85,6 +85,11 @@ HOVER_NONE = 0xFFFFFFFF
 HOVER_VERTEX_THRESHOLD, HOVER_EDGE_THRESHOLD = 6.0, 4.0      # viewport.rs:2428-2429
 BOX_VERTICES, BOX_POLYGONS = 0, 1
 BOX_HEADER_BYTES = 16               # b32_box_select_async's result: {uint32 n_elements; uint32 n_selected; 8 bytes of padding}, then the words
+# B32Bone (b32_scene_pose): get_bone_world_transform(i) with cos / sin taken on the host; rotate == 0: rotate_by_euler's early return
+BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("cos_z", "<f4"), ("sin_z", "<f4"), ("rotate", "<u4")])
+assert BONE_DTYPE.itemsize == 32
+BONE_NONE = 0xFFFF
+MAX_BONES = 64
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -177,6 +182,9 @@ SYMBOLS = [
     ("b32_scene_create", C.c_int, [_P, C.POINTER(_P)]),
     ("b32_scene_destroy", None, [_P, _P]),
     ("b32_scene_swap", C.c_int, [_P, _P]),
+    ("b32_scene_set_rig", C.c_int, [_P, _P, _P]),
+    ("b32_scene_pose", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("b32_scene_read_vertices", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
     ("b32_frame_begin", C.c_int, [_P, _P, _P]),
     ("b32_frame_add_scene", C.c_int, [_P, _P, _P]),
     ("b32_frame_end", C.c_int, [_P]),

@@ -433,6 +433,9 @@ void launch_flag_poll(hipStream_t s, Ctrl* ctrl, uint32_t seq);        // Events
 void launch_flag_wbin(hipStream_t s, Ctrl* ctrl, uint32_t epoch);      // Events::wbin_done = epoch, behind the early k_wire_bin on the side stream
 void launch_join(hipStream_t s, Ctrl* ctrl, uint32_t epoch, uint32_t patience_ticks);
 void launch_pack_streams(hipStream_t s, const B32Vertex* verts, uint32_t nv, float* pos12, float* attr12, bool with_lit);
+// bones (b32_pose.hip): the slot's positions and normals into its rest stream; rest stream + bone table -> the slot's vertices
+void launch_pose_rest(hipStream_t s, const B32Vertex* verts, uint32_t nv, float* rest);
+void launch_pose(hipStream_t s, const float* rest, const uint16_t* bone_of, B32Vertex* verts, uint32_t nv, const B32Bone* bones, uint32_t n_bones);
 void launch_project_fixed(hipStream_t s, const float* pos, uint32_t n, B32Camera cam, uint32_t w, uint32_t h,
                           int32_t* sx, int32_t* sy, float* z);
 void launch_selftest(hipStream_t s, int op, const float* a, const float* b, const float* c, float* out, uint32_t n);

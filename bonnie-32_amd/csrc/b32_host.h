@@ -109,10 +109,13 @@ struct b32_scene {
     float* d_pos12 = nullptr; size_t cap_pos12 = 0; bool pos_valid = false; uint32_t band_frames = 0;
     bool lit_valid = false;             // ... and the 24-byte lit stream behind them (packed on the first frame with a shading pass)
     std::vector<TexSig> tex_sig; bool tex_sig_valid = false;
+    // bones (b32_scene_set_rig): the rest stream (nv positions and normals, 24 B each) k_pose starts from, and a bone index per vertex.
+    // Part of the scene's content: swapped with it, dropped (have_rig = false, the buffers stay for the next rig) by every upload
+    float* d_rest = nullptr; size_t cap_rest = 0; uint16_t* d_bone_of = nullptr; size_t cap_bone_of = 0; bool have_rig = false;
     // The only list of a scene's device buffers (the caller has drained the streams that use them).
     void release() {
         for (void* p : { (void*)d_verts, (void*)d_faces, (void*)d_texels, (void*)d_texels32, (void*)d_tex, (void*)d_consts, (void*)d_texmask,
-                         (void*)d_pos12, (void*)d_atlas0 }) if (p) (void)hipFree(p);
+                         (void*)d_pos12, (void*)d_atlas0, (void*)d_rest, (void*)d_bone_of }) if (p) (void)hipFree(p);
     }
 };
 

@@ -49,6 +49,7 @@ struct HoverArgs {
     uint32_t gv, ge, vwords, ewords;            // workgroups of the vertex and of the half-edge range; words of the two bitmaps
     uint32_t *vbits, *ebits;
     HoverWords* words;
+    const float* rest;                          // a rigged slot's rest stream (24 B per vertex: position, normal), else nullptr
 };
 struct BoxArgs {
     PickArgs p; PickItem it;
@@ -65,11 +66,21 @@ __device__ __forceinline__ bool hover_editable(const HoverArgs& a, const float* 
     const float v = a.mirror_axis == 1u ? local[0] : (a.mirror_axis == 2u ? local[1] : local[2]);
     return v >= -a.mirror_thr;
 }
+// ... of vertex i, whose position in the slot is `local`: find_hovered_element tests the LOCAL position and projects the posed one
+// (viewport.rs:2482-2486), and the local position of a rigged slot is in its rest stream.  RIG is a compile-time switch (a.rest != nullptr):
+// the kernel of a slot without a rig is the text it was before there were rigs.
+template <bool RIG>
+__device__ __forceinline__ bool hover_editable_at(const HoverArgs& a, uint32_t i, const float* local) {
+    if (!RIG) return hover_editable(a, local);
+    if (a.mirror_axis == 0u) return true;
+    return a.rest[(size_t)i * 6 + (a.mirror_axis - 1u)] >= -a.mirror_thr;       // (mirror_axis is 1, 2 or 3: checked by the entry)
+}
 // vertex i (< nv): its mirror test and its projection (world_to_screen_with_ortho, math.rs:538-575)
+template <bool RIG>
 __device__ __forceinline__ bool hover_screen(const HoverArgs& a, uint32_t i, bool mirror, float& sx, float& sy) {
     float local[3], world[3], z;
     pick_vertex(a.it, a.placed != 0u, i, local, world);
-    if (mirror && !hover_editable(a, local)) return false;
+    if (mirror && !hover_editable_at<RIG>(a, i, local)) return false;
     return world_point(a.p.w, world, a.p.w.has_ortho != 0u, sx, sy, z);
 }
 __device__ __forceinline__ bool hover_bit(const uint32_t* bits, uint32_t i) { return ((bits[i >> 5] >> (i & 31u)) & 1u) != 0u; }
@@ -84,7 +95,7 @@ __global__ __launch_bounds__(256) void k_hover_front(HoverArgs a) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const uint32_t i = a.poly_verts[s + k];
-        if (i >= a.it.nv || !hover_screen(a, i, false, sx[k], sy[k])) return;
+        if (i >= a.it.nv || !hover_screen<false>(a, i, false, sx[k], sy[k])) return;
     }
     const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
     if (!(area > 0.0f)) return;
@@ -113,6 +124,7 @@ __device__ __forceinline__ float hover_line_dist(float px, float py, float x0, f
     return hover_dist(px, py, proj_x, proj_y);
 }
 
+template <bool RIG>
 __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
     const uint32_t wg = blockIdx.x;
     const uint32_t range = wg < a.gv ? 0u : (wg < a.gv + a.ge ? 1u : 2u);
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
         if (range == 0u) {                      // viewport.rs:2475-2505
             if (cull && !hover_bit(a.vbits, i)) continue;
             float sx, sy;
-            if (!hover_screen(a, i, true, sx, sy)) continue;
+            if (!hover_screen<RIG>(a, i, true, sx, sy)) continue;
             const float dist = hover_dist(a.p.mx, a.p.my, sx, sy);
             if (dist < a.vthr) m.key = min(m.key, ((unsigned long long)__float_as_uint(dist) << 32) | i);
         } else if (range == 1u) {               // viewport.rs:2507-2542
@@ -138,7 +150,7 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
             float l0[3], l1[3], w0[3], w1[3], z;
             pick_vertex(a.it, a.placed != 0u, h.v0, l0, w0);
             pick_vertex(a.it, a.placed != 0u, h.v1, l1, w1);
-            if (!hover_editable(a, l0) || !hover_editable(a, l1)) continue;
+            if (!hover_editable_at<RIG>(a, h.v0, l0) || !hover_editable_at<RIG>(a, h.v1, l1)) continue;
             const bool ortho = a.p.w.has_ortho != 0u;
             if (!world_point(a.p.w, w0, ortho, x0, y0, z) || !world_point(a.p.w, w1, ortho, x1, y1, z)) continue;
             const float dist = hover_line_dist(a.p.mx, a.p.my, x0, y0, x1, y1);
@@ -153,7 +165,7 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
                 if (a.mirror_axis != 0u) {
                     float local[3], world[3];
                     pick_vertex(a.it, false, vi, local, world);
-                    editable = hover_editable(a, local);
+                    editable = hover_editable_at<RIG>(a, vi, local);
                 }
             }
             float depth;
@@ -343,6 +355,7 @@ int b32_hover_mesh_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
     pick_fill_args(a.p, c, cam, ortho, prm->mx, prm->my, cull);
     hover_item(a.it, slot, place);
     a.placed = place ? 1u : 0u;
+    a.rest = slot->have_rig ? slot->d_rest : nullptr;
     a.he = topo->he; a.fan = topo->fan; a.poly_start = topo->poly_start; a.poly_verts = topo->poly_verts;
     a.np = topo->np; a.nh = topo->nh; a.nt = topo->nt;
     a.mirror_axis = prm->mirror_axis; a.mirror_thr = prm->mirror_threshold; a.vthr = prm->vertex_threshold; a.ethr = prm->edge_threshold;
@@ -380,7 +393,8 @@ int b32_hover_mesh_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
         HIPCHK(c, hipEventRecord(c->hover_tev[0], c->stream));
     }
     if (cull && a.np) hipLaunchKernelGGL(k_hover_front, dim3((a.np + 255u) / 256u), dim3(256), 0, c->stream, a);
-    if (groups) hipLaunchKernelGGL(k_hover, dim3((uint32_t)groups), dim3(256), 0, c->stream, a);
+    if (groups && a.rest) hipLaunchKernelGGL(k_hover<true>, dim3((uint32_t)groups), dim3(256), 0, c->stream, a);
+    else if (groups) hipLaunchKernelGGL(k_hover<false>, dim3((uint32_t)groups), dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(k_hover_resolve, dim3(1), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     if (timed) { HIPCHK(c, hipEventRecord(c->hover_tev[1], c->stream)); c->hover_timed = true; }

@@ -95,6 +95,7 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
     // overflowing frame taught the context stays)
     if (c->scene.nf != nf) { c->scene.direct_cap_opaque = 0; c->scene.direct_ntiles = 0; c->scene.direct_ok = true; }
     c->scene.nv = nv; c->scene.nf = nf;
+    c->scene.have_rig = false;                          // (the rig belongs to the vertices it was set for)
     c->scene.local_sort_ok = true;
     c->scene.pos_valid = false; c->scene.lit_valid = false; c->scene.band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;
@@ -316,6 +317,60 @@ int b32_scene_swap(b32_ctx* c, b32_scene* sl) {
     return B32_OK;
 }
 
+// ------------------------------------------------------------------ bones (b32_pose.hip has the kernels and the why)
+static b32_scene* scene_of(b32_ctx* c, b32_scene* slot) {
+    b32_scene* sc = slot ? slot : &c->scene;
+    return sc->have_scene ? sc : nullptr;
+}
+int b32_scene_set_rig(b32_ctx* c, b32_scene* slot, const uint16_t* bone_of_vertex) {
+    if (!c) return B32_E_ARG;
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc || (sc->nv && !bone_of_vertex)) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc;
+    sc->have_rig = false;
+    if ((rc = ensure(c, sc->d_rest, sc->cap_rest, (size_t)sc->nv * 6 + 1))) return rc;
+    if ((rc = ensure(c, sc->d_bone_of, sc->cap_bone_of, (size_t)sc->nv + 1))) return rc;
+    // (on the stream: behind the upload or the pose that wrote the vertices, in front of the next pose)
+    launch_pose_rest(c->stream, sc->d_verts, sc->nv, sc->d_rest);
+    HIPCHK(c, hipGetLastError());
+    if (sc->nv) HIPCHK(c, hipMemcpyAsync(sc->d_bone_of, bone_of_vertex, (size_t)sc->nv * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // the caller may reuse its array (once per rig, like an upload)
+    sc->have_rig = true;
+    return B32_OK;
+}
+// Order against the side stream (DESIGN.md section 7d has the full argument).  Two kernels read a scene's vertices or what was derived
+// from them there: k_setup of a pipelined frame (the vertices) and the early k_wire_bin (the wire list k_setup wrote, not the vertices).
+// enqueue_frame never returns before the main stream has been made to wait for that k_setup -- by ev_setup, by k_join, or by the fused
+// kernel that polls the hand-over itself -- and launches the wire kernels, which wait for k_wire_bin (ev_wbin or the polled word), on the
+// main stream before it returns.  So everything on the side stream that a pose could overtake is in front of main-stream work enqueued
+// earlier, and the pose, enqueued on the main stream, needs no event of its own.  The other direction is side_dirty: the next pipelined
+// k_setup waits for the main stream as it stands after the pose.
+int b32_scene_pose(b32_ctx* c, b32_scene* slot, const B32Bone* bones, uint32_t n_bones) {
+    if (!c) return B32_E_ARG;
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc || !sc->have_rig || (n_bones && !bones)) return B32_E_ARG;
+    if (n_bones > B32_MAX_BONES) return B32_E_UNSUPPORTED;
+    (void)hipSetDevice(c->device);
+    // a pending frame that may still be redrawn is redrawn from the resident vertices: settle it before they change (b32_scene_upload)
+    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    launch_pose(c->stream, sc->d_rest, sc->d_bone_of, sc->d_verts, sc->nv, bones, n_bones);
+    HIPCHK(c, hipGetLastError());
+    c->side_dirty = true;
+    sc->pos_valid = false; sc->lit_valid = false;       // (frame_positions packs again on the next frame: band_frames stays)
+    sc->gen = ++c->gen_counter;                          // a merged run that holds this scene is rebuilt
+    return B32_OK;
+}
+int b32_scene_read_vertices(b32_ctx* c, b32_scene* slot, uint32_t first, uint32_t count, B32Vertex* out) {
+    if (!c) return B32_E_ARG;
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc || (count && !out) || (unsigned long long)first + count > sc->nv) return B32_E_ARG;
+    if (!count) return B32_OK;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipMemcpyAsync(out, sc->d_verts + first, (size_t)count * sizeof(B32Vertex), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
+}
 
 // RasterTimings of a synchronous call: the per-phase split comes from the device-side phase clock (b32_frame_finish); the wall time of
 // the whole call is reported as draw_ms only for an empty mesh, where no kernel ran.

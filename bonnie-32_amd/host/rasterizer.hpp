@@ -389,6 +389,16 @@ public:
     ResidentMesh(const ResidentMesh&) = delete;
     ResidentMesh& operator=(const ResidentMesh&) = delete;
     b32_scene* slot() const { return slot_; }
+    // Bones (b32_scene_set_rig / b32_scene_pose): the vertices as they are now become the rest pose, bone_of_vertex has one resolved bone
+    // index per vertex (B32_BONE_NONE: none); pose() enqueues one pass from the rest pose with this bone table (empty: the rest vertices
+    // come back); read_vertices() is the blocking read-back of what the slot holds now.  Defined below, behind Bone.
+    void set_rig(const std::vector<uint16_t>& bone_of_vertex) { check(b32_scene_set_rig(ctx_, slot_, bone_of_vertex.data()), "scene_set_rig"); }
+    inline void pose(const std::vector<struct Bone>& bones);
+    std::vector<B32Vertex> read_vertices(uint32_t first, uint32_t count) const {
+        std::vector<B32Vertex> out(count);
+        check(b32_scene_read_vertices(ctx_, slot_, first, count, out.data()), "scene_read_vertices");
+        return out;
+    }
 private:
     b32_ctx* ctx_ = nullptr;
     b32_scene* slot_ = nullptr;
@@ -417,6 +427,54 @@ inline Vertex place_vertex(const Vertex& v, const Placement& p) {
     o.pos = { rx + p.world_pos.x, v.pos.y + p.world_pos.y, rz + p.world_pos.z };
     o.normal = { v.normal.x * p.cos_f - v.normal.z * p.sin_f, v.normal.y, v.normal.x * p.sin_f + v.normal.z * p.cos_f };
     return o;
+}
+// Bone: get_bone_world_transform(i) (modeler/state.rs:2585-2614) as the device takes it.  from_euler takes to_radians as x * (PI / 180),
+// cos / sin on the host, and decides `rotate` as rotate_by_euler's early return does (state.rs:31: both |rot.x| and |rot.z| < 0.001 degrees
+// hand the vector back as it is).
+struct Bone {
+    Vec3 pos; float cos_x = 1.0f, sin_x = 0.0f, cos_z = 1.0f, sin_z = 0.0f; bool rotate = false;
+    static Bone from_euler(Vec3 pos, Vec3 rot_deg) {
+        Bone b; b.pos = pos;
+        if (std::fabs(rot_deg.x) < 0.001f && std::fabs(rot_deg.z) < 0.001f) return b;
+        const float k = 3.14159265358979323846f / 180.0f;
+        const float ax = rot_deg.x * k, az = rot_deg.z * k;
+        b.cos_x = std::cos(ax); b.sin_x = std::sin(ax); b.cos_z = std::cos(az); b.sin_z = std::sin(az); b.rotate = true;
+        return b;
+    }
+    B32Bone pack() const { return B32Bone{ { pos.x, pos.y, pos.z }, cos_x, sin_x, cos_z, sin_z, rotate ? 1u : 0u }; }
+};
+// the host restatement of b32_scene_pose for one vertex (rotate_by_euler(v.pos, bone_rot) + bone_pos, the normal rotated alike):
+// separately rounded f32 operations in the reference's order (compile with -ffp-contract=off where the compiler would fuse).
+// bone == nullptr: bone_transforms.get(idx) == None.
+inline B32Vertex pose_vertex(const B32Vertex& v, const B32Bone* bone) {
+    if (!bone) return v;
+    B32Vertex o = v;
+    if (!bone->rotate) { for (int k = 0; k < 3; ++k) o.pos[k] = v.pos[k] + bone->pos[k]; return o; }
+    const auto turn = [&](const float* a, float* out) {
+        const float y1 = a[1] * bone->cos_x + a[2] * bone->sin_x, z1 = (-a[1]) * bone->sin_x + a[2] * bone->cos_x;
+        const float x2 = a[0] * bone->cos_z + y1 * bone->sin_z, y2 = (-a[0]) * bone->sin_z + y1 * bone->cos_z;
+        out[0] = x2; out[1] = y2; out[2] = z1;
+    };
+    float r[3];
+    turn(v.pos, r);
+    for (int k = 0; k < 3; ++k) o.pos[k] = r[k] + bone->pos[k];
+    turn(v.normal, o.normal);
+    return o;
+}
+inline std::vector<B32Vertex> pose_vertices(const std::vector<B32Vertex>& vertices, const std::vector<uint16_t>& bone_of_vertex, const std::vector<Bone>& bones) {
+    std::vector<B32Bone> tab; tab.reserve(bones.size());
+    for (const auto& b : bones) tab.push_back(b.pack());
+    std::vector<B32Vertex> out; out.reserve(vertices.size());
+    for (size_t i = 0; i < vertices.size(); ++i) {
+        const size_t b = i < bone_of_vertex.size() ? bone_of_vertex[i] : (size_t)B32_BONE_NONE;
+        out.push_back(pose_vertex(vertices[i], b < tab.size() ? &tab[b] : nullptr));
+    }
+    return out;
+}
+inline void ResidentMesh::pose(const std::vector<Bone>& bones) {
+    std::vector<B32Bone> tab; tab.reserve(bones.size());
+    for (const auto& b : bones) tab.push_back(b.pack());
+    check(b32_scene_pose(ctx_, slot_, tab.data(), (uint32_t)tab.size()), "scene_pose");
 }
 struct MeshParams { float ambient; bool backface_cull, backface_wireframe; Fog fog; std::optional<Placement> placement = std::nullopt; };
 

@@ -80,6 +80,134 @@ class Placement:
         return place_vertices(vertices, self.cos_f, self.sin_f, self.world_pos)
 
 
+# ---- bones (b32_scene_set_rig, b32_scene_pose): the modeler's rotate_by_euler(v.pos, bone_rot) + bone_pos
+_RADS_PER_DEG = np.float32(np.pi / 180.0)                  # f32::to_radians: self * (consts::PI / 180.0)
+
+
+class Bone:
+    """get_bone_world_transform(i) (modeler/state.rs:2585-2614) as the device takes it: bone_pos, cos / sin of bone_rot.x and .z in
+    radians, and `rotate` -- False where rotate_by_euler (state.rs:30-54) takes its early return and hands the vector back as it is.
+    Bone.from_euler(pos, rot_deg) takes to_radians as x * f32(pi / 180), cos / sin in f32, and decides `rotate` with the reference's
+    test (|rot.x| < 0.001 && |rot.z| < 0.001, strict, in f32).  Bone(pos, cos_x=..., sin_x=..., cos_z=..., sin_z=...) takes the caller's own
+    libm values (Rust's f32::cos is the target's libm and may differ from numpy's in the last bit), as Placement does."""
+
+    def __init__(self, pos=(0.0, 0.0, 0.0), cos_x=1.0, sin_x=0.0, cos_z=1.0, sin_z=0.0, rotate=True):
+        f32 = np.float32
+        self.pos = tuple(f32(x) for x in pos)
+        self.cos_x, self.sin_x, self.cos_z, self.sin_z = f32(cos_x), f32(sin_x), f32(cos_z), f32(sin_z)
+        self.rotate = bool(rotate)
+
+    @classmethod
+    def from_euler(cls, pos, rot_deg):
+        f32 = np.float32
+        rx, rz = f32(rot_deg[0]), f32(rot_deg[2])
+        if abs(rx) < f32(0.001) and abs(rz) < f32(0.001):
+            return cls(pos, rotate=False)
+        ax, az = rx * _RADS_PER_DEG, rz * _RADS_PER_DEG
+        return cls(pos, cos_x=np.cos(ax), sin_x=np.sin(ax), cos_z=np.cos(az), sin_z=np.sin(az), rotate=True)
+
+    def record(self):
+        r = np.zeros((), abi.BONE_DTYPE)
+        r["pos"] = self.pos
+        r["cos_x"], r["sin_x"], r["cos_z"], r["sin_z"] = self.cos_x, self.sin_x, self.cos_z, self.sin_z
+        r["rotate"] = 1 if self.rotate else 0
+        return r
+
+
+def pack_bones(bones):
+    """A bone table as a contiguous abi.BONE_DTYPE array: from such an array, or from a sequence of Bone."""
+    if isinstance(bones, np.ndarray) and bones.dtype == abi.BONE_DTYPE:
+        return np.ascontiguousarray(bones).reshape(-1)
+    out = np.zeros(len(bones), abi.BONE_DTYPE)
+    for i, b in enumerate(bones):
+        out[i] = b.record()
+    return out
+
+
+def rotate_by_euler(v, rot_deg):
+    """rotate_by_euler (modeler/state.rs:30-54) for one vector in f32: (x, y, z)."""
+    f32 = np.float32
+    b = Bone.from_euler((0.0, 0.0, 0.0), rot_deg)
+    x, y, z = (f32(c) for c in v)
+    if not b.rotate:
+        return x, y, z
+    with np.errstate(all="ignore"):
+        y1 = y * b.cos_x + z * b.sin_x
+        z1 = (-y) * b.sin_x + z * b.cos_x
+        x2 = x * b.cos_z + y1 * b.sin_z
+        y2 = (-x) * b.sin_z + y1 * b.cos_z
+    return x2, y2, z1
+
+
+def bone_world_transforms(local_positions, local_rotations, parents, indices=None):
+    """get_bone_world_transform (modeler/state.rs:2585-2614) for the bones `indices` (default: every bone) of a skeleton given as
+    local positions, local rotations (degrees) and parents (None or a negative number: a root).  Per bone the chain from the root down to
+    it is walked: position += rotate_by_euler(local_position, rotation so far), then rotation += local_rotation, all in f32.  An index
+    past the skeleton gives (0, 0), as in the reference.  Returns (positions, rotations), two (len(indices), 3) f32 arrays; feed row i to
+    Bone.from_euler."""
+    f32 = np.float32
+    lp = np.asarray(local_positions, f32).reshape(-1, 3)
+    lr = np.asarray(local_rotations, f32).reshape(-1, 3)
+    n = len(lp)
+    idxs = range(n) if indices is None else indices
+    pos = np.zeros((len(idxs), 3), f32); rot = np.zeros((len(idxs), 3), f32)
+    with np.errstate(all="ignore"):
+        for row, i in enumerate(idxs):
+            if i < 0 or i >= n:
+                continue
+            chain = []
+            cur = i
+            while cur is not None and cur >= 0:
+                chain.append(cur)
+                if len(chain) > n:
+                    raise ValueError("bone_world_transforms: the parents form a cycle")
+                cur = parents[cur]
+                if cur is not None and cur >= n:
+                    raise IndexError("bone_world_transforms: parent out of range")
+            p = [f32(0.0)] * 3; r = [f32(0.0)] * 3
+            for k in reversed(chain):
+                q = rotate_by_euler(lp[k], r)
+                p = [p[0] + q[0], p[1] + q[1], p[2] + q[2]]
+                r = [r[0] + lr[k][0], r[1] + lr[k][1], r[2] + lr[k][2]]
+            pos[row] = p; rot[row] = r
+    return pos, rot
+
+
+def pose_vertices(vertices, bone_of_vertex, bones):
+    """What b32_scene_pose leaves in a slot, in numpy float32: per vertex rotate_by_euler(pos, bone_rot) + bone_pos and the normal rotated
+    alike (not renormalised), each operation separately rounded in the reference's order (numpy does not fuse).  A bone index past the
+    table (abi.BONE_NONE included) leaves the vertex as it is; a bone with rotate == 0 only translates and leaves the normal's bits.
+    uv and colour are unchanged.  This is what a host without the library does per frame before it uploads."""
+    v = np.array(vertices, dtype=abi.VERTEX_DTYPE, copy=True).reshape(-1)
+    tab = pack_bones(bones)
+    bo = np.asarray(bone_of_vertex).reshape(-1).astype(np.int64)
+    if len(bo) != len(v):
+        raise ValueError("pose_vertices: one bone index per vertex")
+    if not len(tab) or not len(v):
+        return v
+    has = (bo >= 0) & (bo < len(tab))
+    t = tab[np.where(has, bo, 0)]
+    rot = has & (t["rotate"] != 0)
+    tr = has & ~rot
+    cx, sx, cz, sz = t["cos_x"], t["sin_x"], t["cos_z"], t["sin_z"]
+
+    def turned(a):
+        x, y, z = a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy()
+        y1 = y * cx + z * sx
+        z1 = (-y) * sx + z * cx
+        x2 = x * cz + y1 * sz
+        y2 = (-x) * sz + y1 * cz
+        return x2, y2, z1
+
+    with np.errstate(all="ignore"):
+        rp = turned(v["pos"]); rn = turned(v["normal"])
+        for k in range(3):
+            rest = v["pos"][:, k].copy()
+            v["pos"][:, k] = np.where(rot, rp[k] + t["pos"][:, k], np.where(tr, rest + t["pos"][:, k], rest))
+            v["normal"][:, k] = np.where(rot, rn[k], v["normal"][:, k])
+    return v
+
+
 def _placement_triple(placement):
     """(cos_f, sin_f, world_pos) as f32 of a Placement, an abi.B32Placement or such a triple.  Picking always applies the placement
     (viewport_3d.rs:7716-7718 has no has_transform shortcut), so Placement.has_transform is not consulted."""
@@ -317,11 +445,16 @@ class HoverMirror:
     """find_hovered_element (modeler/viewport.rs:2379-2601) for one mesh in numpy float32: what b32_hover_mesh computes, and what a host
     without this library walks per mouse move.  The constructor does what the reference does once per mesh and frame (project every
     vertex, the front pass of viewport.rs:2435-2473); hover() answers one cursor with vectorised f32 operations, each separately rounded in
-    the reference's order.  placement None: the vertices as they are; else it is always applied (as in PickMirror)."""
+    the reference's order.  placement None: the vertices as they are; else it is always applied (as in PickMirror).
+    local_vertices: the rest vertices of a rigged mesh whose posed vertices are `vertices` -- the mirror plane is tested on the LOCAL
+    position (viewport.rs:2482-2486) while the posed one is projected."""
 
-    def __init__(self, vertices, topology, placement, camera, w, h, ortho=None):
+    def __init__(self, vertices, topology, placement, camera, w, h, ortho=None, local_vertices=None):
         f32 = np.float32
         self.pos = _positions(vertices)
+        self.local = self.pos if local_vertices is None else _positions(local_vertices)
+        if len(self.local) != len(self.pos):
+            raise ValueError("HoverMirror: local_vertices must have one entry per vertex")
         self.top = t = topology
         nv = self.nv = len(self.pos)
         with np.errstate(all="ignore"):
@@ -357,7 +490,7 @@ class HoverMirror:
         if not axis:
             return np.ones(self.nv, bool)
         with np.errstate(all="ignore"):
-            return self.pos[:, axis - 1] >= -np.float32(threshold)             # state.rs:797-806 (a NaN fails)
+            return self.local[:, axis - 1] >= -np.float32(threshold)           # state.rs:797-806 (a NaN fails)
 
     def hover(self, mx, my, see_through=False, mirror_axis=0, mirror_threshold=1.0, vertex_threshold=abi.HOVER_VERTEX_THRESHOLD,
               edge_threshold=abi.HOVER_EDGE_THRESHOLD):
@@ -1546,6 +1679,31 @@ class ResidentScene:
         if self._slot is not None:
             self.ctx.lib.b32_scene_destroy(self.ctx.h, self._slot)
             self._slot = None
+
+    def _handle(self):
+        """The slot argument of the bone calls: this scene's slot, or None (the context's resident scene)."""
+        return self._slot
+
+    def set_rig(self, bone_of_vertex):
+        """b32_scene_set_rig: the vertices as they are now become the rest pose; bone_of_vertex has one index per vertex (abi.BONE_NONE:
+        no bone), resolved by the caller (v.bone_index.or(obj.default_bone_index))."""
+        bo = np.ascontiguousarray(bone_of_vertex, np.uint16).reshape(-1)
+        if len(bo) != self.n_vertices:
+            raise ValueError("set_rig: one bone index per vertex")
+        _chk(self.ctx.lib.b32_scene_set_rig(self.ctx.h, self._handle(), abi.ptr(bo) if len(bo) else None), "scene_set_rig")
+
+    def pose(self, bones):
+        """b32_scene_pose: enqueue one pose pass with this bone table (a sequence of Bone or an abi.BONE_DTYPE array; empty: the rest
+        vertices come back)."""
+        tab = pack_bones(bones)
+        _chk(self.ctx.lib.b32_scene_pose(self.ctx.h, self._handle(), abi.ptr(tab) if len(tab) else None, len(tab)), "scene_pose")
+
+    def read_vertices(self, first=0, count=None):
+        """b32_scene_read_vertices (blocking): the slot's vertices as they are on the device now."""
+        count = self.n_vertices - first if count is None else count
+        out = np.zeros(max(count, 0), abi.VERTEX_DTYPE)
+        _chk(self.ctx.lib.b32_scene_read_vertices(self.ctx.h, self._handle(), first, count, abi.ptr(out) if count > 0 else None), "scene_read_vertices")
+        return out
 
     def _pack(self, camera, settings, fog):
         cam = camera.pack()

@@ -59,7 +59,7 @@ extern "C" {
 
 /* ---- POD mirrors of the reference API types ------------------------------ */
 
-/* Vertex, types.rs:947-959 (bone_index is editor-only and dropped). 36 B. */
+/* Vertex, types.rs:947-959.  36 B.  (bone_index is editor-only and not part of the record: b32_scene_set_rig takes it as an array of its own.) */
 typedef struct B32Vertex {
     float   pos[3];
     float   uv[2];
@@ -329,6 +329,60 @@ typedef struct b32_scene b32_scene;
 int b32_scene_create(b32_ctx* ctx, b32_scene** out);
 void b32_scene_destroy(b32_ctx* ctx, b32_scene* slot);
 int b32_scene_swap(b32_ctx* ctx, b32_scene* slot);
+
+/* ---- bones: a rigged resident mesh posed on the device from a per-frame bone table ------------------------------------------------
+ * The modeler skins per vertex on the host, four times per frame -- the draw (modeler/viewport.rs:1196-1240), the box selection
+ * (:1677-1694), the selection brackets (:1796-1810) and the hover (:2401-2421) -- always with
+ *     posed = rotate_by_euler(v.pos, bone_rot) + bone_pos          (modeler/state.rs:30-54)
+ * where (bone_pos, bone_rot) = get_bone_world_transform(v.bone_index.or(obj.default_bone_index)) (state.rs:2585-2614).  Here the mesh stays
+ * resident and is posed ONCE per change of the bone table, into the slot's own vertices: the draw, the wireframe, b32_hover_mesh,
+ * b32_box_select and b32_pick_meshes then read posed vertices like any others, and none of their kernels skins.
+ *
+ * B32Bone is get_bone_world_transform(i) with libm kept on the host (like the camera basis and B32Placement): cos / sin of
+ * bone_rot.x.to_radians() and bone_rot.z.to_radians(), and `rotate` = 0 where rotate_by_euler takes its early return
+ * (|rot.x| < 0.001 && |rot.z| < 0.001, in degrees) -- the reference then returns v as it is, it does not multiply by cos(0).
+ *
+ * b32_scene_set_rig   makes the scene of `slot` (NULL: the context's resident scene) a rigged one.  It copies the scene's CURRENT positions
+ *     and normals, on the device, into a rest stream (24 B per vertex) and uploads bone_of_vertex (nv entries; the caller has resolved
+ *     v.bone_index.or(obj.default_bone_index); B32_BONE_NONE = no bone).  Mirrored vertices are the caller's: the mirror is applied in local
+ *     space before the bone (viewport.rs:1250-1266), so they are static data appended before the upload.  The rig is part of the scene's
+ *     content: it travels with b32_scene_swap, and any b32_scene_upload* into that scene drops it.  A second call replaces the indices and
+ *     takes a NEW rest snapshot of whatever the vertices are at that moment -- after a pose, the posed ones (pose with n_bones = 0 first to
+ *     get the uploaded vertices back).  The caller may reuse bone_of_vertex when the call returns.
+ * b32_scene_pose      enqueues one kernel on the context's stream, one lane per vertex, always from the rest stream (poses never
+ *     accumulate).  With b = bone_of_vertex[i]:
+ *       b >= n_bones (B32_BONE_NONE included; bone_transforms.get(idx) == None): position and normal are the rest bits;
+ *       bones[b].rotate == 0: pos = rest_pos + bone_pos component-wise (a -0.0 becomes +0.0), the normal is the rest bits;
+ *       otherwise, for v = position and, without the translation, for the normal:
+ *           y1 = v.y*cos_x + v.z*sin_x      z1 = (-v.y)*sin_x + v.z*cos_x
+ *           x2 = v.x*cos_z + y1*sin_z       y2 = (-v.x)*sin_z + y1*cos_z
+ *           pos = (x2 + bx, y2 + by, z1 + bz)        normal = (x2, y2, z1)   (not renormalised)
+ *     every operation a separately rounded f32 operation in this order, no fused multiply-add.  uv and colour are untouched; n_bones == 0
+ *     restores the rest vertices bit for bit.  The table is copied by the call (the caller may reuse it at once).  The call performs no
+ *     host synchronisation for small meshes; like b32_scene_upload it first settles a pending frame of a large scene that may still be
+ *     redrawn (from the vertices as they were).  It touches neither framebuffer nor z-buffer and flushes no deferred clear.  What the
+ *     scene's frames taught the context (tile region sizes, sort route) stays, as for placements; the packed streams of a mesh with more
+ *     than 8192 faces are packed again by the next frame.  The scene's content counts as changed: a cached merged run of
+ *     b32_frame_add_scene that contains the slot is rebuilt by the next batched frame (one build with its host synchronisation per pose,
+ *     b32_batch_count(ctx, 2) grows by one) -- a mesh that is posed every frame is better drawn on its own, as the modeler does.
+ *   A B32Placement on top of a pose is pose first, placement second (in k_setup, k_pick, k_hover as before).  The reference has no such
+ *   combination: the modeler has bones and no placements, the world editor placements and no bones.
+ *   b32_hover_mesh on a rigged slot tests the mirror plane on the REST position (find_hovered_element tests the local position,
+ *   viewport.rs:2482-2486, and projects the posed one); box selection and picking have no mirror test.
+ * b32_scene_read_vertices   blocking: vertices first .. first + count of the scene as they are on the device now (posed, if posed).
+ * Errors: NULL context, a slot (or context) without a scene, set_rig with NULL indices and nv > 0, pose without a rig or with NULL bones
+ * and n_bones > 0, read_vertices with NULL out and count > 0 or first + count > nv -> B32_E_ARG; n_bones > B32_MAX_BONES ->
+ * B32_E_UNSUPPORTED. */
+typedef struct B32Bone {            /* 32 bytes: get_bone_world_transform(i) with libm kept on the host */
+    float pos[3];                   /* bone_pos */
+    float cos_x, sin_x, cos_z, sin_z;   /* of bone_rot.x / .z .to_radians(); read only when rotate != 0 */
+    uint32_t rotate;                /* 0: rotate_by_euler's early return (|rot.x| < 0.001 && |rot.z| < 0.001, degrees) */
+} B32Bone;
+#define B32_BONE_NONE 0xFFFFu
+#define B32_MAX_BONES 64u
+int b32_scene_set_rig(b32_ctx* ctx, b32_scene* slot /* NULL: the context's resident scene */, const uint16_t* bone_of_vertex /* nv entries */);
+int b32_scene_pose(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, const B32Bone* bones, uint32_t n_bones);
+int b32_scene_read_vertices(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t first, uint32_t count, B32Vertex* out);  /* blocking */
 
 /* ---- a frame of several meshes (scene.rs:112-261) -------------------------------------------------------------------------------
  * The console's render step is one render_mesh_15 call per room and per asset part onto the same framebuffer, with ONE camera and
