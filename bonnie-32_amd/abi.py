@@ -85,6 +85,18 @@ HOVER_NONE = 0xFFFFFFFF
 HOVER_VERTEX_THRESHOLD, HOVER_EDGE_THRESHOLD = 6.0, 4.0      # viewport.rs:2428-2429
 BOX_VERTICES, BOX_POLYGONS = 0, 1
 BOX_HEADER_BYTES = 16               # b32_box_select_async's result: {uint32 n_elements; uint32 n_selected; 8 bytes of padding}, then the words
+# B32SectorFace / B32RoomGrid / B32RoomHoverParams / B32RoomHover (b32_room, b32_room_hover, b32_room_box_select)
+SECTOR_FACE_DTYPE = np.dtype([("gx", "<u2"), ("gz", "<u2"), ("kind", "u1"), ("index", "u1"), ("_pad", "<u2"), ("heights", "<f4", 4)])
+ROOM_GRID_DTYPE = np.dtype([("position", "<f4", 3), ("sector_size", "<f4")])
+ROOM_HOVER_PARAMS_DTYPE = np.dtype([("mx", "<f4"), ("my", "<f4"), ("vertex_threshold", "<f4"), ("edge_threshold", "<f4")])
+ROOM_HOVER_DTYPE = np.dtype([("vertex_rec", "<u4"), ("vertex_corner", "<u4"), ("vertex_dist", "<f4"), ("vertex_depth", "<f4"),
+                             ("edge_rec", "<u4"), ("edge_idx", "<u4"), ("edge_dist", "<f4"), ("edge_depth", "<f4"),
+                             ("face_rec", "<u4"), ("face_depth", "<f4"), ("_pad", "<u4", 2)])
+assert SECTOR_FACE_DTYPE.itemsize == 24 and ROOM_GRID_DTYPE.itemsize == 16 and ROOM_HOVER_PARAMS_DTYPE.itemsize == 16 and ROOM_HOVER_DTYPE.itemsize == 48
+ROOM_FLOOR, ROOM_CEILING, ROOM_WALL_NORTH, ROOM_WALL_EAST, ROOM_WALL_SOUTH, ROOM_WALL_WEST, ROOM_WALL_NWSE, ROOM_WALL_NESW = range(8)
+SECTOR_SIZE = 1024.0                # world/geometry.rs:10
+ROOM_MAX_FACES = 1 << 24
+ROOM_VERTEX_THRESHOLD, ROOM_EDGE_THRESHOLD = 6.0, 4.0        # viewport_3d.rs:7038-7039
 # B32Bone (b32_scene_pose): get_bone_world_transform(i) with cos / sin taken on the host; rotate == 0: rotate_by_euler's early return
 BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("cos_z", "<f4"), ("sin_z", "<f4"), ("rotate", "<u4")])
 assert BONE_DTYPE.itemsize == 32
@@ -201,6 +213,14 @@ SYMBOLS = [
     ("b32_hover_mesh_async", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("b32_box_select", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     ("b32_box_select_async", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("b32_room_create", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    ("b32_room_update", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_room_destroy", None, [_P, _P]),
+    ("b32_room_hover", C.c_int, [_P, _P, _P, _P, _P]),
+    ("b32_room_hover_async", C.c_int, [_P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    ("b32_room_hover_winner", C.c_int, [_P]),
+    ("b32_room_box_select", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    ("b32_room_box_select_async", C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_uint32, _P, C.POINTER(C.c_uint64)]),
     ("b32_fb_clear_gradient", C.c_int, [_P] + [C.c_uint8] * 8),
     ("b32_fb_clear_transparent", C.c_int, [_P]),
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),

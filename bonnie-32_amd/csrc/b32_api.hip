@@ -71,6 +71,8 @@ void b32_destroy(b32_ctx* c) {
     if (c->hover_bits) (void)hipFree(c->hover_bits);
     if (c->hover_words) (void)hipFree(c->hover_words);
     for (hipEvent_t e : c->hover_tev) if (e) (void)hipEventDestroy(e);
+    if (c->room_words) (void)hipFree(c->room_words);
+    if (c->room_points) (void)hipFree(c->room_points);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);

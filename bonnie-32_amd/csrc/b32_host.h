@@ -255,6 +255,10 @@ struct b32_ctx {
     uint32_t* hover_bits = nullptr; size_t hover_cap_bits = 0;
     void* hover_words = nullptr;
     hipEvent_t hover_tev[2] = {}; bool hover_timed = false;
+    // b32_room_hover / b32_room_box_select[_async] (b32_room.hip): the three sets of minima of a room hover (all ones between two calls) and
+    // the device copy of a box selection's points.  Results leave through the pick's ring of result buffers.
+    void* room_words = nullptr;
+    float* room_points = nullptr; size_t room_cap_points = 0;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only

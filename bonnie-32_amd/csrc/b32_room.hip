@@ -1,0 +1,329 @@
+// b32_room.hip -- the world editor's hover and rubber band over the current room's sector faces: b32_room, b32_room_hover[_async],
+// b32_room_box_select[_async], b32_room_hover_winner.
+//
+// Reference: find_hovered_elements (editor/viewport_3d.rs:7028-7336) asks on every mouse move which sector vertex, edge or face is under
+// the cursor, each loop keeping the candidate of SMALLEST CAMERA DEPTH (the modeler's b32_hover_mesh keeps the smallest distance);
+// find_selections_in_rect (:7512-7594) projects every face's centre and every object's position against a rectangle.  Both walk the
+// sector grid itself -- per face four heights on a lattice -- which a b32_room holds as one 24-byte record per face in the reference's
+// loop order; the arithmetic of one record is b32_room_body.h.
+//
+// GPU form of a hover.  "None yet, or strictly smaller depth" in loop order is the rule of b32_pick.hip's three minima, once per loop.
+//   k_room_hover          one lane per record, 1024 records per workgroup in four trips of 256 lanes; a lane projects its four corners
+//                         once and offers its vertices, edges and face to three sets of minima, which are reduced one after the other
+//                         (pick_reduce's LDS scratch is one array: a barrier between two reductions); at most one agent-scope atomic
+//                         per word and workgroup.
+//   k_room_hover_resolve  one workgroup: decodes the three sets, recomputes the winners' distance and depth from their records (exact
+//                         bits, the sign of a zero), writes the 48-byte result and re-arms the words for the next call on the stream.
+// k_room_box: one lane per element (records, then points); a wave's ballot is two words of the bitmap, as in k_box_select.
+#include "b32_pick_body.h"
+#include "b32_room_body.h"
+
+struct b32_room {
+    B32SectorFace* faces = nullptr;             // n records on the device
+    uint32_t n = 0;
+    B32RoomGrid grid{};                         // travels in the kernel argument: an update is ordered by the launch that follows it
+};
+
+namespace b32 {
+
+constexpr size_t ROOM_BOX_HEADER = 16;          // {uint32 n_elements; uint32 n_selected; 8 bytes of padding} in front of the words
+
+struct RoomWords { PickWords vertex, edge, face; };
+struct RoomHoverArgs {
+    RoomView v; B32RoomGrid grid; B32RoomHoverParams prm;
+    const B32SectorFace* faces; uint32_t n;
+    RoomWords* words;
+    unsigned char* result;                      // one B32RoomHover
+};
+struct RoomBoxArgs {
+    RoomView v; B32RoomGrid grid;
+    const B32SectorFace* faces; const float* points;
+    uint32_t n, n_points, nwords;
+    float x0, y0, x1, y1;
+    unsigned char* result;                      // the header and the words
+};
+static_assert(sizeof(B32SectorFace) == 24 && sizeof(B32RoomGrid) == 16 && sizeof(B32RoomHoverParams) == 16 && sizeof(B32RoomHover) == 48 &&
+              sizeof(RoomWords) == 48, "room records");
+
+__device__ __forceinline__ void room_offer(const PickWords& m, PickWords* w) {
+    if (m.first == PICK_NONE) return;
+    __hip_atomic_fetch_min(&w->first, m.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m.first_nan != PICK_NONE) __hip_atomic_fetch_min(&w->first_nan, m.first_nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m.key != ~0ull) __hip_atomic_fetch_min(&w->key, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_room_hover(RoomHoverArgs a) {
+    const uint32_t e0 = blockIdx.x * PICK_CHUNK;
+    PickWords mv = pick_no_hit(), me = pick_no_hit(), mf = pick_no_hit();
+#pragma unroll 1
+    for (uint32_t trip = 0; trip < PICK_CHUNK / 256u; ++trip) {
+        const uint32_t i = e0 + trip * 256u + threadIdx.x;
+        if (i >= a.n) continue;
+        const B32SectorFace f = a.faces[i];
+        RoomCandidates c;
+        room_candidates(a.v, a.grid, f, a.prm, c);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if ((c.vmask >> k) & 1u) pick_take(mv, c.vdepth[k], i * 4u + k);
+            if ((c.emask >> k) & 1u) pick_take(me, c.edepth[k], i * 4u + k);
+        }
+        if (c.face) pick_take(mf, c.fdepth, i);
+    }
+    mv = pick_reduce(mv);
+    __syncthreads();                            // thread 0 has read the scratch before the next reduction writes it
+    me = pick_reduce(me);
+    __syncthreads();
+    mf = pick_reduce(mf);
+    if (threadIdx.x == 0u) {
+        room_offer(mv, &a.words->vertex);
+        room_offer(me, &a.words->edge);
+        room_offer(mf, &a.words->face);
+    }
+}
+
+// the winner of a set of minima: false = none; nan = the first candidate's depth was a NaN (it stuck)
+__device__ __forceinline__ bool room_winner(const PickWords& w, uint32_t& id, bool& nan) {
+    if (w.first == PICK_NONE) return false;
+    nan = w.first == w.first_nan;
+    id = nan ? w.first : (uint32_t)w.key;
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_room_hover_resolve(RoomHoverArgs a) {
+    if (threadIdx.x != 0u) return;
+    const RoomWords w = *a.words;
+    RoomWords armed; armed.vertex = pick_no_hit(); armed.edge = pick_no_hit(); armed.face = pick_no_hit();
+    *a.words = armed;
+    B32RoomHover r;
+    r.vertex_rec = PICK_NONE; r.vertex_corner = PICK_NONE; r.vertex_dist = 0.0f; r.vertex_depth = 0.0f;
+    r.edge_rec = PICK_NONE; r.edge_idx = PICK_NONE; r.edge_dist = 0.0f; r.edge_depth = 0.0f;
+    r.face_rec = PICK_NONE; r.face_depth = 0.0f; r._pad[0] = 0u; r._pad[1] = 0u;
+    uint32_t id; bool nan;
+    if (room_winner(w.vertex, id, nan) && (id >> 2) < a.n) {
+        RoomQuad q;
+        room_project(a.v, a.grid, a.faces[id >> 2], q);
+        r.vertex_rec = id >> 2; r.vertex_corner = id & 3u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)             // (constant indices: the quad stays in registers)
+            if ((uint32_t)k == (id & 3u)) (void)room_vertex(q, k, a.prm.mx, a.prm.my, a.prm.vertex_threshold, r.vertex_dist, r.vertex_depth);
+        if (nan) r.vertex_depth = __uint_as_float(PICK_QNAN);
+    }
+    if (room_winner(w.edge, id, nan) && (id >> 2) < a.n) {
+        RoomQuad q;
+        room_project(a.v, a.grid, a.faces[id >> 2], q);
+        r.edge_rec = id >> 2; r.edge_idx = id & 3u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((uint32_t)k == (id & 3u)) (void)room_edge(q, k, a.prm.mx, a.prm.my, a.prm.edge_threshold, r.edge_dist, r.edge_depth);
+        if (nan) r.edge_depth = __uint_as_float(PICK_QNAN);
+    }
+    if (room_winner(w.face, id, nan) && id < a.n) {
+        RoomQuad q;
+        room_project(a.v, a.grid, a.faces[id], q);
+        r.face_rec = id;
+        (void)room_face(q, a.prm.mx, a.prm.my, r.face_depth);
+        if (nan) r.face_depth = __uint_as_float(PICK_QNAN);
+    }
+    *reinterpret_cast<B32RoomHover*>(a.result) = r;
+}
+
+// find_selections_in_rect, viewport_3d.rs:7512-7594.  The header's n_selected is zero when the kernel starts.
+__global__ __launch_bounds__(256) void k_room_box(RoomBoxArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t total = a.n + a.n_points;
+    bool sel = false;
+    if (i < total) {
+        float p[3];
+        if (i < a.n) room_centre(a.grid, a.faces[i], p);
+        else { const float* s = a.points + (size_t)(i - a.n) * 3; p[0] = s[0]; p[1] = s[1]; p[2] = s[2]; }
+        sel = room_point_in_rect(a.v, p, a.x0, a.y0, a.x1, a.y1);
+    }
+    const unsigned long long b = __ballot(sel);
+    uint32_t* head = reinterpret_cast<uint32_t*>(a.result);
+    if ((threadIdx.x & 63u) == 0u) {                                                     // (i is a multiple of 64 here)
+        uint32_t* words = head + ROOM_BOX_HEADER / 4;
+        const uint32_t wd = i >> 5;
+        if (wd < a.nwords) words[wd] = (uint32_t)b;
+        if (wd + 1u < a.nwords) words[wd + 1u] = (uint32_t)(b >> 32);
+        const uint32_t cnt = (uint32_t)__popcll(b);
+        if (cnt) __hip_atomic_fetch_add(&head[1], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (i == 0u) head[0] = total;
+}
+
+}  // namespace b32
+
+// ------------------------------------------------------------------ host
+namespace {
+
+void room_view(RoomView& v, const b32_ctx* c, const B32Camera* cam) {
+    v = RoomView{};
+    for (int k = 0; k < 3; ++k) { v.pos[k] = cam->position[k]; v.bx[k] = cam->basis_x[k]; v.by[k] = cam->basis_y[k]; v.bz[k] = cam->basis_z[k]; }
+    v.vs = ((float)(c->width < c->height ? c->width : c->height) / 2.0f) * 0.75f;       // math.rs:642-643
+    v.half_w = (float)c->width / 2.0f; v.half_h = (float)c->height / 2.0f;
+}
+
+bool room_kinds_ok(const B32SectorFace* faces, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) if (faces[i].kind > 7u) return false;
+    return true;
+}
+
+int room_common_check(const b32_ctx* c, const B32Camera* cam, const b32_room* room) {
+    if (!c || !cam || !room || !c->width || !c->height) return B32_E_ARG;
+    return B32_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int b32_room_create(b32_ctx* c, const B32RoomGrid* grid, const B32SectorFace* faces, uint32_t n, b32_room** out) {
+    if (!c || !out) return B32_E_ARG;
+    *out = nullptr;
+    if (!grid || (n && !faces)) return B32_E_ARG;
+    if (n > B32_ROOM_MAX_FACES) return B32_E_UNSUPPORTED;
+    if (!room_kinds_ok(faces, n)) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    b32_room* r = new b32_room();
+    r->n = n; r->grid = *grid;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&r->faces), n ? (size_t)n * sizeof(B32SectorFace) : 4);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(r->faces, faces, (size_t)n * sizeof(B32SectorFace), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) {
+        c->last_hip = (int)e;
+        if (r->faces) (void)hipFree(r->faces);
+        delete r;
+        return B32_E_HIP;
+    }
+    *out = r;
+    return B32_OK;
+}
+
+int b32_room_update(b32_ctx* c, b32_room* room, const B32RoomGrid* grid, uint32_t first, uint32_t count, const B32SectorFace* faces) {
+    if (!c || !room || (count && !faces)) return B32_E_ARG;
+    if ((unsigned long long)first + count > room->n) return B32_E_ARG;
+    if (!room_kinds_ok(faces, count)) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    if (count) HIPCHK(c, hipMemcpyAsync(room->faces + first, faces, (size_t)count * sizeof(B32SectorFace), hipMemcpyHostToDevice, c->stream));
+    if (grid) room->grid = *grid;
+    return B32_OK;
+}
+
+void b32_room_destroy(b32_ctx* c, b32_room* room) {
+    if (!room) return;
+    if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }     // (a hover that reads it may be in flight)
+    if (room->faces) (void)hipFree(room->faces);
+    delete room;
+}
+
+int b32_room_hover_async(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomHoverParams* prm, void* out, uint64_t* ticket) {
+    { const int rc = room_common_check(c, cam, room); if (rc) return rc; }
+    if (!prm || !out || !ticket) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc;
+    RoomHoverArgs a{};
+    room_view(a.v, c, cam);
+    a.grid = room->grid; a.prm = *prm; a.faces = room->faces; a.n = room->n;
+    // the words: all ones whenever no room hover is running (allocated so; k_room_hover_resolve leaves them so)
+    if (!c->room_words) {
+        HIPCHK(c, hipMalloc(&c->room_words, sizeof(RoomWords)));
+        HIPCHK(c, hipMemsetAsync(c->room_words, 0xFF, sizeof(RoomWords), c->stream));
+    }
+    a.words = static_cast<RoomWords*>(c->room_words);
+    unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
+    const size_t bytes = sizeof(B32RoomHover);
+    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.result))) return rc;
+    const uint32_t groups = (a.n + PICK_CHUNK - 1u) / PICK_CHUNK;                       // (n <= 2^24)
+    if (groups) hipLaunchKernelGGL(k_room_hover, dim3(groups), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_room_hover_resolve, dim3(1), dim3(64), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
+}
+
+int b32_room_hover(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomHoverParams* prm, B32RoomHover* out) {
+    { const int rc = room_common_check(c, cam, room); if (rc) return rc; }
+    if (!prm || !out) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = pick_host_ensure(c, sizeof(B32RoomHover)))) return rc;
+    uint64_t t = 0;
+    if ((rc = b32_room_hover_async(c, cam, room, prm, c->pick_host, &t))) return rc;
+    if ((rc = b32_ticket_wait(c, t))) return rc;
+    std::memcpy(out, c->pick_host, sizeof(B32RoomHover));
+    return B32_OK;
+}
+
+// viewport_3d.rs:7283-7336, literally: candidates pushed as (depth, type) in the order vertex, edge, face; sort_by(partial_cmp, a NaN
+// compares Equal) -- for so few elements the standard library's stable insertion sort, which is what this is; tolerance; lowest type
+// within the tolerance, else the closest one's type.
+int b32_room_hover_winner(const B32RoomHover* h) {
+    if (!h) return -1;
+    float depth[3]; int type[3]; int n = 0;
+    if (h->vertex_rec != 0xFFFFFFFFu) { depth[n] = h->vertex_depth; type[n++] = 0; }
+    if (h->edge_rec != 0xFFFFFFFFu) { depth[n] = h->edge_depth; type[n++] = 1; }
+    if (h->face_rec != 0xFFFFFFFFu) { depth[n] = h->face_depth; type[n++] = 2; }
+    if (!n) return -1;
+    for (int i = 1; i < n; ++i) {
+        const float d = depth[i]; const int t = type[i];
+        int j = i;
+        while (j > 0 && d < depth[j - 1]) { depth[j] = depth[j - 1]; type[j] = type[j - 1]; --j; }
+        depth[j] = d; type[j] = t;
+    }
+    const float closest = depth[0];
+    const float tolerance = closest * 0.01f;
+    int best = -1;
+    for (int i = 0; i < n; ++i) if (fabsf(depth[i] - closest) < tolerance && (best < 0 || type[i] < best)) best = type[i];
+    return best >= 0 ? best : type[0];
+}
+
+int b32_room_box_select_async(b32_ctx* c, const B32Camera* cam, b32_room* room, float x0, float y0, float x1, float y1, const float* points_xyz,
+                              uint32_t n_points, void* out, uint64_t* ticket) {
+    { const int rc = room_common_check(c, cam, room); if (rc) return rc; }
+    if ((n_points && !points_xyz) || !out || !ticket) return B32_E_ARG;
+    if ((unsigned long long)room->n + n_points >= (1ull << 32)) return B32_E_UNSUPPORTED;
+    (void)hipSetDevice(c->device);
+    int rc;
+    RoomBoxArgs a{};
+    room_view(a.v, c, cam);
+    a.grid = room->grid; a.faces = room->faces; a.n = room->n; a.n_points = n_points;
+    a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
+    const uint32_t total = a.n + n_points;
+    a.nwords = (uint32_t)(((unsigned long long)total + 31u) / 32u);
+    if (n_points) {                             // the points: copied before return, ordered on the stream behind the last call that read them
+        const size_t need = (size_t)n_points * 3u;
+        if (need > c->room_cap_points) {
+            if (c->room_points) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->room_points)); c->room_points = nullptr; c->room_cap_points = 0; }
+            const size_t cap = need + need / 4 + 64;
+            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->room_points), cap * sizeof(float)));
+            c->room_cap_points = cap;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->room_points, points_xyz, need * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        a.points = c->room_points;
+    }
+    unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
+    const size_t bytes = ROOM_BOX_HEADER + (size_t)a.nwords * 4u;
+    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.result))) return rc;
+    HIPCHK(c, hipMemsetAsync(a.result, 0, ROOM_BOX_HEADER, c->stream));
+    if (total) hipLaunchKernelGGL(k_room_box, dim3((uint32_t)(((unsigned long long)total + 255u) / 256u)), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
+}
+
+int b32_room_box_select(b32_ctx* c, const B32Camera* cam, b32_room* room, float x0, float y0, float x1, float y1, const float* points_xyz,
+                        uint32_t n_points, uint32_t* words, uint32_t* n_selected) {
+    { const int rc = room_common_check(c, cam, room); if (rc) return rc; }
+    if ((n_points && !points_xyz) || !n_selected) return B32_E_ARG;
+    if ((unsigned long long)room->n + n_points >= (1ull << 32)) return B32_E_UNSUPPORTED;
+    (void)hipSetDevice(c->device);
+    const size_t nwords = (size_t)(((unsigned long long)room->n + n_points + 31u) / 32u), bytes = ROOM_BOX_HEADER + nwords * 4u;
+    int rc;
+    if ((rc = pick_host_ensure(c, bytes))) return rc;
+    uint64_t t = 0;
+    if ((rc = b32_room_box_select_async(c, cam, room, x0, y0, x1, y1, points_xyz, n_points, c->pick_host, &t))) return rc;
+    if ((rc = b32_ticket_wait(c, t))) return rc;
+    const unsigned char* h = static_cast<const unsigned char*>(c->pick_host);
+    std::memcpy(n_selected, h + 4, 4);
+    if (words && nwords) std::memcpy(words, h + ROOM_BOX_HEADER, nwords * 4u);
+    return B32_OK;
+}
+
+}  // extern "C"

@@ -652,6 +652,57 @@ inline BoxSelection box_select(Framebuffer& fb, const ResidentMesh& mesh, const 
                          r.words.data(), &r.n_selected), "box_select");
     return r;
 }
+// Room hover and box selection: the world editor's find_hovered_elements (editor/viewport_3d.rs:7028-7336, the three sector loops and the
+// priority rule) and find_selections_in_rect (:7512-7594) for the current room, on the device (b32_room_hover, b32_room_box_select).  A Room
+// holds the grid and one B32SectorFace per sector face in iter_sectors order (world/geometry.rs:2828-2835: gx outer, gz inner; floor,
+// ceiling, north, east, south, west walls by i, then nwse, then nesw); update() is a height drag.
+class Room {
+public:
+    Room(Framebuffer& fb, const std::vector<B32SectorFace>& faces, const B32RoomGrid& grid = B32RoomGrid{ { 0.0f, 0.0f, 0.0f }, B32_SECTOR_SIZE })
+        : ctx_(fb.ctx()), n_((uint32_t)faces.size()) {
+        check(b32_room_create(ctx_, &grid, faces.data(), n_, &r_), "room_create");
+    }
+    ~Room() { if (r_) b32_room_destroy(ctx_, r_); }
+    Room(Room&& o) noexcept : ctx_(o.ctx_), r_(o.r_), n_(o.n_) { o.r_ = nullptr; }
+    Room(const Room&) = delete;
+    Room& operator=(const Room&) = delete;
+    // records [first, first + faces.size()) and, when given, the grid
+    void update(uint32_t first, const std::vector<B32SectorFace>& faces, const B32RoomGrid* grid = nullptr) {
+        check(b32_room_update(ctx_, r_, grid, first, (uint32_t)faces.size(), faces.data()), "room_update");
+    }
+    b32_room* handle() const { return r_; }
+    uint32_t faces() const { return n_; }
+private:
+    b32_ctx* ctx_ = nullptr; b32_room* r_ = nullptr; uint32_t n_ = 0;
+};
+inline B32RoomHoverParams room_hover_params(float mx, float my) { return B32RoomHoverParams{ mx, my, 6.0f, 4.0f }; }   // viewport_3d.rs:7038-7039
+// all three loops, raw; room_hover_winner is the reference's answer
+inline B32RoomHover room_hover(Framebuffer& fb, const Room& room, const Camera& camera, const B32RoomHoverParams& params) {
+    const B32Camera cam = detail::pack(camera);
+    B32RoomHover r{};
+    check(b32_room_hover(fb.ctx(), &cam, room.handle(), &params, &r), "room_hover");
+    return r;
+}
+// The asynchronous form: `out` (48 bytes, preferably from b32_host_alloc) holds a B32RoomHover once the returned ticket is done.
+inline uint64_t room_hover_async(Framebuffer& fb, const Room& room, const Camera& camera, const B32RoomHoverParams& params, void* out) {
+    const B32Camera cam = detail::pack(camera);
+    uint64_t ticket = 0;
+    check(b32_room_hover_async(fb.ctx(), &cam, room.handle(), &params, out, &ticket), "room_hover_async");
+    return ticket;
+}
+// viewport_3d.rs:7283-7336: 0 vertex, 1 edge, 2 face, -1 nothing (closest by depth; within 1 % of the closest depth vertex > edge > face)
+inline int room_hover_winner(const B32RoomHover& r) { return b32_room_hover_winner(&r); }
+// element i is record i, then point i - room.faces() of `points` (the room's object positions)
+inline BoxSelection room_box_select(Framebuffer& fb, const Room& room, const Camera& camera, float x0, float y0, float x1, float y1,
+                                    const std::vector<Vec3>& points = {}) {
+    const B32Camera cam = detail::pack(camera);
+    std::vector<float> xyz; xyz.reserve(points.size() * 3);
+    for (const auto& p : points) { xyz.push_back(p.x); xyz.push_back(p.y); xyz.push_back(p.z); }
+    BoxSelection r; r.words.assign(((size_t)room.faces() + points.size() + 31) / 32, 0u);
+    check(b32_room_box_select(fb.ctx(), &cam, room.handle(), x0, y0, x1, y1, xyz.data(), (uint32_t)points.size(), r.words.data(), &r.n_selected),
+          "room_box_select");
+    return r;
+}
 // The host restatements (what a host without the library walks per mouse move): separately rounded f32 operations in the reference's order
 // (compile with -ffp-contract=off where the compiler would fuse).
 namespace detail {

@@ -636,6 +636,246 @@ class BoxResult:
     close = HoverResult.close
 
 
+# ---- room hover and box selection (b32_room_hover, b32_room_box_select): the world editor's find_hovered_elements / find_selections_in_rect
+_ROOM_KEYS = (("floor", abi.ROOM_FLOOR), ("ceiling", abi.ROOM_CEILING), ("walls_north", abi.ROOM_WALL_NORTH), ("walls_east", abi.ROOM_WALL_EAST),
+              ("walls_south", abi.ROOM_WALL_SOUTH), ("walls_west", abi.ROOM_WALL_WEST), ("walls_nwse", abi.ROOM_WALL_NWSE), ("walls_nesw", abi.ROOM_WALL_NESW))
+# corner k's (x, z) selectors per kind, 0 = base, 1 = base + S (viewport_3d.rs:6603-6657, :7099-7170, :7183-7279)
+_ROOM_XSEL = np.array([[0, 1, 1, 0], [0, 1, 1, 0], [0, 1, 1, 0], [1, 1, 1, 1], [1, 0, 0, 1], [0, 0, 0, 0], [0, 1, 1, 0], [1, 0, 0, 1]], bool)
+_ROOM_ZSEL = np.array([[0, 0, 1, 1], [0, 0, 1, 1], [0, 0, 0, 0], [0, 1, 1, 0], [1, 1, 1, 1], [1, 0, 0, 1], [0, 1, 1, 0], [0, 1, 1, 0]], bool)
+# wall_center_in_rect's own (x0, z0, x1, z1) per direction, as selectors (viewport_3d.rs:7633-7640); rows 0 and 1 are unused
+_ROOM_CENTRE_SEL = np.array([[0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 1, 0], [1, 0, 1, 1], [0, 1, 1, 1], [0, 0, 0, 1], [0, 0, 1, 1], [1, 0, 0, 1]], bool)
+
+
+def room_faces_from_sectors(sectors):
+    """A room's sector grid as abi.SECTOR_FACE_DTYPE records in the reference's one loop order (iter_sectors, world/geometry.rs:2828-2835):
+    gx outer, gz inner; inside a sector floor, ceiling, the north, east, south and west walls by i, then the nwse and the nesw walls.
+    sectors[gx][gz] is None or a mapping with the optional keys floor, ceiling (one face) and walls_north, walls_east, walls_south,
+    walls_west, walls_nwse, walls_nesw (lists of faces); a face is four heights or a mapping with "heights"."""
+    rows = []
+    for gx, col in enumerate(sectors):
+        for gz, sec in enumerate(col):
+            if sec is None:
+                continue
+            for key, kind in _ROOM_KEYS:
+                got = sec.get(key)
+                if got is None:
+                    continue
+                faces = [got] if kind < 2 else list(got)
+                for i, face in enumerate(faces):
+                    h = face["heights"] if hasattr(face, "keys") else face
+                    rows.append((gx, gz, kind, i, 0, tuple(float(np.float32(v)) for v in h)))
+    out = T.make_sector_faces(len(rows))
+    for j, r in enumerate(rows):
+        out[j] = r
+    return out
+
+
+def _room_grid(grid):
+    """(position, sector_size) or an abi.ROOM_GRID_DTYPE record -> one abi.ROOM_GRID_DTYPE record."""
+    if isinstance(grid, np.ndarray) and grid.dtype == abi.ROOM_GRID_DTYPE:
+        return grid.reshape(-1)[:1].copy()
+    g = np.zeros(1, abi.ROOM_GRID_DTYPE)
+    pos, size = grid if len(grid) == 2 else (grid, abi.SECTOR_SIZE)
+    g["position"][0] = pos; g["sector_size"] = size
+    return g
+
+
+class RoomMirror:
+    """find_hovered_elements' three sector loops (editor/viewport_3d.rs:7050-7281) and find_selections_in_rect (:7512-7655) for one room in
+    numpy float32: what b32_room_hover / b32_room_box_select compute, and what a host without this library walks per mouse move.  The
+    constructor does what the reference does once per frame (derive and project every corner); hover() and box_select() answer one
+    cursor / rectangle with vectorised f32 operations, each separately rounded in the reference's order."""
+
+    def __init__(self, faces, grid, camera, w, h):
+        f32 = np.float32
+        self.faces = f = np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+        self.grid = g = _room_grid(grid)[0]
+        self.camera, self.w, self.h = camera, w, h
+        self.n = len(f)
+        px, py, pz = (f32(v) for v in g["position"]); S = f32(g["sector_size"])
+        with np.errstate(all="ignore"):
+            self.bx = bx = px + f["gx"].astype(f32) * S
+            self.bz = bz = pz + f["gz"].astype(f32) * S
+            kind = np.minimum(f["kind"], 7)
+            x = np.where(_ROOM_XSEL[kind], (bx + S)[:, None], bx[:, None])
+            z = np.where(_ROOM_ZSEL[kind], (bz + S)[:, None], bz[:, None])
+            y = py + f["heights"]
+            sx, sy, d, some = _project_f32(x.reshape(-1), y.reshape(-1).astype(f32), z.reshape(-1), camera, w, h, None)
+        self.sx, self.sy, self.d, self.some = (a.reshape(-1, 4) for a in (sx, sy, d, some))
+
+    @staticmethod
+    def _triangle(px, py, x0, y0, e0, x1, y1, e1, x2, y2, e2):
+        """(inside, depth): point_in_triangle_2d (math.rs:687-706), interpolate_depth_in_triangle (viewport_3d.rs:7485-7508)."""
+        f32 = np.float32
+        d1 = (px - x1) * (y0 - y1) - (x0 - x1) * (py - y1)
+        d2 = (px - x2) * (y1 - y2) - (x1 - x2) * (py - y2)
+        d3 = (px - x0) * (y2 - y0) - (x2 - x0) * (py - y0)
+        has_neg = (d1 < 0) | (d2 < 0) | (d3 < 0)
+        has_pos = (d1 > 0) | (d2 > 0) | (d3 > 0)
+        area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)
+        w0 = ((x1 - px) * (y2 - py) - (x2 - px) * (y1 - py)) / area
+        w1 = ((x2 - px) * (y0 - py) - (x0 - px) * (y2 - py)) / area
+        w2 = f32(1.0) - w0 - w1
+        depth = np.where(np.abs(area) < f32(0.0001), (e0 + e1 + e2) / f32(3.0), w0 * e0 + w1 * e1 + w2 * e2).astype(f32)
+        return ~(has_neg & has_pos), depth
+
+    def hover(self, mx, my, vertex_threshold=abi.ROOM_VERTEX_THRESHOLD, edge_threshold=abi.ROOM_EDGE_THRESHOLD):
+        """One abi.ROOM_HOVER_DTYPE record: all three loops, raw (room_hover_winner() is the reference's answer)."""
+        f32 = np.float32
+        px, py = f32(mx), f32(my)
+        r = np.zeros((), abi.ROOM_HOVER_DTYPE)
+        for k in ("vertex_rec", "vertex_corner", "edge_rec", "edge_idx", "face_rec"):
+            r[k] = abi.HOVER_NONE
+        if not self.n:
+            return r
+        sx, sy, d, some = self.sx, self.sy, self.d, self.some
+        with np.errstate(all="ignore"):
+            # vertices, viewport_3d.rs:7050-7068
+            dx, dy = px - sx, py - sy
+            dist = np.sqrt(dx * dx + dy * dy)
+            c = np.nonzero((some & (dist < f32(vertex_threshold))).reshape(-1))[0]
+            hit, j, depth = _closest_in_order(c, d.reshape(-1)[c])
+            if hit:
+                r["vertex_rec"], r["vertex_corner"] = j >> 2, j & 3
+                r["vertex_dist"] = dist.reshape(-1)[j]; r["vertex_depth"] = depth
+            # edges (k, (k + 1) % 4), viewport_3d.rs:7078-7096
+            x0, y0, e0 = sx, sy, d
+            x1, y1, e1 = (np.roll(a, -1, axis=1) for a in (sx, sy, d))
+            ok = some & np.roll(some, -1, axis=1)
+            ex, ey = x1 - x0, y1 - y0
+            len_sq = ex * ex + ey * ey
+            tt = ((px - x0) * ex + (py - y0) * ey) / len_sq
+            tt = np.where(tt < f32(0.0), f32(0.0), tt)                          # f32::clamp: a NaN and -0.0 stay
+            tt = np.where(tt > f32(1.0), f32(1.0), tt)
+            qx, qy = px - (x0 + tt * ex), py - (y0 + tt * ey)
+            p0x, p0y = px - x0, py - y0
+            dist = np.where(len_sq < f32(1e-6), np.sqrt(p0x * p0x + p0y * p0y), np.sqrt(qx * qx + qy * qy)).astype(f32)
+            edepth = np.where(len_sq < f32(0.0001), (e0 + e1) * f32(0.5), e0 + tt * (e1 - e0)).astype(f32)
+            c = np.nonzero((ok & (dist < f32(edge_threshold))).reshape(-1))[0]
+            hit, j, depth = _closest_in_order(c, edepth.reshape(-1)[c])
+            if hit:
+                r["edge_rec"], r["edge_idx"] = j >> 2, j & 3
+                r["edge_dist"] = dist.reshape(-1)[j]; r["edge_depth"] = depth
+            # faces, check_quad_hit_with_depth, viewport_3d.rs:7436-7481
+            col = lambda a, k: a[:, k]
+            in_a, dep_a = self._triangle(px, py, *(col(a, k) for k in (0, 1, 2) for a in (sx, sy, d)))
+            in_b, dep_b = self._triangle(px, py, *(col(a, k) for k in (0, 2, 3) for a in (sx, sy, d)))
+            all4 = some.all(axis=1)
+            c = np.nonzero(all4 & (in_a | in_b))[0]
+            hit, j, depth = _closest_in_order(c, np.where(in_a, dep_a, dep_b)[c])
+            if hit:
+                r["face_rec"] = j; r["face_depth"] = depth
+        return r
+
+    def centres(self):
+        """The (x, y, z) the rubber band projects per record: face_center_in_rect / wall_center_in_rect, viewport_3d.rs:7597-7655."""
+        f32 = np.float32
+        f, g = self.faces, self.grid
+        py = f32(g["position"][1]); S = f32(g["sector_size"])
+        h = f["heights"]
+        with np.errstate(all="ignore"):
+            avg = (((h[:, 0] + h[:, 1]) + h[:, 2]) + h[:, 3]) / f32(4.0)
+            kind = np.minimum(f["kind"], 7)
+            sel = _ROOM_CENTRE_SEL[kind]
+            bx, bz = self.bx, self.bz
+            x0, z0, x1, z1 = (np.where(sel[:, k], (b + S), b) for k, b in ((0, bx), (1, bz), (2, bx), (3, bz)))
+            flat = kind < 2
+            cx = np.where(flat, bx + S / f32(2.0), (x0 + x1) / f32(2.0))
+            cz = np.where(flat, bz + S / f32(2.0), (z0 + z1) / f32(2.0))
+            return cx.astype(f32), (py + avg).astype(f32), cz.astype(f32)
+
+    def box_select(self, rect, points=None):
+        """(words, n_selected) for the rectangle (x0, y0, x1, y1): element i is record i, then point i - n of `points` ((m, 3) positions)."""
+        f32 = np.float32
+        x0, y0, x1, y1 = (f32(v) for v in rect)
+        pts = np.zeros((0, 3), f32) if points is None else np.ascontiguousarray(points, f32).reshape(-1, 3)
+        cx, cy, cz = self.centres() if self.n else (np.zeros(0, f32),) * 3
+        with np.errstate(all="ignore"):
+            x, y, z = (np.concatenate([a, pts[:, k]]) for k, a in enumerate((cx, cy, cz)))
+            sx, sy, _, ok = _project_f32(x, y, z, self.camera, self.w, self.h, None)   # world_to_screen, math.rs:503-534
+            sel = ok & (sx >= x0) & (sx <= x1) & (sy >= y0) & (sy <= y1)
+        n = len(sel)
+        bits = np.zeros(((n + 31) // 32) * 32, np.uint8)
+        bits[:n] = sel
+        words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+        return words, int(sel.sum())
+
+
+def room_hover(faces, grid, camera, w, h, mx, my, **params):
+    """Host mirror of b32_room_hover (see RoomMirror): one abi.ROOM_HOVER_DTYPE record."""
+    return RoomMirror(faces, grid, camera, w, h).hover(mx, my, **params)
+
+
+def room_box_select(faces, grid, camera, w, h, rect, points=None):
+    """Host mirror of b32_room_box_select (see RoomMirror): (words, n_selected)."""
+    return RoomMirror(faces, grid, camera, w, h).box_select(rect, points)
+
+
+def room_hover_winner(result):
+    """find_hovered_elements' answer (viewport_3d.rs:7283-7336) of a room hover record: 0 vertex, 1 edge, 2 face, -1 nothing.  The
+    candidates (depth, type) are sorted by depth (a stable insertion sort in which a NaN compares equal to everything, as
+    partial_cmp(..).unwrap_or(Equal) in the standard library's sort of so few elements); tolerance = closest * 0.01; the lowest type among
+    those with |d - closest| < tolerance wins, else the closest one's type."""
+    f32 = np.float32
+    cand = [(f32(result[d]), t) for t, (i, d) in enumerate((("vertex_rec", "vertex_depth"), ("edge_rec", "edge_depth"), ("face_rec", "face_depth")))
+            if int(result[i]) != abi.HOVER_NONE]
+    if not cand:
+        return -1
+    for i in range(1, len(cand)):
+        c, j = cand[i], i
+        while j > 0 and c[0] < cand[j - 1][0]:
+            cand[j] = cand[j - 1]; j -= 1
+        cand[j] = c
+    with np.errstate(all="ignore"):
+        closest = cand[0][0]
+        tolerance = closest * f32(0.01)
+        near = [t for d, t in cand if np.abs(d - closest) < tolerance]
+    return min(near) if near else cand[0][1]
+
+
+class Room:
+    """A resident room (b32_room): its grid and its abi.SECTOR_FACE_DTYPE records on the device.  update() is a height drag."""
+
+    def __init__(self, ctx, faces, grid=((0.0, 0.0, 0.0), abi.SECTOR_SIZE)):
+        self.ctx = getattr(ctx, "ctx", ctx)
+        f = np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+        g = _room_grid(grid)
+        self.n = len(f)
+        self._h = C.c_void_p()
+        _chk(self.ctx.lib.b32_room_create(self.ctx.h, g.ctypes.data, f.ctypes.data if len(f) else None, len(f), C.byref(self._h)), "b32_room_create")
+
+    def update(self, first=0, faces=None, grid=None):
+        """b32_room_update: records [first, first + len(faces)) and / or the grid."""
+        f = np.zeros(0, abi.SECTOR_FACE_DTYPE) if faces is None else np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+        g = _room_grid(grid) if grid is not None else None
+        _chk(self.ctx.lib.b32_room_update(self.ctx.h, self._h, g.ctypes.data if g is not None else None, int(first), len(f),
+                                          f.ctypes.data if len(f) else None), "b32_room_update")
+
+    def close(self):
+        if self._h and getattr(self.ctx, "h", None):
+            self.ctx.lib.b32_room_destroy(self.ctx.h, self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class RoomHoverResult:
+    """What b32_room_hover_async delivers into `buf` (48 bytes) once its ticket is done."""
+
+    def __init__(self, buf, owner=None):
+        self.buf, self._owner = buf, owner
+
+    @property
+    def record(self):
+        return self.buf[:48].view(abi.ROOM_HOVER_DTYPE)[0].copy()
+
+    close = HoverResult.close
+
+
 def _pack_placement(placement):
     if placement is None or isinstance(placement, abi.B32Placement):
         return placement
@@ -925,6 +1165,74 @@ class Context:
         if rc != abi.B32_OK and own:
             self.host_free(ptr)
         _chk(rc, "b32_box_select_async")
+        return int(t.value), BoxResult(arr, (self, ptr) if own else None)
+
+    # ---- room hover and box selection (b32_room_hover, b32_room_box_select): one Room
+    @staticmethod
+    def _room_hover_params(mouse, vertex_threshold, edge_threshold):
+        prm = np.zeros(1, abi.ROOM_HOVER_PARAMS_DTYPE)
+        prm["mx"], prm["my"] = mouse
+        prm["vertex_threshold"], prm["edge_threshold"] = vertex_threshold, edge_threshold
+        return prm
+
+    def room_hover(self, room, camera, mouse, vertex_threshold=abi.ROOM_VERTEX_THRESHOLD, edge_threshold=abi.ROOM_EDGE_THRESHOLD):
+        """b32_room_hover: one abi.ROOM_HOVER_DTYPE record (all three loops, raw; room_hover_winner() is the reference's answer)."""
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        prm = self._room_hover_params(mouse, vertex_threshold, edge_threshold)
+        out = np.zeros(1, abi.ROOM_HOVER_DTYPE)
+        _chk(self.lib.b32_room_hover(self.h, C.byref(cam), room._h, prm.ctypes.data, out.ctypes.data), "b32_room_hover")
+        return out[0]
+
+    def room_hover_async(self, room, camera, mouse, vertex_threshold=abi.ROOM_VERTEX_THRESHOLD, edge_threshold=abi.ROOM_EDGE_THRESHOLD, out=None):
+        """b32_room_hover_async -> (ticket, RoomHoverResult).  out: an (array, pointer) pair from host_alloc of at least 48 bytes; None:
+        page-locked memory of the result's own, released by RoomHoverResult.close()."""
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        prm = self._room_hover_params(mouse, vertex_threshold, edge_threshold)
+        own = out is None
+        arr, ptr = self.host_alloc(48) if own else out
+        if len(arr) < 48:
+            raise ValueError("room_hover_async: the result buffer is too small")
+        t = C.c_uint64()
+        rc = self.lib.b32_room_hover_async(self.h, C.byref(cam), room._h, prm.ctypes.data, ptr, C.byref(t))
+        if rc != abi.B32_OK and own:
+            self.host_free(ptr)
+        _chk(rc, "b32_room_hover_async")
+        return int(t.value), RoomHoverResult(arr, (self, ptr) if own else None)
+
+    def room_hover_winner(self, record):
+        """b32_room_hover_winner of one abi.ROOM_HOVER_DTYPE record."""
+        rec = np.ascontiguousarray(record, abi.ROOM_HOVER_DTYPE).reshape(1)
+        return int(self.lib.b32_room_hover_winner(rec.ctypes.data))
+
+    @staticmethod
+    def _room_points(points):
+        pts = np.zeros((0, 3), np.float32) if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        return pts, (pts.ctypes.data if len(pts) else None)
+
+    def room_box_select(self, room, camera, rect, points=None):
+        """b32_room_box_select: (words, n_selected) for the rectangle (x0, y0, x1, y1); element i is record i, then point i - n."""
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        pts, pp = self._room_points(points)
+        words = np.zeros((room.n + len(pts) + 31) // 32, np.uint32)
+        cnt = C.c_uint32()
+        _chk(self.lib.b32_room_box_select(self.h, C.byref(cam), room._h, *[float(v) for v in rect], pp, len(pts),
+                                          words.ctypes.data if len(words) else None, C.byref(cnt)), "b32_room_box_select")
+        return words, int(cnt.value)
+
+    def room_box_select_async(self, room, camera, rect, points=None, out=None):
+        """b32_room_box_select_async -> (ticket, BoxResult); out as for room_hover_async, of at least 16 + 4 * ceil(n_elements / 32) bytes."""
+        cam = camera.pack() if hasattr(camera, "pack") else camera
+        pts, pp = self._room_points(points)
+        need = abi.BOX_HEADER_BYTES + 4 * ((room.n + len(pts) + 31) // 32)
+        own = out is None
+        arr, ptr = self.host_alloc(need) if own else out
+        if len(arr) < need:
+            raise ValueError("room_box_select_async: the result buffer is too small")
+        t = C.c_uint64()
+        rc = self.lib.b32_room_box_select_async(self.h, C.byref(cam), room._h, *[float(v) for v in rect], pp, len(pts), ptr, C.byref(t))
+        if rc != abi.B32_OK and own:
+            self.host_free(ptr)
+        _chk(rc, "b32_room_box_select_async")
         return int(t.value), BoxResult(arr, (self, ptr) if own else None)
 
     def finish(self) -> T.RasterTimings:

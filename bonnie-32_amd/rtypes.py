@@ -248,6 +248,11 @@ def make_faces(n, texture_id=None):
     return f
 
 
+def make_sector_faces(n):
+    """n zeroed B32SectorFace records (abi.SECTOR_FACE_DTYPE): one face of a room's sector grid each, in iter_sectors order."""
+    return np.zeros(n, dtype=abi.SECTOR_FACE_DTYPE)
+
+
 def pack_fog(fog):
     """fog: None or (start, falloff, cull_distance, Color) as in render.rs:2309."""
     if fog is None:

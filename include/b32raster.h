@@ -564,6 +564,85 @@ int b32_box_select_async(b32_ctx* ctx, const B32Camera* camera, const struct B32
                          b32_topology* topology /* nullable for B32_BOX_VERTICES */, const B32Placement* place /* nullable */,
                          const B32BoxParams* params, void* out /* 16 + 4 * ceil(n_elements / 32) bytes */, uint64_t* ticket);
 
+/* ---- room hover and box selection: which sector vertex, edge or face of the CURRENT ROOM lies under the cursor ---------------------------
+ * The world editor's find_hovered_elements (editor/viewport_3d.rs:7028-7336: the three sector loops and the priority rule; its object
+ * loop is b32_pick_meshes) and find_selections_in_rect (:7512-7594) walk the sector grid itself, not a render mesh: per face four heights
+ * on a lattice of sector_size units (SECTOR_SIZE = 1024.0), which the editor changes while it drags.  A b32_room holds the grid and one
+ * B32SectorFace per face in the reference's one loop order (iter_sectors, world/geometry.rs:2828-2835: gx outer, gz inner; inside a
+ * sector floor, ceiling, the north, east, south and west walls by i, then the nwse and the nesw walls by i), which all four walks share.
+ * kind: 0 Floor, 1 Ceiling, 2 WallNorth, 3 WallEast, 4 WallSouth, 5 WallWest, 6 WallNwSe, 7 WallNeSw; index: the i of SectorFace::Wall*(i),
+ * 0 for floor and ceiling (carried, not read).  The device derives the corners, each a separately rounded f32 operation:
+ *   bx = position[0] + (float)gx * S, bz = position[2] + (float)gz * S, corner k = (bx or bx + S, position[1] + heights[k], bz or bz + S)
+ * with the (x, z) selectors (0 = base, 1 = base + S) of viewport_3d.rs:6603-6657, :7099-7170 and :7183-7279, which agree:
+ *   Floor / Ceiling (0,0) (1,0) (1,1) (0,1)     North (0,0) (1,0) (1,0) (0,0)     East (1,0) (1,1) (1,1) (1,0)     South (1,1) (0,1) (0,1) (1,1)
+ *   West (0,1) (0,0) (0,0) (0,1)                NwSe  (0,0) (1,1) (1,1) (0,0)     NeSw (1,0) (0,1) (0,1) (1,0)
+ * b32_room_create copies n records (n == 0 is legal, faces may then be NULL); kind > 7 -> B32_E_ARG, n > 2^24 -> B32_E_UNSUPPORTED (ordinals
+ * are 4 * record + k); numbers are not validated.  b32_room_update is a height drag: records [first, first + count) are replaced and,
+ * when grid is not NULL, the grid too; the data is copied before return and ordered on the context's stream like a slot upload, so a
+ * hover enqueued behind it sees it.  first + count > n or a kind > 7 -> B32_E_ARG (nothing is changed).  b32_room_destroy waits for the
+ * stream.
+ *
+ * b32_room_hover evaluates ALL THREE loops for the cursor and reports each raw.  Projection is world_to_screen_with_depth
+ * (math.rs:621-652), perspective only; the framebuffer size is the context's, a band is ignored.  A record's four corners are projected
+ * once and feed all three branches (the reference projects the same corner with the same function in each loop).
+ *   vertices, ordinal 4 * rec + k: the corner projects; dist = sqrt((mx-sx)*(mx-sx) + (my-sy)*(my-sy)); candidate when
+ *       dist < vertex_threshold; its depth is the corner's camera depth.
+ *   edges (k, (k + 1) % 4), ordinal 4 * rec + k: both ends project; dist = point_to_segment_distance (math.rs:655-683; len_sq < 1e-6 -> the
+ *       distance to the first end; t.clamp(0.0, 1.0) keeps a NaN) in the edge's own orientation; candidate when dist < edge_threshold;
+ *       depth = interpolate_edge_depth (viewport_3d.rs:7411-7431: len_sq < 0.0001 -> (d0 + d1) * 0.5, else d0 + t * (d1 - d0)).
+ *   faces, ordinal rec: check_quad_hit_with_depth (:7436-7481): all four corners project; triangle (0,1,2), and only when it misses
+ *       (0,2,3); point_in_triangle_2d and interpolate_depth_in_triangle as in b32_pick_meshes, no culling.
+ * In every loop a candidate is kept when there is none yet or its depth is strictly smaller: the SMALLEST DEPTH wins, not the smallest
+ * distance; ties go to the first in loop order, with its own bits; a NaN depth sticks when it comes first and is ignored after a number;
+ * it is reported as 0x7FC00000.  "None": indices 0xFFFFFFFF, floats 0.
+ * b32_room_hover_winner is the reference's answer (:7283-7336), a pure host function: 0 vertex, 1 edge, 2 face, -1 nothing.  The
+ * candidates (depth, type) are sorted by depth, tolerance = closest * 0.01, the lowest type among those with |d - closest| < tolerance
+ * wins, else the closest one's type (a tolerance <= 0 -- a closest depth <= 0 -- selects nobody, so the closest wins).  With a NaN among
+ * the depths the reference's result depends on its standard library's sort; here the sort is a stable insertion sort in which a NaN
+ * compares equal to everything (partial_cmp(..).unwrap_or(Equal)), so a NaN stays where it was pushed relative to its neighbours.
+ * Like a pick, the work is enqueued on the context's stream behind the room's uploads, touches neither framebuffer nor z-buffer, flushes
+ * no clear and settles no frame; the asynchronous form performs no host synchronisation and delivers 48 bytes through the tickets of
+ * b32_fb_download_async.  NULL context, camera, room, params or out, a zero-size framebuffer -> B32_E_ARG.
+ *
+ * b32_room_box_select is find_selections_in_rect for the rectangle (x0, y0, x1, y1).  Element i is record i for i < n, then point i - n of
+ * points_xyz (the room's object positions, :7584-7591; nullable with n_points == 0).  A record's centre (face_center_in_rect /
+ * wall_center_in_rect, :7597-7655): avg = (((h0 + h1) + h2) + h3) / 4.0; floor and ceiling (bx + S / 2.0, position[1] + avg, bz + S / 2.0);
+ * walls ((x0 + x1) / 2.0, position[1] + avg, (z0 + z1) / 2.0) with that function's own (x0, z0, x1, z1) per direction.  The centre is
+ * projected by world_to_screen (math.rs:503-534) and selected when sx >= x0 && sx <= x1 && sy >= y0 && sy <= y1 (inclusive; any NaN is
+ * false).  The result has b32_box_select's layout: {uint32 n_elements; uint32 n_selected; 8 bytes of padding}, then ceil(n_elements / 32)
+ * words.  n + n_points >= 2^32 -> B32_E_UNSUPPORTED. */
+typedef struct b32_room b32_room;
+typedef struct B32SectorFace {
+    uint16_t gx, gz;                          /* the sector on the room's grid */
+    uint8_t  kind;                            /* 0 Floor, 1 Ceiling, 2 WallNorth, 3 WallEast, 4 WallSouth, 5 WallWest, 6 WallNwSe, 7 WallNeSw */
+    uint8_t  index;                           /* the i of SectorFace::Wall*(i); 0 for floor and ceiling */
+    uint16_t _pad;
+    float    heights[4];
+} B32SectorFace;                              /* 24 bytes */
+typedef struct B32RoomGrid { float position[3]; float sector_size; } B32RoomGrid;   /* Room::position; SECTOR_SIZE = 1024.0 */
+#define B32_SECTOR_SIZE 1024.0f
+#define B32_ROOM_MAX_FACES (1u << 24)
+typedef struct B32RoomHoverParams { float mx, my, vertex_threshold, edge_threshold; } B32RoomHoverParams;   /* the reference's: 6.0, 4.0 */
+typedef struct B32RoomHover {
+    uint32_t vertex_rec, vertex_corner; float vertex_dist, vertex_depth;
+    uint32_t edge_rec,   edge_idx;      float edge_dist,   edge_depth;
+    uint32_t face_rec;                  float face_depth;
+    uint32_t _pad[2];
+} B32RoomHover;                               /* 48 bytes; none: indices 0xFFFFFFFF, floats 0 */
+int  b32_room_create(b32_ctx* ctx, const B32RoomGrid* grid, const B32SectorFace* faces, uint32_t n, b32_room** out);
+int  b32_room_update(b32_ctx* ctx, b32_room* room, const B32RoomGrid* grid /* nullable */, uint32_t first, uint32_t count, const B32SectorFace* faces);
+void b32_room_destroy(b32_ctx* ctx, b32_room* room);
+int  b32_room_hover(b32_ctx* ctx, const B32Camera* camera, b32_room* room, const B32RoomHoverParams* params, B32RoomHover* out);
+int  b32_room_hover_async(b32_ctx* ctx, const B32Camera* camera, b32_room* room, const B32RoomHoverParams* params, void* out /* 48 bytes */,
+                          uint64_t* ticket);
+int  b32_room_hover_winner(const B32RoomHover* hover);
+int  b32_room_box_select(b32_ctx* ctx, const B32Camera* camera, b32_room* room, float x0, float y0, float x1, float y1,
+                         const float* points_xyz /* 3 * n_points, nullable */, uint32_t n_points,
+                         uint32_t* words /* ceil((n + n_points) / 32), nullable */, uint32_t* n_selected);
+int  b32_room_box_select_async(b32_ctx* ctx, const B32Camera* camera, b32_room* room, float x0, float y0, float x1, float y1,
+                               const float* points_xyz /* 3 * n_points, nullable */, uint32_t n_points,
+                               void* out /* 16 + 4 * ceil((n + n_points) / 32) bytes */, uint64_t* ticket);
+
 /* ---- the 8-bit-colour path: render_mesh (render.rs:1971-2264) + rasterize_triangle (render.rs:1202-1433) ----
  * What every caller of the reference runs when settings.use_rgb555 is false (scene.rs:163-169).  Same pipeline and settings
  * as render_mesh_15 except: Texture texels are Color values with a per-texel blend mode, no fog, no opaque/transparent
