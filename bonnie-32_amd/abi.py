@@ -67,6 +67,22 @@ GIZMO_MAX_THICKNESS = 16
 # the third point's x and y are the bit patterns of z0 and z1
 PRIM_TRIANGLE_INTERNAL = 11
 
+# B32MeshOverlay (the modeler's selection overlays from resident vertices, b32_draw_mesh_overlay): sections = OVERLAY_* bits
+OVERLAY_BRACKETS, OVERLAY_EDGES, OVERLAY_DOTS, OVERLAY_HOVER, OVERLAY_SELECTED, OVERLAY_PREVIEW = 1, 2, 4, 8, 16, 32
+OVERLAY_ALL = 63
+OVERLAY_NONE = 0xFFFFFFFF
+SELECT_NONE, SELECT_VERTICES, SELECT_EDGES, SELECT_POLYGONS = range(4)
+PREVIEW_VERTEX, PREVIEW_EDGE, PREVIEW_FACE = range(3)
+
+
+class B32MeshOverlay(C.Structure):
+    _fields_ = [("sections", C.c_uint32), ("hover_vertex", C.c_uint32), ("hover_edge_v0", C.c_uint32), ("hover_edge_v1", C.c_uint32),
+                ("hover_face", C.c_uint32), ("select_kind", C.c_uint32), ("n_selected", C.c_uint32), ("preview_mode", C.c_uint32),
+                ("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
+
+
+assert C.sizeof(B32MeshOverlay) == 48
+
 # B32PickHit (b32_pick_meshes): hit == 0 -> tri = 0xFFFFFFFF, depth = 0
 PICK_HIT_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("depth", "<f4"), ("_pad", "<u4")])
 assert PICK_HIT_DTYPE.itemsize == 16
@@ -237,6 +253,9 @@ SYMBOLS = [
     ("b32_gizmo_project_batch", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_gizmo_counts", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("b32_octahedron_items", C.c_int, [_P, C.c_float, _P, _P]),
+    ("b32_draw_mesh_overlay", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("b32_mesh_overlay_project_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_mesh_overlay_record_count", C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32)]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

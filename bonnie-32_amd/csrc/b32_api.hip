@@ -1,6 +1,7 @@
 // b32_api.hip -- the C ABI of include/b32raster.h, part 1: context, stream, device-resident framebuffer, test taps and switches.
 // (Scene uploads: b32_scene.hip; frames: b32_frame.hip; batched frames: b32_batch.hip; shared declarations: b32_host.h.)
 #include "b32_host.h"
+#include "b32_overlay_body.h"
 
 extern "C" {
 
@@ -73,6 +74,9 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : c->hover_tev) if (e) (void)hipEventDestroy(e);
     if (c->room_words) (void)hipFree(c->room_words);
     if (c->room_points) (void)hipFree(c->room_points);
+    c->overlay_sel.release();
+    if (c->overlay_tab) (void)hipFree(c->overlay_tab);
+    if (c->overlay_bounds) (void)hipFree(c->overlay_bounds);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->stage_host) (void)hipHostFree(c->stage_host);
     for (hipEvent_t e : c->dl_ev) if (e) (void)hipEventDestroy(e);
@@ -393,6 +397,75 @@ static int gizmo_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, u
     return rc;
 }
 
+// ------------------------------------------------------------------ the modeler's selection overlays (b32_overlay.hip)
+// Everything checked and laid out before anything is enqueued: the kernels' arguments but for the device buffers the caller provides
+// (w.out, tab, selected), the list to upload (*up / *n_up words: the list as given, or c->overlay_pairs for polygons), the record total.
+static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const b32_scene* slot, const b32_topology* topo,
+                           const B32MeshOverlay* o, const uint32_t* selected, uint32_t w, uint32_t h, OverlayArgs& a, const uint32_t** up,
+                           uint32_t* n_up, uint64_t* total) {
+    if (!c || !cam || !slot || !o || !w || !h || !slot->have_scene) return B32_E_ARG;
+    { const int rc = overlay_check(topo != nullptr, o, selected); if (rc) return rc; }
+    const uint32_t np = topo ? topo->np : 0u, nh = topo ? topo->nh : 0u;
+    const OverlayLayout l = overlay_layout(topo ? topo->h_poly_start.data() : nullptr, np, nh, topo ? topo->ne : 0u, slot->nv, *o, selected);
+    *total = l.total;
+    if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+    a = OverlayArgs{};
+    int rc;
+    (void)hipSetDevice(c->device);
+    if ((rc = world_args(c, cam, ortho, w, h, 0u, a.w))) return rc;
+    a.w.counts = nullptr;
+    const bool packed = slot->pos_valid && slot->d_pos12;
+    a.pos = packed ? slot->d_pos12 : reinterpret_cast<const float*>(slot->d_verts);
+    a.stride = packed ? 3u : (uint32_t)(sizeof(B32Vertex) / sizeof(float));
+    a.nv = slot->nv;
+    if (topo) { a.he = topo->he; a.poly_start = topo->poly_start; a.poly_verts = topo->poly_verts; a.np = np; a.nh = nh; }
+    a.o = *o;
+    a.at_brackets = (uint32_t)l.brackets; a.at_edges = (uint32_t)l.edges; a.at_dots = (uint32_t)l.dots;
+    a.at_hover_vertex = (uint32_t)l.hover_vertex; a.at_hover_edge = (uint32_t)l.hover_edge; a.at_hover_face = (uint32_t)l.hover_face;
+    a.at_selected = (uint32_t)l.selected; a.at_preview = (uint32_t)l.preview;
+    a.hover_face_cnt = l.hover_face_cnt;
+    *up = nullptr; *n_up = 0u;
+    const uint32_t sec = o->sections;
+    const auto groups = [](uint32_t n) { return (uint32_t)(((unsigned long long)n + 255u) / 256u); };
+    if (sec & B32_OVERLAY_EDGES) a.g_edges = groups(nh);
+    if ((sec & B32_OVERLAY_PREVIEW) && o->preview_mode == 1u) a.g_pedges = groups(nh);
+    if ((sec & B32_OVERLAY_PREVIEW) && o->preview_mode == 2u) a.g_pfaces = groups(np);
+    if ((sec & B32_OVERLAY_SELECTED) && o->select_kind && o->n_selected) {
+        if (o->select_kind == 3u) {                                                   // (polygon, first record) pairs of the polygons that exist
+            c->overlay_pairs.clear();
+            uint64_t at = l.selected;
+            for (uint32_t i = 0; i < o->n_selected; ++i) {
+                const uint32_t p = selected[i];
+                if (p >= np) continue;
+                c->overlay_pairs.push_back(p); c->overlay_pairs.push_back((uint32_t)at);
+                at += overlay_polygon_slots(OVERLAY_POLY_SELECTED, topo->h_poly_start[p + 1u] - topo->h_poly_start[p]);
+            }
+            a.n_sel = (uint32_t)(c->overlay_pairs.size() / 2u);
+            *up = c->overlay_pairs.data(); *n_up = (uint32_t)c->overlay_pairs.size();
+        } else {
+            if (o->select_kind == 2u && o->n_selected > 0x7FFFFFFFu) return B32_E_UNSUPPORTED;
+            a.n_sel = o->n_selected;
+            *up = selected; *n_up = o->select_kind == 2u ? 2u * o->n_selected : o->n_selected;
+        }
+        a.g_sel = groups(a.n_sel);
+    }
+    if ((sec & B32_OVERLAY_HOVER) && (o->hover_vertex != OVERLAY_NONE || o->hover_edge_v0 != OVERLAY_NONE || o->hover_edge_v1 != OVERLAY_NONE || l.hover_face_cnt))
+        a.g_hover = 1u;
+    if ((sec & B32_OVERLAY_BRACKETS) && slot->nv) a.g_brackets = 1u;
+    if ((unsigned long long)a.g_edges + a.g_pedges + a.g_sel + a.g_pfaces + 2u >= (1ull << 31)) return B32_E_UNSUPPORTED;
+    return B32_OK;
+}
+// the bounds' keys: armed whenever no overlay is running (allocated so; k_overlay_emit leaves them so)
+static int overlay_bounds(b32_ctx* c, OverlayArgs& a) {
+    if (!c->overlay_bounds) {
+        static const OverlayBounds armed = overlay_bounds_start();
+        HIPCHK(c, hipMalloc(&c->overlay_bounds, sizeof(OverlayBounds)));
+        HIPCHK(c, hipMemcpyAsync(c->overlay_bounds, &armed, sizeof(OverlayBounds), hipMemcpyHostToDevice, c->stream));
+    }
+    a.bounds = static_cast<OverlayBounds*>(c->overlay_bounds);
+    return B32_OK;
+}
+
 extern "C" {
 
 // The line family of Framebuffer (render.rs:684-872), b32_lines.hip.
@@ -553,6 +626,54 @@ int b32_gizmo_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* r
     if (c->gizmo_counts) HIPCHK(c, hipMemcpyAsync(h, c->gizmo_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
+    return B32_OK;
+}
+// The modeler's selection overlays (modeler/viewport.rs:1782-2247): made into records by k_overlay_points / k_overlay_emit in the primitive
+// pass's device record buffer, from the slot's vertices as they are on the device; binned and drawn from there like any other primitive batch.
+int b32_draw_mesh_overlay(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_scene* slot, b32_topology* topo, const B32MeshOverlay* o,
+                          const uint32_t* selected) {
+    if (!c || !c->fb) return B32_E_ARG;
+    OverlayArgs a; const uint32_t* up = nullptr; uint32_t n_up = 0; uint64_t total = 0;
+    int rc;
+    if ((rc = overlay_prepare(c, cam, ortho, slot, topo, o, selected, c->width, c->height, a, &up, &n_up, &total))) return rc;
+    if (!total) return B32_OK;
+    if ((rc = draw_enter(c))) return rc;
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)total))) return rc;
+    if ((rc = ensure(c, c->overlay_tab, c->overlay_cap_tab, (size_t)a.nv))) return rc;
+    if ((rc = overlay_bounds(c, a))) return rc;
+    a.w.out = c->prims.dev; a.tab = reinterpret_cast<OverlayPoint*>(c->overlay_tab);
+    if (n_up) {
+        if ((rc = stage_records(c, c->overlay_sel, up, n_up))) return rc;
+        a.selected = c->overlay_sel.dev;
+    }
+    launch_overlay(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    DrawArgs<B32Prim> d = draw_args<B32Prim>(c, (uint32_t)total);
+    d.recs = c->prims.dev;
+    return draw_resident(c, c->prims, d, total > PRIM_SMALL, B32_ROUTE_PRIM_TILES);
+}
+int b32_mesh_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_scene* slot, b32_topology* topo,
+                                   const B32MeshOverlay* o, const uint32_t* selected, uint32_t w, uint32_t h, B32Prim* out, uint32_t cap,
+                                   uint32_t* n_records) {
+    if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
+    OverlayArgs a; const uint32_t* up = nullptr; uint32_t n_up = 0; uint64_t total = 0;
+    int rc;
+    if ((rc = overlay_prepare(c, cam, ortho, slot, topo, o, selected, w, h, a, &up, &n_up, &total))) return rc;
+    if (total > cap || (total && !out)) return B32_E_ARG;
+    *n_records = (uint32_t)total;
+    if (!total) return B32_OK;
+    B32Prim* d_out = nullptr; OverlayPoint* d_tab = nullptr; uint32_t* d_sel = nullptr;
+    Scratch tmp(c);
+    if ((rc = tmp.alloc(&d_out, (size_t)total))) return rc;
+    if ((rc = tmp.alloc(&d_tab, (size_t)a.nv))) return rc;
+    if (n_up && (rc = tmp.upload(up, (size_t)n_up, &d_sel))) return rc;
+    if ((rc = overlay_bounds(c, a))) return rc;
+    a.w.out = d_out; a.tab = d_tab; a.selected = d_sel;
+    launch_overlay(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return B32_OK;
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {

@@ -536,6 +536,26 @@ struct PickItem {
     float cos_f, sin_f, wpos[3];
     uint32_t first_wg, _pad;                    // the item's workgroups are [first_wg, first_wg + ceil(nf / PICK_CHUNK))
 };   // small != nullptr: n <= WORLD_SMALL items passed by value
+// The modeler's polygons on the device (b32_topology, b32_hover.hip): per polygon position one half-edge, and the fan triangles.
+struct HoverHalfEdge { uint32_t v0, v1, edge, first; };     // (v[k], v[(k + 1) % n]), the id of the normalised edge (min, max), and -- for the
+                                                            // first half-edge of its edge in loop order -- 1 + how many edges began before it (else 0)
+struct HoverFanTri { uint32_t v[3], poly; };                // (v[0], v[k], v[k + 1]) and its polygon
+// The modeler's selection overlays made into B32Prim records on the device (b32_draw_mesh_overlay, b32_overlay.hip): where a record lies
+// is decided by the host (overlay_layout, b32_overlay_body.h), the kernels fill the places.  w.out: the records; w.items / n / counts unused.
+struct OverlayPoint; struct OverlayBounds;
+struct OverlayArgs {
+    WorldArgs w;
+    const float* pos; uint32_t stride, nv;      // the slot's positions as they are: `stride` floats between two vertices
+    const HoverHalfEdge* he; const uint32_t* poly_start; const uint32_t* poly_verts; uint32_t np, nh;
+    OverlayPoint* tab;                          // nv projected vertices (k_overlay_points writes, k_overlay_emit reads)
+    OverlayBounds* bounds;                      // armed between two calls (k_overlay_emit's last workgroup leaves it so)
+    const uint32_t* selected; uint32_t n_sel;   // the list as given; polygons: n_sel (polygon, first record) pairs
+    B32MeshOverlay o;
+    uint32_t at_brackets, at_edges, at_dots, at_hover_vertex, at_hover_edge, at_hover_face, at_selected, at_preview;   // first record of each
+    uint32_t hover_face_cnt;                    // positions of the hovered polygon; 0: no polygon to walk
+    uint32_t g_edges, g_pedges, g_sel, g_pfaces, g_hover, g_brackets;     // workgroups of k_overlay_emit's ranges, in this order
+};
+void launch_overlay(hipStream_t s, const OverlayArgs& a);
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

@@ -119,6 +119,16 @@ struct b32_scene {
     }
 };
 
+// The modeler's polygons over a slot's vertices (b32_topology_create, b32_hover.hip).
+struct b32_topology {
+    b32::HoverHalfEdge* he = nullptr;           // nh half-edges in loop order (half-edge h sits at position h of poly_verts)
+    b32::HoverFanTri* fan = nullptr;            // nt fan triangles in loop order
+    uint32_t* poly_start = nullptr;             // np + 1
+    uint32_t* poly_verts = nullptr;             // nh
+    uint32_t np = 0, nh = 0, nt = 0, ne = 0;    // polygons, half-edges, fan triangles, distinct normalised edges
+    std::vector<uint32_t> h_poly_start;         // np + 1 on the host: where the overlay's records lie (overlay_layout)
+};
+
 struct b32_ctx {
     int device = 0;
     int n_cu = 256;
@@ -259,6 +269,11 @@ struct b32_ctx {
     // the device copy of a box selection's points.  Results leave through the pick's ring of result buffers.
     void* room_words = nullptr;
     float* room_points = nullptr; size_t room_cap_points = 0;
+    // b32_draw_mesh_overlay (b32_overlay.hip): the projected vertices of the call being enqueued, the bounds' keys (armed between two
+    // calls), the selected list's pinned ring and device copy (the staging half of DrawPassState, as `world`)
+    uint4* overlay_tab = nullptr; size_t overlay_cap_tab = 0;     // (16 bytes per vertex: OverlayPoint)
+    void* overlay_bounds = nullptr;
+    DrawPassState<uint32_t> overlay_sel; std::vector<uint32_t> overlay_pairs;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only

@@ -23,19 +23,6 @@
 #include "b32_pick_body.h"
 
 namespace b32 {
-struct HoverHalfEdge { uint32_t v0, v1, edge, _pad; };      // (v[k], v[(k + 1) % n]) and the id of the normalised edge (min, max)
-struct HoverFanTri { uint32_t v[3], poly; };                // (v[0], v[k], v[k + 1]) and its polygon
-}  // namespace b32
-
-struct b32_topology {
-    b32::HoverHalfEdge* he = nullptr;           // nh half-edges in loop order (half-edge h sits at position h of poly_verts)
-    b32::HoverFanTri* fan = nullptr;            // nt fan triangles in loop order
-    uint32_t* poly_start = nullptr;             // np + 1
-    uint32_t* poly_verts = nullptr;             // nh
-    uint32_t np = 0, nh = 0, nt = 0, ne = 0;    // polygons, half-edges, fan triangles, distinct normalised edges
-};
-
-namespace b32 {
 
 constexpr size_t BOX_HEADER = 16;               // {uint32 n_elements; uint32 n_selected; 8 bytes of padding} in front of the words
 
@@ -311,10 +298,16 @@ int b32_topology_create(b32_ctx* c, const uint32_t* poly_start, uint32_t np, con
         he[keys[j].second].edge = ne;
     }
     if (nh) ++ne;
+    {   // the first half-edge of every edge in loop order (draw_box_selection_preview's HashSet, b32_overlay.hip)
+        std::vector<uint8_t> seen(ne, 0);
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < nh; ++j) if (!seen[he[j].edge]) { seen[he[j].edge] = 1; he[j].first = ++rank; }
+    }
     if (fan.size() >= 0xFFFFFFFFull) return B32_E_UNSUPPORTED;
 
     b32_topology* t = new b32_topology();
     t->np = np; t->nh = nh; t->nt = (uint32_t)fan.size(); t->ne = ne;
+    if (np) t->h_poly_start.assign(poly_start, poly_start + (size_t)np + 1u); else t->h_poly_start.assign(1, 0u);
     const uint32_t zero = 0u;
     hipError_t e = hipSuccess;
     const auto up = [&](void** dst, const void* src, size_t bytes) {

@@ -652,6 +652,35 @@ inline BoxSelection box_select(Framebuffer& fb, const ResidentMesh& mesh, const 
                          r.words.data(), &r.n_selected), "box_select");
     return r;
 }
+// The modeler's selection overlays (modeler/viewport.rs:1782-2247: draw_selected_object_brackets, draw_mesh_selection_overlays,
+// draw_box_selection_preview) made into records on the device from the mesh's resident vertices, posed or not, and drawn in the reference's
+// order (b32_draw_mesh_overlay): enqueued, nothing read back.  The hovered element is a masked hover result (hovered_element), the
+// selection one of the three lists, the preview its SelectMode and rectangle; the preview of an orthographic viewport is a second call
+// with that viewport's camera and ortho.
+struct MeshOverlay {
+    uint32_t sections = 0;                                                     // B32_OVERLAY_* bits
+    HoveredElement hover;
+    uint32_t select_kind = 0;                                                  // 0 none, 1 vertices, 2 edges, 3 polygons
+    std::vector<uint32_t> selected;                                            // indices; edges: (v0, v1) pairs one after another
+    uint32_t preview_mode = 0; float x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    B32MeshOverlay pack() const {
+        B32MeshOverlay o{};
+        o.sections = sections;
+        o.hover_vertex = hover.vertex.value_or(0xFFFFFFFFu);
+        o.hover_edge_v0 = hover.edge ? hover.edge->first : 0xFFFFFFFFu; o.hover_edge_v1 = hover.edge ? hover.edge->second : 0xFFFFFFFFu;
+        o.hover_face = hover.face.value_or(0xFFFFFFFFu);
+        o.select_kind = select_kind; o.n_selected = (uint32_t)(select_kind == 2u ? selected.size() / 2 : selected.size());
+        o.preview_mode = preview_mode; o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
+        return o;
+    }
+};
+inline void draw_mesh_overlay(Framebuffer& fb, const ResidentMesh& mesh, const Topology* top, const MeshOverlay& overlay, const Camera& camera,
+                              const std::optional<Vec3>& ortho = std::nullopt) {
+    const detail::MeshCall c(camera, ortho, std::nullopt);
+    const B32MeshOverlay o = overlay.pack();
+    check(b32_draw_mesh_overlay(fb.ctx(), &c.cam, c.has_ortho ? &c.ortho : nullptr, mesh.slot(), top ? top->handle() : nullptr, &o,
+                                overlay.selected.empty() ? nullptr : overlay.selected.data()), "draw_mesh_overlay");
+}
 // Room hover and box selection: the world editor's find_hovered_elements (editor/viewport_3d.rs:7028-7336, the three sector loops and the
 // priority rule) and find_selections_in_rect (:7512-7594) for the current room, on the device (b32_room_hover, b32_room_box_select).  A Room
 // holds the grid and one B32SectorFace per sector face in iter_sectors order (world/geometry.rs:2828-2835: gx outer, gz inner; floor,

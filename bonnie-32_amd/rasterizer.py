@@ -393,6 +393,15 @@ class Topology:
         self.fan_poly = fan_poly
         self._handles = []
 
+    def first_half_edges(self):
+        """Per half-edge: 1 + how many edges began before it when it is the first half-edge of its normalised edge in loop order, else 0
+        (what b32_topology_create derives for the edge preview of b32_draw_mesh_overlay)."""
+        first = np.zeros(len(self.poly_verts), np.int64)
+        if self.ne:
+            _, idx = np.unique(self.he_edge, return_index=True)
+            first[np.sort(idx)] = np.arange(1, self.ne + 1)
+        return first
+
     @classmethod
     def from_polygons(cls, polygons):
         """polygons: a list of vertex-index lists."""
@@ -1264,6 +1273,14 @@ class Context:
         """b32_set_pipeline_depth: 2 or 3 frame sets -- the setup kernel one or two frames ahead of the fill (include/b32raster.h)."""
         _chk(self.lib.b32_set_pipeline_depth(self.h, int(sets)), "b32_set_pipeline_depth")
 
+    def mesh_overlay_record_count(self, topology, nv, overlay, selected=None):
+        """b32_mesh_overlay_record_count (host only; the topology's device object is only read for its host copy of poly_start)."""
+        o, sel = overlay.pack(selected)
+        n = C.c_uint32()
+        _chk(self.lib.b32_mesh_overlay_record_count(topology.handle(self) if topology is not None else None, nv, C.byref(o),
+                                                    abi.ptr(sel) if len(sel) else None, C.byref(n)), "mesh_overlay_record_count")
+        return int(n.value)
+
     def gizmo_project_batch(self, items, camera: T.Camera, ortho, width, height):
         """b32_gizmo_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_gizmos hands to the tile pass for a width x height
         framebuffer -- one per item, `size` of them for a thick line of thickness > 1 -- in item order; synchronous."""
@@ -1599,6 +1616,30 @@ class Framebuffer:
         _chk(self.ctx.lib.b32_gizmo_counts(self.ctx.h, *[C.byref(x) for x in v]), "gizmo_counts")
         return tuple(int(x.value) for x in v)
 
+    # ---- the modeler's selection overlays from a slot's resident vertices (modeler/viewport.rs:1782-2247): b32_draw_mesh_overlay
+    def _overlay_args(self, scene, topology, overlay, camera, ortho, selected):
+        cam = camera.pack()
+        o = _pack_ortho(ortho)
+        ov, sel = overlay.pack(selected)
+        top = topology.handle(self.ctx) if topology is not None else None
+        return (self.ctx.h, C.byref(cam), C.byref(o) if o is not None else None, scene._slot, top, C.byref(ov), abi.ptr(sel) if len(sel) else None), (cam, o, ov, sel)
+
+    def draw_mesh_overlay(self, scene, topology, overlay, camera: T.Camera, ortho=None, selected=None):
+        """b32_draw_mesh_overlay: the sections of `overlay` (a MeshOverlay) made into records on the device from the vertices of `scene` (a
+        detached ResidentScene, posed or not) and drawn in the reference's order; enqueued, no host synchronisation, nothing read back."""
+        args, _keep = self._overlay_args(scene, topology, overlay, camera, ortho, selected)
+        _chk(self.ctx.lib.b32_draw_mesh_overlay(*args), "draw_mesh_overlay")
+
+    def mesh_overlay_project_batch(self, scene, topology, overlay, camera: T.Camera, ortho=None, selected=None, width=None, height=None):
+        """b32_mesh_overlay_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_mesh_overlay hands to the tile pass."""
+        n = mesh_overlay_record_count(topology, scene.n_vertices, overlay, selected)
+        out = np.zeros(n, abi.PRIM_DTYPE)
+        got = C.c_uint32()
+        args, _keep = self._overlay_args(scene, topology, overlay, camera, ortho, selected)
+        _chk(self.ctx.lib.b32_mesh_overlay_project_batch(*args, width or self.width, height or self.height, abi.ptr(out) if n else None, n,
+                                                         C.byref(got)), "mesh_overlay_project_batch")
+        return out[:int(got.value)]
+
     def present_nearest(self, dst_w, dst_h):
         """The presenter's nearest-neighbour upscale (game/renderer.rs:179-214) -> uint8 [dst_h, dst_w, 4]."""
         out = np.empty((dst_h, dst_w, 4), np.uint8)
@@ -1870,6 +1911,340 @@ class GizmoBatch:
 
 
 _ZERO3 = (0.0, 0.0, 0.0)
+
+
+# ---- the modeler's selection overlays (modeler/viewport.rs:1782-2247) from vertex positions: b32_draw_mesh_overlay and its mirror
+class MeshOverlay:
+    """B32MeshOverlay: which sections to draw (abi.OVERLAY_* bits), the hovered element (a masked hover result: None = none), the kind of
+    the selection (abi.SELECT_*; the list itself travels beside the struct), the preview's mode (abi.PREVIEW_*) and rectangle."""
+
+    def __init__(self, sections=0, hover_vertex=None, hover_edge=None, hover_face=None, select_kind=abi.SELECT_NONE, preview_mode=abi.PREVIEW_VERTEX,
+                 rect=(0.0, 0.0, 0.0, 0.0)):
+        self.sections, self.select_kind, self.preview_mode, self.rect = sections, select_kind, preview_mode, tuple(rect)
+        self.hover_vertex = abi.OVERLAY_NONE if hover_vertex is None else int(hover_vertex)
+        self.hover_edge = (abi.OVERLAY_NONE, abi.OVERLAY_NONE) if hover_edge is None else (int(hover_edge[0]), int(hover_edge[1]))
+        self.hover_face = abi.OVERLAY_NONE if hover_face is None else int(hover_face)
+
+    def selected_list(self, selected):
+        """The list as the C entry takes it: a flat uint32 array (pairs flattened) and n_selected."""
+        sel = np.ascontiguousarray(selected if selected is not None else [], np.uint32).reshape(-1)
+        return sel, (len(sel) // 2 if self.select_kind == abi.SELECT_EDGES else len(sel))
+
+    def pack(self, selected=None):
+        sel, n = self.selected_list(selected)
+        return abi.B32MeshOverlay(self.sections, self.hover_vertex, self.hover_edge[0], self.hover_edge[1], self.hover_face, self.select_kind, n,
+                                  self.preview_mode, *[float(v) for v in self.rect]), sel
+
+
+OVERLAY_COLORS = {"brackets": (0, 200, 230), "edges": (80, 80, 80), "dots": (40, 40, 50), "hover": (255, 200, 150), "selected": (100, 180, 255),
+                  "preview": (255, 220, 100)}
+
+
+def _poly_slots(mode, cnt):
+    """Records of a polygon of cnt positions: hovered (0), selected (1), previewed (2)."""
+    cnt = np.asarray(cnt, np.int64)
+    return cnt + (cnt >= 4) if mode == 0 else (2 * cnt + 1 if mode == 1 else cnt + 1)
+
+
+def mesh_overlay_layout(topology, nv, overlay, selected=None):
+    """First record of every part, and the total: {"brackets", "edges", "dots", "hover_vertex", "hover_edge", "hover_face", "selected",
+    "preview", "total"} -- a function of the topology, nv, the struct and the list alone (overlay_layout, b32_overlay_body.h)."""
+    o = overlay
+    sel, n_sel = o.selected_list(selected)
+    if (o.sections & ~abi.OVERLAY_ALL) or o.select_kind > 3 or o.preview_mode > 2:
+        raise ValueError("MeshOverlay: unknown section bit, select_kind or preview_mode")
+    polygons = (o.sections & abi.OVERLAY_EDGES) or ((o.sections & abi.OVERLAY_HOVER) and o.hover_face != abi.OVERLAY_NONE) or \
+        ((o.sections & abi.OVERLAY_SELECTED) and o.select_kind == abi.SELECT_POLYGONS and n_sel) or ((o.sections & abi.OVERLAY_PREVIEW) and o.preview_mode != 0)
+    if polygons and topology is None:
+        raise ValueError("MeshOverlay: a section that walks polygons needs a topology")
+    t = topology
+    np_, nh, ne = (t.np, len(t.poly_verts), t.ne) if t is not None else (0, 0, 0)
+    lay, at = {}, 0
+    lay["brackets"] = at
+    at += 24 if (o.sections & abi.OVERLAY_BRACKETS) and nv else 0
+    lay["edges"] = at
+    at += nh if o.sections & abi.OVERLAY_EDGES else 0
+    lay["dots"] = at
+    at += nv if o.sections & abi.OVERLAY_DOTS else 0
+    lay["hover_vertex"] = lay["hover_edge"] = lay["hover_face"] = at
+    if o.sections & abi.OVERLAY_HOVER:
+        at += 1 if o.hover_vertex != abi.OVERLAY_NONE else 0
+        lay["hover_edge"] = at
+        at += 3 if o.hover_edge != (abi.OVERLAY_NONE, abi.OVERLAY_NONE) else 0
+        lay["hover_face"] = at
+        if o.hover_face != abi.OVERLAY_NONE and o.hover_face < np_:
+            at += int(_poly_slots(0, t.count[o.hover_face]))
+    lay["selected"] = at
+    if o.sections & abi.OVERLAY_SELECTED:
+        if o.select_kind == abi.SELECT_VERTICES:
+            at += n_sel
+        elif o.select_kind == abi.SELECT_EDGES:
+            at += 4 * n_sel
+        elif o.select_kind == abi.SELECT_POLYGONS and n_sel:
+            at += int(_poly_slots(1, t.count[sel[sel < np_].astype(np.int64)]).sum())
+    lay["preview"] = at
+    if o.sections & abi.OVERLAY_PREVIEW:
+        at += nv if o.preview_mode == 0 else (2 * ne if o.preview_mode == 1 else nh + np_)
+    lay["total"] = at
+    return lay
+
+
+def mesh_overlay_record_count(topology, nv, overlay, selected=None):
+    """How many records b32_draw_mesh_overlay makes (b32_mesh_overlay_record_count): known before anything is projected."""
+    return mesh_overlay_layout(topology, nv, overlay, selected)["total"]
+
+
+def _ov_i32(f):
+    """Rust's `as i32` on an f32 array: NaN -> 0, saturating, truncation toward zero."""
+    f = np.asarray(f, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        r = np.where(np.isnan(f), 0.0, np.clip(np.trunc(f), -2147483648.0, 2147483647.0))
+    return r.astype(np.int64).astype(np.int32)
+
+
+def _ov_inc(v):
+    """`as i32 + 1` of a release build: wraps."""
+    return (v.astype(np.int64) + 1).astype(np.uint32).view(np.int32) if isinstance(v, np.ndarray) else _ov_inc(np.asarray([v], np.int32))[0]
+
+
+def _ov_depth(z):
+    z = np.asarray(z, np.float32).copy()
+    z[np.isnan(z)] = np.array([0x7FC00000], np.uint32).view(np.float32)[0]
+    return z
+
+
+def _ov_lines(out, idx, ok, kind, x0, y0, x1, y1, z0, z1, rgb, alpha=255):
+    """Line records at out[idx[ok]]; an extent that reaches 2^30 leaves the no-op."""
+    lim = 1 << 30
+    ok = ok & (np.abs(x1.astype(np.int64) - x0) < lim) & (np.abs(y1.astype(np.int64) - y0) < lim)
+    i = idx[ok]
+    for name, v in (("x0", x0), ("y0", y0), ("x1", x1), ("y1", y1)):
+        out[name][i] = v[ok]
+    depth = abi.LINE_3D <= kind <= abi.LINE_3D_ALPHA
+    out["z0"][i] = _ov_depth(z0[ok]) if depth else 0.0
+    out["z1"][i] = _ov_depth(z1[ok]) if depth else 0.0
+    out["size"][i] = 0
+    out["r"][i], out["g"][i], out["b"][i] = rgb
+    out["kind"][i], out["alpha"][i] = kind, alpha
+
+
+def _ov_circles(out, idx, ok, kind, sx, sy, radius, rgb, alpha=255):
+    """Circle records at out[idx[ok]]; a centre that reaches 2^30 leaves the no-op."""
+    lim = 1 << 30
+    x, y = _ov_i32(sx), _ov_i32(sy)
+    ok = ok & (np.abs(x.astype(np.int64)) < lim) & (np.abs(y.astype(np.int64)) < lim)
+    i = idx[ok]
+    out["x0"][i], out["y0"][i], out["size"][i] = x[ok], y[ok], radius
+    out["r"][i], out["g"][i], out["b"][i] = rgb
+    out["kind"][i], out["alpha"][i] = kind, alpha
+
+
+def _ov_segs(out, idx, ok, sx0, sy0, sx1, sy1, rgb, ox=False, oy=False):
+    x0, y0, x1, y1 = _ov_i32(sx0), _ov_i32(sy0), _ov_i32(sx1), _ov_i32(sy1)
+    if ox:
+        x0, x1 = _ov_inc(x0), _ov_inc(x1)
+    if oy:
+        y0, y1 = _ov_inc(y0), _ov_inc(y1)
+    zero = np.zeros(len(x0), np.float32)
+    _ov_lines(out, idx, ok, abi.LINE_2D, x0, y0, x1, y1, zero, zero, rgb)
+
+
+def _ov_inside(x, y, rect):
+    x0, y0, x1, y1 = (np.float32(v) for v in rect)
+    with np.errstate(invalid="ignore"):
+        return (x >= x0) & (x <= x1) & (y >= y0) & (y <= y1)
+
+
+def _ov_polygons(out, mode, polys, first, top, pos, nv, tab, project, rect, rgb):
+    """The polygons `polys` (all < np) into their records at out[first[i] ...], all polygons at once, one position of the loop at a time:
+    the streamed outline of overlay_polygon (b32_overlay_body.h) -- hovered (mode 0), selected (1), previewed (2)."""
+    f32 = np.float32
+    sx, sy, some = tab
+    polys = np.asarray(polys, np.int64)
+    first = np.asarray(first, np.int64)
+    m = len(polys)
+    if not m:
+        return
+    start, cnt = top.poly_start.astype(np.int64)[polys], top.count[polys]
+    pv = top.poly_verts.astype(np.int64)
+    acc = np.zeros((m, 3), f32)
+    count = np.zeros(m, np.int64)
+    go = np.ones(m, bool)
+    csx = csy = np.zeros(m, f32)
+    maxc = int(cnt.max()) if m else 0
+    if mode != 0:
+        for j in range(maxc):
+            act = j < cnt
+            vi = np.where(act, pv[np.minimum(start + j, len(pv) - 1)] if len(pv) else 0, nv)
+            ok = act & (vi < nv)
+            p = pos[np.where(ok, vi, 0)] if nv else np.zeros((m, 3), f32)
+            acc[ok] = acc[ok] + p[ok]
+            count += ok
+    if mode == 2:
+        with np.errstate(all="ignore"):
+            inv = f32(1.0) / count.astype(f32)
+            c = acc * inv[:, None]
+            csx, csy, _cz, csome = project(c[:, 0], c[:, 1], c[:, 2])
+        go = (count != 0) & csome & _ov_inside(csx, csy, rect)
+    n = np.zeros(m, np.int64)
+    k = np.zeros(m, np.int64)
+    pts = {name: [np.zeros(m, f32), np.zeros(m, f32)] for name in ("first", "third", "prev")}
+    for j in range(maxc):
+        act = go & (j < cnt)
+        vi = np.where(act, pv[np.minimum(start + j, len(pv) - 1)] if len(pv) else 0, nv)
+        ok = act & (vi < nv)
+        vc = np.where(ok, vi, 0)
+        ok = ok & (some[vc] if nv else False)
+        ex, ey = (sx[vc], sy[vc]) if nv else (np.zeros(m, f32), np.zeros(m, f32))
+        isfirst = ok & (n == 0)
+        emit = ok & (n > 0)
+        _ov_segs(out, first + k, emit, pts["prev"][0], pts["prev"][1], ex, ey, rgb)
+        k += emit
+        if mode == 1:
+            _ov_segs(out, first + k, emit, pts["prev"][0], pts["prev"][1], ex, ey, rgb, ox=True)
+            k += emit
+        for name, sel in (("first", isfirst), ("third", ok & (n == 2)), ("prev", ok)):
+            pts[name][0] = np.where(sel, ex, pts[name][0])
+            pts[name][1] = np.where(sel, ey, pts[name][1])
+        n += ok
+    done = n >= 3
+    # fewer than three projected vertices: what the walk wrote is taken back
+    back = ~done
+    for d in range(2):
+        i = (first + d)[back & (k > d)]
+        out[i] = noop_prims(len(i))
+    _ov_segs(out, first + k, done, pts["prev"][0], pts["prev"][1], pts["first"][0], pts["first"][1], rgb)
+    k += done
+    if mode == 1:
+        _ov_segs(out, first + k, done, pts["prev"][0], pts["prev"][1], pts["first"][0], pts["first"][1], rgb, ox=True)
+        k += done
+        with np.errstate(all="ignore"):
+            inv = f32(1.0) / n.astype(f32)                                              # n = screen_positions.len() (:2088)
+            c = acc * inv[:, None]
+            csx, csy, _cz, csome = project(c[:, 0], c[:, 1], c[:, 2])
+        _ov_circles(out, first + k, done & csome, abi.PRIM_CIRCLE, csx, csy, 4, rgb)
+    elif mode == 2:
+        _ov_circles(out, first + k, done, abi.PRIM_CIRCLE, csx, csy, 4, rgb)
+    else:
+        _ov_segs(out, first + k, n >= 4, pts["first"][0], pts["first"][1], pts["third"][0], pts["third"][1], rgb)
+
+
+def noop_prims(n):
+    """n records that draw nothing (a circle of radius -1): what a call the reference does not make leaves in its place."""
+    r = np.zeros(n, abi.PRIM_DTYPE)
+    r["kind"], r["size"] = abi.PRIM_CIRCLE, -1
+    return r
+
+
+def mesh_overlay_records(vertices, topology, overlay, selected, camera, w, h, ortho=None):
+    """The numpy / float32 mirror of b32_draw_mesh_overlay: the abi.PRIM_DTYPE records, place for place, that the device makes from
+    `vertices` (abi.VERTEX_DTYPE or (n, 3) positions, posed or not) -- draw_selected_object_brackets, draw_mesh_selection_overlays and
+    draw_box_selection_preview (modeler/viewport.rs:1782-2247) for the sections of `overlay`."""
+    f32 = np.float32
+    o, t = overlay, topology
+    pos = _positions(vertices)
+    nv = len(pos)
+    sel, n_sel = o.selected_list(selected)
+    lay = mesh_overlay_layout(t, nv, o, selected)
+    out = noop_prims(lay["total"])
+    col = OVERLAY_COLORS
+
+    def project(x, y, z):
+        with np.errstate(all="ignore"):
+            return _project_f32(np.asarray(x, f32), np.asarray(y, f32), np.asarray(z, f32), camera, w, h, ortho)
+
+    sx, sy, cz, some = project(pos[:, 0], pos[:, 1], pos[:, 2])
+    tab = (sx, sy, some)
+    allv = np.arange(nv, dtype=np.int64)
+
+    def ends(v0, v1):
+        """Both indices < nv and both ends projected; the indices clipped for the gathers."""
+        v0, v1 = np.asarray(v0, np.int64), np.asarray(v1, np.int64)
+        ok = (v0 < nv) & (v1 < nv)
+        a, b = np.where(ok, v0, 0), np.where(ok, v1, 0)
+        if nv:
+            ok = ok & some[a] & some[b]
+        return ok, a, b
+
+    if (o.sections & abi.OVERLAY_BRACKETS) and nv:
+        with np.errstate(all="ignore"):
+            mn, mx = np.empty(3, f32), np.empty(3, f32)
+            for c in range(3):
+                v = pos[:, c][~np.isnan(pos[:, c])]
+                lo = min(np.finfo(f32).max, v.min()) if len(v) else np.finfo(f32).max
+                hi = max(np.finfo(f32).min, v.max()) if len(v) else np.finfo(f32).min
+                mn[c] = (f32(lo) + f32(0.0)) - f32(4.0)                                 # (the sign of a zero disappears in the margin)
+                mx[c] = (f32(hi) + f32(0.0)) + f32(4.0)
+            size = mx - mn
+            blen = f32(min(min(size[0], size[1]), size[2]) if not np.isnan(size).any() else np.nanmin(size)) * f32(0.25)
+            ci, di = np.arange(24) // 3, np.arange(24) % 3
+            hi_ = np.stack([np.isin(ci, (1, 2, 5, 6)), ci >= 4, np.isin(ci, (2, 3, 6, 7))], 1)
+            corner = np.where(hi_, mx[None, :], mn[None, :]).astype(f32)
+            dirs = np.where(np.arange(3)[None, :] == di[:, None], np.where(hi_, f32(-1.0), f32(1.0)), f32(0.0)).astype(f32)
+            end = corner + dirs * blen
+            ax, ay, az, asome = project(corner[:, 0], corner[:, 1], corner[:, 2])
+            bx, by, bz, bsome = project(end[:, 0], end[:, 1], end[:, 2])
+        _ov_lines(out, lay["brackets"] + np.arange(24), asome & bsome, abi.LINE_3D, _ov_i32(ax), _ov_i32(ay), _ov_i32(bx), _ov_i32(by), az, bz, col["brackets"])
+
+    if o.sections & abi.OVERLAY_EDGES:
+        ok, a, b = ends(t.he_v0, t.he_v1)
+        if nv:
+            _ov_lines(out, lay["edges"] + np.arange(len(a)), ok, abi.LINE_3D_ALPHA, _ov_i32(sx[a]), _ov_i32(sy[a]), _ov_i32(sx[b]), _ov_i32(sy[b]),
+                      cz[a], cz[b], col["edges"], 191)
+    if o.sections & abi.OVERLAY_DOTS:
+        _ov_circles(out, lay["dots"] + allv, some, abi.PRIM_CIRCLE_ALPHA, sx, sy, 3, col["dots"], 140)
+
+    if o.sections & abi.OVERLAY_HOVER:
+        if o.hover_vertex != abi.OVERLAY_NONE and o.hover_vertex < nv:
+            v = np.array([o.hover_vertex])
+            _ov_circles(out, np.array([lay["hover_vertex"]]), some[v], abi.PRIM_CIRCLE, sx[v], sy[v], 5, col["hover"])
+        if o.hover_edge != (abi.OVERLAY_NONE, abi.OVERLAY_NONE) and nv:
+            ok, a, b = ends([o.hover_edge[0]], [o.hover_edge[1]])
+            for d, (ox, oy) in enumerate(((False, False), (True, False), (False, True))):
+                _ov_segs(out, np.array([lay["hover_edge"] + d]), ok, sx[a], sy[a], sx[b], sy[b], col["hover"], ox=ox, oy=oy)
+        if o.hover_face != abi.OVERLAY_NONE and t is not None and o.hover_face < t.np:
+            _ov_polygons(out, 0, [o.hover_face], [lay["hover_face"]], t, pos, nv, tab, project, o.rect, col["hover"])
+
+    if (o.sections & abi.OVERLAY_SELECTED) and n_sel:
+        at = lay["selected"]
+        if o.select_kind == abi.SELECT_VERTICES:
+            v = sel.astype(np.int64)
+            ok = v < nv
+            vc = np.where(ok, v, 0)
+            if nv:
+                _ov_circles(out, at + np.arange(n_sel), ok & some[vc], abi.PRIM_CIRCLE, sx[vc], sy[vc], 4, col["selected"])
+        elif o.select_kind == abi.SELECT_EDGES and nv:
+            pairs = sel[:2 * n_sel].reshape(-1, 2)
+            ok, a, b = ends(pairs[:, 0], pairs[:, 1])
+            idx = at + 4 * np.arange(n_sel)
+            _ov_segs(out, idx, ok, sx[a], sy[a], sx[b], sy[b], col["selected"])
+            _ov_segs(out, idx + 1, ok, sx[a], sy[a], sx[b], sy[b], col["selected"], ox=True)
+            _ov_circles(out, idx + 2, ok, abi.PRIM_CIRCLE, sx[a], sy[a], 3, col["selected"])
+            _ov_circles(out, idx + 3, ok, abi.PRIM_CIRCLE, sx[b], sy[b], 3, col["selected"])
+        elif o.select_kind == abi.SELECT_POLYGONS:
+            polys = sel[sel < t.np].astype(np.int64)
+            slots = _poly_slots(1, t.count[polys])
+            first = at + np.concatenate([[0], np.cumsum(slots)])[:-1]
+            _ov_polygons(out, 1, polys, first, t, pos, nv, tab, project, o.rect, col["selected"])
+
+    if o.sections & abi.OVERLAY_PREVIEW:
+        at = lay["preview"]
+        if o.preview_mode == abi.PREVIEW_VERTEX:
+            _ov_circles(out, at + allv, some & _ov_inside(sx, sy, o.rect), abi.PRIM_CIRCLE, sx, sy, 6, col["preview"])
+        elif o.preview_mode == abi.PREVIEW_EDGE and nv:
+            rank = t.first_half_edges()
+            h = np.nonzero(rank)[0]
+            ok, a, b = ends(t.he_v0[h], t.he_v1[h])
+            with np.errstate(all="ignore"):
+                mid_x, mid_y = (sx[a] + sx[b]) / f32(2.0), (sy[a] + sy[b]) / f32(2.0)
+            ok = ok & _ov_inside(mid_x, mid_y, o.rect)
+            idx = at + 2 * (rank[h] - 1)
+            _ov_segs(out, idx, ok, sx[a], sy[a], sx[b], sy[b], col["preview"])
+            _ov_segs(out, idx + 1, ok, sx[a], sy[a], sx[b], sy[b], col["preview"], ox=True)
+        elif o.preview_mode == abi.PREVIEW_FACE:
+            polys = np.arange(t.np, dtype=np.int64)
+            _ov_polygons(out, 2, polys, at + t.poly_start.astype(np.int64)[:-1] + polys, t, pos, nv, tab, project, o.rect, col["preview"])
+    return out
 
 
 class PrimBatch:

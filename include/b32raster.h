@@ -848,6 +848,69 @@ int b32_gizmo_counts(b32_ctx* ctx, uint64_t* drawn, uint64_t* dropped, uint64_t*
  * (modeler/viewport.rs:4575-4660) is the same faces as B32_GIZMO_TRIANGLE_VIEW followed by its edges as B32_LINE_3D items of
  * b32_draw_world. */
 int b32_octahedron_items(const float center[3], float size, const uint8_t rgbb[4], B32GizmoItem out[20]);
+/* The modeler's selection overlays (modeler/viewport.rs:1782-2247), drawn from a slot's RESIDENT vertices: draw_selected_object_brackets
+ * (:1782-1884), draw_mesh_selection_overlays (:1890-2105) and draw_box_selection_preview (:2108-2247) all start from the selected
+ * object's posed positions, which after b32_scene_pose exist in the slot only.  One call makes, on the device, the B32Prim records of the
+ * sections asked for -- in the bit order below, which is the reference's call order -- and hands them to the ordered tile pass of
+ * b32_draw_prims without visiting the host.  Positions are the slot's as they are (posed or not); there is no placement.  The arithmetic
+ * is the reference's, operation for operation (f32, no contraction, saturating `as i32`, a wrapping `as i32 + 1`); all colours are
+ * RasterColor::new (blend Opaque):
+ *   BRACKETS  min / max over all nv positions (f32::min / max: a NaN never wins), -= 4.0 / += 4.0, bracket_len = the smallest extent * 0.25,
+ *             the 8 corners x 3 directions of :1842-1863 as 24 B32_LINE_3D records (0, 200, 230); nv == 0: nothing.
+ *   EDGES     every half-edge of the topology in loop order (duplicates included) whose indices are < nv and whose ends project:
+ *             B32_LINE_3D_ALPHA (80, 80, 80) alpha 191.
+ *   DOTS      every vertex that projects: B32_PRIM_CIRCLE_ALPHA radius 3 (40, 40, 50) alpha 140.
+ *   HOVER     (255, 200, 150): the vertex a circle of radius 5; the edge three B32_LINE_2D (as cast, + 1 on both x, + 1 on both y); the
+ *             face the outline over its projected vertices when there are >= 3, plus [0] -> [2] when there are >= 4.
+ *   SELECTED  (100, 180, 255): vertices a circle of radius 4 each; edges (pairs as given) the line, its + 1 x twin and a circle of radius
+ *             3 at each end; polygons the outline with + 1 x twins and a circle of radius 4 at the projected centre -- the sum over the
+ *             vertices with index < nv times 1.0 / n, n the number that PROJECTED (:2088); fewer than 3 projected: nothing.
+ *   PREVIEW   (255, 220, 100), inclusive tests against (x0, y0)-(x1, y1) (a NaN fails): mode 0 a circle of radius 6 per vertex inside; mode 1
+ *             the first half-edge of every normalised edge in loop order whose midpoint is inside, as the line and its + 1 x twin in that
+ *             half-edge's orientation; mode 2 per polygon whose centre (sum over indices < nv times 1.0 / their count) projects inside and
+ *             that has >= 3 projected vertices: the outline, then a circle of radius 4 at the centre.
+ * The reference draws gizmos and the skeleton between the overlays and the preview, and the preview takes the camera and ortho of its own
+ * viewport: a caller makes two calls.  wireframe_overlay on: leave out EDGES and DOTS (:1923).  An index out of range is never an error: it
+ * behaves as get_pos(..) == None / mesh.faces.get(..) == None.
+ * How many records there are, and where each lies, depends on the topology, nv, this struct and the selected list alone -- never on the
+ * camera (b32_mesh_overlay_record_count); a call the reference does not make leaves a record that draws nothing (a circle of radius
+ * -1).  A record whose extent or circle centre reaches 2^30 becomes such a no-op too, as in b32_draw_world; a NaN depth is stored as
+ * 0x7FC00000. */
+typedef struct B32MeshOverlay {
+    uint32_t sections;                       /* B32_OVERLAY_* bits */
+    uint32_t hover_vertex;                   /* 0xFFFFFFFF: none */
+    uint32_t hover_edge_v0, hover_edge_v1;   /* both 0xFFFFFFFF: none */
+    uint32_t hover_face;                     /* POLYGON index, 0xFFFFFFFF: none -- i.e. a masked B32HoverResult */
+    uint32_t select_kind;                    /* 0 none, 1 vertices, 2 edges (pairs), 3 polygons */
+    uint32_t n_selected;
+    uint32_t preview_mode;                   /* 0 vertex, 1 edge, 2 face (SelectMode) */
+    float    x0, y0, x1, y1;                 /* preview rectangle, framebuffer coordinates */
+} B32MeshOverlay;                            /* 48 bytes */
+#define B32_OVERLAY_BRACKETS 1u   /* draw_selected_object_brackets */
+#define B32_OVERLAY_EDGES    2u   /* :1923-1935 */
+#define B32_OVERLAY_DOTS     4u   /* :1937-1954 */
+#define B32_OVERLAY_HOVER    8u   /* :1960-2020 */
+#define B32_OVERLAY_SELECTED 16u  /* :2025-2104 */
+#define B32_OVERLAY_PREVIEW  32u  /* draw_box_selection_preview */
+/* Draws the sections with b32_draw_world's contract: enqueued on the context's stream with no host synchronisation, a deferred clear
+ * flushed first, only rows of the band written, the z-buffer read (f32::MAX while it is not valid) and never written, `overlay` and
+ * `selected` (n_selected indices, 2 * n_selected for pairs; copied) reusable on return.  `topology` may be NULL when no section reads
+ * polygons (BRACKETS, DOTS, the hovered vertex / edge, selected vertices / edges, PREVIEW mode 0).
+ * NULL context, camera, slot or overlay, an unknown section bit, select_kind > 3, preview_mode > 2, a section that walks polygons (EDGES, a
+ * hovered face, selected polygons, PREVIEW modes 1 and 2) without a topology, n_selected > 0 with selected == NULL, a zero-size framebuffer,
+ * a slot that does not hold its scene -> B32_E_ARG.  More than 2^31 - 1 records -> B32_E_UNSUPPORTED, before anything is enqueued. */
+int b32_draw_mesh_overlay(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable */, b32_scene* slot,
+                          b32_topology* topology /* nullable, see above */, const B32MeshOverlay* overlay, const uint32_t* selected);
+/* Stage tap: the records b32_draw_mesh_overlay would hand to the tile pass for a width x height framebuffer, copied back (synchronous).
+ * *n_records = how many there are; more than `cap`: B32_E_ARG and nothing is written. */
+int b32_mesh_overlay_project_batch(b32_ctx* ctx, const B32Camera* camera, const B32Ortho* ortho /* nullable */, b32_scene* slot,
+                                   b32_topology* topology, const B32MeshOverlay* overlay, const uint32_t* selected, uint32_t width,
+                                   uint32_t height, B32Prim* out, uint32_t cap, uint32_t* n_records);
+/* How many records the call makes for a slot of nv vertices (host only): 24 (nv > 0) + nh + nv + hover (1, 3, n + (n >= 4)) + selected
+ * (n_selected, 4 * n_selected, the sum of 2 * n + 1 over the listed polygons that exist) + preview (nv, 2 * distinct edges, nh + np), each
+ * for the sections that are on.  The argument rules of b32_draw_mesh_overlay. */
+int b32_mesh_overlay_record_count(const b32_topology* topology /* nullable */, uint32_t nv, const B32MeshOverlay* overlay,
+                                  const uint32_t* selected, uint32_t* n);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
