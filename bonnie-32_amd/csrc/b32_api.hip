@@ -846,6 +846,41 @@ int b32_last_draw_order(b32_ctx* c, uint32_t* face_idx, uint32_t cap, uint32_t* 
     return B32_OK;
 }
 
+int b32_last_surface_shading(b32_ctx* c, uint32_t* face_idx, float* shades, uint32_t* colors, uint32_t cap, uint32_t* n, uint32_t* n_shaded) {
+    if (!c || !n || !n_shaded || c->frame_pending || c->frame_batched || c->band_set || !c->scene.have_scene) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    const uint32_t nf = c->scene.nf, cnt = c->h_ctrl.n_visible;
+    const bool lit = c->last_settings.shading != B32_SHADE_NONE;
+    *n = 0; *n_shaded = 0;
+    if (!nf || !cnt) return B32_OK;
+    // the frame set must be the one that mesh's frame wrote (a slot swapped out since then is another mesh: refused, not read past its end)
+    if (cnt > nf || nf > c->cur.cap_work || !c->cur.face_of || !c->cur.srecs || !c->cur.keys0 || !c->vals[0]) return B32_E_ARG;
+    if (lit && (!c->cur.shades || nf > c->cur.cap_shades)) return B32_E_ARG;
+    // which record slots hold a surface: the fast path leaves k_setup's keys as they were written (KEY_INVALID behind each wave's
+    // survivors); a frame with a global sort has sorted over them and left the slots, in draw order, where b32_last_draw_order reads them
+    std::vector<uint32_t> live(c->last_local_sort ? nf : cnt), fo(nf);
+    std::vector<ShadeRec> sr(nf);
+    std::vector<float> sh(lit ? (size_t)nf * 9 : 0);
+    HIPCHK(c, hipMemcpyAsync(live.data(), c->last_local_sort ? c->cur.keys0 : c->vals[0], live.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fo.data(), c->cur.face_of, (size_t)nf * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sr.data(), c->cur.srecs, (size_t)nf * sizeof(ShadeRec), hipMemcpyDeviceToHost, c->stream));
+    if (lit) HIPCHK(c, hipMemcpyAsync(sh.data(), c->cur.shades, sh.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> slots;
+    slots.reserve(cnt);
+    if (c->last_local_sort) { for (uint32_t s = 0; s < nf; ++s) if (live[s] != KEY_INVALID) slots.push_back(s); }
+    else { slots = live; std::sort(slots.begin(), slots.end()); }
+    if (slots.size() != cnt || slots.back() >= nf) return B32_E_ARG;
+    *n = cnt; *n_shaded = lit ? cnt : 0;
+    for (uint32_t i = 0; i < cnt && i < cap; ++i) {          // (slots ascend with the face id: k_setup packs each wave's survivors in order)
+        const uint32_t s = slots[i];
+        if (face_idx) face_idx[i] = fo[s];
+        if (colors) { colors[i * 3] = sr[s].pk0 & 0xFFFFFFu; colors[i * 3 + 1] = sr[s].pk1 & 0xFFFFFFu; colors[i * 3 + 2] = sr[s].pk2 & 0xFFFFFFu; }
+        if (shades && lit) std::memcpy(shades + (size_t)i * 9, sh.data() + (size_t)s * 9, 9 * sizeof(float));
+    }
+    return B32_OK;
+}
+
 int b32_selftest_f32(b32_ctx* c, int op, const float* a, const float* b, const float* cc, float* out, uint32_t n) {
     if (!c || !a || !b || !cc || !out) return B32_E_ARG;
     if (!n) return B32_OK;

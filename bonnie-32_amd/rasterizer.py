@@ -1435,6 +1435,18 @@ class Context:
         _chk(self.lib.b32_last_draw_order(self.h, buf.ctypes.data, cap, C.byref(n)), "last_draw_order")
         return buf[:min(n.value, cap)].copy()
 
+    def last_surface_shading(self, cap):
+        """b32_last_surface_shading: (face_idx [n], shades f32 [n or 0, 9], colors u32 [n, 3]) of the last finished frame's surviving
+        surfaces, in ascending face index -- the shades of an unlit frame come back empty."""
+        cap = max(int(cap), 1)
+        faces = np.zeros(cap, np.uint32); shades = np.zeros((cap, 9), np.float32); colors = np.zeros((cap, 3), np.uint32)
+        n = C.c_uint32(); ns = C.c_uint32()
+        _chk(self.lib.b32_last_surface_shading(self.h, faces.ctypes.data, shades.ctypes.data, colors.ctypes.data, cap, C.byref(n), C.byref(ns)),
+             "last_surface_shading")
+        if n.value > cap:
+            raise ValueError(f"last_surface_shading: {n.value} surfaces, room for {cap}")
+        return faces[:n.value].copy(), shades[:ns.value].copy(), colors[:n.value].copy()
+
 
 class Framebuffer:
     """Framebuffer (render.rs:10-45), device resident. `pixels` downloads the RGBA8 bytes."""

@@ -923,6 +923,16 @@ int b32_project_fixed_batch(b32_ctx* ctx, const float* pos_xyz, uint32_t n,
 /* Draw order of the last frame: face index of every surviving surface, in the order drawn
  * (opaque sorted, then transparent sorted; render.rs:2518-2569). `cap` entries max; returns count via n. */
 int b32_last_draw_order(b32_ctx* ctx, uint32_t* face_idx, uint32_t cap, uint32_t* n);
+/* What the last frame shaded with, before the fill quantises it: for every surviving surface, in ascending face index,
+ * face_idx[i] = its face, shades[9 * i ..] = the nine floats the setup kernel stored for it (render.rs:1466-1483: the flat shade three
+ * times, or the Gouraud shades of v1, v2, v3 in the surface's own vertex order, r g b each), colors[3 * i ..] = its three vertex colours
+ * after fog (render.rs:2419-2442), r | g << 8 | b << 16, as the shade record holds them.  *n = how many surfaces there are, *n_shaded =
+ * how many have shades: *n on a lit frame, 0 when shading is None (the colours are valid either way).  At most `cap` surfaces are
+ * written; face_idx, shades and colors may each be NULL.  Copies what the frame's own kernels wrote and launches nothing.  For a finished
+ * frame of ONE mesh that is still the context's resident scene (drop-in, resident, placed or posed): B32_E_ARG while a frame is
+ * pending, after a merged batch, with a band set, or when the buffers do not belong to that mesh. */
+int b32_last_surface_shading(b32_ctx* ctx, uint32_t* face_idx, float* shades, uint32_t* colors, uint32_t cap, uint32_t* n,
+                             uint32_t* n_shaded);
 /* IEEE-754 f32 self-test of the device arithmetic the pipeline relies on (no FMA contraction,
  * correctly rounded / and sqrt, denormals kept): evaluates op(a[i], b[i], c[i]) on the GPU.
  * op: 0 a*b+c (two roundings), 1 a/b, 2 sqrt(a), 3 (a+b)/c, 4 acos(a) as the lighting code computes it (render.rs:1049),

@@ -573,6 +573,25 @@ static inline void editor_alpha_store(FB* fb, size_t idx, uint16_t color, uint32
     fb->pixels[idx + 3] = 255;
 }
 
+/* the shades both rasterize_triangle functions start with (render.rs:1466-1483, 1220-1237), for the stage dump: the same calls on the same
+ * operands, made whether or not the surface's bounding box is empty */
+static int surface_shades(const Surface* s, const B32Settings* st, float out[9]) {
+    Shade sh[3] = { { 1.0f, 1.0f, 1.0f }, { 1.0f, 1.0f, 1.0f }, { 1.0f, 1.0f, 1.0f } };
+    int rc = B32_OK;
+    if (st->shading == B32_SHADE_FLAT) {
+        V3 center_pos = v3scale(v3add(v3add(s->w1, s->w2), s->w3), 1.0f / 3.0f);
+        V3 world_normal = v3normalize(v3scale(v3add(v3add(s->wn1, s->wn2), s->wn3), 1.0f / 3.0f));
+        rc = shade_multi_light_color(world_normal, center_pos, st->lights, st->n_lights, st->ambient, &sh[0]);
+        sh[1] = sh[0]; sh[2] = sh[0];
+    } else if (st->shading == B32_SHADE_GOURAUD) {
+        rc = shade_multi_light_color(s->wn1, s->w1, st->lights, st->n_lights, st->ambient, &sh[0]);
+        if (!rc) rc = shade_multi_light_color(s->wn2, s->w2, st->lights, st->n_lights, st->ambient, &sh[1]);
+        if (!rc) rc = shade_multi_light_color(s->wn3, s->w3, st->lights, st->n_lights, st->ambient, &sh[2]);
+    }
+    for (int k = 0; k < 3; ++k) { out[k * 3] = sh[k].r; out[k * 3 + 1] = sh[k].g; out[k * 3 + 2] = sh[k].b; }
+    return rc;
+}
+
 /* rasterize_triangle_15, render.rs:1440-1714 */
 static int rasterize_triangle_15(FB* fb, const Surface* s, const B32Texture15* texture, uint32_t face_blend_mode,
                                  int black_transparent, const B32Settings* st, int skip_z_write) {
@@ -1073,6 +1092,10 @@ typedef struct B32OracleDump {
     uint32_t* draw_order;  /* nf capacity: face_idx in draw order */
     uint32_t  n_drawn;
     uint32_t  n_opaque;
+    /* (appended: a caller that zero-fills the struct and knows nothing of them gets neither) */
+    float*    shades;      /* nf capacity x 9, in draw order: what the fill shades surface i with (render.rs:1466-1483) -- the flat shade
+                            * three times, or the Gouraud shades of v1, v2, v3; 1.0 throughout when shading is None */
+    uint32_t* colors;      /* nf capacity x 3, in draw order: the vertex colours after fog (render.rs:2419-2442), r | g << 8 | b << 16 */
 } B32OracleDump;
 
 /* Framebuffer::clear, render.rs:36-45 + Color::to_bytes types.rs:829-832 */
@@ -1310,6 +1333,15 @@ static int render_mesh_impl(uint8_t* fb_pixels, float* fb_zbuffer, uint32_t widt
             if (!st->use_zbuffer) merge_sort_desc_mt(order, tmp, key, n_op, (uint32_t)g_threads); /* :2535-2542 */
             if (timings) timings->triangles_drawn = ns;
             if (dump) { dump->n_drawn = ns; dump->n_opaque = n_op; if (dump->draw_order) for (uint32_t i = 0; i < ns; ++i) dump->draw_order[i] = surfaces[order[i]].face_idx; }
+            if (dump && (dump->shades || dump->colors))
+                for (uint32_t i = 0; i < ns; ++i) {
+                    const Surface* s = &surfaces[order[i]];
+                    if (dump->shades) (void)surface_shades(s, st, dump->shades + (size_t)i * 9);
+                    if (dump->colors) {
+                        const Col vc[3] = { s->vc1, s->vc2, s->vc3 };
+                        for (int k = 0; k < 3; ++k) dump->colors[(size_t)i * 3 + k] = (uint32_t)vc[k].r | ((uint32_t)vc[k].g << 8) | ((uint32_t)vc[k].b << 16);
+                    }
+                }
             /* DRAW, :2547-2572 */
             if (!st->wireframe_overlay) {
                 const uint32_t by0 = fb.band_y0 < height ? fb.band_y0 : height, by1 = fb.band_y1 < height ? fb.band_y1 : height;

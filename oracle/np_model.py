@@ -255,7 +255,7 @@ def render_mesh(pixels, width, height, vertices, faces, textures, camera, settin
 
 def render_mesh_15(pixels, width, height, vertices, faces, textures, camera, settings, fog=None, zbuffer=None, fmt8=False):
     """Draw into `pixels` (uint8 [H*W*4]) (and `zbuffer` f32 [H*W] when settings.use_zbuffer); returns dict(triangles_drawn,
-    fragments, draw_order, sx, sy)."""
+    fragments, draw_order, sx, sy, sz, shades, colors)."""
     img = pixels.reshape(height, width, 4)
     zb = zbuffer.reshape(height, width) if settings.use_zbuffer else None
     pos = vertices["pos"].astype(np.float32)
@@ -369,8 +369,17 @@ def render_mesh_15(pixels, width, height, vertices, faces, textures, camera, set
     if settings.wireframe_overlay and front_wires:
         for e in _unique_edges(front_wires):
             draw_line(img, width, height, e, (200, 200, 220), None, depth_test=False)
+    # what the oracle's stage dump reports per drawn surface, in draw order: the nine shades the fill starts from (:1466-1483; none on an
+    # unlit frame) and the three vertex colours after fog (:2419-2442) as r | g << 8 | b << 16
+    shades = np.zeros((len(draw) if settings.shading != 0 else 0, 9), np.float32)
+    for k in range(len(shades)):
+        s = surfaces[draw[k]]
+        if "_sh" not in s:
+            _prep_shades(s, settings)
+        shades[k] = np.concatenate(s["_sh"])
+    colors = np.array([[int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16 for c in surfaces[i]["vc"]] for i in draw], np.uint32).reshape(-1, 3)
     return dict(triangles_drawn=len(surfaces), fragments=fragments, draw_order=np.array([surfaces[i]["face"] for i in draw], np.uint32),
-                sx=sx, sy=sy, sz=scr[:, 2])
+                sx=sx, sy=sy, sz=scr[:, 2], shades=shades, colors=colors)
 
 
 def _as_i32(x):

@@ -20,7 +20,7 @@ _fast = None
 
 class B32OracleDump(C.Structure):
     _fields_ = [("sx", C.c_void_p), ("sy", C.c_void_p), ("sz", C.c_void_p), ("draw_order", C.c_void_p),
-                ("n_drawn", C.c_uint32), ("n_opaque", C.c_uint32)]
+                ("n_drawn", C.c_uint32), ("n_opaque", C.c_uint32), ("shades", C.c_void_p), ("colors", C.c_void_p)]
 
 
 def build(force=False):
@@ -169,7 +169,7 @@ def render_mesh(fb: Framebuffer, vertices, faces, textures, camera: T.Camera, se
 
 def render_mesh_15(fb: Framebuffer, vertices, faces, textures, camera: T.Camera, settings: T.RasterSettings,
                    fog=None, dump=False, _fmt8=False, fast=False, threads=1):
-    """render_mesh_15 (render.rs:2302-2638) on the CPU. Returns (rc, RasterTimings[, dump dict]).
+    """render_mesh_15 (render.rs:2302-2638) on the CPU. Returns (rc, RasterTimings[, dump dict: sx, sy, sz, draw_order, n_opaque, shades, colors]).
     fast: the baseline build (release profile) instead of the checker; threads > 1: the all-cores schedule (b32o_set_threads)."""
     L = fast_lib() if fast else lib()
     L.b32o_set_threads(int(threads))
@@ -186,7 +186,9 @@ def render_mesh_15(fb: Framebuffer, vertices, faces, textures, camera: T.Camera,
         sx = np.zeros(max(len(vertices), 1), np.int32); sy = np.zeros_like(sx)
         sz = np.zeros(max(len(vertices), 1), np.float32)
         order = np.zeros(max(len(faces), 1), np.uint32)
+        shades = np.zeros((max(len(faces), 1), 9), np.float32); colors = np.zeros((max(len(faces), 1), 3), np.uint32)
         d.sx, d.sy, d.sz, d.draw_order = sx.ctypes.data, sy.ctypes.data, sz.ctypes.data, order.ctypes.data
+        d.shades, d.colors = shades.ctypes.data, colors.ctypes.data
     common = (fb.pixels.ctypes.data, fb.zbuffer.ctypes.data, fb.width, fb.height,
               vertices.ctypes.data if len(vertices) else None, len(vertices),
               faces.ctypes.data if len(faces) else None, len(faces), C.cast(tex_arr, C.c_void_p), len(textures), C.byref(cam), C.byref(st))
@@ -201,7 +203,10 @@ def render_mesh_15(fb: Framebuffer, vertices, faces, textures, camera: T.Camera,
     t = T.RasterTimings.from_c(tm)
     if dump:
         return rc, t, {"sx": sx[:len(vertices)], "sy": sy[:len(vertices)], "sz": sz[:len(vertices)],
-                       "draw_order": order[:d.n_drawn].copy(), "n_opaque": int(d.n_opaque)}
+                       "draw_order": order[:d.n_drawn].copy(), "n_opaque": int(d.n_opaque),
+                       # per drawn surface, in draw order: the nine shades the fill starts from (render.rs:1466-1483; none on an unlit
+                       # frame) and the three vertex colours after fog (render.rs:2419-2442), r | g << 8 | b << 16
+                       "shades": shades[:d.n_drawn if settings.shading != 0 else 0].copy(), "colors": colors[:d.n_drawn].copy()}
     return rc, t
 
 

@@ -74,6 +74,21 @@ def test_no_cpu_fallback(lib):
     assert lib.b32_strerror(abi.B32_E_NO_DEVICE).decode().startswith("no HIP device")
 
 
+def test_shading_tap_is_declared_bound_and_checks_its_arguments(lib):
+    """b32_last_surface_shading sits with the stage taps in the header, is bound with the seven arguments the header gives it, and
+    refuses a missing context before it touches anything (no device needed for that)."""
+    from bonnie32_amd import abi
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"int\s+b32_last_surface_shading\s*\(([^)]*)\)", src)
+    assert m and len(m.group(1).split(",")) == 7
+    assert src.index("b32_last_draw_order") < m.start() < src.index("b32_selftest_f32")
+    argtypes = {n: a for n, _, a in abi.SYMBOLS}["b32_last_surface_shading"]
+    assert len(argtypes) == 7
+    n = C.c_uint32(7); ns = C.c_uint32(7)
+    assert lib.b32_last_surface_shading(None, None, None, None, 0, C.byref(n), C.byref(ns)) == abi.B32_E_ARG
+    assert (n.value, ns.value) == (7, 7)
+
+
 def test_product_never_imports_oracle():
     """The product package must not reference the oracle (tests/bench/smoke are the only allowed users)."""
     pkg = os.path.join(ROOT, "bonnie-32_amd")

@@ -113,6 +113,38 @@ def test_project_fixed_stage(gpu_ctx, oracle):
     assert np.array_equal(sx, ex) and np.array_equal(sy, ey)
     for i in range(0, 400):
         assert oracle.project_fixed(pos[i], cam, 2560, 1920)[:2] == (sx[i], sy[i])
+    # The returned z is the per-vertex float depth of render.rs:2331-2345 (cam_pos.z + 5.0), bit for bit.  oracle.project_fixed's third
+    # value is another quantity (the fixed-point depth the reference discards), so the expected depth is `sz` of the oracle's stage dump for
+    # a draw of the same positions (no faces).  A second camera (translated, rotated about two axes), a second size, and positions with
+    # zeros of both signs, denormals, 3e38 and cam-space depths on both sides of the near plane.
+
+    def depth_bits_equal(a, b):
+        return bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+    cy, sy_, cx, sx_ = (np.float32(t) for t in (np.cos(0.5), np.sin(0.5), np.cos(0.3), np.sin(0.3)))
+    cam2 = b32.Camera(position=(-310.5, 44.125, -87.0), basis_x=(cy, 0.0, -sy_), basis_y=(sx_ * sy_, cx, sx_ * cy), basis_z=(cx * sy_, -sx_, cx * cy))
+    extra = [[0.0, 0.0, 0.0], [-0.0, -0.0, -0.0], [0.0, -0.0, 1e-40], [1e-40, -1e-45, 1e-39], [3e38, 0.0, 0.0], [0.0, -3e38, 3e38], [3e38, 3e38, 3e38]]
+    for c in (cam, cam2):                                          # cam-space z = 0.1 (the near plane, math.rs:155) and its neighbours
+        o, bz = np.asarray(c.position, np.float32), np.asarray(c.basis_z, np.float32)
+        for zc in (0.1, np.nextafter(np.float32(0.1), np.float32(0)), np.nextafter(np.float32(0.1), np.float32(1)), 0.0999, 0.1001, -0.1, 0.0):
+            extra.append((o + bz * np.float32(zc)).astype(np.float32))
+            extra.append((o + bz * np.float32(zc) + np.asarray(c.basis_x, np.float32) * np.float32(3.0)).astype(np.float32))
+    pos2 = np.concatenate([pos, np.array(extra, np.float32)])
+    verts = b32.make_vertices(len(pos2)); verts["pos"] = pos2
+    for c in (cam, cam2):
+        for w, h in ((2560, 1920), (333, 197)):
+            gx, gy, gz = gpu_ctx.project_fixed_batch(pos2, c, w, h)
+            ofb = oracle.Framebuffer(w, h)
+            with np.errstate(all="ignore"):
+                rc, _t, d = oracle.render_mesh_15(ofb, verts, b32.make_faces(0), [], c, b32.RasterSettings.game(), dump=True)
+                mx, my = M.project_fixed(pos2, c, w, h)
+                rel = (pos2 - np.asarray(c.position, np.float32)).astype(np.float32)
+                mz = M.dot3(rel, np.asarray(c.basis_z, np.float32)) + M.K("mesh.distance")
+            assert rc == 0
+            assert np.array_equal(gx, d["sx"]) and np.array_equal(gy, d["sy"]) and np.array_equal(gx, mx) and np.array_equal(gy, my)
+            assert depth_bits_equal(gz, d["sz"]), f"{int((gz.view(np.uint32) != d['sz'].view(np.uint32)).sum())} depths differ ({w}x{h})"
+            assert depth_bits_equal(gz, mz.astype(np.float32))
+            assert (gz[:len(pos)] == gz[:len(pos)]).all() and ((gz > 5.1) & (gz < 5.1001)).any() and ((gz < 5.1) & (gz > 5.0998)).any()
+    assert np.array_equal(gpu_ctx.project_fixed_batch(pos, cam, 2560, 1920)[2].view(np.uint32), z.view(np.uint32))
 
 
 REAL = [n for n in SCENES if n.startswith("real:")]       # the reference's own sample meshes and level rooms (tests/golden/scenes/real/*.b32scene)
