@@ -109,6 +109,16 @@ ROOM_HOVER_DTYPE = np.dtype([("vertex_rec", "<u4"), ("vertex_corner", "<u4"), ("
                              ("edge_rec", "<u4"), ("edge_idx", "<u4"), ("edge_dist", "<f4"), ("edge_depth", "<f4"),
                              ("face_rec", "<u4"), ("face_depth", "<f4"), ("_pad", "<u4", 2)])
 assert SECTOR_FACE_DTYPE.itemsize == 24 and ROOM_GRID_DTYPE.itemsize == 16 and ROOM_HOVER_PARAMS_DTYPE.itemsize == 16 and ROOM_HOVER_DTYPE.itemsize == 48
+# B32FaceMaterial (b32_room_set_materials, b32_room_build_mesh): one per B32SectorFace; flags = MAT_HAS_*
+FACE_MATERIAL_DTYPE = np.dtype([("texture_id", "<u4"), ("tex_width", "<u4"), ("texture_id_2", "<u4"), ("tex_width_2", "<u4"),
+                                ("uv", "<f4", (4, 2)), ("uv_2", "<f4", (4, 2)), ("colors", "u1", (4, 4)), ("colors_2", "u1", (4, 4)),
+                                ("heights_2", "<f4", 4), ("normal_mode", "u1"), ("split_direction", "u1"), ("uv_projection", "u1"),
+                                ("blend_mode", "u1"), ("black_transparent", "u1"), ("flags", "u1"), ("_pad", "u1", 2)])
+assert FACE_MATERIAL_DTYPE.itemsize == 136
+MAT_HAS_UV, MAT_HAS_UV_2, MAT_HAS_HEIGHTS_2 = 1, 2, 4
+NORMAL_FRONT, NORMAL_BOTH, NORMAL_BACK = range(3)
+SPLIT_NWSE, SPLIT_NESW = range(2)
+UV_DEFAULT, UV_PROJECTED = range(2)
 ROOM_FLOOR, ROOM_CEILING, ROOM_WALL_NORTH, ROOM_WALL_EAST, ROOM_WALL_SOUTH, ROOM_WALL_WEST, ROOM_WALL_NWSE, ROOM_WALL_NESW = range(8)
 SECTOR_SIZE = 1024.0                # world/geometry.rs:10
 ROOM_MAX_FACES = 1 << 24
@@ -232,6 +242,11 @@ SYMBOLS = [
     ("b32_room_create", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_P)]),
     ("b32_room_update", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     ("b32_room_destroy", None, [_P, _P]),
+    ("b32_room_set_materials", C.c_int, [_P, _P, _P]),
+    ("b32_room_update_materials", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_room_mesh_counts", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("b32_room_build_mesh", C.c_int, [_P, _P, _P]),
+    ("b32_scene_read_faces", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
     ("b32_room_hover", C.c_int, [_P, _P, _P, _P, _P]),
     ("b32_room_hover_async", C.c_int, [_P, _P, _P, _P, _P, C.POINTER(C.c_uint64)]),
     ("b32_room_hover_winner", C.c_int, [_P]),

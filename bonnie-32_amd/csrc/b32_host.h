@@ -95,6 +95,7 @@ struct b32_scene {
     unsigned long long gen = 0;         // identity of the scene's content (every upload gets a new number)
     bool fmt8 = false;                  // uploaded by b32_scene_upload_rgba (render_mesh path)
     bool blend8 = false;                // 8-bit path: some texel blends or some face has editor_alpha < 255 -> ordered walk
+    bool blend_texels8 = false;         // ... the texels' part of it, which stays when b32_room_build_mesh replaces the faces
     bool may_blend = true;              // some face / texture can produce a transparent-pass surface (render.rs:2403-2415)
     bool cheap_ok = false;              // every texture has few skippable texels: CHEAP coverage + repair is profitable
     bool tex_blend_any = false;         // some texture has a blend mode other than Opaque

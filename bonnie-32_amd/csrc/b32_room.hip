@@ -15,13 +15,27 @@
 //   k_room_hover_resolve  one workgroup: decodes the three sets, recomputes the winners' distance and depth from their records (exact
 //                         bits, the sign of a zero), writes the 48-byte result and re-arms the words for the next call on the stream.
 // k_room_box: one lane per element (records, then points); a wave's ballot is two words of the bitmap, as in k_box_select.
+//
+// The room's render mesh (b32_room_set_materials, b32_room_update_materials, b32_room_build_mesh): Room::to_render_data_with_textures
+// (world/geometry.rs:2839-3352) from the resident records and one B32FaceMaterial per record; the arithmetic of one vertex and one face
+// is b32_room_mesh_body.h.  Where a record's output lies depends on (kind, normal_mode) alone, which the room keeps on the host with the
+// prefix sums of the counts; the sums are uploaded in stream order whenever a kind or a mode changes, no scan runs on the device.
+//   k_room_mesh           one lane per vertex slot, 12 slots per record (a floor or ceiling with Both), surplus slots idle: consecutive
+//                         lanes write consecutive B32Vertex records; the first 2 or 4 slots also write the record's faces.  A lane reads
+//                         record and material where they lie (the corner index is divergent: no private copy, no scratch) and never reads
+//                         the slot's vertices.  Lane 0 writes the slot's device-side face count.
 #include "b32_pick_body.h"
-#include "b32_room_body.h"
+#include "b32_room_mesh_body.h"
 
 struct b32_room {
     B32SectorFace* faces = nullptr;             // n records on the device
     uint32_t n = 0;
     B32RoomGrid grid{};                         // travels in the kernel argument: an update is ordered by the launch that follows it
+    // the render mesh: materials and per record {first vertex, first face} on the device; on the host what decides where a record's
+    // output lies (kind, normal_mode) and which faces can blend (blend_mode, the two texture ids), and the prefix sums (n + 1 entries)
+    B32FaceMaterial* mats = nullptr; uint2* first = nullptr; bool have_mats = false;
+    std::vector<uint8_t> h_kind, h_mode, h_blend; std::vector<uint32_t> h_tex; std::vector<uint2> h_first;
+    uint32_t own_blend_faces = 0;               // faces whose own blend mode puts them in the transparent pass
 };
 
 namespace b32 {
@@ -42,8 +56,17 @@ struct RoomBoxArgs {
     float x0, y0, x1, y1;
     unsigned char* result;                      // the header and the words
 };
+struct RoomMeshArgs {
+    B32RoomGrid grid;
+    const B32SectorFace* faces; const B32FaceMaterial* mats; const uint2* first;
+    B32Vertex* verts; B32Face* out_faces; uint32_t* consts;
+    uint32_t n, nv, nf;
+};
 static_assert(sizeof(B32SectorFace) == 24 && sizeof(B32RoomGrid) == 16 && sizeof(B32RoomHoverParams) == 16 && sizeof(B32RoomHover) == 48 &&
               sizeof(RoomWords) == 48, "room records");
+static_assert(sizeof(B32FaceMaterial) == 136 && offsetof(B32FaceMaterial, uv) == 16 && offsetof(B32FaceMaterial, uv_2) == 48 &&
+              offsetof(B32FaceMaterial, colors) == 80 && offsetof(B32FaceMaterial, colors_2) == 96 && offsetof(B32FaceMaterial, heights_2) == 112 &&
+              offsetof(B32FaceMaterial, normal_mode) == 128 && offsetof(B32FaceMaterial, flags) == 133 && sizeof(B32Face) == 20, "room mesh records");
 
 __device__ __forceinline__ void room_offer(const PickWords& m, PickWords* w) {
     if (m.first == PICK_NONE) return;
@@ -151,6 +174,29 @@ __global__ __launch_bounds__(256) void k_room_box(RoomBoxArgs a) {
     if (i == 0u) head[0] = total;
 }
 
+// Room::to_render_data_with_textures: lane t is vertex slot t % 12 of record t / 12 (12 * n <= 12 * 2^24).  The stores are guarded by the
+// counts the host allocated for, whatever the tables say.
+__global__ __launch_bounds__(256) void k_room_mesh(RoomMeshArgs a) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t == 0u) { a.consts[0] = a.nf; a.consts[1] = 0u; a.consts[2] = 0u; a.consts[3] = 0u; }      // (h_consts of an upload)
+    const uint32_t rec = t / ROOM_MESH_SLOTS, slot = t - rec * ROOM_MESH_SLOTS;
+    if (rec >= a.n) return;
+    const B32SectorFace& f = a.faces[rec];
+    const B32FaceMaterial& m = a.mats[rec];
+    const uint2 at = a.first[rec];
+    const uint32_t kind = f.kind, mode = m.normal_mode;
+    if (slot < room_mesh_vertex_count(kind, mode) && at.x + slot < a.nv) {
+        B32Vertex v;
+        room_mesh_vertex(a.grid, f, m, slot, v);
+        a.verts[at.x + slot] = v;
+    }
+    if (slot < room_mesh_face_count(mode) && at.y + slot < a.nf) {
+        B32Face o;
+        room_mesh_face(f, m, slot, at.x, o);
+        a.out_faces[at.y + slot] = o;
+    }
+}
+
 }  // namespace b32
 
 // ------------------------------------------------------------------ host
@@ -166,6 +212,36 @@ void room_view(RoomView& v, const b32_ctx* c, const B32Camera* cam) {
 bool room_kinds_ok(const B32SectorFace* faces, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) if (faces[i].kind > 7u) return false;
     return true;
+}
+
+bool room_materials_ok(const B32FaceMaterial* m, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (m[i].normal_mode > B32_NORMAL_BACK || m[i].split_direction > B32_SPLIT_NESW || m[i].uv_projection > B32_UV_PROJECTED || m[i].blend_mode > B32_BLEND_ERASE) return false;
+    return true;
+}
+// The prefix sums from record `from` on (entry i: vertices and faces in front of record i; entry n: the mesh's counts), and their upload
+// in stream order.
+int room_mesh_layout(b32_ctx* c, b32_room* r, uint32_t from) {
+    for (uint32_t i = from; i < r->n; ++i) {
+        const uint2 at = r->h_first[i];
+        r->h_first[i + 1] = make_uint2(at.x + room_mesh_vertex_count(r->h_kind[i], r->h_mode[i]), at.y + room_mesh_face_count(r->h_mode[i]));
+    }
+    if (from < r->n) HIPCHK(c, hipMemcpyAsync(r->first + from, r->h_first.data() + from, (size_t)(r->n - from) * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+    return B32_OK;
+}
+// What the host keeps of materials [first, first + count); returns the first record whose normal_mode changed (n: none)
+uint32_t room_materials_keep(b32_room* r, uint32_t first, uint32_t count, const B32FaceMaterial* m) {
+    uint32_t changed = r->n;
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t k = first + i;
+        const uint32_t faces = room_mesh_face_count(r->h_mode[k]);
+        if (r->have_mats && r->h_blend[k] != B32_BLEND_OPAQUE) r->own_blend_faces -= faces;
+        if (r->h_mode[k] != m[i].normal_mode && changed == r->n) changed = k;
+        r->h_mode[k] = m[i].normal_mode; r->h_blend[k] = m[i].blend_mode;
+        r->h_tex[2 * (size_t)k] = m[i].texture_id; r->h_tex[2 * (size_t)k + 1] = m[i].texture_id_2;
+        if (m[i].blend_mode != B32_BLEND_OPAQUE) r->own_blend_faces += room_mesh_face_count(m[i].normal_mode);
+    }
+    return changed;
 }
 
 int room_common_check(const b32_ctx* c, const B32Camera* cam, const b32_room* room) {
@@ -186,6 +262,8 @@ int b32_room_create(b32_ctx* c, const B32RoomGrid* grid, const B32SectorFace* fa
     (void)hipSetDevice(c->device);
     b32_room* r = new b32_room();
     r->n = n; r->grid = *grid;
+    r->h_kind.resize(n);
+    for (uint32_t i = 0; i < n; ++i) r->h_kind[i] = faces[i].kind;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&r->faces), n ? (size_t)n * sizeof(B32SectorFace) : 4);
     if (e == hipSuccess && n) e = hipMemcpyAsync(r->faces, faces, (size_t)n * sizeof(B32SectorFace), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) {
@@ -205,13 +283,102 @@ int b32_room_update(b32_ctx* c, b32_room* room, const B32RoomGrid* grid, uint32_
     (void)hipSetDevice(c->device);
     if (count) HIPCHK(c, hipMemcpyAsync(room->faces + first, faces, (size_t)count * sizeof(B32SectorFace), hipMemcpyHostToDevice, c->stream));
     if (grid) room->grid = *grid;
+    uint32_t changed = room->n;                 // a kind that changes moves every later record's place in the render mesh
+    for (uint32_t i = 0; i < count; ++i) {
+        if (room->h_kind[first + i] != faces[i].kind && changed == room->n) changed = first + i;
+        room->h_kind[first + i] = faces[i].kind;
+    }
+    if (room->have_mats && changed < room->n) return room_mesh_layout(c, room, changed);
+    return B32_OK;
+}
+
+int b32_room_set_materials(b32_ctx* c, b32_room* room, const B32FaceMaterial* m) {
+    if (!c || !room || (room->n && !m)) return B32_E_ARG;
+    if (!room_materials_ok(m, room->n)) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    const uint32_t n = room->n;
+    if (!room->mats) {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&room->mats), n ? (size_t)n * sizeof(B32FaceMaterial) : 8));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&room->first), n ? (size_t)n * sizeof(uint2) : 8));
+        room->h_mode.assign(n, 0); room->h_blend.assign(n, 0); room->h_tex.assign(2 * (size_t)n, 0); room->h_first.assign((size_t)n + 1, make_uint2(0, 0));
+    }
+    if (n) HIPCHK(c, hipMemcpyAsync(room->mats, m, (size_t)n * sizeof(B32FaceMaterial), hipMemcpyHostToDevice, c->stream));
+    room->have_mats = false; room->own_blend_faces = 0;
+    (void)room_materials_keep(room, 0, n, m);
+    room->have_mats = true;
+    return room_mesh_layout(c, room, 0);
+}
+
+int b32_room_update_materials(b32_ctx* c, b32_room* room, uint32_t first, uint32_t count, const B32FaceMaterial* m) {
+    if (!c || !room || !room->have_mats || (count && !m)) return B32_E_ARG;
+    if ((unsigned long long)first + count > room->n) return B32_E_ARG;
+    if (!room_materials_ok(m, count)) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    if (count) HIPCHK(c, hipMemcpyAsync(room->mats + first, m, (size_t)count * sizeof(B32FaceMaterial), hipMemcpyHostToDevice, c->stream));
+    const uint32_t changed = room_materials_keep(room, first, count, m);
+    if (changed < room->n) return room_mesh_layout(c, room, changed);
+    return B32_OK;
+}
+
+int b32_room_mesh_counts(const b32_room* room, uint32_t* nv, uint32_t* nf) {
+    if (!room || !room->have_mats || !nv || !nf) return B32_E_ARG;
+    *nv = room->h_first[room->n].x; *nf = room->h_first[room->n].y;
+    return B32_OK;
+}
+
+// Leaves the slot as upload_geometry and b32_scene_pose would (b32_scene.hip); the ordering argument is the pose's.
+int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
+    if (!c || !room || !room->have_mats) return B32_E_ARG;
+    b32_scene* sc = slot ? slot : &c->scene;
+    if (!sc->have_scene) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    // a pending frame that may still be redrawn is redrawn from the resident geometry: settle it before that changes (b32_scene_upload)
+    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    const uint32_t n = room->n, nv = room->h_first[n].x, nf = room->h_first[n].y;
+    int rc;
+    if ((rc = ensure(c, sc->d_verts, sc->cap_verts, (size_t)nv + 1))) return rc;
+    if ((rc = ensure(c, sc->d_faces, sc->cap_faces, (size_t)nf + 1))) return rc;
+    if (!sc->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_consts), 16 * sizeof(uint32_t)));
+    {   // upload_geometry's face loop: editor_alpha is 255, so a face's own part is its blend mode; a texture's blend mode adds to it
+        bool tex_blend = false;
+        for (const TexDesc& d : sc->h_tex) tex_blend |= d.blend_mode != B32_BLEND_OPAQUE;
+        uint32_t nbt = room->own_blend_faces;
+        if (tex_blend) {
+            nbt = 0;
+            auto blends = [&](uint32_t t) { return t != B32_NO_TEXTURE && t < sc->nt && t < sc->h_tex.size() && sc->h_tex[t].blend_mode != B32_BLEND_OPAQUE; };
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t sides = room_mesh_sides(room->h_mode[i]);
+                const bool own = room->h_blend[i] != B32_BLEND_OPAQUE, flat = room->h_kind[i] < 2u;
+                nbt += (own || blends(room->h_tex[2 * (size_t)i])) ? sides : 0u;
+                nbt += (own || blends(room->h_tex[2 * (size_t)i + (flat ? 1 : 0)])) ? sides : 0u;
+            }
+        }
+        sc->blend_faces = nbt;
+        if (sc->fmt8) { sc->may_blend = false; sc->blend8 = sc->blend_texels8; }        // (b32_scene_upload_rgba: no face has editor_alpha < 255)
+        else sc->may_blend = room->own_blend_faces != 0 || tex_blend;
+    }
+    if (sc->nf != nf) { sc->direct_cap_opaque = 0; sc->direct_ntiles = 0; sc->direct_ok = true; }
+    sc->nv = nv; sc->nf = nf;
+    sc->have_rig = false;
+    sc->local_sort_ok = true;
+    sc->pos_valid = false; sc->lit_valid = false; sc->band_frames = 0;
+    if ((rc = ensure_work(c, nf))) return rc;
+    sc->gen = ++c->gen_counter;
+    RoomMeshArgs a{};
+    a.grid = room->grid; a.faces = room->faces; a.mats = room->mats; a.first = room->first;
+    a.verts = sc->d_verts; a.out_faces = sc->d_faces; a.consts = sc->d_consts;
+    a.n = n; a.nv = nv; a.nf = nf;
+    const uint32_t groups = (uint32_t)(((unsigned long long)n * ROOM_MESH_SLOTS + 255u) / 256u);
+    hipLaunchKernelGGL(k_room_mesh, dim3(groups ? groups : 1u), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->side_dirty = true;
     return B32_OK;
 }
 
 void b32_room_destroy(b32_ctx* c, b32_room* room) {
     if (!room) return;
     if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }     // (a hover that reads it may be in flight)
-    if (room->faces) (void)hipFree(room->faces);
+    for (void* p : { (void*)room->faces, (void*)room->mats, (void*)room->first }) if (p) (void)hipFree(p);
     delete room;
 }
 

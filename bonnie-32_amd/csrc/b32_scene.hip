@@ -233,6 +233,7 @@ int b32_scene_upload_rgba(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32
     if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
     bool alpha_faces = false;
     for (uint32_t i = 0; i < nf && !alpha_faces; ++i) alpha_faces = f[i].editor_alpha < 255;
+    c->scene.blend_texels8 = blend_texels;
     c->scene.blend8 = blend_texels || alpha_faces;
     c->scene.may_blend = false;
     c->scene.fmt8 = true;
@@ -368,6 +369,16 @@ int b32_scene_read_vertices(b32_ctx* c, b32_scene* slot, uint32_t first, uint32_
     if (!count) return B32_OK;
     (void)hipSetDevice(c->device);
     HIPCHK(c, hipMemcpyAsync(out, sc->d_verts + first, (size_t)count * sizeof(B32Vertex), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
+}
+int b32_scene_read_faces(b32_ctx* c, b32_scene* slot, uint32_t first, uint32_t count, B32Face* out) {
+    if (!c) return B32_E_ARG;
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc || (count && !out) || (unsigned long long)first + count > sc->nf) return B32_E_ARG;
+    if (!count) return B32_OK;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipMemcpyAsync(out, sc->d_faces + first, (size_t)count * sizeof(B32Face), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return B32_OK;
 }

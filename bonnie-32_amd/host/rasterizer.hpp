@@ -685,6 +685,26 @@ inline void draw_mesh_overlay(Framebuffer& fb, const ResidentMesh& mesh, const T
 // priority rule) and find_selections_in_rect (:7512-7594) for the current room, on the device (b32_room_hover, b32_room_box_select).  A Room
 // holds the grid and one B32SectorFace per sector face in iter_sectors order (world/geometry.rs:2828-2835: gx outer, gz inner; floor,
 // ceiling, north, east, south, west walls by i, then nwse, then nesw); update() is a height drag.
+// The room's render mesh (Room::to_render_data_with_textures, world/geometry.rs:2839-3352) is made on the device from the same records and
+// one FaceMaterial per record (set_materials / update_materials): build_mesh() writes it into a resident mesh's slot, whose textures stay
+// -- one launch, no upload, no host synchronisation.
+using FaceMaterial = B32FaceMaterial;
+// the reference's defaults: texture (0, 64) on both triangles, Color::NEUTRAL corners, Front, NwSe, Default, Opaque, black_transparent
+inline FaceMaterial face_material() {
+    FaceMaterial m{};
+    m.tex_width = m.tex_width_2 = 64;
+    for (int k = 0; k < 4; ++k) for (int c = 0; c < 3; ++c) m.colors[k][c] = m.colors_2[k][c] = 128;
+    m.black_transparent = 1;
+    return m;
+}
+// (n_vertices, n_faces) of the mesh of these records: where a record's output lies depends on (kind, normal_mode) alone
+inline void room_mesh_counts(const std::vector<B32SectorFace>& faces, const std::vector<FaceMaterial>& materials, uint32_t& n_vertices, uint32_t& n_faces) {
+    n_vertices = 0; n_faces = 0;
+    for (size_t i = 0; i < faces.size() && i < materials.size(); ++i) {
+        const uint32_t sides = materials[i].normal_mode == B32_NORMAL_BOTH ? 2u : 1u;
+        n_vertices += (faces[i].kind < 2 ? 6u : 4u) * sides; n_faces += 2u * sides;
+    }
+}
 class Room {
 public:
     Room(Framebuffer& fb, const std::vector<B32SectorFace>& faces, const B32RoomGrid& grid = B32RoomGrid{ { 0.0f, 0.0f, 0.0f }, B32_SECTOR_SIZE })
@@ -699,6 +719,17 @@ public:
     void update(uint32_t first, const std::vector<B32SectorFace>& faces, const B32RoomGrid* grid = nullptr) {
         check(b32_room_update(ctx_, r_, grid, first, (uint32_t)faces.size(), faces.data()), "room_update");
     }
+    // one material per record; a range of them (ordered on the stream like update())
+    void set_materials(const std::vector<FaceMaterial>& materials) {
+        if (materials.size() != n_) throw std::invalid_argument("Room::set_materials: one material per face");
+        check(b32_room_set_materials(ctx_, r_, materials.data()), "room_set_materials");
+    }
+    void update_materials(uint32_t first, uint32_t count, const FaceMaterial* materials) {
+        check(b32_room_update_materials(ctx_, r_, first, count, materials), "room_update_materials");
+    }
+    void mesh_counts(uint32_t& n_vertices, uint32_t& n_faces) const { check(b32_room_mesh_counts(r_, &n_vertices, &n_faces), "room_mesh_counts"); }
+    // the render mesh into `slot` (nullptr: the context's resident scene), which must hold an uploaded scene
+    void build_mesh(b32_scene* slot = nullptr) { check(b32_room_build_mesh(ctx_, r_, slot), "room_build_mesh"); }
     b32_room* handle() const { return r_; }
     uint32_t faces() const { return n_; }
 private:

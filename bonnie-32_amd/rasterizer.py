@@ -679,6 +679,195 @@ def room_faces_from_sectors(sectors):
     return out
 
 
+# ---- a room's render mesh (b32_room_build_mesh): Room::to_render_data_with_textures, world/geometry.rs:2839-3352
+_BLEND_NAMES = {"Opaque": abi.OPAQUE, "Average": abi.AVERAGE, "Add": abi.ADD, "Subtract": abi.SUBTRACT, "AddQuarter": abi.ADD_QUARTER, "Erase": abi.ERASE}
+_NORMAL_NAMES = {"Front": abi.NORMAL_FRONT, "Both": abi.NORMAL_BOTH, "Back": abi.NORMAL_BACK}
+_SPLIT_NAMES = {"NwSe": abi.SPLIT_NWSE, "NeSw": abi.SPLIT_NESW}
+_PROJECTION_NAMES = {"Default": abi.UV_DEFAULT, "Projected": abi.UV_PROJECTED}
+# SplitDirection::triangle_1_corners / triangle_2_corners by [split][triangle][j]
+_ROOM_TRI = np.array([[[0, 1, 2], [0, 2, 3]], [[0, 1, 3], [1, 2, 3]]], np.intp)
+
+
+def _enum(v, names):
+    return names[v] if isinstance(v, str) else int(v)
+
+
+def _vec2s(uv):
+    return [(u["x"], u["y"]) if hasattr(u, "keys") else tuple(u) for u in uv]
+
+
+def _colors(cols):
+    return [(c["r"], c["g"], c["b"], _enum(c.get("blend", abi.OPAQUE), _BLEND_NAMES)) if hasattr(c, "keys") else tuple(c) for c in cols]
+
+
+def room_materials_from_sectors(sectors, resolve):
+    """The twin of room_faces_from_sectors: one abi.FACE_MATERIAL_DTYPE record per face in the same loop order, the Options resolved as
+    the reference's getters do (geometry.rs:1193-1210).  A face is a mapping with the optional keys texture, texture_2, uv, uv_2 (four
+    {x, y} or pairs), colors, colors_2 (four {r, g, b, blend} or quadruples), heights_2, normal_mode, split_direction, uv_projection,
+    blend_mode (names or numbers) and black_transparent -- the field names of HorizontalFace / VerticalFace; four bare heights are a face
+    with every default.  resolve(texture_ref) -> (texture_id, width) or None: the reference's resolve_texture, `.unwrap_or((0, 64))`."""
+    rows = []
+    for gx, col in enumerate(sectors):
+        for gz, sec in enumerate(col):
+            if sec is None:
+                continue
+            for key, kind in _ROOM_KEYS:
+                got = sec.get(key)
+                if got is None:
+                    continue
+                rows += [(kind, face if hasattr(face, "keys") else {}) for face in ([got] if kind < 2 else list(got))]
+    out = T.make_face_materials(len(rows))
+    for j, (kind, face) in enumerate(rows):
+        m = out[j]
+        m["texture_id"], m["tex_width"] = resolve(face.get("texture")) or (0, 64)
+        flags = 0
+        if face.get("uv") is not None:
+            m["uv"] = _vec2s(face["uv"]); flags |= abi.MAT_HAS_UV
+        if face.get("colors") is not None:
+            m["colors"] = _colors(face["colors"])
+        m["colors_2"] = m["colors"]
+        m["texture_id_2"], m["tex_width_2"] = m["texture_id"], m["tex_width"]
+        if kind < 2:                                                          # HorizontalFace only
+            if face.get("texture_2") is not None:
+                m["texture_id_2"], m["tex_width_2"] = resolve(face["texture_2"]) or (0, 64)
+            uv2 = face.get("uv_2") if face.get("uv_2") is not None else face.get("uv")        # get_uv_2: uv_2.or(uv)
+            if uv2 is not None:
+                m["uv_2"] = _vec2s(uv2); flags |= abi.MAT_HAS_UV_2
+            if face.get("colors_2") is not None:
+                m["colors_2"] = _colors(face["colors_2"])
+            if face.get("heights_2") is not None:
+                m["heights_2"] = [np.float32(v) for v in face["heights_2"]]; flags |= abi.MAT_HAS_HEIGHTS_2
+            m["split_direction"] = _enum(face.get("split_direction", abi.SPLIT_NWSE), _SPLIT_NAMES)
+        else:
+            m["uv_projection"] = _enum(face.get("uv_projection", abi.UV_DEFAULT), _PROJECTION_NAMES)
+        m["normal_mode"] = _enum(face.get("normal_mode", abi.NORMAL_FRONT), _NORMAL_NAMES)
+        m["blend_mode"] = _enum(face.get("blend_mode", abi.OPAQUE), _BLEND_NAMES)
+        m["black_transparent"] = 1 if face.get("black_transparent", True) else 0
+        m["flags"] = flags
+    return out
+
+
+def _room_mesh_layout(faces, materials):
+    """(sides, vertices per record, faces per record): where a record's output lies depends on (kind, normal_mode) alone."""
+    sides = np.where(materials["normal_mode"] == abi.NORMAL_BOTH, 2, 1).astype(np.int64)
+    return sides, np.where(faces["kind"] < 2, 6, 4) * sides, 2 * sides
+
+
+def room_mesh_counts(faces, materials):
+    """(n_vertices, n_faces) of room_mesh / b32_room_mesh_counts."""
+    f = np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+    m = np.ascontiguousarray(materials, abi.FACE_MATERIAL_DTYPE).reshape(-1)
+    _, nv, nf = _room_mesh_layout(f, m)
+    return int(nv.sum()), int(nf.sum())
+
+
+def room_mesh(faces, materials, grid):
+    """Room::to_render_data_with_textures (world/geometry.rs:2839-3352) in numpy float32, every operation separately rounded in the
+    reference's order: (abi.VERTEX_DTYPE array, abi.FACE_DTYPE array) -- what b32_room_build_mesh leaves in a slot, and what a host
+    without it computes per drag.  As on the device, a float that is a NaN is written as 0x7FC00000."""
+    f32 = np.float32
+    f = np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+    m = np.ascontiguousarray(materials, abi.FACE_MATERIAL_DTYPE).reshape(-1)
+    if len(f) != len(m):
+        raise ValueError("room_mesh: one material per face")
+    g = _room_grid(grid)[0]
+    n = len(f)
+    px, py, pz = (f32(v) for v in g["position"]); S = f32(g["sector_size"])
+    sides, nv_rec, nf_rec = _room_mesh_layout(f, m)
+    kind = np.minimum(f["kind"], 7).astype(np.intp)
+    flat = kind < 2
+    mode = m["normal_mode"]
+    rec = np.arange(n)[:, None]
+    neg = f32(-1.0)
+    with np.errstate(all="ignore"):
+        bx = px + f["gx"].astype(f32) * S
+        bz = pz + f["gz"].astype(f32) * S
+        bxs, bzs = bx + S, bz + S
+        # ---- floors and ceilings: slot s is corner s % 3 of rendered triangle s / 3
+        s12 = np.arange(12)
+        t, j = (s12 // 3)[None, :], (s12 % 3)[None, :]
+        second = t >= sides[:, None]
+        back = (mode[:, None] == abi.NORMAL_BACK) | ((mode[:, None] == abi.NORMAL_BOTH) & ((t & 1) == 1))
+        c = _ROOM_TRI[np.minimum(m["split_direction"], 1).astype(np.intp)[:, None], second.astype(np.intp), j]
+        has_h2 = (m["flags"] & abi.MAT_HAS_HEIGHTS_2) != 0
+        hsets = np.stack([f["heights"], np.where(has_h2[:, None], m["heights_2"], f["heights"])], axis=1).astype(f32)   # (n, 2, 4)
+        hsel = hsets[rec, second.astype(np.intp)]                                  # (n, 12, 4)
+        east, south = (c == 1) | (c == 2), c >= 2
+        hpos = np.stack([np.where(east, bxs[:, None], bx[:, None]), py + np.take_along_axis(hsel, c[..., None], 2)[..., 0],
+                         np.where(south, bzs[:, None], bz[:, None])], axis=-1)
+        y0 = py + hsets[..., 0]
+        e1 = ((bxs - bx)[:, None], (py + hsets[..., 1]) - y0, (bz - bz)[:, None])
+        e2 = ((bx - bx)[:, None], (py + hsets[..., 3]) - y0, (bzs - bz)[:, None])
+        fl = (kind == 0)[:, None]
+        a = tuple(np.where(fl, u, v) for u, v in zip(e2, e1))                      # floor: edge2.cross(edge1); ceiling: edge1.cross(edge2)
+        b = tuple(np.where(fl, u, v) for u, v in zip(e1, e2))
+        nx = a[1] * b[2] - a[2] * b[1]
+        ny = a[2] * b[0] - a[0] * b[2]
+        nz = a[0] * b[1] - a[1] * b[0]
+        ln = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        nrm = np.stack([np.where(ln == 0, f32(0.0), q / ln) for q in (nx, ny, nz)], axis=-1).astype(f32)       # (n, 2, 3)
+        hnrm = nrm[rec, second.astype(np.intp)]
+        hnrm = np.where(back[..., None], hnrm * neg, hnrm)
+        w1, w2 = m["tex_width"], m["tex_width_2"]
+        first = ~second | (((m["flags"] & abi.MAT_HAS_UV_2) == 0) & (w1 == w2))[:, None]
+        has = np.where(first, ((m["flags"] & abi.MAT_HAS_UV) != 0)[:, None], ((m["flags"] & abi.MAT_HAS_UV_2) != 0)[:, None])
+        sc = f32(32.0) / np.where(first, w1[:, None], w2[:, None]).astype(f32)
+        uo, vo = f["gx"].astype(f32)[:, None] * sc, f["gz"].astype(f32)[:, None] * sc
+        duv = np.stack([np.where(east, uo + sc, uo), np.where(south, vo + sc, vo)], axis=-1)
+        ouv = np.where(first[..., None], m["uv"][rec, c], m["uv_2"][rec, c])
+        huv = np.where(has[..., None], ouv, duv)
+        hcol = np.where(second[..., None], m["colors_2"][rec, c], m["colors"][rec, c])
+        # ---- walls: slot s is corner s % 4 of side s / 4; a diagonal's corner i is the hover's corner i ^ 1
+        side, i = (s12 // 4)[None, :], np.broadcast_to((s12 % 4)[None, :], (n, 12))
+        wback = (mode[:, None] == abi.NORMAL_BACK) | (side != 0)
+        k = np.where((kind >= 6)[:, None], i ^ 1, i)
+        wpos = np.stack([np.where(_ROOM_XSEL[kind[:, None], k], bxs[:, None], bx[:, None]), py + f["heights"][rec, k],
+                         np.where(_ROOM_ZSEL[kind[:, None], k], bzs[:, None], bz[:, None])], axis=-1)
+        d = f32(1.0) / np.sqrt(f32(2.0))
+        z = f32(0.0)
+        table = np.array([[z, z, z], [z, z, z], [z, z, 1], [-1, z, z], [z, z, -1], [1, z, z], [d, z, -d], [d, z, d]], f32)
+        wnrm = np.broadcast_to(table[kind][:, None, :], (n, 12, 3))
+        wnrm = np.where(wback[..., None], wnrm * neg, wnrm)
+        ws = (f32(32.0) / w1.astype(f32))[:, None]
+        along = np.where((kind == 3) | (kind == 5), f["gz"], f["gx"]).astype(f32)[:, None] * ws
+        right = (i == 1) | (i == 2)
+        wuv = np.stack([np.where(right, along + ws, along), np.where(i < 2, ws, f32(0.0))], axis=-1)
+        wuv = np.where(((m["flags"] & abi.MAT_HAS_UV) != 0)[:, None, None], m["uv"][rec, i], wuv)
+        proj = ((-(py + f["heights"][rec, i])) / S) * ws
+        wuv[..., 1] = np.where((m["uv_projection"] == abi.UV_PROJECTED)[:, None], proj, wuv[..., 1])
+        wcol = m["colors"][rec, i]
+    fl3 = flat[:, None, None]
+    valid = s12[None, :] < nv_rec[:, None]
+    v = T.make_vertices(int(nv_rec.sum()))
+    for name, hh, ww in (("pos", hpos, wpos), ("uv", huv, wuv), ("normal", hnrm, wnrm)):
+        arr = np.ascontiguousarray(np.where(fl3, hh, ww)[valid], f32)
+        arr.view(np.uint32)[np.isnan(arr)] = 0x7FC00000
+        v[name] = arr
+    col = np.where(fl3, hcol, wcol)[valid]
+    v["r"], v["g"], v["b"], v["blend"] = col[:, 0], col[:, 1], col[:, 2], col[:, 3]
+    # ---- faces: slot k < 2 * sides; indices are absolute
+    first_v = (np.cumsum(nv_rec) - nv_rec).astype(np.int64)[:, None]
+    k4 = np.arange(4)[None, :]
+    hsecond = k4 >= sides[:, None]
+    hback = (mode[:, None] == abi.NORMAL_BACK) | ((mode[:, None] == abi.NORMAL_BOTH) & ((k4 & 1) == 1))
+    flip = np.where(hback, (kind == 0)[:, None], (kind != 0)[:, None])
+    hb = first_v + 3 * k4
+    hidx = np.stack([hb, np.where(flip, hb + 2, hb + 1), np.where(flip, hb + 1, hb + 2)], axis=-1)
+    htex = np.where(hsecond, m["texture_id_2"][:, None], m["texture_id"][:, None])
+    wside, ww = k4 // 2, k4 % 2
+    wb = first_v + 4 * wside
+    wbk = (mode[:, None] == abi.NORMAL_BACK) | (wside != 0)
+    widx = np.stack([wb, np.where(wbk, wb + 1 + ww, wb + 2 + ww), np.where(wbk, wb + 2 + ww, wb + 1 + ww)], axis=-1)
+    fvalid = k4 < nf_rec[:, None]
+    out = np.zeros(int(nf_rec.sum()), abi.FACE_DTYPE)
+    out["v"] = np.where(fl3, hidx, widx)[fvalid].astype(np.uint32)
+    out["texture_id"] = np.where(flat[:, None], htex, m["texture_id"][:, None])[fvalid]
+    out["black_transparent"] = np.broadcast_to((m["black_transparent"] != 0)[:, None], (n, 4))[fvalid]
+    out["blend_mode"] = np.broadcast_to(m["blend_mode"][:, None], (n, 4))[fvalid]
+    out["editor_alpha"] = 255
+    return v, out
+
+
 def _room_grid(grid):
     """(position, sector_size) or an abi.ROOM_GRID_DTYPE record -> one abi.ROOM_GRID_DTYPE record."""
     if isinstance(grid, np.ndarray) and grid.dtype == abi.ROOM_GRID_DTYPE:
@@ -859,6 +1048,31 @@ class Room:
         g = _room_grid(grid) if grid is not None else None
         _chk(self.ctx.lib.b32_room_update(self.ctx.h, self._h, g.ctypes.data if g is not None else None, int(first), len(f),
                                           f.ctypes.data if len(f) else None), "b32_room_update")
+
+    def set_materials(self, materials):
+        """b32_room_set_materials: one abi.FACE_MATERIAL_DTYPE record per face (room_materials_from_sectors)."""
+        m = np.ascontiguousarray(materials, abi.FACE_MATERIAL_DTYPE).reshape(-1)
+        if len(m) != self.n:
+            raise ValueError("set_materials: one material per face")
+        _chk(self.ctx.lib.b32_room_set_materials(self.ctx.h, self._h, m.ctypes.data if len(m) else None), "b32_room_set_materials")
+
+    def update_materials(self, first, materials):
+        """b32_room_update_materials: records [first, first + len(materials)); ordered on the stream like update()."""
+        m = np.ascontiguousarray(materials, abi.FACE_MATERIAL_DTYPE).reshape(-1)
+        _chk(self.ctx.lib.b32_room_update_materials(self.ctx.h, self._h, int(first), len(m), m.ctypes.data if len(m) else None), "b32_room_update_materials")
+
+    def mesh_counts(self):
+        """b32_room_mesh_counts: (n_vertices, n_faces) of the mesh build_mesh would write now."""
+        nv, nf = C.c_uint32(), C.c_uint32()
+        _chk(self.ctx.lib.b32_room_mesh_counts(self._h, C.byref(nv), C.byref(nf)), "b32_room_mesh_counts")
+        return int(nv.value), int(nf.value)
+
+    def build_mesh(self, scene=None):
+        """b32_room_build_mesh: the room's render mesh into `scene` (a ResidentScene, detached or not; None: the context's resident
+        scene), whose textures stay and whose geometry is replaced.  One launch, no upload, no host synchronisation."""
+        _chk(self.ctx.lib.b32_room_build_mesh(self.ctx.h, self._h, scene._handle() if scene is not None else None), "b32_room_build_mesh")
+        if scene is not None:
+            scene.n_vertices, scene.n_faces = self.mesh_counts()
 
     def close(self):
         if self._h and getattr(self.ctx, "h", None):
@@ -2398,6 +2612,13 @@ class ResidentScene:
         count = self.n_vertices - first if count is None else count
         out = np.zeros(max(count, 0), abi.VERTEX_DTYPE)
         _chk(self.ctx.lib.b32_scene_read_vertices(self.ctx.h, self._handle(), first, count, abi.ptr(out) if count > 0 else None), "scene_read_vertices")
+        return out
+
+    def read_faces(self, first=0, count=None):
+        """b32_scene_read_faces (blocking): the slot's faces as they are on the device now."""
+        count = self.n_faces - first if count is None else count
+        out = np.zeros(max(count, 0), abi.FACE_DTYPE)
+        _chk(self.ctx.lib.b32_scene_read_faces(self.ctx.h, self._handle(), first, count, abi.ptr(out) if count > 0 else None), "scene_read_faces")
         return out
 
     def _pack(self, camera, settings, fog):

@@ -253,6 +253,17 @@ def make_sector_faces(n):
     return np.zeros(n, dtype=abi.SECTOR_FACE_DTYPE)
 
 
+def make_face_materials(n):
+    """n B32FaceMaterial records (abi.FACE_MATERIAL_DTYPE) with the reference's defaults: texture (0, 64) on both triangles, Color::NEUTRAL
+    corners, Front, NwSe, Default projection, Opaque, black_transparent, no overrides."""
+    m = np.zeros(n, dtype=abi.FACE_MATERIAL_DTYPE)
+    m["tex_width"] = m["tex_width_2"] = 64
+    m["colors"][..., :3] = 128
+    m["colors_2"][..., :3] = 128
+    m["black_transparent"] = 1
+    return m
+
+
 def pack_fog(fog):
     """fog: None or (start, falloff, cull_distance, Color) as in render.rs:2309."""
     if fog is None:

@@ -643,6 +643,71 @@ int  b32_room_box_select_async(b32_ctx* ctx, const B32Camera* camera, b32_room* 
                                const float* points_xyz /* 3 * n_points, nullable */, uint32_t n_points,
                                void* out /* 16 + 4 * ceil((n + n_points) / 32) bytes */, uint64_t* ticket);
 
+/* ---- a room's render mesh, built on the device from its resident sector table ------------------------------------------------------------
+ * render_scene calls Room::to_render_data_with_textures (world/geometry.rs:2839-3352) for every room on every frame; a host of this
+ * library keeps the result in a scene slot and has to re-run it, upload 36 bytes per vertex and wait whenever the editor drags a height.
+ * The room's heights are resident already (b32_room_update), so the mesh is made where they are: b32_room_build_mesh writes the
+ * vertices and faces of that function into a slot's own geometry with one launch on the context's stream.
+ *
+ * One B32FaceMaterial per B32SectorFace, in the same order, holds everything add_horizontal_face_to_render_data, add_wall_to_render_data
+ * and add_diagonal_wall_to_render_data read besides the grid and the heights; the host resolves the Options as the reference's getters
+ * do (geometry.rs:1193-1210):
+ *   texture_id, tex_width       resolve_texture(&face.texture).unwrap_or((0, 64)); uv_scale = 32.0 / (tex_width as f32), a width of 0 gives inf
+ *   texture_id_2, tex_width_2   floor and ceiling only: the same of get_texture_2()
+ *   uv, B32_MAT_HAS_UV          face.uv; without the flag the world-aligned defaults from (gx, gz) and uv_scale
+ *   uv_2, B32_MAT_HAS_UV_2      get_uv_2(), that is uv_2.or(uv): the flag is set when EITHER is Some; without it triangle 2 has triangle 1's
+ *                               UVs when the widths are equal, else the defaults at its own scale
+ *   colors, colors_2            r, g, b, blend per corner; colors_2 is get_colors_2() (floor and ceiling only)
+ *   heights_2, B32_MAT_HAS_HEIGHTS_2   triangle 2's heights; without the flag the record's own (the hover never reads them)
+ *   normal_mode 0 Front 1 Both 2 Back; split_direction 0 NwSe 1 NeSw; uv_projection 0 Default 1 Projected (walls); blend_mode; black_transparent
+ * Where a record's output lies depends on (kind, normal_mode) alone: a floor or ceiling emits 6 vertices and 2 faces per rendered side
+ * (triangle 1 front, triangle 1 back, triangle 2 front, triangle 2 back), a wall 4 vertices and 2 faces per side (front, then back); Both
+ * renders two sides.  The room keeps kinds and modes on the host with the prefix sums of those counts and uploads the sums in stream order
+ * whenever b32_room_update or b32_room_update_materials changes a kind or a mode; b32_room_mesh_counts is a pure host function.
+ * A face's indices are absolute (vertices.len() in the reference), editor_alpha is 255.  The arithmetic is the reference's, each
+ * operation rounded separately (csrc/b32_room_mesh_body.h), with one exception: a float of a vertex that is a NaN is written as
+ * 0x7FC00000 -- the sign of a generated NaN is the machine's, not the reference's.
+ *
+ * b32_room_set_materials copies the whole table (n records); b32_room_update_materials a range, with b32_room_update's contract: the data
+ * is copied before return and ordered on the context's stream; first + count > n or normal_mode > 2, split_direction > 1,
+ * uv_projection > 1, blend_mode > 5 in any record -> B32_E_ARG, nothing changed (also for a range before any table was set).
+ * b32_room_build_mesh(ctx, room, slot): the slot (NULL: the context's resident scene) must hold an uploaded scene -- its textures stay, its
+ * geometry, of which it may have had none (an upload with nv == nf == 0 is legal), is replaced, a rig is dropped (b32_scene_pose then
+ * returns B32_E_ARG), merged runs that hold the slot are rebuilt.  A pending frame that may still be redrawn is settled first.  No host
+ * synchronisation unless the slot's buffers have to grow.  Works for RGB555 and 8-bit-colour slots.  No materials set, no scene in the
+ * slot -> B32_E_ARG.  b32_scene_read_faces is b32_scene_read_vertices for the faces (blocking; for tests). */
+typedef struct B32FaceMaterial {
+    uint32_t texture_id, tex_width;
+    uint32_t texture_id_2, tex_width_2;
+    float    uv[4][2];
+    float    uv_2[4][2];
+    uint8_t  colors[4][4];                    /* r, g, b, blend */
+    uint8_t  colors_2[4][4];
+    float    heights_2[4];
+    uint8_t  normal_mode, split_direction, uv_projection, blend_mode, black_transparent, flags;
+    uint8_t  _pad[2];
+} B32FaceMaterial;                            /* 136 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(B32FaceMaterial) == 136, "B32FaceMaterial layout");
+#else
+_Static_assert(sizeof(B32FaceMaterial) == 136, "B32FaceMaterial layout");
+#endif
+#define B32_MAT_HAS_UV 1u
+#define B32_MAT_HAS_UV_2 2u
+#define B32_MAT_HAS_HEIGHTS_2 4u
+#define B32_NORMAL_FRONT 0u
+#define B32_NORMAL_BOTH 1u
+#define B32_NORMAL_BACK 2u
+#define B32_SPLIT_NWSE 0u
+#define B32_SPLIT_NESW 1u
+#define B32_UV_DEFAULT 0u
+#define B32_UV_PROJECTED 1u
+int  b32_room_set_materials(b32_ctx* ctx, b32_room* room, const B32FaceMaterial* materials /* n records */);
+int  b32_room_update_materials(b32_ctx* ctx, b32_room* room, uint32_t first, uint32_t count, const B32FaceMaterial* materials);
+int  b32_room_mesh_counts(const b32_room* room, uint32_t* n_vertices, uint32_t* n_faces);
+int  b32_room_build_mesh(b32_ctx* ctx, b32_room* room, b32_scene* slot /* NULL: the context's resident scene */);
+int  b32_scene_read_faces(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t first, uint32_t count, B32Face* out);  /* blocking */
+
 /* ---- the 8-bit-colour path: render_mesh (render.rs:1971-2264) + rasterize_triangle (render.rs:1202-1433) ----
  * What every caller of the reference runs when settings.use_rgb555 is false (scene.rs:163-169).  Same pipeline and settings
  * as render_mesh_15 except: Texture texels are Color values with a per-texel blend mode, no fog, no opaque/transparent

@@ -1,0 +1,895 @@
+"""b32_room_build_mesh: Room::to_render_data_with_textures (world/geometry.rs:2839-3352) on the device, from a room's resident sector
+table and one B32FaceMaterial per record.
+
+Four statements of the same function are compared bit for bit, vertices and faces as raw bytes:
+  (a) ref_room_mesh              a literal scalar restatement of the Rust text, written from the reference (below, with path:line)
+  (b) b32.room_mesh              the package's vectorised numpy f32 mirror (the expected value of the GPU tests)
+  (c) csrc/b32_room_mesh_body.h  the device header, compiled for the host (tests/cpp/room_mesh_host.cpp) and, on the GPU, k_room_mesh
+  (d) the golden room scenes     tests/golden/scenes/real/*-room0-*.b32scene: the reference's sample levels through this function
+One thing is not the reference's: the sign and payload of a NaN belong to the machine that made it (inf - inf is 0xFFC00000 on x86,
+0x7FC00000 on the device), so (b) and (c) write every NaN as 0x7FC00000 and (a), which does not, is compared after the same mapping.
+"""
+import atexit
+import ctypes as C
+import functools
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+import bonnie32_amd as b32
+from bonnie32_amd import abi, scenefile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOMS = os.path.join(ROOT, "tests", "golden", "rooms")
+REAL = os.path.join(ROOT, "tests", "golden", "scenes", "real")
+f32 = np.float32
+QNAN = 0x7FC00000
+REAL_ROOMS = {"dungeon": ("dungeon-room0-game", "dungeon-room0-painter"), "cave": ("cave-room0-game",),
+              "cathedral": ("cathedral-room0-game-640",), "sewers": ("sewers-room0-painter",)}
+REAL_COUNTS = {"dungeon": (204, 1062, 408), "cave": (98, 548, 196), "cathedral": (1029, 5480, 2058), "sewers": (105, 512, 210)}
+
+
+# ================================================================== (a) the literal restatement
+def v_sub(a, b):                                                 # impl Sub for Vec3, math.rs:71-79
+    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+
+def v_cross(a, b):                                               # Vec3::cross, math.rs:27-33
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def v_normalize(a):                                              # Vec3::len / normalize, math.rs:35-49
+    l = np.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
+    if l == f32(0.0):
+        return (f32(0.0), f32(0.0), f32(0.0))
+    return (a[0] / l, a[1] / l, a[2] / l)
+
+
+def v_scale(a, s):                                               # Vec3::scale, math.rs:51-57
+    return (a[0] * s, a[1] * s, a[2] * s)
+
+
+class RefMesh:
+    def __init__(self):
+        self.vertices, self.faces = [], []
+
+    def add_triangle(self, corners, c, uvs, colors, normal, texture_id, flip_winding, black_transparent, blend_mode):   # geometry.rs:3010-3027
+        base_idx = len(self.vertices)
+        for k in c:
+            self.vertices.append((corners[k], uvs[k], normal, colors[k]))
+        if flip_winding:
+            self.faces.append((base_idx, base_idx + 2, base_idx + 1, texture_id, black_transparent, blend_mode))
+        else:
+            self.faces.append((base_idx, base_idx + 1, base_idx + 2, texture_id, black_transparent, blend_mode))
+
+    def add_quad(self, corners, uvs, front_normal, colors, normal_mode, texture_id, black_transparent, blend_mode):     # geometry.rs:3205-3230, :3326-3351
+        render_front = normal_mode != abi.NORMAL_BACK
+        render_back = normal_mode != abi.NORMAL_FRONT
+        if render_front:
+            base_idx = len(self.vertices)
+            for i in range(4):
+                self.vertices.append((corners[i], uvs[i], front_normal, colors[i]))
+            self.faces.append((base_idx, base_idx + 2, base_idx + 1, texture_id, black_transparent, blend_mode))
+            self.faces.append((base_idx, base_idx + 3, base_idx + 2, texture_id, black_transparent, blend_mode))
+        if render_back:
+            base_idx = len(self.vertices)
+            back_normal = v_scale(front_normal, f32(-1.0))
+            for i in range(4):
+                self.vertices.append((corners[i], uvs[i], back_normal, colors[i]))
+            self.faces.append((base_idx, base_idx + 1, base_idx + 2, texture_id, black_transparent, blend_mode))
+            self.faces.append((base_idx, base_idx + 2, base_idx + 3, texture_id, black_transparent, blend_mode))
+
+
+def ref_horizontal(mesh, f, m, pos_y, S, base_x, base_z, is_floor):          # add_horizontal_face_to_render_data, geometry.rs:2906-3048
+    grid_x, grid_z = int(f["gx"]), int(f["gz"])
+    h1 = [f32(h) for h in f["heights"]]
+    h2 = [f32(h) for h in m["heights_2"]] if m["flags"] & abi.MAT_HAS_HEIGHTS_2 else h1                 # get_heights_2, :1208-1210
+    corners_1 = [(base_x, pos_y + h1[0], base_z), (base_x + S, pos_y + h1[1], base_z),
+                 (base_x + S, pos_y + h1[2], base_z + S), (base_x, pos_y + h1[3], base_z + S)]          # :2923-2928
+    corners_2 = [(base_x, pos_y + h2[0], base_z), (base_x + S, pos_y + h2[1], base_z),
+                 (base_x + S, pos_y + h2[2], base_z + S), (base_x, pos_y + h2[3], base_z + S)]          # :2932-2937
+    texture_id_1, tex_width_1 = int(m["texture_id"]), int(m["tex_width"])                               # :2940-2941
+    texture_id_2, tex_width_2 = int(m["texture_id_2"]), int(m["tex_width_2"])
+    uv_scale_1 = f32(32.0) / f32(tex_width_1)                                                            # :2944-2945
+    uv_scale_2 = f32(32.0) / f32(tex_width_2)
+
+    def default_uvs(s):                                                                                  # :2949-2958, :2966-2973
+        u_offset = f32(grid_x) * s
+        v_offset = f32(grid_z) * s
+        return [(u_offset, v_offset), (u_offset + s, v_offset), (u_offset + s, v_offset + s), (u_offset, v_offset + s)]
+    uvs_1 = [tuple(f32(x) for x in uv) for uv in m["uv"]] if m["flags"] & abi.MAT_HAS_UV else default_uvs(uv_scale_1)
+    if m["flags"] & abi.MAT_HAS_UV_2:                                                                    # get_uv_2, :1198-1200
+        uvs_2 = [tuple(f32(x) for x in uv) for uv in m["uv_2"]]
+    elif tex_width_1 == tex_width_2:                                                                     # :2961-2975
+        uvs_2 = uvs_1
+    else:
+        uvs_2 = default_uvs(uv_scale_2)
+    colors_1 = [tuple(int(x) for x in c) for c in m["colors"]]                                           # :2978-2979
+    colors_2 = [tuple(int(x) for x in c) for c in m["colors_2"]]
+    render_front = m["normal_mode"] != abi.NORMAL_BACK                                                   # :2982-2983
+    render_back = m["normal_mode"] != abi.NORMAL_FRONT
+    tri1, tri2 = ((0, 1, 2), (0, 2, 3)) if m["split_direction"] == abi.SPLIT_NWSE else ((0, 1, 3), (1, 2, 3))    # :2986-2988
+    edge1_t1 = v_sub(corners_1[1], corners_1[0])                                                         # :2991-2998
+    edge2_t1 = v_sub(corners_1[3], corners_1[0])
+    front_normal_1 = v_normalize(v_cross(edge2_t1, edge1_t1)) if is_floor else v_normalize(v_cross(edge1_t1, edge2_t1))
+    back_normal_1 = v_scale(front_normal_1, f32(-1.0))
+    edge1_t2 = v_sub(corners_2[1], corners_2[0])                                                         # :3000-3007
+    edge2_t2 = v_sub(corners_2[3], corners_2[0])
+    front_normal_2 = v_normalize(v_cross(edge2_t2, edge1_t2)) if is_floor else v_normalize(v_cross(edge1_t2, edge2_t2))
+    back_normal_2 = v_scale(front_normal_2, f32(-1.0))
+    bt, bm = int(m["black_transparent"] != 0), int(m["blend_mode"])
+    if render_front:                                                                                     # :3030-3047
+        mesh.add_triangle(corners_1, tri1, uvs_1, colors_1, front_normal_1, texture_id_1, not is_floor, bt, bm)
+    if render_back:
+        mesh.add_triangle(corners_1, tri1, uvs_1, colors_1, back_normal_1, texture_id_1, is_floor, bt, bm)
+    if render_front:
+        mesh.add_triangle(corners_2, tri2, uvs_2, colors_2, front_normal_2, texture_id_2, not is_floor, bt, bm)
+    if render_back:
+        mesh.add_triangle(corners_2, tri2, uvs_2, colors_2, back_normal_2, texture_id_2, is_floor, bt, bm)
+
+
+def ref_wall_uvs(f, m, y_offset, S, corner_u, uv_scale):                     # geometry.rs:3165-3203, :3294-3324
+    base_uvs = [tuple(f32(x) for x in uv) for uv in m["uv"]] if m["flags"] & abi.MAT_HAS_UV else \
+        [(corner_u[0], uv_scale), (corner_u[1], uv_scale), (corner_u[2], f32(0.0)), (corner_u[3], f32(0.0))]
+    if m["uv_projection"] == abi.UV_PROJECTED:
+        world_heights = [y_offset + f32(h) for h in f["heights"]]
+        return [(base_uvs[i][0], -world_heights[i] / S * uv_scale) for i in range(4)]
+    return base_uvs
+
+
+def ref_wall(mesh, f, m, y_offset, S, base_x, base_z):                       # add_wall_to_render_data, geometry.rs:3051-3231
+    h = [f32(x) for x in f["heights"]]
+    kind = int(f["kind"])
+    one, zero = f32(1.0), f32(0.0)
+    if kind == abi.ROOM_WALL_NORTH:                                                                      # :3072-3081
+        corners = [(base_x, y_offset + h[0], base_z), (base_x + S, y_offset + h[1], base_z), (base_x + S, y_offset + h[2], base_z), (base_x, y_offset + h[3], base_z)]
+        front_normal = (zero, zero, one)
+    elif kind == abi.ROOM_WALL_EAST:                                                                     # :3082-3091
+        corners = [(base_x + S, y_offset + h[0], base_z), (base_x + S, y_offset + h[1], base_z + S), (base_x + S, y_offset + h[2], base_z + S), (base_x + S, y_offset + h[3], base_z)]
+        front_normal = (-one, zero, zero)
+    elif kind == abi.ROOM_WALL_SOUTH:                                                                    # :3092-3101
+        corners = [(base_x + S, y_offset + h[0], base_z + S), (base_x, y_offset + h[1], base_z + S), (base_x, y_offset + h[2], base_z + S), (base_x + S, y_offset + h[3], base_z + S)]
+        front_normal = (zero, zero, -one)
+    else:                                                                                                # West, :3102-3111
+        corners = [(base_x, y_offset + h[0], base_z + S), (base_x, y_offset + h[1], base_z), (base_x, y_offset + h[2], base_z), (base_x, y_offset + h[3], base_z + S)]
+        front_normal = (one, zero, zero)
+    uv_scale = f32(32.0) / f32(int(m["tex_width"]))                                                      # :3143-3144
+    if kind in (abi.ROOM_WALL_NORTH, abi.ROOM_WALL_SOUTH):                                               # :3150-3159
+        u = f32(int(f["gx"])) * uv_scale
+    else:
+        u = f32(int(f["gz"])) * uv_scale
+    u_left, u_right = u, u + uv_scale
+    uvs = ref_wall_uvs(f, m, y_offset, S, [u_left, u_right, u_right, u_left], uv_scale)
+    mesh.add_quad(corners, uvs, front_normal, [tuple(int(x) for x in c) for c in m["colors"]], m["normal_mode"], int(m["texture_id"]),
+                  int(m["black_transparent"] != 0), int(m["blend_mode"]))
+
+
+def ref_diagonal(mesh, f, m, y_offset, S, base_x, base_z):                   # add_diagonal_wall_to_render_data, geometry.rs:3235-3352
+    h = [f32(x) for x in f["heights"]]
+    n = f32(1.0) / np.sqrt(f32(2.0))
+    if int(f["kind"]) == abi.ROOM_WALL_NWSE:                                                             # :3256-3267
+        corners = [(base_x + S, y_offset + h[1], base_z + S), (base_x, y_offset + h[0], base_z), (base_x, y_offset + h[3], base_z), (base_x + S, y_offset + h[2], base_z + S)]
+        front_normal = (n, f32(0.0), -n)
+    else:                                                                                                # :3268-3280
+        corners = [(base_x, y_offset + h[1], base_z + S), (base_x + S, y_offset + h[0], base_z), (base_x + S, y_offset + h[3], base_z), (base_x, y_offset + h[2], base_z + S)]
+        front_normal = (n, f32(0.0), n)
+    uv_scale = f32(32.0) / f32(int(m["tex_width"]))                                                      # :3283-3284
+    u_left = f32(int(f["gx"])) * uv_scale                                                                # :3288-3291
+    u_right = u_left + uv_scale
+    uvs = ref_wall_uvs(f, m, y_offset, S, [u_left, u_right, u_right, u_left], uv_scale)
+    mesh.add_quad(corners, uvs, front_normal, [tuple(int(x) for x in c) for c in m["colors"]], m["normal_mode"], int(m["texture_id"]),
+                  int(m["black_transparent"] != 0), int(m["blend_mode"]))
+
+
+def ref_room_mesh(faces, mats, grid):
+    """to_render_data_with_textures, geometry.rs:2839-2903: the records are iter_sectors' order already."""
+    g = np.ascontiguousarray(grid, abi.ROOM_GRID_DTYPE).reshape(-1)[0]
+    px, py, pz = (f32(x) for x in g["position"])
+    S = f32(g["sector_size"])
+    mesh = RefMesh()
+    with np.errstate(all="ignore"):
+        for f, m in zip(faces, mats):
+            base_x = px + f32(int(f["gx"])) * S                                                          # :2847-2848
+            base_z = pz + f32(int(f["gz"])) * S
+            kind = int(f["kind"])
+            if kind < 2:
+                ref_horizontal(mesh, f, m, py, S, base_x, base_z, kind == abi.ROOM_FLOOR)
+            elif kind < 6:
+                ref_wall(mesh, f, m, py, S, base_x, base_z)
+            else:
+                ref_diagonal(mesh, f, m, py, S, base_x, base_z)
+    v = np.zeros(len(mesh.vertices), abi.VERTEX_DTYPE)
+    if len(v):
+        v["pos"] = np.array([x[0] for x in mesh.vertices], f32); v["uv"] = np.array([x[1] for x in mesh.vertices], f32)
+        v["normal"] = np.array([x[2] for x in mesh.vertices], f32)
+        col = np.array([x[3] for x in mesh.vertices], np.uint8)
+        v["r"], v["g"], v["b"], v["blend"] = col[:, 0], col[:, 1], col[:, 2], col[:, 3]
+    out = np.zeros(len(mesh.faces), abi.FACE_DTYPE)
+    if len(out):
+        ff = np.array(mesh.faces, np.int64)
+        out["v"] = ff[:, 0:3]; out["texture_id"] = ff[:, 3]; out["black_transparent"] = ff[:, 4]; out["blend_mode"] = ff[:, 5]
+        out["editor_alpha"] = 255
+    return canon_nans(v), out
+
+
+def canon_nans(v):
+    """Every NaN of the vertices' floats as 0x7FC00000 (see the module's docstring)."""
+    v = v.copy()
+    for k in ("pos", "uv", "normal"):
+        a = np.ascontiguousarray(v[k])
+        a.view(np.uint32)[np.isnan(a)] = QNAN
+        v[k] = a
+    return v
+
+
+def same(a, b):
+    return a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+# ================================================================== rooms
+def grid_of(position=(0.0, 0.0, 0.0), sector_size=abi.SECTOR_SIZE):
+    g = np.zeros(1, abi.ROOM_GRID_DTYPE)
+    g["position"][0] = position; g["sector_size"] = sector_size
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def real_room(name):
+    """(faces, materials, grid) of tests/golden/rooms/<name>-room0[.materials].npz."""
+    z = np.load(os.path.join(ROOMS, name + "-room0.npz"))
+    m = np.load(os.path.join(ROOMS, name + "-room0.materials.npz"))["materials"]
+    return z["faces"].astype(abi.SECTOR_FACE_DTYPE), m.astype(abi.FACE_MATERIAL_DTYPE), z["grid"].astype(abi.ROOM_GRID_DTYPE)
+
+
+@functools.lru_cache(maxsize=None)
+def real_scene(scene):
+    return scenefile.read_scene(os.path.join(REAL, scene + ".b32scene"))
+
+
+@functools.lru_cache(maxsize=None)
+def real_mesh(name):
+    """The mirror's mesh of a real room: computed once, shared by the host and the GPU tests."""
+    return b32.room_mesh(*real_room(name))
+
+
+TEX_TABLE = {"t0": (0, 64), "t1": (1, 32), "t2": (2, 48), "t3": (3, 128), "t4": (4, 256), "t5": (5, 0), "t6": (1, 64)}
+BLENDS = ("Opaque", "Average", "Add", "Subtract", "AddQuarter", "Erase")
+MODES = ("Front", "Both", "Back")
+
+
+def resolve(ref):
+    return TEX_TABLE.get(ref["name"]) if ref and ref.get("name") else None       # (an unknown or empty name: unwrap_or((0, 64)))
+
+
+def random_room(seed, n=None, flavour="mixed", width=6, depth=5):
+    """(faces, materials, grid) of a random room with what the real rooms lack: Both and Back on every kind, uv_2 with and without uv,
+    colors_2, heights_2, every blend mode, widths 0 / 32 / 48 / 128 / 256 (unequal on the two triangles), heights off the lattice and,
+    for flavour "wild", NaN and inf heights and a sector size of 0 (where normalize returns ZERO); several walls per side.
+    flavour "both": every record Both; "drawable": finite heights, widths of the textures a frame test uploads, a few Average faces.
+    n: exactly that many records (the grid grows until there are enough; records are independent, so the tail is cut)."""
+    rng = np.random.default_rng(seed)
+    wild, drawable = flavour == "wild", flavour == "drawable"
+
+    def height(lo, hi):
+        if wild and rng.random() < 0.08:
+            return float(rng.choice([np.nan, np.inf, -np.inf, 0.0, -0.0]))
+        return float(f32(rng.uniform(lo, hi))) if rng.random() < 0.7 else float(rng.choice([0.0, 256.0, 512.0, 1024.0]))
+
+    def colors():
+        return [{"r": int(rng.integers(0, 256)), "g": int(rng.integers(0, 256)), "b": int(rng.integers(0, 256)), "blend": str(rng.choice(BLENDS))} for _ in range(4)]
+
+    def uvs():
+        return [{"x": float(f32(rng.uniform(-2, 2))), "y": float(f32(rng.uniform(-2, 2)))} for _ in range(4)]
+
+    def common(face, lo, hi):
+        face["heights"] = [height(lo, hi) for _ in range(4)]
+        names = ["t0", "t1", "t6"] if drawable else list(TEX_TABLE) + ["", "nosuch"]
+        face["texture"] = {"pack": "p", "name": str(rng.choice(names))}
+        face["colors"] = colors() if not drawable else [{"r": 128, "g": int(rng.integers(90, 160)), "b": 128, "blend": "Opaque"} for _ in range(4)]
+        face["normal_mode"] = "Both" if flavour == "both" else str(rng.choice(MODES))
+        face["blend_mode"] = (str(rng.choice(["Opaque", "Opaque", "Average"])) if drawable else str(rng.choice(BLENDS)))
+        face["black_transparent"] = bool(rng.random() < 0.7)
+        if rng.random() < 0.4:
+            face["uv"] = uvs()
+        return face
+
+    def horizontal(lo, hi):
+        face = common({}, lo, hi)
+        if rng.random() < 0.5:
+            face["texture_2"] = {"pack": "p", "name": str(rng.choice(["t0", "t1", "t6"] if drawable else list(TEX_TABLE)))}
+        if rng.random() < 0.4:
+            face["uv_2"] = uvs()
+        if rng.random() < 0.4:
+            face["colors_2"] = colors() if not drawable else face["colors"]
+        if rng.random() < 0.5:
+            face["heights_2"] = [height(lo, hi) for _ in range(4)]
+        face["split_direction"] = str(rng.choice(["NwSe", "NeSw"]))
+        return face
+
+    def wall():
+        face = common({}, 0.0, 2048.0)
+        face["uv_projection"] = str(rng.choice(["Default", "Projected"]))
+        return face
+
+    while True:
+        sectors = []
+        for gx in range(width):
+            col = []
+            for gz in range(depth):
+                if rng.random() < 0.1:
+                    col.append(None)
+                    continue
+                sec = {}
+                if rng.random() < 0.9:
+                    sec["floor"] = horizontal(0.0, 600.0)
+                if rng.random() < 0.7:
+                    sec["ceiling"] = horizontal(1400.0, 2048.0)
+                for key in ("walls_north", "walls_east", "walls_south", "walls_west", "walls_nwse", "walls_nesw"):
+                    sec[key] = [wall() for _ in range(int(rng.integers(1, 4)) if rng.random() < 0.45 else 0)]
+                col.append(sec)
+            sectors.append(col)
+        faces = b32.room_faces_from_sectors(sectors)
+        if n is None or len(faces) >= n:
+            break
+        width += 3
+    mats = b32.room_materials_from_sectors(sectors, resolve)
+    assert len(mats) == len(faces)
+    if n is not None:
+        faces, mats = faces[:n].copy(), mats[:n].copy()
+    size = 0.0 if wild and seed % 2 else abi.SECTOR_SIZE
+    grid = grid_of((float(f32(rng.uniform(-900, 900))), float(f32(rng.uniform(-300, 300))), float(f32(rng.uniform(-900, 900)))), size)
+    return faces, mats, grid
+
+
+# ---------------------------------------------------------------- (c) the host build of the device header
+# (g++ forms fused multiply-adds from -O2 on, and only where the target has them)
+HOST_FLAGS = {"off": ["-O1", "-ffp-contract=off"], "fused": ["-O2", "-ffp-contract=fast", "-mfma"],
+              "sanitized": ["-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+
+
+@functools.lru_cache(maxsize=None)
+def _host_dir():
+    d = tempfile.mkdtemp(prefix="b32_room_mesh_host_")
+    atexit.register(shutil.rmtree, d, True)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def host_exe(mode):
+    exe = os.path.join(_host_dir(), "room_mesh_host_" + mode)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + HOST_FLAGS[mode] + ["-I", os.path.join(ROOT, "bonnie-32_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "room_mesh_host.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def host_mesh(faces, mats, grid, mode="off"):
+    """(vertices, faces) from b32_room_mesh_body.h compiled for the host."""
+    d = _host_dir()
+    fin, fout = os.path.join(d, f"in_{mode}.bin"), os.path.join(d, f"out_{mode}.bin")
+    with open(fin, "wb") as fh:
+        fh.write(np.array([len(faces), 0], np.uint32).tobytes())
+        fh.write(np.ascontiguousarray(grid, abi.ROOM_GRID_DTYPE).reshape(-1)[:1].tobytes())
+        fh.write(np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).tobytes()); fh.write(np.ascontiguousarray(mats, abi.FACE_MATERIAL_DTYPE).tobytes())
+    r = subprocess.run([host_exe(mode), fin, fout], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr)
+    blob = open(fout, "rb").read()
+    nv, nf = (int(x) for x in np.frombuffer(blob, np.uint32, 2))
+    return np.frombuffer(blob, abi.VERTEX_DTYPE, nv, 8).copy(), np.frombuffer(blob, abi.FACE_DTYPE, nf, 8 + 36 * nv).copy()
+
+
+RANDOM_CPU = [(1, None, "mixed"), (2, 600, "mixed"), (3, 257, "wild"), (4, 300, "wild"), (5, 63, "both"), (6, 200, "drawable")]
+
+
+@functools.lru_cache(maxsize=None)
+def random_answers(seed, n, flavour):
+    room = random_room(seed, n, flavour)
+    return room, ref_room_mesh(*room), b32.room_mesh(*room)
+
+
+# ================================================================== CPU
+def test_material_pod_layout_matches_c():
+    """B32FaceMaterial compiled with gcc against the public header has the size and offsets of abi.FACE_MATERIAL_DTYPE."""
+    dt = abi.FACE_MATERIAL_DTYPE
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "b32raster.h"\nint main(void){ printf("%zu ", sizeof(B32FaceMaterial));'
+    prog += "".join(f' printf("%zu ", offsetof(B32FaceMaterial, {f}));' for f in dt.names)
+    prog += ' printf("%u %u %u %u %u %u\\n", B32_MAT_HAS_UV, B32_MAT_HAS_UV_2, B32_MAT_HAS_HEIGHTS_2, B32_NORMAL_BOTH, B32_NORMAL_BACK, B32_UV_PROJECTED); return 0; }\n'
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(prog)
+        subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")], check=True)
+        got = [int(x) for x in subprocess.run([os.path.join(d, "t")], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [dt.itemsize] + [dt.fields[f][1] for f in dt.names] + [abi.MAT_HAS_UV, abi.MAT_HAS_UV_2, abi.MAT_HAS_HEIGHTS_2, abi.NORMAL_BOTH, abi.NORMAL_BACK, abi.UV_PROJECTED]
+    assert dt.itemsize == 136 and len(b32.rtypes.make_face_materials(3)) == 3
+
+
+@pytest.mark.parametrize("name", list(REAL_ROOMS))
+def test_real_rooms_equal_the_golden_scenes(name):
+    """(a), (b) and (c) on a real room equal the golden scenes' vertex and face arrays byte for byte (Dungeon has two scenes)."""
+    faces, mats, grid = real_room(name)
+    n, nv, nf = REAL_COUNTS[name]
+    assert len(faces) == len(mats) == n and b32.room_mesh_counts(faces, mats) == (nv, nf)
+    meshes = {"ref": ref_room_mesh(faces, mats, grid), "mirror": real_mesh(name), "host": host_mesh(faces, mats, grid)}
+    for scene in REAL_ROOMS[name]:
+        sc = real_scene(scene)
+        gv, gf = np.ascontiguousarray(sc.vertices, abi.VERTEX_DTYPE), np.ascontiguousarray(sc.faces, abi.FACE_DTYPE)
+        assert (len(gv), len(gf)) == (nv, nf) and not np.isnan(gv["pos"]).any()
+        for what, (v, f) in meshes.items():
+            assert same(v, gv), (scene, what, "vertices")
+            assert same(f, gf), (scene, what, "faces")
+
+
+def test_real_rooms_exercise_what_the_issue_lists():
+    faces, mats, _ = real_room("cathedral")
+    flat = faces["kind"] < 2
+    assert int(((mats["flags"] & abi.MAT_HAS_HEIGHTS_2) != 0).sum()) == 7 and int((mats["split_direction"][flat] == abi.SPLIT_NESW).sum()) == 5
+    neg_zero = [int((real_mesh(n)[0]["normal"].view(np.uint32) == 0x80000000).sum()) for n in REAL_ROOMS]
+    assert min(neg_zero) >= 64 and max(neg_zero) <= 1864 * 3, neg_zero
+    every = np.concatenate([real_room(n)[1] for n in REAL_ROOMS]); kinds = np.concatenate([real_room(n)[0]["kind"] for n in REAL_ROOMS])
+    assert (every["uv_projection"] == abi.UV_PROJECTED).any() and (every["normal_mode"][kinds >= 2] == abi.NORMAL_BACK).any()
+    assert (every["flags"] & abi.MAT_HAS_UV).any() and (every["black_transparent"] == 0).any() and {6, 7} <= set(kinds.tolist())
+    assert not (every["normal_mode"] == abi.NORMAL_BOTH).any() and (every["blend_mode"] == abi.OPAQUE).all() and set(every["tex_width"].tolist()) == {64}
+
+
+@pytest.mark.parametrize("seed,n,flavour", RANDOM_CPU)
+def test_random_rooms_three_statements_agree(seed, n, flavour):
+    """(a), (b) and (c) agree on random rooms of at most 600 records; the counts equal the array lengths."""
+    (faces, mats, grid), (rv, rf), (mv, mf) = random_answers(seed, n, flavour)
+    assert len(faces) <= 600 and (n is None or len(faces) == n)
+    hv, hf = host_mesh(faces, mats, grid)
+    assert same(mv, rv) and same(mf, rf), "mirror"
+    assert same(hv, rv) and same(hf, rf), "host header"
+    assert b32.room_mesh_counts(faces, mats) == (len(rv), len(rf))
+
+
+def test_random_rooms_cover_what_the_real_rooms_lack():
+    rooms = [random_answers(*k)[0] for k in RANDOM_CPU]
+    faces = np.concatenate([r[0] for r in rooms]); mats = np.concatenate([r[1] for r in rooms])
+    for kind in range(8):
+        assert {0, 1, 2} <= set(mats["normal_mode"][faces["kind"] == kind].tolist()), kind
+        assert int((faces["kind"] == kind).sum()) > 8
+    flat = faces["kind"] < 2
+    fl = mats["flags"][flat]
+    assert ((fl & 3) == 2).any() and ((fl & 3) == 3).any() and ((fl & 3) == 0).any()            # uv_2 without uv, both, neither
+    assert not ((fl & 3) == 1).any()                                                               # (get_uv_2: uv alone sets both flags)
+    assert (mats["colors_2"][flat] != mats["colors"][flat]).any() and (fl & abi.MAT_HAS_HEIGHTS_2).any()
+    assert set(mats["blend_mode"].tolist()) == set(range(6))
+    assert {0, 32, 48, 64, 128, 256} <= set(mats["tex_width"].tolist()) and (mats["tex_width"][flat] != mats["tex_width_2"][flat]).any()
+    assert ((mats["tex_width"][flat] != mats["tex_width_2"][flat]) & ((fl & 2) == 0)).any()       # ... with default UVs at triangle 2's own scale
+    assert np.isnan(faces["heights"]).any() and np.isinf(faces["heights"]).any() and np.isnan(mats["heights_2"]).any()
+    assert (np.nan_to_num(faces["heights"], nan=0.0, posinf=0.0, neginf=0.0) % 1 != 0).any()                                                       # off the lattice
+    assert (np.bincount(faces["index"]) > 0).sum() >= 3                                            # several walls per side
+    # normalize's ZERO return: a sector size of 0 makes every cross product zero (or NaN)
+    wild = [r for r in rooms if float(r[2]["sector_size"][0]) == 0.0]
+    assert wild
+    v, _ = b32.room_mesh(*wild[0])
+    z = (v["normal"].view(np.uint32) & 0x7FFFFFFF) == 0
+    assert z.all(axis=1).any() and (v["normal"].view(np.uint32) == 0x80000000).all(axis=1).any()  # ZERO, and ZERO.scale(-1.0)
+    assert any((np.isnan(random_answers(*k)[2][0]["normal"])).any() for k in RANDOM_CPU)
+
+
+@pytest.mark.parametrize("n", [0, 1])
+def test_empty_and_single_record(n):
+    faces, mats, grid = random_room(11, 40, "mixed")
+    for first in range(0, 8 if n else 1):
+        f, m = faces[first:first + n], mats[first:first + n]
+        rv, rf = ref_room_mesh(f, m, grid)
+        mv, mf = b32.room_mesh(f, m, grid)
+        hv, hf = host_mesh(f, m, grid)
+        assert same(mv, rv) and same(mf, rf) and same(hv, rv) and same(hf, rf)
+        assert b32.room_mesh_counts(f, m) == (len(rv), len(rf)) and (len(rv) > 0) == (n > 0)
+
+
+def test_host_header_differs_with_contraction():
+    """The same program built with FMA contraction (g++ -O2 -ffp-contract=fast -mfma) gives other bits on the off-lattice rooms: the
+    cross products and position + gx * S are contraction candidates.  So the equality above does rest on -ffp-contract=off."""
+    differ = 0
+    for key in RANDOM_CPU[:2]:
+        (faces, mats, grid), (rv, rf), _ = random_answers(*key)
+        fv, ff = host_mesh(faces, mats, grid, "fused")
+        assert same(ff, rf) and len(fv) == len(rv)
+        differ += int((fv["normal"].view(np.uint32) != rv["normal"].view(np.uint32)).sum()) + int((fv["pos"].view(np.uint32) != rv["pos"].view(np.uint32)).sum())
+    assert differ > 0
+
+
+def test_host_program_runs_clean_under_sanitizers():
+    """The stand-alone host program built with -fsanitize=address,undefined runs clean on a real room, a wild room and the empty room
+    (host_mesh asserts exit status 0 and an empty stderr), and computes the same bytes."""
+    for room, want in ((real_room("cathedral"), real_mesh("cathedral")), (random_answers(*RANDOM_CPU[3])[0], random_answers(*RANDOM_CPU[3])[2])):
+        v, f = host_mesh(*room, mode="sanitized")
+        assert same(v, want[0]) and same(f, want[1])
+    faces, mats, grid = real_room("cave")
+    v, f = host_mesh(faces[:0], mats[:0], grid, mode="sanitized")
+    assert len(v) == 0 and len(f) == 0
+
+
+def test_room_materials_from_sectors_resolves_the_options():
+    """The getters of geometry.rs:1193-1210 and the loop order of room_faces_from_sectors."""
+    col = lambda r: [{"r": r, "g": 2, "b": 3, "blend": "Add"}] * 4
+    uv = lambda x: [{"x": x, "y": 0.5}] * 4
+    sectors = [[{"floor": {"heights": [1, 2, 3, 4], "texture": {"pack": "p", "name": "t3"}, "uv": uv(0.25), "colors": col(9), "normal_mode": "Both", "split_direction": "NeSw"},
+                 "ceiling": {"heights": [5, 5, 5, 5], "texture": {"pack": "p", "name": "nosuch"}, "texture_2": {"pack": "p", "name": "t1"}, "uv_2": uv(0.75),
+                             "colors_2": col(7), "heights_2": [6, 7, 8, 9], "blend_mode": "Erase", "black_transparent": False},
+                 "walls_west": [[0, 0, 9, 9], {"heights": [0, 0, 1, 1], "texture": {"pack": "p", "name": "t4"}, "uv_projection": "Projected", "normal_mode": "Back"}]}]]
+    f = b32.room_faces_from_sectors(sectors)
+    m = b32.room_materials_from_sectors(sectors, resolve)
+    assert f["kind"].tolist() == [0, 1, 5, 5] and len(m) == 4
+    assert (int(m[0]["texture_id"]), int(m[0]["tex_width"]), int(m[0]["texture_id_2"]), int(m[0]["tex_width_2"])) == (3, 128, 3, 128)
+    assert int(m[0]["flags"]) == abi.MAT_HAS_UV | abi.MAT_HAS_UV_2 and m[0]["uv_2"].tolist() == m[0]["uv"].tolist() == [[0.25, 0.5]] * 4
+    assert m[0]["colors_2"].tolist() == m[0]["colors"].tolist() == [[9, 2, 3, abi.ADD]] * 4
+    assert (int(m[0]["normal_mode"]), int(m[0]["split_direction"])) == (abi.NORMAL_BOTH, abi.SPLIT_NESW)
+    assert (int(m[1]["texture_id"]), int(m[1]["tex_width"]), int(m[1]["texture_id_2"]), int(m[1]["tex_width_2"])) == (0, 64, 1, 32)
+    assert int(m[1]["flags"]) == abi.MAT_HAS_UV_2 | abi.MAT_HAS_HEIGHTS_2 and m[1]["heights_2"].tolist() == [6, 7, 8, 9]
+    assert m[1]["colors"].tolist() == [[128, 128, 128, 0]] * 4 and m[1]["colors_2"].tolist() == [[7, 2, 3, abi.ADD]] * 4
+    assert (int(m[1]["blend_mode"]), int(m[1]["black_transparent"])) == (abi.ERASE, 0)
+    assert same(m[2:3], b32.rtypes.make_face_materials(1))                                         # four bare heights: every default
+    assert (int(m[3]["texture_id"]), int(m[3]["tex_width"]), int(m[3]["uv_projection"]), int(m[3]["normal_mode"])) == (4, 256, abi.UV_PROJECTED, abi.NORMAL_BACK)
+    assert b32.room_mesh_counts(f, m) == (12 + 6 + 4 + 4, 4 + 2 + 2 + 2)
+
+
+def test_cpp_mirror_room_mesh_compiles():
+    """host/rasterizer.hpp with the room mesh calls still passes -fsyntax-only, and a program that uses them does."""
+    hpp_dir = os.path.join(ROOT, "bonnie-32_amd", "host")
+    prog = ('#include "rasterizer.hpp"\n'
+            "int main() { b32::Framebuffer fb(64, 48); std::vector<B32SectorFace> f(2); std::vector<b32::FaceMaterial> m(2, b32::face_material());\n"
+            "  uint32_t nv = 0, nf = 0; b32::Room room(fb, f); room.set_materials(m); room.update_materials(1, 1, m.data());\n"
+            "  room.mesh_counts(nv, nf); room.build_mesh(); b32::room_mesh_counts(f, m, nv, nf); return (int)(nv + nf); }\n")
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.cpp"), "w").write(prog)
+        subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", "-I", hpp_dir, "-I", os.path.join(ROOT, "include"),
+                        os.path.join(d, "t.cpp")], check=True)
+
+
+# ================================================================== GPU
+def _textures_for(mats):
+    """Six small textures (ids 0..5) for a random room's frame: checker patterns with some black (skippable) texels."""
+    out = []
+    for t in range(6):
+        w = (64, 32, 48, 128, 16, 8)[t]
+        y, x = np.mgrid[0:w, 0:w]
+        px = (((x // 4 + y // 4 + t) % 3) * (0x0421 * (5 + 3 * t)) & 0x7FFF).astype(np.uint16)
+        out.append(b32.Texture15(w, w, px.reshape(-1), abi.OPAQUE))
+    return out
+
+
+def _empty_scene(R, fb, textures=None, textures8=None):
+    """A slot that holds textures and no geometry: what b32_room_build_mesh fills."""
+    v, f = b32.make_vertices(0), b32.make_faces(0)
+    return (R.ResidentScene(fb, v, f, textures8=textures8) if textures8 is not None else R.ResidentScene(fb, v, f, textures or [])).detach()
+
+
+def _assert_frame(fb, pixels, zbuffer, what=""):
+    got = fb.pixels
+    assert np.array_equal(got, pixels), f"{what}: {int((got != pixels).sum())} bytes differ"
+    gz = fb.zbuffer.view(np.uint32)
+    assert np.array_equal(gz, zbuffer.view(np.uint32)), f"{what}: {int((gz != zbuffer.view(np.uint32)).sum())} depths differ"
+
+
+_ORACLE = {}
+
+
+def _oracle_frame(oracle, key, w, h, clear, draws, st, cam, fmt8=False):
+    """The oracle's frame of `draws` = [(vertices, faces, textures, fog)] drawn one after the other: (pixels, zbuffer, triangles_drawn)."""
+    if key not in _ORACLE:
+        ofb = oracle.Framebuffer(w, h); ofb.clear(clear)
+        drawn = 0
+        for v, f, tex, fog in draws:
+            rc, tm = oracle.render_mesh(ofb, v, f, tex, cam, st) if fmt8 else oracle.render_mesh_15(ofb, v, f, tex, cam, st, fog)
+            assert rc == 0
+            drawn += tm.triangles_drawn
+        _ORACLE[key] = (ofb.pixels.copy(), ofb.zbuffer.copy(), drawn)
+    return _ORACLE[key]
+
+
+GPU_RANDOM = [(21, 0, "mixed"), (22, 1, "mixed"), (23, 63, "both"), (24, 257, "mixed"), (25, 600, "wild"), (26, 600, "mixed")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(REAL_ROOMS) + GPU_RANDOM, ids=lambda c: c if isinstance(c, str) else f"random-{c[1]}-{c[2]}")
+def test_gpu_build_mesh_equals_the_mirror(gpu_ctx, case):
+    """build_mesh into a slot, then read_vertices and read_faces: both equal room_mesh byte for byte -- the four real rooms, and random
+    rooms of 0, 1, 63 (all Both), 257, 600 (NaN and inf heights, sector size 0) and 600 records whose modes make every offset differ
+    from 6 * rec."""
+    from bonnie32_amd import rasterizer as R
+    if isinstance(case, str):
+        (faces, mats, grid), (wv, wf) = real_room(case), real_mesh(case)
+    else:
+        faces, mats, grid = random_room(*case)
+        if case == GPU_RANDOM[-1]:
+            mats["normal_mode"][:40] = abi.NORMAL_BOTH                             # (a head start: the offsets never come back to 6 * rec)
+        wv, wf = b32.room_mesh(faces, mats, grid)
+        assert len(faces) == case[1]
+        if case[2] == "both":
+            assert (mats["normal_mode"] == abi.NORMAL_BOTH).all()
+        if case == GPU_RANDOM[-1]:
+            _, nv_rec, _ = R._room_mesh_layout(faces, mats)
+            first = np.cumsum(nv_rec) - nv_rec
+            assert (first[1:] != 6 * np.arange(1, len(faces))).all()
+        if case[2] == "wild":
+            assert np.isnan(wv["pos"]).any() and np.isnan(wv["normal"]).any() and ((wv["normal"].view(np.uint32) & 0x7FFFFFFF) == 0).all(axis=1).any()
+    fb = R.Framebuffer(64, 48, gpu_ctx)
+    rs = _empty_scene(R, fb)
+    room = R.Room(gpu_ctx, faces, grid)
+    try:
+        room.set_materials(mats)
+        assert room.mesh_counts() == (len(wv), len(wf))
+        room.build_mesh(rs)
+        assert (rs.n_vertices, rs.n_faces) == (len(wv), len(wf))
+        gv, gf = rs.read_vertices(), rs.read_faces()
+        bad = np.nonzero(np.frombuffer(gv.tobytes(), np.uint8).reshape(-1, 36) != np.frombuffer(wv.tobytes(), np.uint8).reshape(-1, 36))[0]
+        assert same(gv, wv), f"{len(set(bad.tolist()))} vertices differ, first {bad[:1]}"
+        assert same(gf, wf)
+        room.build_mesh(rs)                                                        # again into the same slot: the same bytes
+        assert same(rs.read_vertices(), wv) and same(rs.read_faces(), wf)
+    finally:
+        room.close(); rs.close()
+
+
+def _real_frame_case(oracle, R, name, scene, fmt8):
+    sc = real_scene(scene)
+    faces, mats, grid = real_room(name)
+    st = sc.settings
+    tex8 = [b32.Texture.from_texture15(t) for t in sc.textures] if fmt8 else None
+    want = _oracle_frame(oracle, (scene, fmt8), sc.width, sc.height, sc.clear_color,
+                         [(sc.vertices, sc.faces, tex8 if fmt8 else sc.textures, None if fmt8 else sc.fog)], st, sc.camera, fmt8)
+    ctx = R.Context(0)
+    try:
+        fb = R.Framebuffer(sc.width, sc.height, ctx)
+        up = (R.ResidentScene(fb, sc.vertices, sc.faces, textures8=tex8) if fmt8 else R.ResidentScene(fb, sc.vertices, sc.faces, sc.textures)).detach()
+        built = _empty_scene(R, fb, sc.textures, tex8)
+        room = R.Room(ctx, faces, grid)
+        room.set_materials(mats)
+        room.build_mesh(built)
+        frames = []
+        for rs in (up, built):
+            fb.clear(sc.clear_color)
+            rs.render_async(sc.camera, st, None if fmt8 else sc.fog)
+            tm = rs.finish()
+            _assert_frame(fb, want[0], want[1], scene)
+            assert tm.triangles_drawn == want[2]
+            frames.append((fb.pixels.tobytes(), fb.zbuffer.tobytes()))
+        assert frames[0] == frames[1]
+        room.close(); up.close(); built.close()
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,scene", [(n, s) for n, ss in REAL_ROOMS.items() for s in ss])
+def test_gpu_frame_from_the_built_slot_rgb555(oracle, name, scene):
+    """The frame drawn from the built slot is byte-equal to the frame drawn from the uploaded golden mesh, with the golden scene's camera,
+    settings and fog, and to the oracle."""
+    from bonnie32_amd import rasterizer as R
+    _real_frame_case(oracle, R, name, scene, False)
+
+
+@pytest.mark.gpu
+def test_gpu_frame_from_the_built_slot_8bit(oracle):
+    """The same through the 8-bit-colour path (b32_scene_upload_rgba, render_mesh) for one room."""
+    from bonnie32_amd import rasterizer as R
+    _real_frame_case(oracle, R, "cave", "cave-room0-game", True)
+
+
+def _drawable_room(seed=31, n=220):
+    faces, mats, grid = random_room(seed, n, "drawable")
+    cam = b32.Camera((float(grid["position"][0][0]) + 2600.0, float(grid["position"][0][1]) + 1000.0, float(grid["position"][0][2]) + 2100.0),
+                     (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    return faces, mats, grid, cam
+
+
+@pytest.mark.gpu
+def test_gpu_frame_with_average_faces(oracle):
+    """A random room with Average faces: the transparent pass and blend_faces come from the materials' blend modes."""
+    from bonnie32_amd import rasterizer as R
+    faces, mats, grid, cam = _drawable_room()
+    assert (mats["blend_mode"] == abi.AVERAGE).any() and (mats["normal_mode"] == abi.NORMAL_BOTH).any()
+    v, f = b32.room_mesh(faces, mats, grid)
+    tex = _textures_for(mats)
+    W, H = 320, 240
+    clear = b32.Color(20, 22, 28)
+    ctx = R.Context(0)
+    try:
+        fb = R.Framebuffer(W, H, ctx)
+        for zb in (True, False):
+            st = b32.RasterSettings.game()
+            st.use_zbuffer = zb
+            want = _oracle_frame(oracle, ("average", zb), W, H, clear, [(v, f, tex, None)], st, cam)
+            assert want[2] > 50
+            up = R.ResidentScene(fb, v, f, tex).detach()
+            built = _empty_scene(R, fb, tex)
+            room = R.Room(ctx, faces, grid)
+            room.set_materials(mats)
+            room.build_mesh(built)
+            for rs in (up, built):
+                fb.clear(clear)
+                rs.render_async(cam, st)
+                tm = rs.finish()
+                _assert_frame(fb, want[0], want[1], f"zbuffer {zb}")
+                assert tm.triangles_drawn == want[2]
+            room.close(); up.close(); built.close()
+    finally:
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_drag_frames_by_ticket_and_batched(oracle):
+    """A drag: b32_room_update of 7 records, b32_room_update_materials of 3 (one flips Front -> Both, so the counts and every later offset
+    change), build, draw, all enqueued back to back and delivered by ticket: the frame equals mirror plus oracle.  Then a frame through
+    b32_frame_submit with two room slots, one rebuilt and one not, equals the sequential draws: the merged run notices the new gen."""
+    from bonnie32_amd import rasterizer as R
+    name, scene = "dungeon", "dungeon-room0-game"
+    sc = real_scene(scene)
+    faces, mats, grid = (a.copy() for a in real_room(name))
+    W, H = sc.width, sc.height
+    st = sc.settings
+    assert st.use_zbuffer and st.use_rgb555
+    ofaces, omats, ogrid, _ = _drawable_room(33, 120)
+    eye = np.array(sc.camera.position, f32) + np.array(sc.camera.basis_z, f32) * f32(2500.0)      # (in front of the camera: it shows in the frame)
+    ogrid["position"][0] = (eye[0] - 1024.0, eye[1] - 900.0, eye[2] - 2560.0)
+    otex = _textures_for(omats)
+    ov, of_ = b32.room_mesh(ofaces, omats, ogrid)
+    ctx = R.Context(0)
+    bufs = []
+    try:
+        fb = R.Framebuffer(W, H, ctx)
+        a = _empty_scene(R, fb, sc.textures)
+        b = _empty_scene(R, fb, otex)
+        room, other = R.Room(ctx, faces, grid), R.Room(ctx, ofaces, ogrid)
+        room.set_materials(mats); other.set_materials(omats)
+        room.build_mesh(a); other.build_mesh(b)
+        fb.clear(sc.clear_color); a.render_async(sc.camera, st, sc.fog); a.finish()          # (capacities settled by a warm-up frame)
+        bufs = [ctx.host_alloc(W * H * 4) for _ in range(2)]
+        table = ctx.make_frame_table(sc.camera, st, [a, b], fogs=[sc.fog, None])
+        built = []
+        for step in range(2):
+            first = 40 + 50 * step
+            flat = np.nonzero((faces["kind"] < 2) & (np.arange(len(faces)) >= first))[0]
+            drag = faces[first:first + 7].copy(); drag["heights"] += f32(96.0 + 32.0 * step)
+            faces[first:first + 7] = drag
+            k = int(flat[0])
+            mm = mats[k:k + 3].copy()
+            assert mm["normal_mode"][0] == abi.NORMAL_FRONT
+            mm["normal_mode"][0] = abi.NORMAL_BOTH; mm["blend_mode"][1] = abi.OPAQUE; mm["colors"][2, :, 0] = 200
+            mats[k:k + 3] = mm
+            wv, wf = b32.room_mesh(faces, mats, grid)
+            # ---- everything enqueued without a host synchronisation in between
+            room.update(first, drag)
+            room.update_materials(k, mm)
+            room.build_mesh(a)
+            fb.clear(sc.clear_color)
+            a.render_async(sc.camera, st, sc.fog)
+            t0 = ctx.download_async(bufs[0][1])
+            fb.clear(sc.clear_color)
+            ctx.frame_submit(table)
+            t1 = ctx.download_async(bufs[1][1])
+            assert (a.n_vertices, a.n_faces) == (len(wv), len(wf)) and len(wv) == len(real_mesh(name)[0]) + 6 * (step + 1)
+            ctx.ticket_wait(t0); ctx.ticket_wait(t1)
+            ctx.finish()
+            built.append(ctx.batch_counts()["merged_built"])
+            one = _oracle_frame(oracle, ("drag", step), W, H, sc.clear_color, [(wv, wf, sc.textures, sc.fog)], st, sc.camera)
+            two = _oracle_frame(oracle, ("drag2", step), W, H, sc.clear_color, [(wv, wf, sc.textures, sc.fog), (ov, of_, otex, None)], st, sc.camera)
+            assert np.array_equal(bufs[0][0], one[0].reshape(-1)), f"step {step}: {int((bufs[0][0] != one[0].reshape(-1)).sum())} bytes differ"
+            assert np.array_equal(bufs[1][0], two[0].reshape(-1)), f"step {step}, batched: {int((bufs[1][0] != two[0].reshape(-1)).sum())} bytes differ"
+            assert not np.array_equal(one[0], two[0])
+            assert same(a.read_vertices(), wv) and same(a.read_faces(), wf) and same(b.read_vertices(), ov)
+        assert built[1] == built[0] + 1, built                                       # one rebuilt member, one rebuild of the merged mesh
+        assert ctx.batch_counts()["merged_draws"] >= 2, ctx.batch_counts()
+        room.close(); other.close(); a.close(); b.close()
+    finally:
+        for _, p in bufs:
+            ctx.host_free(p)
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_build_behind_a_pending_frame_and_rig(oracle):
+    """A build between a frame's submission and its delivery leaves the pending frame's bytes as they were (settle_pending); a rig set on
+    the slot is gone afterwards: b32_scene_pose then returns B32_E_ARG."""
+    from bonnie32_amd import rasterizer as R
+    name, scene = "cave", "cave-room0-game"
+    sc = real_scene(scene)
+    faces, mats, grid = real_room(name)
+    want = _oracle_frame(oracle, (scene, False), sc.width, sc.height, sc.clear_color, [(sc.vertices, sc.faces, sc.textures, sc.fog)], sc.settings, sc.camera)
+    ctx = R.Context(0)
+    buf = None
+    try:
+        fb = R.Framebuffer(sc.width, sc.height, ctx)
+        rs = R.ResidentScene(fb, sc.vertices, sc.faces, sc.textures).detach()
+        rs.set_rig(np.zeros(len(sc.vertices), np.uint16))
+        bone = np.zeros(1, abi.BONE_DTYPE)
+        assert ctx.lib.b32_scene_pose(ctx.h, rs._slot, None, 0) == 0                 # (the empty table: the rest bits come back)
+        moved = faces.copy(); moved["heights"] += f32(400.0)
+        room = R.Room(ctx, moved, grid)
+        room.set_materials(mats)
+        buf = ctx.host_alloc(sc.width * sc.height * 4)
+        table = ctx.make_frame_table(sc.camera, sc.settings, [rs], fogs=[sc.fog])
+        fb.clear(sc.clear_color)
+        ctx.frame_submit(table)
+        t = ctx.download_async(buf[1])
+        room.build_mesh(rs)                                                          # behind the frame, in front of its delivery
+        ctx.ticket_wait(t)
+        assert np.array_equal(buf[0], want[0].reshape(-1)), f"{int((buf[0] != want[0].reshape(-1)).sum())} bytes differ"
+        ctx.finish()
+        assert ctx.lib.b32_scene_pose(ctx.h, rs._slot, abi.ptr(bone), 1) == abi.B32_E_ARG
+        wv, wf = b32.room_mesh(moved, mats, grid)
+        assert same(rs.read_vertices(), wv) and same(rs.read_faces(), wf)
+        fb.clear(sc.clear_color); rs.render_async(sc.camera, sc.settings, sc.fog); rs.finish()
+        assert not np.array_equal(fb.pixels, want[0])
+        room.close(); rs.close()
+    finally:
+        if buf is not None:
+            ctx.host_free(buf[1])
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_room_mesh_errors():
+    """Build without materials, build into a slot without a scene, an update out of range, and an enum out of range after which the
+    table is unchanged, verified by a rebuild."""
+    from bonnie32_amd import rasterizer as R
+    faces, mats, grid = random_room(41, 64, "mixed")
+    wv, wf = b32.room_mesh(faces, mats, grid)
+    ctx = R.Context(0)
+    lib, E = ctx.lib, abi.B32_E_ARG
+    try:
+        fb = R.Framebuffer(64, 48, ctx)
+        rs = _empty_scene(R, fb)
+        room = R.Room(ctx, faces, grid)
+        nv, nf = C.c_uint32(7), C.c_uint32(7)
+        assert lib.b32_room_build_mesh(ctx.h, room._h, rs._slot) == E                # no materials yet
+        assert lib.b32_room_mesh_counts(room._h, C.byref(nv), C.byref(nf)) == E
+        assert lib.b32_room_update_materials(ctx.h, room._h, 0, 1, abi.ptr(mats)) == E
+        assert lib.b32_room_set_materials(ctx.h, room._h, None) == E
+        bad = mats.copy(); bad["normal_mode"][63] = 3
+        assert lib.b32_room_set_materials(ctx.h, room._h, abi.ptr(bad)) == E
+        assert lib.b32_room_build_mesh(ctx.h, room._h, rs._slot) == E                # ... still none
+        room.set_materials(mats)
+        empty = C.c_void_p()
+        assert lib.b32_scene_create(ctx.h, C.byref(empty)) == 0
+        assert lib.b32_room_build_mesh(ctx.h, room._h, empty) == E                   # a slot without a scene
+        assert lib.b32_room_build_mesh(ctx.h, room._h, None) == E                    # the context holds none either (rs is detached)
+        assert lib.b32_room_build_mesh(ctx.h, None, rs._slot) == E and lib.b32_room_build_mesh(None, room._h, rs._slot) == E
+        assert lib.b32_scene_read_faces(ctx.h, empty, 0, 0, None) == E
+        room.build_mesh(rs)
+        assert lib.b32_room_mesh_counts(room._h, C.byref(nv), C.byref(nf)) == 0 and (nv.value, nf.value) == (len(wv), len(wf))
+        assert lib.b32_room_mesh_counts(room._h, None, C.byref(nf)) == E and lib.b32_room_mesh_counts(None, C.byref(nv), C.byref(nf)) == E
+        out = np.zeros(2, abi.FACE_DTYPE)
+        assert lib.b32_scene_read_faces(ctx.h, rs._slot, len(wf) - 1, 2, abi.ptr(out)) == E and lib.b32_scene_read_faces(ctx.h, rs._slot, 0, 2, None) == E
+        # out of range, and every enum out of range: nothing changed
+        assert lib.b32_room_update_materials(ctx.h, room._h, 63, 2, abi.ptr(mats)) == E
+        assert lib.b32_room_update_materials(ctx.h, room._h, 0xFFFFFFFF, 2, abi.ptr(mats)) == E
+        assert lib.b32_room_update_materials(ctx.h, room._h, 0, 2, None) == E
+        for field, value in (("normal_mode", 3), ("split_direction", 2), ("uv_projection", 2), ("blend_mode", 6)):
+            bad = mats[10:14].copy()
+            bad["normal_mode"] = (bad["normal_mode"] + 1) % 3; bad["colors"] = 1       # (would move every later record and change bytes)
+            bad[field][3] = value
+            assert lib.b32_room_update_materials(ctx.h, room._h, 10, 4, abi.ptr(bad)) == E, field
+        room.build_mesh(rs)
+        assert room.mesh_counts() == (len(wv), len(wf)) and same(rs.read_vertices(), wv) and same(rs.read_faces(), wf)
+        # a kind that changes through b32_room_update moves the later records too
+        f2 = faces.copy(); m2 = mats.copy()
+        k = int(np.nonzero(f2["kind"] >= 2)[0][0])
+        f2["kind"][k] = abi.ROOM_FLOOR
+        room.update(k, f2[k:k + 1])
+        room.build_mesh(rs)
+        w2 = b32.room_mesh(f2, m2, grid)
+        assert len(w2[0]) != len(wv) and same(rs.read_vertices(), w2[0]) and same(rs.read_faces(), w2[1])
+        # the context's own resident scene (slot NULL), and a slot that shrinks to nothing
+        rs._swap()
+        assert lib.b32_room_build_mesh(ctx.h, room._h, None) == 0
+        rs._swap()
+        assert same(rs.read_vertices(), w2[0])
+        none = R.Room(ctx, faces[:0], grid)
+        none.set_materials(mats[:0])
+        none.build_mesh(rs)
+        assert (rs.n_vertices, rs.n_faces) == (0, 0)
+        fb.clear(b32.Color(1, 2, 3)); rs.render_async(b32.Camera(), b32.RasterSettings.game()); rs.finish()
+        assert (fb.pixels.reshape(-1, 4)[:, :3] == (1, 2, 3)).all()
+        room.build_mesh(rs)
+        assert same(rs.read_vertices(), w2[0])
+        none.close(); room.close(); rs.close()
+        lib.b32_scene_destroy(ctx.h, empty)
+    finally:
+        ctx.close()
