@@ -62,18 +62,11 @@ void b32_destroy(b32_ctx* c) {
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
     c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release();
-    if (c->world_counts) (void)hipFree(c->world_counts);
-    if (c->gizmo_counts) (void)hipFree(c->gizmo_counts);
-    for (hipEvent_t e : c->world_ev) if (e) (void)hipEventDestroy(e);
+    for (ArmedWords* w : { &c->world_counts, &c->gizmo_counts, &c->pick_words, &c->hover_bits, &c->hover_words, &c->room_words, &c->room_points })
+        if (w->p) (void)hipFree(w->p);
+    for (EventPair* t : { &c->world_timer, &c->pick_timer, &c->hover_timer }) t->destroy();
     c->pick_tab.release();
-    if (c->pick_words) (void)hipFree(c->pick_words);
     if (c->pick_host) (void)hipHostFree(c->pick_host);
-    for (hipEvent_t e : c->pick_tev) if (e) (void)hipEventDestroy(e);
-    if (c->hover_bits) (void)hipFree(c->hover_bits);
-    if (c->hover_words) (void)hipFree(c->hover_words);
-    for (hipEvent_t e : c->hover_tev) if (e) (void)hipEventDestroy(e);
-    if (c->room_words) (void)hipFree(c->room_words);
-    if (c->room_points) (void)hipFree(c->room_points);
     c->overlay_sel.release();
     if (c->overlay_tab) (void)hipFree(c->overlay_tab);
     if (c->overlay_bounds) (void)hipFree(c->overlay_bounds);
@@ -357,16 +350,10 @@ static int world_check(const B32WorldItem* items, uint32_t n) {
     return B32_OK;
 }
 static int world_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, WorldArgs& wa) {
-    if (!c->world_counts) {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->world_counts), 3 * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->world_counts, 0, 3 * sizeof(unsigned long long), c->stream));
-    }
+    { const int rc = armed_ensure(c, c->world_counts, 3 * sizeof(unsigned long long), 0); if (rc) return rc; }
     wa = WorldArgs{};
-    wa.n = n; wa.counts = c->world_counts;
-    for (int k = 0; k < 3; ++k) { wa.pos[k] = cam->position[k]; wa.bx[k] = cam->basis_x[k]; wa.by[k] = cam->basis_y[k]; wa.bz[k] = cam->basis_z[k]; }
-    wa.vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f;                        // math.rs:524-525
-    wa.half_w = (float)w / 2.0f; wa.half_h = (float)h / 2.0f;
-    if (ortho) { wa.has_ortho = 1u; wa.zoom = ortho->zoom; wa.center_x = ortho->center_x; wa.center_y = ortho->center_y; }
+    wa.n = n; wa.counts = static_cast<unsigned long long*>(c->world_counts.p);
+    view_fill(wa.v, *cam, w, h, ortho);
     return B32_OK;
 }
 
@@ -387,19 +374,16 @@ static int gizmo_check(const B32GizmoItem* items, uint32_t n, GizmoRow* rows, ui
     return B32_OK;
 }
 static int gizmo_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, GizmoArgs& ga) {
-    if (!c->gizmo_counts) {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->gizmo_counts), 3 * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->gizmo_counts, 0, 3 * sizeof(unsigned long long), c->stream));
-    }
+    { const int rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0); if (rc) return rc; }
     ga = GizmoArgs{};
-    const int rc = world_args(c, cam, ortho, w, h, n, ga.w);
-    ga.w.counts = c->gizmo_counts;
-    return rc;
+    ga.w.n = n; ga.w.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
+    view_fill(ga.w.v, *cam, w, h, ortho);
+    return B32_OK;
 }
 
 // ------------------------------------------------------------------ the modeler's selection overlays (b32_overlay.hip)
 // Everything checked and laid out before anything is enqueued: the kernels' arguments but for the device buffers the caller provides
-// (w.out, tab, selected), the list to upload (*up / *n_up words: the list as given, or c->overlay_pairs for polygons), the record total.
+// (out, tab, selected), the list to upload (*up / *n_up words: the list as given, or c->overlay_pairs for polygons), the record total.
 static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const b32_scene* slot, const b32_topology* topo,
                            const B32MeshOverlay* o, const uint32_t* selected, uint32_t w, uint32_t h, OverlayArgs& a, const uint32_t** up,
                            uint32_t* n_up, uint64_t* total) {
@@ -410,10 +394,8 @@ static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ort
     *total = l.total;
     if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
     a = OverlayArgs{};
-    int rc;
     (void)hipSetDevice(c->device);
-    if ((rc = world_args(c, cam, ortho, w, h, 0u, a.w))) return rc;
-    a.w.counts = nullptr;
+    view_fill(a.v, *cam, w, h, ortho);
     const bool packed = slot->pos_valid && slot->d_pos12;
     a.pos = packed ? slot->d_pos12 : reinterpret_cast<const float*>(slot->d_verts);
     a.stride = packed ? 3u : (uint32_t)(sizeof(B32Vertex) / sizeof(float));
@@ -514,13 +496,10 @@ int b32_draw_world(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, cons
         wa.items = c->world.dev;
     }
     const bool timed = c->profile_level >= 1;
-    if (timed) {
-        for (hipEvent_t& e : c->world_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->world_ev[0], c->stream));
-    }
+    if (timed) HIPCHK(c, c->world_timer.begin(c->stream));
     launch_world_project(c->stream, wa, n > WORLD_SMALL ? nullptr : items);
     HIPCHK(c, hipGetLastError());
-    if (timed) { HIPCHK(c, hipEventRecord(c->world_ev[1], c->stream)); c->world_timed = true; }
+    if (timed) HIPCHK(c, c->world_timer.end(c->stream));
     DrawArgs<B32Prim> a = draw_args<B32Prim>(c, n);
     a.recs = c->prims.dev;
     bool tiled = false;
@@ -562,7 +541,7 @@ int b32_world_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* r
     if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     unsigned long long h[3] = { 0, 0, 0 };
-    if (c->world_counts) HIPCHK(c, hipMemcpyAsync(h, c->world_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    if (c->world_counts.p) HIPCHK(c, hipMemcpyAsync(h, c->world_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
     return B32_OK;
@@ -623,7 +602,7 @@ int b32_gizmo_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* r
     if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     unsigned long long h[3] = { 0, 0, 0 };
-    if (c->gizmo_counts) HIPCHK(c, hipMemcpyAsync(h, c->gizmo_counts, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    if (c->gizmo_counts.p) HIPCHK(c, hipMemcpyAsync(h, c->gizmo_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
     return B32_OK;
@@ -642,7 +621,7 @@ int b32_draw_mesh_overlay(b32_ctx* c, const B32Camera* cam, const B32Ortho* orth
     if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)total))) return rc;
     if ((rc = ensure(c, c->overlay_tab, c->overlay_cap_tab, (size_t)a.nv))) return rc;
     if ((rc = overlay_bounds(c, a))) return rc;
-    a.w.out = c->prims.dev; a.tab = reinterpret_cast<OverlayPoint*>(c->overlay_tab);
+    a.out = c->prims.dev; a.tab = reinterpret_cast<OverlayPoint*>(c->overlay_tab);
     if (n_up) {
         if ((rc = stage_records(c, c->overlay_sel, up, n_up))) return rc;
         a.selected = c->overlay_sel.dev;
@@ -669,7 +648,7 @@ int b32_mesh_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32Or
     if ((rc = tmp.alloc(&d_tab, (size_t)a.nv))) return rc;
     if (n_up && (rc = tmp.upload(up, (size_t)n_up, &d_sel))) return rc;
     if ((rc = overlay_bounds(c, a))) return rc;
-    a.w.out = d_out; a.tab = d_tab; a.selected = d_sel;
+    a.out = d_out; a.tab = d_tab; a.selected = d_sel;
     launch_overlay(c->stream, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
@@ -940,23 +919,12 @@ int b32_last_kernel_times(b32_ctx* c, const char** names, float* ms, uint32_t ca
         if (p != 3 && c->phase_level < 2) continue;
         names[k] = kNames[p]; ms[k] = c->phase_ms[p]; ++k;
     }
-    // the projection kernel of the last b32_draw_world enqueued while profiling was on (waits for it)
-    float world_ms = 0.0f;
-    if (c->world_timed && k < cap && hipEventSynchronize(c->world_ev[1]) == hipSuccess &&
-        hipEventElapsedTime(&world_ms, c->world_ev[0], c->world_ev[1]) == hipSuccess) {
-        names[k] = "world_project"; ms[k] = world_ms; ++k;
-    }
-    // the pick and resolve kernels of the last b32_pick_meshes[_async] enqueued while profiling was on (waits for them)
-    float pick_ms = 0.0f;
-    if (c->pick_timed && k < cap && hipEventSynchronize(c->pick_tev[1]) == hipSuccess &&
-        hipEventElapsedTime(&pick_ms, c->pick_tev[0], c->pick_tev[1]) == hipSuccess) {
-        names[k] = "pick"; ms[k] = pick_ms; ++k;
-    }
-    // ... and the kernels of the last b32_hover_mesh[_async]
-    float hover_ms = 0.0f;
-    if (c->hover_timed && k < cap && hipEventSynchronize(c->hover_tev[1]) == hipSuccess &&
-        hipEventElapsedTime(&hover_ms, c->hover_tev[0], c->hover_tev[1]) == hipSuccess) {
-        names[k] = "hover"; ms[k] = hover_ms; ++k;
+    // the kernels of the last b32_draw_world (its projection), b32_pick_meshes[_async] (pick and resolve) and b32_hover_mesh[_async]
+    // enqueued while profiling was on (waits for them)
+    const struct { const char* name; const EventPair* pair; } timers[3] = { { "world_project", &c->world_timer }, { "pick", &c->pick_timer }, { "hover", &c->hover_timer } };
+    for (const auto& t : timers) {
+        float t_ms = 0.0f;
+        if (k < cap && t.pair->elapsed(&t_ms)) { names[k] = t.name; ms[k] = t_ms; ++k; }
     }
     return (int)k;
 }
@@ -994,8 +962,7 @@ extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {
 extern "C" int b32_set_profiling(b32_ctx* c, int level) {
     if (!c) return B32_E_ARG;
     c->profile_level = level < 0 ? 0 : (level > 2 ? 2 : level);
-    if (!c->profile_level) c->hover_timed = false;
-    if (!c->profile_level) c->world_timed = false;      // (b32_last_kernel_times no longer reports "world_project")
+    if (!c->profile_level) c->hover_timer.timed = c->world_timer.timed = false;     // (b32_last_kernel_times no longer reports "hover", "world_project")
     c->prof_seq = 0;
     if (c->profile_level >= 1 && !c->ev_created) {      // (here, not in the first profiled frame: 384 hipEventCreate calls are ~0.2 ms of host time)
         (void)hipSetDevice(c->device);

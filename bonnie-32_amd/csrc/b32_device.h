@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/b32raster.h"
+#include "b32_world_point.h"
 
 namespace b32 {
 
@@ -515,11 +516,9 @@ constexpr uint32_t WORLD_SMALL = 48;           // batches of at most this many i
 struct WorldArgs {
     const B32WorldItem* items; uint32_t n;     // items == nullptr: the batch is the kernel argument
     B32Prim* out; unsigned long long* counts;
-    float pos[3], bx[3], by[3], bz[3];         // Camera
-    float vs, half_w, half_h;                  // (min(w, h) as f32 / 2.0) * 0.75, w as f32 / 2.0, h as f32 / 2.0 (math.rs:524-531)
-    float zoom, center_x, center_y; uint32_t has_ortho;
+    ViewBlock v;                               // camera and projection constants (b32_world_point.h)
 };
-void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);
+void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small);   // small != nullptr: n <= WORLD_SMALL items passed by value
 // The world editor's overlay helpers projected into B32Prim records on the device (b32_draw_gizmos, b32_gizmo.hip): one lane per row, the
 // item's records at out[first ...] (`first`: the records of the rows before it, added up by the host).  w.items is unused, w.n the rows,
 // w.counts the gizmo entry's own drawn / dropped / rejected.  The records go through the pass's GizmoPass kernels (b32_prims.hip).
@@ -535,16 +534,16 @@ struct PickItem {
     uint32_t nv, nf;
     float cos_f, sin_f, wpos[3];
     uint32_t first_wg, _pad;                    // the item's workgroups are [first_wg, first_wg + ceil(nf / PICK_CHUNK))
-};   // small != nullptr: n <= WORLD_SMALL items passed by value
+};
 // The modeler's polygons on the device (b32_topology, b32_hover.hip): per polygon position one half-edge, and the fan triangles.
 struct HoverHalfEdge { uint32_t v0, v1, edge, first; };     // (v[k], v[(k + 1) % n]), the id of the normalised edge (min, max), and -- for the
                                                             // first half-edge of its edge in loop order -- 1 + how many edges began before it (else 0)
 struct HoverFanTri { uint32_t v[3], poly; };                // (v[0], v[k], v[k + 1]) and its polygon
 // The modeler's selection overlays made into B32Prim records on the device (b32_draw_mesh_overlay, b32_overlay.hip): where a record lies
-// is decided by the host (overlay_layout, b32_overlay_body.h), the kernels fill the places.  w.out: the records; w.items / n / counts unused.
+// is decided by the host (overlay_layout, b32_overlay_body.h), the kernels fill the places.
 struct OverlayPoint; struct OverlayBounds;
 struct OverlayArgs {
-    WorldArgs w;
+    ViewBlock v; B32Prim* out;                  // camera and projection constants; the records
     const float* pos; uint32_t stride, nv;      // the slot's positions as they are: `stride` floats between two vertices
     const HoverHalfEdge* he; const uint32_t* poly_start; const uint32_t* poly_verts; uint32_t np, nh;
     OverlayPoint* tab;                          // nv projected vertices (k_overlay_points writes, k_overlay_emit reads)

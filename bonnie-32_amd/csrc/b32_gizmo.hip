@@ -23,7 +23,7 @@ __device__ __forceinline__ void gizmo_project(const GizmoArgs& a, const GizmoRow
     if (threadIdx.x < 3u) tally[threadIdx.x] = 0u;
     __syncthreads();
     uint32_t which = 3u;
-    if (live) which = gizmo_item(a.w, row.it, a.w.out + row.first);
+    if (live) which = gizmo_item(a.w.v, row.it, a.w.out + row.first);
     // one add per wave into LDS, one per workgroup and counter into memory (as k_world_project)
 #pragma unroll
     for (uint32_t k = 0; k < 3u; ++k) {

@@ -5,11 +5,11 @@
 // reference's order; the text also compiles for the host (B32_HD, b32_world_point.h), where tests/test_gizmos.py runs it against a
 // literal restatement, built with and without -ffp-contract=off.
 #pragma once
-#include "b32_world_point.h"
-#if !defined(__HIPCC__)
+#if defined(__HIPCC__)
+#include "b32_device.h"
+#else
 #include <math.h>
-#include <stdint.h>
-#include "../../include/b32raster.h"
+#include "b32_world_point.h"
 #endif
 
 namespace b32 {
@@ -95,8 +95,7 @@ B32_HD void gizmo_thick_offset(float px, float py, float half, int32_t i, int32_
 
 // the editor's project_vertex, viewport_3d.rs:6239-6245: perspective_transform (math.rs:103-109), `cam.z < 0.1` -> None, project
 // (math.rs:117-136), `as i32`
-template <class A>
-B32_HD bool gizmo_project_vertex(const A& a, const float* p, int32_t& x, int32_t& y) {
+B32_HD bool gizmo_project_vertex(const ViewBlock& a, const float* p, int32_t& x, int32_t& y) {
     const float rel[3] = { p[0] - a.pos[0], p[1] - a.pos[1], p[2] - a.pos[2] };
     const float cam_x = world_dot(rel, a.bx), cam_y = world_dot(rel, a.by), cam_z = world_dot(rel, a.bz);
     if (cam_z < WORLD_NEAR) return false;
@@ -141,9 +140,8 @@ B32_HD B32Prim gizmo_noop() {                      // draws nothing (PrimPass::b
 B32_HD float gizmo_depth(float z) { return z != z ? gizmo_bits_f32(0x7FC00000) : z; }   // (one quiet NaN, as b32_draw_world's records)
 
 // One item into its gizmo_record_count(kind, size) records at `out`, in the reference's call order; returns 0 drawn, 1 dropped (the
-// reference draws nothing), 2 rejected (the reference's i32 arithmetic cannot carry it).  `a`: WorldArgs's camera and projection members.
-template <class A>
-B32_HD uint32_t gizmo_item(const A& a, const B32GizmoItem& it, B32Prim* out) {
+// reference draws nothing), 2 rejected (the reference's i32 arithmetic cannot carry it).
+B32_HD uint32_t gizmo_item(const ViewBlock& a, const B32GizmoItem& it, B32Prim* out) {
     const uint32_t n_rec = gizmo_record_count(it.kind, it.size);
     for (uint32_t k = 0; k < n_rec; ++k) out[k] = gizmo_noop();
     B32Prim base{};

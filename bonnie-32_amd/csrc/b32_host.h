@@ -130,6 +130,20 @@ struct b32_topology {
     std::vector<uint32_t> h_poly_start;         // np + 1 on the host: where the overlay's records lie (overlay_layout)
 };
 
+// Device words that stay armed between two calls (armed_ensure).
+struct ArmedWords { void* p = nullptr; size_t cap = 0; };
+// HIP events around the kernels of the last call of its kind enqueued while profiling was on (b32_last_kernel_times); created on first use.
+struct EventPair {
+    hipEvent_t ev[2] = {}; bool timed = false;
+    hipError_t begin(hipStream_t s) {
+        for (hipEvent_t& e : ev) if (!e) { const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; }
+        return hipEventRecord(ev[0], s);
+    }
+    hipError_t end(hipStream_t s) { const hipError_t r = hipEventRecord(ev[1], s); if (r == hipSuccess) timed = true; return r; }
+    bool elapsed(float* ms) const { return timed && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess; }   // (waits)
+    void destroy() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct b32_ctx {
     int device = 0;
     int n_cu = 256;
@@ -208,12 +222,12 @@ struct b32_ctx {
     // written into prims.dev and drawn as a primitive batch); drawn / dropped / rejected on the device; HIP events around the last
     // projection kernel enqueued while profiling was on (b32_last_kernel_times "world_project")
     DrawPassState<B32WorldItem> world;
-    unsigned long long* world_counts = nullptr;
+    ArmedWords world_counts;
     unsigned long long world_tile_batches = 0, world_scan_batches = 0;
-    hipEvent_t world_ev[2] = {}; bool world_timed = false;
+    EventPair world_timer;
     // b32_draw_gizmos: the rows' pinned ring and device copy (as `world`), the rows of the batch being validated, the entry's own counts
     DrawPassState<GizmoRow> gizmo; std::vector<GizmoRow> gizmo_rows;
-    unsigned long long* gizmo_counts = nullptr;
+    ArmedWords gizmo_counts;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
     Ctrl h_ctrl{}; Stamps h_stamps{};          // host copies of the frame set's control block (FrameSet::d_ctrl: Ctrl followed by Stamps)
@@ -255,21 +269,19 @@ struct b32_ctx {
     // transfer has left, dl_stream), the blocking form's page-locked landing buffer, HIP events around the last pick enqueued while
     // profiling was on (b32_last_kernel_times "pick")
     static constexpr uint32_t PICK_RING = 4;
-    void* pick_words = nullptr; size_t pick_cap_words = 0;
+    ArmedWords pick_words;
     DrawPassState<PickItem> pick_tab;
     void* pick_res[PICK_RING] = {}; size_t pick_cap_res[PICK_RING] = {}; hipEvent_t pick_done[PICK_RING] = {}, pick_left[PICK_RING] = {}; uint32_t pick_slot = 0;
     void* pick_host = nullptr; size_t pick_cap_host = 0;
-    hipEvent_t pick_tev[2] = {}; bool pick_timed = false;
+    EventPair pick_timer;
     // b32_hover_mesh / b32_box_select[_async] (b32_hover.hip): the front pass's vertex bitmap and, behind it, its edge bitmap (all zero
     // between two calls), the minima of a hover (HoverWords, all ones between two calls), HIP events around the last hover enqueued while
     // profiling was on (b32_last_kernel_times "hover").  Results leave through the pick's ring of result buffers.
-    uint32_t* hover_bits = nullptr; size_t hover_cap_bits = 0;
-    void* hover_words = nullptr;
-    hipEvent_t hover_tev[2] = {}; bool hover_timed = false;
+    ArmedWords hover_bits, hover_words;
+    EventPair hover_timer;
     // b32_room_hover / b32_room_box_select[_async] (b32_room.hip): the three sets of minima of a room hover (all ones between two calls) and
     // the device copy of a box selection's points.  Results leave through the pick's ring of result buffers.
-    void* room_words = nullptr;
-    float* room_points = nullptr; size_t room_cap_points = 0;
+    ArmedWords room_words, room_points;
     // b32_draw_mesh_overlay (b32_overlay.hip): the projected vertices of the call being enqueued, the bounds' keys (armed between two
     // calls), the selected list's pinned ring and device copy (the staging half of DrawPassState, as `world`)
     uint4* overlay_tab = nullptr; size_t overlay_cap_tab = 0;     // (16 bytes per vertex: OverlayPoint)
@@ -301,6 +313,18 @@ static int ensure(b32_ctx* c, T*& p, size_t& cap, size_t need) {
     size_t n = need + need / 4 + 16;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
     cap = n;
+    return B32_OK;
+}
+// Device words that stay armed between two calls (all ones, all zero: `fill`, a byte; < 0: no fill): at least `bytes` of them, allocated
+// on first use and filled on the context's stream; growing waits for the stream before it frees.  Unlike ensure() it leaves side_dirty
+// alone: nothing on the side stream reads these.
+static int armed_ensure(b32_ctx* c, ArmedWords& w, size_t bytes, int fill) {
+    if (w.p && bytes <= w.cap) return B32_OK;
+    if (w.p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(w.p)); w.p = nullptr; w.cap = 0; }
+    const size_t cap = bytes + bytes / 4 + 64;
+    HIPCHK(c, hipMalloc(&w.p, cap));
+    w.cap = cap;
+    if (fill >= 0) HIPCHK(c, hipMemsetAsync(w.p, fill, cap, c->stream));
     return B32_OK;
 }
 template <typename T>

@@ -24,11 +24,9 @@
 
 namespace b32 {
 
-constexpr size_t BOX_HEADER = 16;               // {uint32 n_elements; uint32 n_selected; 8 bytes of padding} in front of the words
-
 struct HoverWords { unsigned long long vkey, ekey; PickWords face; };
 struct HoverArgs {
-    PickArgs p;                                 // camera, cursor, cull = !SEE_THROUGH, result (table / words / n unused)
+    QueryArgs q;                                // camera, cursor, cull = !SEE_THROUGH, result
     PickItem it;                                // the slot's vertices and the placement (faces / nf / first_wg unused)
     const HoverHalfEdge* he; const HoverFanTri* fan; const uint32_t* poly_start; const uint32_t* poly_verts;
     uint32_t np, nh, nt, placed;
@@ -39,7 +37,7 @@ struct HoverArgs {
     const float* rest;                          // a rigged slot's rest stream (24 B per vertex: position, normal), else nullptr
 };
 struct BoxArgs {
-    PickArgs p; PickItem it;
+    QueryArgs q; PickItem it;
     const uint32_t* poly_start; const uint32_t* poly_verts;
     uint32_t n, mode, placed, nwords;
     float x0, y0, x1, y1;
@@ -68,7 +66,7 @@ __device__ __forceinline__ bool hover_screen(const HoverArgs& a, uint32_t i, boo
     float local[3], world[3], z;
     pick_vertex(a.it, a.placed != 0u, i, local, world);
     if (mirror && !hover_editable_at<RIG>(a, i, local)) return false;
-    return world_point(a.p.w, world, a.p.w.has_ortho != 0u, sx, sy, z);
+    return world_point(a.q.v, world, a.q.v.has_ortho != 0u, sx, sy, z);
 }
 __device__ __forceinline__ bool hover_bit(const uint32_t* bits, uint32_t i) { return ((bits[i >> 5] >> (i & 31u)) & 1u) != 0u; }
 
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
     const uint32_t range = wg < a.gv ? 0u : (wg < a.gv + a.ge ? 1u : 2u);
     const uint32_t e0 = (wg - (range == 0u ? 0u : (range == 1u ? a.gv : a.gv + a.ge))) * PICK_CHUNK;
     const uint32_t count = range == 0u ? a.it.nv : (range == 1u ? a.nh : a.nt);
-    const bool cull = a.p.cull != 0u;
+    const bool cull = a.q.cull != 0u;
     PickWords m = pick_no_hit();                // vertices and half-edges use the key alone
 #pragma unroll 1
     for (uint32_t trip = 0; trip < PICK_CHUNK / 256u; ++trip) {
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
             if (cull && !hover_bit(a.vbits, i)) continue;
             float sx, sy;
             if (!hover_screen<RIG>(a, i, true, sx, sy)) continue;
-            const float dist = hover_dist(a.p.mx, a.p.my, sx, sy);
+            const float dist = hover_dist(a.q.mx, a.q.my, sx, sy);
             if (dist < a.vthr) m.key = min(m.key, ((unsigned long long)__float_as_uint(dist) << 32) | i);
         } else if (range == 1u) {               // viewport.rs:2507-2542
             const HoverHalfEdge h = a.he[i];
@@ -138,9 +136,9 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
             pick_vertex(a.it, a.placed != 0u, h.v0, l0, w0);
             pick_vertex(a.it, a.placed != 0u, h.v1, l1, w1);
             if (!hover_editable_at<RIG>(a, h.v0, l0) || !hover_editable_at<RIG>(a, h.v1, l1)) continue;
-            const bool ortho = a.p.w.has_ortho != 0u;
-            if (!world_point(a.p.w, w0, ortho, x0, y0, z) || !world_point(a.p.w, w1, ortho, x1, y1, z)) continue;
-            const float dist = hover_line_dist(a.p.mx, a.p.my, x0, y0, x1, y1);
+            const bool ortho = a.q.v.has_ortho != 0u;
+            if (!world_point(a.q.v, w0, ortho, x0, y0, z) || !world_point(a.q.v, w1, ortho, x1, y1, z)) continue;
+            const float dist = hover_line_dist(a.q.mx, a.q.my, x0, y0, x1, y1);
             if (dist < a.ethr) m.key = min(m.key, ((unsigned long long)__float_as_uint(dist) << 32) | i);
         } else {                                // viewport.rs:2544-2594
             const HoverFanTri f = a.fan[i];
@@ -156,24 +154,19 @@ __global__ __launch_bounds__(256) void k_hover(HoverArgs a) {
                 }
             }
             float depth;
-            if (editable && pick_triangle_idx(a.p, a.it, a.placed != 0u, f.v, depth)) pick_take(m, depth, i);
+            if (editable && pick_triangle_idx(a.q, a.it, a.placed != 0u, f.v, depth)) pick_take(m, depth, i);
         }
     }
     m = pick_reduce(m);
     if (threadIdx.x == 0u) {
         if (range == 0u) { if (m.key != ~0ull) __hip_atomic_fetch_min(&a.words->vkey, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         else if (range == 1u) { if (m.key != ~0ull) __hip_atomic_fetch_min(&a.words->ekey, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        else if (m.first != PICK_NONE) {
-            PickWords* w = &a.words->face;
-            __hip_atomic_fetch_min(&w->first, m.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (m.first_nan != PICK_NONE) __hip_atomic_fetch_min(&w->first_nan, m.first_nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (m.key != ~0ull) __hip_atomic_fetch_min(&w->key, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        else pick_offer(m, &a.words->face);
     }
 }
 
 __global__ __launch_bounds__(256) void k_hover_resolve(HoverArgs a) {
-    if (a.p.cull) {                                                                     // the bitmaps of the front pass: zero for the next call
+    if (a.q.cull) {                                                                     // the bitmaps of the front pass: zero for the next call
         for (uint32_t i = threadIdx.x; i < a.vwords; i += 256u) a.vbits[i] = 0u;
         for (uint32_t i = threadIdx.x; i < a.ewords; i += 256u) a.ebits[i] = 0u;
     }
@@ -189,17 +182,16 @@ __global__ __launch_bounds__(256) void k_hover_resolve(HoverArgs a) {
         const HoverHalfEdge h = a.he[(uint32_t)w.ekey];
         r.edge_v0 = min(h.v0, h.v1); r.edge_v1 = max(h.v0, h.v1); r.edge_dist = __uint_as_float((uint32_t)(w.ekey >> 32));
     }
-    if (w.face.first != PICK_NONE) {
-        uint32_t tri;
-        if (w.face.first == w.face.first_nan) { tri = w.face.first; r.face_depth = __uint_as_float(PICK_QNAN); }
+    uint32_t tri; bool nan;
+    if (pick_winner(w.face, tri, nan)) {
+        if (nan) r.face_depth = __uint_as_float(PICK_QNAN);
         else {
-            tri = (uint32_t)w.face.key;
             const HoverFanTri f = a.fan[tri];
-            (void)pick_triangle_idx(a.p, a.it, a.placed != 0u, f.v, r.face_depth);     // the winner's own bits (the sign of a zero)
+            (void)pick_triangle_idx(a.q, a.it, a.placed != 0u, f.v, r.face_depth);     // the winner's own bits (the sign of a zero)
         }
         r.face = a.fan[tri].poly;
     }
-    *reinterpret_cast<B32HoverResult*>(a.p.result) = r;
+    *reinterpret_cast<B32HoverResult*>(a.q.result) = r;
 }
 
 // apply_box_selection, viewport.rs:1708-1726 (mode 0) and :1743-1766 (mode 1).  The header's n_selected is zero when the kernel starts.
@@ -227,20 +219,10 @@ __global__ __launch_bounds__(256) void k_box_select(BoxArgs a) {
             world[0] = acc[0] * inv; world[1] = acc[1] * inv; world[2] = acc[2] * inv;
         }
         float sx, sy, z;
-        if (some && world_point(a.p.w, world, a.p.w.has_ortho != 0u, sx, sy, z))
+        if (some && world_point(a.q.v, world, a.q.v.has_ortho != 0u, sx, sy, z))
             sel = sx >= a.x0 && sx <= a.x1 && sy >= a.y0 && sy <= a.y1;
     }
-    const unsigned long long b = __ballot(sel);
-    uint32_t* head = reinterpret_cast<uint32_t*>(a.p.result);
-    if ((threadIdx.x & 63u) == 0u) {                                                     // (i is a multiple of 64 here)
-        uint32_t* words = head + BOX_HEADER / 4;
-        const uint32_t wd = i >> 5;
-        if (wd < a.nwords) words[wd] = (uint32_t)b;
-        if (wd + 1u < a.nwords) words[wd + 1u] = (uint32_t)(b >> 32);
-        const uint32_t cnt = (uint32_t)__popcll(b);
-        if (cnt) __hip_atomic_fetch_add(&head[1], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (i == 0u) head[0] = a.n;
+    box_emit(a.q.result, i, a.n, a.nwords, sel);
 }
 
 }  // namespace b32
@@ -345,7 +327,7 @@ int b32_hover_mesh_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
     int rc;
     HoverArgs a{};
     const bool cull = !(prm->flags & B32_HOVER_SEE_THROUGH);
-    pick_fill_args(a.p, c, cam, ortho, prm->mx, prm->my, cull);
+    query_fill(a.q, c, cam, ortho, prm->mx, prm->my, cull);
     hover_item(a.it, slot, place);
     a.placed = place ? 1u : 0u;
     a.rest = slot->have_rig ? slot->d_rest : nullptr;
@@ -358,39 +340,26 @@ int b32_hover_mesh_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
     if (groups >= (1ull << 31)) return B32_E_UNSUPPORTED;
 
     // the words: all ones whenever no hover is running (allocated so; k_hover_resolve leaves them so)
-    if (!c->hover_words) {
-        HIPCHK(c, hipMalloc(&c->hover_words, sizeof(HoverWords)));
-        HIPCHK(c, hipMemsetAsync(c->hover_words, 0xFF, sizeof(HoverWords), c->stream));
-    }
-    a.words = static_cast<HoverWords*>(c->hover_words);
+    if ((rc = armed_ensure(c, c->hover_words, sizeof(HoverWords), 0xFF))) return rc;
+    a.words = static_cast<HoverWords*>(c->hover_words.p);
     // the bitmaps: all zero whenever no hover is running
     if (cull) {
         a.vwords = (uint32_t)(((unsigned long long)a.it.nv + 31u) / 32u); a.ewords = (uint32_t)(((unsigned long long)topo->ne + 31u) / 32u);
-        const size_t need = (size_t)a.vwords + a.ewords;
-        if (need > c->hover_cap_bits || !c->hover_bits) {
-            const size_t cap = need + need / 4 + 64;
-            if (c->hover_bits) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->hover_bits)); c->hover_bits = nullptr; c->hover_cap_bits = 0; }
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->hover_bits), cap * 4u));
-            HIPCHK(c, hipMemsetAsync(c->hover_bits, 0, cap * 4u, c->stream));
-            c->hover_cap_bits = cap;
-        }
-        a.vbits = c->hover_bits; a.ebits = c->hover_bits + a.vwords;
+        if ((rc = armed_ensure(c, c->hover_bits, ((size_t)a.vwords + a.ewords) * 4u, 0))) return rc;
+        a.vbits = static_cast<uint32_t*>(c->hover_bits.p); a.ebits = a.vbits + a.vwords;
     }
 
     unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
     const size_t bytes = sizeof(B32HoverResult);
-    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.p.result))) return rc;
+    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.q.result))) return rc;
     const bool timed = c->profile_level >= 1;
-    if (timed) {
-        for (hipEvent_t& e : c->hover_tev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->hover_tev[0], c->stream));
-    }
+    if (timed) HIPCHK(c, c->hover_timer.begin(c->stream));
     if (cull && a.np) hipLaunchKernelGGL(k_hover_front, dim3((a.np + 255u) / 256u), dim3(256), 0, c->stream, a);
     if (groups && a.rest) hipLaunchKernelGGL(k_hover<true>, dim3((uint32_t)groups), dim3(256), 0, c->stream, a);
     else if (groups) hipLaunchKernelGGL(k_hover<false>, dim3((uint32_t)groups), dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(k_hover_resolve, dim3(1), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    if (timed) { HIPCHK(c, hipEventRecord(c->hover_tev[1], c->stream)); c->hover_timed = true; }
+    if (timed) HIPCHK(c, c->hover_timer.end(c->stream));
     return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
 }
 
@@ -399,12 +368,11 @@ int b32_hover_mesh(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_
     { const int rc = hover_common_check(c, cam, slot); if (rc) return rc; }
     if (!out) return B32_E_ARG;
     (void)hipSetDevice(c->device);
-    int rc;
-    if ((rc = pick_host_ensure(c, sizeof(B32HoverResult)))) return rc;
-    uint64_t t = 0;
-    if ((rc = b32_hover_mesh_async(c, cam, ortho, slot, topo, place, prm, c->pick_host, &t))) return rc;
-    if ((rc = b32_ticket_wait(c, t))) return rc;
-    std::memcpy(out, c->pick_host, sizeof(B32HoverResult));
+    const unsigned char* h = nullptr;
+    const int rc = pick_blocking(c, sizeof(B32HoverResult), &h, [&](void* landing, uint64_t* t) {
+        return b32_hover_mesh_async(c, cam, ortho, slot, topo, place, prm, landing, t); });
+    if (rc) return rc;
+    std::memcpy(out, h, sizeof(B32HoverResult));
     return B32_OK;
 }
 
@@ -413,9 +381,8 @@ int b32_box_select_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
     { const int rc = hover_common_check(c, cam, slot); if (rc) return rc; }
     if (!prm || prm->mode > B32_BOX_POLYGONS || (prm->mode == B32_BOX_POLYGONS && !topo) || !out || !ticket) return B32_E_ARG;
     (void)hipSetDevice(c->device);
-    int rc;
     BoxArgs a{};
-    pick_fill_args(a.p, c, cam, ortho, 0.0f, 0.0f, false);
+    query_fill(a.q, c, cam, ortho, 0.0f, 0.0f, false);
     hover_item(a.it, slot, place);
     a.placed = place ? 1u : 0u;
     a.mode = prm->mode;
@@ -423,13 +390,8 @@ int b32_box_select_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho
     else a.n = a.it.nv;
     a.nwords = (uint32_t)(((unsigned long long)a.n + 31u) / 32u);
     a.x0 = prm->x0; a.y0 = prm->y0; a.x1 = prm->x1; a.y1 = prm->y1;
-    unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
-    const size_t bytes = BOX_HEADER + (size_t)a.nwords * 4u;
-    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.p.result))) return rc;
-    HIPCHK(c, hipMemsetAsync(a.p.result, 0, BOX_HEADER, c->stream));
-    if (a.n) hipLaunchKernelGGL(k_box_select, dim3((uint32_t)(((unsigned long long)a.n + 255u) / 256u)), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
+    return box_run(c, a.nwords, &a.q.result, out, ticket, [&] {
+        if (a.n) hipLaunchKernelGGL(k_box_select, dim3((uint32_t)(((unsigned long long)a.n + 255u) / 256u)), dim3(256), 0, c->stream, a); });
 }
 
 int b32_box_select(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_scene* slot, b32_topology* topo, const B32Placement* place,
@@ -438,15 +400,12 @@ int b32_box_select(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_
     if (!prm || prm->mode > B32_BOX_POLYGONS || (prm->mode == B32_BOX_POLYGONS && !topo) || !n_selected) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     const uint32_t n = prm->mode == B32_BOX_POLYGONS ? topo->np : slot->nv;
-    const size_t nwords = (size_t)(((unsigned long long)n + 31u) / 32u), bytes = BOX_HEADER + nwords * 4u;
-    int rc;
-    if ((rc = pick_host_ensure(c, bytes))) return rc;
-    uint64_t t = 0;
-    if ((rc = b32_box_select_async(c, cam, ortho, slot, topo, place, prm, c->pick_host, &t))) return rc;
-    if ((rc = b32_ticket_wait(c, t))) return rc;
-    const unsigned char* h = static_cast<const unsigned char*>(c->pick_host);
-    std::memcpy(n_selected, h + 4, 4);
-    if (words && nwords) std::memcpy(words, h + BOX_HEADER, nwords * 4u);
+    const size_t nwords = (size_t)(((unsigned long long)n + 31u) / 32u);
+    const unsigned char* h = nullptr;
+    const int rc = pick_blocking(c, box_bytes(nwords), &h, [&](void* landing, uint64_t* t) {
+        return b32_box_select_async(c, cam, ortho, slot, topo, place, prm, landing, t); });
+    if (rc) return rc;
+    box_landed(h, nwords, words, n_selected);
     return B32_OK;
 }
 

@@ -55,12 +55,12 @@ __global__ __launch_bounds__(256) void k_overlay_points(OverlayArgs a) {
     if (i < a.nv) {
         const float* src = a.pos + (size_t)i * a.stride;
         const float p[3] = { src[0], src[1], src[2] };
-        const OverlayPoint e = overlay_point(a.w, p);
+        const OverlayPoint e = overlay_point(a.v, p);
         a.tab[i] = e;
-        if (a.o.sections & B32_OVERLAY_DOTS) a.w.out[a.at_dots + i] = overlay_dot(e);
+        if (a.o.sections & B32_OVERLAY_DOTS) a.out[a.at_dots + i] = overlay_dot(e);
         if ((a.o.sections & B32_OVERLAY_PREVIEW) && a.o.preview_mode == 0u) {
             const float rect[4] = { a.o.x0, a.o.y0, a.o.x1, a.o.y1 };
-            a.w.out[a.at_preview + i] = overlay_preview_vertex(e, rect);
+            a.out[a.at_preview + i] = overlay_preview_vertex(e, rect);
         }
         if (brackets) overlay_bounds_take(b, p);
     }
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_overlay_emit(OverlayArgs a) {
     uint32_t wg = blockIdx.x;
     const OverlayPoint* tab = a.tab;
     const float rect[4] = { a.o.x0, a.o.y0, a.o.x1, a.o.y1 };
-    B32Prim* out = a.w.out;
+    B32Prim* out = a.out;
     if (wg < a.g_edges) {                           // :1924-1935
         const uint32_t h = wg * 256u + threadIdx.x;
         if (h >= a.nh) return;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void k_overlay_emit(OverlayArgs a) {
         } else {
             const uint32_t p = a.selected[2u * i], first = a.selected[2u * i + 1u];      // (p < np: the host left the others out)
             const uint32_t s = a.poly_start[p], e = a.poly_start[p + 1u];
-            overlay_polygon(a.w, OVERLAY_POLY_SELECTED, a.poly_verts + s, e - s, a.pos, a.stride, a.nv, tab, rect, out + first);
+            overlay_polygon(a.v, OVERLAY_POLY_SELECTED, a.poly_verts + s, e - s, a.pos, a.stride, a.nv, tab, rect, out + first);
         }
         return;
     }
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_overlay_emit(OverlayArgs a) {
         const uint32_t p = wg * 256u + threadIdx.x;
         if (p >= a.np) return;
         const uint32_t s = a.poly_start[p], e = a.poly_start[p + 1u];
-        overlay_polygon(a.w, OVERLAY_POLY_PREVIEW, a.poly_verts + s, e - s, a.pos, a.stride, a.nv, tab, rect, out + a.at_preview + s + p);
+        overlay_polygon(a.v, OVERLAY_POLY_PREVIEW, a.poly_verts + s, e - s, a.pos, a.stride, a.nv, tab, rect, out + a.at_preview + s + p);
         return;
     }
     wg -= a.g_pfaces;
@@ -128,13 +128,13 @@ __global__ __launch_bounds__(256) void k_overlay_emit(OverlayArgs a) {
             overlay_hover_edge(a.o.hover_edge_v0, a.o.hover_edge_v1, a.nv, tab, out + a.at_hover_edge);
         if (threadIdx.x == 2u && a.hover_face_cnt) {
             const uint32_t s = a.poly_start[a.o.hover_face];
-            overlay_polygon(a.w, OVERLAY_POLY_HOVER, a.poly_verts + s, a.hover_face_cnt, a.pos, a.stride, a.nv, tab, rect, out + a.at_hover_face);
+            overlay_polygon(a.v, OVERLAY_POLY_HOVER, a.poly_verts + s, a.hover_face_cnt, a.pos, a.stride, a.nv, tab, rect, out + a.at_hover_face);
         }
         return;
     }
     // the brackets, :1821-1883: the bounds are complete (k_overlay_points ran before this kernel on the stream)
     const OverlayBounds b = *a.bounds;
-    if (threadIdx.x < 24u) out[a.at_brackets + threadIdx.x] = overlay_bracket(a.w, b, threadIdx.x);
+    if (threadIdx.x < 24u) out[a.at_brackets + threadIdx.x] = overlay_bracket(a.v, b, threadIdx.x);
     __syncthreads();                                // every lane has read the bounds
     if (threadIdx.x < 3u) { a.bounds->mn[threadIdx.x] = OVERLAY_KEY_MIN0; a.bounds->mx[threadIdx.x] = OVERLAY_KEY_MAX0; }
 }

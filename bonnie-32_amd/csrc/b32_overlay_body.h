@@ -14,11 +14,11 @@
 //   SELECTED  n_selected | 4 * n_selected | sum of 2 * n + 1 over the listed polygons < np
 //   PREVIEW   nv | 2 * ne (first half-edge of every edge, in loop order) | nh + np (polygon p at poly_start[p] + p)
 #pragma once
-#include "b32_world_point.h"
-#if !defined(__HIPCC__)
+#if defined(__HIPCC__)
+#include "b32_device.h"
+#else
 #include <math.h>
-#include <stdint.h>
-#include "../../include/b32raster.h"
+#include "b32_world_point.h"
 #endif
 
 namespace b32 {
@@ -119,9 +119,7 @@ B32_HD B32Prim overlay_circle(const OverlayPoint& e, int32_t radius, OverlayColo
 // sx >= fb_x0 && sx <= fb_x1 && sy >= fb_y0 && sy <= fb_y1 (a NaN gives false); rect = x0, y0, x1, y1
 B32_HD bool overlay_inside(float x, float y, const float* rect) { return x >= rect[0] && x <= rect[2] && y >= rect[1] && y <= rect[3]; }
 
-// `a`: WorldArgs's camera and projection members
-template <class A>
-B32_HD OverlayPoint overlay_point(const A& a, const float* p) {
+B32_HD OverlayPoint overlay_point(const ViewBlock& a, const float* p) {
     OverlayPoint e; e.sx = 0.0f; e.sy = 0.0f; e.z = 0.0f;
     e.some = world_point(a, p, a.has_ortho != 0u, e.sx, e.sy, e.z) ? 1u : 0u;
     return e;
@@ -194,8 +192,7 @@ constexpr uint32_t overlay_polygon_slots(uint32_t mode, uint32_t cnt) {
 // into its overlay_polygon_slots records at `out`.  The outline is streamed: the first, the third and the previous projected vertex are
 // kept, prev -> cur is written as the walk goes and last -> first closes it; fewer than three projected vertices take it back.
 // pos / stride: the slot's positions (floats between two vertices).
-template <class A>
-B32_HD void overlay_polygon(const A& a, uint32_t mode, const uint32_t* pv, uint32_t cnt, const float* pos, uint32_t stride, uint32_t nv,
+B32_HD void overlay_polygon(const ViewBlock& a, uint32_t mode, const uint32_t* pv, uint32_t cnt, const float* pos, uint32_t stride, uint32_t nv,
                             const OverlayPoint* tab, const float* rect, B32Prim* out) {
     const uint32_t slots = overlay_polygon_slots(mode, cnt);
     const OverlayColor col = mode == OVERLAY_POLY_HOVER ? OVERLAY_HOVER_COLOR : (mode == OVERLAY_POLY_SELECTED ? OVERLAY_SELECT_COLOR : OVERLAY_PREVIEW_COLOR);
@@ -258,8 +255,7 @@ B32_HD void overlay_polygon(const A& a, uint32_t mode, const uint32_t* pv, uint3
 }
 
 // :1821-1883, bracket k (corner k / 3, direction k % 3) from the finished bounds
-template <class A>
-B32_HD B32Prim overlay_bracket(const A& a, const OverlayBounds& b, uint32_t k) {
+B32_HD B32Prim overlay_bracket(const ViewBlock& a, const OverlayBounds& b, uint32_t k) {
     float mn[3], mx[3];
     for (int c = 0; c < 3; ++c) { mn[c] = overlay_unkey(b.mn[c]) - 4.0f; mx[c] = overlay_unkey(b.mx[c]) + 4.0f; }
     const float size[3] = { mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2] };

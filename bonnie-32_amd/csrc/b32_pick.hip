@@ -51,32 +51,27 @@ __global__ __launch_bounds__(256) void k_pick(PickArgs a, PickTable small) {
     for (uint32_t trip = 0; trip < PICK_CHUNK / 256u; ++trip) {
         const uint32_t t = t0 + trip * 256u + threadIdx.x;
         float depth;
-        if (t >= t0 && t < it.nf && pick_triangle(a, it, t, depth)) pick_take(m, depth, t);
+        if (t >= t0 && t < it.nf && pick_triangle(a.q, it, t, depth)) pick_take(m, depth, t);
     }
     m = pick_reduce(m);
-    if (threadIdx.x == 0u && m.first != PICK_NONE) {
-        PickWords* w = a.words + item;
-        __hip_atomic_fetch_min(&w->first, m.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (m.first_nan != PICK_NONE) __hip_atomic_fetch_min(&w->first_nan, m.first_nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (m.key != ~0ull) __hip_atomic_fetch_min(&w->key, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (threadIdx.x == 0u) pick_offer(m, a.words + item);
 }
 
 template <bool SMALL>
 __global__ __launch_bounds__(256) void k_pick_resolve(PickArgs a, PickTable small) {
-    B32PickHit* hits = reinterpret_cast<B32PickHit*>(a.result + PICK_HEADER);
+    B32PickHit* hits = reinterpret_cast<B32PickHit*>(a.q.result + PICK_HEADER);
     PickWords m = pick_no_hit();
     for (uint32_t i = threadIdx.x; i < a.n; i += 256u) {
         const PickWords w = a.words[i];
         a.words[i] = pick_no_hit();                                                      // armed for the next pick on this stream
         B32PickHit h; h.hit = 0u; h.tri = PICK_NONE; h.depth = 0.0f; h._pad = 0u;
-        if (w.first != PICK_NONE) {
+        bool nan;
+        if (pick_winner(w, h.tri, nan)) {
             h.hit = 1u;
-            if (w.first == w.first_nan) { h.tri = w.first; h.depth = __uint_as_float(PICK_QNAN); }
+            if (nan) h.depth = __uint_as_float(PICK_QNAN);
             else {
-                h.tri = (uint32_t)w.key;
                 const PickItem it = SMALL ? small.r[i] : a.table[i];
-                (void)pick_triangle(a, it, h.tri, h.depth);                              // the winner's own bits (the sign of a zero)
+                (void)pick_triangle(a.q, it, h.tri, h.depth);                            // the winner's own bits (the sign of a zero)
             }
             pick_take(m, h.depth, i);
         }
@@ -84,8 +79,9 @@ __global__ __launch_bounds__(256) void k_pick_resolve(PickArgs a, PickTable smal
     }
     m = pick_reduce(m);
     if (threadIdx.x == 0u) {
-        int32_t* head = reinterpret_cast<int32_t*>(a.result);
-        head[0] = m.first == PICK_NONE ? -1 : (int32_t)(m.first == m.first_nan ? m.first : (uint32_t)m.key);
+        int32_t* head = reinterpret_cast<int32_t*>(a.q.result);
+        uint32_t best; bool nan;
+        head[0] = pick_winner(m, best, nan) ? (int32_t)best : -1;
         head[1] = (int32_t)a.n; head[2] = 0; head[3] = 0;
     }
 }
@@ -138,23 +134,17 @@ int b32_pick_meshes_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* orth
     if ((rc = pick_table(slots, places, n, rows, groups))) return rc;
 
     PickArgs a{};
-    pick_fill_args(a, c, cam, ortho, mx, my, (flags & B32_PICK_CULL_BACKFACES) != 0u);
+    query_fill(a.q, c, cam, ortho, mx, my, (flags & B32_PICK_CULL_BACKFACES) != 0u);
     a.n = n;
 
     // the words: all ones whenever no pick is running (allocated so; k_pick_resolve leaves them so)
-    if ((size_t)n > c->pick_cap_words || !c->pick_words) {
-        const size_t cap = (size_t)n + n / 4 + 64;
-        if (c->pick_words) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->pick_words)); c->pick_words = nullptr; c->pick_cap_words = 0; }
-        HIPCHK(c, hipMalloc(&c->pick_words, cap * sizeof(PickWords)));
-        HIPCHK(c, hipMemsetAsync(c->pick_words, 0xFF, cap * sizeof(PickWords), c->stream));
-        c->pick_cap_words = cap;
-    }
-    a.words = static_cast<PickWords*>(c->pick_words);
+    if ((rc = armed_ensure(c, c->pick_words, (size_t)n * sizeof(PickWords), 0xFF))) return rc;
+    a.words = static_cast<PickWords*>(c->pick_words.p);
 
     // the ticket and the result buffer of this pick (pick_result_open)
     unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
     const size_t bytes = PICK_HEADER + (size_t)n * sizeof(B32PickHit);
-    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.result))) return rc;
+    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.q.result))) return rc;
 
     const bool small = n <= PICK_SMALL;
     PickTable tab{};
@@ -164,10 +154,7 @@ int b32_pick_meshes_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* orth
         a.table = c->pick_tab.dev;
     }
     const bool timed = c->profile_level >= 1;
-    if (timed) {
-        for (hipEvent_t& e : c->pick_tev) if (!e) HIPCHK(c, hipEventCreate(&e));
-        HIPCHK(c, hipEventRecord(c->pick_tev[0], c->stream));
-    }
+    if (timed) HIPCHK(c, c->pick_timer.begin(c->stream));
     if (groups) {
         if (small) hipLaunchKernelGGL(k_pick<true>, dim3(groups), dim3(256), 0, c->stream, a, tab);
         else hipLaunchKernelGGL(k_pick<false>, dim3(groups), dim3(256), 0, c->stream, a, tab);
@@ -175,7 +162,7 @@ int b32_pick_meshes_async(b32_ctx* c, const B32Camera* cam, const B32Ortho* orth
     if (small) hipLaunchKernelGGL(k_pick_resolve<true>, dim3(1), dim3(256), 0, c->stream, a, tab);
     else hipLaunchKernelGGL(k_pick_resolve<false>, dim3(1), dim3(256), 0, c->stream, a, tab);
     HIPCHK(c, hipGetLastError());
-    if (timed) { HIPCHK(c, hipEventRecord(c->pick_tev[1], c->stream)); c->pick_timed = true; }
+    if (timed) HIPCHK(c, c->pick_timer.end(c->stream));
     return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
 }
 
@@ -184,13 +171,10 @@ int b32_pick_meshes(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, flo
     { const int rc = pick_check(c, cam, flags, slots, places, n); if (rc) return rc; }
     if (!best) return B32_E_ARG;
     (void)hipSetDevice(c->device);
-    const size_t bytes = PICK_HEADER + (size_t)n * sizeof(B32PickHit);
-    { const int rc = pick_host_ensure(c, bytes); if (rc) return rc; }
-    uint64_t t = 0;
-    int rc;
-    if ((rc = b32_pick_meshes_async(c, cam, ortho, mx, my, flags, slots, places, n, c->pick_host, &t))) return rc;
-    if ((rc = b32_ticket_wait(c, t))) return rc;
-    const unsigned char* h = static_cast<const unsigned char*>(c->pick_host);
+    const unsigned char* h = nullptr;
+    const int rc = pick_blocking(c, PICK_HEADER + (size_t)n * sizeof(B32PickHit), &h, [&](void* out, uint64_t* t) {
+        return b32_pick_meshes_async(c, cam, ortho, mx, my, flags, slots, places, n, out, t); });
+    if (rc) return rc;
     std::memcpy(best, h, sizeof(int32_t));
     if (hits && n) std::memcpy(hits, h + PICK_HEADER, (size_t)n * sizeof(B32PickHit));
     return B32_OK;

@@ -1,37 +1,29 @@
-// b32_pick_body.h -- what b32_pick.hip (b32_pick_meshes) and b32_hover.hip (b32_hover_mesh, b32_box_select) share: the body of the
-// reference's triangle loops for one triangle, the three minima that stand for "closest in loop order" and their reduction in a
-// workgroup, and on the host the ring of device result buffers whose content leaves through a ticket.  See b32_pick.hip for the why.
+// b32_pick_body.h -- what b32_pick.hip (b32_pick_meshes), b32_hover.hip (b32_hover_mesh, b32_box_select) and b32_room.hip (b32_room_hover,
+// b32_room_box_select) share.  On the device: the body of the reference's triangle loops for one triangle, the reduction of the three
+// minima (b32_pick_words.h) in a workgroup and their offer to memory, the bitmap tail of a box selection.  On the host: the ring of device
+// result buffers whose content leaves through a ticket, and the blocking forms' landing buffer.  See b32_pick.hip for the why.
 #pragma once
 #include "b32_host.h"
-#include "b32_world_point.h"
+#include "b32_pick_words.h"
 
 namespace b32 {
 
-constexpr uint32_t PICK_CHUNK = 1024;           // elements per workgroup: 256 lanes, four trips
-constexpr uint32_t PICK_NONE = 0xFFFFFFFFu;
-constexpr uint32_t PICK_QNAN = 0x7FC00000u;     // the one NaN a NaN depth is reported as (as b32_draw_world's records)
-
-struct PickWords { unsigned long long key; uint32_t first, first_nan; };
-// What the pick, the hover and the box selection hand their kernels in common.  The hover and the box selection (HoverArgs, BoxArgs in
-// b32_hover.hip) use w, mx, my, cull and result, and keep their own element counts and words.
-struct PickArgs {
-    WorldArgs w;                                // camera and projection constants (items / out / counts unused)
+// What the pick, the hover and the mesh box selection hand their kernels in common (PickArgs, HoverArgs, BoxArgs add their own).
+struct QueryArgs {
+    ViewBlock v;                                // camera and projection constants
     float mx, my; uint32_t cull;                // the cursor (unused by the box selection); back-face culling, for the hover "not SEE_THROUGH"
-    uint32_t n;                                 // pick: entries of the table
-    const PickItem* table;                      // pick: nullptr = the table is the kernel argument
-    PickWords* words;                           // pick: n entries, all ones between two picks (the hover's are HoverArgs::words)
     unsigned char* result;                      // the call's device result buffer (pick_result_open), whose layout is the call's:
                                                 //   pick   {int32 best; uint32 n; 8 bytes of padding} + n * sizeof(B32PickHit)
                                                 //   hover  one B32HoverResult
                                                 //   box    {uint32 n_elements; uint32 n_selected; 8 bytes of padding} + ceil(n_elements / 32) words
 };
-
-// total order of the non-NaN f32 as u32, both zeros on one value
-__device__ __forceinline__ uint32_t pick_orderable(float d) {
-    uint32_t u = __float_as_uint(d);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+struct PickArgs {
+    QueryArgs q;
+    uint32_t n;                                 // entries of the table
+    const PickItem* table;                      // nullptr = the table is the kernel argument
+    PickWords* words;                           // n entries, all ones between two picks
+};
+constexpr size_t BOX_HEADER = 16;               // {uint32 n_elements; uint32 n_selected; 8 bytes of padding} in front of a box selection's words
 
 // Vertex i (< it.nv) of an item: its local position, and the position the loops project -- placed (viewport_3d.rs:7716-7718) or, for
 // the modeler without a placement, as it is.
@@ -48,15 +40,15 @@ __device__ __forceinline__ void pick_vertex(const PickItem& it, bool placed, uin
 
 // The triangle (idx[0], idx[1], idx[2]) of an item through the body of the reference's loops: false = skipped or missed, true = hit
 // with `depth`.
-__device__ __forceinline__ bool pick_triangle_idx(const PickArgs& a, const PickItem& it, bool placed, const uint32_t* idx, float& depth) {
+__device__ __forceinline__ bool pick_triangle_idx(const QueryArgs& a, const PickItem& it, bool placed, const uint32_t* idx, float& depth) {
     if (idx[0] >= it.nv || idx[1] >= it.nv || idx[2] >= it.nv) return false;            // screen_verts.get(..) == None
-    const bool ortho = a.w.has_ortho != 0u;
+    const bool ortho = a.v.has_ortho != 0u;
     float sx[3], sy[3], d[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         float local[3], world[3];
         pick_vertex(it, placed, idx[k], local, world);
-        if (!world_point(a.w, world, ortho, sx[k], sy[k], d[k])) return false;
+        if (!world_point(a.v, world, ortho, sx[k], sy[k], d[k])) return false;
     }
     const float px = a.mx, py = a.my;
     const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sx[2] - sx[0]) * (sy[1] - sy[0]);
@@ -77,45 +69,55 @@ __device__ __forceinline__ bool pick_triangle_idx(const PickArgs& a, const PickI
     return true;
 }
 // Triangle t of an item's face list, placed.
-__device__ __forceinline__ bool pick_triangle(const PickArgs& a, const PickItem& it, uint32_t t, float& depth) {
+__device__ __forceinline__ bool pick_triangle(const QueryArgs& a, const PickItem& it, uint32_t t, float& depth) {
     const uint32_t* fv = it.faces[t].v;
     const uint32_t idx[3] = { fv[0], fv[1], fv[2] };
     return pick_triangle_idx(a, it, true, idx, depth);
 }
 
-// One hit into a lane's three minima; `id` is the triangle (k_pick, k_hover) or the item (k_pick_resolve).
-__device__ __forceinline__ void pick_take(PickWords& m, float depth, uint32_t id) {
-    m.first = min(m.first, id);
-    if (depth != depth) m.first_nan = min(m.first_nan, id);
-    else m.key = min(m.key, ((unsigned long long)pick_orderable(depth) << 32) | id);
-}
 // The workgroup's minima in thread 0 (256 lanes): shuffles in the wave, then the four waves through LDS.
 __device__ __forceinline__ PickWords pick_reduce(PickWords m) {
     __shared__ PickWords part[4];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
-        m.key = min(m.key, __shfl_xor(m.key, off));
-        m.first = min(m.first, __shfl_xor(m.first, off));
-        m.first_nan = min(m.first_nan, __shfl_xor(m.first_nan, off));
+        PickWords o;
+        o.key = __shfl_xor(m.key, off); o.first = __shfl_xor(m.first, off); o.first_nan = __shfl_xor(m.first_nan, off);
+        pick_fold(m, o);
     }
     if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0u) {
 #pragma unroll
-        for (int k = 1; k < 4; ++k) {
-            m.key = min(m.key, part[k].key); m.first = min(m.first, part[k].first); m.first_nan = min(m.first_nan, part[k].first_nan);
-        }
+        for (int k = 1; k < 4; ++k) pick_fold(m, part[k]);
     }
     return m;
 }
-__device__ __forceinline__ PickWords pick_no_hit() { PickWords m; m.key = ~0ull; m.first = PICK_NONE; m.first_nan = PICK_NONE; return m; }
+// A workgroup's minima offered to the words in memory: nothing without a hit, else at most one agent-scope atomic per word.
+__device__ __forceinline__ void pick_offer(const PickWords& m, PickWords* w) {
+    if (m.first == PICK_NONE) return;
+    __hip_atomic_fetch_min(&w->first, m.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m.first_nan != PICK_NONE) __hip_atomic_fetch_min(&w->first_nan, m.first_nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m.key != ~0ull) __hip_atomic_fetch_min(&w->key, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The tail of a box selection's kernel (256 lanes, lane i decides element i; the lanes behind n_elements pass false): a wave's ballot is
+// two words of the bitmap behind the header, its popcount is added to n_selected (zero when the kernel starts), lane 0 writes n_elements.
+__device__ __forceinline__ void box_emit(unsigned char* result, uint32_t i, uint32_t n_elements, uint32_t nwords, bool sel) {
+    const unsigned long long b = __ballot(sel);
+    uint32_t* head = reinterpret_cast<uint32_t*>(result);
+    if ((threadIdx.x & 63u) == 0u) {                                                     // (i is a multiple of 64 here)
+        uint32_t* words = head + BOX_HEADER / 4;
+        const uint32_t wd = i >> 5;
+        if (wd < nwords) words[wd] = (uint32_t)b;
+        if (wd + 1u < nwords) words[wd + 1u] = (uint32_t)(b >> 32);
+        const uint32_t cnt = (uint32_t)__popcll(b);
+        if (cnt) __hip_atomic_fetch_add(&head[1], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (i == 0u) head[0] = n_elements;
+}
 
 // camera, projection constants and cursor of a call (checked arguments)
-static inline void pick_fill_args(PickArgs& a, const b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, float mx, float my, bool cull) {
-    for (int k = 0; k < 3; ++k) { a.w.pos[k] = cam->position[k]; a.w.bx[k] = cam->basis_x[k]; a.w.by[k] = cam->basis_y[k]; a.w.bz[k] = cam->basis_z[k]; }
-    a.w.vs = ((float)(c->width < c->height ? c->width : c->height) / 2.0f) * 0.75f;     // math.rs:642-643
-    a.w.half_w = (float)c->width / 2.0f; a.w.half_h = (float)c->height / 2.0f;
-    if (ortho) { a.w.has_ortho = 1u; a.w.zoom = ortho->zoom; a.w.center_x = ortho->center_x; a.w.center_y = ortho->center_y; }
+static inline void query_fill(QueryArgs& a, const b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, float mx, float my, bool cull) {
+    view_fill(a.v, *cam, c->width, c->height, ortho);
     a.mx = mx; a.my = my; a.cull = cull ? 1u : 0u;
 }
 
@@ -163,6 +165,38 @@ static inline int pick_host_ensure(b32_ctx* c, size_t bytes) {
     HIPCHK(c, hipHostMalloc(&c->pick_host, cap, hipHostMallocDefault));
     c->pick_cap_host = cap;
     return B32_OK;
+}
+// A blocking form (checked arguments): the landing buffer, the async form into it (enqueue(out, &ticket)), the wait.  *landed: the
+// result's `bytes`, valid until the next blocking form.
+template <class Enqueue>
+static inline int pick_blocking(b32_ctx* c, size_t bytes, const unsigned char** landed, Enqueue enqueue) {
+    int rc;
+    if ((rc = pick_host_ensure(c, bytes))) return rc;
+    uint64_t t = 0;
+    if ((rc = enqueue(c->pick_host, &t))) return rc;
+    if ((rc = b32_ticket_wait(c, t))) return rc;
+    *landed = static_cast<const unsigned char*>(c->pick_host);
+    return B32_OK;
+}
+
+// A box selection's async form around its kernel: the result buffer into *result with the header zeroed on the stream, the caller's
+// launch() (which reads *result), the delivery of header and words.
+static inline size_t box_bytes(size_t nwords) { return BOX_HEADER + nwords * 4u; }
+template <class Launch>
+static inline int box_run(b32_ctx* c, uint32_t nwords, unsigned char** result, void* out, uint64_t* ticket, Launch launch) {
+    unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
+    const size_t bytes = box_bytes(nwords);
+    int rc;
+    if ((rc = pick_result_open(c, bytes, t, tev, k, result))) return rc;
+    HIPCHK(c, hipMemsetAsync(*result, 0, BOX_HEADER, c->stream));
+    launch();
+    HIPCHK(c, hipGetLastError());
+    return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
+}
+// ... and its blocking form's way out of the landing buffer (words: nullable)
+static inline void box_landed(const unsigned char* h, size_t nwords, uint32_t* words, uint32_t* n_selected) {
+    std::memcpy(n_selected, h + 4, 4);
+    if (words && nwords) std::memcpy(words, h + BOX_HEADER, nwords * 4u);
 }
 
 }  // namespace b32

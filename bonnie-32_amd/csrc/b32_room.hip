@@ -40,17 +40,15 @@ struct b32_room {
 
 namespace b32 {
 
-constexpr size_t ROOM_BOX_HEADER = 16;          // {uint32 n_elements; uint32 n_selected; 8 bytes of padding} in front of the words
-
 struct RoomWords { PickWords vertex, edge, face; };
 struct RoomHoverArgs {
-    RoomView v; B32RoomGrid grid; B32RoomHoverParams prm;
+    ViewBlock v; B32RoomGrid grid; B32RoomHoverParams prm;      // (v: perspective only, has_ortho == 0)
     const B32SectorFace* faces; uint32_t n;
     RoomWords* words;
     unsigned char* result;                      // one B32RoomHover
 };
 struct RoomBoxArgs {
-    RoomView v; B32RoomGrid grid;
+    ViewBlock v; B32RoomGrid grid;
     const B32SectorFace* faces; const float* points;
     uint32_t n, n_points, nwords;
     float x0, y0, x1, y1;
@@ -67,13 +65,6 @@ static_assert(sizeof(B32SectorFace) == 24 && sizeof(B32RoomGrid) == 16 && sizeof
 static_assert(sizeof(B32FaceMaterial) == 136 && offsetof(B32FaceMaterial, uv) == 16 && offsetof(B32FaceMaterial, uv_2) == 48 &&
               offsetof(B32FaceMaterial, colors) == 80 && offsetof(B32FaceMaterial, colors_2) == 96 && offsetof(B32FaceMaterial, heights_2) == 112 &&
               offsetof(B32FaceMaterial, normal_mode) == 128 && offsetof(B32FaceMaterial, flags) == 133 && sizeof(B32Face) == 20, "room mesh records");
-
-__device__ __forceinline__ void room_offer(const PickWords& m, PickWords* w) {
-    if (m.first == PICK_NONE) return;
-    __hip_atomic_fetch_min(&w->first, m.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (m.first_nan != PICK_NONE) __hip_atomic_fetch_min(&w->first_nan, m.first_nan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (m.key != ~0ull) __hip_atomic_fetch_min(&w->key, m.key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __global__ __launch_bounds__(256) void k_room_hover(RoomHoverArgs a) {
     const uint32_t e0 = blockIdx.x * PICK_CHUNK;
@@ -98,18 +89,10 @@ __global__ __launch_bounds__(256) void k_room_hover(RoomHoverArgs a) {
     __syncthreads();
     mf = pick_reduce(mf);
     if (threadIdx.x == 0u) {
-        room_offer(mv, &a.words->vertex);
-        room_offer(me, &a.words->edge);
-        room_offer(mf, &a.words->face);
+        pick_offer(mv, &a.words->vertex);
+        pick_offer(me, &a.words->edge);
+        pick_offer(mf, &a.words->face);
     }
-}
-
-// the winner of a set of minima: false = none; nan = the first candidate's depth was a NaN (it stuck)
-__device__ __forceinline__ bool room_winner(const PickWords& w, uint32_t& id, bool& nan) {
-    if (w.first == PICK_NONE) return false;
-    nan = w.first == w.first_nan;
-    id = nan ? w.first : (uint32_t)w.key;
-    return true;
 }
 
 __global__ __launch_bounds__(64) void k_room_hover_resolve(RoomHoverArgs a) {
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(64) void k_room_hover_resolve(RoomHoverArgs a) {
     r.edge_rec = PICK_NONE; r.edge_idx = PICK_NONE; r.edge_dist = 0.0f; r.edge_depth = 0.0f;
     r.face_rec = PICK_NONE; r.face_depth = 0.0f; r._pad[0] = 0u; r._pad[1] = 0u;
     uint32_t id; bool nan;
-    if (room_winner(w.vertex, id, nan) && (id >> 2) < a.n) {
+    if (pick_winner(w.vertex, id, nan) && (id >> 2) < a.n) {
         RoomQuad q;
         room_project(a.v, a.grid, a.faces[id >> 2], q);
         r.vertex_rec = id >> 2; r.vertex_corner = id & 3u;
@@ -131,7 +114,7 @@ __global__ __launch_bounds__(64) void k_room_hover_resolve(RoomHoverArgs a) {
             if ((uint32_t)k == (id & 3u)) (void)room_vertex(q, k, a.prm.mx, a.prm.my, a.prm.vertex_threshold, r.vertex_dist, r.vertex_depth);
         if (nan) r.vertex_depth = __uint_as_float(PICK_QNAN);
     }
-    if (room_winner(w.edge, id, nan) && (id >> 2) < a.n) {
+    if (pick_winner(w.edge, id, nan) && (id >> 2) < a.n) {
         RoomQuad q;
         room_project(a.v, a.grid, a.faces[id >> 2], q);
         r.edge_rec = id >> 2; r.edge_idx = id & 3u;
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(64) void k_room_hover_resolve(RoomHoverArgs a) {
             if ((uint32_t)k == (id & 3u)) (void)room_edge(q, k, a.prm.mx, a.prm.my, a.prm.edge_threshold, r.edge_dist, r.edge_depth);
         if (nan) r.edge_depth = __uint_as_float(PICK_QNAN);
     }
-    if (room_winner(w.face, id, nan) && id < a.n) {
+    if (pick_winner(w.face, id, nan) && id < a.n) {
         RoomQuad q;
         room_project(a.v, a.grid, a.faces[id], q);
         r.face_rec = id;
@@ -161,17 +144,7 @@ __global__ __launch_bounds__(256) void k_room_box(RoomBoxArgs a) {
         else { const float* s = a.points + (size_t)(i - a.n) * 3; p[0] = s[0]; p[1] = s[1]; p[2] = s[2]; }
         sel = room_point_in_rect(a.v, p, a.x0, a.y0, a.x1, a.y1);
     }
-    const unsigned long long b = __ballot(sel);
-    uint32_t* head = reinterpret_cast<uint32_t*>(a.result);
-    if ((threadIdx.x & 63u) == 0u) {                                                     // (i is a multiple of 64 here)
-        uint32_t* words = head + ROOM_BOX_HEADER / 4;
-        const uint32_t wd = i >> 5;
-        if (wd < a.nwords) words[wd] = (uint32_t)b;
-        if (wd + 1u < a.nwords) words[wd + 1u] = (uint32_t)(b >> 32);
-        const uint32_t cnt = (uint32_t)__popcll(b);
-        if (cnt) __hip_atomic_fetch_add(&head[1], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (i == 0u) head[0] = total;
+    box_emit(a.result, i, total, a.nwords, sel);
 }
 
 // Room::to_render_data_with_textures: lane t is vertex slot t % 12 of record t / 12 (12 * n <= 12 * 2^24).  The stores are guarded by the
@@ -201,13 +174,6 @@ __global__ __launch_bounds__(256) void k_room_mesh(RoomMeshArgs a) {
 
 // ------------------------------------------------------------------ host
 namespace {
-
-void room_view(RoomView& v, const b32_ctx* c, const B32Camera* cam) {
-    v = RoomView{};
-    for (int k = 0; k < 3; ++k) { v.pos[k] = cam->position[k]; v.bx[k] = cam->basis_x[k]; v.by[k] = cam->basis_y[k]; v.bz[k] = cam->basis_z[k]; }
-    v.vs = ((float)(c->width < c->height ? c->width : c->height) / 2.0f) * 0.75f;       // math.rs:642-643
-    v.half_w = (float)c->width / 2.0f; v.half_h = (float)c->height / 2.0f;
-}
 
 bool room_kinds_ok(const B32SectorFace* faces, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) if (faces[i].kind > 7u) return false;
@@ -388,14 +354,11 @@ int b32_room_hover_async(b32_ctx* c, const B32Camera* cam, b32_room* room, const
     (void)hipSetDevice(c->device);
     int rc;
     RoomHoverArgs a{};
-    room_view(a.v, c, cam);
+    view_fill(a.v, *cam, c->width, c->height, nullptr);
     a.grid = room->grid; a.prm = *prm; a.faces = room->faces; a.n = room->n;
     // the words: all ones whenever no room hover is running (allocated so; k_room_hover_resolve leaves them so)
-    if (!c->room_words) {
-        HIPCHK(c, hipMalloc(&c->room_words, sizeof(RoomWords)));
-        HIPCHK(c, hipMemsetAsync(c->room_words, 0xFF, sizeof(RoomWords), c->stream));
-    }
-    a.words = static_cast<RoomWords*>(c->room_words);
+    if ((rc = armed_ensure(c, c->room_words, sizeof(RoomWords), 0xFF))) return rc;
+    a.words = static_cast<RoomWords*>(c->room_words.p);
     unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
     const size_t bytes = sizeof(B32RoomHover);
     if ((rc = pick_result_open(c, bytes, t, tev, k, &a.result))) return rc;
@@ -410,12 +373,11 @@ int b32_room_hover(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32Ro
     { const int rc = room_common_check(c, cam, room); if (rc) return rc; }
     if (!prm || !out) return B32_E_ARG;
     (void)hipSetDevice(c->device);
-    int rc;
-    if ((rc = pick_host_ensure(c, sizeof(B32RoomHover)))) return rc;
-    uint64_t t = 0;
-    if ((rc = b32_room_hover_async(c, cam, room, prm, c->pick_host, &t))) return rc;
-    if ((rc = b32_ticket_wait(c, t))) return rc;
-    std::memcpy(out, c->pick_host, sizeof(B32RoomHover));
+    const unsigned char* h = nullptr;
+    const int rc = pick_blocking(c, sizeof(B32RoomHover), &h, [&](void* landing, uint64_t* t) {
+        return b32_room_hover_async(c, cam, room, prm, landing, t); });
+    if (rc) return rc;
+    std::memcpy(out, h, sizeof(B32RoomHover));
     return B32_OK;
 }
 
@@ -450,29 +412,19 @@ int b32_room_box_select_async(b32_ctx* c, const B32Camera* cam, b32_room* room, 
     (void)hipSetDevice(c->device);
     int rc;
     RoomBoxArgs a{};
-    room_view(a.v, c, cam);
+    view_fill(a.v, *cam, c->width, c->height, nullptr);
     a.grid = room->grid; a.faces = room->faces; a.n = room->n; a.n_points = n_points;
     a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1;
     const uint32_t total = a.n + n_points;
     a.nwords = (uint32_t)(((unsigned long long)total + 31u) / 32u);
     if (n_points) {                             // the points: copied before return, ordered on the stream behind the last call that read them
-        const size_t need = (size_t)n_points * 3u;
-        if (need > c->room_cap_points) {
-            if (c->room_points) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->room_points)); c->room_points = nullptr; c->room_cap_points = 0; }
-            const size_t cap = need + need / 4 + 64;
-            HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->room_points), cap * sizeof(float)));
-            c->room_cap_points = cap;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->room_points, points_xyz, need * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        a.points = c->room_points;
+        const size_t bytes = (size_t)n_points * 3u * sizeof(float);
+        if ((rc = armed_ensure(c, c->room_points, bytes, -1))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->room_points.p, points_xyz, bytes, hipMemcpyHostToDevice, c->stream));
+        a.points = static_cast<const float*>(c->room_points.p);
     }
-    unsigned long long t = 0; hipEvent_t* tev = nullptr; uint32_t k = 0;
-    const size_t bytes = ROOM_BOX_HEADER + (size_t)a.nwords * 4u;
-    if ((rc = pick_result_open(c, bytes, t, tev, k, &a.result))) return rc;
-    HIPCHK(c, hipMemsetAsync(a.result, 0, ROOM_BOX_HEADER, c->stream));
-    if (total) hipLaunchKernelGGL(k_room_box, dim3((uint32_t)(((unsigned long long)total + 255u) / 256u)), dim3(256), 0, c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
+    return box_run(c, a.nwords, &a.result, out, ticket, [&] {
+        if (total) hipLaunchKernelGGL(k_room_box, dim3((uint32_t)(((unsigned long long)total + 255u) / 256u)), dim3(256), 0, c->stream, a); });
 }
 
 int b32_room_box_select(b32_ctx* c, const B32Camera* cam, b32_room* room, float x0, float y0, float x1, float y1, const float* points_xyz,
@@ -481,15 +433,12 @@ int b32_room_box_select(b32_ctx* c, const B32Camera* cam, b32_room* room, float 
     if ((n_points && !points_xyz) || !n_selected) return B32_E_ARG;
     if ((unsigned long long)room->n + n_points >= (1ull << 32)) return B32_E_UNSUPPORTED;
     (void)hipSetDevice(c->device);
-    const size_t nwords = (size_t)(((unsigned long long)room->n + n_points + 31u) / 32u), bytes = ROOM_BOX_HEADER + nwords * 4u;
-    int rc;
-    if ((rc = pick_host_ensure(c, bytes))) return rc;
-    uint64_t t = 0;
-    if ((rc = b32_room_box_select_async(c, cam, room, x0, y0, x1, y1, points_xyz, n_points, c->pick_host, &t))) return rc;
-    if ((rc = b32_ticket_wait(c, t))) return rc;
-    const unsigned char* h = static_cast<const unsigned char*>(c->pick_host);
-    std::memcpy(n_selected, h + 4, 4);
-    if (words && nwords) std::memcpy(words, h + ROOM_BOX_HEADER, nwords * 4u);
+    const size_t nwords = (size_t)(((unsigned long long)room->n + n_points + 31u) / 32u);
+    const unsigned char* h = nullptr;
+    const int rc = pick_blocking(c, box_bytes(nwords), &h, [&](void* landing, uint64_t* t) {
+        return b32_room_box_select_async(c, cam, room, x0, y0, x1, y1, points_xyz, n_points, landing, t); });
+    if (rc) return rc;
+    box_landed(h, nwords, words, n_selected);
     return B32_OK;
 }
 

@@ -5,24 +5,16 @@
 // Every expression is a separately rounded f32 operation in the reference's order; the text also compiles for the host (B32_HD,
 // b32_world_point.h), where tests/test_room_hover.py runs it against a literal restatement, built with and without -ffp-contract=off.
 #pragma once
-#include "b32_world_point.h"
-#if !defined(__HIPCC__)
-#include <math.h>
-#include <stdint.h>
-#include "../../include/b32raster.h"
-#define B32_ROOM_UNROLL
-#else
+#if defined(__HIPCC__)
+#include "b32_device.h"
 #define B32_ROOM_UNROLL _Pragma("unroll")
+#else
+#include <math.h>
+#include "b32_world_point.h"
+#define B32_ROOM_UNROLL
 #endif
 
 namespace b32 {
-
-// What the projection reads (world_point's camera block; perspective only, so the ortho members stay zero)
-struct RoomView {
-    float pos[3], bx[3], by[3], bz[3];
-    float vs, half_w, half_h;
-    float zoom, center_x, center_y;
-};
 
 // Corner k's (x, z) selectors per kind, bit k of nibble `kind`: 0 = base, 1 = base + S (viewport_3d.rs:6603-6657, :7099-7170, :7183-7279)
 //   kind       0 Floor  1 Ceiling  2 North  3 East  4 South  5 West  6 NwSe  7 NeSw
@@ -54,7 +46,7 @@ B32_HD void room_corner(const B32RoomGrid& g, const B32SectorFace& f, float base
 // The record's four corners through world_to_screen_with_depth (math.rs:621-652), once: the three loops project the same corner with the
 // same function, so one projection serves them all.
 struct RoomQuad { bool some[4]; float sx[4], sy[4], d[4]; };
-B32_HD void room_project(const RoomView& v, const B32RoomGrid& g, const B32SectorFace& f, RoomQuad& q) {
+B32_HD void room_project(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, RoomQuad& q) {
     float base_x, base_z;
     room_base(g, f, base_x, base_z);
     B32_ROOM_UNROLL
@@ -141,7 +133,7 @@ B32_HD bool room_face(const RoomQuad& q, float mx, float my, float& depth) {
 
 // What one record offers a cursor: bit k of vmask / emask = corner k / edge k is a candidate, with its distance and depth
 struct RoomCandidates { uint32_t vmask, emask; bool face; float vdist[4], vdepth[4], edist[4], edepth[4], fdepth; };
-B32_HD void room_candidates(const RoomView& v, const B32RoomGrid& g, const B32SectorFace& f, const B32RoomHoverParams& p, RoomCandidates& c) {
+B32_HD void room_candidates(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, const B32RoomHoverParams& p, RoomCandidates& c) {
     RoomQuad q;
     room_project(v, g, f, q);
     c.vmask = 0u; c.emask = 0u;
@@ -175,7 +167,7 @@ B32_HD void room_centre(const B32RoomGrid& g, const B32SectorFace& f, float* c) 
     c[0] = (x0 + x1) / 2.0f; c[2] = (z0 + z1) / 2.0f;
 }
 // world_to_screen (math.rs:503-534) of a point against the rectangle, inclusive; any NaN is false
-B32_HD bool room_point_in_rect(const RoomView& v, const float* p, float x0, float y0, float x1, float y1) {
+B32_HD bool room_point_in_rect(const ViewBlock& v, const float* p, float x0, float y0, float x1, float y1) {
     float sx, sy, z;
     if (!world_point(v, p, false, sx, sy, z)) return false;
     return sx >= x0 && sx <= x1 && sy >= y0 && sy <= y1;

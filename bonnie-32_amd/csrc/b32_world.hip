@@ -10,7 +10,7 @@
 // f2i32_sat = `as i32`).  Record i is written from item i, so the array order is the reference's call order; an item that draws nothing
 // becomes a circle of radius -1, which the tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of
 // b32_prims.hip reads them where this kernel wrote them.
-#include "b32_world_point.h"
+#include "b32_device.h"
 #include <cmath>
 
 namespace b32 {
@@ -26,12 +26,12 @@ __device__ __forceinline__ void world_project(const WorldArgs& a, const B32World
     const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
     const bool depth = it.kind >= B32_LINE_3D && it.kind <= B32_LINE_3D_ALPHA;
     float p0[3] = { it.p0[0], it.p0[1], it.p0[2] }, p1[3] = { it.p1[0], it.p1[1], it.p1[2] };
-    bool ortho = a.has_ortho != 0u, some = true;
+    bool ortho = a.v.has_ortho != 0u, some = true;
     if (!circle && (it.flags & B32_WORLD_CLIP_NEAR)) {          // draw_3d_line_clipped, draw.rs:19-42 (the projection after it takes no ortho)
         ortho = false;
-        const float rel0[3] = { p0[0] - a.pos[0], p0[1] - a.pos[1], p0[2] - a.pos[2] };
-        const float rel1[3] = { p1[0] - a.pos[0], p1[1] - a.pos[1], p1[2] - a.pos[2] };
-        const float z0 = world_dot(rel0, a.bz), z1 = world_dot(rel1, a.bz);
+        const float rel0[3] = { p0[0] - a.v.pos[0], p0[1] - a.v.pos[1], p0[2] - a.v.pos[2] };
+        const float rel1[3] = { p1[0] - a.v.pos[0], p1[1] - a.v.pos[1], p1[2] - a.v.pos[2] };
+        const float z0 = world_dot(rel0, a.v.bz), z1 = world_dot(rel1, a.v.bz);
         if (z0 <= WORLD_NEAR && z1 <= WORLD_NEAR) {
             some = false;
         } else if (z0 <= WORLD_NEAR || z1 <= WORLD_NEAR) {
@@ -44,8 +44,8 @@ __device__ __forceinline__ void world_project(const WorldArgs& a, const B32World
         }
     }
     float sx0 = 0.0f, sy0 = 0.0f, cz0 = 0.0f, sx1 = 0.0f, sy1 = 0.0f, cz1 = 0.0f;
-    if (some) some = world_point(a, p0, ortho, sx0, sy0, cz0);
-    if (some && !circle) some = world_point(a, p1, ortho, sx1, sy1, cz1);
+    if (some) some = world_point(a.v, p0, ortho, sx0, sy0, cz0);
+    if (some && !circle) some = world_point(a.v, p1, ortho, sx1, sy1, cz1);
 
     B32Prim o{};
     o.kind = B32_PRIM_CIRCLE; o.size = -1;                      // draws nothing

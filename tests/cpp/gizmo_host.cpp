@@ -7,32 +7,22 @@
 //        n_span_rows x 4 i32 (record index, y, x_start, x_end) -- every row of every triangle record that is not skipped, rows
 //        y0.max(0) ..= y2.min(h - 1), x_start = (ax as i32).max(0), x_end = (bx as i32).min(w - 1) (x_start > x_end: an empty row)
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "b32_gizmo_body.h"
-
-struct HostArgs {
-    float pos[3], bx[3], by[3], bz[3];
-    float vs, half_w, half_h;
-    float zoom, center_x, center_y; uint32_t has_ortho;
-};
 
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
     FILE* in = std::fopen(argv[1], "rb");
     if (!in) return 3;
-    uint32_t head[4]; float cam[12], ortho[3];
-    if (std::fread(head, 4, 4, in) != 4 || std::fread(cam, 4, 12, in) != 12 || std::fread(ortho, 4, 3, in) != 3) return 3;
+    uint32_t head[4]; B32Camera cam; B32Ortho ortho;
+    if (std::fread(head, 4, 4, in) != 4 || std::fread(&cam, 4, 12, in) != 12 || std::fread(&ortho, 4, 3, in) != 3) return 3;
     const uint32_t w = head[0], h = head[1], n = head[3];
     std::vector<B32GizmoItem> items(n);
     if (n && std::fread(items.data(), sizeof(B32GizmoItem), n, in) != n) return 3;
     std::fclose(in);
-    HostArgs a{};
-    std::memcpy(a.pos, cam, 12); std::memcpy(a.bx, cam + 3, 12); std::memcpy(a.by, cam + 6, 12); std::memcpy(a.bz, cam + 9, 12);
-    a.vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f;
-    a.half_w = (float)w / 2.0f; a.half_h = (float)h / 2.0f;
-    a.has_ortho = head[2]; a.zoom = ortho[0]; a.center_x = ortho[1]; a.center_y = ortho[2];
+    b32::ViewBlock a;
+    b32::view_fill(a, cam, w, h, head[2] ? &ortho : nullptr);
 
     std::vector<B32Prim> recs;
     std::vector<uint32_t> which(n);

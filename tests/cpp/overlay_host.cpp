@@ -7,17 +7,10 @@
 //   out: 9 u32 (first record of brackets, edges, dots, hover vertex, hover edge, hover face, selected, preview; total); total B32Prim
 #include <algorithm>
 #include <cstdio>
-#include <cstring>
 #include <utility>
 #include <vector>
 
 #include "b32_overlay_body.h"
-
-struct HostArgs {
-    float pos[3], bx[3], by[3], bz[3];
-    float vs, half_w, half_h;
-    float zoom, center_x, center_y; uint32_t has_ortho;
-};
 
 template <class T>
 static bool get(FILE* f, std::vector<T>& v, size_t n) { v.resize(n); return !n || std::fread(v.data(), sizeof(T), n, f) == n; }
@@ -27,17 +20,14 @@ int main(int argc, char** argv) {
     if (argc != 3) return 2;
     FILE* in = std::fopen(argv[1], "rb");
     if (!in) return 3;
-    uint32_t head[7]; B32MeshOverlay o; float cam[12], ortho[3];
-    if (std::fread(head, 4, 7, in) != 7 || std::fread(&o, sizeof o, 1, in) != 1 || std::fread(cam, 4, 12, in) != 12 || std::fread(ortho, 4, 3, in) != 3) return 3;
+    uint32_t head[7]; B32MeshOverlay o; B32Camera cam; B32Ortho ortho;
+    if (std::fread(head, 4, 7, in) != 7 || std::fread(&o, sizeof o, 1, in) != 1 || std::fread(&cam, 4, 12, in) != 12 || std::fread(&ortho, 4, 3, in) != 3) return 3;
     const uint32_t w = head[0], h = head[1], nv = head[3], np = head[4], nh = head[5], nsel = head[6];
     std::vector<float> pos; std::vector<uint32_t> ps, pv, sel;
     if (!get(in, pos, (size_t)nv * 3) || !get(in, ps, (size_t)np + 1) || !get(in, pv, nh) || !get(in, sel, nsel)) return 3;
     std::fclose(in);
-    HostArgs a{};
-    std::memcpy(a.pos, cam, 12); std::memcpy(a.bx, cam + 3, 12); std::memcpy(a.by, cam + 6, 12); std::memcpy(a.bz, cam + 9, 12);
-    a.vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f;
-    a.half_w = (float)w / 2.0f; a.half_h = (float)h / 2.0f;
-    a.has_ortho = head[2]; a.zoom = ortho[0]; a.center_x = ortho[1]; a.center_y = ortho[2];
+    ViewBlock a;
+    view_fill(a, cam, w, h, head[2] ? &ortho : nullptr);
     if (overlay_check(true, &o, sel.data())) return 5;
 
     // the half-edges as b32_topology_create derives them

@@ -1,6 +1,6 @@
-// room_host.cpp -- csrc/b32_room_body.h (the device code of b32_room_hover's and b32_room_box_select's arithmetic) compiled for the host,
-// for tests/test_room_hover.py.  No device, no library.  The records are driven as k_room_hover drives them: record by record into three
-// sets of minima per workgroup of 1024 records, the workgroups' minima folded with min() as the kernel's atomics fold them, and the
+// room_host.cpp -- csrc/b32_room_body.h and csrc/b32_pick_words.h (the device code of b32_room_hover's and b32_room_box_select's arithmetic
+// and of the three minima) compiled for the host, for tests/test_room_hover.py.  No device, no library.  The records are driven as k_room_hover drives them: record by record into three
+// sets of minima per workgroup of 1024 records, the workgroups' minima folded (pick_fold) as the kernel's atomics fold them, and the
 // winners' distance and depth recomputed from their records as k_room_hover_resolve does.
 //   usage: room_host <in> <out>
 //   in : u32 width, height, n, n_cursors, n_points, 0; 12 f32 camera (position, basis_x, basis_y, basis_z); B32RoomGrid;
@@ -10,36 +10,15 @@
 #include <cstring>
 #include <vector>
 
+#include "b32_pick_words.h"
 #include "b32_room_body.h"
 
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu, QNAN = 0x7FC00000u, CHUNK = 1024u;
+using b32::PickWords; using b32::pick_no_hit; using b32::pick_take; using b32::pick_fold; using b32::pick_winner;
+constexpr uint32_t NONE = b32::PICK_NONE;
 
-// the three minima of "none yet, or strictly smaller, in loop order" (pick_take of b32_pick_body.h, restated for the host)
-struct Min { unsigned long long key = ~0ull; uint32_t first = NONE, first_nan = NONE; };
-uint32_t orderable(float d) {
-    uint32_t u; std::memcpy(&u, &d, 4);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-void take(Min& m, float depth, uint32_t id) {
-    if (id < m.first) m.first = id;
-    if (depth != depth) { if (id < m.first_nan) m.first_nan = id; }
-    else { const unsigned long long k = ((unsigned long long)orderable(depth) << 32) | id; if (k < m.key) m.key = k; }
-}
-void fold(Min& into, const Min& m) {
-    if (m.key < into.key) into.key = m.key;
-    if (m.first < into.first) into.first = m.first;
-    if (m.first_nan < into.first_nan) into.first_nan = m.first_nan;
-}
-bool winner(const Min& m, uint32_t& id, bool& nan) {
-    if (m.first == NONE) return false;
-    nan = m.first == m.first_nan;
-    id = nan ? m.first : (uint32_t)m.key;
-    return true;
-}
-float qnan() { float f; std::memcpy(&f, &QNAN, 4); return f; }
+float qnan() { float f; std::memcpy(&f, &b32::PICK_QNAN, 4); return f; }
 
 }  // namespace
 
@@ -47,9 +26,9 @@ int main(int argc, char** argv) {
     if (argc != 3) return 2;
     FILE* in = std::fopen(argv[1], "rb");
     if (!in) return 3;
-    uint32_t head[6]; float cam[12], thr[2], rect[4];
+    uint32_t head[6]; B32Camera cam; float thr[2], rect[4];
     B32RoomGrid grid;
-    if (std::fread(head, 4, 6, in) != 6 || std::fread(cam, 4, 12, in) != 12 || std::fread(&grid, sizeof grid, 1, in) != 1 ||
+    if (std::fread(head, 4, 6, in) != 6 || std::fread(&cam, 4, 12, in) != 12 || std::fread(&grid, sizeof grid, 1, in) != 1 ||
         std::fread(thr, 4, 2, in) != 2 || std::fread(rect, 4, 4, in) != 4) return 3;
     const uint32_t w = head[0], h = head[1], n = head[2], nc = head[3], np = head[4];
     std::vector<B32SectorFace> faces(n);
@@ -58,45 +37,43 @@ int main(int argc, char** argv) {
     if (nc && std::fread(cursors.data(), 8, nc, in) != nc) return 3;
     if (np && std::fread(points.data(), 12, np, in) != np) return 3;
     std::fclose(in);
-    b32::RoomView v{};
-    std::memcpy(v.pos, cam, 12); std::memcpy(v.bx, cam + 3, 12); std::memcpy(v.by, cam + 6, 12); std::memcpy(v.bz, cam + 9, 12);
-    v.vs = ((float)(w < h ? w : h) / 2.0f) * 0.75f;
-    v.half_w = (float)w / 2.0f; v.half_h = (float)h / 2.0f;
+    b32::ViewBlock v;
+    b32::view_fill(v, cam, w, h, nullptr);
 
     FILE* out = std::fopen(argv[2], "wb");
     if (!out) return 4;
     for (uint32_t ci = 0; ci < nc; ++ci) {
         const B32RoomHoverParams prm{ cursors[2 * ci], cursors[2 * ci + 1], thr[0], thr[1] };
-        Min gv, ge, gf;
-        for (uint32_t e0 = 0; e0 < n; e0 += CHUNK) {
-            Min mv, me, mf;
-            for (uint32_t i = e0; i < n && i < e0 + CHUNK; ++i) {
+        PickWords gv = pick_no_hit(), ge = pick_no_hit(), gf = pick_no_hit();
+        for (uint32_t e0 = 0; e0 < n; e0 += b32::PICK_CHUNK) {
+            PickWords mv = pick_no_hit(), me = pick_no_hit(), mf = pick_no_hit();
+            for (uint32_t i = e0; i < n && i < e0 + b32::PICK_CHUNK; ++i) {
                 b32::RoomCandidates c;
                 b32::room_candidates(v, grid, faces[i], prm, c);
                 for (uint32_t k = 0; k < 4u; ++k) {
-                    if ((c.vmask >> k) & 1u) take(mv, c.vdepth[k], i * 4u + k);
-                    if ((c.emask >> k) & 1u) take(me, c.edepth[k], i * 4u + k);
+                    if ((c.vmask >> k) & 1u) pick_take(mv, c.vdepth[k], i * 4u + k);
+                    if ((c.emask >> k) & 1u) pick_take(me, c.edepth[k], i * 4u + k);
                 }
-                if (c.face) take(mf, c.fdepth, i);
+                if (c.face) pick_take(mf, c.fdepth, i);
             }
-            fold(gv, mv); fold(ge, me); fold(gf, mf);
+            pick_fold(gv, mv); pick_fold(ge, me); pick_fold(gf, mf);
         }
         B32RoomHover r{ NONE, NONE, 0.0f, 0.0f, NONE, NONE, 0.0f, 0.0f, NONE, 0.0f, { 0u, 0u } };
         uint32_t id; bool nan;
         b32::RoomQuad q;
-        if (winner(gv, id, nan)) {
+        if (pick_winner(gv, id, nan)) {
             b32::room_project(v, grid, faces[id >> 2], q);
             r.vertex_rec = id >> 2; r.vertex_corner = id & 3u;
             (void)b32::room_vertex(q, (int)(id & 3u), prm.mx, prm.my, prm.vertex_threshold, r.vertex_dist, r.vertex_depth);
             if (nan) r.vertex_depth = qnan();
         }
-        if (winner(ge, id, nan)) {
+        if (pick_winner(ge, id, nan)) {
             b32::room_project(v, grid, faces[id >> 2], q);
             r.edge_rec = id >> 2; r.edge_idx = id & 3u;
             (void)b32::room_edge(q, (int)(id & 3u), prm.mx, prm.my, prm.edge_threshold, r.edge_dist, r.edge_depth);
             if (nan) r.edge_depth = qnan();
         }
-        if (winner(gf, id, nan)) {
+        if (pick_winner(gf, id, nan)) {
             b32::room_project(v, grid, faces[id], q);
             r.face_rec = id;
             (void)b32::room_face(q, prm.mx, prm.my, r.face_depth);

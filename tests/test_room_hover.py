@@ -841,6 +841,92 @@ def test_gpu_room_box_select(gpu_ctx, name):
     del fb
 
 
+BOX_TAIL_COUNTS = (0, 1, 31, 32, 33, 63, 64, 65, 255, 256, 257)       # around a bitmap word, a wave's two words and a workgroup
+BOX_TAIL_CAM = b32.Camera(position=(-1000.0, 0.0, 0.0))                 # beside stack_room's column: a wall's centre lands at x = 160 + 360000 / (z + 5)
+BOX_TAIL_RECTS = ((0.0, 0.0, 320.0, 240.0), (0.0, 0.0, 240.0, 240.0))   # the full frame; every wall but those at gz = 1 (x = 249.3; gz = 2: 231.2)
+BOX_TAIL_POINTS = np.array([(0.0, 0.0, 4024.0), (0.0, 0.0, 5048.0), (0.0, 0.0, -1.0)], np.float32)    # gz = 1's and gz = 2's centre, one behind the camera
+
+
+def box_tail_mesh(n):
+    """n vertices on a 4-unit lattice, column (5 * i) % 16 and row i // 16, for the identity camera and the unit ortho: vertex i lands at
+    x = 130 + 4 * column, so the rectangle up to x = 148 takes columns 0 to 4 -- vertex 0 and never vertex 1."""
+    v = b32.make_vertices(n)
+    v["pos"] = np.array([(4.0 * ((5 * i) % 16) - 30.0, 4.0 * (i // 16) - 30.0, 2.0) for i in range(n)], np.float32).reshape(n, 3)
+    return v
+
+
+BOX_TAIL_MESH_RECTS = ((0.0, 0.0, 320.0, 240.0), (0.0, 0.0, 148.0, 240.0))
+
+
+def box_tail_room_cases():
+    """(faces, grid, points, rect, (words, n_selected) of the mirror) at every count and both rectangles, and the points alone."""
+    from bonnie32_amd import rasterizer as R
+    cases = []
+    for n, points in [(n, None) for n in BOX_TAIL_COUNTS] + [(0, BOX_TAIL_POINTS)]:
+        faces, grid, _ = stack_room(n)
+        for rect in BOX_TAIL_RECTS:
+            cases.append((faces, grid, points, rect, R.RoomMirror(faces, grid, BOX_TAIL_CAM, 320, 240).box_select(rect, points)))
+    return cases
+
+
+def test_box_tail_cases_select_all_and_a_strict_subset():
+    """What test_gpu_box_select_bitmap_tails compares the device with: under the mirrors the full frame selects every element and the second
+    rectangle a strict subset wherever there are two elements."""
+    from bonnie32_amd.rasterizer import box_select_mesh
+    from tests.test_hover import UNIT_ORTHO
+    for faces, grid, points, rect, (words, cnt) in box_tail_room_cases():
+        n = len(faces) + (0 if points is None else len(points))
+        assert len(words) == (n + 31) // 32
+        if points is not None:
+            assert cnt == (2 if rect == BOX_TAIL_RECTS[0] else 1), (rect, cnt)
+        elif rect == BOX_TAIL_RECTS[0]:
+            assert cnt == n
+        elif n >= 2:
+            assert 0 < cnt < n, (n, cnt)
+    for n in BOX_TAIL_COUNTS:
+        v = box_tail_mesh(n)
+        for k, rect in enumerate(BOX_TAIL_MESH_RECTS):
+            words, cnt = box_select_mesh(v, None, None, IDENTITY_CAM, 320, 240, rect, abi.BOX_VERTICES, UNIT_ORTHO)
+            assert len(words) == (n + 31) // 32 and (cnt == n if k == 0 else (0 < cnt < n or n < 2)), (n, rect, cnt)
+
+
+@pytest.mark.gpu
+def test_gpu_box_select_bitmap_tails(gpu_ctx):
+    """The bitmap tail the two box selections share (box_emit): both at 0, 1, 31, 32, 33, 63, 64, 65, 255, 256 and 257 elements -- where the two
+    guarded word stores and the last partial wave can go wrong --, everything selected and a strict subset, word for word and count for
+    count against the mirrors, blocking and by ticket."""
+    from bonnie32_amd import rasterizer as R
+    from bonnie32_amd.rasterizer import box_select_mesh
+    from tests.test_hover import UNIT_ORTHO
+    fb = R.Framebuffer(320, 240, gpu_ctx)
+    for faces, grid, points, rect, (want_w, want_n) in box_tail_room_cases():
+        n = len(faces) + (0 if points is None else len(points))
+        with R.Room(gpu_ctx, faces, grid) as room:
+            words, cnt = gpu_ctx.room_box_select(room, BOX_TAIL_CAM, rect, points)
+            print("room", n, rect, cnt, want_n)
+            assert cnt == want_n and np.array_equal(words, want_w), (n, rect, cnt, want_n)
+            t, res = gpu_ctx.room_box_select_async(room, BOX_TAIL_CAM, rect, points)
+            gpu_ctx.ticket_wait(t)
+            assert (res.n_elements, res.n_selected) == (n, want_n) and np.array_equal(res.words, want_w), (n, rect)
+            res.close()
+    for n in BOX_TAIL_COUNTS:
+        v = box_tail_mesh(n)
+        rs = R.ResidentScene(fb, v, b32.make_faces(0), []).detach()
+        try:
+            for rect in BOX_TAIL_MESH_RECTS:
+                want_w, want_n = box_select_mesh(v, None, None, IDENTITY_CAM, 320, 240, rect, abi.BOX_VERTICES, UNIT_ORTHO)
+                words, cnt = gpu_ctx.box_select(rs, None, IDENTITY_CAM, rect, abi.BOX_VERTICES, UNIT_ORTHO)
+                print("mesh", n, rect, cnt, want_n)
+                assert cnt == want_n and np.array_equal(words, want_w), (n, rect, cnt, want_n)
+                t, res = gpu_ctx.box_select_async(rs, None, IDENTITY_CAM, rect, abi.BOX_VERTICES, UNIT_ORTHO)
+                gpu_ctx.ticket_wait(t)
+                assert (res.n_elements, res.n_selected) == (n, want_n) and np.array_equal(res.words, want_w), (n, rect)
+                res.close()
+        finally:
+            rs.close()
+    del fb
+
+
 @pytest.mark.gpu
 def test_gpu_room_errors_and_lifetime(gpu_ctx):
     """NULL arguments, kind > 7, more than 2^24 records, an update out of range, a zero-size framebuffer; an empty room; destroy of NULL;
