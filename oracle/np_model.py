@@ -248,14 +248,16 @@ def shade_multi(normal, wpos, lights, ambient):
 
 
 # ---------------------------------------------------------------- render_mesh_15, render.rs:2302-2572
-def render_mesh(pixels, width, height, vertices, faces, textures, camera, settings, zbuffer=None):
+def render_mesh(pixels, width, height, vertices, faces, textures, camera, settings, zbuffer=None, tap=None):
     """render_mesh (render.rs:1971-2264): the 8-bit-colour path; `textures` are rtypes.Texture."""
-    return render_mesh_15(pixels, width, height, vertices, faces, textures, camera, settings, None, zbuffer, fmt8=True)
+    return render_mesh_15(pixels, width, height, vertices, faces, textures, camera, settings, None, zbuffer, fmt8=True, tap=tap)
 
 
-def render_mesh_15(pixels, width, height, vertices, faces, textures, camera, settings, fog=None, zbuffer=None, fmt8=False):
+def render_mesh_15(pixels, width, height, vertices, faces, textures, camera, settings, fog=None, zbuffer=None, fmt8=False, tap=None):
     """Draw into `pixels` (uint8 [H*W*4]) (and `zbuffer` f32 [H*W] when settings.use_zbuffer); returns dict(triangles_drawn,
-    fragments, draw_order, sx, sy, sz, shades, colors)."""
+    fragments, draw_order, sx, sy, sz, shades, colors).
+    tap: None, or a list that receives one record per rasterized surface, in draw order, with what the colour pipeline saw at every
+    pixel it stored (see _tap_record); the frame does not depend on it."""
     img = pixels.reshape(height, width, 4)
     zb = zbuffer.reshape(height, width) if settings.use_zbuffer else None
     pos = vertices["pos"].astype(np.float32)
@@ -358,9 +360,9 @@ def render_mesh_15(pixels, width, height, vertices, faces, textures, camera, set
     if not settings.wireframe_overlay:                                                               # :2550
         for k, si in enumerate(draw):
             if fmt8:
-                fragments += _rasterize8(img, width, height, surfaces[si], settings, zb)
+                fragments += _rasterize8(img, width, height, surfaces[si], settings, zb, tap=tap)
             else:
-                fragments += _rasterize(img, width, height, surfaces[si], settings, zb, skip_z_write=k >= n_opaque)
+                fragments += _rasterize(img, width, height, surfaces[si], settings, zb, skip_z_write=k >= n_opaque, tap=tap)
     # wireframe phases, :2574-2635
     zfull = zbuffer.reshape(height, width) if zbuffer is not None else None
     if settings.backface_cull and settings.backface_wireframe:
@@ -440,7 +442,17 @@ def draw_line(img, width, height, e, rgb, zb, depth_test):
     img[ys, xs, 0], img[ys, xs, 1], img[ys, xs, 2], img[ys, xs, 3] = rgb[0], rgb[1], rgb[2], 255
 
 
-def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False):
+def _tap_record(tap, s, px, py, texel, vert, mod, shade, m, dithered, back):
+    """The per-pixel tap of render_mesh_15 / render_mesh: for every pixel the surface stored, its position, the sampled texel (a Color15, or
+    the four bytes of a Color), the three interpolated vertex-colour bytes `vert`, tex8 * vert / 128 clamped (`mod`), the shade factors
+    (None on an unlit frame), the three values `m` that go into the dither / quantisation step, whether that step dithers, and the
+    framebuffer bytes the store read."""
+    tap.append(dict(face=s["face"], x=px.copy(), y=py.copy(), texel=np.array(texel), vert=np.stack(vert, axis=1), mod=np.stack(mod, axis=1),
+                    shade=None if shade is None else np.stack(shade, axis=1), m=np.stack(m, axis=1), dithered=bool(dithered), back=back.copy(),
+                    blend=s["blend"], alpha=s["alpha"]))
+
+
+def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False, tap=None):
     """rasterize_triangle_15, render.rs:1440-1714, whole bbox at once (one triangle touches a pixel once, so the sequential
     z-buffer semantics hold within the call)."""
     v1, v2, v3 = s["v"]
@@ -529,11 +541,12 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False):
     bx, by, bz, tx_ = bcx[ys, xs], bcy[ys, xs], bcz[ys, xs], texel[ys, xs]
     px, py = xs + min_x, ys + min_y
     chans = [(tx_ >> 10) & 31, (tx_ >> 5) & 31, tx_ & 31]
-    out5 = []
+    out5, t_vert, t_mod, t_shade = [], [], [], []
     for i in range(3):
         tex8 = expand5(chans[i])
         vert = as_u8((bx * f32(s["vc"][0][i]) + by * f32(s["vc"][1][i])).astype(np.float32) + bz * f32(s["vc"][2][i]))   # :1618-1620
         m = np.minimum((tex8 * vert) // K("fill.modulate_div"), K("fill.modulate_max"))               # :1624-1626
+        t_vert.append(vert); t_mod.append(m)
         if st.shading != 0:
             if "_sh" not in s:
                 _prep_shades(s, st)
@@ -543,6 +556,7 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False):
                 sv = ((bx * s["_sh"][0][i] + by * s["_sh"][1][i]).astype(np.float32) + bz * s["_sh"][2][i]).astype(np.float32)
             lo, hi = K("fill.shade_clamp_lo"), K("fill.shade_clamp_hi")
             svc = np.where(sv < lo, lo, np.where(sv > hi, hi, sv)).astype(np.float32)                # clamp propagates NaN
+            t_shade.append(sv)
             m = as_u8(rmin((m.astype(np.float32) * svc).astype(np.float32), f32(255.0)))              # :1643-1645
         out5.append(m)
     vc = s["vc"]
@@ -556,6 +570,8 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False):
     semi = ((tx_ & K("color15.semi_bit")) != 0) | all_black                                                          # :1659-1661
     front = np.stack([expand5(q[0]), expand5(q[1]), expand5(q[2])], axis=1)                           # Color15::r8 etc.
     back = img[py, px, :3].astype(np.int64)
+    if tap is not None:
+        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, out5, needs_dither, back)
     mode, alpha = s["blend"], s["alpha"]
     do_blend = semi & (mode != 0)
     ps1 = np.where(do_blend[:, None], blend555(front, back, mode), front)
@@ -585,7 +601,7 @@ def blend8(front, back, mode):
     return front
 
 
-def _rasterize8(img, width, height, s, st, zb=None):
+def _rasterize8(img, width, height, s, st, zb=None, tap=None):
     """rasterize_triangle (render.rs:1202-1433), whole bbox at once."""
     v1, v2, v3 = s["v"]
     min_x = int(as_usize(rmax(rmin(rmin(v1[0], v2[0]), v3[0]), f32(0.0))))
@@ -663,10 +679,11 @@ def _rasterize8(img, width, height, s, st, zb=None):
         zb[ys + min_y, xs + min_x] = zgrid[ys, xs]                                                   # every passing fragment writes depth
     bx, by, bz, tx_ = bcx[ys, xs], bcy[ys, xs], bcz[ys, xs], texel[ys, xs]
     px, py = xs + min_x, ys + min_y
-    cols = []
+    cols, t_vert, t_mod, t_shade = [], [], [], []
     for i in range(3):
         vert = as_u8((bx * f32(s["vc"][0][i]) + by * f32(s["vc"][1][i])).astype(np.float32) + bz * f32(s["vc"][2][i]))
         m = np.minimum((tx_[:, i] * vert) // 128, 255)                                                # modulate, types.rs:801-808
+        t_vert.append(vert); t_mod.append(m)
         if st.shading != 0:
             if "_sh" not in s:
                 _prep_shades(s, st)
@@ -675,14 +692,18 @@ def _rasterize8(img, width, height, s, st, zb=None):
             else:
                 sv = ((bx * s["_sh"][0][i] + by * s["_sh"][1][i]).astype(np.float32) + bz * s["_sh"][2][i]).astype(np.float32)
             m = as_u8(rmin((m.astype(np.float32) * sv).astype(np.float32), f32(255.0)))               # shade_color_rgb :1074-1081 (no clamp)
+            t_shade.append(sv)
         cols.append(m)
     vc = s["vc"]
     needs_dither = st.dithering and (st.shading == 2 or tex is not None or not np.array_equal(vc[0], vc[1]) or not np.array_equal(vc[1], vc[2]))
+    t_m = list(cols)
     if needs_dither:                                                                                  # apply_dither :1186-1197
         off = DITHER[py & 3, px & 3]
         cols = [np.clip((c + off) >> K("dither8.shift"), 0, K("dither8.clamp_hi")) << K("dither8.expand_shift") for c in cols]
     front = np.stack(cols, axis=1).astype(np.int64)
     back = img[py, px, :3].astype(np.int64)
+    if tap is not None:
+        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, t_m, needs_dither, back)
     mode = tx_[:, 3]
     ps1 = front.copy()
     a_out = np.full(len(ys), 255, np.int64)
