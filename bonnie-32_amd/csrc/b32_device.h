@@ -15,7 +15,8 @@ namespace b32 {
 constexpr int TILE_W = 64;          // screen tile owned by one workgroup pass of k_fill
 constexpr int TILE_H = 64;
 constexpr int TILE_STRIDE = 72;     // LDS row stride in dwords (64 + 8: an 8x8 lane block maps to 32 distinct banks per half-wave)
-constexpr int FILL_THREADS = 1024;  // 16 waves: 4 per SIMD
+constexpr int FILL_THREADS = 1024;  // the LARGEST fill workgroup (16 waves: the fused kernel's form for few tiles, the LDS-staged texture form); every
+                                    // other fill form is launched with 512 threads.  Sizes LDS_MARK_BYTES only.
 constexpr int FILL_WAVES = FILL_THREADS / 64;
 constexpr uint32_t KEY_INVALID = 0xFFFFFFFFu;
 
@@ -616,7 +617,7 @@ struct FillArgs {
     // pixel of the band nobody draws, so the frame has no clear launch and uncovered pixels are written once, not twice)
     uint32_t clear_on, clear_rgba;
     uint32_t clear_depth;       // with clear_on in z-buffer mode: the clear resets the depth buffer too (every depth f32::MAX, render.rs:43)
-    uint32_t narrow_only;       // 1: never the 16-wave workgroups of the fused kernel (b32_set_routes)
+    uint32_t wide;              // host only (launch_fill): the fused kernel's workgroup form, 1 = 16 waves (plan_wide, b32_frame_plan.h; b32_set_routes can rule it out)
     // One indexed texture (b32_scene_upload_indexed, nt == 1): 256 CLUT entries (zero behind the palette: an index past it looks up 0x0000,
     // Clut::lookup types.rs:390-397) followed by width * height index bytes.  atlas_idx_bytes > 0: every workgroup of the fused kernel
     // stages both in LDS behind its tile planes and the shading phase looks the texel up there instead of fetching the expanded texel
@@ -631,8 +632,8 @@ struct FillArgs {
     uint32_t start_seq;         // != 0: workgroup 0 publishes it in Events::fill_started when the fused kernel starts (see k_gate) ...
     uint32_t start_defer;       // ... unless the frame's transparent pass does (1: k_blend).  The next frame's setup kernel then runs beside THAT kernel and
                                 //     the fill has the GPU to itself (b32_frame.hip)
-    uint32_t prio64;            // 1: sort-free coverage -- visibility is a 64-bit max of (painter's key << 32 | face id); `vis` holds
-                                //    two words per pixel: winner face id + 1, runner-up face id + 1 (0 = none)
+    uint32_t fused;             // host only (launch_fill): 1 = the fused kernel is the kernel that runs (plan_fused, b32_frame_plan.h) -- sort-free
+                                //    coverage, visibility is a 64-bit max of (painter's key << 32 | face id), coverage and shading are one launch
 #ifdef B32_TIMELINE
     unsigned long long* dbg;    // experiment builds only: [0] = entry counter, then 4 words per tile (wg << 32 | tile, t_start, t_covered, t_shaded)
 #endif

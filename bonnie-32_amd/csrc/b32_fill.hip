@@ -548,17 +548,46 @@ extern "C" int b32_debug_timeline(unsigned long long* out, unsigned cap_words) {
     return 1;
 }
 #endif
+// The large-LDS opt-in of one kernel (hipFuncSetAttribute is per device: once per kernel and device, on its first launch there)
+template <auto KERNEL>
+static void raise_lds_limit() {
+    static bool attr[64] = {};
+    if (first_launch_on_device(attr)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+// One form of the fused kernel: the kernel, its opt-in, its workgroup size.
+struct P64Form { void (*kernel)(FillArgs); void (*raise)(); uint32_t threads; };
+template <auto KERNEL>
+static P64Form p64_form(uint32_t threads) { return { KERNEL, &raise_lds_limit<KERNEL>, threads }; }
+
+// Which of the eight forms draws this frame (of the coverage rule, depth mode and pixel format <EXACT, ZMODE, FMT8>): the 16-wave form for
+// few tiles; else a straight-line form where the frame's settings allow one -- each a kernel of its own under a register cap, see above --;
+// else the generic 8-wave form.
+template <bool EXACT, bool ZMODE, bool FMT8>
+static P64Form pick_p64(const FillArgs& a, bool wide) {
+    if (wide) return p64_form<k_cover<0, EXACT, 1024, ZMODE, FMT8, true>>(1024);
+    const bool plain = a.fp.affine && a.fp.shading == B32_SHADE_NONE && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;
+    // (the straight-line shading's frames: see cover_body)
+    const bool straight = !FMT8 && !a.atlas_idx_bytes && a.tex0.width && a.tex0.height;
+    const bool lit_plain = a.fp.affine && a.fp.shading != B32_SHADE_NONE && a.shades && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;
+    if constexpr (!EXACT && ZMODE && !FMT8) {
+        if (lit_plain && straight) return p64_form<k_cover_lit>(512);
+    }
+    if (!plain) return p64_form<k_cover<0, EXACT, 512, ZMODE, FMT8, true>>(512);
+    // (named here, in front of the forms that return first: the painter's CHEAP 8-bit frames all take k_cover_plain8, and the generic plain
+    // form of that combination stays a kernel of the library although nothing launches it)
+    const P64Form generic_plain = p64_form<k_cover<0, EXACT, 512, ZMODE, FMT8, true, 2>>(512);
+    if (straight) {
+        if constexpr (!EXACT && !ZMODE) return p64_form<k_cover_plain>(512);
+        else if constexpr (!EXACT && ZMODE) return p64_form<k_cover_plain_z>(512);
+        else return p64_form<k_cover<0, EXACT, 512, ZMODE, false, true, 1>>(512);
+    }
+    if constexpr (!EXACT && !ZMODE && FMT8) return p64_form<k_cover_plain8>(512);
+    return generic_plain;
+}
+
 template <bool EXACT, bool ZMODE, bool FMT8>
 static void launch_p64(hipStream_t s, const FillArgs& a_in, uint32_t ntiles, int n_cu, bool wide) {
     FillArgs a = a_in;
-    // tile planes, misc words, 64 words of repair queue per wave, then the staged index atlas (if any)
-    const size_t atlas = a.atlas_idx_bytes ? (((size_t)ATLAS_CLUT_BYTES + a.atlas_idx_bytes + 15) & ~(size_t)15) : 0;
-    const size_t lds_n = 4 * LDS_TILE_BYTES + LDS_MISC_BYTES + 8 * RQ_BYTES + atlas, lds_w = 4 * LDS_TILE_BYTES + LDS_MISC_BYTES + 16 * RQ_BYTES + atlas;
-    static bool attr[64] = {};
-    if (first_launch_on_device(attr)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<0, EXACT, 512, ZMODE, FMT8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<0, EXACT, 1024, ZMODE, FMT8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
     const dim3 g(min(ntiles, (uint32_t)n_cu * 2));
 #ifndef B32_STAGGER_TICKS
 #define B32_STAGGER_TICKS 400
@@ -575,40 +604,12 @@ static void launch_p64(hipStream_t s, const FillArgs& a_in, uint32_t ntiles, int
         g_timeline = dbg;
     }
 #endif
-    const bool plain = a.fp.affine && a.fp.shading == B32_SHADE_NONE && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;
-    // (the straight-line shading's frames: see cover_body)
-    const bool straight = !FMT8 && !a.atlas_idx_bytes && a.tex0.width && a.tex0.height;
-    const bool lit_plain = a.fp.affine && a.fp.shading != B32_SHADE_NONE && a.shades && a.fp.fixed_point && !a.fp.ortho && a.fp.nt == 1 && !a.inline_bin && !a.gather_blend;
-    if constexpr (!EXACT && ZMODE && !FMT8) {
-        if (lit_plain && straight && !wide) {
-            static bool attr_lit[64] = {};
-            if (first_launch_on_device(attr_lit)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover_lit), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(k_cover_lit, g, dim3(512), lds_n, s, a);
-            return;
-        }
-    }
-    if (plain && !wide) {
-        static bool attr_plain[64] = {};
-        const bool first = first_launch_on_device(attr_plain);
-        if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<0, EXACT, 512, ZMODE, FMT8, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if constexpr (!EXACT && !ZMODE) {
-            if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (straight) { hipLaunchKernelGGL(k_cover_plain, g, dim3(512), lds_n, s, a); return; }
-        } else if constexpr (!EXACT && ZMODE) {
-            if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover_plain_z), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (straight) { hipLaunchKernelGGL(k_cover_plain_z, g, dim3(512), lds_n, s, a); return; }
-        } else {
-            if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<0, EXACT, 512, ZMODE, false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (straight) { hipLaunchKernelGGL((k_cover<0, EXACT, 512, ZMODE, false, true, 1>), g, dim3(512), lds_n, s, a); return; }
-        }
-        if constexpr (!EXACT && !ZMODE && FMT8) {
-            if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover_plain8), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(k_cover_plain8, g, dim3(512), lds_n, s, a);
-            return;
-        }
-        hipLaunchKernelGGL((k_cover<0, EXACT, 512, ZMODE, FMT8, true, 2>), g, dim3(512), lds_n, s, a);
-    } else if (wide) hipLaunchKernelGGL((k_cover<0, EXACT, 1024, ZMODE, FMT8, true>), g, dim3(1024), lds_w, s, a);
-    else hipLaunchKernelGGL((k_cover<0, EXACT, 512, ZMODE, FMT8, true>), g, dim3(512), lds_n, s, a);
+    const P64Form form = pick_p64<EXACT, ZMODE, FMT8>(a, wide);
+    // tile planes, misc words, 64 words of repair queue per wave, then the staged index atlas (if any)
+    const size_t atlas = a.atlas_idx_bytes ? (((size_t)ATLAS_CLUT_BYTES + a.atlas_idx_bytes + 15) & ~(size_t)15) : 0;
+    const size_t lds = 4 * LDS_TILE_BYTES + LDS_MISC_BYTES + (form.threads / 64) * RQ_BYTES + atlas;
+    form.raise();
+    hipLaunchKernelGGL(form.kernel, g, dim3(form.threads), lds, s, a);
 }
 
 void launch_fill(hipStream_t s, const FillArgs& a, int n_cu, hipEvent_t after_cover) {
@@ -622,12 +623,10 @@ void launch_fill(hipStream_t s, const FillArgs& a, int n_cu, hipEvent_t after_co
         return;
     }
     const size_t lds_sort = LDS_TEX_OFFSET + LDS_SORT_CNT_BYTES + 2048;
-    if (a.prio64) {   // sort-free fused kernel: coverage and shading are one launch; 64-bit tile buffers (2 x 36 KB)
+    if (a.fused) {   // sort-free fused kernel (plan_fused; the two returns above are its other operands): coverage and shading are one launch; 64-bit tile buffers (2 x 36 KB)
         // EXACT = texel rule per fragment (textures with many skippable texels, or exact store counting); z-buffer mode = the
-        // priority's high word is the fragment depth.  Few tiles (narrow multi-GPU bands, small frames): 16 waves per tile.
-        // (16-wave workgroups only while every tile can have a CU of its own: with more tiles than CUs the 8-wave form, two workgroups per
-        // CU, is faster -- a 960-row band of C3, 600 tiles: 0.112 -> 0.086 ms; 480 rows: 0.086 -> 0.067; 240 rows: 0.067 -> 0.057)
-        const bool wide = ntiles <= (uint32_t)n_cu && !a.narrow_only;
+        // priority's high word is the fragment depth.  Few tiles (narrow multi-GPU bands, small frames): 16 waves per tile (plan_wide).
+        const bool wide = a.wide != 0;
         const int sel = (a.exact_coverage ? 4 : 0) | (a.fp.zmode ? 2 : 0) | (f8 ? 1 : 0);
         switch (sel) {
             case 0: launch_p64<false, false, false>(s, a, ntiles, n_cu, wide); break;
@@ -650,8 +649,7 @@ void launch_fill(hipStream_t s, const FillArgs& a, int n_cu, hipEvent_t after_co
             hipLaunchKernelGGL((k_cover<0, true, 512, false, true>), dim3(min(ntiles, (uint32_t)n_cu * 2)), dim3(512), LDS_TEX_OFFSET, s, a);
         } else if (a.lds_tex_texels) {     // texture sampled once per fragment: stage it in LDS, one 16-wave workgroup per CU
             const size_t lds = LDS_TEX_OFFSET + (((size_t)a.lds_tex_texels * 2 + 15) & ~(size_t)15);
-            static bool attr_set[64] = {};
-            if (first_launch_on_device(attr_set)) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cover<1, true, 1024, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            raise_lds_limit<k_cover<1, true, 1024, false, false>>();
             hipLaunchKernelGGL((k_cover<1, true, 1024, false, false>), dim3(min(ntiles, (uint32_t)n_cu)), dim3(1024), lds, s, a);
         } else {
             hipLaunchKernelGGL((k_cover<0, true, 512, false, false>), dim3(min(ntiles, (uint32_t)n_cu * 2)), dim3(512), LDS_TEX_OFFSET, s, a);

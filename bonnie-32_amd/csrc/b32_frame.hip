@@ -76,8 +76,11 @@ int validate_settings(const B32Settings* st) {
 static uint32_t bits_for(uint32_t n_keys) { uint32_t b = 1; while ((1ull << b) < n_keys) ++b; return b; }
 
 // ------------------------------------------------------------------ one frame = the pieces below, in order (enqueue_frame)
-// Which pipeline a frame takes.  Every route produces the same framebuffer (tests run every scene through several of them).
-struct Route {
+// The frame's plan: which pipeline it takes (every route produces the same framebuffer: tests run every scene through several of them)
+// and what the steps of enqueue_frame pass to each other.  The decisions themselves are b32_frame_plan.h's.
+struct FramePlan {
+    bool wire_back = false, wire_front = false;      // the wireframe phases of this frame (render.rs:2577, 2603)
+    // ---- the route (plan_route)
     bool with_class = false;     // the scene can have a transparent pass: tile lists are split by class
     bool ordered_all = false;    // ordered walk of whole tile lists instead of the overwrite pass (x-ray; 8-bit path with blending texels)
     bool want_prio64 = false;    // sort-free fused path (painter's or z-buffer mode)
@@ -85,9 +88,38 @@ struct Route {
     bool local_sort = false;     // keyed fast path: per-tile LDS sort instead of the global painter's sort
     bool want_inline = false;    // small mesh: the fused kernel's workgroups collect their own tile lists
     bool direct_bin = false;     // large mesh: k_setup appends to fixed tile regions (DirectBin)
-    bool inline_bin = false, prio64 = false;     // what was finally launched
+    bool inline_bin = false, prio64 = false;     // the tile lists the fill reads (inline / direct binning: known from the route; span binning: once it ran)
     uint32_t list_stride = 0;    // entries per tile region (inline / direct binning)
     DirectBin db{};
+    uint32_t ntiles = 0;         // of the grid plan_route left in FrameParams
+    bool fused = false, wide = false;                // plan_fused / plan_wide: asked once, here (set_prio64, plan_pipeline); FillArgs carries them to launch_fill
+    void set_prio64(bool on) { prio64 = on; fused = plan_fused(prio64, wire_front, ordered_all); }
+    // ---- two frames in flight (plan_pipeline, order_side_stream, hand_over)
+    HandOver hand_over_kind = HandOver::None;
+    hipStream_t setup_stream = nullptr;              // the side stream of a pipelined frame, else the context's
+    uint32_t poll_seq = 0, poll_patience = 0;        // FillArgs::join_seq / join_patience of a polled hand-over
+    uint32_t start_seq = 0;                          // the start word this frame's fused kernel was meant to publish
+    // ---- wireframe phases (wire_args, hand_over, wire_phases)
+    bool wire_on = false, wire_binned = false, wire_polled = false;
+    WireArgs wa{};
+    // ---- the rest
+    const float *pos12 = nullptr, *attr12 = nullptr; // packed vertex streams (frame_positions)
+    bool prof_all = false, prof_fill = false;        // profiling level 2 / >= 1 on this frame
+    hipEvent_t* ev = nullptr;                        // its row of events
+    int pair_buf = 0;                                // the pair buffer that holds the keyed routes' grouped lists (bin_keyed)
+};
+
+// The frame sets between rotate_sets and the frame's first launch into the set it rotated to: every return in between -- the ones inside
+// HIPCHK too -- puts the sets back (the pending frame stays the current set's) and the frame is not pipelined.  Dismissed immediately
+// before launch_setup: from there on the frame is in flight in that set and no return may unrotate.
+struct SetsGuard {
+    b32_ctx* c; bool armed = false;
+    explicit SetsGuard(b32_ctx* ctx) : c(ctx) {}
+    SetsGuard(const SetsGuard&) = delete;
+    SetsGuard& operator=(const SetsGuard&) = delete;
+    void rotate() { rotate_sets(c); armed = true; }
+    void dismiss() { armed = false; }
+    ~SetsGuard() { if (armed) { unrotate_sets(c); c->pipelined = false; } }
 };
 
 static FrameParams frame_params(const b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, bool wire_any) {
@@ -214,7 +246,8 @@ static int frame_buffers(b32_ctx* c, const FrameParams& fp, bool wire_back) {
 }
 
 // Route selection.  May cut the tile grid (fp.tile_h / tile_yb / tiles_y) and prepares the direct binning's regions.
-static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool wire_front, Route& r) {
+static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, FramePlan& r) {
+    const bool wire_front = r.wire_front;
     int rc;
     // z-buffer frames without a transparent pass take the sort-free fused path too (depth is the priority); otherwise z-buffer
     // mode applies depth + skip rule per fragment (EXACT coverage)
@@ -226,17 +259,12 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
     r.want_prio64 = spans_ok && !fp.ortho && !r.ordered_all;
     // too few 64x64 tiles to fill the GPU (narrow multi-GPU band, PS1-sized frame): tiles of 32 or 16 rows multiply the parallelism
     // of the fused kernel.  Only the sort-free path knows about them (its k_blend included); the keyed kernels keep 64 rows.
-    if (r.want_prio64 && c->band_y1 > c->band_y0 && !(c->route_off & B32_ROUTE_CUT_TILES)) {
-        uint32_t th = TILE_H;
-        // 64 -> 32 rows below two tiles per CU, 32 -> 16 -> 8 rows below one tile per CU (measured: a 240-row band of C3 prefers 320 tiles
-        // of 32 rows to 600 of 16; C2's 20 tiles prefer 150 of 8 rows -- 0.039 ms against 0.051 with 75 of 16 rows, 0.049 with 300 of 4)
-        while (th > (uint32_t)B32_MIN_TILE_H && fp.tiles_x * ((c->band_y1 + th - 1) / th - c->band_y0 / th) < (th == TILE_H ? 2u : 1u) * (uint32_t)c->n_cu &&
-               (c->band_y1 - c->band_y0) / (th / 2) + 2 <= 255 /* tile rows must fit the packed spans */) th /= 2;
-        fp.tile_h = th;
-        fp.tile_yb = (c->band_y0 / th) * th;
-        fp.tiles_y = (c->band_y1 - fp.tile_yb + th - 1) / th;
+    if (r.want_prio64 && !(c->route_off & B32_ROUTE_CUT_TILES)) {
+        static_assert(PLAN_TILE_H == (uint32_t)TILE_H, "b32_frame_plan.h cuts the tiles of b32_device.h");
+        const TileGrid g = plan_cut_grid(fp.tiles_x, c->band_y0, c->band_y1, (uint32_t)c->n_cu, (uint32_t)B32_MIN_TILE_H);
+        fp.tile_h = g.tile_h; fp.tile_yb = g.tile_yb; fp.tiles_y = g.tiles_y;
     }
-    const uint32_t ntiles = fp.tiles_x * fp.tiles_y;
+    const uint32_t ntiles = r.ntiles = fp.tiles_x * fp.tiles_y;
     // EXACT coverage = texel rule per fragment: exact store counting, textures with many skippable texels; the keyed z-buffer kernel
     // is EXACT by construction
     r.exact_cov = c->count_fragments || !c->scene.cheap_ok || (fp.zmode && !r.want_prio64);
@@ -280,6 +308,17 @@ static int plan_route(b32_ctx* c, FrameParams& fp, const SortScratch& sc, bool w
             r.list_stride = region;
         } else c->scene.direct_ok = false;
     }
+    // (the small mesh's list regions: allocated here, in front of every launch of the frame -- growing them synchronises the stream and
+    // frees the old buffer, which must not happen between a frame's setup kernel and its fill)
+    if (!r.direct_bin && r.want_inline) {
+        const size_t need = (size_t)ntiles * r.list_stride + 64;
+        if (need > c->cap_inline) {
+            if ((rc = ensure_plain(c, c->inline_lists, need + need / 2))) return rc;
+            c->cap_inline = need + need / 2;
+        }
+        r.inline_bin = true;
+    }
+    r.set_prio64(r.direct_bin || r.inline_bin);        // (a span-binned frame: decided when the binning has run, tile_lists)
     return B32_OK;
 }
 
@@ -309,10 +348,11 @@ static int frame_positions(b32_ctx* c, const FrameParams& fp, const float*& pos1
 }
 
 // The keyed pipelines (no sort-free path for this frame): pairs keyed by (tile, class), grouped by radix passes; returns the pair buffer
-// that holds the grouped lists.  ev_bin: event to record when the binning proper starts (profiling level 2), or nullptr.
-static int bin_keyed(b32_ctx* c, const FrameParams& fp, const Route& r, const SortScratch& sc, hipEvent_t ev_bin, int& cur) {
+// that holds the grouped lists (FramePlan::pair_buf).  ev_bin: event to record when the binning proper starts (profiling level 2), or nullptr.
+static int bin_keyed(b32_ctx* c, const FrameParams& fp, FramePlan& r, const SortScratch& sc, hipEvent_t ev_bin) {
     hipStream_t s = c->stream;
-    const uint32_t ntiles = fp.tiles_x * fp.tiles_y;
+    const uint32_t ntiles = r.ntiles;
+    int& cur = r.pair_buf;
     cur = 0;
     if (r.local_sort) {
         // fast path: no global depth sort.  Pairs are emitted in face order from k_setup's spans; k_cover sorts every tile
@@ -351,9 +391,9 @@ static int bin_keyed(b32_ctx* c, const FrameParams& fp, const Route& r, const So
     return B32_OK;
 }
 
-static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const Route& r, int cur, bool wire_front) {
+static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const FramePlan& r) {
     FillArgs fa{};
-    fa.fp = fp; fa.crecs = c->cur.crecs; fa.srecs = c->cur.srecs; fa.xrecs = c->cur.xrecs; fa.shades = c->cur.shades; fa.pair_vals = c->pvals[cur]; fa.ranges = c->ranges;
+    fa.fp = fp; fa.crecs = c->cur.crecs; fa.srecs = c->cur.srecs; fa.xrecs = c->cur.xrecs; fa.shades = c->cur.shades; fa.pair_vals = c->pvals[r.pair_buf]; fa.ranges = c->ranges;
     fa.keys = c->cur.keys0; fa.local_sort = r.local_sort ? 1u : 0u; fa.tile_keys_only = (r.local_sort || r.prio64) ? 1u : 0u; fa.tile_mid = c->tile_mid;
     fa.tex = c->scene.d_tex; fa.texels = c->scene.d_texels; fa.fb = c->fb; fa.vis = c->vis; fa.zbuf = c->zbuf; fa.ctrl = c->cur.d_ctrl;
     fa.tex0 = c->scene.nt ? c->scene.h_tex[0] : TexDesc{ 0, 0, 0, 0 };
@@ -364,11 +404,11 @@ static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const Route& 
     }
     fa.exact_coverage = r.exact_cov ? 1u : 0u;
     fa.may_blend = c->scene.may_blend ? 1u : 0u;
-    fa.skip_solid = wire_front ? 1u : 0u;
+    fa.skip_solid = r.wire_front ? 1u : 0u;
     fa.texels32 = c->scene.d_texels32;
     fa.ordered_all = r.ordered_all ? 1u : 0u;
-    fa.prio64 = r.prio64 ? 1u : 0u;
-    fa.narrow_only = (c->route_off & B32_ROUTE_WIDE_GROUPS) ? 1u : 0u;
+    fa.fused = r.fused ? 1u : 0u;
+    fa.wide = r.wide ? 1u : 0u;
     fa.texmask = c->scene.d_texmask;
     { const uint32_t words = c->scene.pool_texels / 32 + 2; fa.mask_lds_words = (c->scene.pool_texels && words <= MASK_LDS_MAX_WORDS) ? words : 0u; }
     fa.inline_bin = r.inline_bin ? 1u : 0u; fa.list_stride = r.list_stride; fa.spans = c->cur.spans; fa.partials = c->cur.partials;
@@ -379,27 +419,19 @@ static FillArgs fill_args(const b32_ctx* c, const FrameParams& fp, const Route& 
     fa.stagger = (c->route_off & B32_ROUTE_STAGGER) ? 0u : 1u;       // (launch_fill decides whether the frame qualifies)
     fa.span_cover = (r.prio64 && !r.exact_cov && !fp.zmode && !(c->route_off & B32_ROUTE_SPAN_COVER)) ? 1u : 0u;
     // index atlas + CLUT sampled from LDS: the fused kernel with one indexed texture, when they fit beside the tile planes of the
-    // workgroup form launch_fill is going to choose (16 waves, one workgroup per CU: ~84 KB; two 8-wave workgroups per CU: ~6 KB)
+    // workgroup form launch_fill is told to launch (16 waves, one workgroup per CU: ~84 KB; two 8-wave workgroups per CU: ~6 KB)
     fa.atlas0 = c->scene.d_atlas0; fa.atlas_idx_bytes = 0;
-    if (r.prio64 && !c->scene.fmt8 && c->scene.nt == 1 && c->scene.atlas_idx_bytes && !(c->route_off & B32_ROUTE_LDS_ATLAS)) {
-        const bool wide = fp.tiles_x * fp.tiles_y <= (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
-        if (c->scene.atlas_idx_bytes + ATLAS_CLUT_BYTES + 16u <= fill_lds_atlas_room(wide)) fa.atlas_idx_bytes = c->scene.atlas_idx_bytes;
-    }
+    if (r.prio64 && !c->scene.fmt8 && c->scene.nt == 1 && c->scene.atlas_idx_bytes && !(c->route_off & B32_ROUTE_LDS_ATLAS) &&
+        c->scene.atlas_idx_bytes + ATLAS_CLUT_BYTES + 16u <= fill_lds_atlas_room(r.wide))
+        fa.atlas_idx_bytes = c->scene.atlas_idx_bytes;
     if (c->scene.fmt8) fa.fp.xray = 0;                        // render_mesh: x-ray only changes culling; its stores keep their own depth tests
     return fa;
 }
 
-int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog) {
-    hipStream_t s = c->stream;
-    const bool wire_back = st->backface_cull && st->backface_wireframe;      // render.rs:2577
-    const bool wire_front = st->wireframe_overlay != 0;                       // render.rs:2603 (an empty list draws nothing either way)
-    FrameParams fp = frame_params(c, cam, st, fog, wire_back || wire_front);
-    LightSet lset{};
-    int rc;
-    const bool prof_sample = c->profile_level >= 1 && (c->prof_seq++ % c->prof_stride) == 0;
-    const bool prof_all = prof_sample && c->profile_level >= 2, prof_fill = prof_sample;
-    // Two frames in flight: when an earlier frame of this context is still pending, this frame of a large mesh takes the OTHER frame set
-    // and (if it ends up on the direct-binning route) its setup kernel runs on the side stream, beside that frame's fill.
+// ------------------------------------------------------------------ the steps of enqueue_frame, in the order it calls them
+// Two frames in flight: when an earlier frame of this context is still pending, this frame of a large mesh takes the OTHER frame set
+// and (if it ends up on the direct-binning route) its setup kernel runs on the side stream, beside that frame's fill.
+static int choose_frame_set(b32_ctx* c, const FramePlan& r, SetsGuard& sets) {
     c->pipelined = false;
     // (pipe_hint: whether the previous frame's route qualified -- a frame that will not, e.g. every frame of a PS1-sized target, skips
     // the set swap and its event as well: 0.030 -> 0.028 ms on 20 k triangles at 320x240)
@@ -407,185 +439,172 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // (not on the legacy default stream -- hipStreamLegacy, what torch's default stream maps to: it synchronises implicitly with every
     // blocking stream, and recording / waiting cross-stream events on that handle crashed the runtime, found when safe mode began to
     // leave superseded frames in flight)
-    if (c->frame_pending && c->pipe_hint && !c->redrawing && !prof_all && c->scene.nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
-        c->stream != hipStreamLegacy) {
-        if ((rc = pipeline_ensure(c))) return rc;
-        rotate_sets(c);
-        c->pipelined = true;
-        if (c->join_stream != s) {
-            // Streams of different priorities never share a hardware queue (the runtime pools its queues by priority); two streams of ONE
-            // priority may, and k_join in front of k_flag in the same queue would wait for its patience: those keep the event.
-            int pm = 0, ps = 0;
-            c->join_ok = hipStreamGetPriority(s, &pm) == hipSuccess && hipStreamGetPriority(c->side, &ps) == hipSuccess && pm != ps;
-            c->join_stream = s;
-        }
+    if (!(c->frame_pending && c->pipe_hint && !c->redrawing && !r.prof_all && c->scene.nf > pipe_min_faces && !(c->route_off & B32_ROUTE_PIPELINE) &&
+          c->stream != hipStreamLegacy))
+        return B32_OK;
+    int rc;
+    if ((rc = pipeline_ensure(c))) return rc;
+    sets.rotate();
+    c->pipelined = true;
+    if (c->join_stream != c->stream) {
+        // Streams of different priorities never share a hardware queue (the runtime pools its queues by priority); two streams of ONE
+        // priority may, and k_join in front of k_flag in the same queue would wait for its patience: those keep the event.
+        int pm = 0, ps = 0;
+        c->join_ok = hipStreamGetPriority(c->stream, &pm) == hipSuccess && hipStreamGetPriority(c->side, &ps) == hipSuccess && pm != ps;
+        c->join_stream = c->stream;
     }
-    // (an error return between the rotation and the launches puts the sets back: the pending frame stays the current set's)
-    bool rotated = c->pipelined;
-    auto fail = [&](int e) { if (rotated) { unrotate_sets(c); rotated = false; c->pipelined = false; } return e; };
-    if ((rc = frame_lights(c, st, fp, lset))) return fail(rc);
-    if ((rc = frame_buffers(c, fp, wire_back))) return fail(rc);
-    hipEvent_t* ev = nullptr;
-    if (prof_fill) {
-        if (!c->ev_created) {
-            for (auto& fr : c->ev) for (auto& e : fr) if (hipEventCreate(&e) != hipSuccess) return fail(B32_E_HIP);
-            c->ev_created = true;
-        }
-        ev = c->ev[c->ev_frames % EV_RING];
-    }
+    return B32_OK;
+}
 
-    const SortScratch sc{ c->block_hist, c->hist_blocks, c->digit_total };
-    Route r;
-    if ((rc = plan_route(c, fp, sc, wire_front, r))) return fail(rc);
-    // (only large meshes: the frames of small ones are launch-latency bound and the cross-stream events cost them more than the overlap
-    // returns -- a 12-room console frame 0.72 ms against 0.65; keyed routes have binning launches behind k_setup: one stream)
-    const uint32_t ntiles = fp.tiles_x * fp.tiles_y;
-    // ... and a frame whose fused kernel has no more tiles than workgroup slots has no tail to fill: the cross-stream waits (~10 us
-    // between two kernels) then cost more than the overlap returns (C2, 100 k triangles at 320x240: 0.052 against 0.048 ms).  The merged
-    // runs of a batched frame are the exception: their kernels leave most of the GPU idle anyway (75 tiles for 256 CUs).
-    // Round 6: with the flag / join kernel pair (no cross-stream event: ~5 us instead of ~12) frames WITHOUT a tail pay too when their two
-    // kernels are of comparable length -- C2, 100 k triangles at 320x240: setup 15.7 + fill 21.9 us, 0.0375 -> 0.0339 ms per frame --
-    // but only on that hand-over (the small-mesh route keeps the event: C1 0.0235 -> 0.0281), i.e. while the caller's stream and the side
-    // stream have different priorities (unknown before the first pipelined frame of a stream: tried once, then decided).
-    // The same for the frames of a screen band (one rank of a sharded frame: 240 rows of C4 are 320 tiles of 32 rows) -- round 5 had measured
-    // them with the event (N = 8 band 0.067 -> 0.071: no); with the kernel pair the weak series' N = 8 point goes 0.054 -> 0.042 ms per rank.
-    const bool join_small = !c->frame_batched && (c->join_stream != s || c->join_ok);
-    c->pipe_hint = r.direct_bin && (ntiles > 2u * (uint32_t)c->n_cu || c->frame_batched || join_small);
+// the frame's row of profiling events (created on first use)
+static int profiling_row(b32_ctx* c, FramePlan& r) {
+    if (!r.prof_fill) return B32_OK;
+    if (!c->ev_created) {
+        for (auto& fr : c->ev) for (auto& e : fr) if (hipEventCreate(&e) != hipSuccess) return B32_E_HIP;
+        c->ev_created = true;
+    }
+    r.ev = c->ev[c->ev_frames % EV_RING];
+    return B32_OK;
+}
+
+// What follows from the route for the two frame sets: whether the NEXT frame may rotate (pipe_hint), whether this one keeps the side
+// stream, its hand-over, and the fused kernel's workgroup form.  What b32_frame_finish needs to know about the route is noted here too.
+static void plan_pipeline(b32_ctx* c, const FrameParams& fp, FramePlan& r) {
+    const bool join_small = !c->frame_batched && (c->join_stream != c->stream || c->join_ok);
+    c->pipe_hint = plan_pipe_hint(r.direct_bin, r.ntiles, (uint32_t)c->n_cu, c->frame_batched, join_small);
     if (!c->pipe_hint) c->pipelined = false;       // (the frame keeps the set it rotated to -- the route's regions are that set's -- but runs on the main stream)
     c->last_local_sort = r.local_sort || r.want_prio64;                         // the global draw order is not materialised
     c->last_exact = r.ordered_all ? true : (r.exact_cov && !fp.zmode);          // the ordered walk counts every store it performs
     c->last_direct = r.direct_bin;
-    if (c->scene.nf == 0) {                                                             // otherwise k_setup resets it (all but `sticky`)
-        HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl, 0, offsetof(Ctrl, sticky), s));
-        HIPCHK(c, hipMemsetAsync(&c->cur.d_ctrl->fragments, 0, sizeof(unsigned long long), s));
-        HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl + 1, 0, sizeof(Stamps), s));          // (and the phase clock: b32_last_shader_clock of an empty frame is 0, not the frame before's)
-    }
-    const float *pos12 = nullptr, *attr12 = nullptr;
-    if ((rc = frame_positions(c, fp, pos12, attr12))) return fail(rc);
+    const bool narrow_only = (c->route_off & B32_ROUTE_WIDE_GROUPS) != 0;
+    r.wide = plan_wide(r.ntiles, (uint32_t)c->n_cu, narrow_only);
+    r.hand_over_kind = plan_hand_over({ c->pipelined, c->frame_batched, c->join_ok, r.direct_bin, r.wire_front, r.ordered_all, r.ntiles, (uint32_t)c->n_cu, narrow_only });
+}
 
-    // ---- transform, cull, setup (+ tile binning of large meshes)
-    hipStream_t ss = s;
-    if (c->pipelined) {
-        if (c->side_dirty) { HIPCHK(c, hipEventRecord(c->ev_main, s)); HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0)); c->side_dirty = false; }
-        ss = c->side;
-        c->pipelined_frames++;
-        uint32_t polled_tiles = 0, polled_groups = 0, polled_seq = 0;       // the fused kernel of the frame whose cursor the gate polls (alt[0]: n_sets - 1 frames back)
-        for (const auto& co : c->cover_of) if (co.ctrl && co.ctrl == c->alt[0].d_ctrl) { polled_tiles = co.tiles; polled_groups = co.groups; polled_seq = co.seq; }
-        // The set this frame's setup kernel writes was last read by the fill n_sets frames back.  That fill lies in front of alt[0]'s on the main
-        // stream: when alt[0]'s frame launched a fused kernel, "it has started" orders the two on the device (k_gate, no event on the main
-        // stream); else the side stream waits for the main stream as it stands now.
-        const bool start_gate = polled_tiles && polled_seq && c->alt[0].d_ctrl;
-        if (!start_gate) { HIPCHK(c, hipEventRecord(c->ev_main, s)); HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0)); }
-        uint32_t gate_need = 0;
-        if (c->gate_permille && polled_tiles && c->alt[0].d_ctrl) {
-            // The fused kernel's workgroups take their next tile from the cursor after the coverage of the current one: the cursor
-            // passes tiles - groups when the last tile is handed out, and every fetch beyond that is a workgroup that found the queue
-            // empty and has only the shading of its last tile left, i.e. is about to free its place on a CU.
-            const uint32_t groups = polled_groups, tiles = polled_tiles;
-            const uint32_t pre = tiles > groups ? tiles - groups : 0u;      // cursor value when the last tile is handed out
-            const uint32_t need = c->gate_permille > 1000u ? (uint32_t)((uint64_t)(c->gate_permille - 1000u) * pre / 1000u)
-                                                           : pre + (uint32_t)((uint64_t)(c->gate_permille - 1u) * groups / 1000u);
-            gate_need = need;
-        }
-        // (b32_debug_inject(ctx, 2): the fill in front did not publish its start -- this gate's patience is 2 ms, then the error)
-        const uint32_t start_patience = c->start_lost ? 200000u : 200000000u;
-        c->start_lost = false;                               // (one gate only, whichever way this frame is ordered)
-        if (gate_need || start_gate) launch_gate(ss, c->alt[0].d_ctrl, gate_need, 30000u /* 300 us */, start_gate ? polled_seq : 0u, c->cur.d_ctrl, start_patience);      // alt[0]: the frame n_sets - 1 back (rotate_sets)
+// an empty mesh launches no setup kernel: the control block it would have reset (all but `sticky`)
+static int reset_ctrl_of_empty_frame(b32_ctx* c) {
+    if (c->scene.nf) return B32_OK;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl, 0, offsetof(Ctrl, sticky), s));
+    HIPCHK(c, hipMemsetAsync(&c->cur.d_ctrl->fragments, 0, sizeof(unsigned long long), s));
+    HIPCHK(c, hipMemsetAsync(c->cur.d_ctrl + 1, 0, sizeof(Stamps), s));          // (and the phase clock: b32_last_shader_clock of an empty frame is 0, not the frame before's)
+    return B32_OK;
+}
+
+// A pipelined frame's setup kernel runs on the side stream: behind whatever the main stream wrote that it reads (side_dirty), behind the
+// last reader of the frame set it writes (start gate, or an event), and -- b32_set_pipeline_gate -- behind the tail of the fill in front.
+static int order_side_stream(b32_ctx* c, FramePlan& r) {
+    hipStream_t s = c->stream;
+    r.setup_stream = s;
+    if (!c->pipelined) return B32_OK;
+    if (c->side_dirty) { HIPCHK(c, hipEventRecord(c->ev_main, s)); HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0)); c->side_dirty = false; }
+    r.setup_stream = c->side;
+    c->pipelined_frames++;
+    uint32_t polled_tiles = 0, polled_groups = 0, polled_seq = 0;       // the fused kernel of the frame whose cursor the gate polls (alt[0]: n_sets - 1 frames back)
+    for (const auto& co : c->cover_of) if (co.ctrl && co.ctrl == c->alt[0].d_ctrl) { polled_tiles = co.tiles; polled_groups = co.groups; polled_seq = co.seq; }
+    // The set this frame's setup kernel writes was last read by the fill n_sets frames back.  That fill lies in front of alt[0]'s on the main
+    // stream: when alt[0]'s frame launched a fused kernel, "it has started" orders the two on the device (k_gate, no event on the main
+    // stream); else the side stream waits for the main stream as it stands now.
+    const bool start_gate = polled_tiles && polled_seq && c->alt[0].d_ctrl;
+    if (!start_gate) { HIPCHK(c, hipEventRecord(c->ev_main, s)); HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_main, 0)); }
+    const uint32_t gate_need = c->alt[0].d_ctrl ? plan_gate_need(c->gate_permille, polled_tiles, polled_groups) : 0u;
+    // (b32_debug_inject(ctx, 2): the fill in front did not publish its start -- this gate's patience is 2 ms, then the error)
+    const uint32_t start_patience = c->start_lost ? PATIENCE_INJECTED_TICKS : PATIENCE_TICKS;
+    c->start_lost = false;                               // (one gate only, whichever way this frame is ordered)
+    if (gate_need || start_gate) launch_gate(c->side, c->alt[0].d_ctrl, gate_need, 30000u /* 300 us */, start_gate ? polled_seq : 0u, c->cur.d_ctrl, start_patience);      // alt[0]: the frame n_sets - 1 back (rotate_sets)
+    return B32_OK;
+}
+
+// the wire kernels' arguments: known before the setup kernel is launched -- a pipelined frame bins its wire list on the side stream
+static void wire_args(b32_ctx* c, const FrameParams& fp, FramePlan& r) {
+    r.wire_on = fp.wire_collect && c->scene.nf;
+    if (!r.wire_on) return;
+    WireArgs& wa = r.wa;
+    wa.tris = c->cur.wire; wa.nf = c->scene.nf; wa.table_owner = c->wire_owner; wa.table_first = c->wire_first;
+    wa.table_mask = c->cap_wire_table ? (uint32_t)(c->cap_wire_table - 1) : 0;
+    wa.fb = c->fb; wa.zbuf = (c->zbuf && c->zbuf_valid) ? c->zbuf : nullptr;
+    wa.width = c->width; wa.height = c->height; wa.band_y0 = c->band_y0; wa.band_y1 = c->band_y1; wa.ctrl = c->cur.d_ctrl;
+    if (++c->wire_seq == 0) c->wire_seq = 1;
+    wa.epoch = c->wire_seq;
+    if (!(c->route_off & B32_ROUTE_WIRE_TILES) && c->cur.wire_fill && c->band_y1 > c->band_y0) {
+        wa.tile_yb = (c->band_y0 / WIRE_TH) * WIRE_TH; wa.tiles_x = (c->width + TILE_W - 1) / TILE_W;
+        wa.tiles_y = (c->band_y1 - wa.tile_yb + WIRE_TH - 1) / WIRE_TH;
+        if ((size_t)wa.tiles_x * wa.tiles_y <= c->cur.cap_wire_tiles) { wa.tile_fill = c->cur.wire_fill; wa.tile_lists = c->cur.wire_lists; c->wire_tile_frames++; }
     }
-    // (the wire kernels' arguments: known before the setup kernel is launched -- a pipelined frame bins its wire list on the side stream)
-    const bool wire_on = fp.wire_collect && c->scene.nf;
-    bool wire_binned = false, wire_polled = false;
-    WireArgs wa{};
-    if (wire_on) {
-        wa.tris = c->cur.wire; wa.nf = c->scene.nf; wa.table_owner = c->wire_owner; wa.table_first = c->wire_first;
-        wa.table_mask = c->cap_wire_table ? (uint32_t)(c->cap_wire_table - 1) : 0;
-        wa.fb = c->fb; wa.zbuf = (c->zbuf && c->zbuf_valid) ? c->zbuf : nullptr;
-        wa.width = c->width; wa.height = c->height; wa.band_y0 = c->band_y0; wa.band_y1 = c->band_y1; wa.ctrl = c->cur.d_ctrl;
-        if (++c->wire_seq == 0) c->wire_seq = 1;
-        wa.epoch = c->wire_seq;
-        if (!(c->route_off & B32_ROUTE_WIRE_TILES) && c->cur.wire_fill && c->band_y1 > c->band_y0) {
-            wa.tile_yb = (c->band_y0 / WIRE_TH) * WIRE_TH; wa.tiles_x = (c->width + TILE_W - 1) / TILE_W;
-            wa.tiles_y = (c->band_y1 - wa.tile_yb + WIRE_TH - 1) / WIRE_TH;
-            if ((size_t)wa.tiles_x * wa.tiles_y <= c->cur.cap_wire_tiles) { wa.tile_fill = c->cur.wire_fill; wa.tile_lists = c->cur.wire_lists; c->wire_tile_frames++; }
-        }
-    }
-    if (prof_all) HIPCHK(c, hipEventRecord(ev[0], s));
-    launch_setup(ss, fp, c->scene.d_verts, c->scene.d_faces, c->scene.d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->cur.crecs, c->cur.srecs, c->cur.xrecs }, r.db, c->cur.shades, c->cur.keys0,
-                 r.direct_bin ? nullptr : c->cur.spans /* (direct binning: nobody reads the spans) */, c->cur.partials, c->cur.d_ctrl, c->cur.wire, c->n_cu, pos12, attr12, c->cur.face_of);
-    // The merged draws of a batched frame: the hand-over polled by the fused kernel itself (FillArgs::join_seq) -- their fills are few 16-wave
-    // workgroups (at most 5 / 8 of the CUs: the setup kernel they may have to spin for keeps the rest of the GPU), the setup kernel of draw
-    // k + 1 has normally finished beside draw k's fill and blend pass, and what the cross-stream event cost the main stream per draw (6.5 us
-    // between k_blend's end and the next fill's start: tools/console_trace.sh) was most of what there was to save in a console frame.
-    uint32_t poll_seq = 0, poll_patience = 0;
-    const bool poll_batched = c->pipelined && c->frame_batched && c->join_ok && (r.direct_bin || r.want_inline) && !wire_front && !r.ordered_all &&
-                              ntiles && 8u * ntiles <= 5u * (uint32_t)c->n_cu && !(c->route_off & B32_ROUTE_WIDE_GROUPS);
-    if (poll_batched) {
-        // (b32_debug_inject(ctx, 1) as below: the flag carries another value, the patience is 2 ms)
-        const bool lose_flag = (c->inject & 1u) != 0;
-        c->inject &= ~1u;
+}
+
+// b32_debug_inject(ctx, 1): the next hand-over's flag carries another value and whoever waits for it has a patience of 2 ms -- the "setup
+// kernel never arrived" path.  Taken by one hand-over.
+static bool take_lost_flag(b32_ctx* c) {
+    const bool lose_flag = (c->inject & 1u) != 0;
+    c->inject &= ~1u;
+    return lose_flag;
+}
+
+// The main stream is made to wait for the setup kernel just launched on the side stream, by the hand-over the plan chose (the decision and
+// its measurements: plan_hand_over).  Then the early wire binning, on the side stream behind the setup kernel: the fill does not wait for it.
+// On return everything this frame has on the side stream lies in front of main-stream work.
+static int hand_over(b32_ctx* c, FramePlan& r) {
+    hipStream_t s = c->stream;
+    if (r.hand_over_kind == HandOver::Poll) {          // the fused kernel polls the word itself (FillArgs::join_seq)
+        const bool lose_flag = take_lost_flag(c);
         if (++c->join_seq == 0) c->join_seq = 1;
         launch_flag_poll(c->side, c->cur.d_ctrl, lose_flag ? c->join_seq ^ 0x40000000u : c->join_seq);
-        poll_seq = c->join_seq; poll_patience = lose_flag ? 200000u : 200000000u;
+        r.poll_seq = c->join_seq; r.poll_patience = lose_flag ? PATIENCE_INJECTED_TICKS : PATIENCE_TICKS;
         c->flag_join_frames++; c->poll_join_frames++;
-    } else if (c->pipelined && r.direct_bin && c->join_ok && !c->frame_batched) {
-        // (no cross-stream event on the fill's path: see k_flag / k_join.  The merged runs of a batched frame keep the event: their kernels
-        // are so short that the two extra launches cost what the barrier packet did -- console frame 0.268-0.275 against 0.264-0.265 ms)
-        // (b32_debug_inject(ctx, 1): this frame's flag carries another epoch and the join's patience is 2 ms -- the "setup kernel never arrived" path)
-        const bool lose_flag = (c->inject & 1u) != 0;
-        c->inject &= ~1u;
+    } else if (r.hand_over_kind == HandOver::FlagJoin) {
+        const bool lose_flag = take_lost_flag(c);
         launch_flag(c->side, c->cur.d_ctrl, lose_flag ? c->epoch ^ 0x40000000u : c->epoch);
-        launch_join(s, c->cur.d_ctrl, c->epoch, lose_flag ? 200000u : 200000000u /* 2 s: a last resort -- queues of an oversubscribed GPU are time-sliced in milliseconds */);
+        launch_join(s, c->cur.d_ctrl, c->epoch, lose_flag ? PATIENCE_INJECTED_TICKS : PATIENCE_TICKS);
         c->flag_join_frames++;
-    } else if (c->pipelined) {
+    } else if (r.hand_over_kind == HandOver::Event) {
         hipError_t e1 = hipEventRecord(c->cur.ev_setup, c->side);
         if (e1 == hipSuccess) e1 = hipStreamWaitEvent(s, c->cur.ev_setup, 0);
+        // (the setup kernel is in flight and nothing orders the main stream behind it: wait for it here)
         if (e1 != hipSuccess) { (void)hipStreamSynchronize(c->side); c->last_hip = (int)e1; return B32_E_HIP; }
         c->event_join_frames++;
     }
-    if (c->pipelined && wire_on && wa.tile_fill) {       // (behind ev_setup: the fill does not wait for the binning)
-        launch_wire_bin(c->side, wa, wire_back, wire_front, true);
+    if (c->pipelined && r.wire_on && r.wa.tile_fill) {       // (behind ev_setup: the fill does not wait for the binning)
+        launch_wire_bin(c->side, r.wa, r.wire_back, r.wire_front, true);
         // (back-face edges: the first wire kernel on the main stream, k_wire_table_clear, looks at Events::wbin_done itself -- no event
         // for the main stream to wait for; the overlay alone has no such kernel in front of k_wire_tile and keeps the event)
-        if (wire_back) { launch_flag_wbin(c->side, c->cur.d_ctrl, wa.epoch); wire_polled = true; }
+        if (r.wire_back) { launch_flag_wbin(c->side, c->cur.d_ctrl, r.wa.epoch); r.wire_polled = true; }
         else HIPCHK(c, hipEventRecord(c->ev_wbin, c->side));
-        wire_binned = true;
+        r.wire_binned = true;
     }
     c->cur.in_flight = true;
-    if (prof_all) HIPCHK(c, hipEventRecord(ev[1], s));
+    if (r.prof_all) HIPCHK(c, hipEventRecord(r.ev[1], s));
+    return B32_OK;
+}
 
-    // ---- tile lists
-    int cur = 0;
-    if (r.direct_bin) {
-        if (prof_all) HIPCHK(c, hipEventRecord(ev[2], s));
-        r.prio64 = true;
-    } else if (r.want_inline) {
-        const size_t need = (size_t)ntiles * r.list_stride + 64;
-        if (need > c->cap_inline) {
-            if ((rc = ensure_plain(c, c->inline_lists, need + need / 2))) return rc;
-            c->cap_inline = need + need / 2;
-        }
-        if (prof_all) HIPCHK(c, hipEventRecord(ev[2], s));
-        r.prio64 = r.inline_bin = true;
-    } else if (r.want_prio64) {
-        if (prof_all) HIPCHK(c, hipEventRecord(ev[2], s));
-        r.prio64 = launch_bin_spans(s, fp, c->cur.spans, r.with_class ? c->cur.keys0 : nullptr, c->cur.partials, c->cur.d_ctrl, sc, (uint32_t)c->cap_pairs, c->ranges,
-                                    c->tile_mid, BLEND_SORT_CAP, c->pvals[0]);
-    }
-    if (!r.prio64 && (rc = bin_keyed(c, fp, r, sc, prof_all ? ev[2] : nullptr, cur))) return rc;
+// The tile lists the fill reads.  Direct and inline binning launch nothing here (k_setup and the fused kernel build them); a sort-free frame
+// that is neither bins its spans with a counting sort, and falls back to the keyed pipelines when that does not apply.
+static int tile_lists(b32_ctx* c, const FrameParams& fp, const SortScratch& sc, FramePlan& r) {
+    hipStream_t s = c->stream;
+    int rc;
+    if (r.prof_all && r.want_prio64) HIPCHK(c, hipEventRecord(r.ev[2], s));
+    if (r.want_prio64 && !r.prio64)
+        r.set_prio64(launch_bin_spans(s, fp, c->cur.spans, r.with_class ? c->cur.keys0 : nullptr, c->cur.partials, c->cur.d_ctrl, sc, (uint32_t)c->cap_pairs, c->ranges,
+                                      c->tile_mid, BLEND_SORT_CAP, c->pvals[0]));
+    if (!r.prio64 && (rc = bin_keyed(c, fp, r, sc, r.prof_all ? r.ev[2] : nullptr))) return rc;
     c->routes[r.direct_bin ? 0 : r.inline_bin ? 1 : r.prio64 ? 2 : 3]++;
     // (direct binning with regions that hold the whole mesh, and no more faces that can be transparent than k_blend sorts per tile:
     // nothing can overflow)
     const bool direct_safe = r.direct_bin && r.db.cap_opaque >= c->scene.nf && (!r.with_class || c->scene.blend_faces <= BLEND_SORT_CAP);
     c->pending_may_redraw = !(r.inline_bin || direct_safe);
-    if (prof_fill) HIPCHK(c, hipEventRecord(ev[3], s));
+    if (r.prof_fill) HIPCHK(c, hipEventRecord(r.ev[3], s));
+    return B32_OK;
+}
 
-    // ---- coverage, shading, transparent pass
-    FillArgs fa = fill_args(c, fp, r, cur, wire_front);
+// coverage, shading, transparent pass: the fill's arguments, the words it publishes and polls, a deferred clear, the launch
+static int fill(b32_ctx* c, const FrameParams& fp, FramePlan& r) {
+    const bool fused = r.fused;
+    int rc;
+    FillArgs fa = fill_args(c, fp, r);
     if (++c->fill_seq == 0) c->fill_seq = 1;
-    fa.start_seq = c->fill_seq;
-    fa.join_seq = poll_seq; fa.join_patience = poll_patience;
-    const uint32_t start_seq_meant = fa.start_seq;
-    if ((c->inject & 2u) && fa.prio64 && !wire_front && !r.ordered_all && ntiles) { c->inject &= ~2u; fa.start_seq = 0; c->start_lost = true; }    // (fault injection: see b32_debug_inject)
+    fa.start_seq = r.start_seq = c->fill_seq;
+    fa.join_seq = r.poll_seq; fa.join_patience = r.poll_patience;
+    if ((c->inject & 2u) && fused && r.ntiles) { c->inject &= ~2u; fa.start_seq = 0; c->start_lost = true; }    // (fault injection: see b32_debug_inject)
     // Which kernel of the frame says "started": the fused kernel -- or, when the frame has a transparent pass, that pass (k_blend, the next
     // kernel on the main stream).  The next frame's setup kernel is released by that word, i.e. it then runs beside the blend kernel and the
     // fill has the GPU to itself: C3 with 10 % transparent faces 0.227 -> 0.192 ms per frame, the same in z-buffer mode 0.264 -> 0.222 (the fill
@@ -593,34 +612,75 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     // default() in that role: 0.284 -> 0.331 -- its setup kernel is the long one and then starts too late; not done.
     // Only frames that fill the GPU (more tiles than workgroup slots): a console-sized draw leaves most CUs idle anyway and its setup kernel is
     // a chain of round trips that wants to start as early as it may (12-room console frame with the deferral: 0.171 -> 0.213 ms).
-    fa.start_defer = (fa.prio64 && !wire_front && !r.ordered_all && ntiles > 2u * (uint32_t)c->n_cu && fa.gather_blend) ? 1u : 0u;
+    fa.start_defer = (fused && r.ntiles > 2u * (uint32_t)c->n_cu && fa.gather_blend) ? 1u : 0u;
     // a deferred Framebuffer::clear: folded into this frame's fused kernel when that kernel is the one that runs, the frame has no
     // depth buffer to reset and the clear was issued for this very band; else the clear launches go first
     if (c->clear_pending) {
         // (a frame with a depth buffer to reset: only in z-buffer mode, where the fused kernel owns the depth buffer too -- it seeds its
         // winners with f32::MAX instead of reading the buffer and writes f32::MAX where nothing is drawn)
         const bool has_z = c->zbuf && c->zbuf_valid;
-        if (r.prio64 && !wire_front && !r.ordered_all && (!has_z || fp.zmode) && c->scene.nf && ntiles && c->clear_y0 == c->band_y0 && c->clear_y1 == c->band_y1) {
+        if (fused && (!has_z || fp.zmode) && c->scene.nf && r.ntiles && c->clear_y0 == c->band_y0 && c->clear_y1 == c->band_y1) {
             fa.clear_on = 1; fa.clear_rgba = c->clear_rgba; fa.clear_depth = (has_z && fp.zmode) ? 1u : 0u; c->clear_pending = false;
         } else if ((rc = flush_clear(c))) return rc;
     }
-    if (fa.atlas_idx_bytes && !wire_front && !r.ordered_all) c->lds_atlas_frames++;
-    if (fa.span_cover && !wire_front && !r.ordered_all) c->span_cover_frames++;
-    launch_fill(s, fa, c->n_cu, prof_fill ? ev[4] : nullptr);
+    if (fa.atlas_idx_bytes && fused) c->lds_atlas_frames++;
+    if (fa.span_cover && fused) c->span_cover_frames++;
+    launch_fill(c->stream, fa, c->n_cu, r.prof_fill ? r.ev[4] : nullptr);
+    return B32_OK;
+}
 
-    // ---- wireframe phases
-    if (wire_on) {
-        if (wire_binned && !wire_polled) HIPCHK(c, hipStreamWaitEvent(s, c->ev_wbin, 0));
-        launch_wire(s, wa, wire_back, wire_front, wire_binned, wire_polled ? c->cur.d_ctrl : nullptr, wa.epoch);
-    }
-    if (prof_fill) { if (prof_all) HIPCHK(c, hipEventRecord(ev[5], s)); c->ev_frames++; }
-    c->last_cover_tiles = (r.prio64 && !wire_front && !r.ordered_all) ? ntiles : 0u;
-    c->last_cover_groups = std::min<uint32_t>(ntiles, (uint32_t)c->n_cu * 2u);
-    {   // remembered per frame set
-        b32_ctx::CoverOf* slot = &c->cover_of[0];
-        for (auto& co : c->cover_of) { if (co.ctrl == c->cur.d_ctrl) { slot = &co; break; } if (!co.ctrl) slot = &co; }
-        *slot = { c->cur.d_ctrl, c->last_cover_tiles, c->last_cover_groups, c->last_cover_tiles ? start_seq_meant : 0u };
-    }
+// the wireframe phases on the main stream (behind the early binning of a pipelined frame), and the end of the frame's profiling row
+static int wire_phases(b32_ctx* c, FramePlan& r) {
+    hipStream_t s = c->stream;
+    if (r.wire_on && r.wire_binned && !r.wire_polled) HIPCHK(c, hipStreamWaitEvent(s, c->ev_wbin, 0));
+    if (r.wire_on) launch_wire(s, r.wa, r.wire_back, r.wire_front, r.wire_binned, r.wire_polled ? c->cur.d_ctrl : nullptr, r.wa.epoch);
+    if (r.prof_all) HIPCHK(c, hipEventRecord(r.ev[5], s));
+    if (r.prof_fill) c->ev_frames++;
+    return B32_OK;
+}
+
+// What the gates of the frames that follow need to know about this frame's fused kernel, per frame set (keyed by its control block): its
+// tile count (0: it launched none), its workgroups, the start word it was meant to publish.
+static void remember_cover(b32_ctx* c, const FramePlan& r) {
+    const uint32_t tiles = r.fused ? r.ntiles : 0u;
+    b32_ctx::CoverOf* slot = &c->cover_of[0];
+    for (auto& co : c->cover_of) { if (co.ctrl == c->cur.d_ctrl) { slot = &co; break; } if (!co.ctrl) slot = &co; }
+    *slot = { c->cur.d_ctrl, tiles, std::min<uint32_t>(r.ntiles, (uint32_t)c->n_cu * 2u), tiles ? r.start_seq : 0u };
+}
+
+// One frame on the GPU: called by the drop-in calls, the resident scenes, every draw of a batched frame and every redraw.
+int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog) {
+    FramePlan r;
+    r.wire_back = st->backface_cull && st->backface_wireframe;      // render.rs:2577
+    r.wire_front = st->wireframe_overlay != 0;                       // render.rs:2603 (an empty list draws nothing either way)
+    FrameParams fp = frame_params(c, cam, st, fog, r.wire_back || r.wire_front);
+    LightSet lset{};
+    r.prof_fill = c->profile_level >= 1 && (c->prof_seq++ % c->prof_stride) == 0;
+    r.prof_all = r.prof_fill && c->profile_level >= 2;
+    int rc;
+    // ---- everything that can fail without a trace: buffers, the plan, the stream order.  A return in here puts the frame sets back.
+    SetsGuard sets(c);
+    if ((rc = choose_frame_set(c, r, sets))) return rc;
+    if ((rc = frame_lights(c, st, fp, lset))) return rc;
+    if ((rc = frame_buffers(c, fp, r.wire_back))) return rc;
+    if ((rc = profiling_row(c, r))) return rc;
+    const SortScratch sc{ c->block_hist, c->hist_blocks, c->digit_total };
+    if ((rc = plan_route(c, fp, sc, r))) return rc;
+    plan_pipeline(c, fp, r);
+    if ((rc = reset_ctrl_of_empty_frame(c))) return rc;
+    if ((rc = frame_positions(c, fp, r.pos12, r.attr12))) return rc;
+    if ((rc = order_side_stream(c, r))) return rc;
+    wire_args(c, fp, r);
+    if (r.prof_all) HIPCHK(c, hipEventRecord(r.ev[0], c->stream));
+    // ---- transform, cull, setup (+ tile binning of large meshes): from here on the frame is in flight in the set it rotated to
+    sets.dismiss();
+    launch_setup(r.setup_stream, fp, c->scene.d_verts, c->scene.d_faces, c->scene.d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->cur.crecs, c->cur.srecs, c->cur.xrecs }, r.db, c->cur.shades, c->cur.keys0,
+                 r.direct_bin ? nullptr : c->cur.spans /* (direct binning: nobody reads the spans) */, c->cur.partials, c->cur.d_ctrl, c->cur.wire, c->n_cu, r.pos12, r.attr12, c->cur.face_of);
+    if ((rc = hand_over(c, r))) return rc;
+    if ((rc = tile_lists(c, fp, sc, r))) return rc;
+    if ((rc = fill(c, fp, r))) return rc;
+    if ((rc = wire_phases(c, r))) return rc;
+    remember_cover(c, r);
     HIPCHK(c, hipGetLastError());
     return B32_OK;
 }
@@ -681,6 +741,16 @@ static void collect_events(b32_ctx* c) {
     c->ev_frames = 0;
 }
 
+// The pending frame drew nothing (it reported what it ran out of): the same frame again, counted under b32_route_count(route_index).
+static int redraw_pending(b32_ctx* c, int route_index) {
+    c->routes[route_index]++;
+    c->ev_frames = 0;                                  // the aborted frame must not enter the phase averages
+    c->redrawing = true;
+    const int rc = enqueue_frame(c, &c->last_cam, &c->last_settings, c->last_has_fog ? &c->last_fog : nullptr);
+    c->redrawing = false;
+    return rc;
+}
+
 int b32_frame_finish(b32_ctx* c, B32Timings* out) {
     if (!c) return B32_E_ARG;
     (void)hipSetDevice(c->device);
@@ -724,11 +794,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
             // longest list it reported (enqueue_frame falls back to the compact counting sort if those would not fit)
             c->scene.direct_cap_opaque = c->h_ctrl.list_demand + c->h_ctrl.list_demand / 4 + 64;
             if (no_redraw) break;
-            c->routes[4]++;
-            c->ev_frames = 0;
-            c->redrawing = true;
-            const int rc = enqueue_frame(c, &c->last_cam, &c->last_settings, c->last_has_fog ? &c->last_fog : nullptr);
-            c->redrawing = false;
+            const int rc = redraw_pending(c, 4);
             if (rc) return rc;
             continue;
         }
@@ -737,11 +803,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
             // this scene) with the global depth sort
             c->scene.local_sort_ok = false;
             if (no_redraw) break;
-            c->routes[5]++;
-            c->ev_frames = 0;
-            c->redrawing = true;
-            const int rc = enqueue_frame(c, &c->last_cam, &c->last_settings, c->last_has_fog ? &c->last_fog : nullptr);
-            c->redrawing = false;
+            const int rc = redraw_pending(c, 5);
             if (rc) return rc;
             continue;
         }
@@ -752,12 +814,7 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
         for (int i = 0; i < 2; ++i) { if ((rc = ensure_plain(c, c->pkeys[i], n))) return rc; if ((rc = ensure_plain(c, c->pvals[i], n))) return rc; }
         c->cap_pairs = n;
         if (no_redraw) break;
-        c->routes[6]++;
-        c->ev_frames = 0;                              // the aborted frame must not enter the phase averages
-        c->redrawing = true;
-        rc = enqueue_frame(c, &c->last_cam, &c->last_settings, c->last_has_fog ? &c->last_fog : nullptr);
-        c->redrawing = false;
-        if (rc) return rc;
+        if ((rc = redraw_pending(c, 6))) return rc;
     }
     c->frame_pending = false;
     c->pending_superseded = false;

@@ -8,6 +8,7 @@
 //   b32_batch.hip  b32_frame_begin / _add_scene / _end (merged runs)
 #pragma once
 #include "b32_device.h"
+#include "b32_frame_plan.h"
 #include <algorithm>
 #include <cstdio>
 #include <chrono>
@@ -165,9 +166,8 @@ struct b32_ctx {
     uint32_t join_seq = 0;               // FillArgs::join_seq of the last polled hand-over (never 0)
     uint32_t fill_seq = 0;               // FillArgs::start_seq of the last fused kernel launched (never 0)
     bool pipe_hint = true;               // the previous frame's route could use the second frame set
-    struct CoverOf { const Ctrl* ctrl; uint32_t tiles, groups, seq; } cover_of[3] = {};   // the same per frame set (keyed by its control block): the gate polls the
-                                                                                      // cursor of the frame n_sets - 1 back, whose grid may differ from the previous frame's
-    uint32_t last_cover_tiles = 0, last_cover_groups = 0;   // tile count / workgroups of the previous frame's fused kernel (0: it had none)
+    struct CoverOf { const Ctrl* ctrl; uint32_t tiles, groups, seq; } cover_of[3] = {};   // the last fused kernel of each frame set (keyed by its control block; tiles 0: the set's last
+                                                                                      // frame had none), written by remember_cover: the gate polls the cursor of the frame n_sets - 1 back
     bool pipelined = false;              // the frame being enqueued runs its k_setup on the side stream
     unsigned long long pipelined_frames = 0;
     unsigned long long flag_join_frames = 0, event_join_frames = 0, poll_join_frames = 0;    // ... handed over to the fill by k_flag / k_join, or by a cross-stream event

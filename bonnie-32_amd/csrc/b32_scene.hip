@@ -342,9 +342,10 @@ int b32_scene_set_rig(b32_ctx* c, b32_scene* slot, const uint16_t* bone_of_verte
 }
 // Order against the side stream (DESIGN.md section 7d has the full argument).  Two kernels read a scene's vertices or what was derived
 // from them there: k_setup of a pipelined frame (the vertices) and the early k_wire_bin (the wire list k_setup wrote, not the vertices).
-// enqueue_frame never returns before the main stream has been made to wait for that k_setup -- by ev_setup, by k_join, or by the fused
-// kernel that polls the hand-over itself -- and launches the wire kernels, which wait for k_wire_bin (ev_wbin or the polled word), on the
-// main stream before it returns.  So everything on the side stream that a pose could overtake is in front of main-stream work enqueued
+// enqueue_frame's hand_over step, the call right behind launch_setup, makes the main stream wait for that k_setup -- by ev_setup, by
+// k_join, or by the fused kernel that polls the hand-over itself (where the event cannot be recorded it drains the side stream before it
+// returns the error) -- and its wire_phases step launches the wire kernels, which wait for k_wire_bin (ev_wbin or the polled word), on
+// the main stream; no return lies between launch_setup and hand_over.  So everything on the side stream that a pose could overtake is in front of main-stream work enqueued
 // earlier, and the pose, enqueued on the main stream, needs no event of its own.  The other direction is side_dirty: the next pipelined
 // k_setup waits for the main stream as it stands after the pose.
 int b32_scene_pose(b32_ctx* c, b32_scene* slot, const B32Bone* bones, uint32_t n_bones) {

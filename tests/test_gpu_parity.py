@@ -757,6 +757,99 @@ def test_streams_of_one_priority_hand_over_by_event(oracle):
         hip.hipStreamDestroy(stream)
 
 
+# Route-counter deltas of test_route_census_of_a_fixed_frame_sequence, group by group (counters that did not move are left out).  Recorded
+# by running this test body on the commit BEFORE enqueue_frame was split into steps (profiles/frame_plan_refactor.md), on 256 CUs.
+CENSUS_CUS = 256
+CENSUS = {
+    "small": {"inline_bin": 1},
+    "large": {"direct_bin": 3, "pipelined": 2, "flag_join": 2},
+    "large-narrow": {"direct_bin": 3, "pipelined": 2, "flag_join": 2},
+    "batched": {"direct_bin": 3, "pipelined": 2, "flag_join": 2, "poll_join": 2},      # (a polled hand-over counts under flag_join too)
+    "wire": {"direct_bin": 3, "pipelined": 2, "wire_tiles": 3, "flag_join": 2},
+    "clear": {"direct_bin": 1},
+    "keyed": {"keyed": 2, "redraw_pairs": 1},      # (the first keyed frame of the context outgrows its pair buffers and is redrawn)
+}
+
+
+def test_route_census_of_a_fixed_frame_sequence(oracle):
+    """Every route draws the same pixels, and the other tests assert the route counters with `>=`: a frame sent down a neighbouring route
+    would pass them.  One context on its own stream, a fixed sequence of 320x240 frames that reaches each branch of the frame's plan -- inline
+    binning; direct binning with the flag / join hand-over of small frames, with and without the 16-wave form; the polled hand-over of a batched
+    frame; wire binning on the side stream; a folded clear; the keyed route -- and after each group the EXACT delta of every counter of
+    route_counts(), against the values the commit before the split gave; every frame bit for bit against the oracle."""
+    import torch
+    from bonnie32_amd import rasterizer as R
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count        # (b32_device_constants does not export it)
+    if n_cu != CENSUS_CUS:
+        pytest.skip(f"the census was recorded on {CENSUS_CUS} CUs, this device has {n_cu}: the routes depend on the count")
+    small = scenegen.make_scene("C1", n_tris=300, seed=61)
+    large = scenegen.make_scene("C2", n_tris=9000, seed=62)
+    wired = copy.copy(large); wired.settings = copy.copy(large.settings)
+    wired.settings.backface_cull = True; wired.settings.backface_wireframe = True
+    rooms = [scenegen.make_scene("C1", n_tris=1500, seed=63 + i, variant="blend" if i == 2 else "gouraud", bbox_px=400.0) for i in range(3)]
+    room_st = b32.RasterSettings.game()
+    room_st.lights = [b32.Light.directional((-1.0, -1.0, -1.0), 0.7), b32.Light.point((0.0, -100.0, 1500.0), 3000.0, 1.2)]
+    room_cam = b32.Camera(position=(15.0, -10.0, -40.0))
+    room_clear = b32.Color(10, 10, 30)
+    W, H = small.width, small.height
+    ofb = oracle.Framebuffer(W, H); ofb.clear(room_clear)
+    for sc in rooms:
+        assert oracle.render_mesh_15(ofb, sc.vertices, sc.faces, sc.textures, room_cam, room_st, None)[0] == 0
+    want = {"small": cpu_render(oracle, small)[0], "large": cpu_render(oracle, large)[0], "wire": cpu_render(oracle, wired)[0], "rooms": ofb.pixels}
+
+    ctx = R.Context(0); ctx.set_async_depth(1)
+    fb = R.Framebuffer(W, H, ctx)
+    rs_small = R.ResidentScene(fb, small.vertices, small.faces, small.textures).detach()
+    rs_large = R.ResidentScene(fb, large.vertices, large.faces, large.textures).detach()
+    slots = [R.ResidentScene(fb, sc.vertices, sc.faces, sc.textures).detach() for sc in rooms]
+    seen = {}
+    last = ctx.route_counts()
+
+    def group(name, key):
+        nonlocal last
+        got = fb.pixels
+        assert np.array_equal(got, want[key]), f"{name}: {int((got != want[key]).sum())} bytes differ from the oracle"
+        now = ctx.route_counts()
+        seen[name] = {k: now[k] - last[k] for k in now if now[k] != last[k]}
+        print(f"census {name}: {seen[name]}")
+        last = now
+
+    def three(rs, sc):                                        # three frames with the finish deferred: the second and third may run two in flight
+        for _ in range(3):
+            fb.clear(sc.clear_color); rs.render_async(sc.camera, sc.settings, sc.fog)
+        rs.finish()
+    try:
+        fb.clear(small.clear_color); rs_small.render(small.camera, small.settings, small.fog)
+        group("small", "small")
+        three(rs_large, large)
+        group("large", "large")
+        ctx.set_routes(R.Context.ROUTE_WIDE_GROUPS)
+        three(rs_large, large)
+        group("large-narrow", "large")
+        ctx.set_routes(0)
+        for _ in range(3):
+            fb.clear(room_clear)
+            ctx.frame_begin(room_cam, room_st)
+            for rs in slots:
+                ctx.frame_add(rs)
+            ctx.frame_end()
+        ctx.finish()
+        group("batched", "rooms")
+        three(rs_large, wired)
+        group("wire", "wire")
+        fb.clear(b32.Color(200, 10, 10)); fb.clear(large.clear_color)
+        rs_large.render(large.camera, large.settings, large.fog)
+        group("clear", "large")
+        ctx.set_routes(R.Context.ROUTE_SORT_FREE)
+        fb.clear(large.clear_color); rs_large.render(large.camera, large.settings, large.fog)
+        group("keyed", "large")
+    finally:
+        for rs in slots + [rs_small, rs_large]:
+            rs.close()
+        ctx.close()
+    assert seen == CENSUS, seen
+
+
 def test_superseded_frame_is_not_redrawn_over_an_executed_clear(oracle):
     """ADVICE r5 (b32_frame.hip): draw A (overflows its tile regions on a fresh context: nothing drawn), b32_fb_clear (safe mode marks A
     superseded, the clear stays deferred), b32_synchronize (flushes the clear WITHOUT settling: it now sits behind A on the stream), draw
