@@ -442,14 +442,33 @@ def draw_line(img, width, height, e, rgb, zb, depth_test):
     img[ys, xs, 0], img[ys, xs, 1], img[ys, xs, 2], img[ys, xs, 3] = rgb[0], rgb[1], rgb[2], 255
 
 
-def _tap_record(tap, s, px, py, texel, vert, mod, shade, m, dithered, back):
+def _tap_record(tap, s, px, py, texel, vert, mod, shade, m, dithered, back, addr=None):
     """The per-pixel tap of render_mesh_15 / render_mesh: for every pixel the surface stored, its position, the sampled texel (a Color15, or
     the four bytes of a Color), the three interpolated vertex-colour bytes `vert`, tex8 * vert / 128 clamped (`mod`), the shade factors
     (None on an unlit frame), the three values `m` that go into the dither / quantisation step, whether that step dithers, and the
-    framebuffer bytes the store read."""
+    framebuffer bytes the store read.  Texture addressing (see _tap_address): the barycentrics, the interpolated `u` and `v` (before the
+    flip), the texel column `tx` and row `ty` of every stored pixel, and the same for every pixel inside the triangle before the
+    transparency rule (`in_*`); `sv` / `suv` are the surface's screen vertices and texture coordinates."""
     tap.append(dict(face=s["face"], x=px.copy(), y=py.copy(), texel=np.array(texel), vert=np.stack(vert, axis=1), mod=np.stack(mod, axis=1),
                     shade=None if shade is None else np.stack(shade, axis=1), m=np.stack(m, axis=1), dithered=bool(dithered), back=back.copy(),
-                    blend=s["blend"], alpha=s["alpha"]))
+                    blend=s["blend"], alpha=s["alpha"], **(addr or {})))
+
+
+def _tap_address(s, bc, uvt, inside, ys, xs, min_x, min_y):
+    """The addressing part of a tap record.  bc: the three barycentric grids; uvt: None (untextured), or (u, v, tx, ty) grids with
+    tx = ty = None for a texture without texels; inside: the coverage grid before the texel rule and the depth test of the store."""
+    iy, ix = np.nonzero(inside)
+    out = dict(bcx=bc[0][ys, xs], bcy=bc[1][ys, xs], bcz=bc[2][ys, xs], sv=np.array(s["v"], np.float32), suv=np.array(s["uv"], np.float32),
+               in_x=ix + min_x, in_y=iy + min_y, in_bcx=bc[0][iy, ix], in_bcy=bc[1][iy, ix], in_bcz=bc[2][iy, ix])
+    for k in ("u", "v", "tx", "ty", "in_tx", "in_ty"):
+        out[k] = None
+    if uvt is not None:
+        u, v, tx, ty = uvt
+        out["u"], out["v"] = u[ys, xs], v[ys, xs]
+        none = lambda n: np.full(n, -1, np.int64)
+        out["tx"], out["ty"] = (none(len(ys)), none(len(ys))) if tx is None else (tx[ys, xs], ty[ys, xs])
+        out["in_tx"], out["in_ty"] = (none(len(iy)), none(len(iy))) if tx is None else (tx[iy, ix], ty[iy, ix])
+    return out
 
 
 def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False, tap=None):
@@ -510,6 +529,7 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False, tap=None)
             with np.errstate(divide="ignore", invalid="ignore"):
                 u = (over_z(0) / inv_z).astype(np.float32)
                 v = (over_z(1) / inv_z).astype(np.float32)
+        uvt = (u, v, None, None)
         if tex.width == 0 or tex.height == 0 or tex.pixels.size == 0:
             texel = np.zeros(u.shape, np.int64)
         else:                                                                                         # types.rs:671-681
@@ -520,8 +540,11 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False, tap=None)
             tx = wrapc(u, tex.width)
             ty = wrapc((f32(1.0) - v).astype(np.float32), tex.height)
             texel = tex.pixels.astype(np.int64)[ty * tex.width + tx]
+            uvt = (u, v, tx, ty)
     else:
         texel = np.full(bcx.shape, K("color15.white"), np.int64)
+        uvt = None
+    inside_cov = inside
     black = (texel & ~K("color15.semi_bit") & 0xFFFF) == 0
     if s["black_tr"]:
         drawn = inside & ~black                                                                       # :1592-1608
@@ -571,7 +594,8 @@ def _rasterize(img, width, height, s, st, zb=None, skip_z_write=False, tap=None)
     front = np.stack([expand5(q[0]), expand5(q[1]), expand5(q[2])], axis=1)                           # Color15::r8 etc.
     back = img[py, px, :3].astype(np.int64)
     if tap is not None:
-        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, out5, needs_dither, back)
+        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, out5, needs_dither, back,
+                    _tap_address(s, (bcx, bcy, bcz), uvt, inside_cov, ys, xs, min_x, min_y))
     mode, alpha = s["blend"], s["alpha"]
     do_blend = semi & (mode != 0)
     ps1 = np.where(do_blend[:, None], blend555(front, back, mode), front)
@@ -653,6 +677,7 @@ def _rasterize8(img, width, height, s, st, zb=None, tap=None):
             with np.errstate(divide="ignore", invalid="ignore"):
                 u = (over_z(0) / inv_z).astype(np.float32)
                 v = (over_z(1) / inv_z).astype(np.float32)
+        uvt = (u, v, None, None)
         if tex.width == 0 or tex.height == 0 or tex.pixels.size == 0:
             texel = np.zeros(u.shape + (4,), np.int64); texel[..., 3] = 5
         else:
@@ -663,8 +688,11 @@ def _rasterize8(img, width, height, s, st, zb=None, tap=None):
             tx = wrapc(u, tex.width)
             ty = wrapc((f32(1.0) - v).astype(np.float32), tex.height)
             texel = tex.pixels.astype(np.int64)[ty * tex.width + tx]
+            uvt = (u, v, tx, ty)
     else:
         texel = np.zeros(bcx.shape + (4,), np.int64); texel[..., :3] = 255                            # Color::WHITE
+        uvt = None
+    inside_cov = inside
     drawn = inside & (texel[..., 3] != 5)                                                             # is_transparent :1348
     if s["alpha"] == 0:
         return 0
@@ -703,7 +731,8 @@ def _rasterize8(img, width, height, s, st, zb=None, tap=None):
     front = np.stack(cols, axis=1).astype(np.int64)
     back = img[py, px, :3].astype(np.int64)
     if tap is not None:
-        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, t_m, needs_dither, back)
+        _tap_record(tap, s, px, py, tx_, t_vert, t_mod, t_shade or None, t_m, needs_dither, back,
+                    _tap_address(s, (bcx, bcy, bcz), uvt, inside_cov, ys, xs, min_x, min_y))
     mode = tx_[:, 3]
     ps1 = front.copy()
     a_out = np.full(len(ys), 255, np.int64)
