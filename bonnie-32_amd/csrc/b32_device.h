@@ -426,9 +426,33 @@ struct DirectBin {
 void launch_merge_mesh(hipStream_t s, const B32Vertex* sv, uint32_t nv, const B32Face* sf, uint32_t nf, uint32_t nt, B32Vertex* dv, B32Face* df,
                        uint32_t vbase, uint32_t tbase, uint32_t mesh);
 void launch_offset_tex(hipStream_t s, const TexDesc* src, uint32_t nt, TexDesc* dst, uint32_t texel_base);
-void launch_setup(hipStream_t s, const FrameParams& fp, const B32Vertex* verts, const B32Face* faces, const TexDesc* tex,
-                  const B32Light* lights, const LightSet& inline_lights, const MeshTable& mesh_table, const PlaceTable& place_table, RecArrays recs, const DirectBin& direct, float* shades, uint32_t* keys, uint32_t* spans,
-                  uint32_t* partials, Ctrl* ctrl, WireTri* wire, int n_cu, const float* pos12, const float* attr12, uint32_t* face_of);
+// Everything k_setup receives, by value in the kernel arguments (2136 bytes of the 4096 a launch may carry).  The buffers are a struct
+// of their own, which the kernel copies into registers as it starts.
+struct SetupBuffers {
+    const B32Vertex* verts;     // full 36-byte vertices (read when pos12 == nullptr, and for the normals of a lit frame)
+    const B32Face* faces;
+    const TexDesc* tex;
+    const B32Light* lights;     // the frame's lights in memory (read unless fp.lights_inline; else SetupArgs::lset)
+    RecArrays recs;
+    DirectBin db;
+    float* shades;              // [slot][9], written when fp.shading != B32_SHADE_NONE
+    uint32_t* keys;             // painter's key per record slot
+    uint32_t* spans;            // packed tile span per record slot; nullptr with direct binning (nobody reads them)
+    uint32_t* partials;         // [block][8]: the block's counters
+    Ctrl* ctrl;
+    WireTri* wire;              // per face, written when fp.wire_collect
+    const float* pos12;         // packed streams of a resident mesh (nullptr: full vertices): positions ...
+    const float* attr12;        // ... and attributes
+    uint32_t* face_of;          // record slot -> face id (b32_last_draw_order); may be nullptr
+};
+struct SetupArgs {
+    FrameParams fp;
+    SetupBuffers buf;
+    LightSet lset;              // up to LIGHTS_INLINE lights by value
+    MeshTable mtab;             // per-mesh rows of a batched frame
+    PlaceTable ptab;            // placements (read when fp.placed)
+};
+void launch_setup(hipStream_t s, const SetupArgs& a);
 void launch_gate(hipStream_t s, Ctrl* prev, uint32_t need, uint32_t patience_ticks, uint32_t start_seq, Ctrl* mine, uint32_t start_patience_ticks = 200000000u);
 void launch_flag(hipStream_t s, Ctrl* ctrl, uint32_t epoch);
 void launch_flag_poll(hipStream_t s, Ctrl* ctrl, uint32_t seq);        // Events::poll_done = seq, behind the setup kernel of a polled hand-over

@@ -533,6 +533,20 @@ static void wire_args(b32_ctx* c, const FrameParams& fp, FramePlan& r) {
     }
 }
 
+// the setup kernel's arguments: the resident scene, the frame's lights and tables, and the frame set it writes
+static SetupArgs setup_args(const b32_ctx* c, const FrameParams& fp, const FramePlan& r, const LightSet& lset) {
+    SetupArgs a{};
+    a.fp = fp; a.lset = lset; a.mtab = c->frame_table; a.ptab = c->frame_places;
+    SetupBuffers& b = a.buf;
+    b.verts = c->scene.d_verts; b.faces = c->scene.d_faces; b.tex = c->scene.d_tex; b.lights = c->d_lights;
+    b.recs = RecArrays{ c->cur.crecs, c->cur.srecs, c->cur.xrecs }; b.db = r.db;
+    b.shades = c->cur.shades; b.keys = c->cur.keys0;
+    b.spans = r.direct_bin ? nullptr : c->cur.spans;      // (direct binning: nobody reads the spans)
+    b.partials = c->cur.partials; b.ctrl = c->cur.d_ctrl; b.wire = c->cur.wire;
+    b.pos12 = r.pos12; b.attr12 = r.attr12; b.face_of = c->cur.face_of;
+    return a;
+}
+
 // b32_debug_inject(ctx, 1): the next hand-over's flag carries another value and whoever waits for it has a patience of 2 ms -- the "setup
 // kernel never arrived" path.  Taken by one hand-over.
 static bool take_lost_flag(b32_ctx* c) {
@@ -674,8 +688,7 @@ int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const
     if (r.prof_all) HIPCHK(c, hipEventRecord(r.ev[0], c->stream));
     // ---- transform, cull, setup (+ tile binning of large meshes): from here on the frame is in flight in the set it rotated to
     sets.dismiss();
-    launch_setup(r.setup_stream, fp, c->scene.d_verts, c->scene.d_faces, c->scene.d_tex, c->d_lights, lset, c->frame_table, c->frame_places, RecArrays{ c->cur.crecs, c->cur.srecs, c->cur.xrecs }, r.db, c->cur.shades, c->cur.keys0,
-                 r.direct_bin ? nullptr : c->cur.spans /* (direct binning: nobody reads the spans) */, c->cur.partials, c->cur.d_ctrl, c->cur.wire, c->n_cu, r.pos12, r.attr12, c->cur.face_of);
+    launch_setup(r.setup_stream, setup_args(c, fp, r, lset));
     if ((rc = hand_over(c, r))) return rc;
     if ((rc = tile_lists(c, fp, sc, r))) return rc;
     if ((rc = fill(c, fp, r))) return rc;

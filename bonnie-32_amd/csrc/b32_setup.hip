@@ -128,7 +128,7 @@ __device__ float acosf_musl(float x) {
 }
 
 // shade_multi_light_color, render.rs:1013-1071
-__device__ void shade_multi(V3 normal, V3 world_pos, const B32Light* lights, uint32_t n_lights, float ambient, float out[3]) {
+__device__ __forceinline__ void shade_multi(V3 normal, V3 world_pos, const B32Light* lights, uint32_t n_lights, float ambient, float out[3]) {
     float tr = ambient, tg = ambient, tb = ambient;
     for (uint32_t i = 0; i < n_lights; ++i) {
         const B32Light& l = lights[i];
@@ -215,7 +215,8 @@ __device__ __forceinline__ uint32_t agg_position(const AggSlot& g) {
 }
 
 // ---------------------------------------------------------------- k_setup
-// SETUP_FPT = faces per thread (1 everywhere today: registers, i.e. waves per SIMD, are worth more than loads issued ahead)
+// One face per lane: registers, i.e. waves per SIMD, are worth more than loads issued ahead (two faces per thread was 73 VGPRs and 43 us
+// against 39 at 1 M faces; three was 49 us).
 // PLAIN = the frame uses none of the optional stages (fixed-point snap, perspective, no fog, no lighting, no wireframe lists, no x-ray,
 // RGB555): those branches are compiled out -- fewer live scalars, less code in the instruction cache, no exec-mask juggling around them
 // (the plain form is compiled for 8 waves per SIMD: left to itself the register allocator lands on 57 ... 65 VGPRs depending on unrelated
@@ -228,393 +229,495 @@ __device__ __forceinline__ uint32_t agg_position(const AggSlot& g) {
 #ifndef B32_LIT_SETUP_WAVES
 #define B32_LIT_SETUP_WAVES 6
 #endif
-template <int SETUP_FPT, int PLAIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 4), PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 5)))) void k_setup(FrameParams fp_in, const B32Vertex* __restrict__ verts, const B32Face* __restrict__ faces,
-                                               const TexDesc* __restrict__ tex, const B32Light* __restrict__ lights_mem, LightSet lset, MeshTable mtab, PlaceTable ptab,
-                                               RecArrays recs, DirectBin db, float* __restrict__ shades, uint32_t* __restrict__ keys,
-                                               uint32_t* __restrict__ spans, uint32_t* __restrict__ partials, Ctrl* __restrict__ ctrl,
-                                               WireTri* __restrict__ wire, const float* __restrict__ pos12, const float* __restrict__ attr12,
-                                               uint32_t* __restrict__ face_of) {
-    FrameParams fp_plain = fp_in;                 // (dead code unless PLAIN)
-    if (PLAIN) { fp_plain.ortho = 0; fp_plain.fixed_point = 1; fp_plain.has_fog = 0; fp_plain.wire_collect = 0; fp_plain.xray = 0; fp_plain.batched = 0; fp_plain.placed = 0; }   // (fmt8 stays a run-time flag: one scalar test)
-    if (PLAIN == 1) { fp_plain.shading = B32_SHADE_NONE; fp_plain.n_lights = 0; }
-    const FrameParams& fp = PLAIN ? fp_plain : fp_in;
+// What a lane carries from phase to phase.
+struct FaceIn { uint32_t w[5]; float v[3][5]; uint32_t col[3]; bool live, bad; };                 // the face words and its three vertices as loaded
+struct FaceMode { uint32_t tid, black_tr, face_blend, editor_alpha, tex_blend; bool have_tex; };  // texture and blend of the face
+struct MeshParams { float ambient; bool cull, has_fog, placed; B32Fog fog; float cos, sin; V3 world; };
+struct FaceAttr { float uvx[3], uvy[3]; uint32_t col[3]; V3 wn[3]; };                              // per vertex, in the face's own vertex order
+struct Winding { V3 v1, v2, v3; int i1, i2, i3; };                                                 // the Surface's vertices and where each came from
+struct TriSetup {                                                                                  // the prologue of rasterize_triangle_15
+    uint32_t min_x, max_x, min_y, max_y, bbx, bby;
+    bool empty;
+    float area, inv_area, a0, b0, a1, b1, w0_start, w1_start;
+};
+struct FaceOut {                                                                                   // what the wave publishes for the face
+    bool visible = false, transparent = false, nan_key = false, bad_index = false;
+    uint32_t key = KEY_INVALID, span = 0xFFFFFFFFu, n_tiles = 0;
+};
+
+// Block 0's frame-start reset (no memset launch).  Reads the previous frame's drop flags in Ctrl; leaves every word of Ctrl zero but
+// `sticky`, which gains one lost frame where there was one, and the Stamps behind it zero with ST_SETUP taken.
+__device__ __forceinline__ void reset_frame(Ctrl* __restrict__ ctrl, const FrameParams& fp) {
+    // If the previous frame was dropped (pair overflow / long list: nothing drawn) and this
+    // is a NEW frame rather than the host's redraw of it, that frame is lost for good: count it, b32_frame_finish reports it
+    const bool lost = !fp.redraw && (ctrl->pairs_overflow || ctrl->need_global_sort);
+    __syncthreads();
+    if (threadIdx.x < sizeof(Ctrl) / 4 && threadIdx.x != offsetof(Ctrl, sticky) / 4) reinterpret_cast<uint32_t*>(ctrl)[threadIdx.x] = 0;
+    if (threadIdx.x == 0 && lost) ctrl->sticky += 0x100u;
+    if (threadIdx.x == 0) { Stamps* st = reinterpret_cast<Stamps*>(ctrl + 1); for (int k = 1; k < 8; ++k) st->t[k] = 0; st->t[ST_SETUP] = wall_clock64(); }
+}
+
+// Face f's inputs.  Reads the five face words, then -- once the three indices are known to be in range -- the packed positions of a
+// resident mesh or the full vertices.  Leaves `live` (f is a face), `bad` (an index out of range: nothing else was loaded), the words and
+// positions, and UVs and colours where the full vertices were read (zero from the packed streams: fetch_attributes brings them later).
+// All of a path's loads are requested before anything is used.
+__device__ __forceinline__ FaceIn load_face(const SetupBuffers& a, const FrameParams& fp, uint32_t f) {
+    FaceIn in;
+    in.live = f < fp.nf; in.bad = false;
+    if (in.live) {
+        const uint32_t* fw = reinterpret_cast<const uint32_t*>(a.faces) + (size_t)f * 5;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) in.w[k] = fw[k];
+    }
+    if (in.live) {
+        in.bad = in.w[0] >= fp.nv || in.w[1] >= fp.nv || in.w[2] >= fp.nv;       // index panic, render.rs:2375-2377
+        if (!in.bad) {
+            if (a.pos12) {        // packed streams of a resident mesh: positions only (12 B instead of a 36-B vertex); the rest once the face is known to be drawn
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const float* pp = a.pos12 + (size_t)in.w[j] * 3;
+                    in.v[j][0] = pp[0]; in.v[j][1] = pp[1]; in.v[j][2] = pp[2];
+                    in.v[j][3] = in.v[j][4] = 0.0f; in.col[j] = 0;
+                }
+            } else                // (one branch around all three vertices: every load of a path is issued before the first is used)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float* vp = reinterpret_cast<const float*>(a.verts) + (size_t)in.w[j] * 9;
+#pragma unroll
+                for (int k = 0; k < 5; ++k) in.v[j][k] = vp[k];
+                in.col[j] = reinterpret_cast<const uint32_t*>(vp)[8];
+            }
+        }
+    }
+    return in;
+}
+
+// What the reference's callers vary from mesh to mesh.  Reads the face's spare byte (the mesh number of a batched frame) and that mesh's
+// rows of the two tables; leaves ambient, cull, fog and the placement, which are the frame's own when the frame is neither batched nor placed.
+__device__ __forceinline__ MeshParams mesh_params(const FrameParams& fp, const MeshTable& mtab, const PlaceTable& ptab, uint32_t fb4) {
+    // per-mesh parameters of a batched frame (mesh number in the face's spare byte), else the frame's
+    MeshParams m = { fp.ambient, fp.backface_cull != 0, fp.has_fog != 0, false, fp.fog, 1.0f, 0.0f, { 0.0f, 0.0f, 0.0f } };
+    if (fp.batched) {
+        const MeshRow& mr = mtab.m[(fb4 >> 24) & (BATCH_MESHES - 1u)];
+        m.ambient = mr.ambient; m.cull = (mr.flags & ROW_CULL) != 0; m.has_fog = (mr.flags & ROW_FOG) != 0; m.fog = mr.fog;
+    }
+    // placement of this face's mesh (render_asset_parts, scene.rs:123-159): row 0 for a draw on its own, the mesh's row in a merged run.
+    // Not placed = the reference's untransformed branch (scene.rs:157-159): the local vertices as they are, NOT times 1 plus 0
+    if (fp.placed) {
+        const uint32_t mesh = fp.batched ? ((fb4 >> 24) & (BATCH_MESHES - 1u)) : 0u;
+        m.placed = !fp.batched || (mtab.m[mesh].flags & ROW_PLACED) != 0;
+        const B32Placement& pl = ptab.p[mesh];
+        m.cos = pl.cos_f; m.sin = pl.sin_f; m.world = ld3(pl.world_pos);
+    }
+    return m;
+}
+
+// A local position into the world.  Reads the mesh's placement; leaves the vertex every later phase works with.
+__device__ __forceinline__ V3 place_vertex(const FrameParams& fp, const MeshParams& m, V3 pos) {
+    if (fp.placed && m.placed) {             // scene.rs:143-146: the placed position IS the vertex from here on
+        const float rx = pos.x * m.cos - pos.z * m.sin;
+        const float rz = pos.x * m.sin + pos.z * m.cos;
+        pos = { rx + m.world.x, pos.y + m.world.y, rz + m.world.z };
+    }
+    return pos;
+}
+
+// A world position onto the screen, by the frame's projection: orthographic, fixed-point snap (the UNR table from LDS) or float
+// perspective.  Reads the camera and its fixed-point form; leaves the screen vertex (x, y, depth) and the camera-space z in `camz`.
+__device__ __forceinline__ V3 project_vertex(const FrameParams& fp, V3 pos, const uint8_t* unr_lds, float& camz) {
+    const CamFx& k = fp.camfx;              // loop-invariant fixed-point conversions, done once on the host
+    const V3 cpos = ld3(fp.cam.position), bx = ld3(fp.cam.basis_x), by = ld3(fp.cam.basis_y), bz = ld3(fp.cam.basis_z);
+    V3 rel = sub3(pos, cpos);
+    V3 cp = { dot3(rel, bx), dot3(rel, by), dot3(rel, bz) };       // perspective_transform, math.rs:103-109
+    camz = cp.z;
+    V3 scr;
+    if (fp.ortho) {                                                  // render.rs:2323-2328, project_ortho math.rs:140-148
+        scr = { (cp.x - fp.ortho_cx) * fp.ortho_zoom + ((float)fp.width / 2.0f),
+                -(cp.y - fp.ortho_cy) * fp.ortho_zoom + ((float)fp.height / 2.0f), cp.z };
+    } else if (fp.fixed_point) {                                     // render.rs:2329-2345
+        int32_t sx, sy;
+        project_fixed_dev(pos.x, pos.y, pos.z, k, sx, sy, unr_lds);
+        scr = { (float)sx, (float)sy, cp.z + K::MESH_DISTANCE };
+    } else {                                                         // project, math.rs:117-136
+        uint32_t mn = fp.width < fp.height ? fp.width : fp.height;
+        const float ud = K::P_DISTANCE, us = ud - K::P_US_SUB;                        // math.rs:121-122 (4.0, folded)
+        float vs = ((float)mn / K::P_VIEWPORT_DIV) * K::P_VIEWPORT_FRAC;
+        float denom = cp.z + ud;
+        if (__builtin_fabsf(denom) < K::P_DENOM_GUARD) scr = { (float)fp.width / 2.0f, (float)fp.height / 2.0f, cp.z };
+        else scr = { (cp.x * us) / denom * vs + ((float)fp.width / 2.0f),
+                     (cp.y * us) / denom * vs + ((float)fp.height / 2.0f), denom };
+    }
+    return scr;
+}
+
+// Is the face drawn?  Reads the screen vertices, the camera depths, the mesh's cull and fog rows and -- where some texture blends -- the
+// face's texture descriptor (its gather sits between the near reject and the fog cull, as early as `keep` allows).  Leaves `keep`
+// (returned), `backface`, the texture's presence and blend mode in `fm`, and the face's WireTri where the frame collects wireframe lists.
+__device__ __forceinline__ bool cull_face(const SetupBuffers& a, const FrameParams& fp, const MeshParams& m, uint32_t f, const V3 (&scr)[3],
+                                          const float (&camz)[3], FaceMode& fm, bool& backface) {
+    bool keep = fp.ortho || !(camz[0] <= K::NEAR_PLANE || camz[1] <= K::NEAR_PLANE || camz[2] <= K::NEAR_PLANE);   // render.rs:2381-2385
+    float signed_area = (scr[1].x - scr[0].x) * (scr[2].y - scr[0].y) - (scr[2].x - scr[0].x) * (scr[1].y - scr[0].y);
+    backface = signed_area <= 0.0f;                                          // render.rs:2393-2394
+    fm.have_tex = fm.tid != B32_NO_TEXTURE && fm.tid < fp.nt;               // textures.get(id)
+    fm.tex_blend = B32_BLEND_OPAQUE;
+    if (fp.tex_blend_any && keep && fm.have_tex) fm.tex_blend = a.tex[fm.tid].blend_mode;     // (all Opaque: no descriptor gather in the chain)
+    // fog, render.rs:2419-2442: the distance cull here, the colours further down (only surfaces whose record is built need them)
+    if (fp.has_fog && m.has_fog && keep && camz[0] > m.fog.cull_distance && camz[1] > m.fog.cull_distance && camz[2] > m.fog.cull_distance) keep = false;
+    if (fp.wire_collect) {                       // wireframe lists take the face before the solid decision (render.rs:2445-2449, 2509-2511)
+        WireTri wt;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { wt.x[j] = f2i32_sat(scr[j].x); wt.y[j] = f2i32_sat(scr[j].y); wt.z[j] = scr[j].z; }
+        wt.kind = !keep ? 0u : (backface ? (fp.xray ? 0u : 1u) : 2u);
+        a.wire[f] = wt;
+    }
+    if (backface && m.cull && !fp.xray) keep = false;              // render.rs:2451-2453
+    return keep;
+}
+
+// The per-triangle prologue of rasterize_triangle_15.  Reads the Surface's vertices and the frame's size and tile grid; leaves the
+// clipped bbox (all zero for an empty surface), `empty`, the area, the edge coefficients and start values, and in `span` / `n_tiles`
+// the packed tile span and the number of tiles this rank's band has of it.
+__device__ __forceinline__ TriSetup triangle_prologue(const FrameParams& fp, const Winding& s, uint32_t& span, uint32_t& n_tiles) {
+    const V3 &v1 = s.v1, &v2 = s.v2, &v3 = s.v3;
+    TriSetup t;
+    // bbox, render.rs:1455-1458
+    t.min_x = f2u_sat(rmax(rmin(rmin(v1.x, v2.x), v3.x), 0.0f));
+    t.max_x = f2u_sat(rmin(rmax(rmax(v1.x, v2.x), v3.x) + 1.0f, (float)fp.width));
+    t.min_y = f2u_sat(rmax(rmin(rmin(v1.y, v2.y), v3.y), 0.0f));
+    t.max_y = f2u_sat(rmin(rmax(rmax(v1.y, v2.y), v3.y) + 1.0f, (float)fp.height));
+    t.empty = t.min_x >= t.max_x || t.min_y >= t.max_y;
+    t.area = (v2.y - v3.y) * (v1.x - v3.x) + (v3.x - v2.x) * (v1.y - v3.y);            // :1500
+    if (__builtin_fabsf(t.area) < K::AREA_EPS) t.empty = true;                          // :1501-1503
+    if (t.empty) { t.min_x = t.max_x = t.min_y = t.max_y = 0; }
+    t.bbx = t.min_x | (t.max_x << 16); t.bby = t.min_y | (t.max_y << 16);
+    span = pack_tile_span(t.bbx, t.bby, t.empty ? F_EMPTY : 0u, fp, n_tiles);
+    t.inv_area = 0.0f; t.w0_start = t.w1_start = 0.0f;
+    return t;
+}
+// ... and its second half, for the surfaces whose record is built: reads the vertices, the area and the bbox's corner; leaves 1 / area,
+// the edge coefficients and the start values.  (Apart from the first half: its results are not alive across the list-slot request.)
+__device__ __forceinline__ void triangle_edges(const Winding& s, TriSetup& t) {
+    const V3 &v1 = s.v1, &v2 = s.v2, &v3 = s.v3;
+    t.inv_area = 1.0f / t.area;
+    t.a0 = v2.y - v3.y; t.b0 = v3.x - v2.x; t.a1 = v3.y - v1.y; t.b1 = v1.x - v3.x;   // :1507-1510
+    const float start_x = (float)t.min_x, start_y = (float)t.min_y;
+    t.w0_start = t.a0 * (start_x - v3.x) + t.b0 * (start_y - v3.y);                    // :1517
+    t.w1_start = t.a1 * (start_x - v3.x) + t.b1 * (start_y - v3.y);                    // :1518
+}
+
+// The largest |coordinate| of the Surface's vertices: the exactness guard and the i16 vertex form of the coverage record both bound it.
+__device__ __forceinline__ float max_abs_coord(const Winding& s) {
+    return rmax(rmax(rmax(__builtin_fabsf(s.v1.x), __builtin_fabsf(s.v1.y)), rmax(__builtin_fabsf(s.v2.x), __builtin_fabsf(s.v2.y))),
+                rmax(__builtin_fabsf(s.v3.x), __builtin_fabsf(s.v3.y)));
+}
+// Closed-form eligibility: with integer vertices every value the reference's incremental walk ever holds
+// is an exact integer when |w| < 2^24 over the bbox and both start products are < 2^24.
+// Reads the vertices, the bbox and the edge coefficients of a non-empty fixed-point surface; leaves nothing but its answer.
+__device__ __forceinline__ bool walk_is_exact(const Winding& s, const TriSetup& t) {
+    const V3& v3 = s.v3;
+    const float lim = 4194304.0f;   // 2^22
+    const float cmax = max_abs_coord(s);
+    // quick acceptance (nearly every triangle): every edge coefficient is at most amax, every offset from v3 to a
+    // corner of the clipped box at most dmax (integers below 2^23), so every product is at most amax * dmax and every
+    // sum of two at most twice that; the float product rounds monotonically and 2^24 is representable
+    const float amax = rmax(rmax(__builtin_fabsf(t.a0), __builtin_fabsf(t.b0)), rmax(__builtin_fabsf(t.a1), __builtin_fabsf(t.b1)));
+    const float dmax = rmax(rmax(__builtin_fabsf((float)t.min_x - v3.x), __builtin_fabsf((float)(t.max_x - 1) - v3.x)),
+                            rmax(__builtin_fabsf((float)t.min_y - v3.y), __builtin_fabsf((float)(t.max_y - 1) - v3.y)));
+    bool exact = true;
+    if (!(cmax <= lim)) exact = false;
+    else if (!(2.0f * (amax * dmax) < 16777216.0f)) {
+        // every operand is an integer-valued float below 2^23, so each product / sum below is exact whenever its
+        // true value is below 2^24, and rounds to >= 2^24 otherwise (rounding is monotonic and 2^24 is
+        // representable): the float comparisons decide exactly what 64-bit integer arithmetic would
+        const float dxs[2] = { (float)t.min_x - v3.x, (float)(t.max_x - 1) - v3.x };
+        const float dys[2] = { (float)t.min_y - v3.y, (float)(t.max_y - 1) - v3.y };
+        const float L = 16777216.0f;   // 2^24
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float p0 = t.a0 * dxs[i], q0 = t.b0 * dys[j], p1 = t.a1 * dxs[i], q1 = t.b1 * dys[j];
+                if (!(__builtin_fabsf(p0) < L && __builtin_fabsf(q0) < L && __builtin_fabsf(p1) < L && __builtin_fabsf(q1) < L &&
+                      __builtin_fabsf(p0 + q0) < L && __builtin_fabsf(p1 + q1) < L)) exact = false;
+            }
+    }
+    return exact;
+}
+
+// The late loads of a surviving face.  Reads, by the vertex layout, the packed attribute stream (with the normals of a lit frame) or the
+// normals of the full vertices, then the mesh's placement and fog row; leaves UVs and colours where the packed streams hold them, the
+// world normals of a lit frame (rotated with a placed mesh) and the fogged vertex colours.
+// (the world normals of a lit frame are requested HERE, with the attributes, and used at the very end: behind the record
+// build their round trip is hidden -- requested where they are used it was 12 of the lit kernel's 77 us, measured by
+// replacing them with a constant)
+__device__ __forceinline__ void fetch_attributes(const SetupBuffers& a, const FrameParams& fp, const MeshParams& m, const uint32_t (&vi)[3],
+                                                 const float (&camz)[3], FaceAttr& at) {
+    if (a.pos12 && fp.shading != B32_SHADE_NONE) {
+        // packed streams, lit frame: attributes AND normal of a vertex from the 24-byte stream (one cache line per face instead
+        // of one in the attribute stream and one in a normal stream of its own: 12 of the lit kernel's 77 us)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float* lp = a.attr12 + (size_t)fp.nv * 3 + (size_t)vi[j] * 6;
+            at.uvx[j] = lp[0]; at.uvy[j] = lp[1]; at.col[j] = reinterpret_cast<const uint32_t*>(lp)[2];
+            at.wn[j] = { lp[3], lp[4], lp[5] };
+        }
+    } else if (a.pos12) {   // packed streams: the survivor's UVs and vertex colours only now (12 B per vertex, culled faces never fetch them)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float* ap = a.attr12 + (size_t)vi[j] * 3;
+            at.uvx[j] = ap[0]; at.uvy[j] = ap[1]; at.col[j] = reinterpret_cast<const uint32_t*>(ap)[2];
+        }
+    } else if (fp.shading != B32_SHADE_NONE) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float* np = reinterpret_cast<const float*>(a.verts) + (size_t)vi[j] * 9 + 5;
+            at.wn[j] = { np[0], np[1], np[2] };
+        }
+    }
+    if (fp.placed && m.placed && fp.shading != B32_SHADE_NONE) {       // scene.rs:148-152: rotated with the mesh, not renormalised
+#pragma unroll
+        for (int j = 0; j < 3; ++j) at.wn[j] = { at.wn[j].x * m.cos - at.wn[j].z * m.sin, at.wn[j].y, at.wn[j].x * m.sin + at.wn[j].z * m.cos };
+    }
+    if (fp.has_fog && m.has_fog) {
+        const uint32_t fogc = m.fog.r | (m.fog.g << 8) | (m.fog.b << 16) | ((uint32_t)m.fog.blend << 24);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) at.col[j] = fog_color(at.col[j], fogc, fog_factor(camz[j], m.fog.start, m.fog.falloff));
+    }
+}
+
+// painter's key, render.rs:2529-2531 / 2538-2540. Perspective keys are > 5 (cam z > 0.1), so the sign bit
+// is free: bit 31 = transparent class, low 31 bits = 0x7FFFFFFF - bits(z) => ascending radix == descending z,
+// stability of the LSD passes == stability of slice::sort_by.
+// Reads the three depths, the face's class and the frame's sort mode; leaves the key (returned) and `nan_key` where the mean depth is a NaN.
+__device__ __forceinline__ uint32_t painter_key(float v1z, float v2z, float v3z, bool transparent, const FrameParams& fp, bool& nan_key) {
+    float kz = (v1z + v2z + v3z) / 3.0f;
+    // z-buffer mode never sorts the opaque list (render.rs:2535): key 0 keeps it in face order through the stable
+    // passes, and a NaN key there is never compared
+    if (fp.zmode && !transparent) kz = 0.0f;
+    if (kz != kz) { nan_key = true; kz = 0.0f; }
+    if (kz == 0.0f) kz = 0.0f;                    // -0.0 == +0.0 under partial_cmp
+    uint32_t zb = __float_as_uint(kz);
+    uint32_t key = ((0x7FFFFFFFu - (zb & 0x7FFFFFFFu)) & 0x7FFFFFFFu) | (transparent ? 0x80000000u : 0u);
+    // orthographic depths may be negative: all 32 bits order the depth (descending), the class partition is a pass of
+    // its own (launch_class_keys).  ~zsort_key(z) == 0xFFFFFFFF only for a NaN pattern, which was replaced above.
+    if (fp.ortho) key = ~zsort_key(kz);
+    if (fp.zmode && !transparent) key = 0;
+    if (key == KEY_INVALID) key = 0xFFFFFFFEu;    // unreachable for z > 5; keeps the sentinel unique
+    return key;
+}
+
+// The record build.  Reads everything the phases before it left for the face; leaves the coverage and shading records of slot `rslot`,
+// and its aux record where the fill may need 1/z or the literal walk's start values.  Nothing it reads is needed after it but the
+// world positions and normals of a lit frame.
+__device__ __forceinline__ void store_records(const RecArrays& recs, const FrameParams& fp, uint32_t rslot, const Winding& s, const TriSetup& t,
+                                              const FaceMode& fm, const FaceAttr& at, uint32_t key, bool slow, bool transparent) {
+    const V3 &v1 = s.v1, &v2 = s.v2, &v3 = s.v3;
+    const int i1 = s.i1, i2 = s.i2, i3 = s.i3;
+    const bool vc_diff = (at.col[i1] != at.col[i2]) || (at.col[i2] != at.col[i3]);                // Color equality incl. blend, types.rs:719
+    const bool needs_dither = fp.dithering && (fp.shading == B32_SHADE_GOURAUD || fm.have_tex || vc_diff);   // :1487-1492
+    const uint32_t eff_blend = fm.have_tex ? fm.tex_blend : fm.face_blend;                          // :1450-1452
+    const uint32_t flags = (fm.have_tex ? fm.tid : F_TEX_NONE) | (fm.black_tr ? F_BLACK_TR : 0) | (eff_blend << F_BLEND_SHIFT) |
+                           (needs_dither ? F_DITHER : 0) | (slow ? F_SLOW : 0) | (transparent ? F_TRANSP : 0) |
+                           (t.empty ? F_EMPTY : 0) | (fm.editor_alpha << F_ALPHA_SHIFT);
+    // vertices as i16 when all six are integers within range: the fixed-point snap yields integers (project_fixed), and
+    // F_SLOW surfaces always take the wide form
+    const bool fits = !slow && max_abs_coord(s) <= 32767.0f;
+    auto pk16 = [](float x, float y) { return ((uint32_t)(int32_t)x & 0xFFFFu) | ((uint32_t)(int32_t)y << 16); };
+    uint4 c0, c1;
+    c0.x = fits ? pk16(v1.x, v1.y) : COV_WIDE; c0.y = fits ? pk16(v2.x, v2.y) : 0u; c0.z = fits ? pk16(v3.x, v3.y) : 0u;
+    c0.w = __float_as_uint(t.inv_area);
+    c1 = make_uint4(t.bbx, t.bby, key, flags);
+    uint4* cp = reinterpret_cast<uint4*>(recs.cov + rslot);
+    cp[0] = c0; cp[1] = c1;
+    const uint32_t slot = fm.have_tex ? fm.tid : F_TEX_NONE;
+    const uint32_t shf = (fm.black_tr ? SH_BLACK_TR : 0u) | (needs_dither ? SH_DITHER : 0u) | (slow ? SH_SLOW : 0u);
+    uint4* sp = reinterpret_cast<uint4*>(recs.shade + rslot);
+    sp[0] = make_uint4(__float_as_uint(v1.x), __float_as_uint(v1.y), __float_as_uint(v2.x), __float_as_uint(v2.y));
+    sp[1] = make_uint4(__float_as_uint(v3.x), __float_as_uint(v3.y), __float_as_uint(t.inv_area), (at.col[i1] & 0xFFFFFFu) | ((slot & 0xFFu) << 24));
+    sp[2] = make_uint4(__float_as_uint(at.uvx[i1]), __float_as_uint(at.uvx[i2]), __float_as_uint(at.uvx[i3]), __float_as_uint(at.uvy[i1]));
+    sp[3] = make_uint4(__float_as_uint(at.uvy[i2]), __float_as_uint(at.uvy[i3]), (at.col[i2] & 0xFFFFFFu) | ((slot >> 8) << 24), (at.col[i3] & 0xFFFFFFu) | (shf << 24));
+    if (fp.zmode || !fp.affine || slow) {
+        uint4* xp = reinterpret_cast<uint4*>(recs.aux + rslot);
+        xp[0] = make_uint4(__float_as_uint(1.0f / v1.z), __float_as_uint(1.0f / v2.z), __float_as_uint(1.0f / v3.z), __float_as_uint(t.w0_start));   // :1546-1548
+        xp[1] = make_uint4(__float_as_uint(t.w1_start), 0u, 0u, 0u);
+    }
+}
+
+// Direct binning: the face id into the list of every tile of the span (any order inside a list).  Reads the span, the list slot of its
+// first tile that the kernel requested before the record build (`first`), and the tile counters; leaves `rslot` in each tile's region
+// and, where a region was full, the frame's overflow event.  Every lane of the wave that has tiles must call it together.
+__device__ __forceinline__ void bin_span(const DirectBin& db, const FrameParams& fp, Ctrl* __restrict__ ctrl, uint32_t span, uint32_t n_tiles,
+                                         bool db_cls, const AggSlot& first, uint32_t rslot) {
+    const uint32_t cap = db_cls ? db.cap_transparent : db.cap_opaque;
+    const uint32_t tx0 = span & 0xFF, tx1 = (span >> 8) & 0xFF, ty0 = (span >> 16) & 0xFF;
+    bool over = false;
+    uint32_t tx = tx0, ty = ty0;
+    AggSlot g = first;
+    // the k-th tile of every lane's span together (wave-uniform loop: the group ballots need every lane of this block)
+    for (uint32_t k = 0; __ballot(k < n_tiles); ++k) {
+        const bool act = k < n_tiles;
+        const uint32_t tile = ty * fp.tiles_x + tx;
+        if (k) agg_issue(db.fill, tile * FILL_PAD + (db_cls ? 1u : 0u), act, threadIdx.x & 63u, g);
+        const uint32_t pos = agg_position(g);
+        if (act) {
+            if (pos < cap) db.lists[(size_t)tile * db.region + (db_cls ? db.region - 1u - pos : pos)] = rslot;
+            else over = true;
+            if (++tx > tx1) { tx = tx0; ++ty; }
+        }
+    }
+    if (over) { Events* ev = events_of(ctrl); if (db_cls) ev->long_transparent = db.epoch; else ev->overflow = db.epoch; }
+}
+
+// The flat or Gouraud vertex shades of a lit frame (render.rs:1013-1071).  Reads the world positions, the world normals that
+// fetch_attributes requested, the frame's lights and the mesh's ambient; leaves the nine shade values of slot `rslot`.
+// (the shades last: the record's values are stored and dead by now, the lighting has the registers to itself)
+__device__ __forceinline__ void store_shades(float* __restrict__ shades, const B32Light* lights, const FrameParams& fp, float ambient, uint32_t rslot,
+                                             bool backface, const Winding& s, const V3 (&wpos)[3], V3 (&wn)[3]) {
+    const int i1 = s.i1, i2 = s.i2, i3 = s.i3;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) if (backface) wn[j] = scale3(wn[j], -1.0f);
+    float* sh = shades + (size_t)rslot * 9;
+    if (fp.shading == B32_SHADE_FLAT) {                                             // :1466-1469
+        V3 center = scale3(add3(add3(wpos[i1], wpos[i2]), wpos[i3]), 1.0f / 3.0f);
+        V3 nrm = normalize3(scale3(add3(add3(wn[i1], wn[i2]), wn[i3]), 1.0f / 3.0f));
+        float c[3]; shade_multi(nrm, center, lights, fp.n_lights, ambient, c);
+        for (int j = 0; j < 9; ++j) sh[j] = c[j % 3];
+    } else {                                                                        // :1475-1483
+        shade_multi(wn[i1], wpos[i1], lights, fp.n_lights, ambient, sh);
+        shade_multi(wn[i2], wpos[i2], lights, fp.n_lights, ambient, sh + 3);
+        shade_multi(wn[i3], wpos[i3], lights, fp.n_lights, ambient, sh + 6);
+    }
+}
+
+// What the wave and the block publish.  Reads every lane's FaceOut; leaves the painter's key, tile span and face id per SLOT (survivors at
+// the front of the wave's 64 slots, KEY_INVALID behind them), the event words a direct-binning frame needs, and the block's six counters.
+// frame counters: ballot per wave -> LDS -> one 5-word record per block (reduced by k_after_setup; no atomics)
+__device__ __forceinline__ void publish_wave(const SetupBuffers& a, uint32_t f, bool live, const FaceOut& o, uint32_t (&wpart)[4][6]) {
+    const unsigned long long mv = __ballot(o.visible), mt = __ballot(o.transparent);
+    {   // painter's key and tile span per SLOT (see `rslot` in k_setup): survivors at the front of the wave's 64 slots, KEY_INVALID behind them
+        const uint32_t lane = threadIdx.x & 63u, nvis = (uint32_t)__popcll(mv), wbase = f - lane;
+        if (o.visible) {
+            const uint32_t slot = wbase + (uint32_t)__popcll(mv & ((1ull << lane) - 1ull));
+            a.keys[slot] = o.key;
+            if (a.spans) a.spans[slot] = o.span;
+            if (a.face_of) a.face_of[slot] = f;
+        }
+        if (live && lane >= nvis) { a.keys[wbase + lane] = KEY_INVALID; if (a.spans) a.spans[wbase + lane] = 0xFFFFFFFFu; }
+    }
+    const unsigned long long mn_op = __ballot(o.nan_key && !o.transparent), mn_tr = __ballot(o.nan_key && o.transparent), mb = __ballot(o.bad_index);
+    const uint32_t wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        wpart[wv][0] = (uint32_t)__popcll(mv); wpart[wv][1] = (uint32_t)__popcll(mt);
+        wpart[wv][2] = (uint32_t)__popcll(mn_op); wpart[wv][3] = (uint32_t)__popcll(mn_tr); wpart[wv][4] = mb ? 1u : 0u;
+        if (a.db.fill && (mn_op | mn_tr | mb)) {   // direct binning: nobody reduces the counters before the fill, which only does so after one of these
+            Events* ev = events_of(a.ctrl);
+            if (mb) ev->bad_index = a.db.epoch;
+            if (mn_op) ev->nan_opaque = a.db.epoch;
+            if (mn_tr) ev->nan_transparent = a.db.epoch;
+        }
+    }
+    uint32_t n_tiles = o.n_tiles;
+    for (int off = 32; off > 0; off >>= 1) n_tiles += __shfl_down(n_tiles, off);      // (tile, surface) pairs of this block
+    if ((threadIdx.x & 63) == 0) wpart[wv][5] = n_tiles;
+    __syncthreads();
+    // (one record per block of 256 faces: the consumers index them by face / 256)
+    if (threadIdx.x < 6) a.partials[blockIdx.x * 8 + threadIdx.x] = wpart[0][threadIdx.x] + wpart[1][threadIdx.x] + wpart[2][threadIdx.x] + wpart[3][threadIdx.x];
+}
+
+template <int PLAIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 4), PLAIN == 1 ? 8 : (PLAIN == 2 ? B32_LIT_SETUP_WAVES : 5)))) void k_setup(SetupArgs args) {
+    // A local copy of the frame's parameters, in every form.  In the PLAIN forms the compiled-out stages are zeroed in it.  In the general form
+    // it keeps the frame's own fog and ambient values apart from the argument block: read from there, next to the mesh table, the
+    // compiler merges "the frame's value or the mesh row's" into one load through a per-lane address (8 vector loads in the way of every
+    // face, batched frame or not: 54 us instead of 52 at 1 M faces with fog).
+    FrameParams fp = args.fp;
+    if (PLAIN) { fp.ortho = 0; fp.fixed_point = 1; fp.has_fog = 0; fp.wire_collect = 0; fp.xray = 0; fp.batched = 0; fp.placed = 0; }   // (fmt8 stays a run-time flag: one scalar test)
+    if (PLAIN == 1) { fp.shading = B32_SHADE_NONE; fp.n_lights = 0; }
     __shared__ uint32_t wpart[4][6];
     __shared__ uint8_t unr_lds[K::UNR_ENTRIES + 3];          // UNR_TABLE in LDS: its lookup sits in every vertex's dependent chain
     for (uint32_t i = threadIdx.x; i < K::UNR_ENTRIES; i += 256) unr_lds[i] = g_unr.v[i];
     __syncthreads();
-    const B32Light* lights = fp.lights_inline ? lset.l : lights_mem;
-    if (blockIdx.x == 0) {
-        // frame-start reset (no memset launch).  If the previous frame was dropped (pair overflow / long list: nothing drawn) and this
-        // is a NEW frame rather than the host's redraw of it, that frame is lost for good: count it, b32_frame_finish reports it
-        const bool lost = !fp.redraw && (ctrl->pairs_overflow || ctrl->need_global_sort);
-        __syncthreads();
-        if (threadIdx.x < sizeof(Ctrl) / 4 && threadIdx.x != offsetof(Ctrl, sticky) / 4) reinterpret_cast<uint32_t*>(ctrl)[threadIdx.x] = 0;
-        if (threadIdx.x == 0 && lost) ctrl->sticky += 0x100u;
-        if (threadIdx.x == 0) { Stamps* st = reinterpret_cast<Stamps*>(ctrl + 1); for (int k = 1; k < 8; ++k) st->t[k] = 0; st->t[ST_SETUP] = wall_clock64(); }
-    }
-    // Every thread owns SETUP_FPT faces, 256 apart (a workgroup covers SETUP_FPT groups of 256 consecutive faces).  All of their
-    // inputs -- the face words, then the three vertices each -- are requested before the first face is processed, so the second
-    // face's two dependent memory latencies pass behind the ~900 VALU instructions of the first.
-    struct FaceIn { uint32_t w[5]; float v[3][5]; uint32_t col[3]; bool live, bad; };
-    FaceIn fin[SETUP_FPT];
-#pragma unroll
-    for (int g = 0; g < SETUP_FPT; ++g) {
-        const uint32_t f = (blockIdx.x * SETUP_FPT + g) * 256u + threadIdx.x;
-        fin[g].live = f < fp.nf; fin[g].bad = false;
-        if (fin[g].live) {
-            const uint32_t* fw = reinterpret_cast<const uint32_t*>(faces) + (size_t)f * 5;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) fin[g].w[k] = fw[k];
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < SETUP_FPT; ++g) {
-        if (fin[g].live) {
-            fin[g].bad = fin[g].w[0] >= fp.nv || fin[g].w[1] >= fp.nv || fin[g].w[2] >= fp.nv;       // index panic, render.rs:2375-2377
-            if (!fin[g].bad) {
-                if (pos12) {          // packed streams of a resident mesh: positions only (12 B instead of a 36-B vertex); the rest once the face is known to be drawn
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float* pp = pos12 + (size_t)fin[g].w[j] * 3;
-                        fin[g].v[j][0] = pp[0]; fin[g].v[j][1] = pp[1]; fin[g].v[j][2] = pp[2];
-                        fin[g].v[j][3] = fin[g].v[j][4] = 0.0f; fin[g].col[j] = 0;
-                    }
-                } else                // (one branch around all three vertices: every load of a path is issued before the first is used)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    const float* vp = reinterpret_cast<const float*>(verts) + (size_t)fin[g].w[j] * 9;
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) fin[g].v[j][k] = vp[k];
-                    fin[g].col[j] = reinterpret_cast<const uint32_t*>(vp)[8];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < SETUP_FPT; ++g) {
-    const uint32_t f = (blockIdx.x * SETUP_FPT + g) * 256u + threadIdx.x;
-    const FaceIn& in = fin[g];
-    bool visible = false, transparent = false, nan_key = false, bad_index = false;
-    uint32_t key = KEY_INVALID, span = 0xFFFFFFFFu, n_tiles = 0;
-    AggSlot db_first = { 0, 0, 0 }; bool db_cls = false;
+    // (every pointer is read here, with the kernel's first instructions: read in the branch that uses it, its scalar load waits in every
+    // face's dependent chain -- the plain form 46.3 us instead of 45.3 at 1 M faces)
+    const SetupBuffers b = args.buf;
+    const B32Light* lights = fp.lights_inline ? args.lset.l : b.lights;
+    if (blockIdx.x == 0) reset_frame(b.ctrl, fp);
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;       // one face per lane, a block's 256 faces consecutive
+    const FaceIn in = load_face(b, fp, f);
+    FaceOut out;
     if (in.live) {
-        uint32_t vi[3] = { in.w[0], in.w[1], in.w[2] };
-        const uint32_t tid = in.w[3], fb4 = in.w[4];
-        const uint32_t black_tr = fb4 & 0xFF, face_blend = (fb4 >> 8) & 0xFF, editor_alpha = (fb4 >> 16) & 0xFF;
-        // per-mesh parameters of a batched frame (mesh number in the face's spare byte), else the frame's
-        float m_ambient = fp.ambient; bool m_cull = fp.backface_cull != 0, m_has_fog = fp.has_fog != 0; B32Fog m_fog = fp.fog;
-        if (fp.batched) {
-            const MeshRow& mr = mtab.m[(fb4 >> 24) & (BATCH_MESHES - 1u)];
-            m_ambient = mr.ambient; m_cull = (mr.flags & ROW_CULL) != 0; m_has_fog = (mr.flags & ROW_FOG) != 0; m_fog = mr.fog;
-        }
-        // placement of this face's mesh (render_asset_parts, scene.rs:123-159): row 0 for a draw on its own, the mesh's row in a merged run.
-        // Not placed = the reference's untransformed branch (scene.rs:157-159): the local vertices as they are, NOT times 1 plus 0
-        bool m_placed = false; float pl_cos = 1.0f, pl_sin = 0.0f; V3 pl_w = { 0.0f, 0.0f, 0.0f };
-        if (fp.placed) {
-            const uint32_t mesh = fp.batched ? ((fb4 >> 24) & (BATCH_MESHES - 1u)) : 0u;
-            m_placed = !fp.batched || (mtab.m[mesh].flags & ROW_PLACED) != 0;
-            const B32Placement& pl = ptab.p[mesh];
-            pl_cos = pl.cos_f; pl_sin = pl.sin_f; pl_w = ld3(pl.world_pos);
-        }
+        const uint32_t vi[3] = { in.w[0], in.w[1], in.w[2] }, fb4 = in.w[4];
+        FaceMode fm = { in.w[3], fb4 & 0xFF, (fb4 >> 8) & 0xFF, (fb4 >> 16) & 0xFF, B32_BLEND_OPAQUE, false };
+        const MeshParams mp = mesh_params(fp, args.mtab, args.ptab, fb4);
         if (in.bad) {
-            bad_index = true;
+            out.bad_index = true;
         } else {
-            const CamFx& k = fp.camfx;              // loop-invariant fixed-point conversions, done once on the host
-            const V3 cpos = ld3(fp.cam.position), bx = ld3(fp.cam.basis_x), by = ld3(fp.cam.basis_y), bz = ld3(fp.cam.basis_z);
-            V3 scr[3]; float camz[3]; V3 wpos[3]; float uvx[3], uvy[3]; uint32_t col[3];
+            // ---- transform and snap
+            V3 scr[3], wpos[3]; float camz[3];
+            FaceAttr at = {};
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                V3 pos = { in.v[j][0], in.v[j][1], in.v[j][2] };
-                if (fp.placed && m_placed) {             // scene.rs:143-146: the placed position IS the vertex from here on
-                    const float rx = pos.x * pl_cos - pos.z * pl_sin;
-                    const float rz = pos.x * pl_sin + pos.z * pl_cos;
-                    pos = { rx + pl_w.x, pos.y + pl_w.y, rz + pl_w.z };
-                }
-                uvx[j] = in.v[j][3]; uvy[j] = in.v[j][4];
-                col[j] = in.col[j];
-                wpos[j] = pos;
-                V3 rel = sub3(pos, cpos);
-                V3 cp = { dot3(rel, bx), dot3(rel, by), dot3(rel, bz) };       // perspective_transform, math.rs:103-109
-                camz[j] = cp.z;
-                if (fp.ortho) {                                                  // render.rs:2323-2328, project_ortho math.rs:140-148
-                    scr[j] = { (cp.x - fp.ortho_cx) * fp.ortho_zoom + ((float)fp.width / 2.0f),
-                               -(cp.y - fp.ortho_cy) * fp.ortho_zoom + ((float)fp.height / 2.0f), cp.z };
-                } else if (fp.fixed_point) {                                     // render.rs:2329-2345
-                    int32_t sx, sy;
-                    project_fixed_dev(pos.x, pos.y, pos.z, k, sx, sy, unr_lds);
-                    scr[j] = { (float)sx, (float)sy, cp.z + K::MESH_DISTANCE };
-                } else {                                                         // project, math.rs:117-136
-                    uint32_t mn = fp.width < fp.height ? fp.width : fp.height;
-                    const float ud = K::P_DISTANCE, us = ud - K::P_US_SUB;                        // math.rs:121-122 (4.0, folded)
-                    float vs = ((float)mn / K::P_VIEWPORT_DIV) * K::P_VIEWPORT_FRAC;
-                    float denom = cp.z + ud;
-                    if (__builtin_fabsf(denom) < K::P_DENOM_GUARD) scr[j] = { (float)fp.width / 2.0f, (float)fp.height / 2.0f, cp.z };
-                    else scr[j] = { (cp.x * us) / denom * vs + ((float)fp.width / 2.0f),
-                                    (cp.y * us) / denom * vs + ((float)fp.height / 2.0f), denom };
-                }
+                wpos[j] = place_vertex(fp, mp, { in.v[j][0], in.v[j][1], in.v[j][2] });
+                at.uvx[j] = in.v[j][3]; at.uvy[j] = in.v[j][4]; at.col[j] = in.col[j];
+                scr[j] = project_vertex(fp, wpos[j], unr_lds, camz[j]);
             }
-            bool keep = fp.ortho || !(camz[0] <= K::NEAR_PLANE || camz[1] <= K::NEAR_PLANE || camz[2] <= K::NEAR_PLANE);   // render.rs:2381-2385
-            float signed_area = (scr[1].x - scr[0].x) * (scr[2].y - scr[0].y) - (scr[2].x - scr[0].x) * (scr[1].y - scr[0].y);
-            bool backface = signed_area <= 0.0f;                                     // render.rs:2393-2394
-            const bool have_tex = tid != B32_NO_TEXTURE && tid < fp.nt;             // textures.get(id)
-            uint32_t tex_blend = B32_BLEND_OPAQUE;
-            if (fp.tex_blend_any && keep && have_tex) tex_blend = tex[tid].blend_mode;     // (all Opaque: no descriptor gather in the chain)
-            // fog, render.rs:2419-2442: the distance cull here, the colours further down (only surfaces whose record is built need them)
-            if (fp.has_fog && m_has_fog && keep && camz[0] > m_fog.cull_distance && camz[1] > m_fog.cull_distance && camz[2] > m_fog.cull_distance) keep = false;
-            if (fp.wire_collect) {                       // wireframe lists take the face before the solid decision (render.rs:2445-2449, 2509-2511)
-                WireTri wt;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) { wt.x[j] = f2i32_sat(scr[j].x); wt.y[j] = f2i32_sat(scr[j].y); wt.z[j] = scr[j].z; }
-                wt.kind = !keep ? 0u : (backface ? (fp.xray ? 0u : 1u) : 2u);
-                wire[f] = wt;
-            }
-            if (backface && m_cull && !fp.xray) keep = false;              // render.rs:2451-2453
-            if (keep) {
-                visible = true;
+            // ---- near, fog and back-face cull (and the wireframe lists' copy of the face)
+            bool backface;
+            if (cull_face(b, fp, mp, f, scr, camz, fm, backface)) {
+                out.visible = true;
                 // Record slot: the survivors of a wave's 64 faces are packed to the front of the wave's 64 slots (slot = first face id of
                 // the wave + rank among its survivors), so the records of a half-culled mesh fill whole cache lines instead of every other
                 // 32 / 64 bytes.  Slots are monotone in the face id, so everything downstream (tile lists, the priority's low word, the
                 // stable sorts) keeps face order; only b32_last_draw_order maps back (face_of).  (The ballot runs inside the branch: it
                 // sees exactly the lanes that got here.)
                 const uint32_t rslot = (f & ~63u) + (uint32_t)__builtin_popcountll(__ballot(true) & ((1ull << (threadIdx.x & 63u)) - 1ull));
-                transparent = (have_tex && tex_blend != B32_BLEND_OPAQUE) || face_blend != B32_BLEND_OPAQUE || editor_alpha < 255;  // :2403-2415
-                if (fp.fmt8) transparent = false;     // render_mesh computes has_transparency but never partitions (render.rs:2175-2184)
+                out.transparent = (fm.have_tex && fm.tex_blend != B32_BLEND_OPAQUE) || fm.face_blend != B32_BLEND_OPAQUE || fm.editor_alpha < 255;  // :2403-2415
+                if (fp.fmt8) out.transparent = false;     // render_mesh computes has_transparency but never partitions (render.rs:2175-2184)
                 // Surface build: rendered backfaces swap v2/v3 and every per-vertex attribute (render.rs:2453-2479)
-                const int i1 = 0, i2 = backface ? 2 : 1, i3 = backface ? 1 : 2;
-                const V3 v1 = scr[i1], v2 = scr[i2], v3 = scr[i3];
-                struct { float inv_area, a0, b0, a1, b1, w0_start, w1_start; uint32_t bbx, bby, flags; } r;
-                // bbox, render.rs:1455-1458
-                uint32_t min_x = f2u_sat(rmax(rmin(rmin(v1.x, v2.x), v3.x), 0.0f));
-                uint32_t max_x = f2u_sat(rmin(rmax(rmax(v1.x, v2.x), v3.x) + 1.0f, (float)fp.width));
-                uint32_t min_y = f2u_sat(rmax(rmin(rmin(v1.y, v2.y), v3.y), 0.0f));
-                uint32_t max_y = f2u_sat(rmin(rmax(rmax(v1.y, v2.y), v3.y) + 1.0f, (float)fp.height));
-                bool empty = min_x >= max_x || min_y >= max_y;
-                float area = (v2.y - v3.y) * (v1.x - v3.x) + (v3.x - v2.x) * (v1.y - v3.y);      // :1500
-                if (__builtin_fabsf(area) < K::AREA_EPS) empty = true;                            // :1501-1503
-                if (empty) { min_x = max_x = min_y = max_y = 0; }
-                r.bbx = min_x | (max_x << 16); r.bby = min_y | (max_y << 16);
-                span = pack_tile_span(r.bbx, r.bby, empty ? F_EMPTY : 0u, fp, n_tiles);
-                if (db.fill && n_tiles) {     // direct binning: the list slot in the first tile is requested now, used after the record build
-                    db_cls = db.with_class && transparent;
-                    const uint32_t t0 = ((span >> 16) & 0xFF) * fp.tiles_x + (span & 0xFF);
-                    agg_issue(db.fill, t0 * FILL_PAD + (db_cls ? 1u : 0u), true, threadIdx.x & 63u, db_first);
+                const int i2 = backface ? 2 : 1, i3 = backface ? 1 : 2;
+                const Winding s = { scr[0], scr[i2], scr[i3], 0, i2, i3 };
+                // ---- triangle prologue
+                TriSetup t = triangle_prologue(fp, s, out.span, out.n_tiles);
+                AggSlot db_first = { 0, 0, 0 }; bool db_cls = false;
+                if (b.db.fill && out.n_tiles) {     // direct binning: the list slot in the first tile is requested now, used after the record build
+                    db_cls = b.db.with_class && out.transparent;
+                    const uint32_t t0 = ((out.span >> 16) & 0xFF) * fp.tiles_x + (out.span & 0xFF);
+                    agg_issue(b.db.fill, t0 * FILL_PAD + (db_cls ? 1u : 0u), true, threadIdx.x & 63u, db_first);
                 }
                 // multi-GPU band sharding: every rank decides visibility for every face (triangles_drawn, painter's keys), but only the
                 // surfaces reaching its own rows are ever read again: the triangle prologue, the exactness guard, the lighting and the
                 // record build are skipped for all the others
-                const bool need_rec = !fp.band_only || n_tiles != 0;
+                const bool need_rec = !fp.band_only || out.n_tiles != 0;
                 bool slow = !fp.fixed_point || fp.ortho;
-                bool needs_dither = false;
-                r.inv_area = 0.0f; r.w0_start = r.w1_start = 0.0f; r.flags = 0;
-                // (the world normals of a lit frame are requested HERE, with the attributes, and used at the very end: behind the record
-                // build their round trip is hidden -- requested where they are used it was 12 of the lit kernel's 77 us, measured by
-                // replacing them with a constant)
-                V3 wn[3] = { { 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
                 if (need_rec) {
-                if (pos12 && fp.shading != B32_SHADE_NONE) {
-                    // packed streams, lit frame: attributes AND normal of a vertex from the 24-byte stream (one cache line per face instead
-                    // of one in the attribute stream and one in a normal stream of its own: 12 of the lit kernel's 77 us)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float* lp = attr12 + (size_t)fp.nv * 3 + (size_t)vi[j] * 6;
-                        uvx[j] = lp[0]; uvy[j] = lp[1]; col[j] = reinterpret_cast<const uint32_t*>(lp)[2];
-                        wn[j] = { lp[3], lp[4], lp[5] };
-                    }
-                } else if (pos12) {   // packed streams: the survivor's UVs and vertex colours only now (12 B per vertex, culled faces never fetch them)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float* ap = attr12 + (size_t)vi[j] * 3;
-                        uvx[j] = ap[0]; uvy[j] = ap[1]; col[j] = reinterpret_cast<const uint32_t*>(ap)[2];
-                    }
-                } else if (fp.shading != B32_SHADE_NONE) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        const float* np = reinterpret_cast<const float*>(verts) + (size_t)vi[j] * 9 + 5;
-                        wn[j] = { np[0], np[1], np[2] };
-                    }
+                    // ---- late attribute loads, exactness guard
+                    fetch_attributes(b, fp, mp, vi, camz, at);
+                    triangle_edges(s, t);
+                    if (!slow && !t.empty) slow = !walk_is_exact(s, t);
                 }
-                if (fp.placed && m_placed && fp.shading != B32_SHADE_NONE) {       // scene.rs:148-152: rotated with the mesh, not renormalised
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) wn[j] = { wn[j].x * pl_cos - wn[j].z * pl_sin, wn[j].y, wn[j].x * pl_sin + wn[j].z * pl_cos };
-                }
-                if (fp.has_fog && m_has_fog) {
-                    const uint32_t fogc = m_fog.r | (m_fog.g << 8) | (m_fog.b << 16) | ((uint32_t)m_fog.blend << 24);
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) col[j] = fog_color(col[j], fogc, fog_factor(camz[j], m_fog.start, m_fog.falloff));
-                }
-                r.inv_area = 1.0f / area;
-                r.a0 = v2.y - v3.y; r.b0 = v3.x - v2.x; r.a1 = v3.y - v1.y; r.b1 = v1.x - v3.x;   // :1507-1510
-                const float start_x = (float)min_x, start_y = (float)min_y;
-                r.w0_start = r.a0 * (start_x - v3.x) + r.b0 * (start_y - v3.y);                    // :1517
-                r.w1_start = r.a1 * (start_x - v3.x) + r.b1 * (start_y - v3.y);                    // :1518
-                // Closed-form eligibility: with integer vertices every value the reference's incremental walk ever holds
-                // is an exact integer when |w| < 2^24 over the bbox and both start products are < 2^24.
-                if (!slow && !empty) {
-                    const float lim = 4194304.0f;   // 2^22
-                    const float cmax = rmax(rmax(rmax(__builtin_fabsf(v1.x), __builtin_fabsf(v1.y)), rmax(__builtin_fabsf(v2.x), __builtin_fabsf(v2.y))),
-                                            rmax(__builtin_fabsf(v3.x), __builtin_fabsf(v3.y)));
-                    // quick acceptance (nearly every triangle): every edge coefficient is at most amax, every offset from v3 to a
-                    // corner of the clipped box at most dmax (integers below 2^23), so every product is at most amax * dmax and every
-                    // sum of two at most twice that; the float product rounds monotonically and 2^24 is representable
-                    const float amax = rmax(rmax(__builtin_fabsf(r.a0), __builtin_fabsf(r.b0)), rmax(__builtin_fabsf(r.a1), __builtin_fabsf(r.b1)));
-                    const float dmax = rmax(rmax(__builtin_fabsf((float)min_x - v3.x), __builtin_fabsf((float)(max_x - 1) - v3.x)),
-                                            rmax(__builtin_fabsf((float)min_y - v3.y), __builtin_fabsf((float)(max_y - 1) - v3.y)));
-                    if (!(cmax <= lim)) slow = true;
-                    else if (!(2.0f * (amax * dmax) < 16777216.0f)) {
-                        // every operand is an integer-valued float below 2^23, so each product / sum below is exact whenever its
-                        // true value is below 2^24, and rounds to >= 2^24 otherwise (rounding is monotonic and 2^24 is
-                        // representable): the float comparisons decide exactly what 64-bit integer arithmetic would
-                        const float dxs[2] = { (float)min_x - v3.x, (float)(max_x - 1) - v3.x };
-                        const float dys[2] = { (float)min_y - v3.y, (float)(max_y - 1) - v3.y };
-                        const float L = 16777216.0f;   // 2^24
-#pragma unroll
-                        for (int a = 0; a < 2; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) {
-                                const float p0 = r.a0 * dxs[a], q0 = r.b0 * dys[b], p1 = r.a1 * dxs[a], q1 = r.b1 * dys[b];
-                                if (!(__builtin_fabsf(p0) < L && __builtin_fabsf(q0) < L && __builtin_fabsf(p1) < L && __builtin_fabsf(q1) < L &&
-                                      __builtin_fabsf(p0 + q0) < L && __builtin_fabsf(p1 + q1) < L)) slow = true;
-                            }
-                    }
-                }
-                const bool vc_diff = (col[i1] != col[i2]) || (col[i2] != col[i3]);                  // Color equality incl. blend, types.rs:719
-                needs_dither = fp.dithering && (fp.shading == B32_SHADE_GOURAUD || have_tex || vc_diff);   // :1487-1492
-                const uint32_t eff_blend = have_tex ? tex_blend : face_blend;                       // :1450-1452
-                r.flags = (have_tex ? tid : F_TEX_NONE) | (black_tr ? F_BLACK_TR : 0) | (eff_blend << F_BLEND_SHIFT) |
-                          (needs_dither ? F_DITHER : 0) | (slow ? F_SLOW : 0) | (transparent ? F_TRANSP : 0) |
-                          (empty ? F_EMPTY : 0) | (editor_alpha << F_ALPHA_SHIFT);
-                }   // need_rec
-                // painter's key, render.rs:2529-2531 / 2538-2540. Perspective keys are > 5 (cam z > 0.1), so the sign bit
-                // is free: bit 31 = transparent class, low 31 bits = 0x7FFFFFFF - bits(z) => ascending radix == descending z,
-                // stability of the LSD passes == stability of slice::sort_by.
-                float kz = (v1.z + v2.z + v3.z) / 3.0f;
-                // z-buffer mode never sorts the opaque list (render.rs:2535): key 0 keeps it in face order through the stable
-                // passes, and a NaN key there is never compared
-                if (fp.zmode && !transparent) kz = 0.0f;
-                if (kz != kz) { nan_key = true; kz = 0.0f; }
-                if (kz == 0.0f) kz = 0.0f;                    // -0.0 == +0.0 under partial_cmp
-                uint32_t zb = __float_as_uint(kz);
-                key = ((0x7FFFFFFFu - (zb & 0x7FFFFFFFu)) & 0x7FFFFFFFu) | (transparent ? 0x80000000u : 0u);
-                // orthographic depths may be negative: all 32 bits order the depth (descending), the class partition is a pass of
-                // its own (launch_class_keys).  ~zsort_key(z) == 0xFFFFFFFF only for a NaN pattern, which was replaced above.
-                if (fp.ortho) key = ~zsort_key(kz);
-                if (fp.zmode && !transparent) key = 0;
-                if (key == KEY_INVALID) key = 0xFFFFFFFEu;    // unreachable for z > 5; keeps the sentinel unique
-                if (need_rec) {
-                    // vertices as i16 when all six are integers within range: the fixed-point snap yields integers (project_fixed), and
-                    // F_SLOW surfaces always take the wide form
-                    const float cmax16 = rmax(rmax(rmax(__builtin_fabsf(v1.x), __builtin_fabsf(v1.y)), rmax(__builtin_fabsf(v2.x), __builtin_fabsf(v2.y))),
-                                              rmax(__builtin_fabsf(v3.x), __builtin_fabsf(v3.y)));
-                    const bool fits = !slow && cmax16 <= 32767.0f;
-                    auto pk16 = [](float x, float y) { return ((uint32_t)(int32_t)x & 0xFFFFu) | ((uint32_t)(int32_t)y << 16); };
-                    uint4 c0, c1;
-                    c0.x = fits ? pk16(v1.x, v1.y) : COV_WIDE; c0.y = fits ? pk16(v2.x, v2.y) : 0u; c0.z = fits ? pk16(v3.x, v3.y) : 0u;
-                    c0.w = __float_as_uint(r.inv_area);
-                    c1 = make_uint4(r.bbx, r.bby, key, r.flags);
-                    uint4* cp = reinterpret_cast<uint4*>(recs.cov + rslot);
-                    cp[0] = c0; cp[1] = c1;
-                    const uint32_t slot = have_tex ? tid : F_TEX_NONE;
-                    const uint32_t shf = (black_tr ? SH_BLACK_TR : 0u) | (needs_dither ? SH_DITHER : 0u) | (slow ? SH_SLOW : 0u);
-                    uint4* sp = reinterpret_cast<uint4*>(recs.shade + rslot);
-                    sp[0] = make_uint4(__float_as_uint(v1.x), __float_as_uint(v1.y), __float_as_uint(v2.x), __float_as_uint(v2.y));
-                    sp[1] = make_uint4(__float_as_uint(v3.x), __float_as_uint(v3.y), __float_as_uint(r.inv_area), (col[i1] & 0xFFFFFFu) | ((slot & 0xFFu) << 24));
-                    sp[2] = make_uint4(__float_as_uint(uvx[i1]), __float_as_uint(uvx[i2]), __float_as_uint(uvx[i3]), __float_as_uint(uvy[i1]));
-                    sp[3] = make_uint4(__float_as_uint(uvy[i2]), __float_as_uint(uvy[i3]), (col[i2] & 0xFFFFFFu) | ((slot >> 8) << 24), (col[i3] & 0xFFFFFFu) | (shf << 24));
-                    if (fp.zmode || !fp.affine || slow) {
-                        uint4* xp = reinterpret_cast<uint4*>(recs.aux + rslot);
-                        xp[0] = make_uint4(__float_as_uint(1.0f / v1.z), __float_as_uint(1.0f / v2.z), __float_as_uint(1.0f / v3.z), __float_as_uint(r.w0_start));   // :1546-1548
-                        xp[1] = make_uint4(__float_as_uint(r.w1_start), 0u, 0u, 0u);
-                    }
-                }
-                if (db.fill && n_tiles) {     // the face id into the list of every tile of the span (any order inside a list)
-                    const uint32_t cap = db_cls ? db.cap_transparent : db.cap_opaque;
-                    const uint32_t tx0 = span & 0xFF, tx1 = (span >> 8) & 0xFF, ty0 = (span >> 16) & 0xFF;
-                    bool over = false;
-                    uint32_t tx = tx0, ty = ty0;
-                    AggSlot g = db_first;
-                    // the k-th tile of every lane's span together (wave-uniform loop: the group ballots need every lane of this block)
-                    for (uint32_t k = 0; __ballot(k < n_tiles); ++k) {
-                        const bool act = k < n_tiles;
-                        const uint32_t tile = ty * fp.tiles_x + tx;
-                        if (k) agg_issue(db.fill, tile * FILL_PAD + (db_cls ? 1u : 0u), act, threadIdx.x & 63u, g);
-                        const uint32_t pos = agg_position(g);
-                        if (act) {
-                            if (pos < cap) db.lists[(size_t)tile * db.region + (db_cls ? db.region - 1u - pos : pos)] = rslot;
-                            else over = true;
-                            if (++tx > tx1) { tx = tx0; ++ty; }
-                        }
-                    }
-                    if (over) { Events* ev = events_of(ctrl); if (db_cls) ev->long_transparent = db.epoch; else ev->overflow = db.epoch; }
-                }
-                // (the shades last: the record's values are stored and dead by now, the lighting has the registers to itself)
-                if (need_rec && fp.shading != B32_SHADE_NONE) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) if (backface) wn[j] = scale3(wn[j], -1.0f);
-                    float* sh = shades + (size_t)rslot * 9;
-                    if (fp.shading == B32_SHADE_FLAT) {                                             // :1466-1469
-                        V3 center = scale3(add3(add3(wpos[i1], wpos[i2]), wpos[i3]), 1.0f / 3.0f);
-                        V3 nrm = normalize3(scale3(add3(add3(wn[i1], wn[i2]), wn[i3]), 1.0f / 3.0f));
-                        float s[3]; shade_multi(nrm, center, lights, fp.n_lights, m_ambient, s);
-                        for (int j = 0; j < 9; ++j) sh[j] = s[j % 3];
-                    } else {                                                                        // :1475-1483
-                        shade_multi(wn[i1], wpos[i1], lights, fp.n_lights, m_ambient, sh);
-                        shade_multi(wn[i2], wpos[i2], lights, fp.n_lights, m_ambient, sh + 3);
-                        shade_multi(wn[i3], wpos[i3], lights, fp.n_lights, m_ambient, sh + 6);
-                    }
-                }
+                // ---- painter's key, records, direct binning, shades
+                out.key = painter_key(s.v1.z, s.v2.z, s.v3.z, out.transparent, fp, out.nan_key);
+                if (need_rec) store_records(b.recs, fp, rslot, s, t, fm, at, out.key, slow, out.transparent);
+                if (b.db.fill && out.n_tiles) bin_span(b.db, fp, b.ctrl, out.span, out.n_tiles, db_cls, db_first, rslot);
+                if (need_rec && fp.shading != B32_SHADE_NONE) store_shades(b.shades, lights, fp, mp.ambient, rslot, backface, s, wpos, at.wn);
             }
         }
-        if (fp.wire_collect && bad_index) wire[f].kind = 0;
+        if (fp.wire_collect && out.bad_index) b.wire[f].kind = 0;
     }
-    // frame counters: ballot per wave -> LDS -> one 5-word record per block (reduced by k_after_setup; no atomics)
-    const unsigned long long mv = __ballot(visible), mt = __ballot(transparent);
-    {   // painter's key and tile span per SLOT (see `slot` above): survivors at the front of the wave's 64 slots, KEY_INVALID behind them
-        const uint32_t lane = threadIdx.x & 63u, nvis = (uint32_t)__popcll(mv), wbase = f - lane;
-        if (visible) {
-            const uint32_t slot = wbase + (uint32_t)__popcll(mv & ((1ull << lane) - 1ull));
-            keys[slot] = key;
-            if (spans) spans[slot] = span;
-            if (face_of) face_of[slot] = f;
-        }
-        if (in.live && lane >= nvis) { keys[wbase + lane] = KEY_INVALID; if (spans) spans[wbase + lane] = 0xFFFFFFFFu; }
-    }
-    const unsigned long long mn_op = __ballot(nan_key && !transparent), mn_tr = __ballot(nan_key && transparent), mb = __ballot(bad_index);
-    const uint32_t wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        wpart[wv][0] = (uint32_t)__popcll(mv); wpart[wv][1] = (uint32_t)__popcll(mt);
-        wpart[wv][2] = (uint32_t)__popcll(mn_op); wpart[wv][3] = (uint32_t)__popcll(mn_tr); wpart[wv][4] = mb ? 1u : 0u;
-        if (db.fill && (mn_op | mn_tr | mb)) {   // direct binning: nobody reduces the counters before the fill, which only does so after one of these
-            Events* ev = events_of(ctrl);
-            if (mb) ev->bad_index = db.epoch;
-            if (mn_op) ev->nan_opaque = db.epoch;
-            if (mn_tr) ev->nan_transparent = db.epoch;
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) n_tiles += __shfl_down(n_tiles, off);      // (tile, surface) pairs of this block
-    if ((threadIdx.x & 63) == 0) wpart[wv][5] = n_tiles;
-    __syncthreads();
-    // (one record per group of 256 faces, as before: the consumers index them by face / 256)
-    const uint32_t grp = blockIdx.x * SETUP_FPT + g;
-    if (threadIdx.x < 6 && grp * 256u < fp.nf) partials[grp * 8 + threadIdx.x] = wpart[0][threadIdx.x] + wpart[1][threadIdx.x] + wpart[2][threadIdx.x] + wpart[3][threadIdx.x];
-    __syncthreads();
-    }   // SETUP_FPT faces per thread
+    publish_wave(b, f, in.live, out, wpart);
 }
 
-void launch_setup(hipStream_t s, const FrameParams& fp, const B32Vertex* verts, const B32Face* faces, const TexDesc* tex,
-                  const B32Light* lights, const LightSet& ls, const MeshTable& mt, const PlaceTable& pt, RecArrays recs, const DirectBin& db, float* shades, uint32_t* keys, uint32_t* spans, uint32_t* partials,
-                  Ctrl* ctrl, WireTri* wire, int n_cu, const float* pos12, const float* attr12, uint32_t* face_of) {
-    (void)n_cu;
+void launch_setup(hipStream_t s, const SetupArgs& a) {
+    const FrameParams& fp = a.fp;
     if (fp.nf == 0) return;
     // (a placed draw takes the general form: the specialised ones compile the placement out, like fog and the mesh table)
     const bool plain = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading == B32_SHADE_NONE && !fp.xray && !fp.batched && !fp.placed;
-    // one face per thread: 52 VGPRs in the plain form = 8 waves per SIMD (two faces per thread with their loads issued up front: 73 VGPRs,
-    // 43 us instead of 39 at 1 M faces; three: 49 us)
+    // one face per thread: 55 VGPRs in the plain form = 8 waves per SIMD
     const dim3 g1((fp.nf + 255) / 256);
     const bool lit = fp.fixed_point && !fp.ortho && !fp.has_fog && !fp.wire_collect && fp.shading != B32_SHADE_NONE && !fp.xray && !fp.batched && !fp.placed;
-    if (lit) hipLaunchKernelGGL((k_setup<1, 2>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
-    else if (plain) hipLaunchKernelGGL((k_setup<1, 1>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
-    else hipLaunchKernelGGL((k_setup<1, 0>), g1, dim3(256), 0, s, fp, verts, faces, tex, lights, ls, mt, pt, recs, db, shades, keys, spans, partials, ctrl, wire, pos12, attr12, face_of);
+    if (lit) hipLaunchKernelGGL(k_setup<2>, g1, dim3(256), 0, s, a);
+    else if (plain) hipLaunchKernelGGL(k_setup<1>, g1, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_setup<0>, g1, dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------- merged mesh of a batched frame
