@@ -16,6 +16,28 @@ __device__ __forceinline__ bool ztest(const Tri& t, float bcx, float bcy, float 
     return ((t.flags >> F_ALPHA_SHIFT) < 255) ? !(z >= zb) : (z < zb);
 }
 
+// texel_drawn<0, FMT8> for the ordered pass, in the order the parent's code had: u and v, then the two sentinels of texel_address as
+// branches in front of the fetch, then ONE texel_rule on what the three paths leave (-1, -2, or a fetched texel).  Through texel_drawn
+// a sign test and the rule's two sentinel selects stand behind the fetch of every fragment, and k_blend measured 1 % slower; with the
+// sentinels as three calls of the rule it still did (profiles/texel_address_resources.md).  This form compiles to the parent's
+// instructions up to their order.  The arithmetic is interp_uv's and texel_index's.
+template <bool FMT8>
+__device__ __forceinline__ bool texel_drawn_ordered(const FillArgs& a, const Tri& t, float bcx, float bcy, float bcz, bool affine, uint32_t& texel) {
+    int taddr = -1;
+    uint32_t fetched = 0;
+    if ((t.flags & F_TEX_MASK) != F_TEX_NONE) {
+        float u, v;
+        interp_uv(bcx, bcy, bcz, t.u1, t.u2, t.u3, t.v1, t.v2, t.v3, t.iz1, t.iz2, t.iz3, affine, u, v);
+        taddr = -2;
+        if (t.tw != 0 && t.th != 0) {
+            const uint32_t ti = t.toff + texel_index(u, v, t.tw, t.th);
+            taddr = 0;
+            fetched = FMT8 ? a.texels32[ti] : (uint32_t)a.texels[ti];
+        }
+    }
+    return texel_rule<FMT8>(t.flags, taddr, fetched, texel);
+}
+
 // One fragment of the ordered pass at a pixel the inside test accepted.  Returns true when a pixel store happened.
 template <bool FMT8>
 __device__ __forceinline__ bool blend_fragment(const FillArgs& a, const Tri& tr, float bcx, float bcy, float bcz, uint32_t px, uint32_t py,
@@ -34,14 +56,14 @@ __device__ __forceinline__ bool blend_fragment(const FillArgs& a, const Tri& tr,
             const float zb = *zdst;
             if (alpha < 255 ? (z >= zb) : !(z < zb)) return false;               // render.rs:387 / :432, :1407
         }
-        if (!texel_drawn<0, true>(tr, bcx, bcy, bcz, reinterpret_cast<const uint16_t*>(a.texels32), nullptr, texel, affine)) return false;
+        if (!texel_drawn_ordered<true>(a, tr, bcx, bcy, bcz, affine, texel)) return false;
         const uint32_t col = shade8(texel, bcx, bcy, bcz, vc1, vc2, vc3, tr.flags, shading, shv, px, py);
         if (zmode) *zdst = z;
         *dst = store8(*dst, col, alpha);
         return true;
     }
     if (!ztest(tr, bcx, bcy, bcz, zmode, *zdst)) return false;
-    if (!texel_drawn<0>(tr, bcx, bcy, bcz, a.texels, nullptr, texel, affine)) return false;
+    if (!texel_drawn_ordered<false>(a, tr, bcx, bcy, bcz, affine, texel)) return false;
     const uint32_t out15 = shade15(texel, bcx, bcy, bcz, vc1, vc2, vc3, tr.flags, shading, shv, px, py);
     *dst = store_blend(*dst, out15, tr.flags, xray);
     return true;
@@ -230,7 +252,7 @@ __global__ __launch_bounds__(NT, 5) void k_blend(FillArgs a) {        // 5 waves
                     const uint32_t j = (uint32_t)__builtin_ctzll(m);
                     m &= m - 1ull;
                     const uint4 r0 = srec[j * SREC_Q], r1 = srec[j * SREC_Q + 1];
-                    Tri t;
+                    Tri t;                                  // (only what the inside test reads: direct loads, not tri_from_view -- this loop searches)
                     t.x3 = __uint_as_float(r0.x); t.y3 = __uint_as_float(r0.y); t.a0 = __uint_as_float(r0.z); t.b0 = __uint_as_float(r0.w);
                     t.a1 = __uint_as_float(r1.x); t.b1 = __uint_as_float(r1.y); t.inv_area = __uint_as_float(r1.z);
                     const uint32_t py = ty_top + wave + ri * NW;
@@ -259,24 +281,21 @@ __global__ __launch_bounds__(NT, 5) void k_blend(FillArgs a) {        // 5 waves
                 if (k < n) {
                     const uint32_t e = mylist[k * 64 + lane], j = e & 63u, row = wave + (e >> 6) * NW;
                     const uint32_t py = ty_top + row, ti = row * BT_STRIDE + lane;
-                    const uint4 r0 = srec[j * SREC_Q], r1 = srec[j * SREC_Q + 1], r2 = srec[j * SREC_Q + 2], r3 = srec[j * SREC_Q + 3], r4 = srec[j * SREC_Q + 4], r6 = srec[j * SREC_Q + 6];
-                    Tri tr;
-                    tr.x3 = __uint_as_float(r0.x); tr.y3 = __uint_as_float(r0.y); tr.a0 = __uint_as_float(r0.z); tr.b0 = __uint_as_float(r0.w);
-                    tr.a1 = __uint_as_float(r1.x); tr.b1 = __uint_as_float(r1.y); tr.inv_area = __uint_as_float(r1.z);
-                    tr.u1 = __uint_as_float(r2.y); tr.u2 = __uint_as_float(r2.z); tr.u3 = __uint_as_float(r2.w);
-                    tr.v1 = __uint_as_float(r3.x); tr.v2 = __uint_as_float(r3.y); tr.v3 = __uint_as_float(r3.z);
-                    tr.flags = r3.w;
+                    // the staged quads 0..4 are the surface's RecView, quad 6 its texture + face id; quad 5 is read where something of it is
+                    // used, as before: the literal walk's start value in its branch, the 1/z terms (perspective-correct UVs, the 8-bit path's
+                    // depth test) behind the inside test -- read in front of tri_from_view they cost a branch and an LDS read per fragment
+                    const bool slow = (slowmask >> j) & 1ull;
+                    RecView rv;
+                    rv.q0 = srec[j * SREC_Q]; rv.q1 = srec[j * SREC_Q + 1]; rv.q2 = srec[j * SREC_Q + 2]; rv.q3 = srec[j * SREC_Q + 3]; rv.q4 = srec[j * SREC_Q + 4];
+                    rv.q5 = make_uint4(0, 0, 0, 0);
+                    const uint4 r4 = rv.q4, r6 = srec[j * SREC_Q + 6];
+                    Tri tr = tri_from_view(rv, true);
                     tr.tw = r6.x; tr.th = r6.y; tr.toff = r6.z;
-                    tr.iz1 = tr.iz2 = tr.iz3 = 0.0f;
                     float w0, w1, bcx, bcy, bcz;
-                    if (!((slowmask >> j) & 1ull)) {
+                    if (!slow) {                            // exact integers (k_setup guard): closed form == accumulation
                         const float dx = (float)px - tr.x3, dy = (float)py - tr.y3;
                         w0 = tr.a0 * dx + tr.b0 * dy; w1 = tr.a1 * dx + tr.b1 * dy;
-                    } else {
-                        tr.min_x = r1.w & 0xFFFF; tr.min_y = r2.x & 0xFFFF;
-                        tr.w0_start = __uint_as_float(r4.w); tr.w1_start = __uint_as_float(srec[j * SREC_Q + 5].x);
-                        replay_w(tr, px, py, w0, w1);
-                    }
+                    } else { tr.w1_start = __uint_as_float(srec[j * SREC_Q + 5].x); replay_w(tr, px, py, w0, w1); }      // (quad 5's start value read here, where it is used)
                     (void)inside_bc(tr, w0, w1, bcx, bcy, bcz);          // (passed in (A): the barycentrics again)
                     if (!affine || (FMT8 && zmode)) { const uint4 r5 = srec[j * SREC_Q + 5]; tr.iz1 = __uint_as_float(r5.y); tr.iz2 = __uint_as_float(r5.z); tr.iz3 = __uint_as_float(r5.w); }
                     float shv[9];

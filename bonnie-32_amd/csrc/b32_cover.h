@@ -365,7 +365,7 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
                 Pj[j] = P; ta[j] = -1;
                 if (in[j]) {
                     if (ZMODE) { uint32_t zkey; in[j] = frag_zkey(tr, cx, cy, cz, zkey); Pj[j] = ((unsigned long long)(~zkey) << 32) | (uint32_t)P; }
-                    ta[j] = tri_texel_addr(tr, cx, cy, cz, affine);
+                    ta[j] = texel_address(tr, cx, cy, cz, affine);
                 }
             }
             uint32_t mw[4];
@@ -379,7 +379,7 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             for (int j = 0; j < 4; ++j) {
                 // skippable texel: the mask bit; a zero-size texture samples TRANSPARENT (-2), no texture samples WHITE (-1)
                 const bool blk = ta[j] == -2 ? true : (ta[j] >= 0 && ((mw[j] >> ((uint32_t)ta[j] & 31u)) & 1u));
-                in[j] = in[j] && !(FMT8 ? blk : (blk && (tr.flags & F_BLACK_TR)));       // render.rs:1591-1608 / 8-bit :1348-1352
+                in[j] = in[j] && !(FMT8 ? blk : (blk && (tr.flags & F_BLACK_TR)));       // texel_rule, on the mask bit instead of the texel
                 any |= in[j];
                 drawn += in[j] ? 1u : 0u;
             }
@@ -410,13 +410,8 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             // lasts as long as its longest remainder: with the ~25-px rows of C5 most lanes idle behind the longest)
             constexpr uint32_t DT = (uint32_t)B32_DRAIN_TRIPS * (uint32_t)B32_TRIP;
             if (EXACT) {
-                Tri tr;
-                tr.u1 = bpermf(s, __uint_as_float(b.q2.y)); tr.u2 = bpermf(s, __uint_as_float(b.q2.z)); tr.u3 = bpermf(s, __uint_as_float(b.q2.w));
-                tr.v1 = bpermf(s, __uint_as_float(b.q3.x)); tr.v2 = bpermf(s, __uint_as_float(b.q3.y)); tr.v3 = bpermf(s, __uint_as_float(b.q3.z));
-                tr.flags = bperm(s, flags);
-                tr.tw = bperm(s, b.tw); tr.th = bperm(s, b.th); tr.toff = bperm(s, b.toff);
-                tr.iz1 = z1; tr.iz2 = z2; tr.iz3 = z3;
-                if (!affine && !ZMODE) { tr.iz1 = bpermf(s, __uint_as_float(b.q5.y)); tr.iz2 = bpermf(s, __uint_as_float(b.q5.z)); tr.iz3 = bpermf(s, __uint_as_float(b.q5.w)); }
+                Tri tr = tri_uv_from_lane(b, s, flags, !affine && !ZMODE);
+                if (ZMODE) { tr.iz1 = z1; tr.iz2 = z2; tr.iz3 = z3; }              // (gathered above for either coverage)
                 uint32_t mine = 0;
 #pragma unroll
                 for (uint32_t i = 0; i < DT; i += 4) mine += exact_trip(tr, addr, w0, w1, sa0, sa1, sinv, i < n ? n - i : 0u, P);
@@ -533,14 +528,8 @@ __device__ __forceinline__ unsigned long long phase_a_rows(const FillArgs& a, ui
             const float sx3 = bpermf(s, __uint_as_float(b.q0.x)), sy3 = bpermf(s, __uint_as_float(b.q0.y));
             const float sa0 = bpermf(s, a0), sb0 = bpermf(s, b0), sa1 = bpermf(s, a1), sb1 = bpermf(s, b1);
             const float sinv = bpermf(s, __uint_as_float(b.q1.z));
-            Tri tr;                                                                              // per-lane view (EXACT only)
-            if (EXACT) {
-                tr.u1 = bpermf(s, __uint_as_float(b.q2.y)); tr.u2 = bpermf(s, __uint_as_float(b.q2.z)); tr.u3 = bpermf(s, __uint_as_float(b.q2.w));
-                tr.v1 = bpermf(s, __uint_as_float(b.q3.x)); tr.v2 = bpermf(s, __uint_as_float(b.q3.y)); tr.v3 = bpermf(s, __uint_as_float(b.q3.z));
-                tr.flags = bperm(s, flags);
-                tr.tw = bperm(s, b.tw); tr.th = bperm(s, b.th); tr.toff = bperm(s, b.toff);
-                if (!affine || ZMODE) { tr.iz1 = bpermf(s, __uint_as_float(b.q5.y)); tr.iz2 = bpermf(s, __uint_as_float(b.q5.z)); tr.iz3 = bpermf(s, __uint_as_float(b.q5.w)); }
-            }
+            Tri tr = {};                                                                         // per-lane view (EXACT only)
+            if (EXACT) tr = tri_uv_from_lane(b, s, flags, !affine || ZMODE);
             uint32_t rx0 = sbox & 0xFF;
             const uint32_t rx1 = (sbox >> 8) & 0xFF, ry = (sbox >> 16) + (k - sP);              // tile-local
             uint32_t n = valid ? rx1 - rx0 : 0u;

@@ -1,7 +1,9 @@
 // b32_fill_common.h -- device helpers shared by the fill kernels (b32_fill.hip: the fused coverage + shading kernel and the keyed k_cover;
-// b32_shade.hip: k_shade of the keyed pipelines; b32_blend.hip: the ordered transparent pass): texture sampling and the transparency
-// rule (types.rs:671-681, render.rs:1563-1607), the colour pipelines of both pixel formats (render.rs:1613-1661, 1355-1387), the pixel
-// stores (render.rs:445-502, 567-628), the per-surface record views and the per-pixel hit test the shading phases and repair paths use.
+// b32_shade.hip: k_shade of the keyed pipelines; b32_blend.hip: the ordered transparent pass): texture addressing and the transparency
+// rule, each stated once (interp_uv, texel_index / texel_address, texel_rule: render.rs:1563-1608, types.rs:671-681), the colour
+// pipelines of both pixel formats (render.rs:1613-1661, 1355-1387), the pixel stores (render.rs:445-502, 567-628), the per-surface
+// record views with their one unpacking into a Tri (tri_from_view; over lanes tri_from_batch, tri_uv_from_lane) and the per-pixel hit
+// test the shading phases and repair paths use.
 // Bit-exactness: barycentrics use the reference's expression order; the edge functions are evaluated from exact integers only for
 // surfaces k_setup proved exact (integer coordinates, every intermediate < 2^24), otherwise the incremental walk (render.rs:1706-1712)
 // is replayed literally.
@@ -45,17 +47,6 @@ struct Tri {            // one SurfRec (+ its texture), wave-uniform in phase A/
     uint32_t tw, th, toff;
 };
 
-template <int TEXMODE>
-__device__ __forceinline__ uint32_t sample15(const Tri& t, const uint16_t* __restrict__ gtex, const uint16_t* ltex, float u, float v) {
-    // Texture15::sample, types.rs:671-681
-    if (t.tw == 0 || t.th == 0) return 0;
-    const float uw = rem_euclid1(u), vw = rem_euclid1(v);
-    const uint32_t tx = min(f2u_sat(uw * (float)t.tw), t.tw - 1);
-    const uint32_t ty = min(f2u_sat(vw * (float)t.th), t.th - 1);
-    if (TEXMODE == 1) return ltex[ty * t.tw + tx];
-    return gtex[t.toff + ty * t.tw + tx];
-}
-
 __device__ __forceinline__ bool inside_bc(const Tri& t, float w0, float w1, float& bcx, float& bcy, float& bcz) {
     bcx = w0 * t.inv_area;                                       // render.rs:1536-1542
     bcy = w1 * t.inv_area;
@@ -66,69 +57,65 @@ __device__ __forceinline__ bool inside_bc(const Tri& t, float w0, float w1, floa
     return (__builtin_fminf(bcx, bcy) >= ERR) & (bcz >= ERR);
 }
 
-// Texture::sample of the 8-bit-colour path (types.rs:1242-1253): Color texel r | g<<8 | b<<16 | blend<<24
-__device__ __forceinline__ uint32_t sample8(const Tri& t, const uint32_t* __restrict__ gtex, float u, float v) {
-    if (t.tw == 0 || t.th == 0) return (uint32_t)B32_BLEND_ERASE << 24;                 // Color::TRANSPARENT
-    const float uw = rem_euclid1(u), vw = rem_euclid1(v);
-    const uint32_t tx = min(f2u_sat(uw * (float)t.tw), t.tw - 1);
-    const uint32_t ty = min(f2u_sat(vw * (float)t.th), t.th - 1);
-    return gtex[t.toff + ty * t.tw + tx];
-}
-
-// Texel address of a fragment (index into the texel pool): -1 = untextured (white), -2 = zero-size texture (transparent sample).
-// Same arithmetic as texel_drawn / Texture15::sample (types.rs:671-681); split off so that several fetches can be in flight.
-__device__ __forceinline__ int tri_texel_addr(const Tri& t, float bcx, float bcy, float bcz, bool affine) {
-    if ((t.flags & F_TEX_MASK) == F_TEX_NONE) return -1;
-    if (t.tw == 0 || t.th == 0) return -2;
-    float u, v;
+// u, v of a fragment from its barycentrics: affine (render.rs:1565-1566) or perspective-correct (render.rs:1568-1579), in the
+// reference's association; the division is the correctly rounded one.
+__device__ __forceinline__ void interp_uv(float bcx, float bcy, float bcz, float u1, float u2, float u3, float v1, float v2, float v3,
+                                          float iz1, float iz2, float iz3, bool affine, float& u, float& v) {
     if (affine) {
-        u = bcx * t.u1 + bcy * t.u2 + bcz * t.u3;
-        v = bcx * t.v1 + bcy * t.v2 + bcz * t.v3;
+        u = bcx * u1 + bcy * u2 + bcz * u3;
+        v = bcx * v1 + bcy * v2 + bcz * v3;
     } else {
-        const float inv_z = bcx * t.iz1 + bcy * t.iz2 + bcz * t.iz3;
-        const float u_over_z = bcx * t.u1 * t.iz1 + bcy * t.u2 * t.iz2 + bcz * t.u3 * t.iz3;
-        const float v_over_z = bcx * t.v1 * t.iz1 + bcy * t.v2 * t.iz2 + bcz * t.v3 * t.iz3;
+        const float inv_z = bcx * iz1 + bcy * iz2 + bcz * iz3;
+        const float u_over_z = bcx * u1 * iz1 + bcy * u2 * iz2 + bcz * u3 * iz3;
+        const float v_over_z = bcx * v1 * iz1 + bcy * v2 * iz2 + bcz * v3 * iz3;
         u = u_over_z / inv_z;
         v = v_over_z / inv_z;
     }
-    const float uw = rem_euclid1(u), vw = rem_euclid1(1.0f - v);
-    const uint32_t tx = min(f2u_sat(uw * (float)t.tw), t.tw - 1);
-    const uint32_t ty = min(f2u_sat(vw * (float)t.th), t.th - 1);
-    return (int)(t.toff + ty * t.tw + tx);
 }
-
-// Texel fetch + transparency rules (render.rs:1563-1607; 8-bit path render.rs:1322-1352). Returns false when the fragment is skipped.
-template <int TEXMODE, bool FMT8 = false>
-__device__ __forceinline__ bool texel_drawn(const Tri& t, float bcx, float bcy, float bcz, const uint16_t* __restrict__ gtex,
-                                            const uint16_t* ltex, uint32_t& texel, bool affine = true) {
-    uint32_t c = FMT8 ? 0x00FFFFFFu : K::C15_WHITE;              // Color::WHITE (render.rs:1344) / Color15::WHITE (render.rs:1585)
-    if ((t.flags & F_TEX_MASK) != F_TEX_NONE) {
-        float u, v;
-        if (affine) {
-            u = bcx * t.u1 + bcy * t.u2 + bcz * t.u3;            // affine, render.rs:1565-1566
-            v = bcx * t.v1 + bcy * t.v2 + bcz * t.v3;
-        } else {                                                 // perspective-correct, render.rs:1568-1579
-            const float inv_z = bcx * t.iz1 + bcy * t.iz2 + bcz * t.iz3;
-            const float u_over_z = bcx * t.u1 * t.iz1 + bcy * t.u2 * t.iz2 + bcz * t.u3 * t.iz3;
-            const float v_over_z = bcx * t.v1 * t.iz1 + bcy * t.v2 * t.iz2 + bcz * t.v3 * t.iz3;
-            u = u_over_z / inv_z;
-            v = v_over_z / inv_z;
-        }
-        if (FMT8) c = sample8(t, reinterpret_cast<const uint32_t*>(gtex), u, 1.0f - v);   // render.rs:1342
-        else c = sample15<TEXMODE>(t, gtex, ltex, u, 1.0f - v);  // render.rs:1583
-    }
-    if (FMT8) {                                                  // color.is_transparent(), render.rs:1348-1352
+// Texture15::sample / Texture::sample (types.rs:671-681 / :1242-1253) of (u, 1 - v) (render.rs:1583 / :1342) as a texel index: flip,
+// wrap, scale, saturating cast, clamp, row stride.  w and h are not zero; wf, hf are (float)w, (float)h (the straight-line shading
+// phase converts its one texture's size per tile: left to texel_index, its step gains five moves).
+__device__ __forceinline__ uint32_t texel_index(float u, float v, uint32_t w, uint32_t h, float wf, float hf) {
+    const float uw = rem_euclid1(u), vw = rem_euclid1(1.0f - v);
+    const uint32_t tx = min(f2u_sat(uw * wf), w - 1);
+    const uint32_t ty = min(f2u_sat(vw * hf), h - 1);
+    return ty * w + tx;
+}
+__device__ __forceinline__ uint32_t texel_index(float u, float v, uint32_t w, uint32_t h) { return texel_index(u, v, w, h, (float)w, (float)h); }
+// Texel address of a fragment (index into the texel pool, or into the LDS-staged texture, whose toff is 0): -1 = untextured (samples
+// WHITE), -2 = zero-size texture (samples TRANSPARENT).  Split from the fetch so that several fetches can be in flight.
+__device__ __forceinline__ int texel_address(const Tri& t, float bcx, float bcy, float bcz, bool affine) {
+    if ((t.flags & F_TEX_MASK) == F_TEX_NONE) return -1;
+    if (t.tw == 0 || t.th == 0) return -2;
+    float u, v;
+    interp_uv(bcx, bcy, bcz, t.u1, t.u2, t.u3, t.v1, t.v2, t.v3, t.iz1, t.iz2, t.iz3, affine, u, v);
+    return (int)(t.toff + texel_index(u, v, t.tw, t.th));
+}
+// Transparency rule on the fetched texel (render.rs:1591-1608; 8-bit path :1348-1352, color.is_transparent()); `fetched` is ignored for
+// the sentinel addresses.  Returns false when the fragment is skipped.
+template <bool FMT8>
+__device__ __forceinline__ bool texel_rule(uint32_t flags, int taddr, uint32_t fetched, uint32_t& texel) {
+    if (FMT8) {                                                  // Color::WHITE (render.rs:1344) / Color::TRANSPARENT
+        const uint32_t c = taddr == -1 ? 0x00FFFFFFu : (taddr == -2 ? ((uint32_t)B32_BLEND_ERASE << 24) : fetched);
         texel = c;
         return (c >> 24) != B32_BLEND_ERASE;
     }
+    uint32_t c = taddr == -1 ? K::C15_WHITE : (taddr == -2 ? K::C15_TRANSPARENT : fetched);     // Color15::WHITE, render.rs:1585
     if (c == K::C15_TRANSPARENT) {                               // render.rs:1592-1602
-        if (t.flags & F_BLACK_TR) return false;
+        if (flags & F_BLACK_TR) return false;
         c = K::C15_BLACK_DRAWABLE;
-    } else if ((t.flags & F_BLACK_TR) && (c & ~K::C15_SEMI_BIT & 0xFFFFu) == 0) {    // is_black: r5 == g5 == b5 == 0, render.rs:1603-1608
-        return false;
-    }
+    } else if ((flags & F_BLACK_TR) && (c & ~K::C15_SEMI_BIT & 0xFFFFu) == 0) return false;   // is_black: r5 == g5 == b5 == 0, render.rs:1603-1608
     texel = c;
     return true;
+}
+// Texel address, fetch (TEXMODE 1: the LDS-staged texture; FMT8: Color words r | g<<8 | b<<16 | blend<<24) and the rule.
+template <int TEXMODE, bool FMT8 = false>
+__device__ __forceinline__ bool texel_drawn(const Tri& t, float bcx, float bcy, float bcz, const uint16_t* __restrict__ gtex,
+                                            const uint16_t* ltex, uint32_t& texel, bool affine = true) {
+    const int taddr = texel_address(t, bcx, bcy, bcz, affine);
+    uint32_t fetched = 0;
+    if (taddr >= 0) fetched = TEXMODE == 1 ? ltex[taddr] : (FMT8 ? reinterpret_cast<const uint32_t*>(gtex)[taddr] : (uint32_t)gtex[taddr]);
+    return texel_rule<FMT8>(t.flags, taddr, fetched, texel);
 }
 
 // Colour pipeline (render.rs:1613-1661): modulate by interpolated vertex colour, shade, dither, quantize to RGB555.
@@ -384,6 +371,23 @@ __device__ __forceinline__ Tri tri_from_batch(const Batch& b, int t, bool full) 
     if (full) { r.iz1 = bcf(__uint_as_float(b.q5.y), t); r.iz2 = bcf(__uint_as_float(b.q5.z), t); r.iz3 = bcf(__uint_as_float(b.q5.w), t); }
     return r;
 }
+// The one unpacking of a surface's RecView (q0..q5) into a Tri: edges, 1/area, bounding box, flags, the literal walk's start values and,
+// with_uv, the UVs and 1/z terms.  The texture (tw, th, toff) is not part of the view: zero here, the caller binds it.
+__device__ __forceinline__ Tri tri_from_view(const RecView& r, bool with_uv) {
+    Tri t;
+    t.x3 = __uint_as_float(r.q0.x); t.y3 = __uint_as_float(r.q0.y); t.a0 = __uint_as_float(r.q0.z); t.b0 = __uint_as_float(r.q0.w);
+    t.a1 = __uint_as_float(r.q1.x); t.b1 = __uint_as_float(r.q1.y); t.inv_area = __uint_as_float(r.q1.z);
+    t.min_x = r.q1.w & 0xFFFF; t.max_x = r.q1.w >> 16; t.min_y = r.q2.x & 0xFFFF; t.max_y = r.q2.x >> 16;
+    t.flags = r.q3.w;
+    t.w0_start = __uint_as_float(r.q4.w); t.w1_start = __uint_as_float(r.q5.x);
+    t.u1 = t.u2 = t.u3 = t.v1 = t.v2 = t.v3 = 0.0f; t.iz1 = t.iz2 = t.iz3 = 0.0f; t.tw = t.th = t.toff = 0;
+    if (with_uv) {
+        t.u1 = __uint_as_float(r.q2.y); t.u2 = __uint_as_float(r.q2.z); t.u3 = __uint_as_float(r.q2.w);
+        t.v1 = __uint_as_float(r.q3.x); t.v2 = __uint_as_float(r.q3.y); t.v3 = __uint_as_float(r.q3.z);
+        t.iz1 = __uint_as_float(r.q5.y); t.iz2 = __uint_as_float(r.q5.z); t.iz3 = __uint_as_float(r.q5.w);
+    }
+    return t;
+}
 // Records a drawn fragment of list entry li in the tile buffer(s).
 //   painter's EXACT: max list position.  painter's CHEAP: exact top-2 (see k_cover).  z-buffer: min of (depth key, list position)
 //   == the first surface in face order reaching the smallest depth, what the sequential `z < zbuffer` test leaves behind.
@@ -411,50 +415,36 @@ __device__ __forceinline__ bool frag_zkey(const Tri& t, float bcx, float bcy, fl
 __device__ inline float exact_depth_at(const FillArgs& a, uint32_t sid, uint32_t px, uint32_t py) {
     RecView rv;
     load_full_view(a, sid, rv);
-    const uint4 q0 = rv.q0, q1 = rv.q1, q2 = rv.q2, q3 = rv.q3, q4 = rv.q4, q5 = rv.q5;
-    Tri tr;
-    tr.x3 = __uint_as_float(q0.x); tr.y3 = __uint_as_float(q0.y); tr.a0 = __uint_as_float(q0.z); tr.b0 = __uint_as_float(q0.w);
-    tr.a1 = __uint_as_float(q1.x); tr.b1 = __uint_as_float(q1.y); tr.inv_area = __uint_as_float(q1.z);
-    tr.min_x = q1.w & 0xFFFF; tr.max_x = q1.w >> 16; tr.min_y = q2.x & 0xFFFF; tr.max_y = q2.x >> 16;
-    tr.flags = q3.w;
-    tr.w0_start = __uint_as_float(q4.w); tr.w1_start = __uint_as_float(q5.x);
+    const Tri tr = tri_from_view(rv, true);
     float w0, w1, bcx, bcy, bcz;
     edge_w(tr, px, py, w0, w1);
     (void)inside_bc(tr, w0, w1, bcx, bcy, bcz);
-    const float inv_z = bcx * __uint_as_float(q5.y) + bcy * __uint_as_float(q5.z) + bcz * __uint_as_float(q5.w);
+    const float inv_z = bcx * tr.iz1 + bcy * tr.iz2 + bcz * tr.iz3;
     return rcp_exact(inv_z);
 }
 
 // ------------------------------------------------------------------------------------------------ k_shade
-// Coverage test of list entry li at pixel (px,py): inside test + texel + transparency rule. Keeps what colouring needs.
+// What the coverage test of a surface at a pixel (hit_test; hit_prepare -> fetch_texel -> texel_rule) keeps for colouring.
 struct Hit { float bcx, bcy, bcz; uint32_t texel, vc1, vc2, vc3, flags, sid; };
+// Coverage test of surface sid at pixel (px,py): inside test, then texel_drawn.  (Not hit_prepare -> fetch_texel -> texel_rule, the
+// same steps the two-pixel shading step takes apart: spelled that way the z-buffer forms of the fused kernel, which inline this at
+// every repair site under their 128-register cap, spill a fifth register: profiles/texel_address_resources.md.)
 template <bool FMT8>
 __device__ __forceinline__ bool hit_test(const FillArgs& a, uint32_t sid, uint32_t px, uint32_t py, Hit& h) {
-    const bool affine = a.fp.affine != 0;
     RecView rv;
-    load_shade_view(a, sid, !affine, rv);
-    const uint4 q0 = rv.q0, q1 = rv.q1, q2 = rv.q2, q3 = rv.q3, q4 = rv.q4, q5 = rv.q5;
-    Tri tr;
-    tr.x3 = __uint_as_float(q0.x); tr.y3 = __uint_as_float(q0.y); tr.a0 = __uint_as_float(q0.z); tr.b0 = __uint_as_float(q0.w);
-    tr.a1 = __uint_as_float(q1.x); tr.b1 = __uint_as_float(q1.y); tr.inv_area = __uint_as_float(q1.z);
-    tr.min_x = q1.w & 0xFFFF; tr.max_x = q1.w >> 16; tr.min_y = q2.x & 0xFFFF; tr.max_y = q2.x >> 16;
-    tr.u1 = __uint_as_float(q2.y); tr.u2 = __uint_as_float(q2.z); tr.u3 = __uint_as_float(q2.w);
-    tr.v1 = __uint_as_float(q3.x); tr.v2 = __uint_as_float(q3.y); tr.v3 = __uint_as_float(q3.z);
-    tr.flags = q3.w;
-    tr.w0_start = __uint_as_float(q4.w); tr.w1_start = __uint_as_float(q5.x);
-    tr.iz1 = __uint_as_float(q5.y); tr.iz2 = __uint_as_float(q5.z); tr.iz3 = __uint_as_float(q5.w);
-    tr.tw = tr.th = tr.toff = 0;
+    load_shade_view(a, sid, a.fp.affine == 0, rv);
+    Tri tr = tri_from_view(rv, true);
     const uint32_t txid = tr.flags & F_TEX_MASK;
     if (txid != F_TEX_NONE) {
-        if (a.fp.nt == 1) { tr.tw = a.tex0.width; tr.th = a.tex0.height; tr.toff = a.tex0.offset; }   // uniform: no descriptor gather
+        if (a.fp.nt == 1) { tr.tw = a.tex0.width; tr.th = a.tex0.height; tr.toff = a.tex0.offset; }
         else { const TexDesc d = a.tex[txid]; tr.tw = d.width; tr.th = d.height; tr.toff = d.offset; }
     }
     float w0, w1;
     edge_w(tr, px, py, w0, w1);
     if (!inside_bc(tr, w0, w1, h.bcx, h.bcy, h.bcz)) return false;
     h.texel = 0;
-    if (!texel_drawn<0, FMT8>(tr, h.bcx, h.bcy, h.bcz, FMT8 ? reinterpret_cast<const uint16_t*>(a.texels32) : a.texels, nullptr, h.texel, affine)) return false;
-    h.vc1 = q4.x; h.vc2 = q4.y; h.vc3 = q4.z; h.flags = tr.flags; h.sid = sid;
+    if (!texel_drawn<0, FMT8>(tr, h.bcx, h.bcy, h.bcz, FMT8 ? reinterpret_cast<const uint16_t*>(a.texels32) : a.texels, nullptr, h.texel, a.fp.affine != 0)) return false;
+    h.vc1 = rv.q4.x; h.vc2 = rv.q4.y; h.vc3 = rv.q4.z; h.flags = tr.flags; h.sid = sid;
     return true;
 }
 template <bool FMT8>
@@ -473,14 +463,11 @@ __device__ __forceinline__ uint32_t colour(const FillArgs& a, const Hit& h, int 
 // either is used, then both texel fetches, so two dependent load chains are in flight per lane.
 using RecRegs = RecView;
 __device__ __forceinline__ void rec_load(const FillArgs& a, uint32_t sid, bool need5, RecRegs& r) { load_shade_view(a, sid, need5, r); }
-// inside test + texel address (index into the texel pool; -1 = untextured -> white, -2 = zero-size texture -> transparent)
+// inside test + texel address with texel_address's sentinels (-1 = untextured, -2 = zero-size texture), which are spelled out here:
+// an untextured surface returns before the texture's descriptor is read, and through texel_address -- which tests the slot again --
+// the general painter's forms of the fused kernel gain 12 bytes of scratch (profiles/texel_address_resources.md)
 __device__ __forceinline__ bool hit_prepare(const FillArgs& a, const RecRegs& r, uint32_t px, uint32_t py, Hit& h, int& taddr) {
-    Tri tr;
-    tr.x3 = __uint_as_float(r.q0.x); tr.y3 = __uint_as_float(r.q0.y); tr.a0 = __uint_as_float(r.q0.z); tr.b0 = __uint_as_float(r.q0.w);
-    tr.a1 = __uint_as_float(r.q1.x); tr.b1 = __uint_as_float(r.q1.y); tr.inv_area = __uint_as_float(r.q1.z);
-    tr.min_x = r.q1.w & 0xFFFF; tr.max_x = r.q1.w >> 16; tr.min_y = r.q2.x & 0xFFFF; tr.max_y = r.q2.x >> 16;
-    tr.flags = r.q3.w;
-    tr.w0_start = __uint_as_float(r.q4.w); tr.w1_start = __uint_as_float(r.q5.x);
+    Tri tr = tri_from_view(r, true);
     float w0, w1;
     edge_w(tr, px, py, w0, w1);
     taddr = -1;
@@ -491,40 +478,9 @@ __device__ __forceinline__ bool hit_prepare(const FillArgs& a, const RecRegs& r,
     TexDesc d;
     if (a.fp.nt == 1) d = a.tex0; else d = a.tex[txid];
     if (d.width == 0 || d.height == 0) { taddr = -2; return true; }
-    const float u1 = __uint_as_float(r.q2.y), u2 = __uint_as_float(r.q2.z), u3 = __uint_as_float(r.q2.w);
-    const float v1 = __uint_as_float(r.q3.x), v2 = __uint_as_float(r.q3.y), v3 = __uint_as_float(r.q3.z);
     float u, v;
-    if (a.fp.affine) {
-        u = h.bcx * u1 + h.bcy * u2 + h.bcz * u3;                // render.rs:1565-1566
-        v = h.bcx * v1 + h.bcy * v2 + h.bcz * v3;
-    } else {                                                     // render.rs:1568-1579
-        const float iz1 = __uint_as_float(r.q5.y), iz2 = __uint_as_float(r.q5.z), iz3 = __uint_as_float(r.q5.w);
-        const float inv_z = h.bcx * iz1 + h.bcy * iz2 + h.bcz * iz3;
-        const float u_over_z = h.bcx * u1 * iz1 + h.bcy * u2 * iz2 + h.bcz * u3 * iz3;
-        const float v_over_z = h.bcx * v1 * iz1 + h.bcy * v2 * iz2 + h.bcz * v3 * iz3;
-        u = u_over_z / inv_z;
-        v = v_over_z / inv_z;
-    }
-    const float uw = rem_euclid1(u), vw = rem_euclid1(1.0f - v);                        // Texture15::sample, types.rs:671-681
-    const uint32_t tx = min(f2u_sat(uw * (float)d.width), d.width - 1);
-    const uint32_t ty = min(f2u_sat(vw * (float)d.height), d.height - 1);
-    taddr = (int)(d.offset + ty * d.width + tx);
-    return true;
-}
-// transparency rule on the fetched texel (render.rs:1591-1608 / 8-bit :1348-1352)
-template <bool FMT8>
-__device__ __forceinline__ bool hit_finish(uint32_t flags, int taddr, uint32_t fetched, uint32_t& texel) {
-    if (FMT8) {
-        const uint32_t c = taddr == -1 ? 0x00FFFFFFu : (taddr == -2 ? ((uint32_t)B32_BLEND_ERASE << 24) : fetched);
-        texel = c;
-        return (c >> 24) != B32_BLEND_ERASE;
-    }
-    uint32_t c = taddr == -1 ? K::C15_WHITE : (taddr == -2 ? K::C15_TRANSPARENT : fetched);
-    if (c == K::C15_TRANSPARENT) {
-        if (flags & F_BLACK_TR) return false;
-        c = K::C15_BLACK_DRAWABLE;
-    } else if ((flags & F_BLACK_TR) && (c & ~K::C15_SEMI_BIT & 0xFFFFu) == 0) return false;
-    texel = c;
+    interp_uv(h.bcx, h.bcy, h.bcz, tr.u1, tr.u2, tr.u3, tr.v1, tr.v2, tr.v3, tr.iz1, tr.iz2, tr.iz3, a.fp.affine != 0, u, v);
+    taddr = (int)(d.offset + texel_index(u, v, d.width, d.height));
     return true;
 }
 // texel of the LDS-staged index atlas: [256 x Color15 CLUT][index bytes]; taddr is an address in the texel pool (texture 0 starts at off0)
@@ -570,6 +526,18 @@ __device__ __forceinline__ uint32_t dpp_add_scan(uint32_t v) {          // inclu
 }
 __device__ __forceinline__ uint32_t bperm(uint32_t src_lane, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v); }
 __device__ __forceinline__ float bpermf(uint32_t src_lane, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), __float_as_int(v))); }
+
+// Per-lane view of the surface held by lane s of the batch, as far as the texel address needs it: UVs, flags, texture and, want_iz, the
+// 1/z terms -- 10 (13) ds_bpermute.
+__device__ __forceinline__ Tri tri_uv_from_lane(const Batch& b, uint32_t s, uint32_t flags, bool want_iz) {
+    Tri t = {};
+    t.u1 = bpermf(s, __uint_as_float(b.q2.y)); t.u2 = bpermf(s, __uint_as_float(b.q2.z)); t.u3 = bpermf(s, __uint_as_float(b.q2.w));
+    t.v1 = bpermf(s, __uint_as_float(b.q3.x)); t.v2 = bpermf(s, __uint_as_float(b.q3.y)); t.v3 = bpermf(s, __uint_as_float(b.q3.z));
+    t.flags = bperm(s, flags);
+    t.tw = bperm(s, b.tw); t.th = bperm(s, b.th); t.toff = bperm(s, b.toff);
+    if (want_iz) { t.iz1 = bpermf(s, __uint_as_float(b.q5.y)); t.iz2 = bpermf(s, __uint_as_float(b.q5.z)); t.iz3 = bpermf(s, __uint_as_float(b.q5.w)); }
+    return t;
+}
 
 // hipFuncSetAttribute is per device: remember, per kernel instantiation, on which devices the large-LDS opt-in has been made
 // (a process may own contexts on several GPUs)

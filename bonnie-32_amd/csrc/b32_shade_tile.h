@@ -119,8 +119,8 @@ __device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t
             if (!FMT8 && latlas) { fA = atlas_texel(latlas, okA ? taA : -1, a.tex0.offset); fB = atlas_texel(latlas, okB ? taB : -1, a.tex0.offset); }
             else { fA = fetch_texel<FMT8>(a, okA ? taA : -1); fB = fetch_texel<FMT8>(a, okB ? taB : -1); }
             hA.sid = sid_of(tA); hB.sid = sid_of(tB);
-            okA = okA && hit_finish<FMT8>(hA.flags, taA, fA, hA.texel);
-            okB = okB && hit_finish<FMT8>(hB.flags, taB, fB, hB.texel);
+            okA = okA && texel_rule<FMT8>(hA.flags, taA, fA, hA.texel);
+            okB = okB && texel_rule<FMT8>(hB.flags, taB, fB, hB.texel);
             // (a covered pixel whose winner is skipped waits in the queue; everything else is final)
             mA = __ballot(cA && !okA); mB = __ballot(cB && !okB);
             if (!FMT8 && !ZMODE && shading == B32_SHADE_NONE) {
@@ -153,10 +153,10 @@ __device__ __forceinline__ void shade_tile_p64(const FillArgs& a, const uint32_t
 
 // The straight-line shading phase (RGB555, affine UVs, fixed-point snap, perspective camera, ONE texture fetched from global memory;
 // painter's or z-buffer mode; with or without a shading pass): the general shade_tile_p64 reaches the same arithmetic through
-// hit_prepare / hit_finish / colour, whose per-pixel branches (texture present?, zero-sized?, literal replay?, inside?) cost the
+// hit_prepare / texel_rule / colour, whose per-pixel branches (texture present?, zero-sized?, literal replay?, inside?) cost the
 // benchmark's instantiation ~90 branches and ~470 VALU instructions per two-pixel step.  Here every lane runs the one path -- record
-// view, edge values in closed form, barycentrics, UVs, texel address (render.rs:1507-1583, types.rs:671-681), both texel fetches in flight,
-// texel rule (render.rs:1591-1608), colour pipeline -- on whatever its two pixels hold (an uncovered pixel computes on surface 0's record
+// view, edge values in closed form, barycentrics, UVs, texel address (render.rs:1507-1538, interp_uv, texel_index), both texel fetches in flight,
+// texel rule (texel_rule), colour pipeline -- on whatever its two pixels hold (an uncovered pixel computes on surface 0's record
 // and stores nothing of it).  The winner of a covered pixel passed the inside test during coverage (same arithmetic, or the span form
 // proven equal to it), so it is not evaluated again.  A step in which some winner must replay the edge walk literally (SH_SLOW) takes
 // the general per-pixel functions; skipped winners go to the wave's repair queue as in the general form.
@@ -252,17 +252,16 @@ __device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32
         }
     };
     auto texaddr = [&](const uint4& q0, const uint4& q1, const uint4& q2, const uint4& q3, uint32_t py, bool c, float& b0, float& b1, float& b2) -> uint32_t {
-        // render.rs:1507-1510 (edges), :1517-1518 / 1706-1712 in closed form (exact integers), :1536-1538, :1565-1566, types.rs:671-681
+        // render.rs:1507-1510 (edges), :1517-1518 / 1706-1712 in closed form (exact integers), :1536-1538, then interp_uv and texel_index
         const float x3 = f(q1.x), y3 = f(q1.y), inv = f(q1.z);
         const float ea0 = f(q0.w) - y3, eb0 = x3 - f(q0.z), ea1 = y3 - f(q0.y), eb1 = f(q0.x) - x3;
         const float dx = fx - x3, dy = (float)py - y3;
         const float w0 = ea0 * dx + eb0 * dy, w1 = ea1 * dx + eb1 * dy;
         b0 = w0 * inv; b1 = w1 * inv; b2 = 1.0f - b0 - b1;
-        const float u = b0 * f(q2.x) + b1 * f(q2.y) + b2 * f(q2.z);
-        const float v = b0 * f(q2.w) + b1 * f(q3.x) + b2 * f(q3.y);
-        const float uw = rem_euclid1(u), vw = rem_euclid1(1.0f - v);
-        const uint32_t tx = min(f2u_sat(uw * twf), d.width - 1), ty = min(f2u_sat(vw * thf), d.height - 1);
-        return c ? d.offset + ty * d.width + tx : d.offset;
+        float u, v;
+        interp_uv(b0, b1, b2, f(q2.x), f(q2.y), f(q2.z), f(q2.w), f(q3.x), f(q3.y), 0.0f, 0.0f, 0.0f, true, u, v);
+        const uint32_t ti = texel_index(u, v, d.width, d.height, twf, thf);                  // (one texture of non-zero size: no sentinels)
+        return c ? d.offset + ti : d.offset;
     };
     auto part1 = [&](uint32_t r0, const In& s, Mid& m) {
         const uint32_t pyA = ty_top + r0 + (tid >> 6), pyB = pyA + ROWS_PER_STEP;
@@ -280,7 +279,7 @@ __device__ __forceinline__ void shade_tile_plain(const FillArgs& a, const uint32
         uint32_t* outB = a.fb + (size_t)pyB * W + px;
         shA = m.pkA2 >> 24; shB = m.pkB2 >> 24;
         const float bA[3] = { m.bA0, m.bA1, m.bA2 }, bB[3] = { m.bB0, m.bB1, m.bB2 };
-        // texture slot 0xFFFF = untextured: Color15::WHITE (render.rs:1585); then the transparency rule (render.rs:1591-1608)
+        // texture slot 0xFFFF = untextured: white; then the transparency rule -- texel_rule's, as selects on the SH_* bits of both pixels
         const bool noneA = ((m.pkA0 >> 24) | ((m.pkA1 >> 24) << 8)) == F_TEX_NONE, noneB = ((m.pkB0 >> 24) | ((m.pkB1 >> 24) << 8)) == F_TEX_NONE;
         uint32_t cA15 = noneA ? K::C15_WHITE : m.fetA, cB15 = noneB ? K::C15_WHITE : m.fetB;
         const bool btA = (shA & SH_BLACK_TR) != 0, btB = (shB & SH_BLACK_TR) != 0;

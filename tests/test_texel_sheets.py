@@ -2,10 +2,10 @@
 
 Which pixels a triangle covers and what value a fetched texel becomes are tested elsewhere (test_coverage_sheets.py,
 test_pixel_swatches.py); this file tests the stage between them, WHICH texel a fragment fetches: the interpolation of u and v
-(render.rs:1565-1579), the `1.0 - v` flip and Texture15::sample / Texture::sample (types.rs:671-681, :1242-1253).  The device holds that
-arithmetic in texaddr (b32_shade_tile.h), hit_prepare, tri_texel_addr + the skip mask, sample15 / sample8 and atlas_texel
-(b32_fill_common.h, b32_cover.h, b32_blend.hip).  Every texel of a sheet's textures carries its own address, so the frame is a map of
-fetched addresses.
+(render.rs:1565-1579), the `1.0 - v` flip and Texture15::sample / Texture::sample (types.rs:671-681, :1242-1253).  The device states that
+arithmetic once, in interp_uv and texel_index (b32_fill_common.h), and reaches it through texel_address (texel_drawn, the EXACT trips
+and their skip mask in b32_cover.h, k_blend), hit_prepare, texaddr (b32_shade_tile.h) and atlas_texel.  Every texel of a sheet's
+textures carries its own address, so the frame is a map of fetched addresses.
 
 CPU tests (no mark): every strip lands on its rows and the C oracle equals the numpy model on every sheet and setting; a restatement of
 the address arithmetic, written once below, reproduces the model's tx / ty / texel at every stored pixel from the model's tap; a census
@@ -512,7 +512,7 @@ def test_plain_sheets_on_the_one_texture_kernels(gpu_ctx, oracle, name):
     """launch_p64's one-texture kernels (k_cover_plain, k_cover_plain_z; their EXACT instantiation with counting on): one texture without a
     skippable texel, in-fill collection and the 16-wave workgroups off, direct_bin asserted; painter's and z-buffer mode, counting off
     and on.  Then the keyed route with counting on: EXACT coverage of a one-texture frame stages the texture in LDS when it fits
-    (k_cover<1>, sample15<1>: 31 x 33 and 100 x 60 fit, 255 x 255 does not and is read from global memory).  Which kernel ran is not
+    (k_cover<1>, texel_drawn<1>: 31 x 33 and 100 x 60 fit, 255 x 255 does not and is read from global memory).  Which kernel ran is not
     observable; the conditions are those of launch_p64 and launch_fill.  The Z-plain sheets ask for perspective-correct addressing
     under the same conditions."""
     from bonnie32_amd import rasterizer as R
@@ -563,7 +563,7 @@ def test_sheet_f(gpu_ctx, oracle, name, projection):
 
 @gpu
 def test_sheet_a8_opaque_in_the_fused_fill(gpu_ctx, oracle):
-    """sample8 from the fused fill; with the setup kernel's bins and 8-wave workgroups k_cover_plain8's conditions (launch_p64)"""
+    """Texture::sample (texel_index on Color words) from the fused fill; with the setup kernel's bins and 8-wave workgroups k_cover_plain8's conditions (launch_p64)"""
     from bonnie32_amd import rasterizer as R
     C = R.Context
     sw = TS.sheet_a8(abi.OPAQUE)
