@@ -83,6 +83,27 @@ class B32MeshOverlay(C.Structure):
 
 assert C.sizeof(B32MeshOverlay) == 48
 
+
+# B32RoomOverlay (the world editor's room overlays from a resident room, b32_draw_room_overlay): sections = ROOM_OVERLAY_* bits
+ROOM_OVERLAY_VERTICES, ROOM_OVERLAY_EDGES, ROOM_OVERLAY_HOVER, ROOM_OVERLAY_SELECTED, ROOM_OVERLAY_PREVIEW = 1, 2, 4, 8, 16
+ROOM_OVERLAY_ALL = 31
+ROOM_OVERLAY_HOVER_GIVEN, ROOM_OVERLAY_HOVER_RESIDENT = 0, 1     # hover_source
+
+
+class B32RoomHover(C.Structure):
+    _fields_ = [("vertex_rec", C.c_uint32), ("vertex_corner", C.c_uint32), ("vertex_dist", C.c_float), ("vertex_depth", C.c_float),
+                ("edge_rec", C.c_uint32), ("edge_idx", C.c_uint32), ("edge_dist", C.c_float), ("edge_depth", C.c_float),
+                ("face_rec", C.c_uint32), ("face_depth", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+
+class B32RoomOverlay(C.Structure):
+    _fields_ = [("sections", C.c_uint32), ("hover_source", C.c_uint32), ("hover", B32RoomHover), ("primary_vertex", C.c_uint32),
+                ("skip_first", C.c_uint32), ("skip_count", C.c_uint32), ("n_vertices", C.c_uint32), ("n_edges", C.c_uint32),
+                ("n_faces", C.c_uint32), ("n_points", C.c_uint32), ("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float)]
+
+
+assert C.sizeof(B32RoomHover) == 48 and C.sizeof(B32RoomOverlay) == 100
+
 # B32PickHit (b32_pick_meshes): hit == 0 -> tri = 0xFFFFFFFF, depth = 0
 PICK_HIT_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("depth", "<f4"), ("_pad", "<u4")])
 assert PICK_HIT_DTYPE.itemsize == 16
@@ -271,6 +292,9 @@ SYMBOLS = [
     ("b32_draw_mesh_overlay", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("b32_mesh_overlay_project_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_mesh_overlay_record_count", C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32)]),
+    ("b32_draw_room_overlay", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    ("b32_room_overlay_project_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_room_overlay_record_count", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

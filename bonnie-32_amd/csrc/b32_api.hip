@@ -2,6 +2,7 @@
 // (Scene uploads: b32_scene.hip; frames: b32_frame.hip; batched frames: b32_batch.hip; shared declarations: b32_host.h.)
 #include "b32_host.h"
 #include "b32_overlay_body.h"
+#include "b32_room_overlay_body.h"
 
 extern "C" {
 
@@ -448,6 +449,45 @@ static int overlay_bounds(b32_ctx* c, OverlayArgs& a) {
     return B32_OK;
 }
 
+// ------------------------------------------------------------------ the world editor's room overlays (b32_room_overlay.hip)
+// Everything checked and laid out before anything is enqueued: the kernel's arguments but for the device buffers the caller provides (out,
+// lists), the call's lists as one run of words in c->overlay_pairs (keys, edge pairs, faces, the points' bits), the record total.
+static int room_overlay_prepare(b32_ctx* c, const B32Camera* cam, const b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
+                                const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz, uint32_t w, uint32_t h,
+                                RoomOverlayArgs& a, uint64_t* total) {
+    if (!c || !cam || !room || !o || !w || !h) return B32_E_ARG;
+    { const int rc = room_overlay_check(o, sel_vertices, sel_edges, sel_faces, points_xyz); if (rc) return rc; }
+    if (o->hover_source == 1u && !room->have_hover) return B32_E_ARG;
+    const RoomOverlayLayout l = room_overlay_layout(room->n, *o);
+    *total = l.total;
+    if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+    const uint64_t words = (uint64_t)o->n_vertices + 2ull * o->n_edges + o->n_faces + 3ull * o->n_points;
+    if (words > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+    a = RoomOverlayArgs{};
+    view_fill(a.v, *cam, w, h, nullptr);
+    a.grid = room->grid; a.faces = room->faces; a.mats = room->have_mats ? room->mats : nullptr; a.n = room->n;
+    a.hover = o->hover_source == 1u ? static_cast<const B32RoomHover*>(room->d_hover) : nullptr;
+    a.o = *o;
+    for (int k = 0; k < 4; ++k) a.rect[k] = l.rect[k];
+    a.at_vertices = (uint32_t)l.vertices; a.at_edges = (uint32_t)l.edges; a.at_hover = (uint32_t)l.hover; a.at_sel_faces = (uint32_t)l.sel_faces;
+    a.at_sel_edges = (uint32_t)l.sel_edges; a.at_preview = (uint32_t)l.preview; a.at_points = (uint32_t)l.points;
+    a.l_edges = o->n_vertices; a.l_faces = a.l_edges + 2u * o->n_edges; a.l_points = a.l_faces + o->n_faces;
+    std::vector<uint32_t>& lw = c->overlay_pairs;
+    lw.resize((size_t)words);
+    if (o->n_vertices) std::memcpy(lw.data(), sel_vertices, (size_t)o->n_vertices * 4u);
+    if (o->n_edges) std::memcpy(lw.data() + a.l_edges, sel_edges, (size_t)o->n_edges * 8u);
+    if (o->n_faces) std::memcpy(lw.data() + a.l_faces, sel_faces, (size_t)o->n_faces * 4u);
+    if (o->n_points) std::memcpy(lw.data() + a.l_points, points_xyz, (size_t)o->n_points * 12u);
+    const uint32_t sec = o->sections;
+    const auto groups = [](uint64_t n) { return (uint32_t)((n + 255u) / 256u); };
+    if (sec & B32_ROOM_OVERLAY_VERTICES) a.g_vertices = groups((uint64_t)o->n_vertices + 1u);
+    if (sec & B32_ROOM_OVERLAY_EDGES) a.g_edges = groups(o->n_edges);
+    if (sec & B32_ROOM_OVERLAY_HOVER) a.g_hover = 1u;
+    if (sec & B32_ROOM_OVERLAY_SELECTED) { a.g_sel_faces = groups(o->n_faces); a.g_sel_edges = groups(o->n_edges); }
+    if (l.gate) { a.g_preview = groups(room->n); a.g_points = groups(o->n_points); }
+    return B32_OK;
+}
+
 extern "C" {
 
 // The line family of Framebuffer (render.rs:684-872), b32_lines.hip.
@@ -650,6 +690,55 @@ int b32_mesh_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32Or
     if ((rc = overlay_bounds(c, a))) return rc;
     a.out = d_out; a.tab = d_tab; a.selected = d_sel;
     launch_overlay(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
+}
+// The world editor's room overlays (viewport_3d.rs:4273-4658, :4862-5362): made into records by k_room_overlay in the primitive pass's
+// device record buffer, from the room's records (and its last hover) as they are on the device; binned and drawn from there like any
+// other primitive batch.
+int b32_draw_room_overlay(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
+                          const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz) {
+    if (!c || !c->fb) return B32_E_ARG;
+    RoomOverlayArgs a; uint64_t total = 0;
+    int rc;
+    if ((rc = room_overlay_prepare(c, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz, c->width, c->height, a, &total))) return rc;
+    if (!total) return B32_OK;
+    (void)hipSetDevice(c->device);
+    if ((rc = draw_enter(c))) return rc;
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    if ((rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0))) return rc;
+    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)total))) return rc;
+    a.out = c->prims.dev; a.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
+    if (!c->overlay_pairs.empty()) {
+        if ((rc = stage_records(c, c->overlay_sel, c->overlay_pairs.data(), (uint32_t)c->overlay_pairs.size()))) return rc;
+        a.lists = c->overlay_sel.dev;
+    }
+    launch_room_overlay(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    DrawArgs<B32Prim> d = draw_args<B32Prim>(c, (uint32_t)total);
+    d.recs = c->prims.dev;
+    return draw_resident(c, c->prims, d, total > PRIM_SMALL, B32_ROUTE_PRIM_TILES);
+}
+int b32_room_overlay_project_batch(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
+                                   const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz, uint32_t w, uint32_t h,
+                                   B32Prim* out, uint32_t cap, uint32_t* n_records) {
+    if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
+    RoomOverlayArgs a; uint64_t total = 0;
+    int rc;
+    if ((rc = room_overlay_prepare(c, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz, w, h, a, &total))) return rc;
+    if (total > cap || (total && !out)) return B32_E_ARG;
+    *n_records = (uint32_t)total;
+    if (!total) return B32_OK;
+    (void)hipSetDevice(c->device);
+    if ((rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0))) return rc;
+    B32Prim* d_out = nullptr; uint32_t* d_lists = nullptr;
+    Scratch tmp(c);
+    if ((rc = tmp.alloc(&d_out, (size_t)total))) return rc;
+    if (!c->overlay_pairs.empty() && (rc = tmp.upload(c->overlay_pairs.data(), c->overlay_pairs.size(), &d_lists))) return rc;
+    a.out = d_out; a.lists = d_lists; a.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
+    launch_room_overlay(c->stream, a);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -580,6 +580,21 @@ struct OverlayArgs {
     uint32_t g_edges, g_pedges, g_sel, g_pfaces, g_hover, g_brackets;     // workgroups of k_overlay_emit's ranges, in this order
 };
 void launch_overlay(hipStream_t s, const OverlayArgs& a);
+// The world editor's room overlays made into B32Prim records on the device (b32_draw_room_overlay, b32_room_overlay.hip): where a record
+// lies is decided by the host (room_overlay_layout, b32_room_overlay_body.h), the kernel fills the places.
+struct RoomOverlayArgs {
+    ViewBlock v; B32RoomGrid grid; B32Prim* out;    // camera and projection constants; the records
+    unsigned long long* counts;                     // the gizmo entry's drawn / dropped / rejected -- added to
+    const B32SectorFace* faces; const B32FaceMaterial* mats; uint32_t n;      // the room's records; mats == nullptr: no table was set
+    const B32RoomHover* hover;                      // the room's device copy of its last hover; nullptr: o.hover
+    const uint32_t* lists;                          // the call's lists, one upload: keys, edge pairs, faces, then the points' bits
+    uint32_t l_edges, l_faces, l_points;            // first word of each behind the keys
+    B32RoomOverlay o;
+    float rect[4];                                  // the preview's rectangle: min x, min y, max x, max y
+    uint32_t at_vertices, at_edges, at_hover, at_sel_faces, at_sel_edges, at_preview, at_points;     // first record of each
+    uint32_t g_vertices, g_edges, g_hover, g_sel_faces, g_sel_edges, g_preview, g_points;           // workgroups of the kernel's ranges, in this order
+};
+void launch_room_overlay(hipStream_t s, const RoomOverlayArgs& a);
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

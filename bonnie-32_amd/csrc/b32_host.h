@@ -131,6 +131,21 @@ struct b32_topology {
     std::vector<uint32_t> h_poly_start;         // np + 1 on the host: where the overlay's records lie (overlay_layout)
 };
 
+// The world editor's current room (b32_room_create, b32_room.hip): one record per sector face on the device.
+struct b32_room {
+    B32SectorFace* faces = nullptr;             // n records on the device
+    uint32_t n = 0;
+    B32RoomGrid grid{};                         // travels in the kernel argument: an update is ordered by the launch that follows it
+    // the render mesh: materials and per record {first vertex, first face} on the device; on the host what decides where a record's
+    // output lies (kind, normal_mode) and which faces can blend (blend_mode, the two texture ids), and the prefix sums (n + 1 entries)
+    B32FaceMaterial* mats = nullptr; uint2* first = nullptr; bool have_mats = false;
+    std::vector<uint8_t> h_kind, h_mode, h_blend; std::vector<uint32_t> h_tex; std::vector<uint2> h_first;
+    uint32_t own_blend_faces = 0;               // faces whose own blend mode puts them in the transparent pass
+    // the 48 bytes of the room's last b32_room_hover[_async], copied on the stream behind k_room_hover_resolve: what
+    // b32_draw_room_overlay reads with hover_source 1
+    void* d_hover = nullptr; bool have_hover = false;
+};
+
 // Device words that stay armed between two calls (armed_ensure).
 struct ArmedWords { void* p = nullptr; size_t cap = 0; };
 // HIP events around the kernels of the last call of its kind enqueued while profiling was on (b32_last_kernel_times); created on first use.

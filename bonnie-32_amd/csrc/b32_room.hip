@@ -26,17 +26,7 @@
 //                         the slot's vertices.  Lane 0 writes the slot's device-side face count.
 #include "b32_pick_body.h"
 #include "b32_room_mesh_body.h"
-
-struct b32_room {
-    B32SectorFace* faces = nullptr;             // n records on the device
-    uint32_t n = 0;
-    B32RoomGrid grid{};                         // travels in the kernel argument: an update is ordered by the launch that follows it
-    // the render mesh: materials and per record {first vertex, first face} on the device; on the host what decides where a record's
-    // output lies (kind, normal_mode) and which faces can blend (blend_mode, the two texture ids), and the prefix sums (n + 1 entries)
-    B32FaceMaterial* mats = nullptr; uint2* first = nullptr; bool have_mats = false;
-    std::vector<uint8_t> h_kind, h_mode, h_blend; std::vector<uint32_t> h_tex; std::vector<uint2> h_first;
-    uint32_t own_blend_faces = 0;               // faces whose own blend mode puts them in the transparent pass
-};
+#include "b32_room_winner.h"
 
 namespace b32 {
 
@@ -344,7 +334,7 @@ int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
 void b32_room_destroy(b32_ctx* c, b32_room* room) {
     if (!room) return;
     if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }     // (a hover that reads it may be in flight)
-    for (void* p : { (void*)room->faces, (void*)room->mats, (void*)room->first }) if (p) (void)hipFree(p);
+    for (void* p : { (void*)room->faces, (void*)room->mats, (void*)room->first, room->d_hover }) if (p) (void)hipFree(p);
     delete room;
 }
 
@@ -366,6 +356,10 @@ int b32_room_hover_async(b32_ctx* c, const B32Camera* cam, b32_room* room, const
     if (groups) hipLaunchKernelGGL(k_room_hover, dim3(groups), dim3(256), 0, c->stream, a);
     hipLaunchKernelGGL(k_room_hover_resolve, dim3(1), dim3(64), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
+    // the room's own copy of the result, for b32_draw_room_overlay's hover_source 1: behind the resolve kernel on the stream
+    if (!room->d_hover) HIPCHK(c, hipMalloc(&room->d_hover, sizeof(B32RoomHover)));
+    HIPCHK(c, hipMemcpyAsync(room->d_hover, a.result, sizeof(B32RoomHover), hipMemcpyDeviceToDevice, c->stream));
+    room->have_hover = true;
     return pick_result_deliver(c, k, bytes, out, t, tev, ticket);
 }
 
@@ -381,28 +375,8 @@ int b32_room_hover(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32Ro
     return B32_OK;
 }
 
-// viewport_3d.rs:7283-7336, literally: candidates pushed as (depth, type) in the order vertex, edge, face; sort_by(partial_cmp, a NaN
-// compares Equal) -- for so few elements the standard library's stable insertion sort, which is what this is; tolerance; lowest type
-// within the tolerance, else the closest one's type.
-int b32_room_hover_winner(const B32RoomHover* h) {
-    if (!h) return -1;
-    float depth[3]; int type[3]; int n = 0;
-    if (h->vertex_rec != 0xFFFFFFFFu) { depth[n] = h->vertex_depth; type[n++] = 0; }
-    if (h->edge_rec != 0xFFFFFFFFu) { depth[n] = h->edge_depth; type[n++] = 1; }
-    if (h->face_rec != 0xFFFFFFFFu) { depth[n] = h->face_depth; type[n++] = 2; }
-    if (!n) return -1;
-    for (int i = 1; i < n; ++i) {
-        const float d = depth[i]; const int t = type[i];
-        int j = i;
-        while (j > 0 && d < depth[j - 1]) { depth[j] = depth[j - 1]; type[j] = type[j - 1]; --j; }
-        depth[j] = d; type[j] = t;
-    }
-    const float closest = depth[0];
-    const float tolerance = closest * 0.01f;
-    int best = -1;
-    for (int i = 0; i < n; ++i) if (fabsf(depth[i] - closest) < tolerance && (best < 0 || type[i] < best)) best = type[i];
-    return best >= 0 ? best : type[0];
-}
+// viewport_3d.rs:7283-7336: the one text of the rule is room_hover_winner (b32_room_winner.h), which the room overlay runs on the device.
+int b32_room_hover_winner(const B32RoomHover* h) { return h ? room_hover_winner(*h) : -1; }
 
 int b32_room_box_select_async(b32_ctx* c, const B32Camera* cam, b32_room* room, float x0, float y0, float x1, float y1, const float* points_xyz,
                               uint32_t n_points, void* out, uint64_t* ticket) {

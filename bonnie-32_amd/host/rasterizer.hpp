@@ -763,6 +763,40 @@ inline BoxSelection room_box_select(Framebuffer& fb, const Room& room, const Cam
           "room_box_select");
     return r;
 }
+// The world editor's room overlays (editor/viewport_3d.rs:4273-4658, :4862-5362: the selected / hovered vertices, the selected edges, the
+// hovered edge and face, draw_selection's SectorFace and Edge arms, the box-select preview) made into records on the device from the
+// room's resident records and drawn in the reference's order (b32_draw_room_overlay): enqueued, nothing read back.  hover_source 1 reads
+// the room's last room_hover[_async] where it lies on the device -- no ticket to wait for.  Selection::Sector is a host's own
+// B32_GIZMO_LINE items (draw_gizmos).
+struct RoomOverlay {
+    uint32_t sections = 0;                                                     // B32_ROOM_OVERLAY_* bits
+    uint32_t hover_source = 0;                                                 // 0: `hover`; 1: the room's last hover, on the device
+    B32RoomHover hover{ 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0xFFFFFFFFu, 0, { 0, 0 } };   // raw, all three loops
+    uint32_t primary_vertex = 0xFFFFFFFFu;                                     // key 4 * rec + corner
+    uint32_t skip_first = 0, skip_count = 0;                                   // the records state.selection.includes_face() covers
+    std::vector<uint32_t> vertices;                                            // keys, strictly ascending
+    std::vector<uint32_t> edges;                                               // (rec, edge_idx) pairs one after another
+    std::vector<uint32_t> faces;                                               // recs
+    std::vector<Vec3> points;                                                  // the room's object positions
+    float x0 = 0, y0 = 0, x1 = 0, y1 = 0;                                      // selection_rect_start / _end as stored
+    B32RoomOverlay pack() const {
+        B32RoomOverlay o{};
+        o.sections = sections; o.hover_source = hover_source; o.hover = hover; o.primary_vertex = primary_vertex;
+        o.skip_first = skip_first; o.skip_count = skip_count;
+        o.n_vertices = (uint32_t)vertices.size(); o.n_edges = (uint32_t)(edges.size() / 2); o.n_faces = (uint32_t)faces.size(); o.n_points = (uint32_t)points.size();
+        o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
+        return o;
+    }
+};
+inline void draw_room_overlay(Framebuffer& fb, const Room& room, const RoomOverlay& overlay, const Camera& camera) {
+    const B32Camera cam = detail::pack(camera);
+    const B32RoomOverlay o = overlay.pack();
+    std::vector<float> xyz; xyz.reserve(overlay.points.size() * 3);
+    for (const auto& p : overlay.points) { xyz.push_back(p.x); xyz.push_back(p.y); xyz.push_back(p.z); }
+    check(b32_draw_room_overlay(fb.ctx(), &cam, room.handle(), &o, overlay.vertices.empty() ? nullptr : overlay.vertices.data(),
+                                overlay.edges.empty() ? nullptr : overlay.edges.data(), overlay.faces.empty() ? nullptr : overlay.faces.data(),
+                                xyz.empty() ? nullptr : xyz.data()), "draw_room_overlay");
+}
 // The host restatements (what a host without the library walks per mouse move): separately rounded f32 operations in the reference's order
 // (compile with -ffp-contract=off where the compiler would fuse).
 namespace detail {

@@ -1031,6 +1031,314 @@ def room_hover_winner(result):
     return min(near) if near else cand[0][1]
 
 
+# ---- the world editor's room overlays (editor/viewport_3d.rs:4273-4658, :4862-5362) from a room's records: b32_draw_room_overlay and its mirror
+class RoomOverlay:
+    """B32RoomOverlay and the lists that travel beside it: which sections to draw (abi.ROOM_OVERLAY_* bits), the hover (an
+    abi.ROOM_HOVER_DTYPE record, raw; hover_source = abi.ROOM_OVERLAY_HOVER_RESIDENT: the room's last hover, read on the device -- the
+    mirror still reads `hover`), the primary vertex key, the skip range of includes_face, the rectangle as stored, and the lists:
+    vertices (keys 4 * rec + corner, strictly ascending), edges ((rec, edge_idx) pairs), faces (recs), points ((m, 3) positions)."""
+
+    def __init__(self, sections=0, hover=None, hover_source=abi.ROOM_OVERLAY_HOVER_GIVEN, primary_vertex=None, skip=(0, 0), rect=(0.0, 0.0, 0.0, 0.0),
+                 vertices=None, edges=None, faces=None, points=None):
+        self.sections, self.hover_source, self.skip, self.rect = int(sections), int(hover_source), (int(skip[0]), int(skip[1])), tuple(rect)
+        if hover is None:
+            hover = np.zeros((), abi.ROOM_HOVER_DTYPE)
+            for k in ("vertex_rec", "vertex_corner", "edge_rec", "edge_idx", "face_rec"):
+                hover[k] = abi.HOVER_NONE
+        self.hover = np.array(hover, abi.ROOM_HOVER_DTYPE).reshape(())
+        self.primary_vertex = abi.HOVER_NONE if primary_vertex is None else int(primary_vertex)
+        self.vertices = np.ascontiguousarray(vertices if vertices is not None else [], np.uint32).reshape(-1)
+        self.edges = np.ascontiguousarray(edges if edges is not None else [], np.uint32).reshape(-1, 2)
+        self.faces = np.ascontiguousarray(faces if faces is not None else [], np.uint32).reshape(-1)
+        self.points = np.ascontiguousarray(points if points is not None else [], np.float32).reshape(-1, 3)
+
+    def pack(self):
+        """(abi.B32RoomOverlay, the four list pointers or None)"""
+        h = abi.B32RoomHover.from_buffer_copy(self.hover.tobytes())
+        o = abi.B32RoomOverlay(self.sections, self.hover_source, h, self.primary_vertex, self.skip[0], self.skip[1], len(self.vertices), len(self.edges),
+                               len(self.faces), len(self.points), *[float(v) for v in self.rect])
+        return o, tuple(abi.ptr(a) if len(a) else None for a in (self.vertices, self.edges, self.faces, self.points))
+
+
+ROOM_OVERLAY_COLORS = {"selected_vertex": (100, 255, 100), "hover_vertex": (255, 200, 150), "selected_edge": (100, 255, 100), "hover_edge": (255, 200, 100),
+                       "hover_face": (150, 200, 255), "selected": (255, 200, 80), "preview": (100, 220, 255)}
+# the draw_3d_line calls of a hovered / selected face as (corner set, from, to): viewport_3d.rs:4513-4532 / :4895-4918 and the walls' five
+_ROOM_FACE_LINES = {abi.SPLIT_NWSE: ((1, 0, 1), (1, 1, 2), (2, 2, 3), (2, 3, 0), (1, 0, 2), (2, 0, 2)),
+                    abi.SPLIT_NESW: ((1, 0, 1), (1, 0, 3), (2, 1, 2), (2, 2, 3), (1, 1, 3), (2, 1, 3))}
+_ROOM_WALL_LINES = ((0, 1), (1, 2), (2, 3), (3, 0), (0, 2))
+# the preview's own (x0, z0, x1, z1) per wall direction as selectors, viewport_3d.rs:5305-5311 (rows 0 and 1 are unused): WallSouth and
+# WallWest run the other way round than at every other site
+_ROOM_PREVIEW_SEL = np.array([[0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 1, 0], [1, 0, 1, 1], [0, 1, 1, 1], [0, 0, 0, 1], [0, 0, 1, 1], [1, 0, 0, 1]], bool)
+
+
+def _f32_min(a, b):
+    """f32::min: a NaN loses."""
+    a, b = np.float32(a), np.float32(b)
+    return b if np.isnan(a) else (a if np.isnan(b) else (b if b < a else a))
+
+
+def _f32_max(a, b):
+    a, b = np.float32(a), np.float32(b)
+    return b if np.isnan(a) else (a if np.isnan(b) else (b if b > a else a))
+
+
+def room_overlay_layout(n, overlay):
+    """First record of every part, the total, and the preview's rectangle and gate (viewport_3d.rs:5252-5258): {"vertices", "edges", "hover",
+    "sel_faces", "sel_edges", "preview", "points", "total", "rect", "gate"} -- a function of n, the struct and the lists' lengths alone."""
+    o = overlay
+    if (o.sections & ~abi.ROOM_OVERLAY_ALL) or o.hover_source > 1:
+        raise ValueError("RoomOverlay: unknown section bit or hover source")
+    if len(o.edges) and int(o.edges[:, 1].max()) > 3:
+        raise ValueError("RoomOverlay: edge_idx > 3")
+    if len(o.vertices) > 1 and not (np.diff(o.vertices.astype(np.int64)) > 0).all():
+        raise ValueError("RoomOverlay: vertex keys not strictly ascending")
+    lay, at = {}, 0
+    lay["vertices"] = at
+    at += len(o.vertices) + 1 if o.sections & abi.ROOM_OVERLAY_VERTICES else 0
+    lay["edges"] = at
+    at += len(o.edges) if o.sections & abi.ROOM_OVERLAY_EDGES else 0
+    lay["hover"] = at
+    at += 7 if o.sections & abi.ROOM_OVERLAY_HOVER else 0
+    lay["sel_faces"] = at
+    at += 6 * len(o.faces) if o.sections & abi.ROOM_OVERLAY_SELECTED else 0
+    lay["sel_edges"] = at
+    at += len(o.edges) if o.sections & abi.ROOM_OVERLAY_SELECTED else 0
+    x0, y0, x1, y1 = o.rect
+    rect = (_f32_min(x0, x1), _f32_min(y0, y1), _f32_max(x0, x1), _f32_max(y0, y1))
+    with np.errstate(all="ignore"):
+        gate = bool(o.sections & abi.ROOM_OVERLAY_PREVIEW) and bool((rect[2] - rect[0]) > np.float32(3.0) or (rect[3] - rect[1]) > np.float32(3.0))
+    lay["preview"] = at
+    at += 4 * n if gate else 0
+    lay["points"] = at
+    at += 3 * len(o.points) if gate else 0
+    lay["total"], lay["rect"], lay["gate"] = at, rect, gate
+    return lay
+
+
+def room_overlay_record_count(n, overlay):
+    """How many records b32_draw_room_overlay makes for a room of n records (b32_room_overlay_record_count)."""
+    return room_overlay_layout(n, overlay)["total"]
+
+
+def _np_draw_3d_lines(P0, P1, camera, w, h):
+    """draw_3d_line (viewport_3d.rs:5687-5695, :5783-5882) for m segments at once in f32: the near clip, world_to_screen, the 16 rounds of
+    clip_line_to_rect, the cast.  Returns (x0, y0, x1, y1 as int64, state): state 0 drawn, 1 dropped, 2 rejected (an extent >= 2^30)."""
+    f32 = np.float32
+    m = len(P0)
+    pos, bx, by, bz = (np.array([f32(v) for v in getattr(camera, k)], f32) for k in ("position", "basis_x", "basis_y", "basis_z"))
+    vdot = lambda r, b: (r[:, 0] * b[0] + r[:, 1] * b[1]) + r[:, 2] * b[2]
+    NEAR = f32(0.1)
+    vs = (f32(min(w, h)) / f32(2.0)) * f32(0.75)
+    hw, hh = f32(w) / f32(2.0), f32(h) / f32(2.0)
+    with np.errstate(all="ignore"):
+        def project(P):
+            rel = P - pos
+            cx, cy, cz = vdot(rel, bx), vdot(rel, by), vdot(rel, bz)
+            denom = cz + f32(5.0)
+            return (cx * f32(4.0) / denom) * vs + hw, (cy * f32(4.0) / denom) * vs + hh, cz
+
+        z0, z1 = vdot(P0 - pos, bz), vdot(P1 - pos, bz)
+        b0, b1 = z0 <= NEAR, z1 <= NEAR
+        t = (NEAR - z0) / (z1 - z0)
+        Q = (P0 + (P1 - P0) * t[:, None]).astype(f32)
+        C0 = np.where((b0 & ~b1)[:, None], Q, P0); C1 = np.where((~b0 & b1)[:, None], Q, P1)
+        x0, y0, d0 = project(C0); x1, y1, d1 = project(C1)
+        ok = ~(b0 & b1) & ~(d0 <= NEAR) & ~(d1 <= NEAR)
+        xmax, ymax, one, zero = f32(w), f32(h), f32(1.0), f32(0.0)
+
+        def outcode(x, y):
+            return np.where(x < zero, 1, np.where(x >= xmax, 2, 0)) | np.where(y < zero, 8, np.where(y >= ymax, 4, 0))
+
+        c0, c1 = outcode(x0, y0), outcode(x1, y1)
+        live = np.ones(m, bool); accept = np.zeros(m, bool)
+        for _ in range(16):                         # lanes that have returned keep their state
+            acc = live & ((c0 | c1) == 0); rej = live & ((c0 & c1) != 0)
+            accept |= acc; live &= ~(acc | rej)
+            if not live.any():
+                break
+            co = np.where(c0 != 0, c0, c1)
+            bot, top, right = (co & 4) != 0, (co & 8) != 0, (co & 2) != 0
+            dx, dy = x1 - x0, y1 - y0
+            xh = np.where(bot, x0 + dx * (ymax - one - y0) / dy, x0 + dx * (zero - y0) / dy)
+            yv = np.where(right, y0 + dy * (xmax - one - x0) / dx, y0 + dy * (zero - x0) / dx)
+            horiz = bot | top
+            nx = np.where(horiz, xh, np.where(right, xmax - one, zero)).astype(f32)
+            ny = np.where(horiz, np.where(bot, ymax - one, zero), yv).astype(f32)
+            first = live & (co == c0); second = live & ~(co == c0)
+            x0 = np.where(first, nx, x0); y0 = np.where(first, ny, y0); x1 = np.where(second, nx, x1); y1 = np.where(second, ny, y1)
+            c0 = np.where(first, outcode(x0, y0), c0); c1 = np.where(second, outcode(x1, y1), c1)
+    ix0, iy0, ix1, iy1 = (_ov_i32(v).astype(np.int64) for v in (x0, y0, x1, y1))
+    lim = 1 << 30
+    state = np.where(ok & accept, np.where((np.abs(ix1 - ix0) >= lim) | (np.abs(iy1 - iy0) >= lim), 2, 0), 1)
+    return ix0, iy0, ix1, iy1, state
+
+
+def room_overlay_records(faces, grid, overlay, camera, w, h, materials=None, with_counts=False):
+    """The numpy / float32 mirror of b32_draw_room_overlay: the abi.PRIM_DTYPE records, place for place, that the device makes from the
+    room's records (abi.SECTOR_FACE_DTYPE), its materials (abi.FACE_MATERIAL_DTYPE or None: none set) and `overlay` (a RoomOverlay, whose
+    `hover` is read whatever its hover_source) -- the sections of draw_viewport_3d at viewport_3d.rs:4273-4658 and :4862-5362.
+    with_counts: also (drawn, dropped, rejected), what the call adds to b32_gizmo_counts."""
+    f32 = np.float32
+    o = overlay
+    F = np.ascontiguousarray(faces, abi.SECTOR_FACE_DTYPE).reshape(-1)
+    M = None if materials is None else np.ascontiguousarray(materials, abi.FACE_MATERIAL_DTYPE).reshape(-1)
+    n = len(F)
+    G = _room_grid(grid)
+    g = G[0]
+    px, py, pz = (f32(v) for v in g["position"]); S = f32(g["sector_size"])
+    lay = room_overlay_layout(n, o)
+    out = noop_prims(lay["total"])
+    counts = np.zeros(3, np.int64)
+    col = ROOM_OVERLAY_COLORS
+    lim = 1 << 30
+
+    def corner(rec, xsel, zsel, H, k):
+        """(m, 3) positions: the lattice place the selectors name, with height H[i, k[i]]"""
+        with np.errstate(all="ignore"):
+            bx = px + F["gx"][rec].astype(f32) * S
+            bz = pz + F["gz"][rec].astype(f32) * S
+            return np.stack([np.where(xsel, bx + S, bx), py + H[np.arange(len(rec)), k], np.where(zsel, bz + S, bz)], axis=1).astype(f32)
+
+    def corners(rec, k, H=None):
+        """corner k of records rec as every site but the preview places it (viewport_3d.rs:6603-6657)"""
+        kind = F["kind"][rec].astype(np.int64)
+        return corner(rec, _ROOM_XSEL[kind, k], _ROOM_ZSEL[kind, k], F["heights"][rec] if H is None else H, k)
+
+    def screen(P):
+        with np.errstate(all="ignore"):
+            sx, sy, _cz, some = _project_f32(P[:, 0], P[:, 1], P[:, 2], camera, w, h, None)
+        return sx, sy, some
+
+    def tally(state):
+        counts[:] += np.bincount(state, minlength=3)[:3]
+
+    def lines(idx, P0, P1, rgb):
+        """draw_3d_line per row into out[idx]"""
+        if not len(idx):
+            return
+        x0, y0, x1, y1, state = _np_draw_3d_lines(P0, P1, camera, w, h)
+        tally(state)
+        i = idx[state == 0]
+        d = state == 0
+        out["x0"][i], out["y0"][i], out["x1"][i], out["y1"][i] = x0[d], y0[d], x1[d], y1[d]
+        out["size"][i] = 0
+        out["r"][i], out["g"][i], out["b"][i] = rgb
+        out["kind"][i], out["alpha"][i] = abi.LINE_2D, 0           # (as b32_draw_gizmos leaves it: LINE_2D reads no alpha)
+
+    def circles(idx, P, radius, rgb):
+        if not len(idx):
+            return
+        sx, sy, some = screen(P)
+        x, y = _ov_i32(sx).astype(np.int64), _ov_i32(sy).astype(np.int64)
+        state = np.where(some, np.where((np.abs(x) >= lim) | (np.abs(y) >= lim), 2, 0), 1)
+        tally(state)
+        d = state == 0
+        i = idx[d]
+        out["x0"][i], out["y0"][i], out["size"][i] = x[d], y[d], np.broadcast_to(radius, len(idx))[d]
+        out["r"][i], out["g"][i], out["b"][i] = rgb
+        out["kind"][i], out["alpha"][i] = abi.PRIM_CIRCLE, 255
+
+    def thick(idx, rec, e, rgb):
+        """draw_edge_highlight's fb.draw_thick_line(.., 3, color) per row (:4373-4384)"""
+        if not len(idx):
+            return
+        ax, ay, asome = screen(corners(rec, e))
+        bx_, by_, bsome = screen(corners(rec, (e + 1) % 4))
+        x0, y0, x1, y1 = (_ov_i32(v).astype(np.int64) for v in (ax, ay, bx_, by_))
+        state = np.where(asome & bsome, np.where((np.abs(x1 - x0) >= lim) | (np.abs(y1 - y0) >= lim), 2, 0), 1)
+        tally(state)
+        d = state == 0
+        i = idx[d]
+        out["x0"][i], out["y0"][i], out["x1"][i], out["y1"][i], out["size"][i] = x0[d], y0[d], x1[d], y1[d], 3
+        out["r"][i], out["g"][i], out["b"][i] = rgb
+        out["kind"][i], out["alpha"][i] = abi.PRIM_THICK_LINE, 255
+
+    def face_lines(first, rec, rgb):
+        """the six slots of faces `rec` (all < n) from out[first[i]] on"""
+        if not len(rec):
+            return
+        kind = F["kind"][rec]
+        flat = kind < 2
+        H1 = F["heights"][rec]
+        H2, nesw = H1, np.zeros(len(rec), bool)
+        if M is not None:
+            H2 = np.where(((M["flags"][rec] & abi.MAT_HAS_HEIGHTS_2) != 0)[:, None], M["heights_2"][rec], H1)
+            nesw = M["split_direction"][rec] == abi.SPLIT_NESW
+        for j in range(6):
+            for split in (abi.SPLIT_NWSE, abi.SPLIT_NESW):
+                sel = flat & (nesw == (split == abi.SPLIT_NESW))
+                which, a, b = _ROOM_FACE_LINES[split][j]
+                H = (H1 if which == 1 else H2)[sel]
+                r = rec[sel]
+                lines(first[sel] + j, corners(r, np.full(len(r), a), H), corners(r, np.full(len(r), b), H), rgb)
+            if j < 5:
+                a, b = _ROOM_WALL_LINES[j]
+                r = rec[~flat]
+                lines(first[~flat] + j, corners(r, np.full(len(r), a)), corners(r, np.full(len(r), b)), rgb)
+
+    hov = o.hover
+    winner = room_hover_winner(hov)
+
+    if o.sections & abi.ROOM_OVERLAY_VERTICES:
+        keys = o.vertices.astype(np.int64)
+        m = len(keys)
+        hk = None
+        if winner == 0 and int(hov["vertex_rec"]) < n:
+            hk = int(hov["vertex_rec"]) * 4 + (int(hov["vertex_corner"]) & 3)
+        rank = int(np.searchsorted(keys, hk, "left")) if hk is not None else m
+        place = lay["vertices"] + np.arange(m) + (np.arange(m) >= rank)
+        ok = (keys >> 2) < n
+        k = keys[ok]
+        circles(place[ok], corners(k >> 2, k & 3), np.where(k == o.primary_vertex, 5, 4), col["selected_vertex"])
+        if hk is not None and not (rank < m and keys[rank] == hk):
+            circles(np.array([lay["vertices"] + rank]), corners(np.array([hk >> 2]), np.array([hk & 3])), 4, col["hover_vertex"])
+
+    pairs = o.edges.astype(np.int64)
+    pair_ok = pairs[:, 0] < n if len(pairs) else np.zeros(0, bool)
+    if (o.sections & abi.ROOM_OVERLAY_EDGES) and len(pairs):
+        thick(lay["edges"] + np.nonzero(pair_ok)[0], pairs[pair_ok, 0], pairs[pair_ok, 1], col["selected_edge"])
+
+    if o.sections & abi.ROOM_OVERLAY_HOVER:
+        if winner == 1 and int(hov["edge_rec"]) < n:
+            thick(np.array([lay["hover"]]), np.array([int(hov["edge_rec"])]), np.array([int(hov["edge_idx"]) & 3]), col["hover_edge"])
+        fr = int(hov["face_rec"])
+        if winner == 2 and fr < n and not (o.skip[0] <= fr < o.skip[0] + o.skip[1]):
+            face_lines(np.array([lay["hover"] + 1]), np.array([fr]), col["hover_face"])
+
+    if o.sections & abi.ROOM_OVERLAY_SELECTED:
+        rec = o.faces.astype(np.int64)
+        ok = rec < n
+        face_lines((lay["sel_faces"] + 6 * np.arange(len(rec)))[ok], rec[ok], col["selected"])
+        if len(pairs):
+            r, e = pairs[pair_ok, 0], pairs[pair_ok, 1]
+            lines(lay["sel_edges"] + np.nonzero(pair_ok)[0], corners(r, e), corners(r, (e + 1) % 4), col["selected"])
+
+    if lay["gate"]:
+        words, _ = RoomMirror(F, G, camera, w, h).box_select(lay["rect"], o.points)
+        sel = np.unpackbits(words.view(np.uint8), bitorder="little")[:n + len(o.points)].astype(bool) if len(words) else np.zeros(0, bool)
+        rec = np.nonzero(sel[:n])[0]
+        kind = F["kind"][rec].astype(np.int64)
+        flat = kind < 2
+        for j in range(4):
+            ka, kb = np.full(len(rec), j), np.full(len(rec), (j + 1) % 4)
+            ends = []
+            for k in (ka, kb):
+                first_end = (k == 0) | (k == 3)                      # corners 0 and 3 stand at (x0, z0), 1 and 2 at (x1, z1)
+                ps = _ROOM_PREVIEW_SEL[kind]
+                xsel = np.where(flat, _ROOM_XSEL[kind, k], np.where(first_end, ps[:, 0], ps[:, 2]))
+                zsel = np.where(flat, _ROOM_ZSEL[kind, k], np.where(first_end, ps[:, 1], ps[:, 3]))
+                ends.append(corner(rec, xsel, zsel, F["heights"][rec], k))
+            lines(lay["preview"] + 4 * rec + j, ends[0], ends[1], col["preview"])
+        pt = np.nonzero(sel[n:])[0]
+        P = o.points[pt]
+        size = f32(64.0)
+        for j in range(3):
+            d = np.zeros(3, f32); d[j] = size
+            with np.errstate(all="ignore"):
+                lines(lay["points"] + 3 * pt + j, (P - d).astype(f32), (P + d).astype(f32), col["preview"])
+    return (out, tuple(int(v) for v in counts)) if with_counts else out
+
+
 class Room:
     """A resident room (b32_room): its grid and its abi.SECTOR_FACE_DTYPE records on the device.  update() is a height drag."""
 
@@ -1495,6 +1803,13 @@ class Context:
                                                     abi.ptr(sel) if len(sel) else None, C.byref(n)), "mesh_overlay_record_count")
         return int(n.value)
 
+    def room_overlay_record_count(self, room, overlay):
+        """b32_room_overlay_record_count (host only)."""
+        o, (_v, e, f, _p) = overlay.pack()
+        n = C.c_uint32()
+        _chk(self.lib.b32_room_overlay_record_count(room._h, C.byref(o), e, f, C.byref(n)), "room_overlay_record_count")
+        return int(n.value)
+
     def gizmo_project_batch(self, items, camera: T.Camera, ortho, width, height):
         """b32_gizmo_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_gizmos hands to the tile pass for a width x height
         framebuffer -- one per item, `size` of them for a thick line of thickness > 1 -- in item order; synchronous."""
@@ -1864,6 +2179,26 @@ class Framebuffer:
         args, _keep = self._overlay_args(scene, topology, overlay, camera, ortho, selected)
         _chk(self.ctx.lib.b32_mesh_overlay_project_batch(*args, width or self.width, height or self.height, abi.ptr(out) if n else None, n,
                                                          C.byref(got)), "mesh_overlay_project_batch")
+        return out[:int(got.value)]
+
+    # ---- the world editor's room overlays from a resident room (editor/viewport_3d.rs:4273-4658, :4862-5362): b32_draw_room_overlay
+    def draw_room_overlay(self, room, overlay, camera: T.Camera):
+        """b32_draw_room_overlay: the sections of `overlay` (a RoomOverlay) made into records on the device from the records of `room` (a
+        Room) as they are there -- and, with hover_source = abi.ROOM_OVERLAY_HOVER_RESIDENT, from its last hover without waiting for it --
+        and drawn in the reference's order; enqueued, no host synchronisation, nothing read back."""
+        cam = camera.pack()
+        o, lists = overlay.pack()
+        _chk(self.ctx.lib.b32_draw_room_overlay(self.ctx.h, C.byref(cam), room._h, C.byref(o), *lists), "draw_room_overlay")
+
+    def room_overlay_project_batch(self, room, overlay, camera: T.Camera, width=None, height=None):
+        """b32_room_overlay_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_room_overlay hands to the tile pass."""
+        n = room_overlay_record_count(room.n, overlay)
+        out = np.zeros(n, abi.PRIM_DTYPE)
+        got = C.c_uint32()
+        cam = camera.pack()
+        o, lists = overlay.pack()
+        _chk(self.ctx.lib.b32_room_overlay_project_batch(self.ctx.h, C.byref(cam), room._h, C.byref(o), *lists, width or self.width, height or self.height,
+                                                         abi.ptr(out) if n else None, n, C.byref(got)), "room_overlay_project_batch")
         return out[:int(got.value)]
 
     def present_nearest(self, dst_w, dst_h):

@@ -976,6 +976,75 @@ int b32_mesh_overlay_project_batch(b32_ctx* ctx, const B32Camera* camera, const 
  * for the sections that are on.  The argument rules of b32_draw_mesh_overlay. */
 int b32_mesh_overlay_record_count(const b32_topology* topology /* nullable */, uint32_t nv, const B32MeshOverlay* overlay,
                                   const uint32_t* selected, uint32_t* n);
+/* The world editor's room overlays (editor/viewport_3d.rs:4273-4658, :4862-5362), drawn from a room's RESIDENT sector table: draw_viewport_3d
+ * draws them out of hovered_vertex / hovered_edge / hovered_face, state.selection, state.multi_selection and the box-select preview, from
+ * the sector heights, which after b32_room_update exist in the room only.  One call makes, on the device, the B32Prim records of the
+ * sections asked for -- in the bit order below, which is the reference's call order -- and hands them to the ordered tile pass of
+ * b32_draw_prims without visiting the host.  Only B32_LINE_2D, B32_PRIM_CIRCLE and B32_PRIM_THICK_LINE records are made.  The arithmetic is
+ * the reference's, operation for operation (f32, no contraction, saturating `as i32`); all colours are RasterColor::new (blend Opaque);
+ * projection is world_to_screen (math.rs:503-534), perspective only; draw_3d_line is B32_GIZMO_LINE.  Corners are the room hover's
+ * (bx or bx + S, position[1] + heights[k], bz or bz + S) with the selectors listed there.
+ *   VERTICES  (:4273-4316) the loop is over collect_room_vertices order (:6599-6661), i.e. ascending key 4 * rec + corner, and draws only
+ *             vertices that are selected or hovered: n_vertices + 1 records.  A selected vertex is a circle (100, 255, 100) of radius 5 when
+ *             its key is primary_vertex, else 4.  The hovered vertex, drawn only when the hover's winner is the vertex, is a circle
+ *             (255, 200, 150) of radius 4 at its rank among the keys (coincident corners of neighbouring sectors project to one pixel: the
+ *             later circle wins); when it is also selected its record draws nothing.  Without a hovered vertex the last record is the no-op.
+ *   EDGES     (:4318-4402) one B32_PRIM_THICK_LINE per (rec, edge_idx) pair, thickness 3, (100, 255, 100), between corners edge_idx and
+ *             (edge_idx + 1) % 4 of `heights`; either end None: nothing.
+ *   HOVER     1 + 6 records.  Winner edge: the thick line of :4404-4478 in (255, 200, 100).  Winner face, and face_rec outside
+ *             [skip_first, skip_first + skip_count): the draw_3d_line calls of :4493-4654 in (150, 200, 255) -- floor and ceiling six, in
+ *             the order of :4513-4532, triangle 1 from `heights`, triangle 2 from get_heights_2(), split_direction from the room's material
+ *             table (no table set: the record's own heights and B32_SPLIT_NWSE, the reference's defaults); a wall five.
+ *   SELECTED  draw_selection (:4862-5247) in (255, 200, 80): the listed faces first, six slots each, the same lines as the hover (a wall's
+ *             sixth slot draws nothing); then the listed edges, one draw_3d_line each (:5174-5236).  Selection::Sector (:5050-5173) is OUT
+ *             OF SCOPE: it draws from a sector's floor and ceiling records at once and comes from the 2-D grid view; a host expresses it
+ *             as B32_GIZMO_LINE items of b32_draw_gizmos.
+ *   PREVIEW   (:5249-5362) in (100, 220, 255).  rect = min / max of (x0, x1) and (y0, y1) (f32::min / max); when neither extent is > 3.0
+ *             the section has NO records.  Element i < n is record i, selected exactly as b32_room_box_select selects it, four slots: the
+ *             outline 0-1, 1-2, 2-3, 3-0 from `heights` only, no diagonal.  The preview's own (x0, z0, x1, z1) of WallSouth and WallWest
+ *             (:5307, :5309) is the reverse of every other site: corner k stands where corner k ^ 1 stands elsewhere and keeps heights[k], so
+ *             a sloped south or west wall previews differently from how it is selected.  Element n + j is point j of points_xyz, three
+ *             slots: the 64.0-unit crosses of :5341-5352, p - Vec3(size, 0, 0) to p + Vec3(size, 0, 0) etc. component by component.
+ * Where a record lies depends on n, this struct and the lists alone -- never on the camera or the heights
+ * (b32_room_overlay_record_count): a call the reference does not make leaves a record that draws nothing (a circle of radius -1); so does
+ * a record whose extent or circle centre reaches 2^30, as in b32_draw_gizmos.  A rec >= n in a list or in `hover` behaves as
+ * get_sector(..) == None.  Every circle, thick line and draw_3d_line the reference calls is added to b32_gizmo_counts' totals: drawn,
+ * dropped (a None projection, a line clipped away) or rejected (2^30).
+ * hover_source 1 reads the 48 bytes of the room's last b32_room_hover[_async] ON THE DEVICE, where a copy enqueued behind that call left
+ * them: the host need not wait for the ticket; the winner rule (b32_room_hover_winner) runs on the device.  With hover_source 0 the
+ * member `hover` is used, raw, all three loops. */
+typedef struct B32RoomOverlay {
+    uint32_t sections;                       /* B32_ROOM_OVERLAY_* bits, in the reference's call order */
+    uint32_t hover_source;                   /* 0: the member `hover`; 1: the room's last b32_room_hover[_async], read on the device */
+    B32RoomHover hover;                      /* raw, all three loops; the library applies the winner rule (:7283-7336) */
+    uint32_t primary_vertex;                 /* key 4 * rec + corner of Selection::Vertex in state.selection, 0xFFFFFFFF none */
+    uint32_t skip_first, skip_count;         /* the records state.selection.includes_face() covers (editor/state.rs:349-363) */
+    uint32_t n_vertices, n_edges, n_faces, n_points;
+    float    x0, y0, x1, y1;                 /* selection_rect_start / _end as stored */
+} B32RoomOverlay;                            /* 100 bytes */
+#define B32_ROOM_OVERLAY_VERTICES 1u  /* :4273-4316 */
+#define B32_ROOM_OVERLAY_EDGES    2u  /* :4318-4402 selected edges, thick */
+#define B32_ROOM_OVERLAY_HOVER    4u  /* :4404-4658 hovered edge (thick), hovered face */
+#define B32_ROOM_OVERLAY_SELECTED 8u  /* :4862-5247 draw_selection: SectorFace and Edge */
+#define B32_ROOM_OVERLAY_PREVIEW 16u  /* :5249-5362 box-select preview, the selection made on the device */
+/* Draws the sections with b32_draw_mesh_overlay's contract: enqueued on the context's stream with no host synchronisation, a deferred
+ * clear flushed first, only rows of the band written, the z-buffer never written, the struct and all four arrays copied before return:
+ * sel_vertices n_vertices keys, strictly ascending; sel_edges n_edges pairs (rec, edge_idx); sel_faces n_faces recs; points_xyz
+ * 3 * n_points floats, the room's object positions.
+ * NULL context, camera, room or overlay, an unknown section bit, hover_source > 1, hover_source 1 before any hover of that room, an
+ * edge_idx > 3 (in sel_edges, or in `hover` with hover_source 0), keys that are not strictly ascending, a count > 0 with a NULL list, a
+ * zero-size framebuffer -> B32_E_ARG.  More than 2^31 - 1 records -> B32_E_UNSUPPORTED.  Nothing is enqueued on error. */
+int b32_draw_room_overlay(b32_ctx* ctx, const B32Camera* camera, b32_room* room, const B32RoomOverlay* overlay, const uint32_t* sel_vertices,
+                          const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz);
+/* Stage tap: the records b32_draw_room_overlay would hand to the tile pass for a width x height framebuffer, copied back (synchronous).
+ * *n_records = how many there are; more than `cap`: B32_E_ARG and nothing is written. */
+int b32_room_overlay_project_batch(b32_ctx* ctx, const B32Camera* camera, b32_room* room, const B32RoomOverlay* overlay,
+                                   const uint32_t* sel_vertices, const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz,
+                                   uint32_t width, uint32_t height, B32Prim* out, uint32_t cap, uint32_t* n_records);
+/* How many records the call makes (host only): (n_vertices + 1) + n_edges + 7 + (6 * n_faces + n_edges) + (4 * n + 3 * n_points when the
+ * rectangle passes the gate), each for the sections that are on.  The rules of b32_draw_room_overlay for the struct and these two lists. */
+int b32_room_overlay_record_count(const b32_room* room, const B32RoomOverlay* overlay, const uint32_t* sel_edges, const uint32_t* sel_faces,
+                                  uint32_t* n);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
