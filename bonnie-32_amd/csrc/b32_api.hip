@@ -270,8 +270,8 @@ int b32_draw_star_diamonds(b32_ctx* c, const int32_t* cx, const int32_t* cy, con
 }
 }  // extern "C"
 
-// The ordered tile pass (b32_draw_pass.h) on the stream, in three steps that b32_draw_lines / b32_draw_prims (records from the host) and
-// b32_draw_world (records a kernel wrote on the device) put together.
+// The ordered tile pass (b32_draw_pass.h) on the stream, in three steps that b32_draw_lines / b32_draw_prims (records from the host:
+// draw_pass) and the record producers (records a kernel wrote on the device: produce_draw) put together.
 
 // Before a pass: a pending frame settled (safe mode), a deferred clear flushed.
 static int draw_enter(b32_ctx* c) {
@@ -339,63 +339,138 @@ static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32
     return draw_resident(c, ps, a, true, route);
 }
 
-// ------------------------------------------------------------------ world-space items (b32_world.hip)
-static int world_check(const B32WorldItem* items, uint32_t n) {
-    for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is enqueued
-        const B32WorldItem& it = items[i];
-        const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
-        if (it.kind > B32_PRIM_THICK_LINE || (it.flags & ~B32_WORLD_CLIP_NEAR) || (circle && it.flags) ||
-            (it.kind == B32_PRIM_LINE_BLENDED && it.mode > B32_BLEND_ERASE)) return B32_E_ARG;
-        if (circle && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;      // r * r (render.rs:632)
-    }
-    return B32_OK;
+// ------------------------------------------------------------------ record producers
+// Four features turn caller input into B32Prim records on the device -- in the primitive pass's record buffer, so the records never visit
+// the host -- and hand them to the ordered tile pass: world items, the editor's gizmos, the modeler's mesh overlays and the world editor's
+// room overlays.  Each also has a stage tap (b32_*_project_batch) that runs the same kernel into scratch memory and copies the records to
+// the host.  A producer is a struct that holds the call's arguments and states only what is its own:
+//   prepare(c, w, h)         everything that can fail on the arguments alone: the whole batch checked, the records laid out and counted
+//                            (`total`), the args block `a` filled but for device pointers, the host rows to put on the device (`rows`,
+//                            `n_rows`; none: nullptr, 0).  Enqueues nothing.
+//   bind(c, out, in, tap)    the output, the rows on the device (nullptr: none, or they travel in the kernel argument) and the producer's
+//                            private device state into `a`; tap != nullptr: per-call state from the tap's scratch, not from the context
+//   launch(s, small)         the producer's kernels (small != nullptr: the rows by value, where the producer has such a kernel: SMALL > 0)
+// and, for a draw: staged(c), its pinned ring; pass, the pass's launcher (nullptr: launch_draw); timer(c), events around the launch while
+// profiling is on; routed(c, tiled), its own route counters.  produce_draw and produce_tap below are the only two sequences.
+template <class ArgsT, class RowT, uint32_t SMALL_N>
+struct Producer {
+    using Args = ArgsT; using Row = RowT;
+    static constexpr uint32_t SMALL = SMALL_N;
+    Args a{}; const Row* rows = nullptr; uint32_t n_rows = 0; uint64_t total = 0;
+    static constexpr void (*pass)(hipStream_t, const DrawArgs<B32Prim>&, const B32Prim*) = nullptr;
+    static EventPair* timer(b32_ctx*) { return nullptr; }
+    static void routed(b32_ctx*, bool) {}
+};
+// An entry's drawn / dropped / rejected on the device (zero on first use; the kernels add to them) as a kernel's `counts`.
+static int counts_bind(b32_ctx* c, ArmedWords& w, unsigned long long*& counts) {
+    const int rc = armed_ensure(c, w, 3 * sizeof(unsigned long long), 0);
+    counts = static_cast<unsigned long long*>(w.p);
+    return rc;
 }
-static int world_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, WorldArgs& wa) {
-    { const int rc = armed_ensure(c, c->world_counts, 3 * sizeof(unsigned long long), 0); if (rc) return rc; }
-    wa = WorldArgs{};
-    wa.n = n; wa.counts = static_cast<unsigned long long*>(c->world_counts.p);
-    view_fill(wa.v, *cam, w, h, ortho);
+static int counts_read(b32_ctx* c, const ArmedWords& w, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected) {
+    if (!drawn || !dropped || !rejected) return B32_E_ARG;
+    (void)hipSetDevice(c->device);
+    unsigned long long h[3] = { 0, 0, 0 };
+    if (w.p) HIPCHK(c, hipMemcpyAsync(h, w.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
     return B32_OK;
 }
 
-// ------------------------------------------------------------------ the editor's overlay helpers (b32_gizmo.hip)
-// The whole batch, before anything is enqueued; rows (nullable): the items with the index of their first record.  *n_records: how many
-// records the batch becomes.
-static int gizmo_check(const B32GizmoItem* items, uint32_t n, GizmoRow* rows, uint64_t* n_records) {
-    uint64_t first = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const B32GizmoItem& it = items[i];
-        if (it.kind > B32_GIZMO_TRIANGLE_VIEW || it._pad[0] || it._pad[1] || it._pad[2] ||
-            (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > B32_GIZMO_MAX_THICKNESS)) return B32_E_ARG;
-        if (it.kind == B32_GIZMO_POINT && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;    // r * r (render.rs:632)
-        if (rows) { rows[i].it = it; rows[i].first = (uint32_t)first; }
-        first += (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > 1) ? (uint32_t)it.size : 1u;
+// World-space items (b32_world.hip; draw.rs:12-67, math.rs:503-652): record i from item i.
+struct WorldProducer : Producer<WorldArgs, B32WorldItem, WORLD_SMALL> {
+    const B32Camera* cam; const B32Ortho* ortho; const B32WorldItem* items; uint32_t n;
+    int prepare(b32_ctx*, uint32_t w, uint32_t h) {
+        for (uint32_t i = 0; i < n; ++i) {
+            const B32WorldItem& it = items[i];
+            const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
+            if (it.kind > B32_PRIM_THICK_LINE || (it.flags & ~B32_WORLD_CLIP_NEAR) || (circle && it.flags) ||
+                (it.kind == B32_PRIM_LINE_BLENDED && it.mode > B32_BLEND_ERASE)) return B32_E_ARG;
+            if (circle && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;      // r * r (render.rs:632)
+        }
+        a.n = n;
+        view_fill(a.v, *cam, w, h, ortho);
+        rows = items; n_rows = n; total = n;
+        return B32_OK;
     }
-    *n_records = first;
-    return B32_OK;
-}
-static int gizmo_args(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, uint32_t w, uint32_t h, uint32_t n, GizmoArgs& ga) {
-    { const int rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0); if (rc) return rc; }
-    ga = GizmoArgs{};
-    ga.w.n = n; ga.w.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
-    view_fill(ga.w.v, *cam, w, h, ortho);
-    return B32_OK;
-}
+    int bind(b32_ctx* c, B32Prim* out, const B32WorldItem* in, Scratch*) {
+        a.out = out; a.items = in;
+        return counts_bind(c, c->world_counts, a.counts);
+    }
+    void launch(hipStream_t s, const B32WorldItem* small) const { launch_world_project(s, a, small); }
+    static Staged<B32WorldItem>& staged(b32_ctx* c) { return c->world; }
+    static EventPair* timer(b32_ctx* c) { return &c->world_timer; }         // (b32_last_kernel_times "world_project")
+    static void routed(b32_ctx* c, bool tiled) { ++(tiled ? c->world_tile_batches : c->world_scan_batches); }
+};
+
+// The editor's overlay helpers (b32_gizmo.hip; viewport_3d.rs:5687-6357): the rows are the items with the index of their first record (a
+// thick line becomes `thickness` records), drawn by the pass's GizmoPass kernels.
+struct GizmoProducer : Producer<GizmoArgs, GizmoRow, GIZMO_SMALL> {
+    const B32Camera* cam; const B32Ortho* ortho; const B32GizmoItem* items; uint32_t n;
+    GizmoRow few[GIZMO_SMALL];                                                // (a small batch's rows: no allocation)
+    int prepare(b32_ctx* c, uint32_t w, uint32_t h) {
+        GizmoRow* r = few;
+        if (n > GIZMO_SMALL) { c->gizmo_rows.resize(n); r = c->gizmo_rows.data(); }
+        for (uint32_t i = 0; i < n; ++i) {
+            const B32GizmoItem& it = items[i];
+            if (it.kind > B32_GIZMO_TRIANGLE_VIEW || it._pad[0] || it._pad[1] || it._pad[2] ||
+                (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > B32_GIZMO_MAX_THICKNESS)) return B32_E_ARG;
+            if (it.kind == B32_GIZMO_POINT && std::llabs((long long)it.size) > 32767) return B32_E_UNSUPPORTED;    // r * r (render.rs:632)
+            r[i].it = it; r[i].first = (uint32_t)total;
+            total += (it.kind == B32_GIZMO_THICK_LINE_DEPTH && it.size > 1) ? (uint32_t)it.size : 1u;
+        }
+        if (total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+        a.w.n = n;
+        view_fill(a.w.v, *cam, w, h, ortho);
+        rows = r; n_rows = n;
+        return B32_OK;
+    }
+    int bind(b32_ctx* c, B32Prim* out, const GizmoRow* in, Scratch*) {
+        a.w.out = out; a.rows = in;
+        return counts_bind(c, c->gizmo_counts, a.w.counts);
+    }
+    void launch(hipStream_t s, const GizmoRow* small) const { launch_gizmo_project(s, a, small); }
+    static Staged<GizmoRow>& staged(b32_ctx* c) { return c->gizmo; }
+    static constexpr auto pass = launch_draw_gizmo;
+};
 
 // ------------------------------------------------------------------ the modeler's selection overlays (b32_overlay.hip)
-// Everything checked and laid out before anything is enqueued: the kernels' arguments but for the device buffers the caller provides
-// (out, tab, selected), the list to upload (*up / *n_up words: the list as given, or c->overlay_pairs for polygons), the record total.
-static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const b32_scene* slot, const b32_topology* topo,
-                           const B32MeshOverlay* o, const uint32_t* selected, uint32_t w, uint32_t h, OverlayArgs& a, const uint32_t** up,
-                           uint32_t* n_up, uint64_t* total) {
-    if (!c || !cam || !slot || !o || !w || !h || !slot->have_scene) return B32_E_ARG;
+// the bounds' keys: armed whenever no overlay is running (allocated so; k_overlay_emit leaves them so)
+static int overlay_bounds(b32_ctx* c, OverlayArgs& a) {
+    if (!c->overlay_bounds) {
+        static const OverlayBounds armed = overlay_bounds_start();
+        HIPCHK(c, hipMalloc(&c->overlay_bounds, sizeof(OverlayBounds)));
+        HIPCHK(c, hipMemcpyAsync(c->overlay_bounds, &armed, sizeof(OverlayBounds), hipMemcpyHostToDevice, c->stream));
+    }
+    a.bounds = static_cast<OverlayBounds*>(c->overlay_bounds);
+    return B32_OK;
+}
+
+// (modeler/viewport.rs:1782-2247) Made into records by k_overlay_points / k_overlay_emit from the slot's vertices as they are on the
+// device.  The rows are the selected list to upload: the list as given, or c->overlay_pairs for polygons.
+struct MeshOverlayProducer : Producer<OverlayArgs, uint32_t, 0> {
+    const B32Camera* cam; const B32Ortho* ortho; const b32_scene* slot; const b32_topology* topo; const B32MeshOverlay* o; const uint32_t* selected;
+    int prepare(b32_ctx* c, uint32_t w, uint32_t h);
+    int bind(b32_ctx* c, B32Prim* out, const uint32_t* in, Scratch* tap) {    // the point table and the bounds
+        int rc;
+        a.out = out; a.selected = in;
+        if (tap) { if ((rc = tap->alloc(&a.tab, (size_t)a.nv))) return rc; }
+        else {
+            if ((rc = ensure(c, c->overlay_tab, c->overlay_cap_tab, (size_t)a.nv))) return rc;
+            a.tab = reinterpret_cast<OverlayPoint*>(c->overlay_tab);
+        }
+        return overlay_bounds(c, a);
+    }
+    void launch(hipStream_t s, const uint32_t*) const { launch_overlay(s, a); }
+    static Staged<uint32_t>& staged(b32_ctx* c) { return c->overlay_sel; }
+};
+int MeshOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
+    if (!cam || !slot || !o || !w || !h || !slot->have_scene) return B32_E_ARG;
     { const int rc = overlay_check(topo != nullptr, o, selected); if (rc) return rc; }
     const uint32_t np = topo ? topo->np : 0u, nh = topo ? topo->nh : 0u;
     const OverlayLayout l = overlay_layout(topo ? topo->h_poly_start.data() : nullptr, np, nh, topo ? topo->ne : 0u, slot->nv, *o, selected);
-    *total = l.total;
+    total = l.total;
     if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
-    a = OverlayArgs{};
-    (void)hipSetDevice(c->device);
     view_fill(a.v, *cam, w, h, ortho);
     const bool packed = slot->pos_valid && slot->d_pos12;
     a.pos = packed ? slot->d_pos12 : reinterpret_cast<const float*>(slot->d_verts);
@@ -407,7 +482,6 @@ static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ort
     a.at_hover_vertex = (uint32_t)l.hover_vertex; a.at_hover_edge = (uint32_t)l.hover_edge; a.at_hover_face = (uint32_t)l.hover_face;
     a.at_selected = (uint32_t)l.selected; a.at_preview = (uint32_t)l.preview;
     a.hover_face_cnt = l.hover_face_cnt;
-    *up = nullptr; *n_up = 0u;
     const uint32_t sec = o->sections;
     const auto groups = [](uint32_t n) { return (uint32_t)(((unsigned long long)n + 255u) / 256u); };
     if (sec & B32_OVERLAY_EDGES) a.g_edges = groups(nh);
@@ -424,11 +498,11 @@ static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ort
                 at += overlay_polygon_slots(OVERLAY_POLY_SELECTED, topo->h_poly_start[p + 1u] - topo->h_poly_start[p]);
             }
             a.n_sel = (uint32_t)(c->overlay_pairs.size() / 2u);
-            *up = c->overlay_pairs.data(); *n_up = (uint32_t)c->overlay_pairs.size();
+            rows = c->overlay_pairs.data(); n_rows = (uint32_t)c->overlay_pairs.size();
         } else {
             if (o->select_kind == 2u && o->n_selected > 0x7FFFFFFFu) return B32_E_UNSUPPORTED;
             a.n_sel = o->n_selected;
-            *up = selected; *n_up = o->select_kind == 2u ? 2u * o->n_selected : o->n_selected;
+            rows = selected; n_rows = o->select_kind == 2u ? 2u * o->n_selected : o->n_selected;
         }
         a.g_sel = groups(a.n_sel);
     }
@@ -438,32 +512,31 @@ static int overlay_prepare(b32_ctx* c, const B32Camera* cam, const B32Ortho* ort
     if ((unsigned long long)a.g_edges + a.g_pedges + a.g_sel + a.g_pfaces + 2u >= (1ull << 31)) return B32_E_UNSUPPORTED;
     return B32_OK;
 }
-// the bounds' keys: armed whenever no overlay is running (allocated so; k_overlay_emit leaves them so)
-static int overlay_bounds(b32_ctx* c, OverlayArgs& a) {
-    if (!c->overlay_bounds) {
-        static const OverlayBounds armed = overlay_bounds_start();
-        HIPCHK(c, hipMalloc(&c->overlay_bounds, sizeof(OverlayBounds)));
-        HIPCHK(c, hipMemcpyAsync(c->overlay_bounds, &armed, sizeof(OverlayBounds), hipMemcpyHostToDevice, c->stream));
-    }
-    a.bounds = static_cast<OverlayBounds*>(c->overlay_bounds);
-    return B32_OK;
-}
 
 // ------------------------------------------------------------------ the world editor's room overlays (b32_room_overlay.hip)
-// Everything checked and laid out before anything is enqueued: the kernel's arguments but for the device buffers the caller provides (out,
-// lists), the call's lists as one run of words in c->overlay_pairs (keys, edge pairs, faces, the points' bits), the record total.
-static int room_overlay_prepare(b32_ctx* c, const B32Camera* cam, const b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
-                                const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz, uint32_t w, uint32_t h,
-                                RoomOverlayArgs& a, uint64_t* total) {
-    if (!c || !cam || !room || !o || !w || !h) return B32_E_ARG;
+// (viewport_3d.rs:4273-4658, :4862-5362) Made into records by k_room_overlay from the room's records (and its last hover) as they are on
+// the device.  The rows are the call's lists as one run of words in c->overlay_pairs: keys, edge pairs, faces, the points' bits.  Adds
+// into the gizmo entry's counters (b32_gizmo_counts).
+struct RoomOverlayProducer : Producer<RoomOverlayArgs, uint32_t, 0> {
+    const B32Camera* cam; const b32_room* room; const B32RoomOverlay* o;
+    const uint32_t *sel_vertices, *sel_edges, *sel_faces; const float* points_xyz;
+    int prepare(b32_ctx* c, uint32_t w, uint32_t h);
+    int bind(b32_ctx* c, B32Prim* out, const uint32_t* in, Scratch*) {
+        a.out = out; a.lists = in;
+        return counts_bind(c, c->gizmo_counts, a.counts);
+    }
+    void launch(hipStream_t s, const uint32_t*) const { launch_room_overlay(s, a); }
+    static Staged<uint32_t>& staged(b32_ctx* c) { return c->overlay_sel; }
+};
+int RoomOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
+    if (!cam || !room || !o || !w || !h) return B32_E_ARG;
     { const int rc = room_overlay_check(o, sel_vertices, sel_edges, sel_faces, points_xyz); if (rc) return rc; }
     if (o->hover_source == 1u && !room->have_hover) return B32_E_ARG;
     const RoomOverlayLayout l = room_overlay_layout(room->n, *o);
-    *total = l.total;
+    total = l.total;
     if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
     const uint64_t words = (uint64_t)o->n_vertices + 2ull * o->n_edges + o->n_faces + 3ull * o->n_points;
     if (words > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
-    a = RoomOverlayArgs{};
     view_fill(a.v, *cam, w, h, nullptr);
     a.grid = room->grid; a.faces = room->faces; a.mats = room->have_mats ? room->mats : nullptr; a.n = room->n;
     a.hover = o->hover_source == 1u ? static_cast<const B32RoomHover*>(room->d_hover) : nullptr;
@@ -485,6 +558,65 @@ static int room_overlay_prepare(b32_ctx* c, const B32Camera* cam, const b32_room
     if (sec & B32_ROOM_OVERLAY_HOVER) a.g_hover = 1u;
     if (sec & B32_ROOM_OVERLAY_SELECTED) { a.g_sel_faces = groups(o->n_faces); a.g_sel_edges = groups(o->n_edges); }
     if (l.gate) { a.g_preview = groups(room->n); a.g_points = groups(o->n_points); }
+    rows = lw.data(); n_rows = (uint32_t)lw.size();
+    return B32_OK;
+}
+
+// Where a producer's rows travel: by value in the kernel argument when it has such a kernel and the batch is small (no staging copy, no
+// pinned-ring slot), else on the device.
+template <class P> static bool rows_by_value(const P& p) { return P::SMALL && p.n_rows <= P::SMALL; }
+
+// A producer's records drawn.  The batch is validated before anything is enqueued and before a pending frame is settled; a batch without
+// records settles and flushes nothing; an empty band returns behind draw_enter without running the producer's kernel (no records, no
+// counts).  The records go into c->prims.dev and are binned and drawn from there like any other primitive batch: the tile route when
+// there are more than PRIM_SMALL of them.
+template <class P>
+static int produce_draw(b32_ctx* c, P& p) {
+    int rc;
+    if ((rc = p.prepare(c, c->width, c->height))) return rc;
+    if (!p.total) return B32_OK;
+    if ((rc = draw_enter(c))) return rc;                                    // (sets the device)
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)p.total))) return rc;
+    const bool by_value = rows_by_value(p);
+    const typename P::Row* d_rows = nullptr;
+    if (!by_value && p.n_rows) {
+        if ((rc = stage_records(c, P::staged(c), p.rows, p.n_rows))) return rc;
+        d_rows = P::staged(c).dev;
+    }
+    if ((rc = p.bind(c, c->prims.dev, d_rows, nullptr))) return rc;
+    EventPair* timer = c->profile_level >= 1 ? P::timer(c) : nullptr;
+    if (timer) HIPCHK(c, timer->begin(c->stream));
+    p.launch(c->stream, by_value ? p.rows : nullptr);
+    HIPCHK(c, hipGetLastError());
+    if (timer) HIPCHK(c, timer->end(c->stream));
+    DrawArgs<B32Prim> d = draw_args<B32Prim>(c, (uint32_t)p.total);
+    d.recs = c->prims.dev;
+    bool tiled = false;
+    if ((rc = draw_resident(c, c->prims, d, p.total > PRIM_SMALL, B32_ROUTE_PRIM_TILES, &tiled, P::pass))) return rc;
+    P::routed(c, tiled);
+    return B32_OK;
+}
+// A producer's records for a w x h framebuffer copied to the host (stage tap): the same kernel in the same launch form as the draw's,
+// into scratch memory.  Needs no framebuffer, ignores the band, and always runs the kernel (the counters move).
+template <class P>
+static int produce_tap(b32_ctx* c, P& p, uint32_t w, uint32_t h, B32Prim* out, uint32_t cap, uint32_t* n_records) {
+    int rc;
+    if ((rc = p.prepare(c, w, h))) return rc;
+    if (p.total > cap || (p.total && !out)) return B32_E_ARG;
+    if (n_records) *n_records = (uint32_t)p.total;
+    if (!p.total) return B32_OK;
+    (void)hipSetDevice(c->device);
+    const bool by_value = rows_by_value(p);
+    B32Prim* d_out = nullptr; typename P::Row* d_rows = nullptr;
+    Scratch tmp(c);
+    if ((rc = tmp.alloc(&d_out, (size_t)p.total))) return rc;
+    if (!by_value && p.n_rows && (rc = tmp.upload(p.rows, (size_t)p.n_rows, &d_rows))) return rc;
+    if ((rc = p.bind(c, d_out, d_rows, &tmp))) return rc;
+    p.launch(c->stream, by_value ? p.rows : nullptr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)p.total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return B32_OK;
 }
 
@@ -518,34 +650,11 @@ int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
     }
     return draw_pass(c, c->prims, prims, n, PRIM_SMALL, B32_ROUTE_PRIM_TILES);
 }
-// World-space items (draw.rs:12-67, math.rs:503-652): projected by k_world_project into the primitive pass's device record buffer, then
-// binned and drawn from there like any other primitive batch.  The records never visit the host.
+// The record producers (above): each a draw and its stage tap.
 int b32_draw_world(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32WorldItem* items, uint32_t n) {
     if (!c || !c->fb || !cam || (n && !items)) return B32_E_ARG;
-    { const int rc = world_check(items, n); if (rc) return rc; }
-    if (!n) return B32_OK;
-    { const int rc = draw_enter(c); if (rc) return rc; }
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    WorldArgs wa;
-    int rc;
-    if ((rc = world_args(c, cam, ortho, c->width, c->height, n, wa))) return rc;
-    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)n))) return rc;
-    wa.out = c->prims.dev;
-    if (n > WORLD_SMALL) {
-        if ((rc = stage_records(c, c->world, items, n))) return rc;
-        wa.items = c->world.dev;
-    }
-    const bool timed = c->profile_level >= 1;
-    if (timed) HIPCHK(c, c->world_timer.begin(c->stream));
-    launch_world_project(c->stream, wa, n > WORLD_SMALL ? nullptr : items);
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, c->world_timer.end(c->stream));
-    DrawArgs<B32Prim> a = draw_args<B32Prim>(c, n);
-    a.recs = c->prims.dev;
-    bool tiled = false;
-    if ((rc = draw_resident(c, c->prims, a, n > PRIM_SMALL, B32_ROUTE_PRIM_TILES, &tiled))) return rc;
-    ++(tiled ? c->world_tile_batches : c->world_scan_batches);
-    return B32_OK;
+    WorldProducer p{ {}, cam, ortho, items, n };
+    return produce_draw(c, p);
 }
 int b32_draw_floor_grid(b32_ctx* c, const B32Camera* cam, float y, float spacing, float extent,
                         const uint8_t grid_rgbb[4], const uint8_t x_axis_rgbb[4], const uint8_t z_axis_rgbb[4]) {
@@ -560,189 +669,51 @@ int b32_draw_floor_grid(b32_ctx* c, const B32Camera* cam, float y, float spacing
 int b32_world_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32WorldItem* items, uint32_t n,
                             uint32_t w, uint32_t h, B32Prim* out) {
     if (!c || !cam || (n && (!items || !out)) || w == 0 || h == 0 || w > 16384 || h > 16384) return B32_E_ARG;
-    { const int rc = world_check(items, n); if (rc) return rc; }
-    if (!n) return B32_OK;
-    (void)hipSetDevice(c->device);
-    WorldArgs wa;
-    int rc;
-    if ((rc = world_args(c, cam, ortho, w, h, n, wa))) return rc;
-    B32WorldItem* d_items = nullptr; B32Prim* d_out = nullptr;
-    Scratch tmp(c);
-    if ((rc = tmp.upload(items, (size_t)n, &d_items))) return rc;
-    if ((rc = tmp.alloc(&d_out, (size_t)n))) return rc;
-    wa.items = d_items; wa.out = d_out;
-    launch_world_project(c->stream, wa, nullptr);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return B32_OK;
+    WorldProducer p{ {}, cam, ortho, items, n };
+    return produce_tap(c, p, w, h, out, n, nullptr);
 }
 int b32_world_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected) {
-    if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    unsigned long long h[3] = { 0, 0, 0 };
-    if (c->world_counts.p) HIPCHK(c, hipMemcpyAsync(h, c->world_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
-    return B32_OK;
+    return c ? counts_read(c, c->world_counts, drawn, dropped, rejected) : B32_E_ARG;
 }
-// The editor's overlay helpers (viewport_3d.rs:5687-6357): projected by k_gizmo_project into the primitive pass's device record buffer, then
-// binned and drawn from there by the pass's GizmoPass kernels.  The records never visit the host.
 int b32_draw_gizmos(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32GizmoItem* items, uint32_t n) {
     if (!c || !c->fb || !cam || (n && !items)) return B32_E_ARG;
-    uint64_t n_rec = 0;
-    GizmoRow small[GIZMO_SMALL];
-    GizmoRow* rows = small;
-    if (n > GIZMO_SMALL) { c->gizmo_rows.resize(n); rows = c->gizmo_rows.data(); }
-    { const int rc = gizmo_check(items, n, rows, &n_rec); if (rc) return rc; }
-    if (!n) return B32_OK;
-    if (n_rec > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
-    { const int rc = draw_enter(c); if (rc) return rc; }
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    GizmoArgs ga;
-    int rc;
-    if ((rc = gizmo_args(c, cam, ortho, c->width, c->height, n, ga))) return rc;
-    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)n_rec))) return rc;
-    ga.w.out = c->prims.dev;
-    if (n > GIZMO_SMALL) {
-        if ((rc = stage_records(c, c->gizmo, rows, n))) return rc;
-        ga.rows = c->gizmo.dev;
-    }
-    launch_gizmo_project(c->stream, ga, n > GIZMO_SMALL ? nullptr : rows);
-    HIPCHK(c, hipGetLastError());
-    DrawArgs<B32Prim> a = draw_args<B32Prim>(c, (uint32_t)n_rec);
-    a.recs = c->prims.dev;
-    return draw_resident(c, c->prims, a, n_rec > PRIM_SMALL, B32_ROUTE_PRIM_TILES, nullptr, launch_draw_gizmo);
+    GizmoProducer p{ {}, cam, ortho, items, n };
+    return produce_draw(c, p);
 }
 int b32_gizmo_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, const B32GizmoItem* items, uint32_t n,
                             uint32_t w, uint32_t h, B32Prim* out, uint32_t cap, uint32_t* n_records) {
     if (!c || !cam || !n_records || (n && !items) || w == 0 || h == 0 || w > 16384 || h > 16384) return B32_E_ARG;
-    std::vector<GizmoRow> rows(n);
-    uint64_t n_rec = 0;
-    { const int rc = gizmo_check(items, n, rows.data(), &n_rec); if (rc) return rc; }
-    if (n_rec > cap || (n_rec && !out)) return B32_E_ARG;
-    *n_records = (uint32_t)n_rec;
-    if (!n) return B32_OK;
-    (void)hipSetDevice(c->device);
-    GizmoArgs ga;
-    int rc;
-    if ((rc = gizmo_args(c, cam, ortho, w, h, n, ga))) return rc;
-    GizmoRow* d_rows = nullptr; B32Prim* d_out = nullptr;
-    Scratch tmp(c);
-    if ((rc = tmp.upload(rows.data(), (size_t)n, &d_rows))) return rc;
-    if ((rc = tmp.alloc(&d_out, (size_t)n_rec))) return rc;
-    ga.rows = d_rows; ga.w.out = d_out;
-    launch_gizmo_project(c->stream, ga, nullptr);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_rec * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return B32_OK;
+    GizmoProducer p{ {}, cam, ortho, items, n };
+    return produce_tap(c, p, w, h, out, cap, n_records);
 }
 int b32_gizmo_counts(b32_ctx* c, uint64_t* drawn, uint64_t* dropped, uint64_t* rejected) {
-    if (!c || !drawn || !dropped || !rejected) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    unsigned long long h[3] = { 0, 0, 0 };
-    if (c->gizmo_counts.p) HIPCHK(c, hipMemcpyAsync(h, c->gizmo_counts.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *drawn = h[0]; *dropped = h[1]; *rejected = h[2];
-    return B32_OK;
+    return c ? counts_read(c, c->gizmo_counts, drawn, dropped, rejected) : B32_E_ARG;
 }
-// The modeler's selection overlays (modeler/viewport.rs:1782-2247): made into records by k_overlay_points / k_overlay_emit in the primitive
-// pass's device record buffer, from the slot's vertices as they are on the device; binned and drawn from there like any other primitive batch.
 int b32_draw_mesh_overlay(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_scene* slot, b32_topology* topo, const B32MeshOverlay* o,
                           const uint32_t* selected) {
     if (!c || !c->fb) return B32_E_ARG;
-    OverlayArgs a; const uint32_t* up = nullptr; uint32_t n_up = 0; uint64_t total = 0;
-    int rc;
-    if ((rc = overlay_prepare(c, cam, ortho, slot, topo, o, selected, c->width, c->height, a, &up, &n_up, &total))) return rc;
-    if (!total) return B32_OK;
-    if ((rc = draw_enter(c))) return rc;
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)total))) return rc;
-    if ((rc = ensure(c, c->overlay_tab, c->overlay_cap_tab, (size_t)a.nv))) return rc;
-    if ((rc = overlay_bounds(c, a))) return rc;
-    a.out = c->prims.dev; a.tab = reinterpret_cast<OverlayPoint*>(c->overlay_tab);
-    if (n_up) {
-        if ((rc = stage_records(c, c->overlay_sel, up, n_up))) return rc;
-        a.selected = c->overlay_sel.dev;
-    }
-    launch_overlay(c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    DrawArgs<B32Prim> d = draw_args<B32Prim>(c, (uint32_t)total);
-    d.recs = c->prims.dev;
-    return draw_resident(c, c->prims, d, total > PRIM_SMALL, B32_ROUTE_PRIM_TILES);
+    MeshOverlayProducer p{ {}, cam, ortho, slot, topo, o, selected };
+    return produce_draw(c, p);
 }
 int b32_mesh_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_scene* slot, b32_topology* topo,
                                    const B32MeshOverlay* o, const uint32_t* selected, uint32_t w, uint32_t h, B32Prim* out, uint32_t cap,
                                    uint32_t* n_records) {
     if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
-    OverlayArgs a; const uint32_t* up = nullptr; uint32_t n_up = 0; uint64_t total = 0;
-    int rc;
-    if ((rc = overlay_prepare(c, cam, ortho, slot, topo, o, selected, w, h, a, &up, &n_up, &total))) return rc;
-    if (total > cap || (total && !out)) return B32_E_ARG;
-    *n_records = (uint32_t)total;
-    if (!total) return B32_OK;
-    B32Prim* d_out = nullptr; OverlayPoint* d_tab = nullptr; uint32_t* d_sel = nullptr;
-    Scratch tmp(c);
-    if ((rc = tmp.alloc(&d_out, (size_t)total))) return rc;
-    if ((rc = tmp.alloc(&d_tab, (size_t)a.nv))) return rc;
-    if (n_up && (rc = tmp.upload(up, (size_t)n_up, &d_sel))) return rc;
-    if ((rc = overlay_bounds(c, a))) return rc;
-    a.out = d_out; a.tab = d_tab; a.selected = d_sel;
-    launch_overlay(c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return B32_OK;
+    MeshOverlayProducer p{ {}, cam, ortho, slot, topo, o, selected };
+    return produce_tap(c, p, w, h, out, cap, n_records);
 }
-// The world editor's room overlays (viewport_3d.rs:4273-4658, :4862-5362): made into records by k_room_overlay in the primitive pass's
-// device record buffer, from the room's records (and its last hover) as they are on the device; binned and drawn from there like any
-// other primitive batch.
 int b32_draw_room_overlay(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
                           const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz) {
     if (!c || !c->fb) return B32_E_ARG;
-    RoomOverlayArgs a; uint64_t total = 0;
-    int rc;
-    if ((rc = room_overlay_prepare(c, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz, c->width, c->height, a, &total))) return rc;
-    if (!total) return B32_OK;
-    (void)hipSetDevice(c->device);
-    if ((rc = draw_enter(c))) return rc;
-    if (c->band_y1 <= c->band_y0) return B32_OK;
-    if ((rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0))) return rc;
-    if ((rc = ensure(c, c->prims.dev, c->prims.cap_dev, (size_t)total))) return rc;
-    a.out = c->prims.dev; a.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
-    if (!c->overlay_pairs.empty()) {
-        if ((rc = stage_records(c, c->overlay_sel, c->overlay_pairs.data(), (uint32_t)c->overlay_pairs.size()))) return rc;
-        a.lists = c->overlay_sel.dev;
-    }
-    launch_room_overlay(c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    DrawArgs<B32Prim> d = draw_args<B32Prim>(c, (uint32_t)total);
-    d.recs = c->prims.dev;
-    return draw_resident(c, c->prims, d, total > PRIM_SMALL, B32_ROUTE_PRIM_TILES);
+    RoomOverlayProducer p{ {}, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz };
+    return produce_draw(c, p);
 }
 int b32_room_overlay_project_batch(b32_ctx* c, const B32Camera* cam, b32_room* room, const B32RoomOverlay* o, const uint32_t* sel_vertices,
                                    const uint32_t* sel_edges, const uint32_t* sel_faces, const float* points_xyz, uint32_t w, uint32_t h,
                                    B32Prim* out, uint32_t cap, uint32_t* n_records) {
     if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
-    RoomOverlayArgs a; uint64_t total = 0;
-    int rc;
-    if ((rc = room_overlay_prepare(c, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz, w, h, a, &total))) return rc;
-    if (total > cap || (total && !out)) return B32_E_ARG;
-    *n_records = (uint32_t)total;
-    if (!total) return B32_OK;
-    (void)hipSetDevice(c->device);
-    if ((rc = armed_ensure(c, c->gizmo_counts, 3 * sizeof(unsigned long long), 0))) return rc;
-    B32Prim* d_out = nullptr; uint32_t* d_lists = nullptr;
-    Scratch tmp(c);
-    if ((rc = tmp.alloc(&d_out, (size_t)total))) return rc;
-    if (!c->overlay_pairs.empty() && (rc = tmp.upload(c->overlay_pairs.data(), c->overlay_pairs.size(), &d_lists))) return rc;
-    a.out = d_out; a.lists = d_lists; a.counts = static_cast<unsigned long long*>(c->gizmo_counts.p);
-    launch_room_overlay(c->stream, a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)total * sizeof(B32Prim), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return B32_OK;
+    RoomOverlayProducer p{ {}, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz };
+    return produce_tap(c, p, w, h, out, cap, n_records);
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
     if (!c || !c->fb || !out || !dw || !dh || dw > 32768 || dh > 32768) return B32_E_ARG;

@@ -10,51 +10,31 @@
 // and the kernel needs no scan.  An item that draws nothing fills its place with circles of radius -1.  The records stay on the device:
 // the ordered tile pass (GizmoPass, b32_prims.hip) reads them where this kernel wrote them.
 #include "b32_gizmo_body.h"
+#include "b32_item_kernels.h"
 
 namespace b32 {
 
-struct GizmoBatch { GizmoRow r[GIZMO_SMALL]; };
-// (4096 bytes is what a launch can carry; the pass's other batches stay under 2048, this one's rows are 52 bytes)
-static_assert(sizeof(B32GizmoItem) == 48 && sizeof(GizmoRow) == 52 && sizeof(GizmoBatch) + sizeof(GizmoArgs) <= 3072, "B32GizmoItem layout / kernel argument size");
-
-// row i of the batch (`live`: i < a.w.n; the other lanes only take part in the counting)
-__device__ __forceinline__ void gizmo_project(const GizmoArgs& a, const GizmoRow& row, bool live) {
-    __shared__ uint32_t tally[3];                               // the workgroup's drawn / dropped / rejected
-    if (threadIdx.x < 3u) tally[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t which = 3u;
-    if (live) which = gizmo_item(a.w.v, row.it, a.w.out + row.first);
-    // one add per wave into LDS, one per workgroup and counter into memory (as k_world_project)
-#pragma unroll
-    for (uint32_t k = 0; k < 3u; ++k) {
-        const unsigned long long m = __ballot(which == k);      // (wave64: one bit per lane)
-        if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&tally[k], (uint32_t)__popcll(m));
+struct GizmoProject {
+    using Args = GizmoArgs; using Row = GizmoRow;
+    static constexpr uint32_t SMALL = GIZMO_SMALL;
+    static __host__ __device__ uint32_t n(const GizmoArgs& a) { return a.w.n; }
+    static __device__ const GizmoRow* rows(const GizmoArgs& a) { return a.rows; }
+    // row i of the batch
+    static __device__ __forceinline__ void item(const GizmoArgs& a, const GizmoRow& row, uint32_t, bool live) {
+        uint32_t* tally = outcome_tally();
+        uint32_t which = 3u;
+        if (live) which = gizmo_item(a.w.v, row.it, a.w.out + row.first);
+        outcome_count(tally, a.w.counts, which);
     }
-    __syncthreads();
-    if (threadIdx.x < 3u && tally[threadIdx.x]) atomicAdd(&a.w.counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
-}
+};
+// (4096 bytes is what a launch can carry; the pass's other batches stay under 2048, this one's rows are 52 bytes)
+static_assert(sizeof(B32GizmoItem) == 48 && sizeof(GizmoRow) == 52 && sizeof(ItemBatch<GizmoProject>) + sizeof(GizmoArgs) <= 3072, "B32GizmoItem layout / kernel argument size");
 
-// a.w.n <= GIZMO_SMALL rows out of the kernel argument: one workgroup
-__global__ __launch_bounds__(256) void k_gizmo_project_small(GizmoArgs a, GizmoBatch batch) {
-    const uint32_t i = threadIdx.x;
-    const bool live = i < a.w.n;
-    gizmo_project(a, live ? batch.r[i] : GizmoRow{}, live);
-}
-__global__ __launch_bounds__(256) void k_gizmo_project(GizmoArgs a) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < a.w.n;
-    gizmo_project(a, live ? a.rows[i] : GizmoRow{}, live);
-}
+__global__ __launch_bounds__(256) void k_gizmo_project_small(GizmoArgs a, ItemBatch<GizmoProject> batch) { item_small<GizmoProject>(a, batch); }
+__global__ __launch_bounds__(256) void k_gizmo_project(GizmoArgs a) { item_large<GizmoProject>(a); }
 
 void launch_gizmo_project(hipStream_t s, const GizmoArgs& a, const GizmoRow* small) {
-    if (!a.w.n) return;
-    if (small) {
-        GizmoBatch batch{};
-        for (uint32_t i = 0; i < a.w.n && i < GIZMO_SMALL; ++i) batch.r[i] = small[i];
-        hipLaunchKernelGGL(k_gizmo_project_small, dim3(1), dim3(256), 0, s, a, batch);
-        return;
-    }
-    hipLaunchKernelGGL(k_gizmo_project, dim3((a.w.n + 255u) / 256u), dim3(256), 0, s, a);
+    launch_items<GizmoProject>(s, k_gizmo_project_small, k_gizmo_project, a, small);
 }
 
 }  // namespace b32

@@ -55,19 +55,28 @@ struct FrameSet {
     }
 };
 
-// What one ordered tile pass (b32_draw_pass.h) keeps in the context.  A batch too large for the kernel argument is copied into a pinned
-// ring slot (the caller may reuse its array at once) and from there to `dev` on the stream; a slot is written again LINE_RING batches
-// later, after its copy has left (normally long ago).  counters / lists / long_list: the tile route (DrawArgs).
+// Host records on their way to the device: a batch too large for a kernel argument is copied into a pinned ring slot (the caller may reuse
+// its array at once) and from there to `dev` on the stream (stage_records); a slot is written again LINE_RING batches later, after its copy
+// has left (normally long ago).
 constexpr uint32_t LINE_RING = 4;
 template <class Rec>
-struct DrawPassState {
+struct Staged {
     Rec* host[LINE_RING] = {}; size_t cap_host[LINE_RING] = {}; hipEvent_t ev[LINE_RING] = {}; uint32_t slot = 0;
     Rec* dev = nullptr; size_t cap_dev = 0;
+    void release() {
+        for (uint32_t k = 0; k < LINE_RING; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (host[k]) (void)hipHostFree(host[k]); }
+        if (dev) (void)hipFree(dev);
+    }
+};
+// What one ordered tile pass (b32_draw_pass.h) keeps in the context: its staged records, and counters / lists / long_list of the tile
+// route (DrawArgs).
+template <class Rec>
+struct DrawPassState : Staged<Rec> {
     uint32_t *counters = nullptr, *lists = nullptr, *long_list = nullptr; size_t cap_tiles = 0; uint32_t parity = 0;
     unsigned long long tile_batches = 0, scan_batches = 0;
     void release() {
-        for (uint32_t k = 0; k < LINE_RING; ++k) { if (ev[k]) (void)hipEventDestroy(ev[k]); if (host[k]) (void)hipHostFree(host[k]); }
-        for (void* p : { (void*)dev, (void*)counters, (void*)lists, (void*)long_list }) if (p) (void)hipFree(p);
+        Staged<Rec>::release();
+        for (void* p : { (void*)counters, (void*)lists, (void*)long_list }) if (p) (void)hipFree(p);
     }
 };
 
@@ -233,15 +242,15 @@ struct b32_ctx {
     unsigned long long wire_tile_frames = 0;
     DrawPassState<B32Line> lines;                                 // b32_draw_lines
     DrawPassState<B32Prim> prims;                                 // b32_draw_prims
-    // b32_draw_world: the items' pinned ring and device copy (of DrawPassState only the staging half is used -- the projected records are
-    // written into prims.dev and drawn as a primitive batch); drawn / dropped / rejected on the device; HIP events around the last
-    // projection kernel enqueued while profiling was on (b32_last_kernel_times "world_project")
-    DrawPassState<B32WorldItem> world;
+    // b32_draw_world: the items' pinned ring and device copy (the projected records are written into prims.dev and drawn as a primitive
+    // batch); drawn / dropped / rejected on the device; HIP events around the last projection kernel enqueued while profiling was on
+    // (b32_last_kernel_times "world_project")
+    Staged<B32WorldItem> world;
     ArmedWords world_counts;
     unsigned long long world_tile_batches = 0, world_scan_batches = 0;
     EventPair world_timer;
     // b32_draw_gizmos: the rows' pinned ring and device copy (as `world`), the rows of the batch being validated, the entry's own counts
-    DrawPassState<GizmoRow> gizmo; std::vector<GizmoRow> gizmo_rows;
+    Staged<GizmoRow> gizmo; std::vector<GizmoRow> gizmo_rows;
     ArmedWords gizmo_counts;
     unsigned long long span_cover_frames = 0;                     // frames whose opaque coverage used exact row intervals (B32_ROUTE_SPAN_COVER)
     // control
@@ -285,7 +294,7 @@ struct b32_ctx {
     // profiling was on (b32_last_kernel_times "pick")
     static constexpr uint32_t PICK_RING = 4;
     ArmedWords pick_words;
-    DrawPassState<PickItem> pick_tab;
+    Staged<PickItem> pick_tab;
     void* pick_res[PICK_RING] = {}; size_t pick_cap_res[PICK_RING] = {}; hipEvent_t pick_done[PICK_RING] = {}, pick_left[PICK_RING] = {}; uint32_t pick_slot = 0;
     void* pick_host = nullptr; size_t pick_cap_host = 0;
     EventPair pick_timer;
@@ -298,10 +307,10 @@ struct b32_ctx {
     // the device copy of a box selection's points.  Results leave through the pick's ring of result buffers.
     ArmedWords room_words, room_points;
     // b32_draw_mesh_overlay (b32_overlay.hip): the projected vertices of the call being enqueued, the bounds' keys (armed between two
-    // calls), the selected list's pinned ring and device copy (the staging half of DrawPassState, as `world`)
+    // calls), the selected list's pinned ring and device copy (as `world`)
     uint4* overlay_tab = nullptr; size_t overlay_cap_tab = 0;     // (16 bytes per vertex: OverlayPoint)
     void* overlay_bounds = nullptr;
-    DrawPassState<uint32_t> overlay_sel; std::vector<uint32_t> overlay_pairs;
+    Staged<uint32_t> overlay_sel; std::vector<uint32_t> overlay_pairs;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only
@@ -353,7 +362,7 @@ static int ensure_plain(b32_ctx* c, T*& p, size_t count) {   // exact-size (re)a
 // Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there to ps.dev
 // on the stream.
 template <class Rec>
-static int stage_records(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32_t n) {
+static int stage_records(b32_ctx* c, Staged<Rec>& ps, const Rec* recs, uint32_t n) {
     const uint32_t k = ps.slot;
     ps.slot = (k + 1) % LINE_RING;
     if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));

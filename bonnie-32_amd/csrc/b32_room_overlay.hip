@@ -13,10 +13,10 @@
 // launch.  A lane reads its record where it lies in the room's table and computes a corner from it with a run-time corner index
 // (room_corner's selectors): no per-lane corner array, no scratch (k_room_mesh's idiom).  The hover record is read by every lane at one
 // address (hover_source 1: the room's device copy, filled behind k_room_hover_resolve on the stream) and the winner rule runs in the lane.
-// Drawn / dropped / rejected: a lane's calls in three 10-bit fields of one word, summed by shuffles in the wave, one LDS add per wave and
-// ONE memory atomic per workgroup and counter (profiles/world_time_per_item_adds.json: per-item adds cost more than the projection).
+// Drawn / dropped / rejected: a lane's calls in three 10-bit fields of one word, through the shared counting tail (b32_item_kernels.h).
 // The records stay on the device: the ordered tile pass of b32_prims.hip reads them where this kernel wrote them.  No new record kind.
 #include "b32_host.h"
+#include "b32_item_kernels.h"
 #include "b32_room_overlay_body.h"
 
 namespace b32 {
@@ -25,9 +25,7 @@ static_assert(sizeof(B32RoomOverlay) == 100 && offsetof(B32RoomOverlay, hover) =
               offsetof(B32RoomOverlay, x0) == 84 && sizeof(RoomOverlayArgs) <= 1024, "B32RoomOverlay layout / kernel argument size");
 
 __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
-    __shared__ uint32_t tally[3];                   // the workgroup's drawn / dropped / rejected
-    if (threadIdx.x < 3u) tally[threadIdx.x] = 0u;
-    __syncthreads();
+    uint32_t* tally = outcome_tally();
     uint32_t wg = blockIdx.x;
     const uint32_t i = threadIdx.x;
     B32Prim* out = a.out;
@@ -93,14 +91,7 @@ __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
         }
     }
     // (every lane of the workgroup arrives here: no early return above)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += (uint32_t)__shfl_xor((int)mine, o, 64);
-    if ((threadIdx.x & 63u) == 0u && mine) {
-#pragma unroll
-        for (uint32_t k = 0; k < 3u; ++k) { const uint32_t c = (mine >> (10u * k)) & 1023u; if (c) atomicAdd(&tally[k], c); }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3u && tally[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+    outcome_count_packed(tally, a.counts, mine);
 }
 
 void launch_room_overlay(hipStream_t s, const RoomOverlayArgs& a) {

@@ -10,19 +10,23 @@
 // f2i32_sat = `as i32`).  Record i is written from item i, so the array order is the reference's call order; an item that draws nothing
 // becomes a circle of radius -1, which the tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of
 // b32_prims.hip reads them where this kernel wrote them.
-#include "b32_device.h"
+#include "b32_item_kernels.h"
 #include <cmath>
 
 namespace b32 {
 
-struct WorldBatch { B32WorldItem r[WORLD_SMALL]; };
-static_assert(sizeof(B32WorldItem) == 40 && sizeof(WorldBatch) + sizeof(WorldArgs) <= 2048, "B32WorldItem layout / kernel argument size");
+struct WorldProject {
+    using Args = WorldArgs; using Row = B32WorldItem;
+    static constexpr uint32_t SMALL = WORLD_SMALL;
+    static __host__ __device__ uint32_t n(const WorldArgs& a) { return a.n; }
+    static __device__ const B32WorldItem* rows(const WorldArgs& a) { return a.items; }
+    static __device__ void item(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live);
+};
+static_assert(sizeof(B32WorldItem) == 40 && sizeof(ItemBatch<WorldProject>) + sizeof(WorldArgs) <= 2048, "B32WorldItem layout / kernel argument size");
 
-// item i of the batch (`live`: i < a.n; the other lanes only take part in the counting)
-__device__ __forceinline__ void world_project(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live) {
-    __shared__ uint32_t tally[3];                               // the workgroup's drawn / dropped / rejected
-    if (threadIdx.x < 3u) tally[threadIdx.x] = 0u;
-    __syncthreads();
+// item i of the batch
+__device__ __forceinline__ void WorldProject::item(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live) {
+    uint32_t* tally = outcome_tally();
     const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
     const bool depth = it.kind >= B32_LINE_3D && it.kind <= B32_LINE_3D_ALPHA;
     float p0[3] = { it.p0[0], it.p0[1], it.p0[2] }, p1[3] = { it.p1[0], it.p1[1], it.p1[2] };
@@ -68,38 +72,14 @@ __device__ __forceinline__ void world_project(const WorldArgs& a, const B32World
         }
     }
     if (live) a.out[i] = o;
-    // One add per wave into LDS, one per workgroup and counter into memory: 100 000 single adds to one address take a millisecond.
-    // (integer sums: the totals do not depend on the order of the adds)
-#pragma unroll
-    for (uint32_t k = 0; k < 3u; ++k) {
-        const unsigned long long m = __ballot(live && which == k);
-        if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&tally[k], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    if (threadIdx.x < 3u && tally[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (unsigned long long)tally[threadIdx.x]);
+    outcome_count(tally, a.counts, live ? which : 3u);
 }
 
-// a.n <= WORLD_SMALL items out of the kernel argument: one workgroup
-__global__ __launch_bounds__(256) void k_world_project_small(WorldArgs a, WorldBatch batch) {
-    const uint32_t i = threadIdx.x;
-    const bool live = i < a.n;
-    world_project(a, live ? batch.r[i] : B32WorldItem{}, i, live);
-}
-__global__ __launch_bounds__(256) void k_world_project(WorldArgs a) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < a.n;
-    world_project(a, live ? a.items[i] : B32WorldItem{}, i, live);
-}
+__global__ __launch_bounds__(256) void k_world_project_small(WorldArgs a, ItemBatch<WorldProject> batch) { item_small<WorldProject>(a, batch); }
+__global__ __launch_bounds__(256) void k_world_project(WorldArgs a) { item_large<WorldProject>(a); }
 
 void launch_world_project(hipStream_t s, const WorldArgs& a, const B32WorldItem* small) {
-    if (!a.n) return;
-    if (small) {
-        WorldBatch batch{};
-        for (uint32_t i = 0; i < a.n && i < WORLD_SMALL; ++i) batch.r[i] = small[i];
-        hipLaunchKernelGGL(k_world_project_small, dim3(1), dim3(256), 0, s, a, batch);
-        return;
-    }
-    hipLaunchKernelGGL(k_world_project, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a);
+    launch_items<WorldProject>(s, k_world_project_small, k_world_project, a, small);
 }
 
 }  // namespace b32
