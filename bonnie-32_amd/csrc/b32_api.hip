@@ -628,8 +628,7 @@ int b32_draw_lines(b32_ctx* c, const B32Line* lines, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) {                                      // the whole batch, before anything is drawn
         const B32Line& l = lines[i];
         if (l.kind > B32_LINE_3D_ALPHA) return B32_E_ARG;
-        const long long adx = std::llabs((long long)l.x1 - l.x0), ady = std::llabs((long long)l.y1 - l.y0);
-        if (adx >= (1ll << 30) || ady >= (1ll << 30)) return B32_E_UNSUPPORTED;     // 2 * err overflows i32 (render.rs:735, 800)
+        if (prim_wide(l.x0, l.x1) || prim_wide(l.y0, l.y1)) return B32_E_UNSUPPORTED;   // 2 * err overflows i32 (render.rs:735, 800)
     }
     return draw_pass(c, c->lines, lines, n, LINE_SMALL, B32_ROUTE_LINE_TILES);
 }
@@ -641,11 +640,9 @@ int b32_draw_prims(b32_ctx* c, const B32Prim* prims, uint32_t n) {
         if (p.kind > B32_PRIM_FILLED_RECT || (p.kind == B32_PRIM_LINE_BLENDED && p.mode > B32_BLEND_ERASE)) return B32_E_ARG;
         if (p.kind == B32_PRIM_CIRCLE || p.kind == B32_PRIM_CIRCLE_ALPHA) {
             // r * r, dx * dx + dy * dy and cy +- radius stay inside i32 (render.rs:632-637)
-            if (std::llabs((long long)p.size) > 32767 || std::llabs((long long)p.x0) >= (1ll << 30) || std::llabs((long long)p.y0) >= (1ll << 30))
-                return B32_E_UNSUPPORTED;
+            if (std::llabs((long long)p.size) > 32767 || prim_big(p.x0) || prim_big(p.y0)) return B32_E_UNSUPPORTED;
         } else if (p.kind != B32_PRIM_FILLED_RECT) {
-            const long long adx = std::llabs((long long)p.x1 - p.x0), ady = std::llabs((long long)p.y1 - p.y0);
-            if (adx >= (1ll << 30) || ady >= (1ll << 30)) return B32_E_UNSUPPORTED;     // 2 * err overflows i32 (render.rs:735, 800)
+            if (prim_wide(p.x0, p.x1) || prim_wide(p.y0, p.y1)) return B32_E_UNSUPPORTED;   // 2 * err overflows i32 (render.rs:735, 800)
         }
     }
     return draw_pass(c, c->prims, prims, n, PRIM_SMALL, B32_ROUTE_PRIM_TILES);

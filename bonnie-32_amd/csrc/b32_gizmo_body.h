@@ -5,30 +5,15 @@
 // reference's order; the text also compiles for the host (B32_HD, b32_world_point.h), where tests/test_gizmos.py runs it against a
 // literal restatement, built with and without -ffp-contract=off.
 #pragma once
-#if defined(__HIPCC__)
-#include "b32_device.h"
-#else
+#if !defined(__HIPCC__)
 #include <math.h>
-#include "b32_world_point.h"
 #endif
+#include "b32_prim_record.h"
 
 namespace b32 {
 
 constexpr uint32_t PRIM_TRIANGLE = 11u;             // the library-internal record kind of a filled triangle: (x0, y0), (x1, y1) and a third
                                                     // point whose x and y are the bit patterns of z0 and z1.  No entry takes it from the host.
-constexpr long long GIZMO_LIM = 1ll << 30;          // what the reference's i32 arithmetic cannot carry (extents, x0 + ox, y2 - y0, x2 - x0)
-
-// Rust's `f as i32`: NaN -> 0, saturating, truncation toward zero
-B32_HD int32_t gizmo_i32(float f) {
-#if defined(__HIPCC__)
-    return f2i32_sat(f);
-#else
-    if (f != f) return 0;
-    if (f >= 2147483648.0f) return 2147483647;
-    if (f <= -2147483648.0f) return -2147483647 - 1;
-    return (int32_t)f;
-#endif
-}
 B32_HD float gizmo_sqrt(float x) {
 #if defined(__HIPCC__)
     return __builtin_sqrtf(x);
@@ -36,8 +21,6 @@ B32_HD float gizmo_sqrt(float x) {
     return sqrtf(x);
 #endif
 }
-B32_HD float gizmo_bits_f32(int32_t v) { float f; __builtin_memcpy(&f, &v, 4); return f; }
-B32_HD int32_t gizmo_f32_bits(float f) { int32_t v; __builtin_memcpy(&v, &f, 4); return v; }
 
 // records an item becomes: `size` parallel lines for a thick line of thickness > 1, else one (a no-op where nothing is drawn)
 B32_HD uint32_t gizmo_record_count(uint32_t kind, int32_t size) { return (kind == B32_GIZMO_THICK_LINE_DEPTH && size > 1) ? (uint32_t)size : 1u; }
@@ -89,8 +72,8 @@ B32_HD bool gizmo_thick_setup(int32_t x0, int32_t y0, int32_t x1, int32_t y1, in
 }
 B32_HD void gizmo_thick_offset(float px, float py, float half, int32_t i, int32_t& ox, int32_t& oy) {
     const float offset = (float)i - half + 0.5f;
-    ox = gizmo_i32(px * offset / half);
-    oy = gizmo_i32(py * offset / half);
+    ox = as_i32(px * offset / half);
+    oy = as_i32(py * offset / half);
 }
 
 // the editor's project_vertex, viewport_3d.rs:6239-6245: perspective_transform (math.rs:103-109), `cam.z < 0.1` -> None, project
@@ -105,7 +88,7 @@ B32_HD bool gizmo_project_vertex(const ViewBlock& a, const float* p, int32_t& x,
         sx = (cam_x * 4.0f) / denom * a.vs + a.half_w;
         sy = (cam_y * 4.0f) / denom * a.vs + a.half_h;
     }
-    x = gizmo_i32(sx); y = gizmo_i32(sy);
+    x = as_i32(sx); y = as_i32(sy);
     return true;
 }
 
@@ -128,63 +111,33 @@ B32_HD bool gizmo_tri_row(int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_
     float ax = (float)x0 + (float)(x2 - x0) * alpha;
     float bx = second_half ? (float)x1 + (float)(x2 - x1) * beta : (float)x0 + (float)(x1 - x0) * beta;
     if (ax > bx) { const float t = ax; ax = bx; bx = t; }
-    xa = gizmo_i32(ax); xb = gizmo_i32(bx);
+    xa = as_i32(ax); xb = as_i32(bx);
     return true;
 }
 
-B32_HD B32Prim gizmo_noop() {                      // draws nothing (PrimPass::bounds)
-    B32Prim o{};
-    o.kind = B32_PRIM_CIRCLE; o.size = -1;
-    return o;
-}
-B32_HD float gizmo_depth(float z) { return z != z ? gizmo_bits_f32(0x7FC00000) : z; }   // (one quiet NaN, as b32_draw_world's records)
-
 // One item into its gizmo_record_count(kind, size) records at `out`, in the reference's call order; returns 0 drawn, 1 dropped (the
-// reference draws nothing), 2 rejected (the reference's i32 arithmetic cannot carry it).
+// reference draws nothing), 2 rejected (the reference's i32 arithmetic cannot carry it: prim_big, prim_wide).  The records carry the
+// item's colour and alpha 0.
 B32_HD uint32_t gizmo_item(const ViewBlock& a, const B32GizmoItem& it, B32Prim* out) {
     const uint32_t n_rec = gizmo_record_count(it.kind, it.size);
-    for (uint32_t k = 0; k < n_rec; ++k) out[k] = gizmo_noop();
-    B32Prim base{};
-    base.r = it.r; base.g = it.g; base.b = it.b; base.blend = it.blend;
-    auto big = [](int32_t v) { return (long long)v >= GIZMO_LIM || (long long)v <= -GIZMO_LIM; };
-    auto wide = [](int32_t u, int32_t v) { const long long d = (long long)v - u; return d >= GIZMO_LIM || d <= -GIZMO_LIM; };
+    for (uint32_t k = 0; k < n_rec; ++k) out[k] = prim_noop();
+    const PrimColor col = { it.r, it.g, it.b, it.blend };
 
     if (it.kind <= B32_GIZMO_THICK_LINE_DEPTH) {
         float p0[3] = { it.p0[0], it.p0[1], it.p0[2] }, p1[3] = { it.p1[0], it.p1[1], it.p1[2] };
-        {   // the near-plane clip, viewport_3d.rs:5794-5816 and :5725-5747 (draw.rs:19-42 verbatim)
-            const float rel0[3] = { p0[0] - a.pos[0], p0[1] - a.pos[1], p0[2] - a.pos[2] };
-            const float rel1[3] = { p1[0] - a.pos[0], p1[1] - a.pos[1], p1[2] - a.pos[2] };
-            const float z0 = world_dot(rel0, a.bz), z1 = world_dot(rel1, a.bz);
-            if (z0 <= WORLD_NEAR && z1 <= WORLD_NEAR) return 1u;
-            if (z0 <= WORLD_NEAR || z1 <= WORLD_NEAR) {
-                const float t = (WORLD_NEAR - z0) / (z1 - z0);
-                float q[3];
-                for (int k = 0; k < 3; ++k) q[k] = p0[k] + (p1[k] - p0[k]) * t;
-                for (int k = 0; k < 3; ++k) { if (z0 <= WORLD_NEAR) p0[k] = q[k]; else p1[k] = q[k]; }
-            }
-        }
+        if (!world_near_clip(a, p0, p1)) return 1u;     // viewport_3d.rs:5794-5816 and :5725-5747
         float sx0, sy0, cz0, sx1, sy1, cz1;
         if (!world_point(a, p0, false, sx0, sy0, cz0) || !world_point(a, p1, false, sx1, sy1, cz1)) return 1u;
-        if (it.kind == B32_GIZMO_LINE) {
-            if (!gizmo_clip_line_to_rect(sx0, sy0, sx1, sy1, 0.0f, 0.0f, a.half_w * 2.0f, a.half_h * 2.0f)) return 1u;
-            B32Prim o = base;
-            o.kind = B32_LINE_2D;
-            o.x0 = gizmo_i32(sx0); o.y0 = gizmo_i32(sy0); o.x1 = gizmo_i32(sx1); o.y1 = gizmo_i32(sy1);
-            if (wide(o.x0, o.x1) || wide(o.y0, o.y1)) return 2u;
+        const bool flat = it.kind == B32_GIZMO_LINE;
+        if (flat && !gizmo_clip_line_to_rect(sx0, sy0, sx1, sy1, 0.0f, 0.0f, a.half_w * 2.0f, a.half_h * 2.0f)) return 1u;
+        const int32_t x0 = as_i32(sx0), y0 = as_i32(sy0), x1 = as_i32(sx1), y1 = as_i32(sy1);
+        if (prim_wide(x0, x1) || prim_wide(y0, y1)) return 2u;
+        B32Prim o = prim_line(flat ? B32_LINE_2D : B32_LINE_3D_OVERLAY, x0, y0, x1, y1, cz0, cz1, col, 0u);
+        if (n_rec == 1u) {                          // draw_3d_line, draw_3d_line_depth; thickness <= 1
             out[0] = o;
             return 0u;
         }
-        const int32_t x0 = gizmo_i32(sx0), y0 = gizmo_i32(sy0), x1 = gizmo_i32(sx1), y1 = gizmo_i32(sy1);
-        if (wide(x0, x1) || wide(y0, y1)) return 2u;
-        B32Prim o = base;
-        o.kind = B32_LINE_3D_OVERLAY;
-        o.z0 = gizmo_depth(cz0); o.z1 = gizmo_depth(cz1);
-        if (n_rec == 1u) {                          // draw_3d_line_depth; thickness <= 1
-            o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
-            out[0] = o;
-            return 0u;
-        }
-        if (big(x0) || big(y0) || big(x1) || big(y1)) return 2u;
+        if (prim_big(x0) || prim_big(y0) || prim_big(x1) || prim_big(y1)) return 2u;
         float px, py, half;
         if (!gizmo_thick_setup(x0, y0, x1, y1, it.size, px, py, half)) return 1u;
         for (int32_t i = 0; i < it.size; ++i) {
@@ -198,11 +151,9 @@ B32_HD uint32_t gizmo_item(const ViewBlock& a, const B32GizmoItem& it, B32Prim* 
     if (it.kind == B32_GIZMO_POINT) {               // draw_3d_point, viewport_3d.rs:5958-5976
         float sx, sy, cz;
         if (!world_point(a, it.p0, false, sx, sy, cz)) return 1u;
-        B32Prim o = base;
-        o.kind = B32_PRIM_CIRCLE; o.size = it.size;
-        o.x0 = gizmo_i32(sx); o.y0 = gizmo_i32(sy);
-        if (big(o.x0) || big(o.y0)) return 2u;
-        out[0] = o;
+        const int32_t x = as_i32(sx), y = as_i32(sy);
+        if (prim_big(x) || prim_big(y)) return 2u;
+        out[0] = prim_circle(B32_PRIM_CIRCLE, x, y, it.size, col, 0u);
         return 0u;
     }
     // the triangles: three projections, any None -> nothing
@@ -214,15 +165,13 @@ B32_HD uint32_t gizmo_item(const ViewBlock& a, const B32GizmoItem& it, B32Prim* 
         } else {                                    // modeler/viewport.rs:4592-4607
             float sx, sy, cz;
             if (!world_point(a, p[k], a.has_ortho != 0u, sx, sy, cz)) return 1u;
-            x[k] = gizmo_i32(sx); y[k] = gizmo_i32(sy);
+            x[k] = as_i32(sx); y[k] = as_i32(sy);
         }
     }
-    for (int k = 0; k < 3; ++k) if (big(x[k]) || big(y[k])) return 2u;
+    for (int k = 0; k < 3; ++k) if (prim_big(x[k]) || prim_big(y[k])) return 2u;
     if (y[0] == y[1] && y[1] == y[2]) return 1u;    // y2 == y0 after the sort
-    B32Prim o = base;
-    o.kind = (uint8_t)PRIM_TRIANGLE;
-    o.x0 = x[0]; o.y0 = y[0]; o.x1 = x[1]; o.y1 = y[1];
-    o.z0 = gizmo_bits_f32(x[2]); o.z1 = gizmo_bits_f32(y[2]);
+    B32Prim o = prim_line(PRIM_TRIANGLE, x[0], y[0], x[1], y[1], 0.0f, 0.0f, col, 0u);
+    o.z0 = bits_f32((uint32_t)x[2]); o.z1 = bits_f32((uint32_t)y[2]);    // the third point
     out[0] = o;
     return 0u;
 }

@@ -2,8 +2,10 @@
 // draw_selected_object_brackets (:1782-1884), draw_mesh_selection_overlays (:1890-2105) and draw_box_selection_preview (:2108-2247).
 // k_overlay_points and k_overlay_emit (b32_overlay.hip) turn (slot vertices, topology, hover result, selection, rectangle) into B32Prim
 // records with these functions.  Every expression is a separately rounded f32 operation in the reference's order, `as i32` saturates
-// and `as i32 + 1` wraps (a release build); the text also compiles for the host (B32_HD, b32_world_point.h), where
-// tests/test_mesh_overlay.py runs it against a literal restatement, built with and without -ffp-contract=off.
+// and `as i32 + 1` wraps (a release build).  Not restated here: the casts, f32::min, the 2^30 limit, the no-op and the line and circle
+// records are b32_prim_record.h's -- that a refused call is the no-op and nothing else is this file's.  The text also compiles for the
+// host (B32_HD, b32_world_point.h), where tests/test_mesh_overlay.py runs it against a literal restatement, built with and without
+// -ffp-contract=off.
 //
 // Where a record lies is a function of the topology, nv, the B32MeshOverlay and the selected list alone (overlay_layout): a call the
 // reference does not make leaves the no-op record (a circle of radius -1) in its slot.
@@ -14,17 +16,11 @@
 //   SELECTED  n_selected | 4 * n_selected | sum of 2 * n + 1 over the listed polygons < np
 //   PREVIEW   nv | 2 * ne (first half-edge of every edge, in loop order) | nh + np (polygon p at poly_start[p] + p)
 #pragma once
-#if defined(__HIPCC__)
-#include "b32_device.h"
-#else
-#include <math.h>
-#include "b32_world_point.h"
-#endif
+#include "b32_prim_record.h"
 
 namespace b32 {
 
 constexpr uint32_t OVERLAY_NONE = 0xFFFFFFFFu;
-constexpr long long OVERLAY_LIM = 1ll << 30;        // what the reference's i32 arithmetic cannot carry (b32_draw_prims's extent / centre rules)
 constexpr uint32_t OVERLAY_ALL = 63u;               // every B32_OVERLAY_* bit
 enum : uint32_t { OVERLAY_POLY_HOVER = 0u, OVERLAY_POLY_SELECTED = 1u, OVERLAY_POLY_PREVIEW = 2u };
 
@@ -36,32 +32,16 @@ struct OverlayBounds { uint32_t mn[3], mx[3]; };
 constexpr uint32_t OVERLAY_KEY_MIN0 = 0xFF7FFFFFu;  // overlay_key(f32::MAX): where the minima start
 constexpr uint32_t OVERLAY_KEY_MAX0 = 0x00800000u;  // overlay_key(f32::MIN): where the maxima start
 
-struct OverlayColor { uint8_t r, g, b; };
-constexpr OverlayColor OVERLAY_BRACKET_COLOR = { 0, 200, 230 }, OVERLAY_EDGE_COLOR = { 80, 80, 80 }, OVERLAY_DOT_COLOR = { 40, 40, 50 },
-                       OVERLAY_HOVER_COLOR = { 255, 200, 150 }, OVERLAY_SELECT_COLOR = { 100, 180, 255 }, OVERLAY_PREVIEW_COLOR = { 255, 220, 100 };
-
-// Rust's `f as i32`: NaN -> 0, saturating, truncation toward zero
-B32_HD int32_t overlay_i32(float f) {
-#if defined(__HIPCC__)
-    return f2i32_sat(f);
-#else
-    if (f != f) return 0;
-    if (f >= 2147483648.0f) return 2147483647;
-    if (f <= -2147483648.0f) return -2147483647 - 1;
-    return (int32_t)f;
-#endif
-}
-B32_HD int32_t overlay_inc(int32_t v) { return (int32_t)((uint32_t)v + 1u); }          // `+ 1` of a release build: wraps
-B32_HD float overlay_bits_f32(uint32_t v) { float f; __builtin_memcpy(&f, &v, 4); return f; }
-B32_HD uint32_t overlay_f32_bits(float f) { uint32_t v; __builtin_memcpy(&v, &f, 4); return v; }
+constexpr PrimColor OVERLAY_BRACKET_COLOR = { 0, 200, 230 }, OVERLAY_EDGE_COLOR = { 80, 80, 80 }, OVERLAY_DOT_COLOR = { 40, 40, 50 },
+                    OVERLAY_HOVER_COLOR = { 255, 200, 150 }, OVERLAY_SELECT_COLOR = { 100, 180, 255 }, OVERLAY_PREVIEW_COLOR = { 255, 220, 100 };
 
 // total order of the non-NaN f32 as u32, both zeros on one value (the hover's pick_orderable), and back (a zero comes back as +0.0)
 B32_HD uint32_t overlay_key(float d) {
-    uint32_t u = overlay_f32_bits(d);
+    uint32_t u = f32_bits(d);
     if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-B32_HD float overlay_unkey(uint32_t k) { return overlay_bits_f32((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+B32_HD float overlay_unkey(uint32_t k) { return bits_f32((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 // one position into the bounds: f32::min / f32::max ignore a NaN
 B32_HD void overlay_bounds_take(OverlayBounds& b, const float* p) {
     for (int c = 0; c < 3; ++c) {
@@ -74,47 +54,24 @@ B32_HD void overlay_bounds_take(OverlayBounds& b, const float* p) {
 constexpr OverlayBounds overlay_bounds_start() {   // (constexpr: host and device)
     return OverlayBounds{ { OVERLAY_KEY_MIN0, OVERLAY_KEY_MIN0, OVERLAY_KEY_MIN0 }, { OVERLAY_KEY_MAX0, OVERLAY_KEY_MAX0, OVERLAY_KEY_MAX0 } };
 }
-B32_HD float overlay_min(float a, float b) {        // f32::min
-    if (a != a) return b;
-    if (b != b) return a;
-    return b < a ? b : a;
-}
 
-B32_HD B32Prim overlay_noop() {                     // draws nothing (PrimPass::bounds)
-    B32Prim o{};
-    o.kind = B32_PRIM_CIRCLE; o.size = -1;
-    return o;
-}
-B32_HD float overlay_depth(float z) { return z != z ? overlay_bits_f32(0x7FC00000u) : z; }   // (one quiet NaN, as b32_draw_world's records)
-
-// fb.draw_line / draw_line_3d / draw_line_3d_alpha with cast ends; a no-op when an extent reaches 2^30 (k_world_project's rule)
-B32_HD B32Prim overlay_line(uint32_t kind, int32_t x0, int32_t y0, int32_t x1, int32_t y1, float z0, float z1, OverlayColor c, uint32_t alpha) {
-    const long long dx = (long long)x1 - x0, dy = (long long)y1 - y0;
-    if (dx >= OVERLAY_LIM || dx <= -OVERLAY_LIM || dy >= OVERLAY_LIM || dy <= -OVERLAY_LIM) return overlay_noop();
-    B32Prim o{};
-    const bool depth = kind >= B32_LINE_3D && kind <= B32_LINE_3D_ALPHA;
-    o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
-    o.z0 = depth ? overlay_depth(z0) : 0.0f; o.z1 = depth ? overlay_depth(z1) : 0.0f;
-    o.r = c.r; o.g = c.g; o.b = c.b; o.blend = B32_BLEND_OPAQUE;                         // RasterColor::new
-    o.kind = (uint8_t)kind; o.alpha = (uint8_t)alpha;
-    return o;
+// fb.draw_line / draw_line_3d / draw_line_3d_alpha with cast ends; the no-op, and not a word, when an extent is too wide
+B32_HD B32Prim overlay_line(uint32_t kind, int32_t x0, int32_t y0, int32_t x1, int32_t y1, float z0, float z1, PrimColor c, uint32_t alpha) {
+    if (prim_wide(x0, x1) || prim_wide(y0, y1)) return prim_noop();
+    return prim_line(kind, x0, y0, x1, y1, z0, z1, c, alpha);
 }
 // the 2-D line between two projected vertices, its ends moved by (ox, oy) in {0, 1} after the cast
-B32_HD B32Prim overlay_seg(const OverlayPoint& e0, const OverlayPoint& e1, bool ox, bool oy, OverlayColor c) {
-    int32_t x0 = overlay_i32(e0.sx), y0 = overlay_i32(e0.sy), x1 = overlay_i32(e1.sx), y1 = overlay_i32(e1.sy);
-    if (ox) { x0 = overlay_inc(x0); x1 = overlay_inc(x1); }
-    if (oy) { y0 = overlay_inc(y0); y1 = overlay_inc(y1); }
+B32_HD B32Prim overlay_seg(const OverlayPoint& e0, const OverlayPoint& e1, bool ox, bool oy, PrimColor c) {
+    int32_t x0 = as_i32(e0.sx), y0 = as_i32(e0.sy), x1 = as_i32(e1.sx), y1 = as_i32(e1.sy);
+    if (ox) { x0 = inc_wrap(x0); x1 = inc_wrap(x1); }
+    if (oy) { y0 = inc_wrap(y0); y1 = inc_wrap(y1); }
     return overlay_line(B32_LINE_2D, x0, y0, x1, y1, 0.0f, 0.0f, c, 255u);
 }
-// fb.draw_circle[_alpha] at a projected point; a no-op when the centre reaches 2^30
-B32_HD B32Prim overlay_circle(const OverlayPoint& e, int32_t radius, OverlayColor c, uint32_t kind, uint32_t alpha) {
-    const int32_t x = overlay_i32(e.sx), y = overlay_i32(e.sy);
-    if ((long long)x >= OVERLAY_LIM || (long long)x <= -OVERLAY_LIM || (long long)y >= OVERLAY_LIM || (long long)y <= -OVERLAY_LIM) return overlay_noop();
-    B32Prim o{};
-    o.x0 = x; o.y0 = y; o.size = radius;
-    o.r = c.r; o.g = c.g; o.b = c.b; o.blend = B32_BLEND_OPAQUE;
-    o.kind = (uint8_t)kind; o.alpha = (uint8_t)alpha;
-    return o;
+// fb.draw_circle[_alpha] at a projected point; the no-op when the centre is too big
+B32_HD B32Prim overlay_circle(const OverlayPoint& e, int32_t radius, PrimColor c, uint32_t kind, uint32_t alpha) {
+    const int32_t x = as_i32(e.sx), y = as_i32(e.sy);
+    if (prim_big(x) || prim_big(y)) return prim_noop();
+    return prim_circle(kind, x, y, radius, c, alpha);
 }
 // sx >= fb_x0 && sx <= fb_x1 && sy >= fb_y0 && sy <= fb_y1 (a NaN gives false); rect = x0, y0, x1, y1
 B32_HD bool overlay_inside(float x, float y, const float* rect) { return x >= rect[0] && x <= rect[2] && y >= rect[1] && y <= rect[3]; }
@@ -128,22 +85,22 @@ B32_HD OverlayPoint overlay_point(const ViewBlock& a, const float* p) {
 // ---- per element: what the lanes of k_overlay_points / k_overlay_emit write
 // :1939-1954
 B32_HD B32Prim overlay_dot(const OverlayPoint& e) {
-    return e.some ? overlay_circle(e, 3, OVERLAY_DOT_COLOR, B32_PRIM_CIRCLE_ALPHA, 140u) : overlay_noop();
+    return e.some ? overlay_circle(e, 3, OVERLAY_DOT_COLOR, B32_PRIM_CIRCLE_ALPHA, 140u) : prim_noop();
 }
 // :2160-2178
 B32_HD B32Prim overlay_preview_vertex(const OverlayPoint& e, const float* rect) {
-    return (e.some && overlay_inside(e.sx, e.sy, rect)) ? overlay_circle(e, 6, OVERLAY_PREVIEW_COLOR, B32_PRIM_CIRCLE, 255u) : overlay_noop();
+    return (e.some && overlay_inside(e.sx, e.sy, rect)) ? overlay_circle(e, 6, OVERLAY_PREVIEW_COLOR, B32_PRIM_CIRCLE, 255u) : prim_noop();
 }
 // :1924-1935, one half-edge
 B32_HD B32Prim overlay_edge(uint32_t v0, uint32_t v1, uint32_t nv, const OverlayPoint* tab) {
-    if (v0 >= nv || v1 >= nv) return overlay_noop();
+    if (v0 >= nv || v1 >= nv) return prim_noop();
     const OverlayPoint e0 = tab[v0], e1 = tab[v1];
-    if (!e0.some || !e1.some) return overlay_noop();
-    return overlay_line(B32_LINE_3D_ALPHA, overlay_i32(e0.sx), overlay_i32(e0.sy), overlay_i32(e1.sx), overlay_i32(e1.sy), e0.z, e1.z, OVERLAY_EDGE_COLOR, 191u);
+    if (!e0.some || !e1.some) return prim_noop();
+    return overlay_line(B32_LINE_3D_ALPHA, as_i32(e0.sx), as_i32(e0.sy), as_i32(e1.sx), as_i32(e1.sy), e0.z, e1.z, OVERLAY_EDGE_COLOR, 191u);
 }
 // :2183-2205, the first half-edge of its normalised edge: two records
 B32_HD void overlay_preview_edge(uint32_t v0, uint32_t v1, uint32_t nv, const OverlayPoint* tab, const float* rect, B32Prim* out) {
-    out[0] = overlay_noop(); out[1] = overlay_noop();
+    out[0] = prim_noop(); out[1] = prim_noop();
     if (v0 >= nv || v1 >= nv) return;
     const OverlayPoint e0 = tab[v0], e1 = tab[v1];
     if (!e0.some || !e1.some) return;
@@ -154,12 +111,12 @@ B32_HD void overlay_preview_edge(uint32_t v0, uint32_t v1, uint32_t nv, const Ov
 }
 // :1960-1975, one record
 B32_HD B32Prim overlay_hover_vertex(uint32_t v, uint32_t nv, const OverlayPoint* tab) {
-    if (v >= nv || !tab[v].some) return overlay_noop();
+    if (v >= nv || !tab[v].some) return prim_noop();
     return overlay_circle(tab[v], 5, OVERLAY_HOVER_COLOR, B32_PRIM_CIRCLE, 255u);
 }
 // :1980-1992, three records
 B32_HD void overlay_hover_edge(uint32_t v0, uint32_t v1, uint32_t nv, const OverlayPoint* tab, B32Prim* out) {
-    out[0] = overlay_noop(); out[1] = overlay_noop(); out[2] = overlay_noop();
+    out[0] = prim_noop(); out[1] = prim_noop(); out[2] = prim_noop();
     if (v0 >= nv || v1 >= nv) return;
     const OverlayPoint e0 = tab[v0], e1 = tab[v1];
     if (!e0.some || !e1.some) return;
@@ -169,12 +126,12 @@ B32_HD void overlay_hover_edge(uint32_t v0, uint32_t v1, uint32_t nv, const Over
 }
 // :2026-2041, one record
 B32_HD B32Prim overlay_selected_vertex(uint32_t v, uint32_t nv, const OverlayPoint* tab) {
-    if (v >= nv || !tab[v].some) return overlay_noop();
+    if (v >= nv || !tab[v].some) return prim_noop();
     return overlay_circle(tab[v], 4, OVERLAY_SELECT_COLOR, B32_PRIM_CIRCLE, 255u);
 }
 // :2048-2061, four records; the pair as given
 B32_HD void overlay_selected_edge(uint32_t v0, uint32_t v1, uint32_t nv, const OverlayPoint* tab, B32Prim* out) {
-    for (int k = 0; k < 4; ++k) out[k] = overlay_noop();
+    for (int k = 0; k < 4; ++k) out[k] = prim_noop();
     if (v0 >= nv || v1 >= nv) return;
     const OverlayPoint e0 = tab[v0], e1 = tab[v1];
     if (!e0.some || !e1.some) return;
@@ -195,7 +152,7 @@ constexpr uint32_t overlay_polygon_slots(uint32_t mode, uint32_t cnt) {
 B32_HD void overlay_polygon(const ViewBlock& a, uint32_t mode, const uint32_t* pv, uint32_t cnt, const float* pos, uint32_t stride, uint32_t nv,
                             const OverlayPoint* tab, const float* rect, B32Prim* out) {
     const uint32_t slots = overlay_polygon_slots(mode, cnt);
-    const OverlayColor col = mode == OVERLAY_POLY_HOVER ? OVERLAY_HOVER_COLOR : (mode == OVERLAY_POLY_SELECTED ? OVERLAY_SELECT_COLOR : OVERLAY_PREVIEW_COLOR);
+    const PrimColor col = mode == OVERLAY_POLY_HOVER ? OVERLAY_HOVER_COLOR : (mode == OVERLAY_POLY_SELECTED ? OVERLAY_SELECT_COLOR : OVERLAY_PREVIEW_COLOR);
     uint32_t k = 0u, n = 0u;
     bool go = true;
     float acc[3] = { 0.0f, 0.0f, 0.0f };             // fold(Vec3::ZERO, |acc, p| acc + p) over get_pos(vi) != None
@@ -251,7 +208,7 @@ B32_HD void overlay_polygon(const ViewBlock& a, uint32_t mode, const uint32_t* p
     } else {
         k = 0u;
     }
-    for (; k < slots; ++k) out[k] = overlay_noop();
+    for (; k < slots; ++k) out[k] = prim_noop();
 }
 
 // :1821-1883, bracket k (corner k / 3, direction k % 3) from the finished bounds
@@ -259,7 +216,7 @@ B32_HD B32Prim overlay_bracket(const ViewBlock& a, const OverlayBounds& b, uint3
     float mn[3], mx[3];
     for (int c = 0; c < 3; ++c) { mn[c] = overlay_unkey(b.mn[c]) - 4.0f; mx[c] = overlay_unkey(b.mx[c]) + 4.0f; }
     const float size[3] = { mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2] };
-    const float bracket_len = overlay_min(overlay_min(size[0], size[1]), size[2]) * 0.25f;
+    const float bracket_len = f32_min(f32_min(size[0], size[1]), size[2]) * 0.25f;
     const uint32_t ci = k / 3u, di = k % 3u;
     const bool hi[3] = { ci == 1u || ci == 2u || ci == 5u || ci == 6u, ci >= 4u, ci == 2u || ci == 3u || ci == 6u || ci == 7u };
     float corner[3], end[3];
@@ -269,8 +226,8 @@ B32_HD B32Prim overlay_bracket(const ViewBlock& a, const OverlayBounds& b, uint3
         end[c] = corner[c] + dir * bracket_len;
     }
     const OverlayPoint e0 = overlay_point(a, corner), e1 = overlay_point(a, end);
-    if (!e0.some || !e1.some) return overlay_noop();
-    return overlay_line(B32_LINE_3D, overlay_i32(e0.sx), overlay_i32(e0.sy), overlay_i32(e1.sx), overlay_i32(e1.sy), e0.z, e1.z, OVERLAY_BRACKET_COLOR, 255u);
+    if (!e0.some || !e1.some) return prim_noop();
+    return overlay_line(B32_LINE_3D, as_i32(e0.sx), as_i32(e0.sy), as_i32(e1.sx), as_i32(e1.sy), e0.z, e1.z, OVERLAY_BRACKET_COLOR, 255u);
 }
 
 // ---- host: the struct's own argument rules (0: fine, else B32_E_ARG) ...

@@ -159,7 +159,7 @@ struct GizmoPass : PrimPass {
     // (64), so beyond 2^24 a span can leave the integer box by up to 192 columns: the margin is ((largest |x|) >> 22) + 2.  Rows are exact.
     __device__ static __forceinline__ bool bounds(const B32Prim& p, long long& x0, long long& x1, long long& y0, long long& y1) {
         if (p.kind != PRIM_TRIANGLE) return PrimPass::bounds(p, x0, x1, y0, y1);
-        const int x2 = gizmo_f32_bits(p.z0), y2 = gizmo_f32_bits(p.z1);
+        const int x2 = (int)f32_bits(p.z0), y2 = (int)f32_bits(p.z1);
         x0 = min(min(p.x0, p.x1), x2); x1 = max(max(p.x0, p.x1), x2); y0 = min(min(p.y0, p.y1), y2); y1 = max(max(p.y0, p.y1), y2);
         const long long pad = (max(llabs(x0), llabs(x1)) >> 22) + 2;
         x0 -= pad; x1 += pad;
@@ -175,7 +175,7 @@ struct GizmoPass : PrimPass {
         A.kind = p.kind;
         uint32_t abyte = p.blend != B32_BLEND_ERASE ? 255u : 0u;                      // Color::to_bytes, types.rs:829-832
         if (p.kind == PRIM_TRIANGLE) {                                                  // viewport_3d.rs:6302-6314
-            int x[3] = { p.x0, p.x1, gizmo_f32_bits(p.z0) }, y[3] = { p.y0, p.y1, gizmo_f32_bits(p.z1) };
+            int x[3] = { p.x0, p.x1, (int)f32_bits(p.z0) }, y[3] = { p.y0, p.y1, (int)f32_bits(p.z1) };
             gizmo_tri_sort(x, y);
             A.v[0] = x[0]; A.v[1] = y[0]; A.v[2] = x[1]; A.v[3] = y[1]; A.v[4] = x[2]; A.v[5] = y[2];
             A.bx0 = t.cx0; A.bx1 = t.cx1; A.by0 = max(y[0], t.cy0); A.by1 = min(y[2], t.cy1);

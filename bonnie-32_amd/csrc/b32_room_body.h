@@ -7,11 +7,9 @@
 #pragma once
 #if defined(__HIPCC__)
 #include "b32_device.h"
-#define B32_ROOM_UNROLL _Pragma("unroll")
 #else
 #include <math.h>
 #include "b32_world_point.h"
-#define B32_ROOM_UNROLL
 #endif
 
 namespace b32 {
@@ -49,7 +47,7 @@ struct RoomQuad { bool some[4]; float sx[4], sy[4], d[4]; };
 B32_HD void room_project(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, RoomQuad& q) {
     float base_x, base_z;
     room_base(g, f, base_x, base_z);
-    B32_ROOM_UNROLL
+    B32_UNROLL
     for (int k = 0; k < 4; ++k) {
         float p[3];
         room_corner(g, f, base_x, base_z, k, p);
@@ -137,7 +135,7 @@ B32_HD void room_candidates(const ViewBlock& v, const B32RoomGrid& g, const B32S
     RoomQuad q;
     room_project(v, g, f, q);
     c.vmask = 0u; c.emask = 0u;
-    B32_ROOM_UNROLL
+    B32_UNROLL
     for (int k = 0; k < 4; ++k) {
         c.vdist[k] = c.vdepth[k] = c.edist[k] = c.edepth[k] = 0.0f;
         if (room_vertex(q, k, p.mx, p.my, p.vertex_threshold, c.vdist[k], c.vdepth[k])) c.vmask |= 1u << k;

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
         if (e < a.o.n_edges) {
             const uint32_t rec = a.lists[a.l_edges + 2u * e], idx = a.lists[a.l_edges + 2u * e + 1u];
             B32Prim* o = out + a.at_edges + e;
-            *o = gizmo_noop();
+            *o = prim_noop();
             if (rec < a.n) mine = room_overlay_thick_edge(a.v, a.grid, a.faces[rec], idx & 3u, ROOM_OVERLAY_SELECTED_VERTEX, o);
         }
     } else if ((wg -= a.g_edges) < a.g_hover) {     // :4404-4658: lane 0 the edge, lane 1 the face
@@ -52,14 +52,14 @@ __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
             const int winner = room_hover_winner(h);
             B32Prim* o = out + a.at_hover;
             if (i == 0u) {
-                *o = gizmo_noop();
+                *o = prim_noop();
                 if (winner == 1 && h.edge_rec < a.n) mine = room_overlay_thick_edge(a.v, a.grid, a.faces[h.edge_rec], h.edge_idx & 3u, ROOM_OVERLAY_HOVER_EDGE, o);
             } else {
                 const bool skipped = h.face_rec >= a.o.skip_first && h.face_rec - a.o.skip_first < a.o.skip_count;
                 if (winner == 2 && h.face_rec < a.n && !skipped)
                     mine = room_overlay_face(a.v, a.grid, a.faces[h.face_rec], a.mats ? a.mats + h.face_rec : nullptr, ROOM_OVERLAY_HOVER_FACE, o + 1);
                 else
-                    for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) o[1u + j] = gizmo_noop();
+                    for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) o[1u + j] = prim_noop();
             }
         }
     } else if ((wg -= a.g_hover) < a.g_sel_faces) { // :4868-5047
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
             const uint32_t rec = a.lists[a.l_faces + k];
             B32Prim* o = out + a.at_sel_faces + (size_t)k * ROOM_OVERLAY_FACE_SLOTS;
             if (rec < a.n) mine = room_overlay_face(a.v, a.grid, a.faces[rec], a.mats ? a.mats + rec : nullptr, ROOM_OVERLAY_SELECT, o);
-            else for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) o[j] = gizmo_noop();
+            else for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) o[j] = prim_noop();
         }
     } else if ((wg -= a.g_sel_faces) < a.g_sel_edges) {     // :5174-5236
         const uint32_t e = wg * 256u + i;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_room_overlay(RoomOverlayArgs a) {
             const uint32_t rec = a.lists[a.l_edges + 2u * e], idx = a.lists[a.l_edges + 2u * e + 1u];
             B32Prim* o = out + a.at_sel_edges + e;
             if (rec < a.n) mine = room_overlay_line_edge(a.v, a.grid, a.faces[rec], idx & 3u, ROOM_OVERLAY_SELECT, o);
-            else *o = gizmo_noop();
+            else *o = prim_noop();
         }
     } else if ((wg -= a.g_sel_edges) < a.g_preview) {       // :5267-5340
         const uint32_t rec = wg * 256u + i;

@@ -2,8 +2,9 @@
 // group: the selected / hovered vertex circles (:4273-4316), draw_edge_highlight (:4318-4402), the hovered edge and face (:4404-4658),
 // draw_selection's SectorFace and Edge arms (:4862-5247) and the box-select preview (:5249-5362).  k_room_overlay (b32_room_overlay.hip)
 // turns (resident records, materials, hover, lists, rectangle) into B32Prim records with these functions.  Every expression is a
-// separately rounded f32 operation in the reference's order and `as i32` saturates; draw_3d_line is gizmo_item's B32_GIZMO_LINE
-// (b32_gizmo_body.h), not restated.  The text also compiles for the host (B32_HD, b32_world_point.h), where tests/test_room_overlay.py
+// separately rounded f32 operation in the reference's order.  Not restated here: draw_3d_line is gizmo_item's B32_GIZMO_LINE
+// (b32_gizmo_body.h); the cast, the 2^30 limit, the no-op and the circle and thick-line records are b32_prim_record.h's -- what a
+// refused call means (a tally in 10-bit fields) is this file's.  The text also compiles for the host (B32_HD, b32_world_point.h), where tests/test_room_overlay.py
 // runs it against a literal restatement, built with and without -ffp-contract=off.
 //
 // Where a record lies is a function of n, the B32RoomOverlay and the lists alone (room_overlay_layout): a call the reference does not
@@ -25,10 +26,9 @@ constexpr uint32_t ROOM_OVERLAY_NONE = 0xFFFFFFFFu;
 constexpr uint32_t ROOM_OVERLAY_ALL = 31u;          // every B32_ROOM_OVERLAY_* bit
 constexpr uint32_t ROOM_OVERLAY_HOVER_SLOTS = 7u, ROOM_OVERLAY_FACE_SLOTS = 6u, ROOM_OVERLAY_PREVIEW_SLOTS = 4u, ROOM_OVERLAY_POINT_SLOTS = 3u;
 
-struct RoomOverlayColor { uint8_t r, g, b; };
-constexpr RoomOverlayColor ROOM_OVERLAY_SELECTED_VERTEX = { 100, 255, 100 }, ROOM_OVERLAY_HOVER_VERTEX = { 255, 200, 150 },
-                           ROOM_OVERLAY_HOVER_EDGE = { 255, 200, 100 }, ROOM_OVERLAY_HOVER_FACE = { 150, 200, 255 },
-                           ROOM_OVERLAY_SELECT = { 255, 200, 80 }, ROOM_OVERLAY_PREVIEW = { 100, 220, 255 };
+constexpr PrimColor ROOM_OVERLAY_SELECTED_VERTEX = { 100, 255, 100 }, ROOM_OVERLAY_HOVER_VERTEX = { 255, 200, 150 },
+                    ROOM_OVERLAY_HOVER_EDGE = { 255, 200, 100 }, ROOM_OVERLAY_HOVER_FACE = { 150, 200, 255 },
+                    ROOM_OVERLAY_SELECT = { 255, 200, 80 }, ROOM_OVERLAY_PREVIEW = { 100, 220, 255 };
 
 // What a slot group adds to drawn / dropped / rejected: three 10-bit fields (a lane makes at most six calls, a wave 384)
 B32_HD uint32_t room_overlay_tally(uint32_t which) { return 1u << (10u * which); }
@@ -42,31 +42,27 @@ B32_HD void room_overlay_corner(const B32RoomGrid& g, const B32SectorFace& f, co
 }
 
 // draw_3d_line(fb, p0, p1, camera, color) into one record
-B32_HD uint32_t room_overlay_line(const ViewBlock& v, const float* p0, const float* p1, RoomOverlayColor c, B32Prim* out) {
+B32_HD uint32_t room_overlay_line(const ViewBlock& v, const float* p0, const float* p1, PrimColor c, B32Prim* out) {
     B32GizmoItem it{};
-    B32_ROOM_UNROLL
+    B32_UNROLL
     for (int k = 0; k < 3; ++k) { it.p0[k] = p0[k]; it.p1[k] = p1[k]; }
-    it.r = c.r; it.g = c.g; it.b = c.b; it.blend = B32_BLEND_OPAQUE;     // RasterColor::new
+    it.r = c.r; it.g = c.g; it.b = c.b; it.blend = c.blend;
     it.kind = B32_GIZMO_LINE;
     return room_overlay_tally(gizmo_item(v, it, out));
 }
 
 // world_to_screen -> fb.draw_circle(fb_x as i32, fb_y as i32, radius, color), :4276-4313
-B32_HD uint32_t room_overlay_circle(const ViewBlock& v, const float* p, int32_t radius, RoomOverlayColor c, B32Prim* out) {
+B32_HD uint32_t room_overlay_circle(const ViewBlock& v, const float* p, int32_t radius, PrimColor c, B32Prim* out) {
     float sx, sy, z;
     if (!world_point(v, p, false, sx, sy, z)) return room_overlay_tally(1u);
-    const int32_t x = gizmo_i32(sx), y = gizmo_i32(sy);
-    if ((long long)x >= GIZMO_LIM || (long long)x <= -GIZMO_LIM || (long long)y >= GIZMO_LIM || (long long)y <= -GIZMO_LIM) return room_overlay_tally(2u);
-    B32Prim o{};
-    o.x0 = x; o.y0 = y; o.size = radius;
-    o.r = c.r; o.g = c.g; o.b = c.b; o.blend = B32_BLEND_OPAQUE;
-    o.kind = B32_PRIM_CIRCLE; o.alpha = 255;
-    *out = o;
+    const int32_t x = as_i32(sx), y = as_i32(sy);
+    if (prim_big(x) || prim_big(y)) return room_overlay_tally(2u);
+    *out = prim_circle(B32_PRIM_CIRCLE, x, y, radius, c, 255u);
     return room_overlay_tally(0u);
 }
 
 // edge (e, (e + 1) % 4) of record f as draw_edge_highlight draws it, :4373-4384: both ends through world_to_screen, fb.draw_thick_line(.., 3, color)
-B32_HD uint32_t room_overlay_thick_edge(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, uint32_t e, RoomOverlayColor c, B32Prim* out) {
+B32_HD uint32_t room_overlay_thick_edge(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, uint32_t e, PrimColor c, B32Prim* out) {
     float base_x, base_z, p0[3], p1[3];
     room_base(g, f, base_x, base_z);
     const uint32_t e1 = (e + 1u) & 3u;
@@ -75,19 +71,14 @@ B32_HD uint32_t room_overlay_thick_edge(const ViewBlock& v, const B32RoomGrid& g
     float sx0, sy0, sx1, sy1, z;
     const bool some0 = world_point(v, p0, false, sx0, sy0, z), some1 = world_point(v, p1, false, sx1, sy1, z);
     if (!some0 || !some1) return room_overlay_tally(1u);
-    const int32_t x0 = gizmo_i32(sx0), y0 = gizmo_i32(sy0), x1 = gizmo_i32(sx1), y1 = gizmo_i32(sy1);
-    const long long dx = (long long)x1 - x0, dy = (long long)y1 - y0;
-    if (dx >= GIZMO_LIM || dx <= -GIZMO_LIM || dy >= GIZMO_LIM || dy <= -GIZMO_LIM) return room_overlay_tally(2u);
-    B32Prim o{};
-    o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1; o.size = 3;
-    o.r = c.r; o.g = c.g; o.b = c.b; o.blend = B32_BLEND_OPAQUE;
-    o.kind = B32_PRIM_THICK_LINE; o.alpha = 255;
-    *out = o;
+    const int32_t x0 = as_i32(sx0), y0 = as_i32(sy0), x1 = as_i32(sx1), y1 = as_i32(sy1);
+    if (prim_wide(x0, x1) || prim_wide(y0, y1)) return room_overlay_tally(2u);
+    *out = prim_thick_line(x0, y0, x1, y1, 3, c, 255u);
     return room_overlay_tally(0u);
 }
 
 // draw_selection's Edge arm, :5229-5233: one draw_3d_line between corners e and (e + 1) % 4
-B32_HD uint32_t room_overlay_line_edge(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, uint32_t e, RoomOverlayColor c, B32Prim* out) {
+B32_HD uint32_t room_overlay_line_edge(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, uint32_t e, PrimColor c, B32Prim* out) {
     float base_x, base_z, p0[3], p1[3];
     room_base(g, f, base_x, base_z);
     const uint32_t e1 = (e + 1u) & 3u;
@@ -107,7 +98,7 @@ constexpr uint32_t ROOM_OVERLAY_A_NWSE = room_overlay_pack6(0, 1, 2, 3, 0, 0), R
                    ROOM_OVERLAY_A_NESW = room_overlay_pack6(0, 0, 1, 2, 1, 1), ROOM_OVERLAY_B_NESW = room_overlay_pack6(1, 3, 2, 3, 3, 3),
                    ROOM_OVERLAY_SECOND = 0x2Cu;     // slots 2, 3 and 5 read triangle 2's heights
 // mat: the record's material, or nullptr (no table: the record's own heights and B32_SPLIT_NWSE, the reference's defaults)
-B32_HD uint32_t room_overlay_face(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, const B32FaceMaterial* mat, RoomOverlayColor c, B32Prim* out) {
+B32_HD uint32_t room_overlay_face(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, const B32FaceMaterial* mat, PrimColor c, B32Prim* out) {
     float base_x, base_z;
     room_base(g, f, base_x, base_z);
     const bool flat = f.kind < 2u;
@@ -116,7 +107,7 @@ B32_HD uint32_t room_overlay_face(const ViewBlock& v, const B32RoomGrid& g, cons
     const uint32_t A = nesw ? ROOM_OVERLAY_A_NESW : ROOM_OVERLAY_A_NWSE, B = nesw ? ROOM_OVERLAY_B_NESW : ROOM_OVERLAY_B_NWSE;
     uint32_t tally = 0u;
     for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) {
-        if (!flat && j == 5u) { out[j] = gizmo_noop(); continue; }
+        if (!flat && j == 5u) { out[j] = prim_noop(); continue; }
         const uint32_t ka = (A >> (2u * j)) & 3u, kb = (B >> (2u * j)) & 3u;
         const float* H = (flat && ((ROOM_OVERLAY_SECOND >> j) & 1u)) ? H2 : f.heights;
         float p0[3], p1[3];
@@ -131,7 +122,7 @@ B32_HD uint32_t room_overlay_face(const ViewBlock& v, const B32RoomGrid& g, cons
 // WallSouth and WallWest: the preview's own (x0, z0, x1, z1) is the reverse of every other site (:5307, :5309), so corner k stands where
 // corner k ^ 1 stands elsewhere, with its own height.
 B32_HD uint32_t room_overlay_preview(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace& f, float rx0, float ry0, float rx1, float ry1, B32Prim* out) {
-    for (uint32_t j = 0; j < ROOM_OVERLAY_PREVIEW_SLOTS; ++j) out[j] = gizmo_noop();
+    for (uint32_t j = 0; j < ROOM_OVERLAY_PREVIEW_SLOTS; ++j) out[j] = prim_noop();
     float c[3];
     room_centre(g, f, c);
     if (!room_point_in_rect(v, c, rx0, ry0, rx1, ry1)) return 0u;
@@ -151,13 +142,13 @@ B32_HD uint32_t room_overlay_preview(const ViewBlock& v, const B32RoomGrid& g, c
 
 // The preview of an object position, :5341-5352, three slots: world_pos -+ Vec3(size, 0, 0) etc., component by component
 B32_HD uint32_t room_overlay_preview_point(const ViewBlock& v, const float* p, float rx0, float ry0, float rx1, float ry1, B32Prim* out) {
-    for (uint32_t j = 0; j < ROOM_OVERLAY_POINT_SLOTS; ++j) out[j] = gizmo_noop();
+    for (uint32_t j = 0; j < ROOM_OVERLAY_POINT_SLOTS; ++j) out[j] = prim_noop();
     if (!room_point_in_rect(v, p, rx0, ry0, rx1, ry1)) return 0u;
     const float size = 64.0f;
     uint32_t tally = 0u;
     for (uint32_t j = 0; j < ROOM_OVERLAY_POINT_SLOTS; ++j) {
         float p0[3], p1[3];
-        B32_ROOM_UNROLL
+        B32_UNROLL
         for (uint32_t k = 0; k < 3u; ++k) {
             const float d = k == j ? size : 0.0f;
             p0[k] = p[k] - d; p1[k] = p[k] + d;
@@ -172,7 +163,7 @@ B32_HD uint32_t room_overlay_preview_point(const ViewBlock& v, const float* p, f
 // is the keys' order, and the later circle wins a shared pixel.  A hovered vertex that is also selected is drawn as selected.
 B32_HD uint32_t room_overlay_vertex(const ViewBlock& v, const B32RoomGrid& g, const B32SectorFace* faces, uint32_t n, const uint32_t* keys, uint32_t n_keys,
                                     uint32_t primary, uint32_t hover_key, uint32_t p, B32Prim* out) {
-    *out = gizmo_noop();
+    *out = prim_noop();
     uint32_t lo = n_keys;
     if (hover_key != ROOM_OVERLAY_NONE) {           // the first key >= hover_key
         lo = 0u;
@@ -208,8 +199,6 @@ static inline int room_overlay_check(const B32RoomOverlay* o, const uint32_t* se
     if (o->hover_source == 0u && o->hover.edge_rec != ROOM_OVERLAY_NONE && o->hover.edge_idx > 3u) return B32_E_ARG;
     return B32_OK;
 }
-static inline float room_overlay_fmin(float a, float b) { if (a != a) return b; if (b != b) return a; return b < a ? b : a; }   // f32::min
-static inline float room_overlay_fmax(float a, float b) { if (a != a) return b; if (b != b) return a; return b > a ? b : a; }   // f32::max
 // ... and where the sections lie: first record of every part, the total, the rectangle as the reference passes it on (:5252-5258)
 struct RoomOverlayLayout {
     uint64_t vertices, edges, hover, sel_faces, sel_edges, preview, points, total;
@@ -223,8 +212,8 @@ static inline RoomOverlayLayout room_overlay_layout(uint32_t n, const B32RoomOve
     l.hover = at; if (o.sections & B32_ROOM_OVERLAY_HOVER) at += ROOM_OVERLAY_HOVER_SLOTS;
     l.sel_faces = at; if (o.sections & B32_ROOM_OVERLAY_SELECTED) at += (uint64_t)ROOM_OVERLAY_FACE_SLOTS * o.n_faces;
     l.sel_edges = at; if (o.sections & B32_ROOM_OVERLAY_SELECTED) at += o.n_edges;
-    l.rect[0] = room_overlay_fmin(o.x0, o.x1); l.rect[2] = room_overlay_fmax(o.x0, o.x1);
-    l.rect[1] = room_overlay_fmin(o.y0, o.y1); l.rect[3] = room_overlay_fmax(o.y0, o.y1);
+    l.rect[0] = f32_min(o.x0, o.x1); l.rect[2] = f32_max(o.x0, o.x1);
+    l.rect[1] = f32_min(o.y0, o.y1); l.rect[3] = f32_max(o.y0, o.y1);
     l.gate = (o.sections & B32_ROOM_OVERLAY_PREVIEW) && ((l.rect[2] - l.rect[0]) > 3.0f || (l.rect[3] - l.rect[1]) > 3.0f);
     l.preview = at; if (l.gate) at += (uint64_t)ROOM_OVERLAY_PREVIEW_SLOTS * n;
     l.points = at; if (l.gate) at += (uint64_t)ROOM_OVERLAY_POINT_SLOTS * o.n_points;

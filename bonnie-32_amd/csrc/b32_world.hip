@@ -6,11 +6,12 @@
 // clipped segment is drawn at all can hang on the last bit of p0 + (p1 - p0) * t: the clipped end is projected again and answers None when
 // its camera z comes out <= 0.1.
 //
-// GPU form: one lane per item, the reference's expressions in the reference's order (f32, no contraction, Vec3::dot = (x*ox + y*oy) + z*oz,
-// f2i32_sat = `as i32`).  Record i is written from item i, so the array order is the reference's call order; an item that draws nothing
-// becomes a circle of radius -1, which the tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of
-// b32_prims.hip reads them where this kernel wrote them.
+// GPU form: one lane per item through world_item (b32_world_body.h: the reference's expressions in the reference's order).  Record i is
+// written from item i, so the array order is the reference's call order; an item that draws nothing becomes the no-op record, which the
+// tile pass skips (PrimPass::bounds).  The records stay on the device: the ordered tile pass of b32_prims.hip reads them where this
+// kernel wrote them.
 #include "b32_item_kernels.h"
+#include "b32_world_body.h"
 #include <cmath>
 
 namespace b32 {
@@ -24,53 +25,11 @@ struct WorldProject {
 };
 static_assert(sizeof(B32WorldItem) == 40 && sizeof(ItemBatch<WorldProject>) + sizeof(WorldArgs) <= 2048, "B32WorldItem layout / kernel argument size");
 
-// item i of the batch
+// item i of the batch (a lane without one works on a zeroed item and counts nothing)
 __device__ __forceinline__ void WorldProject::item(const WorldArgs& a, const B32WorldItem& it, uint32_t i, bool live) {
     uint32_t* tally = outcome_tally();
-    const bool circle = it.kind == B32_PRIM_CIRCLE || it.kind == B32_PRIM_CIRCLE_ALPHA;
-    const bool depth = it.kind >= B32_LINE_3D && it.kind <= B32_LINE_3D_ALPHA;
-    float p0[3] = { it.p0[0], it.p0[1], it.p0[2] }, p1[3] = { it.p1[0], it.p1[1], it.p1[2] };
-    bool ortho = a.v.has_ortho != 0u, some = true;
-    if (!circle && (it.flags & B32_WORLD_CLIP_NEAR)) {          // draw_3d_line_clipped, draw.rs:19-42 (the projection after it takes no ortho)
-        ortho = false;
-        const float rel0[3] = { p0[0] - a.v.pos[0], p0[1] - a.v.pos[1], p0[2] - a.v.pos[2] };
-        const float rel1[3] = { p1[0] - a.v.pos[0], p1[1] - a.v.pos[1], p1[2] - a.v.pos[2] };
-        const float z0 = world_dot(rel0, a.v.bz), z1 = world_dot(rel1, a.v.bz);
-        if (z0 <= WORLD_NEAR && z1 <= WORLD_NEAR) {
-            some = false;
-        } else if (z0 <= WORLD_NEAR || z1 <= WORLD_NEAR) {
-            const float t = (WORLD_NEAR - z0) / (z1 - z0);
-            float q[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) q[k] = p0[k] + (p1[k] - p0[k]) * t;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { if (z0 <= WORLD_NEAR) p0[k] = q[k]; else p1[k] = q[k]; }
-        }
-    }
-    float sx0 = 0.0f, sy0 = 0.0f, cz0 = 0.0f, sx1 = 0.0f, sy1 = 0.0f, cz1 = 0.0f;
-    if (some) some = world_point(a.v, p0, ortho, sx0, sy0, cz0);
-    if (some && !circle) some = world_point(a.v, p1, ortho, sx1, sy1, cz1);
-
-    B32Prim o{};
-    o.kind = B32_PRIM_CIRCLE; o.size = -1;                      // draws nothing
-    uint32_t which = 1u;                                        // dropped: the reference draws nothing
-    if (some) {
-        const int32_t x0 = f2i32_sat(sx0), y0 = f2i32_sat(sy0);
-        const int32_t x1 = circle ? 0 : f2i32_sat(sx1), y1 = circle ? 0 : f2i32_sat(sy1);
-        constexpr long long LIM = 1ll << 30;                    // what b32_draw_prims answers B32_E_UNSUPPORTED for
-        const bool bad = circle ? (llabs((long long)x0) >= LIM || llabs((long long)y0) >= LIM)
-                                : (llabs((long long)x1 - x0) >= LIM || llabs((long long)y1 - y0) >= LIM);
-        which = bad ? 2u : 0u;
-        if (!bad) {
-            o.x0 = x0; o.y0 = y0; o.x1 = x1; o.y1 = y1;
-            // (a NaN depth as one fixed quiet NaN: payloads are unspecified, and every NaN fails every depth test alike)
-            o.z0 = !depth ? 0.0f : (cz0 != cz0 ? __uint_as_float(0x7FC00000u) : cz0);
-            o.z1 = !depth ? 0.0f : (cz1 != cz1 ? __uint_as_float(0x7FC00000u) : cz1);
-            o.size = it.size;
-            o.r = it.r; o.g = it.g; o.b = it.b; o.blend = it.blend;
-            o.kind = it.kind; o.alpha = it.alpha; o.mode = it.mode;
-        }
-    }
+    B32Prim o;
+    const uint32_t which = world_item(a.v, it, &o);
     if (live) a.out[i] = o;
     outcome_count(tally, a.counts, live ? which : 3u);
 }

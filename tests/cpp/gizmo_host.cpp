@@ -37,7 +37,7 @@ int main(int argc, char** argv) {
     for (size_t r = 0; r < recs.size(); ++r) {
         const B32Prim& p = recs[r];
         if (p.kind != b32::PRIM_TRIANGLE) continue;
-        int32_t x[3] = { p.x0, p.x1, b32::gizmo_f32_bits(p.z0) }, y[3] = { p.y0, p.y1, b32::gizmo_f32_bits(p.z1) };
+        int32_t x[3] = { p.x0, p.x1, (int32_t)b32::f32_bits(p.z0) }, y[3] = { p.y0, p.y1, (int32_t)b32::f32_bits(p.z1) };
         b32::gizmo_tri_sort(x, y);
         if (y[2] == y[0]) continue;
         const int32_t ya = y[0] > 0 ? y[0] : 0, yb = y[2] < (int32_t)h - 1 ? y[2] : (int32_t)h - 1;

@@ -46,12 +46,12 @@ int main(int argc, char** argv) {
     if (sec & B32_ROOM_OVERLAY_EDGES)
         for (uint32_t e = 0; e < o.n_edges; ++e) {
             B32Prim* q = out.data() + l.edges + e;
-            *q = gizmo_noop();
+            *q = prim_noop();
             if (edges[2 * e] < n) take(room_overlay_thick_edge(v, g, faces[edges[2 * e]], edges[2 * e + 1] & 3u, ROOM_OVERLAY_SELECTED_VERTEX, q));
         }
     if (sec & B32_ROOM_OVERLAY_HOVER) {
         B32Prim* q = out.data() + l.hover;
-        for (uint32_t j = 0; j < ROOM_OVERLAY_HOVER_SLOTS; ++j) q[j] = gizmo_noop();
+        for (uint32_t j = 0; j < ROOM_OVERLAY_HOVER_SLOTS; ++j) q[j] = prim_noop();
         if (winner == 1 && hv.edge_rec < n) take(room_overlay_thick_edge(v, g, faces[hv.edge_rec], hv.edge_idx & 3u, ROOM_OVERLAY_HOVER_EDGE, q));
         const bool skipped = hv.face_rec >= o.skip_first && hv.face_rec - o.skip_first < o.skip_count;
         if (winner == 2 && hv.face_rec < n && !skipped) take(room_overlay_face(v, g, faces[hv.face_rec], M ? M + hv.face_rec : nullptr, ROOM_OVERLAY_HOVER_FACE, q + 1));
@@ -60,12 +60,12 @@ int main(int argc, char** argv) {
         for (uint32_t k = 0; k < o.n_faces; ++k) {
             B32Prim* q = out.data() + l.sel_faces + (size_t)k * ROOM_OVERLAY_FACE_SLOTS;
             if (sel[k] < n) take(room_overlay_face(v, g, faces[sel[k]], M ? M + sel[k] : nullptr, ROOM_OVERLAY_SELECT, q));
-            else for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) q[j] = gizmo_noop();
+            else for (uint32_t j = 0; j < ROOM_OVERLAY_FACE_SLOTS; ++j) q[j] = prim_noop();
         }
         for (uint32_t e = 0; e < o.n_edges; ++e) {
             B32Prim* q = out.data() + l.sel_edges + e;
             if (edges[2 * e] < n) take(room_overlay_line_edge(v, g, faces[edges[2 * e]], edges[2 * e + 1] & 3u, ROOM_OVERLAY_SELECT, q));
-            else *q = gizmo_noop();
+            else *q = prim_noop();
         }
     }
     if (l.gate) {

@@ -9,7 +9,10 @@ ref_world itself is pinned by hand-computed cases and, for the near-plane clip (
 p0 + (p1 - p0) * t), by the same expressions evaluated in exact rational arithmetic with an explicit round-to-nearest-even.
 Every GPU frame is compared byte for byte with a frame composed on the CPU in the same order: the oracle renders the meshes,
 tests.test_prims.np_prims draws np_world's records wherever the GPU side calls a world entry."""
+import atexit
+import functools
 import os
+import shutil
 import subprocess
 import tempfile
 from fractions import Fraction
@@ -554,6 +557,59 @@ def test_vectorised_world_model_equals_literal_model():
     I = np.concatenate([I for _, I in the_20000()])
     assert set(np.unique(I["kind"])) == set(range(9)) and set(np.unique(I["flags"])) == {0, 1}
     assert np.isnan(I["p0"]).any() and np.isinf(I["p1"]).any() and (I["p0"][:, 2] == NEAR).any()
+
+
+@functools.lru_cache(maxsize=None)
+def _world_host_exe():
+    d = tempfile.mkdtemp(prefix="b32_world_host_")
+    atexit.register(shutil.rmtree, d, True)
+    exe = os.path.join(d, "world_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "bonnie-32_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "world_host.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def host_world(items, camera, ortho, w, h):
+    """(records, counts, which) from b32_world_body.h compiled for the host."""
+    items = np.ascontiguousarray(items, abi.WORLD_ITEM_DTYPE).reshape(-1)
+    exe = _world_host_exe()
+    fin, fout = exe + ".in", exe + ".out"
+    with open(fin, "wb") as fh:
+        fh.write(np.array([w, h, int(ortho is not None), len(items)], np.uint32).tobytes())
+        fh.write(np.array([v for g in _cam_f32(camera) for v in g], f32).tobytes())
+        fh.write(np.array(ortho if ortho is not None else (0, 0, 0), f32).tobytes())
+        fh.write(items.tobytes())
+    subprocess.run([exe, fin, fout], check=True)
+    blob = open(fout, "rb").read()
+    assert len(blob) == 24 + 44 * len(items)
+    counts = tuple(int(v) for v in np.frombuffer(blob, np.uint64, 3))
+    which = np.frombuffer(blob, np.uint32, len(items), 24)
+    return np.frombuffer(blob, abi.PRIM_DTYPE, len(items), 24 + 4 * len(items)), counts, which
+
+
+def test_world_body_on_the_host_equals_the_models():
+    """csrc/b32_world_body.h built for the host (g++ -O1 -ffp-contract=off -Wall -Werror): the records, the per-item outcomes and the
+    counts equal np_world bit for bit on the 20 000 items (both sizes, perspective and ortho), and ref_world item by item on 400 hostile
+    items of every kind, with and without the clip flag."""
+    noop = noop_records(1).tobytes()
+    for k, (cam, I) in enumerate(the_20000()):
+        for ortho in (None, ORTHO):
+            for w, h in SIZES:
+                want, wc = np_world(I, cam, ortho, w, h)
+                got, gc, which = host_world(I, cam, ortho, w, h)
+                assert got.tobytes() == want.tobytes(), f"batch {k} {w}x{h} ortho={ortho}: records {np.nonzero(got != want)[0][:8]} differ"
+                assert gc == wc and tuple(np.bincount(which, minlength=3)) == wc
+                assert all(got[i].tobytes() == noop for i in np.nonzero(which != 0)[0])
+    I = hostile_items(np.random.default_rng(77), 400, IDENTITY_CAM)
+    lines = ~np.isin(I["kind"], CIRCLE_KINDS)
+    assert set(np.unique(I["kind"])) == set(range(9))
+    assert all({0, 1} == set(I["flags"][I["kind"] == kd]) for kd in LINE_KINDS) and (I["flags"][~lines] == 0).all()
+    for ortho in (None, ORTHO):
+        want, wc = ref_world(I, IDENTITY_CAM, ortho, 320, 240)
+        got, gc, which = host_world(I, IDENTITY_CAM, ortho, 320, 240)
+        assert got.tobytes() == want.tobytes() and gc == wc and min(wc) > 0
+        each = [ref_world(I[i:i + 1], IDENTITY_CAM, ortho, 320, 240)[1].index(1) for i in range(len(I))]
+        assert list(which) == each
 
 
 def test_cpp_mirror_world_compiles():
