@@ -149,6 +149,13 @@ BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("
 assert BONE_DTYPE.itemsize == 32
 BONE_NONE = 0xFFFF
 MAX_BONES = 64
+# B32SkelBone / B32SkeletonStyle (b32_scene_build_skeleton, b32_skeleton_items): what the bone octahedra read per bone, and the editor state
+SKEL_BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("cos_z", "<f4"), ("sin_z", "<f4"), ("length", "<f4"),
+                            ("width", "<f4"), ("parent", "<u4")])
+SKELETON_STYLE_DTYPE = np.dtype([("selected_bone", "<i4"), ("hovered_bone", "<i4"), ("hovered_tip", "<i4"), ("mode", "<u4"), ("editor_alpha", "u1"),
+                                 ("has_preview", "u1"), ("_pad", "u1", 2), ("preview_start", "<f4", 3), ("preview_end", "<f4", 3)])
+assert SKEL_BONE_DTYPE.itemsize == 40 and SKELETON_STYLE_DTYPE.itemsize == 44
+SKELETON_TRIANGLES, SKELETON_FROM_BONES = 0, 1
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -244,6 +251,9 @@ SYMBOLS = [
     ("b32_scene_set_rig", C.c_int, [_P, _P, _P]),
     ("b32_scene_pose", C.c_int, [_P, _P, _P, C.c_uint32]),
     ("b32_scene_read_vertices", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_scene_build_skeleton", C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    ("b32_skeleton_counts", C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("b32_skeleton_items", C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_frame_begin", C.c_int, [_P, _P, _P]),
     ("b32_frame_add_scene", C.c_int, [_P, _P, _P]),
     ("b32_frame_end", C.c_int, [_P]),

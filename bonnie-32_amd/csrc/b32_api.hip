@@ -468,14 +468,14 @@ int MeshOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
     if (!cam || !slot || !o || !w || !h || !slot->have_scene) return B32_E_ARG;
     { const int rc = overlay_check(topo != nullptr, o, selected); if (rc) return rc; }
     const uint32_t np = topo ? topo->np : 0u, nh = topo ? topo->nh : 0u;
-    const OverlayLayout l = overlay_layout(topo ? topo->h_poly_start.data() : nullptr, np, nh, topo ? topo->ne : 0u, slot->nv, *o, selected);
+    const OverlayLayout l = overlay_layout(topo ? topo->h_poly_start.data() : nullptr, np, nh, topo ? topo->ne : 0u, slot->body_nv(), *o, selected);
     total = l.total;
     if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
     view_fill(a.v, *cam, w, h, ortho);
     const bool packed = slot->pos_valid && slot->d_pos12;
     a.pos = packed ? slot->d_pos12 : reinterpret_cast<const float*>(slot->d_verts);
     a.stride = packed ? 3u : (uint32_t)(sizeof(B32Vertex) / sizeof(float));
-    a.nv = slot->nv;
+    a.nv = slot->body_nv();                             // (bone octahedra behind the mesh get no brackets and no dots)
     if (topo) { a.he = topo->he; a.poly_start = topo->poly_start; a.poly_verts = topo->poly_verts; a.np = np; a.nh = nh; }
     a.o = *o;
     a.at_brackets = (uint32_t)l.brackets; a.at_edges = (uint32_t)l.edges; a.at_dots = (uint32_t)l.dots;
@@ -508,7 +508,7 @@ int MeshOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
     }
     if ((sec & B32_OVERLAY_HOVER) && (o->hover_vertex != OVERLAY_NONE || o->hover_edge_v0 != OVERLAY_NONE || o->hover_edge_v1 != OVERLAY_NONE || l.hover_face_cnt))
         a.g_hover = 1u;
-    if ((sec & B32_OVERLAY_BRACKETS) && slot->nv) a.g_brackets = 1u;
+    if ((sec & B32_OVERLAY_BRACKETS) && a.nv) a.g_brackets = 1u;
     if ((unsigned long long)a.g_edges + a.g_pedges + a.g_sel + a.g_pfaces + 2u >= (1ull << 31)) return B32_E_UNSUPPORTED;
     return B32_OK;
 }

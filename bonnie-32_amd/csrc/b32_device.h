@@ -462,6 +462,11 @@ void launch_pack_streams(hipStream_t s, const B32Vertex* verts, uint32_t nv, flo
 // bones (b32_pose.hip): the slot's positions and normals into its rest stream; rest stream + bone table -> the slot's vertices
 void launch_pose_rest(hipStream_t s, const B32Vertex* verts, uint32_t nv, float* rest);
 void launch_pose(hipStream_t s, const float* rest, const uint16_t* bone_of, B32Vertex* verts, uint32_t nv, const B32Bone* bones, uint32_t n_bones);
+// the bone octahedra (b32_skeleton.hip): n_octs drawn octahedra (b32_skeleton_body.h) -> 6 vertices from verts[first_vertex] and 8 faces
+// from faces[first_face] each, and the scene's face count into consts[0]
+struct SkelOct;
+void launch_skeleton_mesh(hipStream_t s, const SkelOct* octs, uint32_t n_octs, B32Vertex* verts, uint32_t first_vertex, B32Face* faces, uint32_t first_face,
+                          uint32_t* consts);
 void launch_project_fixed(hipStream_t s, const float* pos, uint32_t n, B32Camera cam, uint32_t w, uint32_t h,
                           int32_t* sx, int32_t* sy, float* z);
 void launch_selftest(hipStream_t s, int op, const float* a, const float* b, const float* c, float* out, uint32_t n);

@@ -123,6 +123,13 @@ struct b32_scene {
     // bones (b32_scene_set_rig): the rest stream (nv positions and normals, 24 B each) k_pose starts from, and a bone index per vertex.
     // Part of the scene's content: swapped with it, dropped (have_rig = false, the buffers stay for the next rig) by every upload
     float* d_rest = nullptr; size_t cap_rest = 0; uint16_t* d_bone_of = nullptr; size_t cap_bone_of = 0; bool have_rig = false;
+    // the bone octahedra (b32_scene_build_skeleton): the last tail_v of the nv vertices and the last tail_f of the nf faces.  Everything
+    // that draws reads nv / nf; what the reference does to mesh objects only (rig, pose, hover, box selection, pick, selection overlays)
+    // reads body_nv() / body_nf().  While there is a tail, body_* hold the blend bookkeeping of the body alone (the scene's own values
+    // are body + tail).  Part of the scene's content: swapped with it, dropped by every upload and by b32_room_build_mesh
+    uint32_t tail_v = 0, tail_f = 0, body_blend_faces = 0; bool body_may_blend = false, body_blend8 = false;
+    uint32_t body_nv() const { return nv - tail_v; }
+    uint32_t body_nf() const { return nf - tail_f; }
     // The only list of a scene's device buffers (the caller has drained the streams that use them).
     void release() {
         for (void* p : { (void*)d_verts, (void*)d_faces, (void*)d_texels, (void*)d_texels32, (void*)d_tex, (void*)d_consts, (void*)d_texmask,
@@ -337,6 +344,26 @@ static int ensure(b32_ctx* c, T*& p, size_t& cap, size_t need) {
     size_t n = need + need / 4 + 16;
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
     cap = n;
+    return B32_OK;
+}
+// ensure() for a buffer whose first `keep` elements stay (b32_scene_build_skeleton: the body in front of a growing tail): the new
+// allocation is filled by a copy on the device, on the stream behind whatever wrote the old one, and the old one is freed after the one
+// synchronisation
+template <typename T>
+static int ensure_keep(b32_ctx* c, T*& p, size_t& cap, size_t need, size_t keep) {
+    if (need <= cap && p) return B32_OK;
+    c->side_dirty = true;
+    const size_t n = need + need / 4 + 16;
+    T* q = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&q), n * sizeof(T)));
+    T* old = p;
+    if (old) {
+        hipError_t e = keep ? hipMemcpyAsync(q, old, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { (void)hipFree(q); c->last_hip = (int)e; return B32_E_HIP; }
+    }
+    p = q; cap = n;                                     // (the slot owns the new buffer before the old one goes: a failing free leaves nothing dangling)
+    if (old) HIPCHK(c, hipFree(old));
     return B32_OK;
 }
 // Device words that stay armed between two calls (all ones, all zero: `fill`, a byte; < 0: no fill): at least `bytes` of them, allocated

@@ -237,7 +237,7 @@ int hover_common_check(const b32_ctx* c, const B32Camera* cam, const b32_scene* 
 
 void hover_item(PickItem& r, const b32_scene* sl, const B32Placement* place) {
     r = PickItem{};
-    r.verts = sl->d_verts; r.nv = sl->nv;
+    r.verts = sl->d_verts; r.nv = sl->body_nv();                                      // (bone octahedra are drawn, never hovered or selected)
     r.pos12 = (sl->pos_valid && sl->d_pos12) ? sl->d_pos12 : nullptr;
     if (place) { r.cos_f = place->cos_f; r.sin_f = place->sin_f; for (int k = 0; k < 3; ++k) r.wpos[k] = place->world_pos[k]; }
 }
@@ -399,7 +399,7 @@ int b32_box_select(b32_ctx* c, const B32Camera* cam, const B32Ortho* ortho, b32_
     { const int rc = hover_common_check(c, cam, slot); if (rc) return rc; }
     if (!prm || prm->mode > B32_BOX_POLYGONS || (prm->mode == B32_BOX_POLYGONS && !topo) || !n_selected) return B32_E_ARG;
     (void)hipSetDevice(c->device);
-    const uint32_t n = prm->mode == B32_BOX_POLYGONS ? topo->np : slot->nv;
+    const uint32_t n = prm->mode == B32_BOX_POLYGONS ? topo->np : slot->body_nv();
     const size_t nwords = (size_t)(((unsigned long long)n + 31u) / 32u);
     const unsigned char* h = nullptr;
     const int rc = pick_blocking(c, box_bytes(nwords), &h, [&](void* landing, uint64_t* t) {

@@ -99,12 +99,12 @@ int pick_table(b32_scene* const* slots, const B32Placement* places, uint32_t n, 
         const b32_scene* sl = slots[i];
         PickItem& r = rows[i];
         r = PickItem{};
-        r.verts = sl->d_verts; r.faces = sl->d_faces; r.nv = sl->nv; r.nf = sl->nf;
+        r.verts = sl->d_verts; r.faces = sl->d_faces; r.nv = sl->body_nv(); r.nf = sl->body_nf();       // (bone octahedra are drawn, never picked)
         r.pos12 = (sl->pos_valid && sl->d_pos12) ? sl->d_pos12 : nullptr;
         r.cos_f = places[i].cos_f; r.sin_f = places[i].sin_f;
         for (int k = 0; k < 3; ++k) r.wpos[k] = places[i].world_pos[k];
         r.first_wg = (uint32_t)wg;
-        wg += ((unsigned long long)sl->nf + PICK_CHUNK - 1u) / PICK_CHUNK;
+        wg += ((unsigned long long)sl->body_nf() + PICK_CHUNK - 1u) / PICK_CHUNK;
         if (wg >= (1ull << 24)) return B32_E_UNSUPPORTED;                                 // (16 G triangles in one call)
     }
     groups = (uint32_t)wg;

@@ -316,6 +316,7 @@ int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
     if (sc->nf != nf) { sc->direct_cap_opaque = 0; sc->direct_ntiles = 0; sc->direct_ok = true; }
     sc->nv = nv; sc->nf = nf;
     sc->have_rig = false;
+    sc->tail_v = 0; sc->tail_f = 0;
     sc->local_sort_ok = true;
     sc->pos_valid = false; sc->lit_valid = false; sc->band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;

@@ -1,6 +1,7 @@
 // b32_scene.hip -- the C ABI, part 2: host -> device uploads (the drop-in calls' staged arena, resident scenes with Texture15 / Texture /
 // index atlas + CLUT), scene slots, and the synchronous drop-in calls render_mesh[_15] / render_scene[_15].
 #include "b32_host.h"
+#include "b32_skeleton_body.h"
 
 extern "C" {
 // ------------------------------------------------------------------ scene upload
@@ -96,6 +97,7 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
     if (c->scene.nf != nf) { c->scene.direct_cap_opaque = 0; c->scene.direct_ntiles = 0; c->scene.direct_ok = true; }
     c->scene.nv = nv; c->scene.nf = nf;
     c->scene.have_rig = false;                          // (the rig belongs to the vertices it was set for)
+    c->scene.tail_v = 0; c->scene.tail_f = 0;           // (... and so do the bone octahedra behind them)
     c->scene.local_sort_ok = true;
     c->scene.pos_valid = false; c->scene.lit_valid = false; c->scene.band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;
@@ -326,16 +328,17 @@ static b32_scene* scene_of(b32_ctx* c, b32_scene* slot) {
 int b32_scene_set_rig(b32_ctx* c, b32_scene* slot, const uint16_t* bone_of_vertex) {
     if (!c) return B32_E_ARG;
     b32_scene* sc = scene_of(c, slot);
-    if (!sc || (sc->nv && !bone_of_vertex)) return B32_E_ARG;
+    const uint32_t nv = sc ? sc->body_nv() : 0u;        // (bone octahedra behind the mesh are not skinned: bone_index None)
+    if (!sc || (nv && !bone_of_vertex)) return B32_E_ARG;
     (void)hipSetDevice(c->device);
     int rc;
     sc->have_rig = false;
-    if ((rc = ensure(c, sc->d_rest, sc->cap_rest, (size_t)sc->nv * 6 + 1))) return rc;
-    if ((rc = ensure(c, sc->d_bone_of, sc->cap_bone_of, (size_t)sc->nv + 1))) return rc;
+    if ((rc = ensure(c, sc->d_rest, sc->cap_rest, (size_t)nv * 6 + 1))) return rc;
+    if ((rc = ensure(c, sc->d_bone_of, sc->cap_bone_of, (size_t)nv + 1))) return rc;
     // (on the stream: behind the upload or the pose that wrote the vertices, in front of the next pose)
-    launch_pose_rest(c->stream, sc->d_verts, sc->nv, sc->d_rest);
+    launch_pose_rest(c->stream, sc->d_verts, nv, sc->d_rest);
     HIPCHK(c, hipGetLastError());
-    if (sc->nv) HIPCHK(c, hipMemcpyAsync(sc->d_bone_of, bone_of_vertex, (size_t)sc->nv * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    if (nv) HIPCHK(c, hipMemcpyAsync(sc->d_bone_of, bone_of_vertex, (size_t)nv * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the caller may reuse its array (once per rig, like an upload)
     sc->have_rig = true;
     return B32_OK;
@@ -356,11 +359,99 @@ int b32_scene_pose(b32_ctx* c, b32_scene* slot, const B32Bone* bones, uint32_t n
     (void)hipSetDevice(c->device);
     // a pending frame that may still be redrawn is redrawn from the resident vertices: settle it before they change (b32_scene_upload)
     { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    launch_pose(c->stream, sc->d_rest, sc->d_bone_of, sc->d_verts, sc->nv, bones, n_bones);
+    launch_pose(c->stream, sc->d_rest, sc->d_bone_of, sc->d_verts, sc->body_nv(), bones, n_bones);
     HIPCHK(c, hipGetLastError());
     c->side_dirty = true;
     sc->pos_valid = false; sc->lit_valid = false;       // (frame_positions packs again on the next frame: band_frames stays)
     sc->gen = ++c->gen_counter;                          // a merged run that holds this scene is rebuilt
+    return B32_OK;
+}
+// ------------------------------------------------------------------ the bone octahedra (b32_skeleton.hip has the kernel and the why)
+// The drawn octahedra of a table, in order, the creation preview last: where liveness is decided, once (b32_skeleton_body.h).
+static uint32_t skeleton_octs(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle& st, SkelOct* octs) {
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_bones; ++i) if (skel_bone_oct(bones[i], st, i, octs[n])) ++n;
+    if (skel_preview_oct(st, octs[n])) ++n;
+    return n;
+}
+static int skeleton_check(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* st) {
+    if (!st || (n_bones && !bones) || st->mode > 1u) return B32_E_ARG;
+    return n_bones > B32_MAX_BONES ? B32_E_UNSUPPORTED : B32_OK;
+}
+int b32_skeleton_counts(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, uint32_t* n_vertices, uint32_t* n_faces) {
+    { const int rc = skeleton_check(bones, n_bones, style); if (rc) return rc; }
+    SkelOct octs[SKEL_MAX_OCTS];
+    const uint32_t n = skeleton_octs(bones, n_bones, *style, octs);
+    if (n_vertices) *n_vertices = n * SKEL_OCT_VERTS;
+    if (n_faces) *n_faces = n * SKEL_OCT_FACES;
+    return B32_OK;
+}
+// Ordering against the side stream and the bookkeeping are b32_scene_pose's (above).
+int b32_scene_build_skeleton(b32_ctx* c, b32_scene* slot, const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style) {
+    if (!c) return B32_E_ARG;
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc) return B32_E_ARG;
+    { const int rc = skeleton_check(bones, n_bones, style); if (rc) return rc; }
+    (void)hipSetDevice(c->device);
+    SkelOct octs[SKEL_MAX_OCTS];
+    const uint32_t n_octs = skeleton_octs(bones, n_bones, *style, octs);
+    // a pending frame that may still be redrawn is redrawn from the resident geometry: settle it before that changes (b32_scene_upload)
+    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    const uint32_t bv = sc->body_nv(), bf = sc->body_nf(), nv = bv + n_octs * SKEL_OCT_VERTS, nf = bf + n_octs * SKEL_OCT_FACES;
+    if (!sc->tail_v && !sc->tail_f) { sc->body_blend_faces = sc->blend_faces; sc->body_may_blend = sc->may_blend; sc->body_blend8 = sc->blend8; }
+    int rc;
+    if ((rc = ensure_keep(c, sc->d_verts, sc->cap_verts, (size_t)nv + 1, bv))) return rc;
+    if ((rc = ensure_keep(c, sc->d_faces, sc->cap_faces, (size_t)nf + 1, bf))) return rc;
+    if (!sc->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_consts), 16 * sizeof(uint32_t)));
+    {   // upload_geometry's face loop for the tail: a face with editor_alpha < 255 is a transparent-pass face
+        uint32_t nb = 0;
+        for (uint32_t k = 0; k < n_octs; ++k) nb += octs[k].alpha < 255 ? SKEL_OCT_FACES : 0u;
+        sc->blend_faces = sc->body_blend_faces + nb;
+        if (sc->fmt8) sc->blend8 = sc->body_blend8 || nb != 0;
+        else sc->may_blend = sc->body_may_blend || nb != 0;
+    }
+    if (sc->nf != nf) { sc->direct_cap_opaque = 0; sc->direct_ntiles = 0; sc->direct_ok = true; }
+    sc->nv = nv; sc->nf = nf; sc->tail_v = nv - bv; sc->tail_f = nf - bf;
+    sc->pos_valid = false; sc->lit_valid = false;
+    if ((rc = ensure_work(c, nf))) return rc;
+    launch_skeleton_mesh(c->stream, octs, n_octs, sc->d_verts, bv, sc->d_faces, bf, sc->d_consts);
+    HIPCHK(c, hipGetLastError());
+    c->side_dirty = true;
+    sc->gen = ++c->gen_counter;
+    return B32_OK;
+}
+int b32_skeleton_items(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, B32WorldItem* out, uint32_t cap, uint32_t* n_out) {
+    if (!n_out) return B32_E_ARG;
+    *n_out = 0;
+    { const int rc = skeleton_check(bones, n_bones, style); if (rc) return rc; }
+    uint32_t count = 0;
+    const auto put = [&](const B32WorldItem& it) { if (out && count < cap) out[count] = it; ++count; };
+    const auto colour = [](B32WorldItem& it, uint32_t r, uint32_t g, uint32_t b) { it.r = (uint8_t)r; it.g = (uint8_t)g; it.b = (uint8_t)b; it.blend = B32_BLEND_OPAQUE; it.alpha = 255; };
+    for (uint32_t i = 0; i < n_bones; ++i) {                    // draw_skeleton, skeleton.rs:70-79
+        const uint32_t parent = bones[i].parent;
+        if (parent == B32_BONE_NONE) continue;
+        B32WorldItem it{};
+        for (int k = 0; k < 3; ++k) { it.p0[k] = parent < n_bones ? bones[parent].pos[k] : 0.0f; it.p1[k] = bones[i].pos[k]; }
+        const uint32_t rgb = skel_colour(SKEL_COL_HIERARCHY_LINE);
+        colour(it, rgb & 255u, (rgb >> 8) & 255u, (rgb >> 16) & 255u);
+        it.kind = B32_LINE_2D; it.flags = B32_WORLD_CLIP_NEAR;
+        put(it);
+    }
+    for (uint32_t i = 0; i < n_bones; ++i) {                    // draw_bone_dots, skeleton.rs:110-143: the tip, then the base
+        const bool tip_hovered = style->hovered_tip >= 0 && (uint32_t)style->hovered_tip == i;
+        const bool hovered = style->hovered_bone >= 0 && (uint32_t)style->hovered_bone == i;
+        const bool selected = style->selected_bone >= 0 && (uint32_t)style->selected_bone == i;
+        B32WorldItem tip{}, base{};
+        skel_tip(bones[i], tip.p0);
+        tip.kind = B32_PRIM_CIRCLE; tip.size = tip_hovered ? 11 : (selected ? 8 : 5);
+        if (tip_hovered) colour(tip, 255, 180, 80); else if (selected) colour(tip, 80, 255, 80); else colour(tip, 220, 220, 230);
+        put(tip);
+        for (int k = 0; k < 3; ++k) base.p0[k] = bones[i].pos[k];
+        base.kind = B32_PRIM_CIRCLE; base.size = hovered ? 11 : (selected ? 8 : 5);
+        if (hovered) colour(base, 100, 180, 255); else if (selected) colour(base, 80, 255, 80); else colour(base, 150, 150, 160);
+        put(base);
+    }
+    *n_out = count;
     return B32_OK;
 }
 int b32_scene_read_vertices(b32_ctx* c, b32_scene* slot, uint32_t first, uint32_t count, B32Vertex* out) {

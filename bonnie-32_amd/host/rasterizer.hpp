@@ -394,6 +394,10 @@ public:
     // come back); read_vertices() is the blocking read-back of what the slot holds now.  Defined below, behind Bone.
     void set_rig(const std::vector<uint16_t>& bone_of_vertex) { check(b32_scene_set_rig(ctx_, slot_, bone_of_vertex.data()), "scene_set_rig"); }
     inline void pose(const std::vector<struct Bone>& bones);
+    // The bone octahedra (b32_scene_build_skeleton): one kernel replaces the mesh's tail with 6 vertices and 8 faces per drawn bone
+    // (skeleton_to_triangles), the creation preview last; an empty skeleton without a preview removes it.  The tail is drawn with the
+    // mesh and never hovered, selected, picked, skinned or overlaid.  Defined below, behind SkelBone.
+    inline void build_skeleton(const std::vector<struct SkelBone>& bones, const B32SkeletonStyle& style);
     std::vector<B32Vertex> read_vertices(uint32_t first, uint32_t count) const {
         std::vector<B32Vertex> out(count);
         check(b32_scene_read_vertices(ctx_, slot_, first, count, out.data()), "scene_read_vertices");
@@ -475,6 +479,48 @@ inline void ResidentMesh::pose(const std::vector<Bone>& bones) {
     std::vector<B32Bone> tab; tab.reserve(bones.size());
     for (const auto& b : bones) tab.push_back(b.pack());
     check(b32_scene_pose(ctx_, slot_, tab.data(), (uint32_t)tab.size()), "scene_pose");
+}
+// SkelBone: what the skeleton's drawing reads per bone (modeler/skeleton.rs:412-477, state.rs:2629-2638): the position of
+// get_bone_world_transform(i), cos / sin of the WORLD rotation's .x / .z (always read: get_bone_tip_position has no early return), length,
+// width = display_width() (state.rs:369-375) and the parent (B32_BONE_NONE: a root).
+struct SkelBone {
+    Vec3 pos; float cos_x = 1.0f, sin_x = 0.0f, cos_z = 1.0f, sin_z = 0.0f, length = 20.0f, width = 40.0f; uint32_t parent = B32_BONE_NONE;
+    static float display_width(float length, float width) {
+        if (width > 0.0f) return width;
+        const float w = length * 0.15f;
+        return w < 20.0f ? 20.0f : (w > 200.0f ? 200.0f : w);
+    }
+    static SkelBone from_rig(Vec3 pos, Vec3 rot_deg, float length, float width, uint32_t parent = B32_BONE_NONE) {
+        SkelBone b; b.pos = pos; b.length = length; b.width = display_width(length, width); b.parent = parent;
+        const float k = 3.14159265358979323846f / 180.0f;
+        const float ax = rot_deg.x * k, az = rot_deg.z * k;
+        b.cos_x = std::cos(ax); b.sin_x = std::sin(ax); b.cos_z = std::cos(az); b.sin_z = std::sin(az);
+        return b;
+    }
+    B32SkelBone pack() const { return B32SkelBone{ { pos.x, pos.y, pos.z }, cos_x, sin_x, cos_z, sin_z, length, width, parent }; }
+};
+inline std::vector<B32SkelBone> pack_skeleton(const std::vector<SkelBone>& bones) {
+    std::vector<B32SkelBone> tab; tab.reserve(bones.size());
+    for (const auto& b : bones) tab.push_back(b.pack());
+    return tab;
+}
+// B32SkeletonStyle with nothing selected or hovered: skeleton_to_triangles at this alpha
+inline B32SkeletonStyle skeleton_style(uint8_t editor_alpha = 255, uint32_t mode = 0) {
+    B32SkeletonStyle s{}; s.selected_bone = s.hovered_bone = s.hovered_tip = -1; s.mode = mode; s.editor_alpha = editor_alpha;
+    return s;
+}
+inline void ResidentMesh::build_skeleton(const std::vector<SkelBone>& bones, const B32SkeletonStyle& style) {
+    const std::vector<B32SkelBone> tab = pack_skeleton(bones);
+    check(b32_scene_build_skeleton(ctx_, slot_, tab.data(), (uint32_t)tab.size(), &style), "scene_build_skeleton");
+}
+// draw_skeleton's hierarchy lines followed by draw_bone_dots' circles (skeleton.rs:70-79, :110-143) as world items, for draw_world
+inline std::vector<B32WorldItem> skeleton_items(const std::vector<SkelBone>& bones, const B32SkeletonStyle& style) {
+    const std::vector<B32SkelBone> tab = pack_skeleton(bones);
+    uint32_t n = 0;
+    check(b32_skeleton_items(tab.data(), (uint32_t)tab.size(), &style, nullptr, 0, &n), "skeleton_items");
+    std::vector<B32WorldItem> out(n);
+    check(b32_skeleton_items(tab.data(), (uint32_t)tab.size(), &style, out.data(), n, &n), "skeleton_items");
+    return out;
 }
 struct MeshParams { float ambient; bool backface_cull, backface_wireframe; Fog fog; std::optional<Placement> placement = std::nullopt; };
 

@@ -208,6 +208,223 @@ def pose_vertices(vertices, bone_of_vertex, bones):
     return v
 
 
+# ---- the bone octahedra (b32_scene_build_skeleton, b32_skeleton_items): skeleton_to_triangles / draw_skeleton / draw_bone_dots
+class SkelBone:
+    """What the reference reads per bone when it draws the skeleton (modeler/skeleton.rs:412-477, state.rs:2629-2638): the position of
+    get_bone_world_transform(i), cos / sin of the WORLD rotation's .x and .z in radians (always read: get_bone_tip_position has no early
+    return), length, width = display_width() and the parent (None: a root).  SkelBone.from_rig(pos, rot_deg, length, width, parent) takes
+    to_radians as x * f32(pi / 180), cos / sin in f32 and resolves display_width (state.rs:369-375: width > 0 ? width :
+    (length * 0.15).clamp(20, 200)).  SkelBone(pos, cos_x=..., ...) takes the caller's own libm values, as Bone does."""
+
+    def __init__(self, pos=(0.0, 0.0, 0.0), cos_x=1.0, sin_x=0.0, cos_z=1.0, sin_z=0.0, length=20.0, width=40.0, parent=None):
+        f32 = np.float32
+        self.pos = tuple(f32(x) for x in pos)
+        self.cos_x, self.sin_x, self.cos_z, self.sin_z = f32(cos_x), f32(sin_x), f32(cos_z), f32(sin_z)
+        self.length, self.width = f32(length), f32(width)
+        self.parent = None if parent is None or parent < 0 else int(parent)
+
+    @staticmethod
+    def display_width(length, width):
+        f32 = np.float32
+        length, width = f32(length), f32(width)
+        if width > f32(0.0):
+            return width
+        with np.errstate(all="ignore"):
+            w = length * f32(0.15)
+        return f32(20.0) if w < f32(20.0) else (f32(200.0) if w > f32(200.0) else w)        # f32::clamp: a NaN stays
+
+    @classmethod
+    def from_rig(cls, pos, rot_deg, length, width, parent=None):
+        f32 = np.float32
+        with np.errstate(all="ignore"):
+            ax, az = f32(rot_deg[0]) * _RADS_PER_DEG, f32(rot_deg[2]) * _RADS_PER_DEG
+            return cls(pos, cos_x=np.cos(ax), sin_x=np.sin(ax), cos_z=np.cos(az), sin_z=np.sin(az), length=length,
+                       width=cls.display_width(length, width), parent=parent)
+
+    def record(self):
+        r = np.zeros((), abi.SKEL_BONE_DTYPE)
+        r["pos"] = self.pos
+        r["cos_x"], r["sin_x"], r["cos_z"], r["sin_z"] = self.cos_x, self.sin_x, self.cos_z, self.sin_z
+        r["length"], r["width"] = self.length, self.width
+        r["parent"] = abi.BONE_NONE if self.parent is None else self.parent
+        return r
+
+
+def pack_skel_bones(bones):
+    """A skeleton as a contiguous abi.SKEL_BONE_DTYPE array: from such an array, or from a sequence of SkelBone."""
+    if isinstance(bones, np.ndarray) and bones.dtype == abi.SKEL_BONE_DTYPE:
+        return np.ascontiguousarray(bones).reshape(-1)
+    out = np.zeros(len(bones), abi.SKEL_BONE_DTYPE)
+    for i, b in enumerate(bones):
+        out[i] = b.record()
+    return out
+
+
+class SkeletonStyle:
+    """The editor state the skeleton's colours depend on: selected_bone / hovered_bone / hovered_tip (None: none), editor_alpha, mode
+    (abi.SKELETON_TRIANGLES: skeleton_to_triangles; abi.SKELETON_FROM_BONES: skeleton_to_triangles_from_bones -- root / default colours,
+    editor_alpha on every bone, no preview) and the creation preview as (start, end) or None."""
+
+    def __init__(self, selected_bone=None, hovered_bone=None, hovered_tip=None, editor_alpha=255, mode=abi.SKELETON_TRIANGLES, preview=None):
+        self.selected_bone, self.hovered_bone, self.hovered_tip = selected_bone, hovered_bone, hovered_tip
+        self.editor_alpha, self.mode, self.preview = int(editor_alpha), int(mode), preview
+
+    def pack(self):
+        r = np.zeros(1, abi.SKELETON_STYLE_DTYPE)
+        for k in ("selected_bone", "hovered_bone", "hovered_tip"):
+            v = getattr(self, k)
+            r[k] = -1 if v is None or v < 0 else v
+        r["mode"], r["editor_alpha"] = self.mode, self.editor_alpha
+        if self.preview is not None:
+            r["has_preview"] = 1
+            r["preview_start"], r["preview_end"] = np.asarray(self.preview[0], np.float32), np.asarray(self.preview[1], np.float32)
+        return r
+
+
+class SkeletonMirror:
+    """skeleton_to_triangles, skeleton_to_triangles_from_bones, draw_skeleton and draw_bone_dots in numpy float32, one separately
+    rounded operation at a time in the reference's order: what b32_scene_build_skeleton leaves behind a slot's body and what
+    b32_skeleton_items returns.  The rules are methods and attributes so that a test can change one of them and watch a case move."""
+    f32 = np.float32
+    DEGENERATE, UP_LIMIT, RING_AT, DEFAULT_WIDTH, DIM_ALPHA = np.float32(0.001), np.float32(0.9), np.float32(0.2), np.float32(40.0), 30
+    COLOURS = {"default": (200, 200, 200), "selected": (80, 255, 80), "hovered": (100, 180, 255), "tip_hovered": (255, 180, 80),
+               "root": (255, 220, 100), "creating": (255, 150, 50), "hierarchy_line": (100, 100, 100)}
+    DOTS = {"tip": (5, (220, 220, 230)), "tip_selected": (8, (80, 255, 80)), "tip_hovered": (11, (255, 180, 80)),
+            "base": (5, (150, 150, 160)), "base_selected": (8, (80, 255, 80)), "base_hovered": (11, (100, 180, 255))}
+    RING = ((0, 1), (1, 1), (0, -1), (1, -1))                   # ring[i] = centre + sign * perp[which] * width
+    DOT_ORDER = ("tip", "base")
+
+    # -- Vec3 (math.rs:23-49)
+    def length(self, v):
+        return np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+
+    def normalize(self, v):
+        l = self.length(v)
+        if l == 0.0:
+            return [self.f32(0.0)] * 3
+        return [v[0] / l, v[1] / l, v[2] / l]
+
+    @staticmethod
+    def cross(a, b):
+        return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+    # -- the rules
+    def tip(self, b):
+        """get_bone_tip_position, state.rs:2629-2638"""
+        d = self.normalize([b["sin_z"] * b["cos_x"], b["cos_z"] * b["cos_x"], -b["sin_x"]])
+        return [b["pos"][k] + d[k] * b["length"] for k in range(3)]
+
+    def degenerate(self, length):
+        return length < self.DEGENERATE
+
+    def y_up(self, dir_y):
+        return abs(dir_y) < self.UP_LIMIT
+
+    def dimmed(self, style, i):
+        return style.selected_bone is not None and style.selected_bone >= 0 and style.selected_bone != i
+
+    def bone_style(self, style, i, root):
+        """(rgb, alpha) of bone i, skeleton.rs:430-454 / :546-550"""
+        plain = self.COLOURS["root" if root else "default"]
+        if style.mode != abi.SKELETON_TRIANGLES:
+            return plain, style.editor_alpha
+        if style.selected_bone == i:
+            rgb = self.COLOURS["selected"]
+        elif style.hovered_tip == i:
+            rgb = self.COLOURS["tip_hovered"]
+        elif style.hovered_bone == i:
+            rgb = self.COLOURS["hovered"]
+        else:
+            rgb = plain
+        return rgb, (min(style.editor_alpha, self.DIM_ALPHA) if self.dimmed(style, i) else style.editor_alpha)
+
+    def octahedron(self, base, tip, width, rgb, alpha, v_start):
+        """generate_bone_octahedron, skeleton.rs:565-660: (6 vertices, 8 faces) or None"""
+        f32 = self.f32
+        direction = [tip[k] - base[k] for k in range(3)]
+        length = self.length(direction)
+        if self.degenerate(length):
+            return None
+        inv = f32(1.0) / length
+        dn = [direction[k] * inv for k in range(3)]
+        up = [f32(0.0), f32(1.0), f32(0.0)] if self.y_up(dn[1]) else [f32(1.0), f32(0.0), f32(0.0)]
+        perp1 = self.normalize(self.cross(dn, up))
+        perp2 = self.normalize(self.cross(dn, perp1))
+        along = length * f32(self.RING_AT)
+        centre = [base[k] + dn[k] * along for k in range(3)]
+        perps = (perp1, perp2)
+        ring = [[centre[k] + perps[which][k] * width if sign > 0 else centre[k] - perps[which][k] * width for k in range(3)] for which, sign in self.RING]
+        v = np.zeros(6, abi.VERTEX_DTYPE)
+        v["pos"][0], v["normal"][0] = base, [dn[k] * f32(-1.0) for k in range(3)]
+        v["pos"][1], v["normal"][1] = tip, dn
+        for i in range(4):
+            v["pos"][2 + i], v["normal"][2 + i] = ring[i], self.normalize([ring[i][k] - centre[k] for k in range(3)])
+        v["r"], v["g"], v["b"] = rgb
+        f = np.zeros(8, abi.FACE_DTYPE)
+        for i in range(4):
+            nxt = (i + 1) % 4
+            f["v"][i] = (v_start, v_start + 2 + i, v_start + 2 + nxt)
+            f["v"][4 + i] = (v_start + 1, v_start + 2 + nxt, v_start + 2 + i)
+        f["texture_id"], f["blend_mode"], f["editor_alpha"] = abi.NO_TEXTURE, abi.OPAQUE, alpha
+        return v, f
+
+    def mesh(self, bones, style, vertex_offset=0):
+        """(vertices, faces) of the tail: abi.VERTEX_DTYPE / abi.FACE_DTYPE, face indices from vertex_offset on."""
+        tab = pack_skel_bones(bones)
+        vs, fs = [], []
+        at = int(vertex_offset)
+        with np.errstate(all="ignore"):
+            octs = [(b["pos"], self.tip(b), b["width"]) + self.bone_style(style, i, b["parent"] == abi.BONE_NONE) for i, b in enumerate(tab)]
+            if style.mode == abi.SKELETON_TRIANGLES and style.preview is not None:
+                octs.append((np.asarray(style.preview[0], np.float32), np.asarray(style.preview[1], np.float32), self.DEFAULT_WIDTH,
+                             self.COLOURS["creating"], 255))
+            for base, tip, width, rgb, alpha in octs:
+                o = self.octahedron([self.f32(x) for x in base], [self.f32(x) for x in tip], self.f32(width), rgb, alpha, at)
+                if o is not None:
+                    vs.append(o[0]); fs.append(o[1]); at += 6
+        v = np.concatenate(vs) if vs else np.zeros(0, abi.VERTEX_DTYPE)
+        f = np.concatenate(fs) if fs else np.zeros(0, abi.FACE_DTYPE)
+        for k in ("pos", "normal"):                                 # the one departure: a NaN is the quiet NaN 0x7FC00000
+            w = v[k].view(np.uint32)
+            w[np.isnan(v[k])] = 0x7FC00000
+        return v, f
+
+    def items(self, bones, style):
+        """The calls of draw_skeleton (skeleton.rs:70-79) and then of draw_bone_dots (:110-143) as abi.WORLD_ITEM_DTYPE items."""
+        tab = pack_skel_bones(bones)
+        rows = []                                                   # (kind, p0, p1, size, rgb, flags)
+        zero = np.zeros(3, np.float32)
+        for i, b in enumerate(tab):
+            if b["parent"] != abi.BONE_NONE:
+                rows.append((abi.LINE_2D, tab[b["parent"]]["pos"] if b["parent"] < len(tab) else zero, b["pos"], 0, self.COLOURS["hierarchy_line"], abi.WORLD_CLIP_NEAR))
+        with np.errstate(all="ignore"):
+            for i, b in enumerate(tab):
+                for what in self.DOT_ORDER:
+                    if what == "tip":
+                        key = "tip_hovered" if style.hovered_tip == i else ("tip_selected" if style.selected_bone == i else "tip")
+                        p = np.array(self.tip(b), np.float32)
+                    else:
+                        key = "base_hovered" if style.hovered_bone == i else ("base_selected" if style.selected_bone == i else "base")
+                        p = b["pos"]
+                    rows.append((abi.PRIM_CIRCLE, p, zero, self.DOTS[key][0], self.DOTS[key][1], 0))
+        items = np.zeros(len(rows), abi.WORLD_ITEM_DTYPE)
+        for k, (kind, p0, p1, size, rgb, flags) in enumerate(rows):
+            items[k]["p0"], items[k]["p1"], items[k]["size"], items[k]["kind"], items[k]["flags"] = p0, p1, size, kind, flags
+            items[k]["r"], items[k]["g"], items[k]["b"] = rgb
+        items["alpha"] = 255
+        return items
+
+
+def skeleton_mesh(bones, style, vertex_offset=0):
+    """SkeletonMirror().mesh: the tail b32_scene_build_skeleton writes behind a body of vertex_offset vertices."""
+    return SkeletonMirror().mesh(bones, style, vertex_offset)
+
+
+def skeleton_items(bones, style):
+    """SkeletonMirror().items: what b32_skeleton_items returns, for Framebuffer.draw_world."""
+    return SkeletonMirror().items(bones, style)
+
+
 def _placement_triple(placement):
     """(cos_f, sin_f, world_pos) as f32 of a Placement, an abi.B32Placement or such a triple.  Picking always applies the placement
     (viewport_3d.rs:7716-7718 has no has_transform shortcut), so Placement.has_transform is not consulted."""
@@ -1675,7 +1892,7 @@ class Context:
         (default: the uploaded scene's), the topology's polygon count in mode BOX_POLYGONS."""
         args, _keep = self._mesh_args(scene, topology, camera, ortho, placement)
         prm = self._box_params(rect, mode)
-        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_vertices) if n_elements is None else n_elements
+        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_body_vertices) if n_elements is None else n_elements
         words = np.zeros((n + 31) // 32, np.uint32)
         cnt = C.c_uint32()
         _chk(self.lib.b32_box_select(*args, prm.ctypes.data, words.ctypes.data if len(words) else None, C.byref(cnt)), "b32_box_select")
@@ -1685,7 +1902,7 @@ class Context:
         """b32_box_select_async -> (ticket, BoxResult); out as for hover_mesh_async, of at least 16 + 4 * ceil(n_elements / 32) bytes."""
         args, _keep = self._mesh_args(scene, topology, camera, ortho, placement)
         prm = self._box_params(rect, mode)
-        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_vertices) if n_elements is None else n_elements
+        n = (topology.np if mode == abi.BOX_POLYGONS else scene.n_body_vertices) if n_elements is None else n_elements
         need = abi.BOX_HEADER_BYTES + 4 * ((n + 31) // 32)
         own = out is None
         arr, ptr = self.host_alloc(need) if own else out
@@ -2173,7 +2390,7 @@ class Framebuffer:
 
     def mesh_overlay_project_batch(self, scene, topology, overlay, camera: T.Camera, ortho=None, selected=None, width=None, height=None):
         """b32_mesh_overlay_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_mesh_overlay hands to the tile pass."""
-        n = mesh_overlay_record_count(topology, scene.n_vertices, overlay, selected)
+        n = mesh_overlay_record_count(topology, scene.n_body_vertices, overlay, selected)
         out = np.zeros(n, abi.PRIM_DTYPE)
         got = C.c_uint32()
         args, _keep = self._overlay_args(scene, topology, overlay, camera, ortho, selected)
@@ -2905,6 +3122,24 @@ class ResidentScene:
         self._packed = None
         self._slot = None
 
+    # n_vertices / n_faces are what the slot holds and draws; assigning them (an upload, Room.build_mesh) names a new body and drops
+    # the tail of bone octahedra, as the library does
+    @property
+    def n_vertices(self):
+        return self.n_body_vertices + self._tail_v
+
+    @n_vertices.setter
+    def n_vertices(self, n):
+        self.n_body_vertices, self._tail_v = int(n), 0
+
+    @property
+    def n_faces(self):
+        return self.n_body_faces + self._tail_f
+
+    @n_faces.setter
+    def n_faces(self, n):
+        self.n_body_faces, self._tail_f = int(n), 0
+
     def detach(self):
         """Move this scene into its own slot (b32_scene_swap) so that other scenes can be uploaded and drawn through the same context:
         every later render*/render_async swaps it in, enqueues, and swaps it out again -- no upload, no host sync."""
@@ -2932,7 +3167,7 @@ class ResidentScene:
         """b32_scene_set_rig: the vertices as they are now become the rest pose; bone_of_vertex has one index per vertex (abi.BONE_NONE:
         no bone), resolved by the caller (v.bone_index.or(obj.default_bone_index))."""
         bo = np.ascontiguousarray(bone_of_vertex, np.uint16).reshape(-1)
-        if len(bo) != self.n_vertices:
+        if len(bo) != self.n_body_vertices:
             raise ValueError("set_rig: one bone index per vertex")
         _chk(self.ctx.lib.b32_scene_set_rig(self.ctx.h, self._handle(), abi.ptr(bo) if len(bo) else None), "scene_set_rig")
 
@@ -2941,6 +3176,19 @@ class ResidentScene:
         vertices come back)."""
         tab = pack_bones(bones)
         _chk(self.ctx.lib.b32_scene_pose(self.ctx.h, self._handle(), abi.ptr(tab) if len(tab) else None, len(tab)), "scene_pose")
+
+    def build_skeleton(self, bones, style=None):
+        """b32_scene_build_skeleton: enqueue one kernel that replaces the slot's tail with the octahedra of this skeleton (a sequence of
+        SkelBone or an abi.SKEL_BONE_DTYPE array; empty and no preview: the tail goes).  n_vertices / n_faces are the slot's totals
+        afterwards, n_body_vertices / n_body_faces what the upload left: rig, pose, hover, box selection, pick and the selection overlays
+        see the body only."""
+        tab = pack_skel_bones(bones)
+        st = (style or SkeletonStyle()).pack()
+        nv, nf = C.c_uint32(0), C.c_uint32(0)
+        args = (abi.ptr(tab) if len(tab) else None, len(tab), abi.ptr(st))
+        _chk(self.ctx.lib.b32_skeleton_counts(*args, C.byref(nv), C.byref(nf)), "skeleton_counts")
+        _chk(self.ctx.lib.b32_scene_build_skeleton(self.ctx.h, self._handle(), *args), "scene_build_skeleton")
+        self._tail_v, self._tail_f = nv.value, nf.value
 
     def read_vertices(self, first=0, count=None):
         """b32_scene_read_vertices (blocking): the slot's vertices as they are on the device now."""

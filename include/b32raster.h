@@ -384,6 +384,78 @@ int b32_scene_set_rig(b32_ctx* ctx, b32_scene* slot /* NULL: the context's resid
 int b32_scene_pose(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, const B32Bone* bones, uint32_t n_bones);
 int b32_scene_read_vertices(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t first, uint32_t count, B32Vertex* out);  /* blocking */
 
+/* ---- the bone octahedra: a mesh tail built on the device from the bone table -------------------------------------------------------
+ * The modeler draws ONE combined mesh per frame: every object's faces and, while bones are shown, the eight faces per bone of
+ * skeleton_to_triangles (modeler/skeleton.rs:412-477, :565-660), appended before its single render_mesh_15 / render_mesh call
+ * (modeler/viewport.rs:1196-1395).  Painter's order, the order of equal keys and the editor-alpha blend run over that one list, so a
+ * skeleton drawn as a second mesh is another frame.  Here a slot's geometry is a BODY -- what an upload or b32_room_build_mesh left --
+ * plus a TAIL: 6 vertices and 8 faces per drawn bone, in bone order, the creation preview last, written by one kernel from the table.
+ *
+ * B32SkelBone is what the reference reads per bone, libm kept on the host: pos = get_bone_world_transform(i).0; cos / sin of the WORLD
+ * rotation's .x / .z .to_radians() (always read: get_bone_tip_position has no early return); length; width = display_width() as the
+ * host resolved it (state.rs:369-375); parent: B32_BONE_NONE marks a root (only the colour depends on it here; b32_skeleton_items reads
+ * the parent's position, (0, 0, 0) for an index >= n as get_bone_world_transform answers out of range).
+ * B32SkeletonStyle is the editor state: selected_bone / hovered_bone / hovered_tip (negative: none), editor_alpha, mode 0 =
+ * skeleton_to_triangles, mode 1 = skeleton_to_triangles_from_bones (root / default colours only, editor_alpha on every bone, no
+ * preview); has_preview with preview_start / preview_end = bone_creation (colour `creating`, alpha 255, width DEFAULT_WIDTH = 40).
+ *
+ * Per bone, every operation a separately rounded f32 operation in the reference's order (csrc/b32_skeleton_body.h):
+ *     tip = pos + Vec3(sin_z*cos_x, cos_z*cos_x, -sin_x).normalize() * length      (state.rs:2629-2638)
+ *   Vec3::normalize (math.rs:39-49) is ZERO for len == 0.0, else three divisions by len = sqrt((x*x + y*y) + z*z).
+ *   direction = tip - pos; length = direction.len(); length < 0.001 -> nothing (a NaN is not < and is drawn).
+ *   dir_norm = direction * (1.0 / length); up = +Y while |dir_norm.y| < 0.9, else +X; perp1 = cross(dir_norm, up).normalize(),
+ *   perp2 = cross(dir_norm, perp1).normalize(); ring_center = pos + dir_norm * (length * 0.2); ring = center + perp1*w, + perp2*w,
+ *   - perp1*w, - perp2*w.  Vertices: base (normal dir_norm * -1.0), tip (dir_norm), the ring ((ring[i] - center).normalize()); uv (0, 0),
+ *   the bone's colour.  Faces: (0, 2+i, 2+next) for i = 0..3, then (1, 2+next, 2+i); no texture, Opaque, black_transparent 0,
+ *   editor_alpha = the bone's alpha.  Colour: selected > tip-hovered > hovered > root > default; while a bone is selected every other bone
+ *   has alpha editor_alpha.min(30).  One departure from the reference's bits: a float that is a NaN is written as 0x7FC00000.
+ *
+ * b32_scene_build_skeleton   replaces the tail of `slot` (NULL: the context's resident scene).  The host copies the table, computes each
+ *     tip and decides liveness there, once, with the text above; the drawn octahedra travel by value in the launch, in order, so the
+ *     device never decides a second time where an octahedron lies.  One kernel on the context's stream: one workgroup of 64 lanes per
+ *     drawn octahedron (at most 65 workgroups), of which 14 lanes work, one per output element (6 vertices, 8 faces), and 50 idle -- the
+ *     octahedron's record is then read from the kernel argument by the workgroup's index, with scalar loads.  No upload and no host
+ *     synchronisation unless the slot's buffers must grow (then the body is kept by a copy on the device and the stream is waited for
+ *     once).  Face indices are absolute: the first tail vertex is the body's vertex count.
+ *     n_bones == 0 without a preview removes the tail.  An empty body (nv == nf == 0) is legal: the model browser's skeleton mesh.
+ *     Like b32_scene_pose it first settles a pending frame that may still be redrawn, and the scene's content counts as changed.
+ *     Works for RGB555 and 8-bit-colour scenes; a tail face with alpha < 255 is a transparent-pass face like an uploaded one.
+ *   The tail is DRAWN and never QUERIED.  Frames, merged runs of b32_frame_add_scene, placed draws, the wireframe phases and b32_last_*
+ *   see body + tail; b32_scene_read_vertices / _read_faces read body + tail.  b32_scene_set_rig, b32_scene_pose, b32_hover_mesh,
+ *   b32_box_select (its result size too), b32_pick_meshes and b32_draw_mesh_overlay / _project_batch see the BODY only: the reference
+ *   skins, hovers, selects and overlays mesh objects, and skeleton vertices have bone_index None.  A pose after a build leaves the tail's
+ *   bits alone and a build after a pose the body's.  Any b32_scene_upload* or b32_room_build_mesh into the slot drops the tail, as it
+ *   drops the rig; b32_scene_swap carries it.
+ * b32_skeleton_counts   host only: the tail's vertex and face counts for this table and style (6 and 8 per drawn octahedron).
+ * b32_skeleton_items    host only, like b32_floor_grid_items: the calls of draw_skeleton (skeleton.rs:70-79: per bone with a parent one
+ *     B32_LINE_2D item with B32_WORLD_CLIP_NEAR from the parent's position to the bone's, colour (100, 100, 100)) followed by those of
+ *     draw_bone_dots (:110-143: per bone the tip circle, then the base circle; radius 11 / 8 / 5 and colour by tip-hovered / selected /
+ *     neither, resp. hovered / selected / neither), for b32_draw_world.  The tip is the octahedron's tip vertex, bit for bit.  *n_out = the
+ *     number of items; at most `cap` are written (out may be NULL).
+ * Errors: NULL context or style, a slot (or context) without a scene, NULL bones with n_bones > 0, mode > 1 -> B32_E_ARG;
+ * n_bones > B32_MAX_BONES -> B32_E_UNSUPPORTED. */
+typedef struct B32SkelBone {        /* 40 bytes */
+    float pos[3];                   /* get_bone_world_transform(i).0 */
+    float cos_x, sin_x, cos_z, sin_z;   /* of the world rotation's .x / .z .to_radians() */
+    float length;
+    float width;                    /* display_width() */
+    uint32_t parent;                /* B32_BONE_NONE: a root */
+} B32SkelBone;
+typedef struct B32SkeletonStyle {   /* 44 bytes */
+    int32_t selected_bone, hovered_bone, hovered_tip;     /* negative: none */
+    uint32_t mode;                  /* 0: skeleton_to_triangles; 1: skeleton_to_triangles_from_bones */
+    uint8_t editor_alpha;
+    uint8_t has_preview;            /* mode 0: bone_creation is Some */
+    uint8_t _pad[2];
+    float preview_start[3], preview_end[3];
+} B32SkeletonStyle;
+int b32_scene_build_skeleton(b32_ctx* ctx, b32_scene* slot /* NULL: the context's resident scene */, const B32SkelBone* bones, uint32_t n_bones,
+                             const B32SkeletonStyle* style);
+int b32_skeleton_counts(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, uint32_t* n_vertices, uint32_t* n_faces);
+struct B32WorldItem;
+int b32_skeleton_items(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, struct B32WorldItem* out, uint32_t cap,
+                       uint32_t* n_out);
+
 /* ---- a frame of several meshes (scene.rs:112-261) -------------------------------------------------------------------------------
  * The console's render step is one render_mesh_15 call per room and per asset part onto the same framebuffer, with ONE camera and
  * light list per frame and per-mesh ambient, fog (per room, scene.rs:189-205) and backface culling (per part: double_sided,
