@@ -149,6 +149,10 @@ BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("
 assert BONE_DTYPE.itemsize == 32
 BONE_NONE = 0xFFFF
 MAX_BONES = 64
+# B32VertexPatch / B32FacePatch (b32_scene_patch_vertices / _faces): the element's index, then the whole record
+VERTEX_PATCH_DTYPE = np.dtype([("index", "<u4"), ("v", VERTEX_DTYPE)])
+FACE_PATCH_DTYPE = np.dtype([("index", "<u4"), ("f", FACE_DTYPE)])
+assert VERTEX_PATCH_DTYPE.itemsize == 40 and FACE_PATCH_DTYPE.itemsize == 24
 # B32SkelBone / B32SkeletonStyle (b32_scene_build_skeleton, b32_skeleton_items): what the bone octahedra read per bone, and the editor state
 SKEL_BONE_DTYPE = np.dtype([("pos", "<f4", 3), ("cos_x", "<f4"), ("sin_x", "<f4"), ("cos_z", "<f4"), ("sin_z", "<f4"), ("length", "<f4"),
                             ("width", "<f4"), ("parent", "<u4")])
@@ -251,6 +255,11 @@ SYMBOLS = [
     ("b32_scene_set_rig", C.c_int, [_P, _P, _P]),
     ("b32_scene_pose", C.c_int, [_P, _P, _P, C.c_uint32]),
     ("b32_scene_read_vertices", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_scene_patch_vertices", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("b32_scene_patch_faces", C.c_int, [_P, _P, _P, C.c_uint32]),
+    ("b32_scene_patch_texels", C.c_int, [_P, _P] + [C.c_uint32] * 5 + [_P, C.c_uint32]),
+    ("b32_scene_patch_indexed", C.c_int, [_P, _P] + [C.c_uint32] * 5 + [_P, C.c_uint32, _P, C.c_uint32]),
+    ("b32_scene_read_texels", C.c_int, [_P, _P, C.c_uint32, _P]),
     ("b32_scene_build_skeleton", C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     ("b32_skeleton_counts", C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("b32_skeleton_items", C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),

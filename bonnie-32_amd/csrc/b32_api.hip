@@ -62,7 +62,7 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : { c->ev_main, c->ev_wbin }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release();
+    c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release(); c->patch.release();
     for (ArmedWords* w : { &c->world_counts, &c->gizmo_counts, &c->pick_words, &c->hover_bits, &c->hover_words, &c->room_words, &c->room_points })
         if (w->p) (void)hipFree(w->p);
     for (EventPair* t : { &c->world_timer, &c->pick_timer, &c->hover_timer }) t->destroy();

@@ -462,6 +462,14 @@ void launch_pack_streams(hipStream_t s, const B32Vertex* verts, uint32_t nv, flo
 // bones (b32_pose.hip): the slot's positions and normals into its rest stream; rest stream + bone table -> the slot's vertices
 void launch_pose_rest(hipStream_t s, const B32Vertex* verts, uint32_t nv, float* rest);
 void launch_pose(hipStream_t s, const float* rest, const uint16_t* bone_of, B32Vertex* verts, uint32_t nv, const B32Bone* bones, uint32_t n_bones);
+// in-place edits of a resident scene (b32_patch.hip; the lanes' work is in b32_patch_body.h): n staged records scattered into the
+// slot's vertices (rest != nullptr: a rigged slot, records in rest space, posed with the table) or faces; a staged rectangle into the pool
+struct PatchRect;
+void launch_patch_vertices(hipStream_t s, const uint32_t* recs, uint32_t n, B32Vertex* verts, float* rest, const uint16_t* bone_of, const B32Bone* bones, uint32_t n_bones);
+void launch_patch_faces(hipStream_t s, const uint32_t* recs, uint32_t n, B32Face* faces);
+void launch_patch_texels(hipStream_t s, const PatchRect& r, const void* src, uint16_t* pool15, uint32_t* pool32);
+// (src: PATCH_CLUT_ENTRIES Color15, zero behind the palette, then the packed index bytes; atlas != nullptr: the kept CLUT + index atlas)
+void launch_patch_indexed(hipStream_t s, const PatchRect& r, const void* src, uint32_t clut_len, uint16_t* pool15, uint8_t* atlas, bool write_clut);
 // the bone octahedra (b32_skeleton.hip): n_octs drawn octahedra (b32_skeleton_body.h) -> 6 vertices from verts[first_vertex] and 8 faces
 // from faces[first_face] each, and the scene's face count into consts[0]
 struct SkelOct;

@@ -9,6 +9,7 @@
 #pragma once
 #include "b32_device.h"
 #include "b32_frame_plan.h"
+#include "b32_patch_tally.h"
 #include <algorithm>
 #include <cstdio>
 #include <chrono>
@@ -128,6 +129,15 @@ struct b32_scene {
     // reads body_nv() / body_nf().  While there is a tail, body_* hold the blend bookkeeping of the body alone (the scene's own values
     // are body + tail).  Part of the scene's content: swapped with it, dropped by every upload and by b32_room_build_mesh
     uint32_t tail_v = 0, tail_f = 0, body_blend_faces = 0; bool body_may_blend = false, body_blend8 = false;
+    // in-place edits (b32_scene_patch_*, b32_patch.hip): what they need of the slot on the host.  h_bones: the table of the last
+    // b32_scene_pose (empty before the first one and after b32_scene_set_rig), with which a patched rest vertex is posed.  h_faces: the
+    // body's faces, fetched by the first face patch after an upload or b32_room_build_mesh (one synchronisation) and kept up to date, and
+    // their tally.  h_texels32: the Color pool of an 8-bit-colour scene, fetched by its first texel patch, and how many of its texels
+    // blend (blend_texels8).  h_clut: the kept CLUT of an index atlas (atlas_idx_bytes != 0), 256 entries
+    std::vector<B32Bone> h_bones;
+    std::vector<B32Face> h_faces; bool h_faces_valid = false; b32::FaceTally tally;
+    std::vector<uint32_t> h_texels32; bool h_texels32_valid = false; size_t blend_texel_count = 0;
+    std::vector<uint16_t> h_clut;
     uint32_t body_nv() const { return nv - tail_v; }
     uint32_t body_nf() const { return nf - tail_f; }
     // The only list of a scene's device buffers (the caller has drained the streams that use them).
@@ -253,6 +263,7 @@ struct b32_ctx {
     // batch); drawn / dropped / rejected on the device; HIP events around the last projection kernel enqueued while profiling was on
     // (b32_last_kernel_times "world_project")
     Staged<B32WorldItem> world;
+    Staged<uint32_t> patch;                                       // b32_scene_patch_*: the records' (or the rectangle's) pinned ring and device copy, in dwords
     ArmedWords world_counts;
     unsigned long long world_tile_batches = 0, world_scan_batches = 0;
     EventPair world_timer;

@@ -317,6 +317,7 @@ int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
     sc->nv = nv; sc->nf = nf;
     sc->have_rig = false;
     sc->tail_v = 0; sc->tail_f = 0;
+    sc->h_faces_valid = false;                          // (a face patch fetches the new faces)
     sc->local_sort_ok = true;
     sc->pos_valid = false; sc->lit_valid = false; sc->band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;

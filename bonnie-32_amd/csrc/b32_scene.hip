@@ -98,6 +98,7 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
     c->scene.nv = nv; c->scene.nf = nf;
     c->scene.have_rig = false;                          // (the rig belongs to the vertices it was set for)
     c->scene.tail_v = 0; c->scene.tail_f = 0;           // (... and so do the bone octahedra behind them)
+    c->scene.h_faces_valid = false;                     // (... and the host copy a face patch keeps)
     c->scene.local_sort_ok = true;
     c->scene.pos_valid = false; c->scene.lit_valid = false; c->scene.band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;
@@ -120,6 +121,7 @@ static int layout_textures(b32_ctx* c, uint32_t nt, const uint32_t* w, const uin
     c->scene.h_tex.resize(nt);
     c->scene.tex_blend_any = false;
     c->scene.atlas_idx_bytes = 0;                         // (only b32_scene_upload_indexed with one texture keeps the index atlas)
+    c->scene.h_texels32_valid = false;                    // (the pool is rewritten: a texel patch of an 8-bit-colour scene fetches it again)
     size_t off = 0;
     for (uint32_t i = 0; i < nt; ++i) {
         if (w[i] > 65535 || h[i] > 65535) return B32_E_ARG;
@@ -278,6 +280,8 @@ int b32_scene_upload_indexed(b32_ctx* c, const B32Vertex* v, uint32_t nv, const 
             HIPCHK(c, hipMemsetAsync(c->scene.d_atlas0 + ATLAS_CLUT_BYTES + n, 0, 32, c->stream));      // (the staging copy reads whole 16-byte quads)
             d_clut = reinterpret_cast<uint16_t*>(c->scene.d_atlas0); d_idx = c->scene.d_atlas0 + ATLAS_CLUT_BYTES;
             c->scene.atlas_idx_bytes = (uint32_t)n;
+            c->scene.h_clut.assign(ATLAS_CLUT_BYTES / 2, 0);                                            // (what b32_scene_patch_indexed compares a partial patch's CLUT with)
+            std::copy(tex[i].clut, tex[i].clut + tex[i].clut_len, c->scene.h_clut.begin());
         } else {
             if ((rc = tmp.upload(tex[i].indices, n, &d_idx))) return rc;
             if ((rc = tmp.upload(tex[i].clut, (size_t)tex[i].clut_len, &d_clut))) return rc;
@@ -333,6 +337,7 @@ int b32_scene_set_rig(b32_ctx* c, b32_scene* slot, const uint16_t* bone_of_verte
     (void)hipSetDevice(c->device);
     int rc;
     sc->have_rig = false;
+    sc->h_bones.clear();                                 // (until the next pose the vertices are the rest ones: a patch copies)
     if ((rc = ensure(c, sc->d_rest, sc->cap_rest, (size_t)nv * 6 + 1))) return rc;
     if ((rc = ensure(c, sc->d_bone_of, sc->cap_bone_of, (size_t)nv + 1))) return rc;
     // (on the stream: behind the upload or the pose that wrote the vertices, in front of the next pose)
@@ -361,6 +366,7 @@ int b32_scene_pose(b32_ctx* c, b32_scene* slot, const B32Bone* bones, uint32_t n
     { const int rcs = settle_pending(c); if (rcs) return rcs; }
     launch_pose(c->stream, sc->d_rest, sc->d_bone_of, sc->d_verts, sc->body_nv(), bones, n_bones);
     HIPCHK(c, hipGetLastError());
+    sc->h_bones.assign(bones, bones + n_bones);          // (b32_scene_patch_vertices poses a patched rest vertex with it)
     c->side_dirty = true;
     sc->pos_valid = false; sc->lit_valid = false;       // (frame_positions packs again on the next frame: band_frames stays)
     sc->gen = ++c->gen_counter;                          // a merged run that holds this scene is rebuilt

@@ -403,6 +403,28 @@ public:
         check(b32_scene_read_vertices(ctx_, slot_, first, count, out.data()), "scene_read_vertices");
         return out;
     }
+    std::vector<B32Face> read_faces(uint32_t first, uint32_t count) const {
+        std::vector<B32Face> out(count);
+        check(b32_scene_read_faces(ctx_, slot_, first, count, out.data()), "scene_read_faces");
+        return out;
+    }
+    // In-place edits (b32_scene_patch_*): the mesh stays resident, with its rig, pose and tail, and only the edited elements travel.
+    // Records carry strictly ascending indices below the body's count; on a rigged mesh vertex records are in rest space.  A rectangle's
+    // rows are `stride` elements apart in the caller's array.  Nothing blocks, except that the first face patch after an upload fetches
+    // the faces once.  read_texels() is the blocking read-back of one texture's expanded texels (width * height of them).
+    void patch_vertices(const std::vector<B32VertexPatch>& recs) { check(b32_scene_patch_vertices(ctx_, slot_, recs.data(), (uint32_t)recs.size()), "scene_patch_vertices"); }
+    void patch_faces(const std::vector<B32FacePatch>& recs) { check(b32_scene_patch_faces(ctx_, slot_, recs.data(), (uint32_t)recs.size()), "scene_patch_faces"); }
+    void patch_texels(uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint16_t* texels, uint32_t stride) {
+        check(b32_scene_patch_texels(ctx_, slot_, tex, x, y, w, h, texels, stride), "scene_patch_texels");
+    }
+    void patch_indexed(uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* indices, uint32_t stride, const std::vector<uint16_t>& clut) {
+        check(b32_scene_patch_indexed(ctx_, slot_, tex, x, y, w, h, indices, stride, clut.data(), (uint32_t)clut.size()), "scene_patch_indexed");
+    }
+    std::vector<uint16_t> read_texels(uint32_t tex, uint32_t width, uint32_t height) const {
+        std::vector<uint16_t> out((size_t)width * height);
+        check(b32_scene_read_texels(ctx_, slot_, tex, out.data()), "scene_read_texels");
+        return out;
+    }
 private:
     b32_ctx* ctx_ = nullptr;
     b32_scene* slot_ = nullptr;
@@ -474,6 +496,23 @@ inline std::vector<B32Vertex> pose_vertices(const std::vector<B32Vertex>& vertic
         out.push_back(pose_vertex(vertices[i], b < tab.size() ? &tab[b] : nullptr));
     }
     return out;
+}
+// the host restatement of the in-place edits on the arrays a host keeps: what a patched mesh must be indistinguishable from once these
+// arrays are uploaded afresh.  (On a rigged mesh the vertex records patch the REST vertices, which pose_vertices then poses.)
+inline void patch_vertices(std::vector<B32Vertex>& vertices, const std::vector<B32VertexPatch>& recs) { for (const auto& r : recs) vertices.at(r.index) = r.v; }
+inline void patch_faces(std::vector<B32Face>& faces, const std::vector<B32FacePatch>& recs) { for (const auto& r : recs) faces.at(r.index) = r.f; }
+inline void patch_texels(std::vector<uint16_t>& texels, uint32_t tex_width, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint16_t* src, uint32_t stride) {
+    for (uint32_t row = 0; row < h; ++row)
+        for (uint32_t col = 0; col < w; ++col) texels.at((size_t)(y + row) * tex_width + x + col) = src[(size_t)row * stride + col];
+}
+// Clut::lookup (types.rs:390-397): an index at or past the palette is 0x0000
+inline void patch_indexed(std::vector<uint16_t>& texels, uint32_t tex_width, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* indices, uint32_t stride,
+                          const std::vector<uint16_t>& clut) {
+    for (uint32_t row = 0; row < h; ++row)
+        for (uint32_t col = 0; col < w; ++col) {
+            const size_t k = indices[(size_t)row * stride + col];
+            texels.at((size_t)(y + row) * tex_width + x + col) = k < clut.size() ? clut[k] : (uint16_t)0;
+        }
 }
 inline void ResidentMesh::pose(const std::vector<Bone>& bones) {
     std::vector<B32Bone> tab; tab.reserve(bones.size());

@@ -208,6 +208,99 @@ def pose_vertices(vertices, bone_of_vertex, bones):
     return v
 
 
+# ---- editing a resident scene in place (b32_scene_patch_*): the reference composition in numpy.  The mirrors patch host arrays; what they
+# return is given to the oracle or to a fresh upload, which a patched slot must be indistinguishable from
+def patch_indices(indices, limit):
+    """The `index` column of a patch as the library accepts it: strictly ascending and below `limit`, else ValueError."""
+    idx = np.asarray(indices, np.int64).reshape(-1)
+    if len(idx) and (idx[0] < 0 or idx[-1] >= limit or np.any(np.diff(idx) <= 0)):
+        raise ValueError("patch: indices must be strictly ascending and inside the body")
+    return idx
+
+
+def patch_vertices(vertices, indices, records, rest=None, bone_of_vertex=None, bones=()):
+    """b32_scene_patch_vertices on host arrays.  Without `rest`: a copy of `vertices` with records written at `indices`.  With `rest` (a
+    rigged slot: the (n, 6) float32 rest stream, position then normal): the records are in rest space; returns (vertices, rest) where the
+    rest stream got position and normal and the vertices the records posed by `bones` (pose_vertices; an empty table copies)."""
+    v = np.array(vertices, dtype=abi.VERTEX_DTYPE, copy=True).reshape(-1)
+    idx = patch_indices(indices, len(v))
+    recs = np.asarray(records, abi.VERTEX_DTYPE).reshape(-1)
+    if len(recs) != len(idx):
+        raise ValueError("patch_vertices: one record per index")
+    if rest is None:
+        v[idx] = recs
+        return v
+    r = np.array(rest, dtype=np.float32, copy=True).reshape(-1, 6)
+    r.view(np.uint32)[idx, 0:3] = recs["pos"].view(np.uint32)
+    r.view(np.uint32)[idx, 3:6] = recs["normal"].view(np.uint32)
+    bo = np.asarray(bone_of_vertex).reshape(-1)
+    v[idx] = pose_vertices(recs, bo[idx], bones)
+    return v, r
+
+
+def rest_stream(vertices):
+    """The rest stream b32_scene_set_rig takes from a slot's vertices: (n, 6) float32, position then normal."""
+    v = np.asarray(vertices, abi.VERTEX_DTYPE).reshape(-1)
+    return np.concatenate([v["pos"], v["normal"]], axis=1).astype(np.float32)
+
+
+def patch_faces(faces, indices, records):
+    """b32_scene_patch_faces on a host array: a copy of `faces` with the whole records written at `indices`."""
+    f = np.array(faces, dtype=abi.FACE_DTYPE, copy=True).reshape(-1)
+    idx = patch_indices(indices, len(f))
+    recs = np.asarray(records, abi.FACE_DTYPE).reshape(-1)
+    if len(recs) != len(idx):
+        raise ValueError("patch_faces: one record per index")
+    f[idx] = recs
+    return f
+
+
+def _patch_rect(shape, x, y, block):
+    h, w = block.shape[:2]
+    if h == 0 or w == 0:
+        return None
+    if x < 0 or y < 0 or x + w > shape[1] or y + h > shape[0]:
+        raise ValueError("patch: the rectangle leaves the texture")
+    return slice(y, y + h), slice(x, x + w)
+
+
+def patch_texels(texels, x, y, block):
+    """b32_scene_patch_texels on a host array: `texels` is one texture as (height, width) Color15 or (height, width, 4) Color bytes,
+    `block` the rectangle's texels, (h, w[, 4]); any view will do, its rows need not be contiguous.  Returns the patched copy."""
+    t = np.array(texels, copy=True)
+    block = np.asarray(block, t.dtype)
+    at = _patch_rect(t.shape, x, y, block)
+    if at is not None:
+        t[at] = block
+    return t
+
+
+def clut_lookup(clut, indices):
+    """Clut::lookup (types.rs:390-397) for an array of indices: an index at or past the palette is 0x0000."""
+    clut = np.asarray(clut, np.uint16).reshape(-1)
+    idx = np.asarray(indices, np.int64)
+    pad = np.concatenate([clut, np.zeros(1, np.uint16)])
+    return pad[np.where(idx < len(clut), idx, len(clut))]
+
+
+def patch_indexed(texels, atlas, x, y, index_block, clut):
+    """b32_scene_patch_indexed on host arrays: `texels` (height, width) Color15 and `atlas` (height, width) index bytes of one texture
+    (atlas may be None), `index_block` the rectangle's indices (h, w).  Returns (texels, atlas) patched: the texels get
+    clut_lookup(clut, index_block), the atlas the indices.  (A palette-only change is the whole atlas with the new CLUT.)"""
+    block = np.asarray(index_block, np.uint8)
+    t = patch_texels(np.asarray(texels, np.uint16), x, y, clut_lookup(clut, block))
+    a = None if atlas is None else patch_texels(np.asarray(atlas, np.uint8), x, y, block)
+    return t, a
+
+
+def kept_clut(clut):
+    """The CLUT a slot keeps beside its index atlas: 256 entries, zero behind a shorter palette."""
+    out = np.zeros(256, np.uint16)
+    c = np.asarray(clut, np.uint16).reshape(-1)[:256]
+    out[:len(c)] = c
+    return out
+
+
 # ---- the bone octahedra (b32_scene_build_skeleton, b32_skeleton_items): skeleton_to_triangles / draw_skeleton / draw_bone_dots
 class SkelBone:
     """What the reference reads per bone when it draws the skeleton (modeler/skeleton.rs:412-477, state.rs:2629-2638): the position of
@@ -3202,6 +3295,54 @@ class ResidentScene:
         count = self.n_faces - first if count is None else count
         out = np.zeros(max(count, 0), abi.FACE_DTYPE)
         _chk(self.ctx.lib.b32_scene_read_faces(self.ctx.h, self._handle(), first, count, abi.ptr(out) if count > 0 else None), "scene_read_faces")
+        return out
+
+    # ---- in-place edits (b32_scene_patch_*): nothing is uploaded again, the rig, the pose and the tail stay
+    def patch_vertices(self, indices, vertices):
+        """b32_scene_patch_vertices: whole vertex records at strictly ascending body indices; on a rigged scene they are in rest space."""
+        recs = np.zeros(len(np.asarray(indices).reshape(-1)), abi.VERTEX_PATCH_DTYPE)
+        recs["index"] = np.asarray(indices).reshape(-1)
+        recs["v"] = np.asarray(vertices, abi.VERTEX_DTYPE).reshape(-1)
+        _chk(self.ctx.lib.b32_scene_patch_vertices(self.ctx.h, self._handle(), abi.ptr(recs) if len(recs) else None, len(recs)), "scene_patch_vertices")
+
+    def patch_faces(self, indices, faces):
+        """b32_scene_patch_faces: whole face records at strictly ascending body indices (the first call after an upload synchronises once)."""
+        recs = np.zeros(len(np.asarray(indices).reshape(-1)), abi.FACE_PATCH_DTYPE)
+        recs["index"] = np.asarray(indices).reshape(-1)
+        recs["f"] = np.asarray(faces, abi.FACE_DTYPE).reshape(-1)
+        _chk(self.ctx.lib.b32_scene_patch_faces(self.ctx.h, self._handle(), abi.ptr(recs) if len(recs) else None, len(recs)), "scene_patch_faces")
+
+    @staticmethod
+    def _rows(block, dtype, tail):
+        """A rectangle as the library takes it: (array to keep alive, h, w, stride in elements).  A view whose rows are contiguous is
+        passed with its own stride; anything else is copied."""
+        b = np.asarray(block, dtype)
+        if b.ndim != 2 + len(tail) or b.shape[2:] != tail:
+            raise ValueError("patch: the rectangle is (h, w%s)" % "".join(", %d" % k for k in tail))
+        elem = b.dtype.itemsize * int(np.prod(tail, dtype=np.int64))
+        h, w = b.shape[:2]
+        inner = b.strides[1] == elem and (not tail or b.strides[2] == b.dtype.itemsize)
+        if h and w and not (inner and b.strides[0] % elem == 0 and b.strides[0] >= w * elem):
+            b = np.ascontiguousarray(b)
+        return b, h, w, (b.strides[0] // elem if h and w else w)
+
+    def patch_texels(self, tex, x, y, block):
+        """b32_scene_patch_texels: `block` is (h, w) Color15 for an RGB555 scene, (h, w, 4) Color bytes for an 8-bit-colour one."""
+        b, h, w, stride = self._rows(block, np.uint8 if self.fmt8 else np.uint16, (4,) if self.fmt8 else ())
+        _chk(self.ctx.lib.b32_scene_patch_texels(self.ctx.h, self._handle(), tex, x, y, w, h, b.ctypes.data if b.size else None, stride), "scene_patch_texels")
+
+    def patch_indexed(self, tex, x, y, index_block, clut):
+        """b32_scene_patch_indexed: `index_block` is (h, w) index bytes, `clut` the palette they are looked up in."""
+        b, h, w, stride = self._rows(index_block, np.uint8, ())
+        cl = np.ascontiguousarray(clut, np.uint16).reshape(-1)
+        _chk(self.ctx.lib.b32_scene_patch_indexed(self.ctx.h, self._handle(), tex, x, y, w, h, b.ctypes.data if b.size else None, stride,
+                                                  abi.ptr(cl) if len(cl) else None, len(cl)), "scene_patch_indexed")
+
+    def read_texels(self, tex, width, height):
+        """b32_scene_read_texels (blocking): the expanded pool texels of texture `tex`, whose size the caller states: (height, width)
+        Color15, or (height, width, 4) Color bytes on an 8-bit-colour scene."""
+        out = np.zeros((height, width, 4), np.uint8) if self.fmt8 else np.zeros((height, width), np.uint16)
+        _chk(self.ctx.lib.b32_scene_read_texels(self.ctx.h, self._handle(), tex, abi.ptr(out) if out.size else None), "scene_read_texels")
         return out
 
     def _pack(self, camera, settings, fog):

@@ -456,6 +456,57 @@ struct B32WorldItem;
 int b32_skeleton_items(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, struct B32WorldItem* out, uint32_t cap,
                        uint32_t* n_out);
 
+/* ---- editing a resident scene in place: vertices, faces, texels and palette -----------------------------------------------------------
+ * The modeler changes its mesh every frame while the user drags: the move / rotate / scale tools write the selected vertices' positions
+ * (modeler/viewport.rs:95, :373), the UV editor uv (modeler/layout.rs:3732-3902), the opacity slider editor_alpha of an object's faces
+ * (viewport.rs:1295), the face panel blend_mode and black_transparent, paint mode atlas indices (modeler/mesh_editor.rs:647), the palette
+ * panel one CLUT entry (texture/user_texture.rs:337).  These calls change a resident scene where it lies instead of uploading it again.
+ *
+ * The contract: after any sequence of patches the slot is indistinguishable -- every frame, query, read-back, error and counter -- from a
+ * slot into which the patched arrays were uploaded afresh, followed by the same b32_scene_set_rig, b32_scene_pose with the slot's last
+ * bone table and the same b32_scene_build_skeleton.  Two exceptions, both about speed and never a result: whether the scene's textures
+ * count as having few skippable texels (decided by the upload, b32_set_cheap_threshold) keeps its value, and the tile-region sizes the
+ * slot's frames have learnt stay.
+ *
+ * Common rules.  `index` values are strictly ascending within one call (a parallel scatter has no "last one wins") and below the BODY's
+ * vertex / face count: the tail of bone octahedra is never patched and stays bit for bit.  A rectangle [x, x + w) x [y, y + h) lies inside
+ * texture `tex`; the caller's rows are `stride` elements apart (stride >= w).  Anything else is B32_E_ARG, and a failed call changes
+ * nothing.  n == 0, w == 0 or h == 0 is B32_OK and changes nothing.  The records travel through a pinned ring: the caller may reuse its
+ * arrays when the call returns.  Every call enqueues one copy and one kernel on the context's stream and performs no host synchronisation
+ * (the two documented exceptions below fetch a host copy ONCE per upload); like b32_scene_pose it first settles a pending frame that may
+ * still be redrawn, and the scene's content counts as changed (a merged run of b32_frame_add_scene that holds the slot is rebuilt).
+ *
+ * b32_scene_patch_vertices   one lane per record writes the whole B32Vertex.  On a rigged slot the record is in REST (local) space, where
+ *     the modeler edits: position and normal go into the rest stream, and the vertex gets them posed with the table of the slot's last
+ *     b32_scene_pose (before the first pose, after a pose with n_bones = 0 and after b32_scene_set_rig: copied), by the pose pass's own
+ *     arithmetic.  Later poses start from the patched rest vertex.
+ * b32_scene_patch_faces      one lane per record writes the whole B32Face.  Which faces can reach the transparent pass is host
+ *     bookkeeping derived from ALL faces (editor_alpha, blend_mode, the texture's blend mode); it comes out as a fresh upload's would, the
+ *     transitions to and from "no face blends" included.  This needs the old faces: the FIRST face patch after an upload or
+ *     b32_room_build_mesh copies the body's faces to the host (one host synchronisation); later ones are incremental and do not
+ *     synchronise.  Vertex indices are not validated: as after an upload, one out of range is the frame's B32_E_INDEX.
+ * b32_scene_patch_texels     the rectangle into the texel pool: Color15 (uint16_t) for an RGB555 scene, 4-byte Color for a scene of
+ *     b32_scene_upload_rgba.  The skip mask is rebuilt by the next frame.  On an 8-bit-colour scene whether ANY texel blends decides the
+ *     walk; to know when the last one goes, the first texel patch after an upload copies the pool to the host (one host synchronisation).
+ * b32_scene_patch_indexed    indices[] looked up in clut[] (Clut::lookup: an index at or past clut_len is 0x0000) into the pool of an
+ *     RGB555 scene (B32_E_ARG on an 8-bit-colour one).  A scene of b32_scene_upload_indexed with ONE texture keeps its index atlas and CLUT
+ *     for the fill (B32_ROUTE_LDS_ATLAS): the patch writes the kept indices too; a whole-texture patch also replaces the kept CLUT (zero
+ *     behind a shorter one) -- a palette-only change is a whole-texture patch; a partial patch whose CLUT, zero-padded to 256 entries,
+ *     differs from the kept one drops the kept atlas, and so does b32_scene_patch_texels (expanded texels have no index): the fill then
+ *     reads the pool.
+ * b32_scene_read_texels      blocking: the expanded pool texels of one texture (width * height elements), as they are on the device now.
+ * Out of scope: vertex / face / texture counts and texture sizes (an upload), connectivity (an upload plus b32_topology_create), rooms
+ * (b32_room_update*). */
+typedef struct B32VertexPatch { uint32_t index; B32Vertex v; } B32VertexPatch;   /* 40 bytes */
+typedef struct B32FacePatch   { uint32_t index; B32Face   f; } B32FacePatch;     /* 24 bytes */
+int b32_scene_patch_vertices(b32_ctx* ctx, b32_scene* slot /* NULL: the context's resident scene */, const B32VertexPatch* recs, uint32_t n);
+int b32_scene_patch_faces(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, const B32FacePatch* recs, uint32_t n);
+int b32_scene_patch_texels(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                           const void* texels, uint32_t stride);
+int b32_scene_patch_indexed(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                            const uint8_t* indices, uint32_t stride, const uint16_t* clut, uint32_t clut_len);
+int b32_scene_read_texels(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t tex, void* out);  /* blocking */
+
 /* ---- a frame of several meshes (scene.rs:112-261) -------------------------------------------------------------------------------
  * The console's render step is one render_mesh_15 call per room and per asset part onto the same framebuffer, with ONE camera and
  * light list per frame and per-mesh ambient, fog (per room, scene.rs:189-205) and backface culling (per part: double_sided,
