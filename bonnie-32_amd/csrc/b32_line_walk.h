@@ -108,8 +108,21 @@ __device__ __forceinline__ void walk_line(const Edge& e, DepthOp depth_op, long 
     if (line_k_range(e, cx0, cx1, cy0, cy1, k_lo, k_hi)) walk_line_range(e, depth_op, cx0, cx1, cy0, cy1, k_lo, k_hi, depth_at, plot);
 }
 __device__ __forceinline__ uint32_t abs_diff(int p, int q) { return p < q ? (uint32_t)q - (uint32_t)p : (uint32_t)p - (uint32_t)q; }   // |p - q| of two i32, exact (< 2^32)
-__device__ __forceinline__ bool edge_overflows(const Edge& e) {          // 2*err overflows i32 in the reference (render.rs:735, 800)
-    return abs_diff(e.x1, e.x0) >= (1u << 30) || abs_diff(e.y1, e.y0) >= (1u << 30);
+// Does the reference's i32 Bresenham state overflow (render.rs:742, 803)?  Extents of 2^30 and more: always refused.  Below that, with
+// dmaj >= dmin the extents, `2 * err` reaches 3 * dmaj - 2 * dmin - r_min, where r_min = g = gcd(dmaj, dmin) if dmaj / g is odd and 0 if
+// it is even (err after k steps is 1.5 * dmaj - dmin - r / 2, r = (2 * dmin * k + dmaj) mod (2 * dmaj); the reference restatement
+// states the same rule, tests/test_wire_sheets.py compares both with the literal loop in a short word): a shallow
+// line overflows from an extent of 2^31 / 3 on.  One multiply-subtract-compare for every line a mesh produces; the gcd only beyond it.
+__device__ __forceinline__ bool edge_overflows(const Edge& e) {
+    const uint32_t ax = abs_diff(e.x1, e.x0), ay = abs_diff(e.y1, e.y0);
+    const uint32_t dmaj = ax > ay ? ax : ay, dmin = ax > ay ? ay : ax;
+    if (dmaj >= (1u << 30)) return true;
+    const uint32_t top = 3u * dmaj - 2u * dmin;                          // (< 3 * 2^30: fits)
+    if (top < (1u << 31)) return false;
+    uint32_t a = dmaj, b = dmin;
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    const uint32_t r_min = ((dmaj / a) & 1u) ? a : 0u;
+    return ax >= ay ? top - r_min >= (1u << 31) : top - r_min > (1u << 31);        // (y-major: 2 * err is -(top - r): i32 holds -2^31)
 }
 // lines the tile kernel walks in 32-bit integers with the three-instruction depth parameter (the bounds of walk_line_range's `narrow`)
 __device__ __forceinline__ bool edge_narrow(const Edge& e) {

@@ -30,7 +30,10 @@ extern "C" {
 #define B32_E_INDEX       -2  /* face.v* >= nv            [index panic, render.rs:2375-2377] */
 #define B32_E_NAN_KEY     -3  /* NaN painter's key        [unwrap panic, render.rs:2531]     */
 #define B32_E_HIP         -4  /* HIP runtime failure (b32_last_hip_error has the code)      */
-#define B32_E_UNSUPPORTED -5  /* wireframe edge >= 2^30 px (i32 overflow in the reference); more than 65534 textures */
+#define B32_E_UNSUPPORTED -5  /* a wireframe edge whose Bresenham state overflows i32 in the reference: every extent >= 2^30 px, and below that
+                                  every edge with 3 * dmaj - 2 * dmin - r_min >= 2^31 (dmaj >= dmin its extents; r_min = gcd(dmaj, dmin) if
+                                  dmaj / gcd is odd, else 0; a y-major edge has one value more of room) -- a shallow edge from 2^31 / 3 =
+                                  715 827 883 px on; Framebuffer lines and primitives: >= 2^30; more than 65534 textures */
 #define B32_E_NO_DEVICE   -6  /* no gfx950 device / kernels missing: the product path never falls back to CPU   */
 #define B32_E_FRAME_DROPPED -7 /* deep asynchronous mode only (b32_set_async_depth): an EARLIER frame in flight ran out of buffer
                                   space and drew nothing (its framebuffer kept the cleared / previous contents); the most recent

@@ -896,12 +896,35 @@ static inline int32_t i32_wadd(int32_t a, int32_t b) { return (int32_t)((uint32_
 static inline int32_t i32_wsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
 static inline int32_t i32_wabs(int32_t a) { return a < 0 ? (int32_t)(0u - (uint32_t)a) : a; }
 /* Lines whose Bresenham state would overflow i32 in the reference (debug builds panic, release builds wrap and spin):
- * |dx| or |dy| >= 2^30 makes `2 * err` overflow.  Reported as B32_E_UNSUPPORTED by oracle and GPU alike. */
+ * |dx| or |dy| >= 2^30 makes `2 * err` overflow.  Reported as B32_E_UNSUPPORTED by oracle and GPU alike.
+ * KNOWN GAP: this flat limit is what b32o_draw_line / _3d below still use on their own, i.e. for the Framebuffer line and primitive
+ * producers (whose host-side limit is PRIM_LIM = 2^30 too).  A line with minor steps overflows `2 * err` already from an extent of
+ * 2^31 / 3 on (b32o_wire_edge_overflows has the exact rule): between there and 2^30 the two loops below never end (signed overflow,
+ * undefined in C), where the device draws its closed form.  The wireframe phases ask the exact rule first and never get there. */
 static inline int line_overflows(int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
     int64_t adx = (int64_t)x1 - x0, ady = (int64_t)y1 - y0;
     if (adx < 0) adx = -adx;
     if (ady < 0) ady = -ady;
     return adx >= ((int64_t)1 << 30) || ady >= ((int64_t)1 << 30);
+}
+/* The wireframe phases' rule, exact below 2^30: with dmaj >= dmin the extents, the loop's error term after k steps is
+ * err = 1.5 * dmaj - dmin - r / 2 with r = (2 * dmin * k + dmaj) mod (2 * dmaj), so `2 * err` (render.rs:742, 803) reaches
+ * 3 * dmaj - 2 * dmin - r_min, where r_min -- the smallest residue, taken within the first dmaj steps -- is g = gcd(dmaj, dmin) if
+ * dmaj / g is odd and 0 if it is even (a flat line: r = dmaj throughout, 2 * err = 2 * dmaj).  A shallow line therefore overflows i32
+ * from an extent of 2^31 / 3 on: the literal loop above never ends there.  Extents of 2^30 and more stay refused whatever their slope. */
+EXPORT int b32o_wire_edge_overflows(int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
+    if (line_overflows(x0, y0, x1, y1)) return 1;
+    int64_t adx = (int64_t)x1 - x0, ady = (int64_t)y1 - y0;
+    if (adx < 0) adx = -adx;
+    if (ady < 0) ady = -ady;
+    const int64_t dmaj = adx > ady ? adx : ady, dmin = adx > ady ? ady : adx;
+    const int64_t top = 3 * dmaj - 2 * dmin;
+    if (top < ((int64_t)1 << 31)) return 0;
+    int64_t a = dmaj, b = dmin;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    const int64_t r_min = ((dmaj / a) & 1) ? a : 0;
+    /* (a y-major line's error term has the other sign, 2 * err = -(3 * dmaj - 2 * dmin - r): i32 holds -2^31 and not +2^31) */
+    return adx >= ady ? top - r_min >= ((int64_t)1 << 31) : top - r_min > ((int64_t)1 << 31);
 }
 /* Framebuffer::draw_line -> draw_line_blended(mode = Opaque), render.rs:716-750 */
 EXPORT int b32o_draw_line(uint8_t* pixels, uint32_t width, uint32_t height, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
@@ -1370,14 +1393,14 @@ static int render_mesh_impl(uint8_t* fb_pixels, float* fb_zbuffer, uint32_t widt
         uint32_t ne = 0;
         WireEdge* ue = unique_edges(backface_wireframes, n_bw, &ne);
         for (uint32_t i = 0; i < ne && !rc; ++i)
-            rc = b32o_draw_line_3d(fb.pixels, fb.zbuffer, width, height, ue[i].x0, ue[i].y0, ue[i].z0, ue[i].x1, ue[i].y1, ue[i].z1, 80, 80, 100);
+            rc = b32o_wire_edge_overflows(ue[i].x0, ue[i].y0, ue[i].x1, ue[i].y1) ? B32_E_UNSUPPORTED : b32o_draw_line_3d(fb.pixels, fb.zbuffer, width, height, ue[i].x0, ue[i].y0, ue[i].z0, ue[i].x1, ue[i].y1, ue[i].z1, 80, 80, 100);
         free(ue);
     }
     if (!rc && st->wireframe_overlay && n_fw) {
         uint32_t ne = 0;
         WireEdge* ue = unique_edges(frontface_wireframes, n_fw, &ne);
         for (uint32_t i = 0; i < ne && !rc; ++i)
-            rc = b32o_draw_line(fb.pixels, width, height, ue[i].x0, ue[i].y0, ue[i].x1, ue[i].y1, 200, 200, 220);
+            rc = b32o_wire_edge_overflows(ue[i].x0, ue[i].y0, ue[i].x1, ue[i].y1) ? B32_E_UNSUPPORTED : b32o_draw_line(fb.pixels, width, height, ue[i].x0, ue[i].y0, ue[i].x1, ue[i].y1, 200, 200, 220);
         free(ue);
     }
 done:

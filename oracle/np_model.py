@@ -12,6 +12,7 @@ Scope: perspective projection (fixed-point or float), painter's and z-buffer mod
 directional and point lights, fog, blend modes, editor alpha.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -423,9 +424,22 @@ def line_points(x0, y0, x1, y1):
     return x0 + sx * ((2 * adx * k + ady) // (2 * ady)), y0 + sy * k, k
 
 
+def edge_overflows(x0, y0, x1, y1, word=32):
+    """Does the reference's Bresenham state leave its signed word (i32; `word`: a shorter one, for the tests)?  Extents of 2^(word-2) and
+    more are refused as a rule; below that `2 * err` reaches 3 * dmaj - 2 * dmin - r_min (b32_oracle.c, b32o_wire_edge_overflows)."""
+    dmaj, dmin = max(abs(x1 - x0), abs(y1 - y0)), min(abs(x1 - x0), abs(y1 - y0))
+    if dmaj >= 1 << (word - 2):
+        return True
+    g = math.gcd(dmaj, dmin)
+    r_min = (g if (dmaj // g) % 2 else 0) if g else 0
+    top = 3 * dmaj - 2 * dmin - r_min
+    # (a y-major line's error term has the other sign, 2 * err = -top: the word holds -2^(word-1) and not +2^(word-1))
+    return top >= 1 << (word - 1) if abs(x1 - x0) >= abs(y1 - y0) else top > 1 << (word - 1)
+
+
 def draw_line(img, width, height, e, rgb, zb, depth_test):
     x0, y0, z0, x1, y1, z1 = e
-    if max(abs(x1 - x0), abs(y1 - y0)) >= 1 << 30:
+    if edge_overflows(x0, y0, x1, y1):
         raise OverflowError("Bresenham state overflows i32 in the reference")
     xs, ys, k = line_points(x0, y0, x1, y1)
     on = (xs >= 0) & (xs < width) & (ys >= 0) & (ys < height)

@@ -53,6 +53,7 @@ def _load(path):
         L.b32o_dither_offset.restype = C.c_int32; L.b32o_dither_offset.argtypes = [C.c_uint32, C.c_uint32]
         L.b32o_dither_and_quantize.restype = None
         L.b32o_dither_and_quantize.argtypes = [C.c_uint8] * 3 + [C.c_uint32, C.c_uint32, P]
+        L.b32o_wire_edge_overflows.restype = C.c_int; L.b32o_wire_edge_overflows.argtypes = [C.c_int32] * 4
         L.b32o_unique_edges_selfcheck.restype = C.c_uint32; L.b32o_unique_edges_selfcheck.argtypes = [P, C.c_uint32]
         L.b32o_fb_clear.restype = None
         L.b32o_fb_clear.argtypes = [P, P, C.c_uint32, C.c_uint32] + [C.c_uint8] * 4
