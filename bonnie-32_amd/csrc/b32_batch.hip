@@ -29,26 +29,27 @@ static int build_merged(b32_ctx* c, const b32_ctx::BatchEntry* e, uint32_t n, b3
     if (!m->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&m->d_consts), 16 * sizeof(uint32_t)));
     m->h_tex.clear();
     uint32_t vb = 0, fb = 0, tb = 0, pb = 0;
-    m->may_blend = false; m->cheap_ok = true; m->tex_blend_any = false; m->blend_faces = 0;
+    SlotBlend blend = *m;                                // (a run is RGB555 and has no tail: may_blend and blend_faces are its members')
+    blend.may_blend = false; blend.blend8 = false; blend.blend_faces = 0;
+    m->cheap_ok = true; m->tex_blend_any = false;
     for (uint32_t j = 0; j < n; ++j) {
         const b32_scene* sl = e[j].slot;
         launch_merge_mesh(c->stream, sl->d_verts, sl->nv, sl->d_faces, sl->nf, sl->nt, m->d_verts, m->d_faces + fb, vb, tb, j);
         if (sl->pool_texels) HIPCHK(c, hipMemcpyAsync(m->d_texels + pb, sl->d_texels, (size_t)sl->pool_texels * 2, hipMemcpyDeviceToDevice, c->stream));
         launch_offset_tex(c->stream, sl->d_tex, sl->nt, m->d_tex + tb, pb);
         for (const TexDesc& d : sl->h_tex) m->h_tex.push_back({ d.width, d.height, d.blend_mode, d.offset + pb });
-        m->may_blend |= sl->may_blend; m->cheap_ok &= sl->cheap_ok; m->tex_blend_any |= sl->tex_blend_any;
-        m->blend_faces += sl->blend_faces;
+        blend.may_blend |= sl->may_blend; m->cheap_ok &= sl->cheap_ok; m->tex_blend_any |= sl->tex_blend_any;
+        blend.blend_faces += sl->blend_faces;
         vb += sl->nv; fb += sl->nf; tb += sl->nt; pb += sl->pool_texels;
     }
     const uint32_t consts[4] = { (uint32_t)nf, 0, 0, 0 };
     HIPCHK(c, hipMemcpyAsync(m->d_consts, consts, sizeof(consts), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (`consts` is on the stack; a merged mesh is built once and reused)
     HIPCHK(c, hipGetLastError());
-    m->nv = (uint32_t)nv; m->nf = (uint32_t)nf; m->nt = (uint32_t)nt; m->pool_texels = (uint32_t)pool; m->mask_dirty = true;
-    m->fmt8 = false; m->blend8 = false; m->have_scene = true; m->local_sort_ok = true;
-    m->direct_cap_opaque = 0; m->direct_ntiles = 0; m->direct_ok = true; m->pos_valid = false; m->lit_valid = false; m->band_frames = 0;
-    m->tex_sig_valid = false; m->gen = ++c->gen_counter;
-    c->side_dirty = true;
+    m->nv = (uint32_t)nv; m->nf = (uint32_t)nf; m->nt = (uint32_t)nt; m->pool_texels = (uint32_t)pool;
+    m->fmt8 = false; m->have_scene = true;
+    pool_replaced(*m);
+    geometry_replaced(*m, edit_words(c), false, blend);
     return B32_OK;
 }
 // the merged mesh of a run: from the cache when the same slots with the same contents were merged before

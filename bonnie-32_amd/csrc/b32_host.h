@@ -9,7 +9,7 @@
 #pragma once
 #include "b32_device.h"
 #include "b32_frame_plan.h"
-#include "b32_patch_tally.h"
+#include "b32_scene_state.h"
 #include <algorithm>
 #include <cstdio>
 #include <chrono>
@@ -90,7 +90,7 @@ struct TexSig { const void* ptr; uint32_t w, h, blend; uint64_t hash; };
 // Everything that belongs to ONE uploaded scene: b32_ctx::scene is the resident one, a slot of b32_scene_swap (or a merged mesh of a
 // batched frame) another; b32_scene_swap exchanges whole structs.  What is per context (the routes' switches, h_consts, last_direct,
 // epoch, the frame sets) is not here.
-struct b32_scene {
+struct b32_scene : b32::SceneState {    // (SceneState, b32_scene_state.h: what is derived from the content below and dies when it changes)
     B32Vertex* d_verts = nullptr; size_t cap_verts = 0;
     B32Face* d_faces = nullptr; size_t cap_faces = 0;
     uint16_t* d_texels = nullptr; size_t cap_texels = 0;
@@ -98,45 +98,33 @@ struct b32_scene {
     TexDesc* d_tex = nullptr; size_t cap_tex = 0;
     std::vector<TexDesc> h_tex;
     uint32_t* d_consts = nullptr;       // (h_consts on the device: the face count the first radix pass reads)
-    uint8_t* d_atlas0 = nullptr; size_t cap_atlas0 = 0; uint32_t atlas_idx_bytes = 0;   // indexed upload of ONE texture: CLUT (512 B) + index bytes, kept for the LDS route
-    uint32_t* d_texmask = nullptr; size_t cap_texmask = 0;       // skip mask of the texel pool (FillArgs.texmask), rebuilt when the pool changes
-    uint32_t pool_texels = 0; bool mask_dirty = true;
+    uint8_t* d_atlas0 = nullptr; size_t cap_atlas0 = 0;       // indexed upload of ONE texture: CLUT (512 B) + index bytes (atlas_idx_bytes), kept for the LDS route
+    uint32_t* d_texmask = nullptr; size_t cap_texmask = 0;       // skip mask of the texel pool (FillArgs.texmask), rebuilt when the pool changes (mask_dirty)
+    uint32_t pool_texels = 0;
     uint32_t nv = 0, nf = 0, nt = 0;
     bool have_scene = false;
-    unsigned long long gen = 0;         // identity of the scene's content (every upload gets a new number)
     bool fmt8 = false;                  // uploaded by b32_scene_upload_rgba (render_mesh path)
-    bool blend8 = false;                // 8-bit path: some texel blends or some face has editor_alpha < 255 -> ordered walk
-    bool blend_texels8 = false;         // ... the texels' part of it, which stays when b32_room_build_mesh replaces the faces
-    bool may_blend = true;              // some face / texture can produce a transparent-pass surface (render.rs:2403-2415)
+    bool blend_texels8 = false;         // 8-bit path: some texel blends (the texels' part of blend8, which stays when b32_room_build_mesh replaces the faces)
     bool cheap_ok = false;              // every texture has few skippable texels: CHEAP coverage + repair is profitable
     bool tex_blend_any = false;         // some texture has a blend mode other than Opaque
-    uint32_t blend_faces = 0;           // faces that their own blend mode / editor alpha or their texture's blend mode puts in the transparent pass
-    bool local_sort_ok = true;          // no tile list of this scene has exceeded the LDS sort capacity so far
-    // direct binning (DirectBin, b32_device.h): what the scene's frames taught about its tile regions
-    uint32_t direct_cap_opaque = 0;     // opaque entries per tile region (0: sized from the mesh on first use)
-    uint32_t direct_ntiles = 0;         // the tile grid that size belongs to (another grid: sized again)
-    bool direct_ok = true;              // false: the regions would not fit (one tile's list too long) -> counting sort
-    // packed vertex streams of a resident mesh (k_pack_streams: nv positions of 12 B, then nv (u, v, rgba) of 12 B): built on the second
-    // frame of an uploaded mesh too large for the in-kernel list collection
-    float* d_pos12 = nullptr; size_t cap_pos12 = 0; bool pos_valid = false; uint32_t band_frames = 0;
-    bool lit_valid = false;             // ... and the 24-byte lit stream behind them (packed on the first frame with a shading pass)
-    std::vector<TexSig> tex_sig; bool tex_sig_valid = false;
-    // bones (b32_scene_set_rig): the rest stream (nv positions and normals, 24 B each) k_pose starts from, and a bone index per vertex.
-    // Part of the scene's content: swapped with it, dropped (have_rig = false, the buffers stay for the next rig) by every upload
-    float* d_rest = nullptr; size_t cap_rest = 0; uint16_t* d_bone_of = nullptr; size_t cap_bone_of = 0; bool have_rig = false;
+    // packed vertex streams of a resident mesh (k_pack_streams: nv positions of 12 B, then nv (u, v, rgba) of 12 B; pos_valid, lit_valid):
+    // built on the second frame of an uploaded mesh too large for the in-kernel list collection
+    float* d_pos12 = nullptr; size_t cap_pos12 = 0;
+    std::vector<TexSig> tex_sig;        // (tex_sig_valid)
+    // bones (b32_scene_set_rig, have_rig): the rest stream (nv positions and normals, 24 B each) k_pose starts from, and a bone index per
+    // vertex.  Part of the scene's content: swapped with it; the buffers stay for the next rig when the geometry is replaced
+    float* d_rest = nullptr; size_t cap_rest = 0; uint16_t* d_bone_of = nullptr; size_t cap_bone_of = 0;
     // the bone octahedra (b32_scene_build_skeleton): the last tail_v of the nv vertices and the last tail_f of the nf faces.  Everything
     // that draws reads nv / nf; what the reference does to mesh objects only (rig, pose, hover, box selection, pick, selection overlays)
-    // reads body_nv() / body_nf().  While there is a tail, body_* hold the blend bookkeeping of the body alone (the scene's own values
-    // are body + tail).  Part of the scene's content: swapped with it, dropped by every upload and by b32_room_build_mesh
-    uint32_t tail_v = 0, tail_f = 0, body_blend_faces = 0; bool body_may_blend = false, body_blend8 = false;
+    // reads body_nv() / body_nf().
     // in-place edits (b32_scene_patch_*, b32_patch.hip): what they need of the slot on the host.  h_bones: the table of the last
     // b32_scene_pose (empty before the first one and after b32_scene_set_rig), with which a patched rest vertex is posed.  h_faces: the
-    // body's faces, fetched by the first face patch after an upload or b32_room_build_mesh (one synchronisation) and kept up to date, and
+    // body's faces, fetched by the first face patch after the geometry was replaced (one synchronisation) and kept up to date, and
     // their tally.  h_texels32: the Color pool of an 8-bit-colour scene, fetched by its first texel patch, and how many of its texels
     // blend (blend_texels8).  h_clut: the kept CLUT of an index atlas (atlas_idx_bytes != 0), 256 entries
     std::vector<B32Bone> h_bones;
-    std::vector<B32Face> h_faces; bool h_faces_valid = false; b32::FaceTally tally;
-    std::vector<uint32_t> h_texels32; bool h_texels32_valid = false; size_t blend_texel_count = 0;
+    std::vector<B32Face> h_faces; b32::FaceTally tally;
+    std::vector<uint32_t> h_texels32; size_t blend_texel_count = 0;
     std::vector<uint16_t> h_clut;
     uint32_t body_nv() const { return nv - tail_v; }
     uint32_t body_nf() const { return nf - tail_f; }
@@ -473,4 +461,22 @@ B32_INTERNAL int validate_settings(const B32Settings* st);                      
 B32_INTERNAL int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog);            // b32_frame.hip
 // (place: the placement of a draw on its own, or NULL; a merged run -- frame_batched -- has set frame_placed / frame_places itself)
 B32_INTERNAL int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place);   // b32_frame.hip
+}
+
+// ---- editing a resident scene (the rules: b32_scene_state.h)
+// The slot a call names (NULL: the resident scene), if it holds a scene.
+static inline b32_scene* scene_of(b32_ctx* c, b32_scene* slot) {
+    b32_scene* sc = slot ? slot : &c->scene;
+    return sc->have_scene ? sc : nullptr;
+}
+// Entering an edit.  A pending frame that may still be redrawn (overflowed tile regions / pair buffers) is redrawn from the RESIDENT
+// vertices, faces and texels: it is settled before any of them changes, or the redraw would draw the edited scene in its place.
+static inline int edit_begin(b32_ctx* c) {
+    (void)hipSetDevice(c->device);
+    return settle_pending(c);
+}
+static inline b32::EditWords edit_words(b32_ctx* c) { return { c->gen_counter, c->side_dirty }; }
+// tex_blends(t) of the tally (b32_patch_tally.h): texture t of the slot resolves and its blend mode is not Opaque.
+static inline bool tex_blends(const b32_scene* sc, uint32_t t) {
+    return t < sc->nt && t < sc->h_tex.size() && sc->h_tex[t].blend_mode != B32_BLEND_OPAQUE;
 }

@@ -16,7 +16,8 @@
 //   k_patch_faces     one lane per record, whole dwords.
 //   k_patch_texels<T> one lane per texel of the rectangle, adjacent lanes adjacent texels of one row.
 //   k_patch_indexed   ditto, through Clut::lookup; also the kept index bytes and, for a whole texture, the kept CLUT.
-// Ordering against the side stream and the bookkeeping are b32_scene_pose's (b32_scene.hip).
+// Ordering against the side stream is b32_scene_pose's (b32_scene.hip); what an edit does to the slot's derived state
+// is stated in b32_scene_state.h.
 #include "b32_host.h"
 #include "b32_patch_body.h"
 
@@ -103,11 +104,6 @@ void launch_patch_indexed(hipStream_t s, const PatchRect& r, const void* src, ui
 // ------------------------------------------------------------------ the host side
 namespace {
 
-b32_scene* patch_scene_of(b32_ctx* c, b32_scene* slot) {
-    b32_scene* sc = slot ? slot : &c->scene;
-    return sc->have_scene ? sc : nullptr;
-}
-
 // stage_records (b32_host.h) for a payload the caller assembles in place: `fill` writes n dwords into the pinned ring slot.
 template <class Fill>
 int patch_stage(b32_ctx* c, uint32_t n, Fill fill) {
@@ -131,17 +127,7 @@ int patch_stage(b32_ctx* c, uint32_t n, Fill fill) {
     return B32_OK;
 }
 
-// what every patch leaves behind, like b32_scene_pose: the next pipelined k_setup waits for the main stream, a merged run that holds the
-// slot is rebuilt
-void patch_changed(b32_ctx* c, b32_scene* sc) {
-    c->side_dirty = true;
-    sc->gen = ++c->gen_counter;
-}
-
-bool patch_tex_blends(const b32_scene* sc, uint32_t t) {        // upload_geometry's rule
-    return t < sc->nt && t < sc->h_tex.size() && sc->h_tex[t].blend_mode != B32_BLEND_OPAQUE;
-}
-// The body's faces on the host and their tally: fetched once after an upload or b32_room_build_mesh (ONE host synchronisation).
+// The body's faces on the host and their tally: fetched once after the geometry was replaced (ONE host synchronisation).
 int patch_fetch_faces(b32_ctx* c, b32_scene* sc) {
     if (sc->h_faces_valid) return B32_OK;
     const uint32_t bf = sc->body_nf();
@@ -150,15 +136,12 @@ int patch_fetch_faces(b32_ctx* c, b32_scene* sc) {
         HIPCHK(c, hipMemcpyAsync(sc->h_faces.data(), sc->d_faces, (size_t)bf * sizeof(B32Face), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    sc->tally = tally_faces(sc->h_faces.data(), bf, [sc](uint32_t t) { return patch_tex_blends(sc, t); });
+    sc->tally = tally_faces(sc->h_faces.data(), bf, [sc](uint32_t t) { return tex_blends(sc, t); });
     sc->h_faces_valid = true;
     return B32_OK;
 }
-void patch_apply_tally(b32_scene* sc) {
-    const SlotBlend cur{ sc->may_blend, sc->blend8, sc->blend_faces, sc->body_may_blend, sc->body_blend8, sc->body_blend_faces };
-    const SlotBlend s = tally_slot(sc->tally, cur, sc->fmt8, sc->tex_blend_any, sc->blend_texels8, sc->tail_v != 0 || sc->tail_f != 0);
-    sc->may_blend = s.may_blend; sc->blend8 = s.blend8; sc->blend_faces = s.blend_faces;
-    sc->body_may_blend = s.body_may_blend; sc->body_blend8 = s.body_blend8; sc->body_blend_faces = s.body_blend_faces;
+SlotBlend patch_tally_blend(const b32_scene* sc) {   // the slot's blend bookkeeping as its (patched) tally has it
+    return tally_slot(sc->tally, *sc, sc->fmt8, sc->tex_blend_any, sc->blend_texels8, sc->tail_v != 0 || sc->tail_f != 0);
 }
 
 bool patch_texel_blends8(uint32_t color) {      // b32_scene_upload_rgba: a texel that is neither Opaque nor Erase
@@ -197,58 +180,52 @@ extern "C" {
 
 int b32_scene_patch_vertices(b32_ctx* c, b32_scene* slot, const B32VertexPatch* recs, uint32_t n) {
     if (!c) return B32_E_ARG;
-    b32_scene* sc = patch_scene_of(c, slot);
+    b32_scene* sc = scene_of(c, slot);
     if (!sc) return B32_E_ARG;
     if (!n) return B32_OK;
     if (!recs || !patch_records_ok(recs, sizeof(B32VertexPatch), n, sc->body_nv())) return B32_E_ARG;
     if ((unsigned long long)n * PATCH_VERTEX_WORDS > 0xFFFFFFFFull) return B32_E_UNSUPPORTED;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn is redrawn from the resident vertices: settle it before they change (b32_scene_pose)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rcs = edit_begin(c); if (rcs) return rcs; }
     const uint32_t words = n * PATCH_VERTEX_WORDS;
     { const int rc = patch_stage(c, words, [&](uint32_t* dst) { std::memcpy(dst, recs, (size_t)words * 4); }); if (rc) return rc; }
     const bool rigged = sc->have_rig;
     launch_patch_vertices(c->stream, c->patch.dev, n, sc->d_verts, rigged ? sc->d_rest : nullptr, sc->d_bone_of, sc->h_bones.data(), rigged ? (uint32_t)sc->h_bones.size() : 0u);
     HIPCHK(c, hipGetLastError());
-    sc->pos_valid = false; sc->lit_valid = false;       // (the packed streams are rebuilt by the next frame, as after a pose: band_frames stays)
-    patch_changed(c, sc);
+    vertices_moved(*sc, edit_words(c));
     return B32_OK;
 }
 
 int b32_scene_patch_faces(b32_ctx* c, b32_scene* slot, const B32FacePatch* recs, uint32_t n) {
     if (!c) return B32_E_ARG;
-    b32_scene* sc = patch_scene_of(c, slot);
+    b32_scene* sc = scene_of(c, slot);
     if (!sc) return B32_E_ARG;
     if (!n) return B32_OK;
     if (!recs || !patch_records_ok(recs, sizeof(B32FacePatch), n, sc->body_nf())) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rcs = edit_begin(c); if (rcs) return rcs; }
     int rc;
     if ((rc = patch_fetch_faces(c, sc))) return rc;      // (the first face patch after an upload synchronises once; later ones do not)
     const uint32_t words = n * PATCH_FACE_WORDS;
     if ((rc = patch_stage(c, words, [&](uint32_t* dst) { std::memcpy(dst, recs, (size_t)words * 4); }))) return rc;
     launch_patch_faces(c->stream, c->patch.dev, n, sc->d_faces);
     HIPCHK(c, hipGetLastError());
-    const auto blends = [sc](uint32_t t) { return patch_tex_blends(sc, t); };
+    const auto blends = [sc](uint32_t t) { return tex_blends(sc, t); };
     for (uint32_t k = 0; k < n; ++k) {
         B32Face& f = sc->h_faces[recs[k].index];
         tally_face(sc->tally, f, false, blends);
         f = recs[k].f;
         tally_face(sc->tally, f, true, blends);
     }
-    patch_apply_tally(sc);
-    patch_changed(c, sc);
+    faces_edited(*sc, edit_words(c), patch_tally_blend(sc));
     return B32_OK;
 }
 
 int b32_scene_patch_texels(b32_ctx* c, b32_scene* slot, uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void* texels, uint32_t stride) {
     if (!c) return B32_E_ARG;
-    b32_scene* sc = patch_scene_of(c, slot);
+    b32_scene* sc = scene_of(c, slot);
     if (!sc) return B32_E_ARG;
     bool empty;
     { const int rc = patch_rect_check(sc, tex, x, y, w, h, texels, stride, &empty); if (rc || empty) return rc; }
-    (void)hipSetDevice(c->device);
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rcs = edit_begin(c); if (rcs) return rcs; }
     int rc;
     const TexDesc& d = sc->h_tex[tex];
     const uint32_t elem = sc->fmt8 ? 4u : 2u;
@@ -258,7 +235,7 @@ int b32_scene_patch_texels(b32_ctx* c, b32_scene* slot, uint32_t tex, uint32_t x
     const PatchRect r{ x, y, w, h, d.width, d.offset };
     launch_patch_texels(c->stream, r, c->patch.dev, sc->fmt8 ? nullptr : sc->d_texels, sc->fmt8 ? sc->d_texels32 : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (sc->fmt8) {                                      // does any texel blend now?  (b32_scene_upload_rgba: blend_texels8 -> blend8)
+    if (sc->fmt8) {                                      // does any texel blend now?  (blend_texels8 -> blend8: blend_fresh)
         const uint32_t* src = static_cast<const uint32_t*>(texels);
         for (uint32_t row = 0; row < h; ++row)
             for (uint32_t col = 0; col < w; ++col) {
@@ -273,26 +250,23 @@ int b32_scene_patch_texels(b32_ctx* c, b32_scene* slot, uint32_t tex, uint32_t x
         if (blend_texels != sc->blend_texels8) {
             if ((rc = patch_fetch_faces(c, sc))) return rc;
             sc->blend_texels8 = blend_texels;
-            patch_apply_tally(sc);
+            set_blend(*sc, patch_tally_blend(sc));
         }
     }
-    sc->atlas_idx_bytes = 0;                            // (expanded texels have no index: the fill reads the pool from now on)
-    sc->mask_dirty = true; sc->tex_sig_valid = false;
-    patch_changed(c, sc);
+    texels_rewritten(*sc, edit_words(c), false);        // (expanded texels have no index: the fill reads the pool from now on)
     return B32_OK;
 }
 
 int b32_scene_patch_indexed(b32_ctx* c, b32_scene* slot, uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* indices, uint32_t stride,
                             const uint16_t* clut, uint32_t clut_len) {
     if (!c) return B32_E_ARG;
-    b32_scene* sc = patch_scene_of(c, slot);
+    b32_scene* sc = scene_of(c, slot);
     if (!sc || sc->fmt8) return B32_E_ARG;
     bool empty;
     { const int rc = patch_rect_check(sc, tex, x, y, w, h, indices, stride, &empty); if (rc) return rc; }
     if (clut_len && !clut) return B32_E_ARG;
     if (empty) return B32_OK;
-    (void)hipSetDevice(c->device);
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rcs = edit_begin(c); if (rcs) return rcs; }
     const TexDesc& d = sc->h_tex[tex];
     const uint32_t kept_entries = std::min(clut_len, PATCH_CLUT_ENTRIES);       // (an index is a byte: entries past 256 are never looked up)
     const uint32_t clut_words = PATCH_CLUT_ENTRIES / 2, words = clut_words + (uint32_t)(((size_t)w * h + 3) / 4);
@@ -308,20 +282,18 @@ int b32_scene_patch_indexed(b32_ctx* c, b32_scene* slot, uint32_t tex, uint32_t 
     // brings its own, a partial one must come with the kept one or the atlas is dropped
     const bool whole = x == 0 && y == 0 && w == d.width && h == d.height;
     bool keep = sc->atlas_idx_bytes != 0 && sc->h_clut.size() == PATCH_CLUT_ENTRIES;
-    if (sc->atlas_idx_bytes && !keep) sc->atlas_idx_bytes = 0;
-    if (keep && !whole && std::memcmp(sc->h_clut.data(), padded, sizeof(padded)) != 0) { sc->atlas_idx_bytes = 0; keep = false; }
+    if (keep && !whole && std::memcmp(sc->h_clut.data(), padded, sizeof(padded)) != 0) keep = false;
     if (keep && whole) std::memcpy(sc->h_clut.data(), padded, sizeof(padded));
     const PatchRect r{ x, y, w, h, d.width, d.offset };
     launch_patch_indexed(c->stream, r, c->patch.dev, kept_entries, sc->d_texels, keep ? sc->d_atlas0 : nullptr, keep && whole);
     HIPCHK(c, hipGetLastError());
-    sc->mask_dirty = true; sc->tex_sig_valid = false;
-    patch_changed(c, sc);
+    texels_rewritten(*sc, edit_words(c), keep);
     return B32_OK;
 }
 
 int b32_scene_read_texels(b32_ctx* c, b32_scene* slot, uint32_t tex, void* out) {
     if (!c) return B32_E_ARG;
-    b32_scene* sc = patch_scene_of(c, slot);
+    b32_scene* sc = scene_of(c, slot);
     if (!sc || tex >= sc->nt || tex >= sc->h_tex.size()) return B32_E_ARG;
     const TexDesc& d = sc->h_tex[tex];
     const size_t n = (size_t)d.width * d.height;

@@ -1,7 +1,7 @@
-// b32_patch_tally.h -- host only: what the in-place edits of a resident scene (b32_patch.hip) decide on the host, in a form a stand-alone
-// program can include (tests/cpp/patch_tally_host.cpp, built with the sanitizers): the record rules of b32_scene_patch_* and the blend
-// bookkeeping upload_geometry, b32_scene_upload_rgba and b32_scene_build_skeleton (b32_scene.hip) derive from a slot's faces, kept
-// incrementally while faces are patched.
+// b32_patch_tally.h -- host only, in a form a stand-alone program can include (tests/cpp/patch_tally_host.cpp, built with the sanitizers):
+// the record rules of b32_scene_patch_* and the blend rule -- what a slot's faces, textures and tail say about its transparent pass.
+// Every writer of a slot (b32_scene_state.h) takes its blend bookkeeping from here: an upload counts the faces once (tally_faces), a face
+// patch keeps the count incrementally (tally_face), the room mesh counts from its own tables.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,10 +28,10 @@ inline bool patch_rect_ok(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32
     return w && h && (uint64_t)x + w <= tex_w && (uint64_t)y + h <= tex_h;
 }
 
-// upload_geometry's face loop as three counters over the BODY's faces:
+// The face rule as three counters over the BODY's faces:
 //   own    faces whose own blend mode or editor alpha puts them in the transparent pass (may_blend)
 //   any    ... counting the faces a texture's blend mode puts there too (blend_faces; render.rs:2403-2415)
-//   alpha  faces with editor_alpha < 255 (b32_scene_upload_rgba: blend8)
+//   alpha  faces with editor_alpha < 255 (the 8-bit path's blend8)
 struct FaceTally { uint32_t own = 0, any = 0, alpha = 0; };
 // tex_blends(t): texture t resolves and its blend mode is not Opaque (the caller knows the slot's textures)
 template <class TexBlends>
@@ -50,29 +50,44 @@ inline FaceTally tally_faces(const B32Face* f, uint32_t nf, TexBlends tex_blends
     return t;
 }
 
-// The slot's blend bookkeeping (b32_scene: may_blend, blend8, blend_faces and the body_* copies kept while there is a tail).
+// The slot's blend bookkeeping (b32::SceneState inherits it): may_blend, blend8 and blend_faces of the whole slot, and the same three of
+// the body alone, which mean something only while there is a tail.
 struct SlotBlend {
-    bool may_blend, blend8; uint32_t blend_faces;
-    bool body_may_blend, body_blend8; uint32_t body_blend_faces;
+    bool may_blend = true;              // some face / texture can produce a transparent-pass surface (render.rs:2403-2415)
+    bool blend8 = false;                // 8-bit path: some texel blends or some face has editor_alpha < 255 -> ordered walk
+    uint32_t blend_faces = 0;           // faces that their own blend mode / editor alpha or their texture's blend mode puts in the transparent pass
+    bool body_may_blend = false, body_blend8 = false; uint32_t body_blend_faces = 0;
 };
-// ... as a fresh upload of the body's faces, followed by the same b32_scene_build_skeleton, leaves it.  `cur` is what the slot holds
-// now: an RGB555 upload leaves blend8 alone and an 8-bit-colour one sets may_blend = false; the tail's part is the difference between
-// the slot's and the body's face count.
-inline SlotBlend tally_slot(const FaceTally& body, const SlotBlend& cur, bool fmt8, bool any_texture_blends, bool blend_texels8, bool has_tail) {
+// THE blend rule: what a mesh without a tail whose faces count `body` leaves.  `cur` is what the slot holds now: an RGB555 mesh leaves
+// blend8 alone, an 8-bit-colour one sets may_blend = false, and neither touches the body_* copies.
+inline SlotBlend blend_fresh(const FaceTally& body, const SlotBlend& cur, bool fmt8, bool any_texture_blends, bool blend_texels8) {
     SlotBlend s = cur;
-    const uint32_t tail_faces = has_tail ? cur.blend_faces - cur.body_blend_faces : 0u;
-    const uint32_t faces = body.any;
-    const bool may_blend = fmt8 ? false : (body.own != 0 || any_texture_blends);
-    const bool blend8 = fmt8 ? (blend_texels8 || body.alpha != 0) : cur.blend8;
-    if (has_tail) {
-        s.body_blend_faces = faces; s.body_may_blend = may_blend; s.body_blend8 = fmt8 ? blend8 : cur.body_blend8;
-        s.blend_faces = faces + tail_faces;
-        if (fmt8) s.blend8 = blend8 || tail_faces != 0;
-        else s.may_blend = may_blend || tail_faces != 0;
-    } else {
-        s.blend_faces = faces; s.may_blend = may_blend; s.blend8 = blend8;
-    }
+    s.blend_faces = body.any;
+    s.may_blend = fmt8 ? false : (body.own != 0 || any_texture_blends);
+    if (fmt8) s.blend8 = blend_texels8 || body.alpha != 0;
     return s;
+}
+// ... and a tail behind it (b32_scene_build_skeleton) with tail_faces transparent-pass faces: s.body_* hold the body's three, the slot's
+// are body + tail.  An octahedron blends by editor_alpha alone: blend8 on the 8-bit path, may_blend on the RGB555 one.
+inline SlotBlend blend_with_tail(SlotBlend s, uint32_t tail_faces, bool fmt8) {
+    s.blend_faces = s.body_blend_faces + tail_faces;
+    if (fmt8) s.blend8 = s.body_blend8 || tail_faces != 0;
+    else s.may_blend = s.body_may_blend || tail_faces != 0;
+    return s;
+}
+inline SlotBlend blend_save_body(SlotBlend s) {     // the first tail of a mesh: what the slot holds is the body's
+    s.body_may_blend = s.may_blend; s.body_blend8 = s.blend8; s.body_blend_faces = s.blend_faces;
+    return s;
+}
+// The slot after its body's faces were edited: as a fresh upload of them, followed by the same b32_scene_build_skeleton, leaves it.  The
+// tail's part is the difference between the slot's and the body's face count.
+inline SlotBlend tally_slot(const FaceTally& body, const SlotBlend& cur, bool fmt8, bool any_texture_blends, bool blend_texels8, bool has_tail) {
+    if (!has_tail) return blend_fresh(body, cur, fmt8, any_texture_blends, blend_texels8);
+    const SlotBlend held{ cur.body_may_blend, cur.body_blend8, cur.body_blend_faces };
+    const SlotBlend b = blend_fresh(body, held, fmt8, any_texture_blends, blend_texels8);    // the rule on the body's three ...
+    SlotBlend s = cur;
+    s.body_may_blend = b.may_blend; s.body_blend8 = b.blend8; s.body_blend_faces = b.blend_faces;
+    return blend_with_tail(s, cur.blend_faces - cur.body_blend_faces, fmt8);                 // ... and the same tail on top again
 }
 
 }  // namespace b32

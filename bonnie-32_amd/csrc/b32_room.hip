@@ -282,46 +282,34 @@ int b32_room_mesh_counts(const b32_room* room, uint32_t* nv, uint32_t* nf) {
     return B32_OK;
 }
 
-// Leaves the slot as upload_geometry and b32_scene_pose would (b32_scene.hip); the ordering argument is the pose's.
+// Another mesh in the slot, like an upload's (geometry_replaced); the ordering argument is the pose's.
 int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
     if (!c || !room || !room->have_mats) return B32_E_ARG;
-    b32_scene* sc = slot ? slot : &c->scene;
-    if (!sc->have_scene) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn is redrawn from the resident geometry: settle it before that changes (b32_scene_upload)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    b32_scene* sc = scene_of(c, slot);
+    if (!sc) return B32_E_ARG;
+    { const int rcs = edit_begin(c); if (rcs) return rcs; }
     const uint32_t n = room->n, nv = room->h_first[n].x, nf = room->h_first[n].y;
     int rc;
     if ((rc = ensure(c, sc->d_verts, sc->cap_verts, (size_t)nv + 1))) return rc;
     if ((rc = ensure(c, sc->d_faces, sc->cap_faces, (size_t)nf + 1))) return rc;
     if (!sc->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_consts), 16 * sizeof(uint32_t)));
-    {   // upload_geometry's face loop: editor_alpha is 255, so a face's own part is its blend mode; a texture's blend mode adds to it
-        bool tex_blend = false;
-        for (const TexDesc& d : sc->h_tex) tex_blend |= d.blend_mode != B32_BLEND_OPAQUE;
-        uint32_t nbt = room->own_blend_faces;
-        if (tex_blend) {
-            nbt = 0;
-            auto blends = [&](uint32_t t) { return t != B32_NO_TEXTURE && t < sc->nt && t < sc->h_tex.size() && sc->h_tex[t].blend_mode != B32_BLEND_OPAQUE; };
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint32_t sides = room_mesh_sides(room->h_mode[i]);
-                const bool own = room->h_blend[i] != B32_BLEND_OPAQUE, flat = room->h_kind[i] < 2u;
-                nbt += (own || blends(room->h_tex[2 * (size_t)i])) ? sides : 0u;
-                nbt += (own || blends(room->h_tex[2 * (size_t)i + (flat ? 1 : 0)])) ? sides : 0u;
-            }
+    // the face tally from the room's own tables (the faces exist on the device only): editor_alpha is 255, so a face's own part is its
+    // blend mode; a texture's blend mode adds to it
+    FaceTally tally;
+    tally.own = tally.any = room->own_blend_faces;
+    if (sc->tex_blend_any) {
+        tally.any = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t sides = room_mesh_sides(room->h_mode[i]);
+            const bool own = room->h_blend[i] != B32_BLEND_OPAQUE, flat = room->h_kind[i] < 2u;
+            tally.any += (own || tex_blends(sc, room->h_tex[2 * (size_t)i])) ? sides : 0u;
+            tally.any += (own || tex_blends(sc, room->h_tex[2 * (size_t)i + (flat ? 1 : 0)])) ? sides : 0u;
         }
-        sc->blend_faces = nbt;
-        if (sc->fmt8) { sc->may_blend = false; sc->blend8 = sc->blend_texels8; }        // (b32_scene_upload_rgba: no face has editor_alpha < 255)
-        else sc->may_blend = room->own_blend_faces != 0 || tex_blend;
     }
-    if (sc->nf != nf) { sc->direct_cap_opaque = 0; sc->direct_ntiles = 0; sc->direct_ok = true; }
+    const bool same_nf = sc->nf == nf;
     sc->nv = nv; sc->nf = nf;
-    sc->have_rig = false;
-    sc->tail_v = 0; sc->tail_f = 0;
-    sc->h_faces_valid = false;                          // (a face patch fetches the new faces)
-    sc->local_sort_ok = true;
-    sc->pos_valid = false; sc->lit_valid = false; sc->band_frames = 0;
     if ((rc = ensure_work(c, nf))) return rc;
-    sc->gen = ++c->gen_counter;
+    geometry_replaced(*sc, edit_words(c), same_nf, blend_fresh(tally, *sc, sc->fmt8, sc->tex_blend_any, sc->blend_texels8));
     RoomMeshArgs a{};
     a.grid = room->grid; a.faces = room->faces; a.mats = room->mats; a.first = room->first;
     a.verts = sc->d_verts; a.out_faces = sc->d_faces; a.consts = sc->d_consts;
@@ -329,7 +317,6 @@ int b32_room_build_mesh(b32_ctx* c, b32_room* room, b32_scene* slot) {
     const uint32_t groups = (uint32_t)(((unsigned long long)n * ROOM_MESH_SLOTS + 255u) / 256u);
     hipLaunchKernelGGL(k_room_mesh, dim3(groups ? groups : 1u), dim3(256), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
-    c->side_dirty = true;
     return B32_OK;
 }
 

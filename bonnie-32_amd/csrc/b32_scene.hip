@@ -74,41 +74,29 @@ int ensure_work(b32_ctx* c, uint32_t nf) {
     return B32_OK;
 }
 
-static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf) {
+// What the three uploads end with, behind their texel walk (the textures are laid out: the face tally asks them): vertices and faces to
+// the device, the slot's derived state (geometry_replaced), and the slot holds a scene again.
+static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf, bool fmt8) {
     if ((nv && !v) || (nf && !f)) return B32_E_ARG;
+    b32_scene& sc = c->scene;
     int rc;
-    if ((rc = ensure(c, c->scene.d_verts, c->scene.cap_verts, (size_t)nv + 1))) return rc;
-    if ((rc = ensure(c, c->scene.d_faces, c->scene.cap_faces, (size_t)nf + 1))) return rc;
-    {   // can any face end up in the transparent pass? (face blend mode / editor alpha; texture blend modes are added by the callers)
-        uint32_t nb = 0;
-        uint32_t nbt = 0;                    // ... counting the faces a texture's blend mode puts there too (render.rs:2403-2415)
-        for (uint32_t i = 0; i < nf; ++i) {
-            const bool own = f[i].blend_mode != B32_BLEND_OPAQUE || f[i].editor_alpha < 255;
-            const uint32_t t = f[i].texture_id;
-            nb += own ? 1u : 0u;
-            nbt += (own || (t != B32_NO_TEXTURE && t < c->scene.nt && t < c->scene.h_tex.size() && c->scene.h_tex[t].blend_mode != B32_BLEND_OPAQUE)) ? 1u : 0u;
-        }
-        c->scene.may_blend = nb != 0; c->scene.blend_faces = nbt;
-    }
-    if ((rc = h2d(c, c->scene.d_verts, v, (size_t)nv * sizeof(B32Vertex)))) return rc;
-    if ((rc = h2d(c, c->scene.d_faces, f, (size_t)nf * sizeof(B32Face)))) return rc;
-    // a mesh of another size: tile regions sized afresh (the per-frame drop-in call uploads the same mesh again and again: what an
-    // overflowing frame taught the context stays)
-    if (c->scene.nf != nf) { c->scene.direct_cap_opaque = 0; c->scene.direct_ntiles = 0; c->scene.direct_ok = true; }
-    c->scene.nv = nv; c->scene.nf = nf;
-    c->scene.have_rig = false;                          // (the rig belongs to the vertices it was set for)
-    c->scene.tail_v = 0; c->scene.tail_f = 0;           // (... and so do the bone octahedra behind them)
-    c->scene.h_faces_valid = false;                     // (... and the host copy a face patch keeps)
-    c->scene.local_sort_ok = true;
-    c->scene.pos_valid = false; c->scene.lit_valid = false; c->scene.band_frames = 0;
+    if ((rc = ensure(c, sc.d_verts, sc.cap_verts, (size_t)nv + 1))) return rc;
+    if ((rc = ensure(c, sc.d_faces, sc.cap_faces, (size_t)nf + 1))) return rc;
+    const FaceTally tally = tally_faces(f, nf, [&sc](uint32_t t) { return tex_blends(&sc, t); });
+    if ((rc = h2d(c, sc.d_verts, v, (size_t)nv * sizeof(B32Vertex)))) return rc;
+    if ((rc = h2d(c, sc.d_faces, f, (size_t)nf * sizeof(B32Face)))) return rc;
+    const bool same_nf = sc.nf == nf;
+    sc.nv = nv; sc.nf = nf;
     if ((rc = ensure_work(c, nf))) return rc;
-    c->scene.gen = ++c->gen_counter;
+    geometry_replaced(sc, edit_words(c), same_nf, blend_fresh(tally, sc, fmt8, sc.tex_blend_any, sc.blend_texels8));
     c->h_consts[0] = nf;
-    if (!c->scene.d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->scene.d_consts), 16 * sizeof(uint32_t)));   // (swapped away with a scene)
-    if ((rc = h2d(c, c->scene.d_consts, c->h_consts, sizeof(c->h_consts)))) return rc;
+    if (!sc.d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc.d_consts), 16 * sizeof(uint32_t)));   // (swapped away with a scene)
+    if ((rc = h2d(c, sc.d_consts, c->h_consts, sizeof(c->h_consts)))) return rc;
     // the caller may reuse its host buffers as soon as an upload call returns; the drop-in render calls return only after
     // b32_frame_finish has synchronised the stream, so they skip this extra round trip
     if (!c->defer_upload_sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+    sc.fmt8 = fmt8;
+    sc.have_scene = true;
     return B32_OK;
 }
 
@@ -117,11 +105,10 @@ static int upload_geometry(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B3
 // texture; CHEAP 0.19 ms at K = 256, 0.220 at 64, 0.246 at 32, 0.307 at 16, 0.46 at 8.  (b32_set_cheap_threshold: that tool's switch.)
 
 static int layout_textures(b32_ctx* c, uint32_t nt, const uint32_t* w, const uint32_t* h, const uint32_t* blend, size_t* total, bool rgba = false) {
+    pool_replaced(c->scene);                         // (first: a layout that fails half-way leaves nothing that describes the old pool)
     if (nt > 65534) return B32_E_UNSUPPORTED;        // the surface record holds the texture slot in 16 bits
     c->scene.h_tex.resize(nt);
     c->scene.tex_blend_any = false;
-    c->scene.atlas_idx_bytes = 0;                         // (only b32_scene_upload_indexed with one texture keeps the index atlas)
-    c->scene.h_texels32_valid = false;                    // (the pool is rewritten: a texel patch of an 8-bit-colour scene fetches it again)
     size_t off = 0;
     for (uint32_t i = 0; i < nt; ++i) {
         if (w[i] > 65535 || h[i] > 65535) return B32_E_ARG;
@@ -131,7 +118,7 @@ static int layout_textures(b32_ctx* c, uint32_t nt, const uint32_t* w, const uin
         if (off > 0x7FFFFFFFull) return B32_E_ARG;
     }
     *total = off + 8;
-    c->scene.pool_texels = (uint32_t)off; c->scene.mask_dirty = true;
+    c->scene.pool_texels = (uint32_t)off;
     int rc;
     if ((rc = ensure(c, c->scene.d_texmask, c->scene.cap_texmask, off / 32 + 4))) return rc;
     if (rgba) { if ((rc = ensure(c, c->scene.d_texels32, c->scene.cap_texels32, *total))) return rc; }
@@ -161,18 +148,28 @@ static uint64_t hash_bytes(const void* data, size_t n) {
     return r;
 }
 
-int b32_scene_upload(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf, const B32Texture15* tex, uint32_t nt) {
+// What the three uploads begin with: the resident scene is being replaced (it holds none until upload_geometry has finished), and the
+// textures' dimensions and blend modes as layout_textures takes them.  A texture without texels -- pixels.is_empty() -- samples as
+// TRANSPARENT and takes no room in the pool.
+namespace {
+struct TexDims {
+    std::vector<uint32_t> w, h, bl;
+    void set(uint32_t i, uint32_t width, uint32_t height, uint32_t blend, bool has_texels) { w[i] = has_texels ? width : 0u; h[i] = has_texels ? height : 0u; bl[i] = blend; }
+};
+}
+static int upload_begin(b32_ctx* c, const void* tex, uint32_t nt, TexDims& d) {
     if (!c || (nt && !tex)) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
-    // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rc = edit_begin(c); if (rc) return rc; }
     c->scene.have_scene = false;
-    std::vector<uint32_t> w(nt), h(nt), bl(nt);
-    for (uint32_t i = 0; i < nt; ++i) {
-        w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
-        if (!tex[i].pixels) w[i] = h[i] = 0;                                // pixels.is_empty() -> sample() returns TRANSPARENT
-    }
+    d.w.resize(nt); d.h.resize(nt); d.bl.resize(nt);
+    return B32_OK;
+}
+
+int b32_scene_upload(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf, const B32Texture15* tex, uint32_t nt) {
+    TexDims d;
+    { const int rcb = upload_begin(c, tex, nt, d); if (rcb) return rcb; }
+    for (uint32_t i = 0; i < nt; ++i) d.set(i, tex[i].width, tex[i].height, tex[i].blend_mode, tex[i].pixels != nullptr);
+    const std::vector<uint32_t>&w = d.w, &h = d.h, &bl = d.bl;
     // texture cache: the same set as the pool holds (pointer, size, blend mode, content hash of every texture)?
     std::vector<TexSig> sig(nt);
     for (uint32_t i = 0; i < nt; ++i) sig[i] = { tex[i].pixels, w[i], h[i], bl[i], hash_bytes(tex[i].pixels, (size_t)w[i] * h[i] * 2) };
@@ -183,7 +180,6 @@ int b32_scene_upload(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face*
     }
     int rc;
     if (!hit) {
-        c->scene.tex_sig_valid = false;
         size_t total = 0;
         rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total);
         if (rc) return rc;
@@ -198,28 +194,16 @@ int b32_scene_upload(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face*
         }
         c->scene.tex_sig.swap(sig); c->scene.tex_sig_valid = true;
     }
-    if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
-    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->scene.may_blend = true;
-    c->scene.fmt8 = false;
-    c->scene.have_scene = true;
-    return B32_OK;
+    return upload_geometry(c, v, nv, f, nf, false);
 }
 
 int b32_scene_upload_rgba(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf, const B32Texture* tex, uint32_t nt) {
-    if (!c || (nt && !tex)) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
-    // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    c->scene.have_scene = false;
-    std::vector<uint32_t> w(nt), h(nt), bl(nt);
-    for (uint32_t i = 0; i < nt; ++i) {
-        w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
-        if (!tex[i].pixels) w[i] = h[i] = 0;                                // pixels.is_empty() -> Color::TRANSPARENT
-    }
+    TexDims d;
+    { const int rcb = upload_begin(c, tex, nt, d); if (rcb) return rcb; }
+    for (uint32_t i = 0; i < nt; ++i) d.set(i, tex[i].width, tex[i].height, tex[i].blend_mode, tex[i].pixels != nullptr);
+    const std::vector<uint32_t>&w = d.w, &h = d.h;
     size_t total = 0;
-    c->scene.tex_sig_valid = false;                                               // (the pool is rewritten below)
-    int rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total, true);
+    int rc = layout_textures(c, nt, w.data(), h.data(), d.bl.data(), &total, true);
     if (rc) return rc;
     c->scene.cheap_ok = true;
     bool blend_texels = false;
@@ -234,32 +218,17 @@ int b32_scene_upload_rgba(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32
         }
         if (n == 0 || skippable * c->cheap_den > n) c->scene.cheap_ok = false;
     }
-    if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
-    bool alpha_faces = false;
-    for (uint32_t i = 0; i < nf && !alpha_faces; ++i) alpha_faces = f[i].editor_alpha < 255;
     c->scene.blend_texels8 = blend_texels;
-    c->scene.blend8 = blend_texels || alpha_faces;
-    c->scene.may_blend = false;
-    c->scene.fmt8 = true;
-    c->scene.have_scene = true;
-    return B32_OK;
+    return upload_geometry(c, v, nv, f, nf, true);
 }
 
 int b32_scene_upload_indexed(b32_ctx* c, const B32Vertex* v, uint32_t nv, const B32Face* f, uint32_t nf, const B32IndexedTexture* tex, uint32_t nt) {
-    if (!c || (nt && !tex)) return B32_E_ARG;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn (overflowed tile regions / pair buffers) is drawn from the RESIDENT scene: settle it
-    // before that scene is replaced, or the redraw would draw the new mesh in its place (and the new mesh twice)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
-    c->scene.have_scene = false;
-    std::vector<uint32_t> w(nt), h(nt), bl(nt);
-    for (uint32_t i = 0; i < nt; ++i) {
-        w[i] = tex[i].width; h[i] = tex[i].height; bl[i] = tex[i].blend_mode;
-        if (!tex[i].indices || !tex[i].clut) w[i] = h[i] = 0;
-    }
+    TexDims d;
+    { const int rcb = upload_begin(c, tex, nt, d); if (rcb) return rcb; }
+    for (uint32_t i = 0; i < nt; ++i) d.set(i, tex[i].width, tex[i].height, tex[i].blend_mode, tex[i].indices && tex[i].clut);
+    const std::vector<uint32_t>&w = d.w, &h = d.h;
     size_t total = 0;
-    c->scene.tex_sig_valid = false;                                               // (the pool is rewritten below)
-    int rc = layout_textures(c, nt, w.data(), h.data(), bl.data(), &total);
+    int rc = layout_textures(c, nt, w.data(), h.data(), d.bl.data(), &total);
     if (rc) return rc;
     c->scene.cheap_ok = true;
     for (uint32_t i = 0; i < nt; ++i) {
@@ -294,11 +263,7 @@ int b32_scene_upload_indexed(b32_ctx* c, const B32Vertex* v, uint32_t nv, const 
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if ((size_t)skippable * c->cheap_den > n) c->scene.cheap_ok = false;
     }
-    if ((rc = upload_geometry(c, v, nv, f, nf))) return rc;
-    for (uint32_t i = 0; i < nt; ++i) if (bl[i] != B32_BLEND_OPAQUE) c->scene.may_blend = true;
-    c->scene.fmt8 = false;
-    c->scene.have_scene = true;
-    return B32_OK;
+    return upload_geometry(c, v, nv, f, nf, false);
 }
 
 // ------------------------------------------------------------------ scene slots (several resident scenes per context)
@@ -325,10 +290,6 @@ int b32_scene_swap(b32_ctx* c, b32_scene* sl) {
 }
 
 // ------------------------------------------------------------------ bones (b32_pose.hip has the kernels and the why)
-static b32_scene* scene_of(b32_ctx* c, b32_scene* slot) {
-    b32_scene* sc = slot ? slot : &c->scene;
-    return sc->have_scene ? sc : nullptr;
-}
 int b32_scene_set_rig(b32_ctx* c, b32_scene* slot, const uint16_t* bone_of_vertex) {
     if (!c) return B32_E_ARG;
     b32_scene* sc = scene_of(c, slot);
@@ -361,15 +322,11 @@ int b32_scene_pose(b32_ctx* c, b32_scene* slot, const B32Bone* bones, uint32_t n
     b32_scene* sc = scene_of(c, slot);
     if (!sc || !sc->have_rig || (n_bones && !bones)) return B32_E_ARG;
     if (n_bones > B32_MAX_BONES) return B32_E_UNSUPPORTED;
-    (void)hipSetDevice(c->device);
-    // a pending frame that may still be redrawn is redrawn from the resident vertices: settle it before they change (b32_scene_upload)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rc = edit_begin(c); if (rc) return rc; }
     launch_pose(c->stream, sc->d_rest, sc->d_bone_of, sc->d_verts, sc->body_nv(), bones, n_bones);
     HIPCHK(c, hipGetLastError());
     sc->h_bones.assign(bones, bones + n_bones);          // (b32_scene_patch_vertices poses a patched rest vertex with it)
-    c->side_dirty = true;
-    sc->pos_valid = false; sc->lit_valid = false;       // (frame_positions packs again on the next frame: band_frames stays)
-    sc->gen = ++c->gen_counter;                          // a merged run that holds this scene is rebuilt
+    vertices_moved(*sc, edit_words(c));
     return B32_OK;
 }
 // ------------------------------------------------------------------ the bone octahedra (b32_skeleton.hip has the kernel and the why)
@@ -392,38 +349,28 @@ int b32_skeleton_counts(const B32SkelBone* bones, uint32_t n_bones, const B32Ske
     if (n_faces) *n_faces = n * SKEL_OCT_FACES;
     return B32_OK;
 }
-// Ordering against the side stream and the bookkeeping are b32_scene_pose's (above).
+// Ordering against the side stream is b32_scene_pose's (above); the slot's derived state is tail_rebuilt's.
 int b32_scene_build_skeleton(b32_ctx* c, b32_scene* slot, const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style) {
     if (!c) return B32_E_ARG;
     b32_scene* sc = scene_of(c, slot);
     if (!sc) return B32_E_ARG;
     { const int rc = skeleton_check(bones, n_bones, style); if (rc) return rc; }
-    (void)hipSetDevice(c->device);
     SkelOct octs[SKEL_MAX_OCTS];
     const uint32_t n_octs = skeleton_octs(bones, n_bones, *style, octs);
-    // a pending frame that may still be redrawn is redrawn from the resident geometry: settle it before that changes (b32_scene_upload)
-    { const int rcs = settle_pending(c); if (rcs) return rcs; }
+    { const int rc = edit_begin(c); if (rc) return rc; }
     const uint32_t bv = sc->body_nv(), bf = sc->body_nf(), nv = bv + n_octs * SKEL_OCT_VERTS, nf = bf + n_octs * SKEL_OCT_FACES;
-    if (!sc->tail_v && !sc->tail_f) { sc->body_blend_faces = sc->blend_faces; sc->body_may_blend = sc->may_blend; sc->body_blend8 = sc->blend8; }
     int rc;
     if ((rc = ensure_keep(c, sc->d_verts, sc->cap_verts, (size_t)nv + 1, bv))) return rc;
     if ((rc = ensure_keep(c, sc->d_faces, sc->cap_faces, (size_t)nf + 1, bf))) return rc;
     if (!sc->d_consts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_consts), 16 * sizeof(uint32_t)));
-    {   // upload_geometry's face loop for the tail: a face with editor_alpha < 255 is a transparent-pass face
-        uint32_t nb = 0;
-        for (uint32_t k = 0; k < n_octs; ++k) nb += octs[k].alpha < 255 ? SKEL_OCT_FACES : 0u;
-        sc->blend_faces = sc->body_blend_faces + nb;
-        if (sc->fmt8) sc->blend8 = sc->body_blend8 || nb != 0;
-        else sc->may_blend = sc->body_may_blend || nb != 0;
-    }
-    if (sc->nf != nf) { sc->direct_cap_opaque = 0; sc->direct_ntiles = 0; sc->direct_ok = true; }
-    sc->nv = nv; sc->nf = nf; sc->tail_v = nv - bv; sc->tail_f = nf - bf;
-    sc->pos_valid = false; sc->lit_valid = false;
+    uint32_t tail_blend_faces = 0;                       // the face rule for the tail: editor_alpha < 255 is all an octahedron blends by
+    for (uint32_t k = 0; k < n_octs; ++k) tail_blend_faces += octs[k].alpha < 255 ? SKEL_OCT_FACES : 0u;
     if ((rc = ensure_work(c, nf))) return rc;
     launch_skeleton_mesh(c->stream, octs, n_octs, sc->d_verts, bv, sc->d_faces, bf, sc->d_consts);
     HIPCHK(c, hipGetLastError());
-    c->side_dirty = true;
-    sc->gen = ++c->gen_counter;
+    const bool same_nf = sc->nf == nf;
+    sc->nv = nv; sc->nf = nf;
+    tail_rebuilt(*sc, edit_words(c), same_nf, nv - bv, nf - bf, tail_blend_faces, sc->fmt8);
     return B32_OK;
 }
 int b32_skeleton_items(const B32SkelBone* bones, uint32_t n_bones, const B32SkeletonStyle* style, B32WorldItem* out, uint32_t cap, uint32_t* n_out) {

@@ -87,6 +87,15 @@ void h_tally_slot(const uint32_t* tally3, uint32_t* state6, int fmt8, int any_te
     const SlotBlend s = tally_slot(t, cur, fmt8 != 0, any_texture_blends != 0, blend_texels8 != 0, has_tail != 0);
     state6[0] = s.may_blend; state6[1] = s.blend8; state6[2] = s.blend_faces; state6[3] = s.body_may_blend; state6[4] = s.body_blend8; state6[5] = s.body_blend_faces;
 }
+// what upload_geometry does with the faces of an upload: one tally_faces pass, then blend_fresh on what the slot held (state6, in and out)
+void h_fresh_upload(const B32Face* f, uint32_t nf, const uint32_t* tex_blend, uint32_t nt, uint32_t* state6, int fmt8, int blend_texels8) {
+    bool any_texture_blends = false;
+    for (uint32_t k = 0; k < nt; ++k) any_texture_blends |= tex_blend[k] != B32_BLEND_OPAQUE;
+    const FaceTally t = tally_faces(f, nf, [&](uint32_t k) { return k < nt && tex_blend[k] != B32_BLEND_OPAQUE; });
+    const SlotBlend cur{ state6[0] != 0, state6[1] != 0, state6[2], state6[3] != 0, state6[4] != 0, state6[5] };
+    const SlotBlend s = blend_fresh(t, cur, fmt8 != 0, any_texture_blends, blend_texels8 != 0);
+    state6[0] = s.may_blend; state6[1] = s.blend8; state6[2] = s.blend_faces; state6[3] = s.body_may_blend; state6[4] = s.body_blend8; state6[5] = s.body_blend_faces;
+}
 }
 '''
 # (g++ forms fused multiply-adds from -O2 on, and only where the target has them)
@@ -458,6 +467,40 @@ def test_tally_program_runs_clean_under_the_sanitizers(tmp_path):
     exe = tmp_path / "patch_tally_host"
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
                     os.path.join(ROOT, "tests", "cpp", "patch_tally_host.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "ok" in r.stdout
+
+
+@pytest.mark.parametrize("fmt8", [False, True], ids=["rgb555", "rgba8"])
+@pytest.mark.parametrize("tex_blend", [[abi.OPAQUE] * 3, [abi.OPAQUE, abi.ADD, abi.OPAQUE]], ids=["opaque_textures", "blending_texture"])
+def test_fresh_upload_state_equals_the_scratch_state(fmt8, tex_blend):
+    """The uploads take their blend bookkeeping from the rule the patches use (tally_faces, then blend_fresh): for random faces, all-opaque
+    ones, and opaque ones with one alpha face it equals _scratch_state, whatever the slot held before; what an upload leaves alone (blend8
+    on an RGB555 scene, the body's copies) stays."""
+    lib = _host()
+    rng = np.random.default_rng(31 + fmt8)
+    tb = np.ascontiguousarray(tex_blend, np.uint32)
+    plain = b32.make_faces(60, 0); plain["v"] = np.arange(180).reshape(60, 3)
+    dim = plain.copy(); dim["editor_alpha"][17] = 254
+    textured = plain.copy(); textured["texture_id"][5:9] = 1
+    for faces in (_random_faces(rng, 200), _random_faces(rng, 1), plain, dim, textured, plain[:0]):
+        for blend_texels8 in (False, True):
+            for held in ([1, 1, 77, 1, 1, 55], [0, 0, 0, 0, 0, 0]):
+                state = np.array(held, np.uint32)
+                lib.h_fresh_upload(_p(faces) if len(faces) else None, U32(len(faces)), _p(tb), U32(len(tb)), _p(state), int(fmt8), int(blend_texels8))
+                want = _scratch_state(faces, tex_blend, fmt8, blend_texels8)
+                assert (bool(state[0]), int(state[2])) == (want[0], want[2]), (state, want)
+                assert bool(state[1]) == (want[1] if fmt8 else bool(held[1])), (state, want)
+                assert state[3:].tolist() == held[3:]
+
+
+def test_scene_state_program_runs_clean_under_the_sanitizers(tmp_path):
+    """tests/cpp/scene_state_host.cpp -- every sequence of four writers of a slot, the rules of b32_scene_state.h against the assignments
+    the writers made by hand before -- built with the address and undefined-behaviour sanitizers, ends with every field equal."""
+    exe = tmp_path / "scene_state_host"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "scene_state_host.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert "ok" in r.stdout
