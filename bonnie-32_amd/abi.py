@@ -104,6 +104,18 @@ class B32RoomOverlay(C.Structure):
 
 assert C.sizeof(B32RoomHover) == 48 and C.sizeof(B32RoomOverlay) == 100
 
+# B32ObjectPart / B32ObjectItem (the world editor's object overlays from resident asset parts, b32_draw_object_overlays): kind = OBJECT_*
+OBJECT_PART_HIDDEN = 1
+OBJECT_WIRE, OBJECT_BOX_MESH, OBJECT_BOX = range(3)
+OBJECT_BOX_SLOTS = 12
+OBJECT_PART_DTYPE = np.dtype([("slot", "<u8"), ("topology", "<u8"), ("flags", "<u4"), ("_pad", "<u4")])
+OBJECT_ITEM_DTYPE = np.dtype([("cos_f", "<f4"), ("sin_f", "<f4"), ("world_pos", "<f4", 3), ("first_part", "<u4"), ("n_parts", "<u4"),
+                              ("box_min", "<f4", 3), ("box_max", "<f4", 3), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("blend", "u1"),
+                              ("kind", "u1"), ("_pad", "u1", 3)])
+assert OBJECT_PART_DTYPE.itemsize == 24 and OBJECT_ITEM_DTYPE.itemsize == 60
+SCENE_BOUNDS_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("has_verts", "<u4"), ("_pad", "<u4")])     # b32_scene_bounds_async's 32 bytes
+assert SCENE_BOUNDS_DTYPE.itemsize == 32
+
 # B32PickHit (b32_pick_meshes): hit == 0 -> tri = 0xFFFFFFFF, depth = 0
 PICK_HIT_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("depth", "<f4"), ("_pad", "<u4")])
 assert PICK_HIT_DTYPE.itemsize == 16
@@ -314,6 +326,11 @@ SYMBOLS = [
     ("b32_draw_room_overlay", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     ("b32_room_overlay_project_batch", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_room_overlay_record_count", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    ("b32_draw_object_overlays", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32]),
+    ("b32_object_overlay_project_batch", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_object_overlay_record_count", C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("b32_scene_bounds", C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    ("b32_scene_bounds_async", C.c_int, [_P, _P, _P, C.POINTER(C.c_uint64)]),
     ("b32_render_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P]),
     ("b32_scene_upload_rgba", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32]),
     ("b32_render_scene", C.c_int, [_P, _P, _P, _P]),

@@ -3,6 +3,7 @@
 #include "b32_host.h"
 #include "b32_overlay_body.h"
 #include "b32_room_overlay_body.h"
+#include "b32_object_overlay_body.h"
 
 extern "C" {
 
@@ -340,9 +341,9 @@ static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32
 }
 
 // ------------------------------------------------------------------ record producers
-// Four features turn caller input into B32Prim records on the device -- in the primitive pass's record buffer, so the records never visit
+// Five features turn caller input into B32Prim records on the device -- in the primitive pass's record buffer, so the records never visit
 // the host -- and hand them to the ordered tile pass: world items, the editor's gizmos, the modeler's mesh overlays and the world editor's
-// room overlays.  Each also has a stage tap (b32_*_project_batch) that runs the same kernel into scratch memory and copies the records to
+// room and object overlays.  Each also has a stage tap (b32_*_project_batch) that runs the same kernel into scratch memory and copies the records to
 // the host.  A producer is a struct that holds the call's arguments and states only what is its own:
 //   prepare(c, w, h)         everything that can fail on the arguments alone: the whole batch checked, the records laid out and counted
 //                            (`total`), the args block `a` filled but for device pointers, the host rows to put on the device (`rows`,
@@ -472,10 +473,8 @@ int MeshOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
     total = l.total;
     if (l.total > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
     view_fill(a.v, *cam, w, h, ortho);
-    const bool packed = slot->pos_valid && slot->d_pos12;
-    a.pos = packed ? slot->d_pos12 : reinterpret_cast<const float*>(slot->d_verts);
-    a.stride = packed ? 3u : (uint32_t)(sizeof(B32Vertex) / sizeof(float));
-    a.nv = slot->body_nv();                             // (bone octahedra behind the mesh get no brackets and no dots)
+    a.pos = slot_positions(slot, a.stride);
+    a.nv = slot->body_nv();                            // (bone octahedra behind the mesh get no brackets and no dots)
     if (topo) { a.he = topo->he; a.poly_start = topo->poly_start; a.poly_verts = topo->poly_verts; a.np = np; a.nh = nh; }
     a.o = *o;
     a.at_brackets = (uint32_t)l.brackets; a.at_edges = (uint32_t)l.edges; a.at_dots = (uint32_t)l.dots;
@@ -559,6 +558,69 @@ int RoomOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
     if (sec & B32_ROOM_OVERLAY_SELECTED) { a.g_sel_faces = groups(o->n_faces); a.g_sel_edges = groups(o->n_edges); }
     if (l.gate) { a.g_preview = groups(room->n); a.g_points = groups(o->n_points); }
     rows = lw.data(); n_rows = (uint32_t)lw.size();
+    return B32_OK;
+}
+
+// ------------------------------------------------------------------ the world editor's object overlays (b32_object_overlay.hip)
+// (viewport_3d.rs:255-291, :7658-7697, asset.rs:288-312) Made into records by k_object_overlay from the parts' vertices and half-edges as
+// they are on the device.  The rows are one run of words in c->overlay_pairs: the ObjectRows, the table of bounds blocks of the BOX_MESH
+// rows, then k_scene_bounds' rows for the slots whose bounds are stale (c->bounds_stale) -- reduced in bind, in front of the kernel, into
+// the slot's own block for the draw and for the tap alike.  Adds into the gizmo entry's counters (b32_gizmo_counts).
+struct ObjectOverlayProducer : Producer<ObjectOverlayArgs, uint32_t, 0> {
+    const B32Camera* cam; const B32ObjectPart* parts; uint32_t n_parts; const B32ObjectItem* items; uint32_t n_items;
+    uint32_t w_bounds = 0, w_stale = 0;                                       // first word of the second and of the third table
+    int prepare(b32_ctx* c, uint32_t w, uint32_t h);
+    int bind(b32_ctx* c, B32Prim* out, const uint32_t* in, Scratch*) {
+        a.out = out;
+        a.rows = reinterpret_cast<const ObjectRow*>(in);
+        a.bounds = reinterpret_cast<const OverlayBounds* const*>(in + w_bounds);
+        { const int rc = scene_bounds_run(c, reinterpret_cast<const BoundsRow*>(in + w_stale)); if (rc) return rc; }
+        return counts_bind(c, c->gizmo_counts, a.counts);
+    }
+    void launch(hipStream_t s, const uint32_t*) const { launch_object_overlay(s, a); }
+    static Staged<uint32_t>& staged(b32_ctx* c) { return c->overlay_sel; }
+};
+int ObjectOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
+    if (!cam || !w || !h) return B32_E_ARG;
+    c->bounds_stale.clear();
+    std::vector<ObjectPartView> views;
+    object_part_views(parts, n_parts, views);
+    ObjectOverlayPlan plan;
+    int rc;
+    if ((rc = object_overlay_plan(parts, views.data(), n_parts, items, n_items, false, plan))) return rc;      // the whole batch checked
+    total = plan.total;
+    if (!total) return B32_OK;
+    (void)hipSetDevice(c->device);
+    for (uint32_t i = 0; i < n_items; ++i) {                                // the blocks BOX_MESH reads exist (allocation only)
+        if (items[i].kind != B32_OBJECT_BOX_MESH) continue;
+        for (uint32_t p = items[i].first_part; p < items[i].first_part + items[i].n_parts; ++p) {
+            if ((rc = scene_bounds_alloc(c, parts[p].slot))) return rc;
+            views[p].bounds = parts[p].slot->d_bounds;
+        }
+    }
+    if ((rc = object_overlay_plan(parts, views.data(), n_parts, items, n_items, true, plan))) return rc;
+    for (uint32_t p : plan.bound_parts) {                                   // each stale slot once
+        b32_scene* sc = parts[p].slot;
+        if (!sc->bounds_valid && std::find(c->bounds_stale.begin(), c->bounds_stale.end(), sc) == c->bounds_stale.end()) c->bounds_stale.push_back(sc);
+    }
+    constexpr size_t ROW_W = sizeof(ObjectRow) / 4u, PTR_W = sizeof(void*) / 4u, STALE_W = sizeof(BoundsRow) / 4u;
+    const size_t n_r = plan.rows.size(), n_b = plan.bounds.size(), n_s = c->bounds_stale.size();
+    const size_t words = n_r * ROW_W + n_b * PTR_W + n_s * STALE_W;
+    if (words > 0x7FFFFFFFull || plan.groups > 0x7FFFFFFFull) return B32_E_UNSUPPORTED;
+    std::vector<uint32_t>& lw = c->overlay_pairs;
+    lw.resize(words);
+    std::memcpy(lw.data(), plan.rows.data(), n_r * sizeof(ObjectRow));
+    w_bounds = (uint32_t)(n_r * ROW_W);
+    if (n_b) std::memcpy(lw.data() + w_bounds, plan.bounds.data(), n_b * sizeof(void*));
+    w_stale = w_bounds + (uint32_t)(n_b * PTR_W);
+    for (size_t k = 0; k < n_s; ++k) {
+        BoundsRow br{};
+        scene_bounds_row(c->bounds_stale[k], &br);
+        std::memcpy(lw.data() + w_stale + k * STALE_W, &br, sizeof(BoundsRow));
+    }
+    view_fill(a.v, *cam, w, h, nullptr);
+    a.n_rows = (uint32_t)n_r; a.n_groups = (uint32_t)plan.groups;
+    rows = lw.data(); n_rows = (uint32_t)words;
     return B32_OK;
 }
 
@@ -710,6 +772,18 @@ int b32_room_overlay_project_batch(b32_ctx* c, const B32Camera* cam, b32_room* r
                                    B32Prim* out, uint32_t cap, uint32_t* n_records) {
     if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
     RoomOverlayProducer p{ {}, cam, room, o, sel_vertices, sel_edges, sel_faces, points_xyz };
+    return produce_tap(c, p, w, h, out, cap, n_records);
+}
+int b32_draw_object_overlays(b32_ctx* c, const B32Camera* cam, const B32ObjectPart* parts, uint32_t n_parts, const B32ObjectItem* items,
+                             uint32_t n_items) {
+    if (!c || !c->fb) return B32_E_ARG;
+    ObjectOverlayProducer p{ {}, cam, parts, n_parts, items, n_items };
+    return produce_draw(c, p);
+}
+int b32_object_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32ObjectPart* parts, uint32_t n_parts, const B32ObjectItem* items,
+                                     uint32_t n_items, uint32_t w, uint32_t h, B32Prim* out, uint32_t cap, uint32_t* n_records) {
+    if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
+    ObjectOverlayProducer p{ {}, cam, parts, n_parts, items, n_items };
     return produce_tap(c, p, w, h, out, cap, n_records);
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
@@ -1008,6 +1082,7 @@ extern "C" unsigned long long b32_route_count(const b32_ctx* c, int which) {
     if (c && which == 17) return c->prims.scan_batches;
     if (c && which == 18) return c->world_tile_batches;
     if (c && which == 19) return c->world_scan_batches;
+    if (c && which == 20) return c->bounds_reductions;
     return (c && which >= 0 && which < 8) ? c->routes[which] : 0ull;
 }
 extern "C" int b32_set_async_depth(b32_ctx* c, int deep) {

@@ -608,6 +608,22 @@ struct RoomOverlayArgs {
     uint32_t g_vertices, g_edges, g_hover, g_sel_faces, g_sel_edges, g_preview, g_points;           // workgroups of the kernel's ranges, in this order
 };
 void launch_room_overlay(hipStream_t s, const RoomOverlayArgs& a);
+// The world editor's object overlays made into B32Prim records on the device (b32_draw_object_overlays, b32_object_overlay.hip): where a
+// record lies is decided by the host (object_overlay_plan, b32_object_overlay_body.h), the kernel fills the places.
+struct ObjectRow;
+struct ObjectOverlayArgs {
+    ViewBlock v; B32Prim* out;                      // camera and projection constants; the records
+    unsigned long long* counts;                     // the gizmo entry's drawn / dropped / rejected -- added to
+    const ObjectRow* rows; uint32_t n_rows;         // in record order; first_wg rises strictly
+    const OverlayBounds* const* bounds;             // the bounds blocks of the BOX_MESH rows' parts (ObjectRow::first_bound)
+    uint32_t n_groups;                              // workgroups of all rows
+};
+void launch_object_overlay(hipStream_t s, const ObjectOverlayArgs& a);
+// A slot's bounds reduced on the device (k_scene_bounds): one row per stale slot -- positions, `stride` floats between two vertices, the
+// body's vertex count and the slot's block of six keys.  rows == nullptr: the one row `one`.
+struct BoundsRow { const float* pos; OverlayBounds* out; uint32_t stride, nv; };
+struct BoundsArgs { const BoundsRow* rows; BoundsRow one; };
+void launch_scene_bounds(hipStream_t s, const BoundsArgs& a, uint32_t n_rows, uint32_t max_nv, int n_cu);   // the blocks armed, then reduced
 // Sort-free fast path: tile lists (unordered) by a counting sort straight from k_setup's spans; false = not applicable (too many
 // tiles for the LDS histogram), the caller takes the keyed radix path.  With `keys` the lists are split by class
 // ([opaque..., transparent...], boundary in tile_mid) and a transparent part longer than blend_cap raises need_global_sort.

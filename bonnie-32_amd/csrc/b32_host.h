@@ -110,6 +110,9 @@ struct b32_scene : b32::SceneState {    // (SceneState, b32_scene_state.h: what 
     // packed vertex streams of a resident mesh (k_pack_streams: nv positions of 12 B, then nv (u, v, rgba) of 12 B; pos_valid, lit_valid):
     // built on the second frame of an uploaded mesh too large for the in-kernel list collection
     float* d_pos12 = nullptr; size_t cap_pos12 = 0;
+    // min / max of the BODY's positions as six orderable keys (OverlayBounds, b32_overlay_body.h; bounds_valid): reduced on the device by the
+    // first b32_draw_object_overlays / b32_scene_bounds that reads them after the vertices moved (scene_bounds_ensure); allocated on first use
+    OverlayBounds* d_bounds = nullptr;
     std::vector<TexSig> tex_sig;        // (tex_sig_valid)
     // bones (b32_scene_set_rig, have_rig): the rest stream (nv positions and normals, 24 B each) k_pose starts from, and a bone index per
     // vertex.  Part of the scene's content: swapped with it; the buffers stay for the next rig when the geometry is replaced
@@ -131,7 +134,7 @@ struct b32_scene : b32::SceneState {    // (SceneState, b32_scene_state.h: what 
     // The only list of a scene's device buffers (the caller has drained the streams that use them).
     void release() {
         for (void* p : { (void*)d_verts, (void*)d_faces, (void*)d_texels, (void*)d_texels32, (void*)d_tex, (void*)d_consts, (void*)d_texmask,
-                         (void*)d_pos12, (void*)d_atlas0, (void*)d_rest, (void*)d_bone_of }) if (p) (void)hipFree(p);
+                         (void*)d_pos12, (void*)d_atlas0, (void*)d_rest, (void*)d_bone_of, (void*)d_bounds }) if (p) (void)hipFree(p);
     }
 };
 
@@ -317,6 +320,9 @@ struct b32_ctx {
     uint4* overlay_tab = nullptr; size_t overlay_cap_tab = 0;     // (16 bytes per vertex: OverlayPoint)
     void* overlay_bounds = nullptr;
     Staged<uint32_t> overlay_sel; std::vector<uint32_t> overlay_pairs;
+    // b32_draw_object_overlays / b32_scene_bounds (b32_object_overlay.hip): the slots whose bounds the call being enqueued reduces, and how
+    // many reductions were launched since the context was created (b32_route_count 20).  The rows travel in overlay_pairs / overlay_sel.
+    std::vector<b32_scene*> bounds_stale; unsigned long long bounds_reductions = 0;
     // profiling
     int profile_level = 0;
     uint32_t prof_stride = 1, prof_seq = 0;      // b32_set_profiling_stride: events on every prof_stride-th frame only
@@ -462,12 +468,27 @@ B32_INTERNAL int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settin
 // (place: the placement of a draw on its own, or NULL; a merged run -- frame_batched -- has set frame_placed / frame_places itself)
 B32_INTERNAL int render_scene_async_any(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog, const B32Placement* place);   // b32_frame.hip
 }
+// b32_object_overlay.hip, for ObjectOverlayProducer (b32_api.hip): what object_overlay_plan reads of the call's parts; a slot's bounds
+// block allocated (nothing enqueued); its row of k_scene_bounds' table; the reductions of c->bounds_stale enqueued (d_rows: their rows on
+// the device in that order, nullptr: one slot, its row by value) -- the blocks armed, one launch, the caches valid, the counter moved
+namespace b32 { struct ObjectPartView; }
+B32_INTERNAL void object_part_views(const B32ObjectPart* parts, uint32_t n_parts, std::vector<b32::ObjectPartView>& views);
+B32_INTERNAL int scene_bounds_alloc(b32_ctx* c, b32_scene* sc);
+B32_INTERNAL void scene_bounds_row(const b32_scene* sc, b32::BoundsRow* r);
+B32_INTERNAL int scene_bounds_run(b32_ctx* c, const b32::BoundsRow* d_rows);
 
 // ---- editing a resident scene (the rules: b32_scene_state.h)
 // The slot a call names (NULL: the resident scene), if it holds a scene.
 static inline b32_scene* scene_of(b32_ctx* c, b32_scene* slot) {
     b32_scene* sc = slot ? slot : &c->scene;
     return sc->have_scene ? sc : nullptr;
+}
+// A slot's positions as the overlays read them on the device: the packed stream while it is current, else the B32Vertex array; `stride`
+// floats between two vertices.
+static inline const float* slot_positions(const b32_scene* sc, uint32_t& stride) {
+    const bool packed = sc->pos_valid && sc->d_pos12;
+    stride = packed ? 3u : (uint32_t)(sizeof(B32Vertex) / sizeof(float));
+    return packed ? sc->d_pos12 : reinterpret_cast<const float*>(sc->d_verts);
 }
 // Entering an edit.  A pending frame that may still be redrawn (overflowed tile regions / pair buffers) is redrawn from the RESIDENT
 // vertices, faces and texels: it is settled before any of them changes, or the redraw would draw the edited scene in its place.

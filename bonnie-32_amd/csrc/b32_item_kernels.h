@@ -1,6 +1,6 @@
 // b32_item_kernels.h -- what the kernels that turn caller input into B32Prim records share (b32_world.hip, b32_gizmo.hip,
-// b32_room_overlay.hip): the drawn / dropped / rejected counting tail, and the pair of kernels of a one-lane-per-item producer whose small
-// batches travel in the kernel argument.
+// b32_room_overlay.hip, b32_overlay.hip, b32_object_overlay.hip): the drawn / dropped / rejected counting tail, a wave's minimum and
+// maximum of a key, and the pair of kernels of a one-lane-per-item producer whose small batches travel in the kernel argument.
 #pragma once
 #include "b32_device.h"
 
@@ -39,6 +39,19 @@ __device__ __forceinline__ void outcome_count_packed(uint32_t* tally, unsigned l
         for (uint32_t k = 0; k < 3u; ++k) { const uint32_t c = (packed >> (10u * k)) & 1023u; if (c) atomicAdd(&tally[k], c); }
     }
     outcome_flush(tally, counts);
+}
+
+// ---- a wave's minimum / maximum of an orderable key (overlay_key, b32_overlay_body.h) in every lane: k_overlay_points' and
+// k_scene_bounds' bounds.  Cross-lane only, no LDS round trip.
+__device__ __forceinline__ uint32_t overlay_wave_min(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t overlay_wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
 }
 
 // ---- one lane per item.  A producer P states  Args, Row, SMALL,  n(a) (the batch's rows),  rows(a) (where they lie on the device)  and

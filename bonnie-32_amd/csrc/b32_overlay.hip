@@ -25,23 +25,13 @@
 //                     next call on the stream.
 // The records stay on the device: the ordered tile pass of b32_prims.hip reads them where these kernels wrote them.  No new record kind.
 #include "b32_host.h"
+#include "b32_item_kernels.h"
 #include "b32_overlay_body.h"
 
 namespace b32 {
 
 static_assert(sizeof(OverlayPoint) == 16 && sizeof(OverlayBounds) == 24 && sizeof(B32MeshOverlay) == 48 && sizeof(OverlayArgs) <= 1024,
               "overlay records / kernel argument size");
-
-__device__ __forceinline__ uint32_t overlay_wave_min(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-__device__ __forceinline__ uint32_t overlay_wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_overlay_points(OverlayArgs a) {
     __shared__ OverlayBounds wg;

@@ -3,7 +3,8 @@
 // inherits SceneState; every writer of a slot ends in ONE of the functions below and assigns none of these fields itself.  What makes a
 // field valid again stays with the code that does the work: frame_positions (pos_valid, lit_valid, band_frames), the mask rebuild
 // (mask_dirty), the direct-binning sizing and overflow handling of a frame (direct_*, local_sort_ok), patch_fetch_* (h_*_valid),
-// b32_scene_set_rig (have_rig), the texture cache and the index atlas of the uploads (tex_sig_valid, atlas_idx_bytes).
+// b32_scene_set_rig (have_rig), the texture cache and the index atlas of the uploads (tex_sig_valid, atlas_idx_bytes), scene_bounds_ensure
+// (bounds_valid: b32_draw_object_overlays, b32_scene_bounds, b32_object_overlay.hip).
 #pragma once
 #include "b32_patch_tally.h"
 
@@ -13,6 +14,7 @@ struct SceneState : SlotBlend {         // (the blend bookkeeping: b32_patch_tal
     // packed vertex streams of a mesh too large for the in-kernel list collection (frame_positions): positions, the lit stream behind
     // them, and the frames drawn since the mesh arrived
     bool pos_valid = false, lit_valid = false; uint32_t band_frames = 0;
+    bool bounds_valid = false;          // the slot's min / max keys (b32_scene::d_bounds) are those of the BODY's vertices as they are now
     // direct binning (DirectBin, b32_device.h): what the scene's frames taught about its tile regions
     uint32_t direct_cap_opaque = 0;     // opaque entries per tile region (0: sized from the mesh on first use)
     uint32_t direct_ntiles = 0;         // the tile grid that size belongs to (another grid: sized again)
@@ -44,8 +46,11 @@ inline void content_changed(SceneState& st, EditWords w) {
 
 // Pose, vertex patch: the same mesh with vertices elsewhere.  The packed streams are packed again by the next frame; band_frames stays
 // (the mesh has been drawn before: frame_positions need not wait for a second frame), and so does everything learnt about the faces.
+// The bounds of the body are reduced again by the next call that reads them; uploads, room build and merged meshes end here too, so
+// this is the one place that clears them.
 inline void vertices_moved(SceneState& st, EditWords w) {
     st.pos_valid = false; st.lit_valid = false;
+    st.bounds_valid = false;
     content_changed(st, w);
 }
 
@@ -60,13 +65,16 @@ inline void faces_edited(SceneState& st, EditWords w, const SlotBlend& b) {
 inline void regions_forgotten(SceneState& st) { st.direct_cap_opaque = 0; st.direct_ntiles = 0; st.direct_ok = true; }
 
 // b32_scene_build_skeleton: the body stays, tail_v vertices / tail_f faces behind it are written anew, tail_blend_faces of them for the
-// transparent pass.  band_frames, local_sort_ok, the rig and the host copy of the BODY's faces are the body's business and stay.
+// transparent pass.  band_frames, local_sort_ok, the rig, the host copy of the BODY's faces and the BODY's bounds (no body vertex moves,
+// and a grown vertex buffer receives the body by a copy) are the body's business and stay.
 inline void tail_rebuilt(SceneState& st, EditWords w, bool same_nf, uint32_t tail_v, uint32_t tail_f, uint32_t tail_blend_faces, bool fmt8) {
     const bool first = !st.tail_v && !st.tail_f;
+    const bool bounds = st.bounds_valid;
     set_blend(st, blend_with_tail(first ? blend_save_body(st) : st, tail_blend_faces, fmt8));
     if (!same_nf) regions_forgotten(st);
     st.tail_v = tail_v; st.tail_f = tail_f;
     vertices_moved(st, w);
+    st.bounds_valid = bounds;
 }
 
 // Uploads, b32_room_build_mesh, a merged mesh: another mesh stands in the slot.  Whatever belonged to the old vertices and faces goes: rig,

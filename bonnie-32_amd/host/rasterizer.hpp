@@ -408,6 +408,14 @@ public:
         check(b32_scene_read_faces(ctx_, slot_, first, count, out.data()), "scene_read_faces");
         return out;
     }
+    // Asset::bounds of the body's vertices as they are on the device now (b32_scene_bounds, blocking): the cached reduction the object
+    // overlays' B32_OBJECT_BOX_MESH reads, reduced again only after the vertices changed.  false: no vertices (min f32::MAX, max f32::MIN).
+    bool bounds(Vec3& min, Vec3& max) const {
+        float mn[3], mx[3]; uint32_t has_verts = 0;
+        check(b32_scene_bounds(ctx_, slot_, mn, mx, &has_verts), "scene_bounds");
+        min = { mn[0], mn[1], mn[2] }; max = { mx[0], mx[1], mx[2] };
+        return has_verts != 0;
+    }
     // In-place edits (b32_scene_patch_*): the mesh stays resident, with its rig, pose and tail, and only the edited elements travel.
     // Records carry strictly ascending indices below the body's count; on a rigged mesh vertex records are in rest space.  A rectangle's
     // rows are `stride` elements apart in the caller's array.  Nothing blocks, except that the first face patch after an upload fetches
@@ -881,6 +889,43 @@ inline void draw_room_overlay(Framebuffer& fb, const Room& room, const RoomOverl
     check(b32_draw_room_overlay(fb.ctx(), &cam, room.handle(), &o, overlay.vertices.empty() ? nullptr : overlay.vertices.data(),
                                 overlay.edges.empty() ? nullptr : overlay.edges.data(), overlay.faces.empty() ? nullptr : overlay.faces.data(),
                                 xyz.empty() ? nullptr : xyz.data()), "draw_room_overlay");
+}
+// The world editor's object overlays (draw_asset_wireframe, editor/viewport_3d.rs:255-291; asset.bounds() -> draw_rotated_bounding_box,
+// asset/asset.rs:288-312 and viewport_3d.rs:7658-7697) made into records on the device from resident asset parts and drawn in array order
+// (b32_draw_object_overlays): enqueued, nothing read back, no per-frame walk of half-edges or vertices on the host.  An asset is a run of
+// parts in `parts`; an item is one reference call and always applies its placement.
+struct ObjectPart {
+    const ResidentMesh* mesh = nullptr;                                        // holds the part's mesh
+    const Topology* topology = nullptr;                                        // its polygons; may stay null when hidden or only boxes read it
+    bool visible = true;                                                       // part.visible
+    B32ObjectPart pack() const {
+        return B32ObjectPart{ mesh ? mesh->slot() : nullptr, topology ? topology->handle() : nullptr, visible ? 0u : B32_OBJECT_PART_HIDDEN, 0u };
+    }
+};
+struct ObjectItem {
+    uint8_t kind = B32_OBJECT_WIRE;                                            // B32_OBJECT_*
+    Placement place;                                                           // has_transform is not consulted (viewport_3d.rs:276-285 has no shortcut)
+    uint32_t first_part = 0, n_parts = 0;
+    Vec3 box_min, box_max;                                                     // B32_OBJECT_BOX
+    Color color{ 255, 200, 50 };
+    B32ObjectItem pack() const {
+        B32ObjectItem o{};
+        o.place = B32Placement{ place.cos_f, place.sin_f, { place.world_pos.x, place.world_pos.y, place.world_pos.z } };
+        o.first_part = first_part; o.n_parts = n_parts;
+        o.box_min[0] = box_min.x; o.box_min[1] = box_min.y; o.box_min[2] = box_min.z;
+        o.box_max[0] = box_max.x; o.box_max[1] = box_max.y; o.box_max[2] = box_max.z;
+        o.r = color.r; o.g = color.g; o.b = color.b; o.blend = (uint8_t)color.blend; o.kind = kind;
+        return o;
+    }
+};
+inline void draw_object_overlays(Framebuffer& fb, const std::vector<ObjectPart>& parts, const std::vector<ObjectItem>& items, const Camera& camera) {
+    const B32Camera cam = detail::pack(camera);
+    std::vector<B32ObjectPart> p; p.reserve(parts.size());
+    for (const auto& x : parts) p.push_back(x.pack());
+    std::vector<B32ObjectItem> it; it.reserve(items.size());
+    for (const auto& x : items) it.push_back(x.pack());
+    check(b32_draw_object_overlays(fb.ctx(), &cam, p.empty() ? nullptr : p.data(), (uint32_t)p.size(), it.empty() ? nullptr : it.data(), (uint32_t)it.size()),
+          "draw_object_overlays");
 }
 // The host restatements (what a host without the library walks per mouse move): separately rounded f32 operations in the reference's order
 // (compile with -ffp-contract=off where the compiler would fuse).

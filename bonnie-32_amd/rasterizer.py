@@ -1430,11 +1430,10 @@ def room_overlay_record_count(n, overlay):
     return room_overlay_layout(n, overlay)["total"]
 
 
-def _np_draw_3d_lines(P0, P1, camera, w, h):
-    """draw_3d_line (viewport_3d.rs:5687-5695, :5783-5882) for m segments at once in f32: the near clip, world_to_screen, the 16 rounds of
-    clip_line_to_rect, the cast.  Returns (x0, y0, x1, y1 as int64, state): state 0 drawn, 1 dropped, 2 rejected (an extent >= 2^30)."""
+def _np_near_clip_project(P0, P1, camera, w, h):
+    """The near clip of draw.rs:19-42 (viewport_3d.rs:5794-5816 is the same text) and world_to_screen on both ends for m segments at once
+    in f32: (x0, y0, x1, y1 as f32, ok) -- ok: neither both behind nor an end that does not project."""
     f32 = np.float32
-    m = len(P0)
     pos, bx, by, bz = (np.array([f32(v) for v in getattr(camera, k)], f32) for k in ("position", "basis_x", "basis_y", "basis_z"))
     vdot = lambda r, b: (r[:, 0] * b[0] + r[:, 1] * b[1]) + r[:, 2] * b[2]
     NEAR = f32(0.1)
@@ -1454,6 +1453,26 @@ def _np_draw_3d_lines(P0, P1, camera, w, h):
         C0 = np.where((b0 & ~b1)[:, None], Q, P0); C1 = np.where((~b0 & b1)[:, None], Q, P1)
         x0, y0, d0 = project(C0); x1, y1, d1 = project(C1)
         ok = ~(b0 & b1) & ~(d0 <= NEAR) & ~(d1 <= NEAR)
+    return x0, y0, x1, y1, ok
+
+
+def _np_draw_3d_lines_clipped(P0, P1, camera, w, h):
+    """draw_3d_line_clipped (draw.rs:12-67) for m segments at once in f32: the near clip, world_to_screen, the cast -- no screen clip.
+    Returns what _np_draw_3d_lines returns."""
+    x0, y0, x1, y1, ok = _np_near_clip_project(P0, P1, camera, w, h)
+    ix0, iy0, ix1, iy1 = (_ov_i32(v).astype(np.int64) for v in (x0, y0, x1, y1))
+    lim = 1 << 30
+    state = np.where(ok, np.where((np.abs(ix1 - ix0) >= lim) | (np.abs(iy1 - iy0) >= lim), 2, 0), 1)
+    return ix0, iy0, ix1, iy1, state
+
+
+def _np_draw_3d_lines(P0, P1, camera, w, h):
+    """draw_3d_line (viewport_3d.rs:5687-5695, :5783-5882) for m segments at once in f32: the near clip, world_to_screen, the 16 rounds of
+    clip_line_to_rect, the cast.  Returns (x0, y0, x1, y1 as int64, state): state 0 drawn, 1 dropped, 2 rejected (an extent >= 2^30)."""
+    f32 = np.float32
+    m = len(P0)
+    x0, y0, x1, y1, ok = _np_near_clip_project(P0, P1, camera, w, h)
+    with np.errstate(all="ignore"):
         xmax, ymax, one, zero = f32(w), f32(h), f32(1.0), f32(0.0)
 
         def outcode(x, y):
@@ -1649,6 +1668,173 @@ def room_overlay_records(faces, grid, overlay, camera, w, h, materials=None, wit
     return (out, tuple(int(v) for v in counts)) if with_counts else out
 
 
+# ---- the world editor's object overlays (editor/viewport_3d.rs:255-291, :7658-7697; asset/asset.rs:288-312) from resident asset parts:
+# b32_draw_object_overlays, b32_scene_bounds and their mirror
+class ObjectPart:
+    """One MeshPart of an asset: `scene`, the detached ResidentScene that holds its mesh; `topology`, its polygons (None when the part is
+    hidden or only boxes read it); `visible`, part.visible; `vertices`, the host's copy (abi.VERTEX_DTYPE or (n, 3) positions) -- read by
+    the mirror only, never by the device calls."""
+
+    def __init__(self, scene=None, topology=None, visible=True, vertices=None):
+        self.scene, self.topology, self.visible = scene, topology, bool(visible)
+        self.vertices = None if vertices is None else _positions(vertices)
+
+
+class ObjectItem:
+    """One reference call: kind abi.OBJECT_WIRE (draw_asset_wireframe), abi.OBJECT_BOX_MESH (asset.bounds() -> draw_rotated_bounding_box) or
+    abi.OBJECT_BOX (draw_rotated_bounding_box with box = (min, max)); the asset is parts[first_part : first_part + n_parts] of the call's
+    table; the placement (a Placement, an abi.B32Placement or (cos_f, sin_f, world_pos)) is always applied."""
+
+    def __init__(self, kind, placement, first_part=0, n_parts=0, color=None, box=None):
+        self.kind, self.first_part, self.n_parts = int(kind), int(first_part), int(n_parts)
+        self.cos_f, self.sin_f, self.world_pos = _placement_triple(placement)
+        self.color = color if color is not None else T.Color(255, 200, 50)
+        f32 = np.float32
+        self.box = (tuple(f32(v) for v in box[0]), tuple(f32(v) for v in box[1])) if box is not None else ((f32(0),) * 3, (f32(0),) * 3)
+
+
+def pack_object_items(items):
+    """The abi.OBJECT_ITEM_DTYPE array of a sequence of ObjectItem."""
+    out = np.zeros(len(items), abi.OBJECT_ITEM_DTYPE)
+    for i, it in enumerate(items):
+        r = out[i]
+        r["cos_f"], r["sin_f"], r["world_pos"] = it.cos_f, it.sin_f, it.world_pos
+        r["first_part"], r["n_parts"], r["box_min"], r["box_max"] = it.first_part, it.n_parts, it.box[0], it.box[1]
+        r["r"], r["g"], r["b"], r["blend"], r["kind"] = it.color.r, it.color.g, it.color.b, it.color.blend, it.kind
+    return out
+
+
+def pack_object_parts(parts, ctx):
+    """The abi.OBJECT_PART_DTYPE array of a sequence of ObjectPart for `ctx` (slots and topology handles)."""
+    out = np.zeros(len(parts), abi.OBJECT_PART_DTYPE)
+    for i, p in enumerate(parts):
+        if p.scene is None or p.scene._slot is None:
+            raise ValueError("ObjectPart: the scene must be detached into a slot")
+        out[i]["slot"] = p.scene._slot.value or 0
+        out[i]["topology"] = (p.topology.handle(ctx).value or 0) if p.topology is not None else 0
+        out[i]["flags"] = 0 if p.visible else abi.OBJECT_PART_HIDDEN
+    return out
+
+
+_OBJECT_BOUNDS_START = (np.float32(np.finfo(np.float32).max), np.float32(np.finfo(np.float32).min))      # f32::MAX, f32::MIN (asset.rs:291-292)
+# draw_rotated_bounding_box's corners as (x, y, z) selectors of max (viewport_3d.rs:7669-7678) and its edges (:7688-7692)
+_OBJECT_BOX_CORNERS = np.array([[0, 0, 0], [1, 0, 0], [1, 0, 1], [0, 0, 1], [0, 1, 0], [1, 1, 0], [1, 1, 1], [0, 1, 1]], bool)
+_OBJECT_BOX_EDGES = ((0, 1), (1, 2), (2, 3), (3, 0), (4, 5), (5, 6), (6, 7), (7, 4), (0, 4), (1, 5), (2, 6), (3, 7))
+
+
+def mesh_bounds(parts_vertices):
+    """Asset::bounds (asset/asset.rs:288-312) over the vertices of ALL parts (a sequence of abi.VERTEX_DTYPE arrays or (n, 3) positions):
+    (min, max, has_verts) in f32.  Minima start at f32::MAX and maxima at f32::MIN, f32::min / f32::max ignore a NaN, and a zero comes
+    back as +0.0 (the library's one key for both zeros): what b32_scene_bounds returns for one part, and what OBJECT_BOX_MESH folds."""
+    f32 = np.float32
+    mn = np.full(3, _OBJECT_BOUNDS_START[0], f32); mx = np.full(3, _OBJECT_BOUNDS_START[1], f32)
+    has_verts = False
+    for v in parts_vertices:
+        pos = _positions(v)
+        if not len(pos):
+            continue
+        has_verts = True
+        mn = np.fmin(mn, np.fmin.reduce(pos, axis=0)); mx = np.fmax(mx, np.fmax.reduce(pos, axis=0))
+    zero = f32(0.0)
+    return np.where(mn == zero, zero, mn).astype(f32), np.where(mx == zero, zero, mx).astype(f32), has_verts
+
+
+def _object_bounds_parts(parts):
+    """The parts Asset::bounds reads: all of them, hidden ones included (asset.rs:295)."""
+    return list(parts)
+
+
+def _object_half_edges(topology):
+    """(v0, v1) of draw_asset_wireframe's loop, viewport_3d.rs:271-273: the topology's half-edges in loop order."""
+    return topology.he_v0, topology.he_v1
+
+
+def _object_place(P, cos_f, sin_f, world_pos):
+    """viewport_3d.rs:276-285 and :7681-7685 on (m, 3) positions in f32."""
+    with np.errstate(all="ignore"):
+        x, y, z = P[:, 0], P[:, 1], P[:, 2]
+        return np.stack([(x * cos_f - z * sin_f) + world_pos[0], y + world_pos[1], (x * sin_f + z * cos_f) + world_pos[2]], axis=1).astype(np.float32)
+
+
+_object_wire_lines = _np_draw_3d_lines_clipped      # draw_asset_wireframe draws through draw_3d_line_clipped (:287)
+
+
+def object_overlay_layout(parts, items):
+    """First record of every item and the total: a WIRE item owns the sum of nh over its visible parts, a box 12 -- a function of the
+    topologies and the kinds alone.  ValueError for what the library answers B32_E_ARG."""
+    first, at = [], 0
+    for it in items:
+        if it.kind not in (abi.OBJECT_WIRE, abi.OBJECT_BOX_MESH, abi.OBJECT_BOX):
+            raise ValueError("ObjectItem: unknown kind")
+        if it.first_part < 0 or it.n_parts < 0 or it.first_part + it.n_parts > len(parts):
+            raise ValueError("ObjectItem: part range outside the table")
+        first.append(at)
+        if it.kind == abi.OBJECT_WIRE:
+            for p in parts[it.first_part:it.first_part + it.n_parts]:
+                if p.visible:
+                    if p.topology is None:
+                        raise ValueError("ObjectItem: a visible part of a WIRE item needs a topology")
+                    at += len(p.topology.poly_verts)
+        else:
+            at += abi.OBJECT_BOX_SLOTS
+    return first, at
+
+
+def object_overlay_record_count(parts, items):
+    """How many records b32_draw_object_overlays makes (b32_object_overlay_record_count)."""
+    return object_overlay_layout(parts, items)[1]
+
+
+def object_overlay_records(parts, items, camera, w, h, with_counts=False):
+    """The numpy / float32 mirror of b32_draw_object_overlays: the abi.PRIM_DTYPE records, place for place, that the device makes from the
+    parts' vertices (ObjectPart.vertices) and topologies for `items` (ObjectItem) -- draw_asset_wireframe (viewport_3d.rs:255-291),
+    Asset::bounds (asset.rs:288-312) and draw_rotated_bounding_box (viewport_3d.rs:7658-7697), one call after another.
+    with_counts: also (drawn, dropped, rejected), what the call adds to b32_gizmo_counts."""
+    f32 = np.float32
+    first, total = object_overlay_layout(parts, items)
+    out = noop_prims(total)
+    counts = np.zeros(3, np.int64)
+
+    def lines(where, x0, y0, x1, y1, state, color, alpha):
+        """the calls' records at the places `where`: those that draw are filled in, every call is counted"""
+        draw = state == 0
+        idx = where[draw]
+        for f, v in (("x0", x0), ("y0", y0), ("x1", x1), ("y1", y1)):
+            out[f][idx] = v[draw]
+        out["kind"][idx] = abi.LINE_2D; out["size"][idx] = 0; out["alpha"][idx] = alpha
+        out["r"][idx], out["g"][idx], out["b"][idx], out["blend"][idx] = color.r, color.g, color.b, color.blend
+        counts[:] += np.bincount(state, minlength=3)[:3]
+
+    for it, at in zip(items, first):
+        mine = parts[it.first_part:it.first_part + it.n_parts]
+        if it.kind == abi.OBJECT_WIRE:
+            for p in mine:
+                if not p.visible:
+                    continue
+                v0, v1 = (np.asarray(v, np.int64) for v in _object_half_edges(p.topology))
+                nv = len(p.vertices)
+                good = (v0 >= 0) & (v0 < nv) & (v1 >= 0) & (v1 < nv)
+                counts[1] += int((~good).sum())                  # an index >= nv: the no-op, dropped
+                g = np.nonzero(good)[0]
+                if len(g):
+                    P0 = _object_place(p.vertices[v0[g]], it.cos_f, it.sin_f, it.world_pos)
+                    P1 = _object_place(p.vertices[v1[g]], it.cos_f, it.sin_f, it.world_pos)
+                    lines(at + g, *_object_wire_lines(P0, P1, camera, w, h), it.color, 255)
+                at += len(v0)
+            continue
+        if it.kind == abi.OBJECT_BOX_MESH:
+            mn, mx, has_verts = mesh_bounds([p.vertices for p in _object_bounds_parts(mine)])
+            if not has_verts:                                    # bounds() is None: no call; the item counts once, as dropped
+                counts[1] += 1
+                continue
+        else:
+            mn, mx = np.array(it.box[0], f32), np.array(it.box[1], f32)
+        corners = _object_place(np.where(_OBJECT_BOX_CORNERS, mx, mn).astype(f32), it.cos_f, it.sin_f, it.world_pos)
+        ea = np.array([e[0] for e in _OBJECT_BOX_EDGES]); eb = np.array([e[1] for e in _OBJECT_BOX_EDGES])
+        lines(at + np.arange(abi.OBJECT_BOX_SLOTS), *_np_draw_3d_lines(corners[ea], corners[eb], camera, w, h), it.color, 0)
+    return (out, tuple(int(v) for v in counts)) if with_counts else out
+
+
 class Room:
     """A resident room (b32_room): its grid and its abi.SECTOR_FACE_DTYPE records on the device.  update() is a height drag."""
 
@@ -1771,6 +1957,7 @@ class Context:
     ROUTES = ("direct_bin", "inline_bin", "counting_sort", "keyed", "redraw_region", "redraw_global_sort", "redraw_pairs", "pipelined", "lds_atlas", "wire_tiles", "span_cover",
               "flag_join", "event_join", "poll_join", "line_tiles", "line_scan", "prim_tiles", "prim_scan")
     WORLD_ROUTES = ("world_tiles", "world_scan")      # b32_route_count 18, 19: b32_draw_world batches (they count under prim_tiles / prim_scan too)
+    OBJECT_ROUTES = ("bounds_reductions",)            # b32_route_count 20: reductions of a slot's bounds launched (object overlays, b32_scene_bounds)
 
     ROUTE_SORT_FREE, ROUTE_CUT_TILES, ROUTE_INLINE_BIN, ROUTE_DIRECT_BIN, ROUTE_WIDE_GROUPS, ROUTE_PACKED_STREAMS, ROUTE_PIPELINE, ROUTE_TEX_CACHE, ROUTE_BATCH, ROUTE_LDS_ATLAS, ROUTE_WIRE_TILES, ROUTE_SPAN_COVER, ROUTE_STAGGER, ROUTE_LINE_TILES, ROUTE_PRIM_TILES = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384
 
@@ -2120,6 +2307,14 @@ class Context:
         _chk(self.lib.b32_room_overlay_record_count(room._h, C.byref(o), e, f, C.byref(n)), "room_overlay_record_count")
         return int(n.value)
 
+    def object_overlay_record_count(self, parts, items):
+        """b32_object_overlay_record_count (host only; slots and topologies are only read for their counts)."""
+        pa, ia = pack_object_parts(parts, self), pack_object_items(items)
+        n = C.c_uint64()
+        _chk(self.lib.b32_object_overlay_record_count(abi.ptr(pa) if len(pa) else None, len(pa), abi.ptr(ia) if len(ia) else None, len(ia), C.byref(n)),
+             "object_overlay_record_count")
+        return int(n.value)
+
     def gizmo_project_batch(self, items, camera: T.Camera, ortho, width, height):
         """b32_gizmo_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_gizmos hands to the tile pass for a width x height
         framebuffer -- one per item, `size` of them for a thick line of thickness > 1 -- in item order; synchronous."""
@@ -2145,7 +2340,7 @@ class Context:
 
     def route_counts(self):
         """b32_route_count: how many frames of this context took each internal route (tests assert the targeted one ran)."""
-        return {n: int(self.lib.b32_route_count(self.h, i)) for i, n in enumerate(self.ROUTES + self.WORLD_ROUTES)}
+        return {n: int(self.lib.b32_route_count(self.h, i)) for i, n in enumerate(self.ROUTES + self.WORLD_ROUTES + self.OBJECT_ROUTES)}
 
     def debug_inject(self, what):
         """b32_debug_inject: fault injection (1 = the next flag / join hand-over loses its flag; 2 = the next fused kernel does not publish its start)."""
@@ -2509,6 +2704,27 @@ class Framebuffer:
         o, lists = overlay.pack()
         _chk(self.ctx.lib.b32_room_overlay_project_batch(self.ctx.h, C.byref(cam), room._h, C.byref(o), *lists, width or self.width, height or self.height,
                                                          abi.ptr(out) if n else None, n, C.byref(got)), "room_overlay_project_batch")
+        return out[:int(got.value)]
+
+    # ---- the world editor's object overlays from resident asset parts (viewport_3d.rs:255-291, :7658-7697; asset.rs:288-312)
+    def draw_object_overlays(self, parts, items, camera: T.Camera):
+        """b32_draw_object_overlays: the wireframes and bounding boxes of `items` (ObjectItem) over the asset parts `parts` (ObjectPart with
+        detached scenes) made into records on the device and drawn in array order; enqueued, no host synchronisation, nothing read back."""
+        cam = camera.pack()
+        pa, ia = pack_object_parts(parts, self.ctx), pack_object_items(items)
+        _chk(self.ctx.lib.b32_draw_object_overlays(self.ctx.h, C.byref(cam), abi.ptr(pa) if len(pa) else None, len(pa),
+                                                   abi.ptr(ia) if len(ia) else None, len(ia)), "draw_object_overlays")
+
+    def object_overlay_project_batch(self, parts, items, camera: T.Camera, width=None, height=None):
+        """b32_object_overlay_project_batch (stage tap): the abi.PRIM_DTYPE records b32_draw_object_overlays hands to the tile pass."""
+        n = self.ctx.object_overlay_record_count(parts, items)
+        out = np.zeros(n, abi.PRIM_DTYPE)
+        got = C.c_uint32()
+        cam = camera.pack()
+        pa, ia = pack_object_parts(parts, self.ctx), pack_object_items(items)
+        _chk(self.ctx.lib.b32_object_overlay_project_batch(self.ctx.h, C.byref(cam), abi.ptr(pa) if len(pa) else None, len(pa),
+                                                           abi.ptr(ia) if len(ia) else None, len(ia), width or self.width, height or self.height,
+                                                           abi.ptr(out) if n else None, n, C.byref(got)), "object_overlay_project_batch")
         return out[:int(got.value)]
 
     def present_nearest(self, dst_w, dst_h):
@@ -3289,6 +3505,20 @@ class ResidentScene:
         out = np.zeros(max(count, 0), abi.VERTEX_DTYPE)
         _chk(self.ctx.lib.b32_scene_read_vertices(self.ctx.h, self._handle(), first, count, abi.ptr(out) if count > 0 else None), "scene_read_vertices")
         return out
+
+    def bounds(self):
+        """b32_scene_bounds (blocking): Asset::bounds of the body's vertices as they are on the device now -- (min, max, has_verts), the
+        cached reduction OBJECT_BOX_MESH reads; reduced again only after the vertices changed."""
+        mn, mx, has = (C.c_float * 3)(), (C.c_float * 3)(), C.c_uint32()
+        _chk(self.ctx.lib.b32_scene_bounds(self.ctx.h, self._handle(), mn, mx, C.byref(has)), "scene_bounds")
+        return np.array(mn[:], np.float32), np.array(mx[:], np.float32), bool(has.value)
+
+    def bounds_async(self, out=None):
+        """b32_scene_bounds_async: (ticket, (array, pointer) of 32 page-locked bytes -- abi.SCENE_BOUNDS_DTYPE once the ticket is done)."""
+        buf = out if out is not None else self.ctx.host_alloc(32)
+        t = C.c_uint64()
+        _chk(self.ctx.lib.b32_scene_bounds_async(self.ctx.h, self._handle(), buf[1], C.byref(t)), "scene_bounds_async")
+        return int(t.value), buf
 
     def read_faces(self, first=0, count=None):
         """b32_scene_read_faces (blocking): the slot's faces as they are on the device now."""

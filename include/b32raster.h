@@ -285,7 +285,8 @@ int b32_set_async_depth(b32_ctx* ctx, int deep);
  * 15 b32_draw_lines batches in which every tile scanned the whole batch in order (small batches, or the route switched off), 16 b32_draw_prims
  * batches binned to tiles (B32_ROUTE_PRIM_TILES), 17 b32_draw_prims batches in which every tile scanned the whole batch in order
  * (b32_draw_world batches count under 16 / 17 too: they are primitive batches), 18 b32_draw_world batches binned to tiles, 19 b32_draw_world
- * batches in which every tile scanned the whole batch.
+ * batches in which every tile scanned the whole batch, 20 reductions of a slot's bounds launched by b32_draw_object_overlays, its stage tap
+ * and b32_scene_bounds (one per slot whose vertices changed since its last one).
  * Unknown `which` or null ctx: 0. */
 unsigned long long b32_route_count(const b32_ctx* ctx, int which);
 /* Switch internal routes OFF for the frames enqueued from now on (no reference counterpart: the results are identical on every route;
@@ -1171,6 +1172,76 @@ int b32_room_overlay_project_batch(b32_ctx* ctx, const B32Camera* camera, b32_ro
  * rectangle passes the gate), each for the sections that are on.  The rules of b32_draw_room_overlay for the struct and these two lists. */
 int b32_room_overlay_record_count(const b32_room* room, const B32RoomOverlay* overlay, const uint32_t* sel_edges, const uint32_t* sel_faces,
                                   uint32_t* n);
+/* The world editor's object overlays, drawn from RESIDENT asset parts: draw_asset_wireframe (editor/viewport_3d.rs:255-291; the placement
+ * preview :4833-4845 and the drag preview :4847-4860) and asset.bounds() (asset/asset.rs:288-312) followed by draw_rotated_bounding_box
+ * (viewport_3d.rs:7658-7697; the yellow box of a selected mesh object :4255-4268, the box of a CollisionShapeDef::FromMesh object
+ * :4231-4237, and with a given min / max Collision::Box :4215-4224).  An asset is a run of parts in the call's part table, each a slot that
+ * HOLDS the part's mesh and, for a wireframe, the b32_topology of its polygons; an item is one reference call.  One call makes, on the
+ * device, the B32Prim records of all items in array order and hands them to the ordered tile pass of b32_draw_prims without visiting the
+ * host.  Only B32_LINE_2D records are made.  Every expression is a separately rounded f32 operation in the reference's order.
+ *   WIRE      owns the sum of nh over its VISIBLE parts, in part order then loop order: the topology's half-edges (v[i], v[(i + 1) % n]),
+ *             which are the pairs of :271-273 for n = 0, 1, 2 as well.  Both ends are placed as
+ *                 ((x * cos_f - z * sin_f) + wx, y + wy, (x * sin_f + z * cos_f) + wz)                       (:276-285)
+ *             and the record is what b32_draw_world makes for a B32_LINE_2D item with B32_WORLD_CLIP_NEAR and alpha 255
+ *             (draw_3d_line_clipped, draw.rs:12-67).  The positions are the slot's BODY vertices as they are (posed or patched); bone
+ *             octahedra behind the body are neither drawn nor reduced.  A hidden part (B32_OBJECT_PART_HIDDEN: !part.visible) has no records.
+ *             DEPARTURE: an index >= nv panics in the reference (verts[indices[i]]); here the record draws nothing and counts as dropped.
+ *   BOX_MESH  owns 12 records.  min / max are the fold of asset.rs:291-304 over ALL the item's parts, hidden ones included: minima start at
+ *             f32::MAX and maxima at f32::MIN (not at infinities: a mesh of +inf vertices has min f32::MAX), f32::min / f32::max ignore a
+ *             NaN (only-NaN vertices give the box f32::MAX .. f32::MIN, which is drawn).  has_verts is false when every part is empty: then
+ *             the 12 records draw nothing and one call counts as dropped.  The eight corners in the order of :7669-7678, placed by
+ *             :7681-7685, the twelve edges in the order of :7688-7692, each what b32_draw_gizmos makes for a B32_GIZMO_LINE item
+ *             (draw_3d_line: near clip, world_to_screen, clip_line_to_rect, cast).  The fold is cached per slot (b32_scene_bounds) and
+ *             reduced again on the device only after the slot's vertices changed.
+ *             DEPARTURE: Rust leaves the sign of min(-0.0, +0.0) to the operand order; here both zeros are one key and come back as +0.0.
+ *             No record can tell (tests/test_object_overlay.py).
+ *   BOX       the same 12 records from box_min / box_max as given (min > max is drawn as given); its part range is not read.
+ * Where a record lies depends on the topologies' half-edge counts and the item kinds alone, never on the camera
+ * (b32_object_overlay_record_count): a call the reference does not make leaves a record that draws nothing (a circle of radius -1); so does
+ * a record whose extent reaches 2^30, as in b32_draw_world and b32_draw_gizmos.  Every draw_3d_line_clipped and draw_3d_line the reference
+ * calls is added to b32_gizmo_counts' totals: drawn, dropped (a None projection, a line clipped away) or rejected (2^30). */
+typedef struct B32ObjectPart {
+    b32_scene* slot;                         /* holds the part's mesh (MeshPart::mesh) */
+    b32_topology* topology;                  /* its polygons; nullable when the part is hidden or only boxes use it */
+    uint32_t flags;                          /* B32_OBJECT_PART_* */
+    uint32_t _pad;                           /* must be 0 */
+} B32ObjectPart;                             /* 24 bytes */
+#define B32_OBJECT_PART_HIDDEN 1u            /* !part.visible: no wireframe (:266); asset.bounds() still reads it (asset.rs:295) */
+typedef struct B32ObjectItem {
+    B32Placement place;                      /* ALWAYS applied, as in b32_pick_meshes: draw_asset_wireframe has no has_transform shortcut */
+    uint32_t first_part, n_parts;            /* the asset's parts in the call's part table */
+    float box_min[3], box_max[3];            /* B32_OBJECT_BOX only */
+    uint8_t r, g, b, blend;                  /* RasterColor */
+    uint8_t kind;                            /* B32_OBJECT_* */
+    uint8_t _pad[3];                         /* must be 0 */
+} B32ObjectItem;                             /* 60 bytes */
+#define B32_OBJECT_WIRE      0u  /* draw_asset_wireframe, viewport_3d.rs:255-291 */
+#define B32_OBJECT_BOX_MESH  1u  /* asset.bounds() (asset.rs:288-312) -> draw_rotated_bounding_box (:7658-7697) */
+#define B32_OBJECT_BOX       2u  /* draw_rotated_bounding_box with the given min / max (Collision::Box, :4215-4224) */
+/* Draws the items with b32_draw_world's contract: enqueued on the context's stream with no host synchronisation, a deferred clear flushed
+ * first, only rows of the band written, the z-buffer never written, both arrays reusable on return; n_items == 0 is a no-op.
+ * NULL context or camera, a NULL array with a non-zero count, a part range outside the table, a NULL slot or one that does not hold its
+ * scene, a visible part of a WIRE item without a topology, an unknown kind or flag, non-zero padding, a zero-size framebuffer ->
+ * B32_E_ARG.  More than 2^31 - 1 records -> B32_E_UNSUPPORTED.  Nothing is enqueued on error. */
+int b32_draw_object_overlays(b32_ctx* ctx, const B32Camera* camera, const B32ObjectPart* parts, uint32_t n_parts, const B32ObjectItem* items,
+                             uint32_t n_items);
+/* Stage tap: the records b32_draw_object_overlays would hand to the tile pass for a width x height framebuffer, copied back (synchronous).
+ * *n_records = how many there are; more than `cap`: B32_E_ARG and nothing is written. */
+int b32_object_overlay_project_batch(b32_ctx* ctx, const B32Camera* camera, const B32ObjectPart* parts, uint32_t n_parts,
+                                     const B32ObjectItem* items, uint32_t n_items, uint32_t width, uint32_t height, B32Prim* out, uint32_t cap,
+                                     uint32_t* n_records);
+/* How many records the call makes (host only): per WIRE item the sum of nh over its visible parts, per box 12.  The argument rules of
+ * b32_draw_object_overlays. */
+int b32_object_overlay_record_count(const B32ObjectPart* parts, uint32_t n_parts, const B32ObjectItem* items, uint32_t n_items, uint64_t* n);
+/* asset.bounds() of ONE slot (NULL: the context's resident scene): the cached reduction BOX_MESH reads, for hosts that keep no copy of the
+ * vertices (the modeler's draw_collision_wireframe, modeler/viewport.rs:4215 and :4333-4349; camera framing).  min / max as above (a zero
+ * comes back as +0.0), *has_verts = the body has vertices; without vertices min is f32::MAX and max f32::MIN.  The reduction runs on the
+ * device, once per change of the slot's vertices (b32_route_count 20 counts the launches); the call touches neither framebuffer nor
+ * z-buffer, flushes no clear and settles no frame.  The asynchronous form performs no host synchronisation and delivers 32 bytes -- min[3],
+ * max[3], uint32 has_verts, 4 bytes of padding -- through the tickets of b32_fb_download_async.  NULL context or result pointers, a slot
+ * that does not hold its scene -> B32_E_ARG. */
+int b32_scene_bounds(b32_ctx* ctx, b32_scene* slot, float mn[3], float mx[3], uint32_t* has_verts);
+int b32_scene_bounds_async(b32_ctx* ctx, b32_scene* slot, void* out /* 32 bytes */, uint64_t* ticket);
 /* The presenter's upscale (game/renderer.rs:179-214: Texture2D::from_rgba8 + FilterMode::Nearest + dest_size): destination pixel
  * (x, y) shows source texel floor((x + 0.5) * w / dst_w), floor((y + 0.5) * h / dst_h).  Writes dst_w*dst_h RGBA8 to host memory. */
 int b32_present_nearest(b32_ctx* ctx, uint32_t dst_w, uint32_t dst_h, uint8_t* rgba_out);
