@@ -95,12 +95,14 @@ const char* b32_build_digest(void) { return g_build_digest + 15; }
 
 // A pending frame that may still need a redraw (pair overflow, long transparent lists) is settled before anything reads or rebinds
 // the framebuffer, so that no caller ever sees the cleared frame of an aborted attempt.  Its error, if any, is the frame's error: kept
-// for the b32_frame_finish that ends the frame.
+// for the b32_frame_finish that ends the frame, and so are its counters.
 int settle_pending(b32_ctx* c) {
     if (!c->frame_pending || !c->pending_may_redraw) return B32_OK;
-    const int rc = b32_frame_finish(c, nullptr);
+    B32Timings tm;
+    const int rc = b32_frame_finish(c, &tm);
     if (rc == B32_E_HIP || rc == B32_E_ARG) return rc;
     if (rc && !c->deferred_rc) c->deferred_rc = rc;
+    if (!rc) { c->settled_tm = tm; c->settled_valid = true; }     // "its counters are those of the most recent frame": this one, unless another follows
     return B32_OK;
 }
 

@@ -785,8 +785,11 @@ int b32_frame_finish(b32_ctx* c, B32Timings* out) {
     if (!c->frame_pending) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const int d = c->deferred_rc; c->deferred_rc = 0;
+        if (out && c->settled_valid && !d) *out = c->settled_tm;      // the most recent frame was settled early (settle_pending): its counters
+        c->settled_valid = false;
         return d;
     }
+    c->settled_valid = false;                                        // (a later frame is pending: the counters are its own)
     for (int attempt = 0; attempt < 5; ++attempt) {
         // the frame's counters come back through the pinned arena (one small kernel writing host memory) rather than an SDMA copy:
         // ~5 us of stream time less per synchronous frame

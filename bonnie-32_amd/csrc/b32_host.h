@@ -289,6 +289,7 @@ struct b32_ctx {
     bool deep_async = false;            // b32_set_async_depth(1): large-scene frames are enqueued back to back, a dropped one is reported
     bool redrawing = false;             // enqueue_frame is repeating the pending frame (k_setup must not count it as lost)
     int deferred_rc = 0;                // error of a frame that b32_scene_swap had to settle: reported by the next b32_frame_finish
+    B32Timings settled_tm{}; bool settled_valid = false;   // ... and its counters, for a b32_frame_finish that finds no later frame pending
     B32Camera last_cam{}; B32Settings last_settings{}; B32Fog last_fog{}; bool last_has_fog = false;
 
     // asynchronous framebuffer downloads (b32_fb_download_async): ticket t completes with event dl_ev[t % DL_RING]

@@ -328,7 +328,7 @@ int b32_set_cheap_threshold(b32_ctx* ctx, uint32_t den);
  * b32_frame_finish are reported by it (B32_E_INDEX / B32_E_NAN_KEY / B32_E_UNSUPPORTED; as in the reference, the failing mesh
  * draws nothing); its counters are those of the most recent frame.  A pending frame of a large scene (more than 8192 faces, or
  * more than 2048 with a transparent pass: it may need a redraw with grown buffers) is finished by b32_scene_swap before the exchange; an error of that frame is kept and
- * reported by the b32_frame_finish that ends the frame. */
+ * reported by the b32_frame_finish that ends the frame, and when no later frame is pending then, its counters are that frame's too. */
 typedef struct b32_scene b32_scene;
 int b32_scene_create(b32_ctx* ctx, b32_scene** out);
 void b32_scene_destroy(b32_ctx* ctx, b32_scene* slot);
@@ -525,7 +525,17 @@ int b32_scene_read_texels(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint3
  * frame; b32_frame_finish reports errors as for any asynchronous frame.  Difference to the sequential calls in the ERROR case only: a
  * vertex index out of range or a NaN sort key in one mesh of a merged run (the reference panics there) leaves the whole run undrawn.
  * At most 32 meshes are merged into one draw; longer runs are split.  Merged meshes are cached per context while the member slots'
- * contents stay the same (any b32_scene_upload* into a member rebuilds). */
+ * contents stay the same (any b32_scene_upload* into a member rebuilds).
+ * What a member keeps of its own inside a run (pinned by tests/test_run_sheets.py): a texture id at or above the member's OWN texture
+ * count is no texture (the face is untextured and opaque, whatever the next member's texture 0 is), a vertex index at or above its OWN
+ * vertex count is the index error above; a depth tie between members goes to the earlier member, then to the earlier face, as the
+ * sequential strict `z <` gives it.  Where a run ends: "has a transparent pass" is the host's bound -- a face with a blend mode or
+ * editor_alpha < 255, or ANY texture of the slot with a blend mode, used by a face or not -- so such a slot ends its run even when the
+ * device classifies nothing as transparent; an 8-bit-colour slot, a slot with a wireframe phase (base backface_wireframe and its own
+ * backface_cull) and a slot without faces are drawn on their own and end the run in front of them; a run of one is a draw on its own.
+ * A slot that does not hold its scene makes b32_frame_end return B32_E_ARG: the runs in front of it are enqueued, nothing behind it is,
+ * and the context stays usable.  The cache holds 64 merged meshes and reuses the least recently used one; the same slots in another
+ * order are another run. */
 typedef struct B32MeshParams {
     float   ambient;
     uint8_t backface_cull, backface_wireframe, has_fog, _pad;
