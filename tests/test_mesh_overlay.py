@@ -21,6 +21,7 @@ import pytest
 import bonnie32_amd as b32
 from bonnie32_amd import abi
 from bonnie32_amd import rasterizer as RM
+from bonnie32_amd.mirrors.screen import _project_f32
 from tests.test_lines import ROOT, _upload_zbuffer
 from tests.test_prims import _as_i32, np_prims
 from tests.test_gizmos import cpu_records
@@ -583,7 +584,7 @@ def _warrior_bone_of(n, seed=5):
 
 def _screen(pos, cam, w, h, ortho):
     with np.errstate(all="ignore"):
-        sx, sy, _, some = RM._project_f32(pos[:, 0], pos[:, 1], pos[:, 2], cam, w, h, ortho)
+        sx, sy, _, some = _project_f32(pos[:, 0], pos[:, 1], pos[:, 2], cam, w, h, ortho)
     return sx, sy, some
 
 

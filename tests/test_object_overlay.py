@@ -29,6 +29,7 @@ import pytest
 import bonnie32_amd as b32
 from bonnie32_amd import abi
 from bonnie32_amd import rasterizer as RM
+from bonnie32_amd.mirrors import overlays as OV          # (the mirror's own module: where its private rules are read and changed)
 from tests.test_gizmos import G, K_LINE, cam_point, ref_clip_line_to_rect, ref_gizmos
 from tests.test_prims import np_prims
 from tests.test_world import IDENTITY_CAM, _cam_f32, look_at, noop_records, ref_clip, ref_world, ref_world_to_screen
@@ -487,19 +488,19 @@ def _mutations(mp):
     def other_sign(P, cos_f, sin_f, world_pos):
         return ORIGINAL["place"](P, cos_f, -sin_f, world_pos)
 
-    edges = list(RM._OBJECT_BOX_EDGES)
+    edges = list(OV._OBJECT_BOX_EDGES)
     edges[3], edges[4] = edges[4], edges[3]
     inf = f32(np.inf)
-    return {"bounds over visible parts only": (lambda: mp.setattr(RM, "_object_bounds_parts", visible_only), "asset, rotation, far camera"),
-            "start values +-inf": (lambda: mp.setattr(RM, "_OBJECT_BOUNDS_START", (inf, -inf)), "only NaN vertices"),
-            "(i + 1) % n dropped for the closing edge": (lambda: mp.setattr(RM, "_object_half_edges", open_loops), "asset, rotation, far camera"),
-            "box edge order": (lambda: mp.setattr(RM, "_OBJECT_BOX_EDGES", tuple(edges)), "a box with min > max"),
-            "placement skipped at identity": (lambda: mp.setattr(RM, "_object_place", skip_at_identity), "a facing inside the has_transform threshold"),
-            "rotation sign": (lambda: mp.setattr(RM, "_object_place", other_sign), "asset, rotation, far camera"),
-            "wire through draw_3d_line": (lambda: mp.setattr(RM, "_object_wire_lines", RM._np_draw_3d_lines), "asset, identity, near camera")}
+    return {"bounds over visible parts only": (lambda: mp.setattr(OV, "_object_bounds_parts", visible_only), "asset, rotation, far camera"),
+            "start values +-inf": (lambda: mp.setattr(OV, "_OBJECT_BOUNDS_START", (inf, -inf)), "only NaN vertices"),
+            "(i + 1) % n dropped for the closing edge": (lambda: mp.setattr(OV, "_object_half_edges", open_loops), "asset, rotation, far camera"),
+            "box edge order": (lambda: mp.setattr(OV, "_OBJECT_BOX_EDGES", tuple(edges)), "a box with min > max"),
+            "placement skipped at identity": (lambda: mp.setattr(OV, "_object_place", skip_at_identity), "a facing inside the has_transform threshold"),
+            "rotation sign": (lambda: mp.setattr(OV, "_object_place", other_sign), "asset, rotation, far camera"),
+            "wire through draw_3d_line": (lambda: mp.setattr(OV, "_object_wire_lines", OV._np_draw_3d_lines), "asset, identity, near camera")}
 
 
-ORIGINAL = {"place": RM._object_place}
+ORIGINAL = {"place": OV._object_place}
 MUTATIONS = ("bounds over visible parts only", "start values +-inf", "(i + 1) % n dropped for the closing edge", "box edge order",
              "placement skipped at identity", "rotation sign", "wire through draw_3d_line")
 

@@ -546,7 +546,8 @@ def test_box_mirror_and_host_header_equal_ref(name):
 def box_cases(name):
     """[(rectangle, points)]: about half the centres (left of the median projected centre), an empty rectangle, the full frame, the full
     frame with three points of which the second is behind the camera."""
-    from bonnie32_amd.rasterizer import RoomMirror, _project_f32
+    from bonnie32_amd.rasterizer import RoomMirror
+    from bonnie32_amd.mirrors.screen import _project_f32
     faces, grid, cam, w, h = real_room(name)
     m = RoomMirror(faces, grid, cam, w, h)
     with np.errstate(all="ignore"):

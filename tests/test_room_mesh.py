@@ -604,7 +604,8 @@ def test_gpu_build_mesh_equals_the_mirror(gpu_ctx, case):
         if case[2] == "both":
             assert (mats["normal_mode"] == abi.NORMAL_BOTH).all()
         if case == GPU_RANDOM[-1]:
-            _, nv_rec, _ = R._room_mesh_layout(faces, mats)
+            from bonnie32_amd.mirrors.room import _room_mesh_layout
+            _, nv_rec, _ = _room_mesh_layout(faces, mats)
             first = np.cumsum(nv_rec) - nv_rec
             assert (first[1:] != 6 * np.arange(1, len(faces))).all()
         if case[2] == "wild":

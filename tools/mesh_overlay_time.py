@@ -32,6 +32,7 @@ REAL = os.path.join(ROOT, "tests", "golden", "scenes", "real")
 def modeler(name, sc, polys, scale, reps, n_dev, n_host):
     import bonnie32_amd as b32
     from bonnie32_amd import abi, rasterizer as R
+    from bonnie32_amd.mirrors.screen import _project_f32
     W, H = sc.width, sc.height
     bo = (np.arange(len(sc.vertices)) // 3 % 7).astype(np.uint16)              # 5, 6: past the table
     tables = [bones(i, scale) for i in range(max(n_dev, n_host, 4))]
@@ -41,7 +42,7 @@ def modeler(name, sc, polys, scale, reps, n_dev, n_host):
     rs.set_rig(bo)
     top = R.Topology.from_polygons(polys) if polys is not None else R.Topology.triangles(sc.faces)
     with np.errstate(all="ignore"):
-        sx, _, _, some = R._project_f32(sc.vertices["pos"][:, 0], sc.vertices["pos"][:, 1], sc.vertices["pos"][:, 2], sc.camera, W, H, None)
+        sx, _, _, some = _project_f32(sc.vertices["pos"][:, 0], sc.vertices["pos"][:, 1], sc.vertices["pos"][:, 2], sc.camera, W, H, None)
     rect = (0.0, 0.0, float(np.median(sx[some])), float(H))
     quad = next((i for i in range(top.np) if top.count[i] == 4), 0)
     ov = R.MeshOverlay(abi.OVERLAY_ALL, hover_face=quad, select_kind=abi.SELECT_POLYGONS, preview_mode=abi.PREVIEW_FACE, rect=rect)

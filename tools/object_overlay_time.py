@@ -32,8 +32,10 @@ f32 = np.float32
 
 def host_items(pos, top, place, color):
     """What a host without the call builds per frame: (the wire's B32WorldItems, the box's twelve B32GizmoItems)."""
-    from bonnie32_amd import abi, rasterizer as R
-    c, s, wp = R._placement_triple(place)
+    from bonnie32_amd import abi
+    from bonnie32_amd.mirrors import overlays as R
+    from bonnie32_amd.records import _placement_triple
+    c, s, wp = _placement_triple(place)
     P = R._object_place(pos, c, s, wp)
     wire = np.zeros(len(top.poly_verts), abi.WORLD_ITEM_DTYPE)
     wire["p0"], wire["p1"] = P[top.he_v0], P[top.he_v1]
