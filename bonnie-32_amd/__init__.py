@@ -12,6 +12,7 @@ Layout:
                  triangle table and test), query.py (pick, hover, box), room.py, overlays.py, rig.py (bones, poses, patches, skeleton)
   rasterizer.py  the binding: Context, Framebuffer, ResidentScene, Room + render_mesh_15 with the reference's signature, on the GPU;
                  re-exports every public name of records.py and mirrors/
+  mirror_edit.py mirror editing (b32_scene_build_mirror): build_mirror(dst, src, mirror) over two ResidentScene; re-exports Mirror and mirror_mesh
   scenegen.py    deterministic synthetic scenes of BASELINE.md (C1..C5 + parity variants)
   parallel.py    screen-band sharding across ranks + the RCCL gather of band rows
   build.py       hipcc recipe for csrc/

@@ -172,6 +172,12 @@ SKELETON_STYLE_DTYPE = np.dtype([("selected_bone", "<i4"), ("hovered_bone", "<i4
                                  ("has_preview", "u1"), ("_pad", "u1", 2), ("preview_start", "<f4", 3), ("preview_end", "<f4", 3)])
 assert SKEL_BONE_DTYPE.itemsize == 40 and SKELETON_STYLE_DTYPE.itemsize == 44
 SKELETON_TRIANGLES, SKELETON_FROM_BONES = 0, 1
+# B32Mirror (b32_scene_build_mirror, b32_mirror_counts): the selected object's vertex and face ranges inside the source's body
+MIRROR_DTYPE = np.dtype([("axis", "<u4"), ("dim", "<f4"), ("v_first", "<u4"), ("v_count", "<u4"), ("f_first", "<u4"), ("f_count", "<u4"),
+                         ("_pad", "<u4", 2)])
+assert MIRROR_DTYPE.itemsize == 32
+MIRROR_X, MIRROR_Y, MIRROR_Z = 1, 2, 3
+MIRROR_DIM = 0.85                   # viewport.rs:1273
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
 
 
@@ -275,6 +281,8 @@ SYMBOLS = [
     ("b32_scene_build_skeleton", C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     ("b32_skeleton_counts", C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("b32_skeleton_items", C.c_int, [_P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("b32_scene_build_mirror", C.c_int, [_P, _P, _P, _P]),
+    ("b32_mirror_counts", C.c_int, [C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("b32_frame_begin", C.c_int, [_P, _P, _P]),
     ("b32_frame_add_scene", C.c_int, [_P, _P, _P]),
     ("b32_frame_end", C.c_int, [_P]),

@@ -464,6 +464,7 @@ B32_INTERNAL void band_close_any(b32_ctx* c);                                   
 B32_INTERNAL int h2d(b32_ctx* c, void* dst, const void* src, size_t bytes);       // b32_scene.hip
 B32_INTERNAL bool stage_ensure(b32_ctx* c);                                       // b32_scene.hip
 B32_INTERNAL int ensure_work(b32_ctx* c, uint32_t nf);                            // b32_scene.hip
+B32_INTERNAL int patch_fetch_faces(b32_ctx* c, b32_scene* sc);                    // b32_patch.hip (the body's faces on the host and their tally)
 B32_INTERNAL int validate_settings(const B32Settings* st);                        // b32_frame.hip
 B32_INTERNAL int enqueue_frame(b32_ctx* c, const B32Camera* cam, const B32Settings* st, const B32Fog* fog);            // b32_frame.hip
 // (place: the placement of a draw on its own, or NULL; a merged run -- frame_batched -- has set frame_placed / frame_places itself)

@@ -102,6 +102,20 @@ void launch_patch_indexed(hipStream_t s, const PatchRect& r, const void* src, ui
 }  // namespace b32
 
 // ------------------------------------------------------------------ the host side
+// The body's faces on the host and their tally: fetched once after the geometry was replaced (ONE host synchronisation).  Shared with
+// b32_scene_build_mirror (b32_mirror.hip), which tallies the built mesh from it.
+extern "C" int patch_fetch_faces(b32_ctx* c, b32_scene* sc) {
+    if (sc->h_faces_valid) return B32_OK;
+    const uint32_t bf = sc->body_nf();
+    sc->h_faces.resize(bf);
+    if (bf) {
+        HIPCHK(c, hipMemcpyAsync(sc->h_faces.data(), sc->d_faces, (size_t)bf * sizeof(B32Face), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    sc->tally = tally_faces(sc->h_faces.data(), bf, [sc](uint32_t t) { return tex_blends(sc, t); });
+    sc->h_faces_valid = true;
+    return B32_OK;
+}
 namespace {
 
 // stage_records (b32_host.h) for a payload the caller assembles in place: `fill` writes n dwords into the pinned ring slot.
@@ -127,19 +141,6 @@ int patch_stage(b32_ctx* c, uint32_t n, Fill fill) {
     return B32_OK;
 }
 
-// The body's faces on the host and their tally: fetched once after the geometry was replaced (ONE host synchronisation).
-int patch_fetch_faces(b32_ctx* c, b32_scene* sc) {
-    if (sc->h_faces_valid) return B32_OK;
-    const uint32_t bf = sc->body_nf();
-    sc->h_faces.resize(bf);
-    if (bf) {
-        HIPCHK(c, hipMemcpyAsync(sc->h_faces.data(), sc->d_faces, (size_t)bf * sizeof(B32Face), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    sc->tally = tally_faces(sc->h_faces.data(), bf, [sc](uint32_t t) { return tex_blends(sc, t); });
-    sc->h_faces_valid = true;
-    return B32_OK;
-}
 SlotBlend patch_tally_blend(const b32_scene* sc) {   // the slot's blend bookkeeping as its (patched) tally has it
     return tally_slot(sc->tally, *sc, sc->fmt8, sc->tex_blend_any, sc->blend_texels8, sc->tail_v != 0 || sc->tail_f != 0);
 }

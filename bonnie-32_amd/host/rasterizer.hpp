@@ -398,6 +398,11 @@ public:
     // (skeleton_to_triangles), the creation preview last; an empty skeleton without a preview removes it.  The tail is drawn with the
     // mesh and never hovered, selected, picked, skinned or overlaid.  Defined below, behind SkelBone.
     inline void build_skeleton(const std::vector<struct SkelBone>& bones, const B32SkeletonStyle& style);
+    // Mirror editing (b32_scene_build_mirror): one kernel replaces THIS mesh's geometry with the mesh the modeler assembles from `src`'s
+    // body while MirrorSettings is enabled -- the range's twins behind its vertices, each of its faces followed by its twin.  This mesh's
+    // textures stay, its rig and tail go (build_skeleton afterwards); src is read only and stays what pose, patch, hover and the overlays
+    // address.  Defined below, behind Mirror.
+    inline void build_mirror(const ResidentMesh& src, const struct Mirror& mirror);
     std::vector<B32Vertex> read_vertices(uint32_t first, uint32_t count) const {
         std::vector<B32Vertex> out(count);
         check(b32_scene_read_vertices(ctx_, slot_, first, count, out.data()), "scene_read_vertices");
@@ -559,6 +564,24 @@ inline B32SkeletonStyle skeleton_style(uint8_t editor_alpha = 255, uint32_t mode
 inline void ResidentMesh::build_skeleton(const std::vector<SkelBone>& bones, const B32SkeletonStyle& style) {
     const std::vector<B32SkelBone> tab = pack_skeleton(bones);
     check(b32_scene_build_skeleton(ctx_, slot_, tab.data(), (uint32_t)tab.size(), &style), "scene_build_skeleton");
+}
+// MirrorSettings (modeler/state.rs:777-850) with the selected object's vertex and face ranges inside the source's body
+struct Mirror {
+    uint32_t axis = 1;                          // 1 X, 2 Y, 3 Z
+    uint32_t v_first = 0, v_count = 0, f_first = 0, f_count = 0;
+    float dim = B32_MIRROR_DIM;                 // viewport.rs:1273
+    B32Mirror pack() const { B32Mirror m{}; m.axis = axis; m.dim = dim; m.v_first = v_first; m.v_count = v_count; m.f_first = f_first; m.f_count = f_count; return m; }
+};
+inline void ResidentMesh::build_mirror(const ResidentMesh& src, const Mirror& mirror) {
+    const B32Mirror m = mirror.pack();
+    check(b32_scene_build_mirror(ctx_, src.slot_, slot_, &m), "scene_build_mirror");
+}
+// the built mesh's (vertices, faces) for a body of nv vertices and nf faces
+inline std::pair<uint32_t, uint32_t> mirror_counts(uint32_t nv, uint32_t nf, const Mirror& mirror) {
+    const B32Mirror m = mirror.pack();
+    uint32_t v = 0, f = 0;
+    check(b32_mirror_counts(nv, nf, &m, &v, &f), "mirror_counts");
+    return { v, f };
 }
 // draw_skeleton's hierarchy lines followed by draw_bone_dots' circles (skeleton.rs:70-79, :110-143) as world items, for draw_world
 inline std::vector<B32WorldItem> skeleton_items(const std::vector<SkelBone>& bones, const B32SkeletonStyle& style) {

@@ -182,6 +182,110 @@ def kept_clut(clut):
     return out
 
 
+# ---- mirror editing (b32_scene_build_mirror): the mesh the modeler assembles while MirrorSettings is enabled (viewport.rs:1209-1311)
+class MeshMirror:
+    """What b32_scene_build_mirror leaves in its derived slot, in numpy: the source body's vertices with the selected range's twins
+    behind the range, the range's faces each followed by its twin, later faces shifted.  The rules are methods so that a test can change
+    one of them and watch a case move."""
+
+    @staticmethod
+    def flip(a):
+        """Rust's -x on the bits of a float32 array: -0.0 <-> +0.0, a NaN keeps its payload."""
+        return (np.ascontiguousarray(a, np.float32).view(np.uint32) ^ np.uint32(0x80000000)).view(np.float32)
+
+    def dim_channel(self, ch, dim):
+        """(ch as f32 * dim) as u8 with Rust's saturating cast (NaN -> 0)."""
+        with np.errstate(all="ignore"):
+            f = np.asarray(ch, np.uint8).astype(np.float32) * np.float32(dim)
+            t = np.where(f > 0, np.minimum(np.trunc(f), np.float32(255.0)), np.float32(0.0))
+        return t.astype(np.uint8)
+
+    def mirror_local(self, pos, normal, axis):
+        """mirror_position / mirror_normal (state.rs:832-848): (pos, normal) with the axis component's sign flipped."""
+        pos, normal = np.array(pos, np.float32, copy=True), np.array(normal, np.float32, copy=True)
+        pos[:, axis - 1] = self.flip(pos[:, axis - 1])
+        normal[:, axis - 1] = self.flip(normal[:, axis - 1])
+        return pos, normal
+
+    def twin_posed(self, pos, normal, axis, pose):
+        """First mirror in local space, then the vertex's bone (viewport.rs:1250-1266).  pose: (pos, normal) -> (pos, normal)."""
+        return pose(*self.mirror_local(pos, normal, axis))
+
+    def twin_blend(self, src_blend):
+        """Color::new sets BlendMode::Opaque (types.rs:773-775)."""
+        return np.full(len(src_blend), abi.OPAQUE, np.uint8)
+
+    def twin_face(self, v, c):
+        """(mirror_offset + v0, mirror_offset + v2, mirror_offset + v1), wrapping u32 adds."""
+        return self.shifted(v[:, [0, 2, 1]], c)
+
+    @staticmethod
+    def shifted(v, c):
+        return ((np.asarray(v, np.uint32).astype(np.uint64) + np.uint64(c)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+    def range_faces(self, faces, c):
+        """Each face of the range, its twin directly behind it."""
+        out = np.zeros(2 * len(faces), abi.FACE_DTYPE)
+        out[0::2] = faces
+        tw = np.array(faces, copy=True)
+        tw["v"] = self.twin_face(faces["v"], c)
+        out[1::2] = tw
+        return out
+
+    def later_faces(self, faces, c):
+        """A later object's faces: vertex_offset has grown by the twins."""
+        out = np.array(faces, copy=True)
+        out["v"] = self.shifted(faces["v"], c)
+        return out
+
+    def twins(self, src, local_pos, local_normal, mirror, bone_of, bones):
+        """The twins of the records `src` whose local positions and normals are given; bone_of None: no rig."""
+        t = np.array(src, dtype=abi.VERTEX_DTYPE, copy=True)
+
+        def pose(p, n):
+            if bone_of is None:
+                return p, n
+            r = np.zeros(len(p), abi.VERTEX_DTYPE)
+            r["pos"], r["normal"] = p, n
+            r = pose_vertices(r, bone_of, bones if bones is not None else ())
+            return r["pos"], r["normal"]
+
+        p, n = self.twin_posed(local_pos, local_normal, int(mirror["axis"]), pose)
+        t["pos"].view(np.uint32)[...] = np.ascontiguousarray(p, np.float32).view(np.uint32)
+        t["normal"].view(np.uint32)[...] = np.ascontiguousarray(n, np.float32).view(np.uint32)
+        for ch in ("r", "g", "b"):
+            t[ch] = self.dim_channel(src[ch], mirror["dim"])
+        t["blend"] = self.twin_blend(src["blend"])
+        return t
+
+    def mesh(self, vertices, faces, mirror, rest=None, bone_of=None, bones=None):
+        from ..records import pack_mirror
+        m = pack_mirror(mirror)[0]
+        v = np.asarray(vertices, abi.VERTEX_DTYPE).reshape(-1)
+        f = np.asarray(faces, abi.FACE_DTYPE).reshape(-1)
+        v0, c, f0, fc = int(m["v_first"]), int(m["v_count"]), int(m["f_first"]), int(m["f_count"])
+        if m["axis"] not in (1, 2, 3) or v0 + c > len(v) or f0 + fc > len(f):
+            raise ValueError("mirror_mesh: axis is 1..3 and the ranges lie inside the body")
+        src = v[v0:v0 + c]
+        if rest is not None:
+            r = np.asarray(rest, np.float32).reshape(-1, 6)[v0:v0 + c]
+            lp, ln = r[:, 0:3], r[:, 3:6]
+            bo = np.asarray(bone_of).reshape(-1)[v0:v0 + c]
+        else:
+            lp, ln, bo = src["pos"], src["normal"], None
+        tw = self.twins(src, lp, ln, m, bo, bones)
+        vo = np.concatenate([v[:v0 + c], tw, v[v0 + c:]])
+        fo = np.concatenate([f[:f0], self.range_faces(f[f0:f0 + fc], c), self.later_faces(f[f0 + fc:], c)])
+        return vo, fo
+
+
+def mirror_mesh(vertices, faces, mirror, rest=None, bone_of=None, bones=None):
+    """MeshMirror().mesh: (vertices, faces) b32_scene_build_mirror writes for a source body `vertices` / `faces` (posed, if the source is
+    posed) and a Mirror.  rest / bone_of / bones: the source's rig -- its (n, 6) rest stream, its bone index per vertex and the table of
+    its last pose (None or empty: none yet); without `rest` the source has no rig and the twins mirror the vertices as they are."""
+    return MeshMirror().mesh(vertices, faces, mirror, rest, bone_of, bones)
+
+
 # ---- the bone octahedra (b32_scene_build_skeleton, b32_skeleton_items): skeleton_to_triangles / draw_skeleton / draw_bone_dots
 class SkeletonMirror:
     """skeleton_to_triangles, skeleton_to_triangles_from_bones, draw_skeleton and draw_bone_dots in numpy float32, one separately

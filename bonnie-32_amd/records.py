@@ -226,6 +226,31 @@ class SkeletonStyle:
         return r
 
 
+class Mirror:
+    """Mirror editing (MirrorSettings, modeler/state.rs:777-850) as b32_scene_build_mirror takes it: the axis (abi.MIRROR_X / _Y / _Z, or
+    "x" / "y" / "z"), the selected object's vertices [v_first, v_first + v_count) and faces [f_first, f_first + f_count) inside the source's
+    body, and the twins' colour factor (the reference's 0.85)."""
+    AXES = {"x": abi.MIRROR_X, "y": abi.MIRROR_Y, "z": abi.MIRROR_Z}
+
+    def __init__(self, axis=abi.MIRROR_X, v_first=0, v_count=0, f_first=0, f_count=0, dim=abi.MIRROR_DIM):
+        self.axis = self.AXES[axis.lower()] if isinstance(axis, str) else int(axis)
+        self.v_first, self.v_count, self.f_first, self.f_count = int(v_first), int(v_count), int(f_first), int(f_count)
+        self.dim = np.float32(dim)
+
+    def pack(self):
+        r = np.zeros(1, abi.MIRROR_DTYPE)
+        r["axis"], r["dim"] = self.axis, self.dim
+        r["v_first"], r["v_count"], r["f_first"], r["f_count"] = self.v_first, self.v_count, self.f_first, self.f_count
+        return r
+
+
+def pack_mirror(mirror):
+    """A mirror as a one-element abi.MIRROR_DTYPE array: from such an array (or record), or from a Mirror."""
+    if isinstance(mirror, Mirror):
+        return mirror.pack()
+    return np.ascontiguousarray(mirror, abi.MIRROR_DTYPE).reshape(-1)[:1].copy()
+
+
 class Topology:
     """The modeler's polygons over a slot's vertices (b32_topology): poly_start (np + 1, non-decreasing, [0] == 0) into poly_verts.  The
     constructor derives what b32_topology_create derives: the half-edges (v[k], v[(k + 1) % n]) in loop order (Face::edges,

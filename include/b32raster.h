@@ -348,8 +348,8 @@ int b32_scene_swap(b32_ctx* ctx, b32_scene* slot);
  *
  * b32_scene_set_rig   makes the scene of `slot` (NULL: the context's resident scene) a rigged one.  It copies the scene's CURRENT positions
  *     and normals, on the device, into a rest stream (24 B per vertex) and uploads bone_of_vertex (nv entries; the caller has resolved
- *     v.bone_index.or(obj.default_bone_index); B32_BONE_NONE = no bone).  Mirrored vertices are the caller's: the mirror is applied in local
- *     space before the bone (viewport.rs:1250-1266), so they are static data appended before the upload.  The rig is part of the scene's
+ *     v.bone_index.or(obj.default_bone_index); B32_BONE_NONE = no bone).  Mirror editing's twins (viewport.rs:1250-1266: mirrored in local space
+ *     before the bone) are built from this rig into a derived slot by b32_scene_build_mirror, below.  The rig is part of the scene's
  *     content: it travels with b32_scene_swap, and any b32_scene_upload* into that scene drops it.  A second call replaces the indices and
  *     takes a NEW rest snapshot of whatever the vertices are at that moment -- after a pose, the posed ones (pose with n_bones = 0 first to
  *     get the uploaded vertices back).  The caller may reuse bone_of_vertex when the call returns.
@@ -510,6 +510,56 @@ int b32_scene_patch_texels(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint
 int b32_scene_patch_indexed(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t tex, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                             const uint8_t* indices, uint32_t stride, const uint16_t* clut, uint32_t clut_len);
 int b32_scene_read_texels(b32_ctx* ctx, b32_scene* slot /* NULL: ditto */, uint32_t tex, void* out);  /* blocking */
+
+/* ---- mirror editing: the mirrored half built on the device into a derived slot ----------------------------------------------------------
+ * With MirrorSettings enabled (modeler/state.rs:777-850; the default for symmetric characters) the modeler draws another mesh than it
+ * edits (modeler/viewport.rs:1209-1311): behind the selected object's vertices it appends their twins -- mirrored in LOCAL space
+ * (mirror_position, mirror_normal), then put through the vertex's bone, colour (base_color as f32 * 0.85) as u8 -- behind EACH of the
+ * object's triangles that triangle's twin with reversed winding, and every later object's vertices shift.  The interleaving matters: equal
+ * sort keys in painter's mode and equal depths in z-buffer mode are decided by face order, so twins drawn behind all body faces are
+ * another frame.  Here `src` keeps the combined mesh -- pose, patch, b32_hover_mesh, b32_box_select and the overlays keep addressing it --
+ * and b32_scene_build_mirror writes the mesh the reference would have assembled from src's BODY into `dst`, which the frame draws:
+ *     patch_vertices(src) -> pose(src) -> build_mirror(src, dst) -> build_skeleton(dst) -> draw dst -> hover(src) -> overlay(src)
+ *
+ * The rule, by output position (it never looks at an index value).  c = v_count, v_end = v_first + v_count, f_end = f_first + f_count,
+ * bv / bf = src's body counts.
+ *   Vertices, bv + c: output i < v_end is src's vertex i bit for bit (posed, if src is posed); outputs v_end .. v_end + c are the twins of
+ *   vertices v_first .. v_end; output i + c is src's vertex i for i >= v_end.
+ *   A twin starts from the LOCAL position and normal -- src's rest stream when src is rigged, else its vertex as it is.  The component of
+ *   `axis` gets its sign BIT flipped in both (Rust's -x: -0.0 <-> +0.0, a NaN keeps its payload; not 0 - x).  On a rigged src the twin is
+ *   then posed by the pose pass's own arithmetic with the bone of the SOURCE vertex and the table of src's last b32_scene_pose (before the
+ *   first pose and after a pose with n_bones = 0: the mirrored rest bits), exactly as b32_scene_patch_vertices poses.  uv is copied as
+ *   bits; r, g, b are each (ch as f32 * dim) as u8 with Rust's saturating cast (NaN -> 0); blend is B32_BLEND_OPAQUE (Color::new,
+ *   types.rs:773-775).
+ *   Faces, bf + f_count: output j < f_first is face j; face j of the range goes to f_first + 2 * (j - f_first) and its twin to the next
+ *   place with v = (v0 + c, v2 + c, v1 + c), the other eight bytes copied; face j >= f_end goes to j + f_count with all three indices
+ *   + c.  The adds wrap (u32).  Indices are never validated: one out of range is the frame's B32_E_INDEX, as after an upload.
+ *   v_count == 0 && f_count == 0 is legal: dst becomes a copy of src's body.
+ *
+ * b32_scene_build_mirror   ONE kernel on the context's stream, one lane per output element; no upload.  State is b32_room_build_mesh's:
+ *     dst must hold an uploaded scene, its textures stay, its geometry is replaced, its rig and tail go (call b32_scene_build_skeleton on
+ *     dst afterwards, as after a room build), its content counts as changed.  dst's transparent-pass bookkeeping comes out as a fresh
+ *     upload of the built arrays with dst's textures leaves it.  Works for RGB555 and 8-bit-colour dst; src's pixel format is irrelevant.
+ *     src is read only: its bits, rig, tail, content number, bounds cache, merged runs and query answers stay as they are.
+ *     No host synchronisation, with two exceptions: the FIRST build after src's upload (or room build) copies src's body faces to the
+ *     host once, as the first b32_scene_patch_faces does (face patches of src keep the copy current); and a growth of dst's buffers.
+ *     Like b32_scene_pose it first settles a pending frame that may still be redrawn.
+ * b32_mirror_counts        host only: the built mesh's counts for a body of nv vertices and nf faces.
+ * Errors (nothing is enqueued, dst is untouched): NULL context or struct, src == dst (also through NULL), either slot without a scene, axis
+ * not 1..3, v_first + v_count > bv, f_first + f_count > bf -> B32_E_ARG; an output count past 2^32 - 1 -> B32_E_UNSUPPORTED.
+ * Out of scope: apply_mirror (mesh_editor.rs:1909; connectivity changes: an upload), constrain_to_plane (the host's edit), keeping dst's
+ * tail across a build. */
+#define B32_MIRROR_DIM 0.85f
+typedef struct B32Mirror {          /* 32 bytes */
+    uint32_t axis;                  /* 1 X, 2 Y, 3 Z (B32HoverParams' mirror_axis without the 0) */
+    float    dim;                   /* the reference's 0.85 (viewport.rs:1273): B32_MIRROR_DIM */
+    uint32_t v_first, v_count;      /* the selected object's vertices inside src's BODY */
+    uint32_t f_first, f_count;      /* ... and its faces */
+    uint32_t _pad[2];
+} B32Mirror;
+int b32_scene_build_mirror(b32_ctx* ctx, b32_scene* src /* NULL: the context's resident scene */, b32_scene* dst /* NULL: ditto */,
+                           const B32Mirror* mirror);
+int b32_mirror_counts(uint32_t nv, uint32_t nf, const B32Mirror* mirror, uint32_t* nv_out, uint32_t* nf_out);   /* host only */
 
 /* ---- a frame of several meshes (scene.rs:112-261) -------------------------------------------------------------------------------
  * The console's render step is one render_mesh_15 call per room and per asset part onto the same framebuffer, with ONE camera and
