@@ -9,10 +9,12 @@ Layout:
   records.py     value types and packers: caller input -> ABI records (Placement, Bone, Topology, the overlay structs, prim, ...)
   mirrors/       numpy / float32 restatements of the reference's editor rules -- what a host without the library walks, what the CPU tests
                  compare bit for bit, the CPU baselines of tools/*_time.py: screen.py (what the others share: placement, projection, the
-                 triangle table and test), query.py (pick, hover, box), room.py, overlays.py, rig.py (bones, poses, patches, skeleton)
+                 triangle table and test), query.py (pick, hover, box), room.py, overlays.py, rig.py (bones, poses, patches, skeleton),
+                 sky.py (sky placement and projection, star records)
   rasterizer.py  the binding: Context, Framebuffer, ResidentScene, Room + render_mesh_15 with the reference's signature, on the GPU;
                  re-exports every public name of records.py and mirrors/
   mirror_edit.py mirror editing (b32_scene_build_mirror): build_mirror(dst, src, mirror) over two ResidentScene; re-exports Mirror and mirror_mesh
+  sky.py         the sky without a host wait (b32_sky, b32_draw_stars): ResidentSky and draw_stars; re-exports the mirror mirrors/sky.py
   scenegen.py    deterministic synthetic scenes of BASELINE.md (C1..C5 + parity variants)
   parallel.py    screen-band sharding across ranks + the RCCL gather of band rows
   build.py       hipcc recipe for csrc/

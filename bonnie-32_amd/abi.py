@@ -179,6 +179,10 @@ assert MIRROR_DTYPE.itemsize == 32
 MIRROR_X, MIRROR_Y, MIRROR_Z = 1, 2, 3
 MIRROR_DIM = 0.85                   # viewport.rs:1273
 SKY_VERTEX_DTYPE = np.dtype([("pos", np.float32, 3), ("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("blend", np.uint8)])
+# B32Star (b32_draw_stars): what draw_star_diamond is called with -- the cast screen point and the twinkled colour
+STAR_DTYPE = np.dtype([("cx", "<i4"), ("cy", "<i4"), ("r", "u1"), ("g", "u1"), ("b", "u1"), ("_pad", "u1")])
+assert SKY_VERTEX_DTYPE.itemsize == 16 and STAR_DTYPE.itemsize == 12
+STAR_MAX = (2**31 - 1) // 9         # more stars than this: B32_E_UNSUPPORTED
 
 
 class B32IndexedTexture(C.Structure):
@@ -316,6 +320,14 @@ SYMBOLS = [
     ("b32_fb_clear_transparent", C.c_int, [_P]),
     ("b32_render_skybox_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     ("b32_draw_star_diamonds", C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_float]),
+    ("b32_sky_create", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(_P)]),
+    ("b32_sky_destroy", None, [_P, _P]),
+    ("b32_sky_update", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_render_sky", C.c_int, [_P, _P, _P]),
+    ("b32_sky_project_batch", C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("b32_draw_stars", C.c_int, [_P, _P, C.c_uint32, C.c_float]),
+    ("b32_star_record_count", C.c_int, [C.c_uint32, C.c_float, C.POINTER(C.c_uint64)]),
+    ("b32_star_records_batch", C.c_int, [_P, _P, C.c_uint32, C.c_float, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("b32_present_nearest", C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
     ("b32_draw_lines", C.c_int, [_P, _P, C.c_uint32]),
     ("b32_draw_prims", C.c_int, [_P, _P, C.c_uint32]),

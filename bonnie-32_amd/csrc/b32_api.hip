@@ -63,7 +63,7 @@ void b32_destroy(b32_ctx* c) {
     for (hipEvent_t e : { c->ev_main, c->ev_wbin }) if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_created) for (auto& fr : c->ev) for (auto& e : fr) if (e) (void)hipEventDestroy(e);
-    c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release(); c->patch.release();
+    c->lines.release(); c->prims.release(); c->world.release(); c->gizmo.release(); c->patch.release(); c->stars.release();
     for (ArmedWords* w : { &c->world_counts, &c->gizmo_counts, &c->pick_words, &c->hover_bits, &c->hover_words, &c->room_words, &c->room_points })
         if (w->p) (void)hipFree(w->p);
     for (EventPair* t : { &c->world_timer, &c->pick_timer, &c->hover_timer }) t->destroy();
@@ -343,9 +343,9 @@ static int draw_pass(b32_ctx* c, DrawPassState<Rec>& ps, const Rec* recs, uint32
 }
 
 // ------------------------------------------------------------------ record producers
-// Five features turn caller input into B32Prim records on the device -- in the primitive pass's record buffer, so the records never visit
-// the host -- and hand them to the ordered tile pass: world items, the editor's gizmos, the modeler's mesh overlays and the world editor's
-// room and object overlays.  Each also has a stage tap (b32_*_project_batch) that runs the same kernel into scratch memory and copies the records to
+// Six features turn caller input into B32Prim records on the device -- in the primitive pass's record buffer, so the records never visit
+// the host -- and hand them to the ordered tile pass: world items, the editor's gizmos, the modeler's mesh overlays, the world editor's
+// room and object overlays, and the sky's star sprites.  Each also has a stage tap (b32_*_project_batch) that runs the same kernel into scratch memory and copies the records to
 // the host.  A producer is a struct that holds the call's arguments and states only what is its own:
 //   prepare(c, w, h)         everything that can fail on the arguments alone: the whole batch checked, the records laid out and counted
 //                            (`total`), the args block `a` filled but for device pointers, the host rows to put on the device (`rows`,
@@ -626,6 +626,21 @@ int ObjectOverlayProducer::prepare(b32_ctx* c, uint32_t w, uint32_t h) {
     return B32_OK;
 }
 
+// ------------------------------------------------------------------ the star sprites (b32_sky_resident.hip)
+// (render.rs:206-237) Made into 1x1 filled rectangles by k_star_records: star i's 1, 5 or 9 records at i * per.  The rows are the stars.
+struct StarProducer : Producer<StarArgs, B32Star, STAR_SMALL> {
+    const B32Star* stars; uint32_t n; float size;
+    int prepare(b32_ctx*, uint32_t, uint32_t) {
+        if (n > STAR_MAX) return B32_E_UNSUPPORTED;
+        a.n = n; a.per = star_per(size);
+        rows = stars; n_rows = n; total = (uint64_t)n * a.per;
+        return B32_OK;
+    }
+    int bind(b32_ctx*, B32Prim* out, const B32Star* in, Scratch*) { a.out = out; a.stars = in; return B32_OK; }
+    void launch(hipStream_t s, const B32Star* small) const { launch_star_records(s, a, small); }
+    static Staged<B32Star>& staged(b32_ctx* c) { return c->stars; }
+};
+
 // Where a producer's rows travel: by value in the kernel argument when it has such a kernel and the batch is small (no staging copy, no
 // pinned-ring slot), else on the device.
 template <class P> static bool rows_by_value(const P& p) { return P::SMALL && p.n_rows <= P::SMALL; }
@@ -787,6 +802,82 @@ int b32_object_overlay_project_batch(b32_ctx* c, const B32Camera* cam, const B32
     if (!c || !n_records || w > 16384 || h > 16384) return B32_E_ARG;
     ObjectOverlayProducer p{ {}, cam, parts, n_parts, items, n_items };
     return produce_tap(c, p, w, h, out, cap, n_records);
+}
+int b32_draw_stars(b32_ctx* c, const B32Star* stars, uint32_t n, float size) {
+    if (!c || !c->fb || (n && !stars)) return B32_E_ARG;
+    StarProducer p{ {}, stars, n, size };
+    return produce_draw(c, p);
+}
+int b32_star_record_count(uint32_t n, float size, uint64_t* records) {
+    if (!records) return B32_E_ARG;
+    *records = (uint64_t)n * star_per(size);
+    return B32_OK;
+}
+int b32_star_records_batch(b32_ctx* c, const B32Star* stars, uint32_t n, float size, B32Prim* out, uint32_t cap, uint32_t* n_records) {
+    if (!c || !n_records || (n && !stars)) return B32_E_ARG;
+    StarProducer p{ {}, stars, n, size };
+    return produce_tap(c, p, 1, 1, out, cap, n_records);
+}
+
+// ------------------------------------------------------------------ the resident sky (k_sky_place_project, b32_sky_resident.hip)
+int b32_sky_create(b32_ctx* c, const B32SkyVertex* offsets, uint32_t nv, const uint32_t* faces, uint32_t nf, b32_sky** out) {
+    if (!c || !out || (nv && !offsets) || (nf && !faces)) return B32_E_ARG;
+    for (size_t i = 0; i < (size_t)3 * nf; ++i) if (faces[i] >= nv) return B32_E_INDEX;    // projected[face[k]] index panic
+    (void)hipSetDevice(c->device);
+    b32_sky* s = new b32_sky();
+    s->owner = c; s->nv = nv; s->nf = nf;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->verts), nv ? (size_t)nv * sizeof(B32SkyVertex) : 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->faces), nf ? (size_t)nf * 3 * sizeof(uint32_t) : 16);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->proj), nv ? (size_t)nv * sizeof(float2) : 16);
+    if (e == hipSuccess && nv) e = hipMemcpyAsync(s->verts, offsets, (size_t)nv * sizeof(B32SkyVertex), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && nf) e = hipMemcpyAsync(s->faces, faces, (size_t)nf * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);                   // (the caller's arrays are free again; once per level, not per frame)
+    if (e != hipSuccess) {
+        c->last_hip = (int)e;
+        for (void* p : { (void*)s->verts, (void*)s->faces, (void*)s->proj }) if (p) (void)hipFree(p);
+        delete s;
+        return B32_E_HIP;
+    }
+    *out = s;
+    return B32_OK;
+}
+void b32_sky_destroy(b32_ctx* c, b32_sky* sky) {
+    if (!sky) return;
+    if (c) { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); }     // (a render that reads it may be in flight)
+    sky->ring.release();
+    for (void* p : { (void*)sky->verts, (void*)sky->faces, (void*)sky->proj }) if (p) (void)hipFree(p);
+    delete sky;
+}
+int b32_sky_update(b32_ctx* c, b32_sky* sky, uint32_t first, uint32_t count, const B32SkyVertex* verts) {
+    if (!c || !sky || sky->owner != c || (count && !verts)) return B32_E_ARG;
+    if ((unsigned long long)first + count > sky->nv) return B32_E_ARG;
+    if (!count) return B32_OK;
+    (void)hipSetDevice(c->device);
+    return stage_records(c, sky->ring, verts, count, sky->verts + first);
+}
+int b32_render_sky(b32_ctx* c, b32_sky* sky, const B32Camera* cam) {
+    if (!c || !c->fb || !sky || sky->owner != c || !cam) return B32_E_ARG;
+    if (!sky->nv || !sky->nf) return B32_OK;
+    { const int rc = draw_enter(c); if (rc) return rc; }
+    if (c->band_y1 <= c->band_y0) return B32_OK;
+    launch_sky_place_project(c->stream, sky->verts, sky->nv, *cam, c->width, c->height, sky->proj);
+    launch_sky_fill(c->stream, sky->verts, sky->nv, sky->faces, sky->nf, sky->proj, c->fb, c->width, c->height, c->band_y0, c->band_y1);
+    HIPCHK(c, hipGetLastError());
+    return B32_OK;
+}
+int b32_sky_project_batch(b32_ctx* c, b32_sky* sky, const B32Camera* cam, uint32_t w, uint32_t h, float* xy) {
+    if (!c || !sky || sky->owner != c || !cam || w == 0 || h == 0 || w > 16384 || h > 16384 || (sky->nv && !xy)) return B32_E_ARG;
+    if (!sky->nv) return B32_OK;
+    (void)hipSetDevice(c->device);
+    float2* dp = nullptr;
+    Scratch tmp(c);
+    int rc;
+    if ((rc = tmp.alloc(&dp, (size_t)sky->nv))) return rc;
+    launch_sky_place_project(c->stream, sky->verts, sky->nv, *cam, w, h, dp);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(xy, dp, (size_t)sky->nv * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return B32_OK;
 }
 int b32_present_nearest(b32_ctx* c, uint32_t dw, uint32_t dh, uint8_t* out) {
     if (!c || !c->fb || !out || !dw || !dh || dw > 32768 || dh > 32768) return B32_E_ARG;

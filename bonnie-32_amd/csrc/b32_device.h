@@ -639,6 +639,20 @@ void launch_sky(hipStream_t s, const B32SkyVertex* v, uint32_t nv, const uint32_
 void launch_stars(hipStream_t s, const int32_t* cx, const int32_t* cy, const uint8_t* rgb, uint32_t n, float size, uint32_t* fb,
                   uint32_t width, uint32_t height, uint32_t band_y0, uint32_t band_y1);
 void launch_upscale_nearest(hipStream_t s, const uint32_t* src, uint32_t sw, uint32_t sh, uint32_t* dst, uint32_t dw, uint32_t dh);
+// The resident sky and the star records (b32_sky_resident.hip).  launch_sky_fill (b32_sky.hip): k_sky_fill over the tiles of a non-empty band.
+void launch_sky_fill(hipStream_t s, const B32SkyVertex* v, uint32_t nv, const uint32_t* faces, uint32_t nf, const float2* proj,
+                     uint32_t* fb, uint32_t width, uint32_t height, uint32_t band_y0, uint32_t band_y1);
+void launch_sky_place_project(hipStream_t s, const B32SkyVertex* offsets, uint32_t nv, const B32Camera& cam, uint32_t width, uint32_t height, float2* proj);
+constexpr uint32_t STAR_SMALL = 64;            // batches of at most this many stars travel in the kernel argument (768 bytes)
+constexpr uint32_t STAR_MAX = 0x7FFFFFFFu / 9u;   // more stars than this could write more records than the pass counts
+struct StarArgs {
+    const B32Star* stars; uint32_t n;          // stars == nullptr: the batch is the kernel argument
+    uint32_t per;                              // records per star: 1, 5 or 9 (star_per)
+    B32Prim* out;
+};
+// size.max(1.0) as i32 (render.rs:207) -> the set_pixel_safe calls of one star
+constexpr uint32_t star_per(float size) { return !(size >= 2.0f) ? 1u : (!(size >= 3.0f) ? 5u : 9u); }
+void launch_star_records(hipStream_t s, const StarArgs& a, const B32Star* small);          // small != nullptr: n <= STAR_SMALL stars passed by value
 
 struct FillArgs {
     FrameParams fp;

@@ -163,6 +163,14 @@ struct b32_room {
     void* d_hover = nullptr; bool have_hover = false;
 };
 
+// A resident sky (b32_sky_create, b32_api.hip): the offsets generate_mesh adds to the camera position, with their colours, and the faces.
+struct b32_sky {
+    b32_ctx* owner = nullptr;                   // the context it was created on: every other one answers B32_E_ARG
+    B32SkyVertex* verts = nullptr; uint32_t* faces = nullptr; uint32_t nv = 0, nf = 0;
+    float2* proj = nullptr;                     // nv projected points: written by every b32_render_sky, sized at create
+    Staged<B32SkyVertex> ring;                  // b32_sky_update's pinned ring (its copies land in `verts`; ring.dev stays empty)
+};
+
 // Device words that stay armed between two calls (armed_ensure).
 struct ArmedWords { void* p = nullptr; size_t cap = 0; };
 // HIP events around the kernels of the last call of its kind enqueued while profiling was on (b32_last_kernel_times); created on first use.
@@ -254,6 +262,7 @@ struct b32_ctx {
     // batch); drawn / dropped / rejected on the device; HIP events around the last projection kernel enqueued while profiling was on
     // (b32_last_kernel_times "world_project")
     Staged<B32WorldItem> world;
+    Staged<B32Star> stars;                                        // b32_draw_stars: the pinned ring and device copy of a batch of more than STAR_SMALL stars
     Staged<uint32_t> patch;                                       // b32_scene_patch_*: the records' (or the rectangle's) pinned ring and device copy, in dwords
     ArmedWords world_counts;
     unsigned long long world_tile_batches = 0, world_scan_batches = 0;
@@ -392,10 +401,10 @@ static int ensure_plain(b32_ctx* c, T*& p, size_t count) {   // exact-size (re)a
     return B32_OK;
 }
 
-// Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there to ps.dev
-// on the stream.
+// Stage the records: a batch is copied into a pinned ring slot of `ps` (the caller may reuse its array at once) and from there on the
+// stream to `dst` (device memory of the caller's, n records of room: b32_sky_update), or to ps.dev (dst == nullptr, grown to the batch).
 template <class Rec>
-static int stage_records(b32_ctx* c, Staged<Rec>& ps, const Rec* recs, uint32_t n) {
+static int stage_records(b32_ctx* c, Staged<Rec>& ps, const Rec* recs, uint32_t n, Rec* dst = nullptr) {
     const uint32_t k = ps.slot;
     ps.slot = (k + 1) % LINE_RING;
     if (ps.ev[k]) HIPCHK(c, hipEventSynchronize(ps.ev[k]));
@@ -409,8 +418,8 @@ static int stage_records(b32_ctx* c, Staged<Rec>& ps, const Rec* recs, uint32_t 
     }
     std::memcpy(ps.host[k], recs, (size_t)n * sizeof(Rec));
     int rc;
-    if ((rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
+    if (!dst && (rc = ensure(c, ps.dev, ps.cap_dev, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(dst ? dst : ps.dev, ps.host[k], (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(ps.ev[k], c->stream));
     return B32_OK;
 }

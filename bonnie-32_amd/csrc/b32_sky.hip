@@ -5,6 +5,7 @@
 // The procedural parts that call sin/cos/powf (Skybox::generate_mesh world/geometry.rs:529, star directions render.rs:166-196)
 // stay on the host like the camera basis: they are inputs here.
 #include "b32_device.h"
+#include "b32_sky_body.h"
 
 namespace b32 {
 
@@ -29,21 +30,11 @@ void launch_clear_gradient(hipStream_t s, uint32_t* fb, float* zbuf, uint32_t wi
 }
 
 // ---------------------------------------------------------------- skybox sphere
-// vertex pass: perspective_transform (math.rs:103-109) + project (math.rs:117-136); behind the camera -> NaN marker (render.rs:99-103)
+// vertex pass: the screen point (sky_screen_point, b32_sky_body.h) of `pos - camera.position`
 __global__ void k_sky_project(const B32SkyVertex* __restrict__ v, uint32_t nv, B32Camera cam, uint32_t width, uint32_t height, float2* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nv) return;
-    const float rx = v[i].pos[0] - cam.position[0], ry = v[i].pos[1] - cam.position[1], rz = v[i].pos[2] - cam.position[2];
-    const float cx = rx * cam.basis_x[0] + ry * cam.basis_x[1] + rz * cam.basis_x[2];
-    const float cy = rx * cam.basis_y[0] + ry * cam.basis_y[1] + rz * cam.basis_y[2];
-    const float cz = rx * cam.basis_z[0] + ry * cam.basis_z[1] + rz * cam.basis_z[2];
-    const float qnan = __uint_as_float(0x7FC00000u);
-    if (cz <= 0.1f) { out[i] = make_float2(qnan, qnan); return; }
-    const uint32_t mn = width < height ? width : height;
-    const float vs = ((float)mn / 2.0f) * 0.75f;
-    const float denom = cz + 5.0f;
-    if (__builtin_fabsf(denom) < 0.001f) { out[i] = make_float2((float)width / 2.0f, (float)height / 2.0f); return; }
-    out[i] = make_float2((cx * 4.0f) / denom * vs + ((float)width / 2.0f), (cy * 4.0f) / denom * vs + ((float)height / 2.0f));
+    sky_screen_point(v[i].pos[0] - cam.position[0], v[i].pos[1] - cam.position[1], v[i].pos[2] - cam.position[2], cam, width, height, &out[i]);
 }
 
 constexpr int SKY_LIST_CAP = 4096;      // faces one 64x64 tile can list per round (the walk is chunked beyond that)
@@ -156,12 +147,17 @@ __global__ __launch_bounds__(256) void k_sky_fill(const B32SkyVertex* __restrict
     }
 }
 
+// the fill over the 64x64 tiles the (non-empty) band touches, from a projected table some vertex kernel wrote on the stream
+void launch_sky_fill(hipStream_t s, const B32SkyVertex* v, uint32_t nv, const uint32_t* faces, uint32_t nf, const float2* proj,
+                     uint32_t* fb, uint32_t width, uint32_t height, uint32_t band_y0, uint32_t band_y1) {
+    const uint32_t tiles_x = (width + 63) / 64, tile_y0 = band_y0 / 64, tiles_y = (band_y1 + 63) / 64 - tile_y0;
+    hipLaunchKernelGGL(k_sky_fill, dim3(tiles_x * tiles_y), dim3(256), 0, s, v, faces, nf, nv, proj, fb, width, height, band_y0, band_y1, tiles_x, tile_y0);
+}
 void launch_sky(hipStream_t s, const B32SkyVertex* v, uint32_t nv, const uint32_t* faces, uint32_t nf, const B32Camera& cam, float2* proj,
                 uint32_t* fb, uint32_t width, uint32_t height, uint32_t band_y0, uint32_t band_y1) {
     if (!nv || !nf || band_y1 <= band_y0) return;
     hipLaunchKernelGGL(k_sky_project, dim3((nv + 255) / 256), dim3(256), 0, s, v, nv, cam, width, height, proj);
-    const uint32_t tiles_x = (width + 63) / 64, tile_y0 = band_y0 / 64, tiles_y = (band_y1 + 63) / 64 - tile_y0;
-    hipLaunchKernelGGL(k_sky_fill, dim3(tiles_x * tiles_y), dim3(256), 0, s, v, faces, nf, nv, proj, fb, width, height, band_y0, band_y1, tiles_x, tile_y0);
+    launch_sky_fill(s, v, nv, faces, nf, proj, fb, width, height, band_y0, band_y1);
 }
 
 // ---------------------------------------------------------------- star sprites, draw_star_diamond (render.rs:199-240): strictly in order

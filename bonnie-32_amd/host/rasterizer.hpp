@@ -131,6 +131,8 @@ public:
     void draw_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { draw_prim(prim(B32_PRIM_RECT, x0, y0, x1, y1, c)); }
     void draw_filled_rect(int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c) { draw_prim(prim(B32_PRIM_FILLED_RECT, x0, y0, x1, y1, c)); }
     void draw_prims(const std::vector<B32Prim>& prims) { check(b32_draw_prims(ctx_, prims.data(), (uint32_t)prims.size()), "draw_prims"); }
+    // draw_star_diamond, render.rs:206-237, for every star in order (enqueued: the records are made on the device and go through the pass)
+    void draw_stars(const std::vector<B32Star>& stars, float size) { check(b32_draw_stars(ctx_, stars.data(), (uint32_t)stars.size(), size), "draw_stars"); }
     // one B32Prim record (kinds B32_LINE_* / B32_PRIM_*; z0 / z1 only for the 3-D line kinds)
     static B32Prim prim(uint8_t kind, int32_t x0, int32_t y0, int32_t x1, int32_t y1, Color c, int32_t size = 0, uint8_t alpha = 255,
                         BlendMode mode = BlendMode::Opaque, float z0 = 0.0f, float z1 = 0.0f) {
@@ -1118,12 +1120,41 @@ inline RasterTimings render_frame(Framebuffer& fb, const std::vector<std::pair<c
 }
 
 // The console's loop as the reference runs it -- every frame drawn (scene::render_scene, scene.rs:158-261) AND handed to the presenter from host
-// memory (game/renderer.rs:179-214) -- without a host round trip per frame: submit() enqueues Framebuffer::clear, the frame's draws
+// memory (game/renderer.rs:179-214) -- without a host round trip per frame: submit() enqueues Framebuffer::clear, the sky (`sky`), the frame's draws
 // (b32_frame_submit: the mesh table in one call) and the copy of the finished frame into page-locked memory (b32_fb_download_async), and
 // returns a ticket; wait(ticket) blocks until THAT frame's pixels are in the returned buffer.  Two buffers alternate, so the presenter reads
 // frame i while frame i + 1 is drawn: keep at most two tickets outstanding.  A frame may carry one pick (submit's `pick`): it is enqueued
 // behind the frame's draws, delivered into page-locked memory of its own and waited for one frame behind like the pixels (wait_pick); and,
 // beside it, one hover of one of its meshes (submit's `hover`, wait_hover).
+// A resident sky (b32_sky): Skybox::generate_mesh((0, 0, 0), time) once -- its positions are the offsets the reference adds to the camera
+// position (world/geometry.rs:555-559, :686-710) -- then render() per frame from the camera alone (render.rs:81-139), and update() for the
+// rows of a scrolling cloud layer.  Nothing here waits for the device but the constructor and the destructor.
+class Sky {
+public:
+    Sky(Framebuffer& fb, const std::vector<B32SkyVertex>& offsets, const std::vector<uint32_t>& faces /* 3 per face */)
+        : ctx_(fb.ctx()), nv_((uint32_t)offsets.size()) {
+        check(b32_sky_create(ctx_, offsets.data(), nv_, faces.data(), (uint32_t)(faces.size() / 3), &s_), "sky_create");
+    }
+    ~Sky() { if (s_) b32_sky_destroy(ctx_, s_); }
+    Sky(Sky&& o) noexcept : ctx_(o.ctx_), s_(o.s_), nv_(o.nv_) { o.s_ = nullptr; }
+    Sky(const Sky&) = delete;
+    Sky& operator=(const Sky&) = delete;
+    void update(uint32_t first, const std::vector<B32SkyVertex>& verts) { check(b32_sky_update(ctx_, s_, first, (uint32_t)verts.size(), verts.data()), "sky_update"); }
+    void render(Framebuffer& fb, const Camera& camera) const { const B32Camera c = detail::pack(camera); check(b32_render_sky(fb.ctx(), s_, &c), "render_sky"); }
+    // stage tap (blocking): x, y per vertex for a w x h framebuffer, a NaN pair behind the camera
+    std::vector<float> project(const Camera& camera, uint32_t w, uint32_t h) const {
+        const B32Camera c = detail::pack(camera);
+        std::vector<float> xy((size_t)nv_ * 2);
+        check(b32_sky_project_batch(ctx_, s_, &c, w, h, xy.data()), "sky_project_batch");
+        return xy;
+    }
+    b32_sky* handle() const { return s_; }
+    uint32_t vertices() const { return nv_; }
+private:
+    b32_ctx* ctx_ = nullptr; b32_sky* s_ = nullptr; uint32_t nv_ = 0;
+};
+// What FrameLoop::submit draws between the clear and the meshes (game/renderer.rs:88-96): the sky, then the stars of `size`.
+struct FrameSky { const Sky* sky = nullptr; std::vector<B32Star> stars; float size = 3.0f; };
 struct FrameHover { const ResidentMesh* mesh; const Topology* topology; B32HoverParams params; std::optional<Vec3> ortho = std::nullopt; std::optional<Placement> placement = std::nullopt; };
 struct FramePick { std::vector<PickItem> items; float mx = 0, my = 0; std::optional<Vec3> ortho = std::nullopt; bool cull_backfaces = false; };
 class FrameLoop {
@@ -1136,7 +1167,7 @@ public:
     FrameLoop(const FrameLoop&) = delete;
     FrameLoop& operator=(const FrameLoop&) = delete;
     uint64_t submit(Color clear, const std::vector<std::pair<const ResidentMesh*, MeshParams>>& meshes, const Camera& camera, const RasterSettings& base,
-                    const FramePick* pick = nullptr, const FrameHover* hover = nullptr) {
+                    const FramePick* pick = nullptr, const FrameHover* hover = nullptr, const FrameSky* sky = nullptr) {
         const std::vector<B32Light> l = detail::pack(base.lights);
         const B32Camera c = detail::pack(camera);
         const B32Settings s = detail::pack(base, l);
@@ -1150,6 +1181,10 @@ public:
             has_place.push_back(detail::pack(m.second.placement, pl) ? 1 : 0); places.push_back(pl);
         }
         fb_.clear(clear);
+        if (sky) {                                                  // behind the clear, in front of the meshes
+            if (sky->sky) sky->sky->render(fb_, camera);
+            fb_.draw_stars(sky->stars, sky->size);
+        }
         check(b32_frame_submit_placed(fb_.ctx(), &c, &s, slots.data(), params.data(), places.data(), has_place.data(), (uint32_t)slots.size()), "frame_submit_placed");
         const size_t k = n_++ & 1;
         pick_ticket_[k] = 0;

@@ -328,6 +328,23 @@ def prim(kind, x0, y0, x1, y1, color: T.Color, z0=0.0, z1=0.0, size=0, alpha=255
     return p
 
 
+def pack_sky_vertices(vertices):
+    """abi.SKY_VERTEX_DTYPE records (b32_sky_create, b32_sky_update) of a structured array as it is."""
+    return np.ascontiguousarray(vertices, abi.SKY_VERTEX_DTYPE).reshape(-1)
+
+
+def pack_stars(stars, cy=None, rgb=None):
+    """abi.STAR_DTYPE records (b32_draw_stars): a structured array as it is, or the three arrays draw_star_diamonds takes (cx, cy, rgb)."""
+    if cy is None:
+        return np.ascontiguousarray(stars, abi.STAR_DTYPE).reshape(-1)
+    cx = np.asarray(stars, np.int32).reshape(-1)
+    c = np.asarray(rgb, np.uint8).reshape(-1, 3)
+    s = np.zeros(len(cx), abi.STAR_DTYPE)
+    s["cx"], s["cy"] = cx, np.asarray(cy, np.int32).reshape(-1)
+    s["r"], s["g"], s["b"] = c[:, 0], c[:, 1], c[:, 2]
+    return s
+
+
 def noop_prims(n):
     """n records that draw nothing (a circle of radius -1): what a call the reference does not make leaves in its place."""
     r = np.zeros(n, abi.PRIM_DTYPE)

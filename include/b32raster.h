@@ -254,7 +254,7 @@ int b32_frame_finish(b32_ctx* ctx, B32Timings* out /* nullable */);
  * redrawn by the host.
  *   deep = 0 (default): safe.  Enqueueing another frame, or any call that reads, writes or rebinds the framebuffer (b32_fb_download,
  *            b32_zbuffer_download, b32_fb_upload, b32_fb_clear*, b32_render_skybox_mesh, b32_draw_star_diamonds, b32_draw_lines,
- *            b32_draw_prims, b32_fb_bind_device,
+ *            b32_draw_prims, b32_render_sky, b32_draw_stars, b32_fb_bind_device,
  *            b32_set_stream, b32_present_nearest, b32_scene_upload*, b32_scene_swap, b32_set_band), first settles the pending frame (one host synchronisation, redraw if needed): no
  *            frame is ever lost, and none is redrawn on top of a later clear.  One exception that cannot be observed (round 5): a
  *            b32_fb_clear of the whole band behind a pending frame overwrites every pixel and depth that frame can have drawn, so the
@@ -928,6 +928,32 @@ int b32_render_skybox_mesh(b32_ctx* ctx, const B32SkyVertex* vertices, uint32_t 
                            const B32Camera* camera);
 /* draw_star_diamond, render.rs:199-240, for n stars in order: centre (cx, cy) = (screen.x as i32, screen.y as i32), colour rgb[3*i..]. */
 int b32_draw_star_diamonds(b32_ctx* ctx, const int32_t* cx, const int32_t* cy, const uint8_t* rgb, uint32_t n, float size);
+
+/* A resident sky: the mesh of Skybox::generate_mesh (world/geometry.rs:529-720) kept on the device and drawn per frame from the camera
+ * alone.  The reference computes every position as camera_pos + x * radius (sphere :555-559, mountains :686-710) with x * radius
+ * independent of the camera, and colours that depend on `time` only inside cloud layers: the host keeps the libm part (sin, cos, acos,
+ * powf), the device adds the camera.  A b32_sky belongs to the context it was created on: with another context -> B32_E_ARG. */
+typedef struct b32_sky b32_sky;
+/* offsets[i].pos = the three products the reference ADDS to camera_pos (world/geometry.rs:555-559, :686-710): x * radius, y * radius,
+ * z * radius -- generate_mesh((0, 0, 0), time) gives them, but for the sign of a zero (0.0 + -0.0 = +0.0), which no projected coordinate
+ * can see: camera_pos + -0.0 and camera_pos + +0.0 are the same f32 unless camera_pos is -0.0, and then the position is -0.0 or +0.0
+ * and position - camera_pos is +0.0 either way (tests/test_resident_sky.py walks every combination).  Colours as in B32SkyVertex.  faces: 3 indices per face, drawn in order.  An index >= nv -> B32_E_INDEX and nothing is created (*out
+ * is written on success only).  nv == 0 or nf == 0: a sky that draws nothing.  The arrays are reusable when the call returns. */
+int  b32_sky_create(b32_ctx* ctx, const B32SkyVertex* offsets, uint32_t nv, const uint32_t* faces, uint32_t nf, b32_sky** out);
+void b32_sky_destroy(b32_ctx* ctx, b32_sky* sky);                           /* NULL: no-op; waits for the context's stream */
+/* vertices [first, first + count) replaced (offset and colour; a scrolling cloud layer of world/geometry.rs:600-660 changes the colours
+ * of its rows), ordered on the context's stream: a render enqueued before the call sees the old ones, one enqueued after it the new
+ * ones.  `verts` reusable when the call returns.  No host synchronisation.  first + count > nv, or count != 0 with verts == NULL ->
+ * B32_E_ARG and nothing changes; count == 0: no-op. */
+int  b32_sky_update(b32_ctx* ctx, b32_sky* sky, uint32_t first, uint32_t count, const B32SkyVertex* verts);
+/* Step 1 of Framebuffer::render_skybox (render.rs:81-139) for generate_mesh(camera.position, ..): per vertex pos = camera.position +
+ * offset, then render.rs:99-103 on pos - camera.position (two roundings: not the offset), then the fill of b32_render_skybox_mesh.
+ * Only rows of the band are written, the z-buffer is untouched.  Enqueued on the context's stream behind everything enqueued before (a
+ * deferred b32_fb_clear is flushed first); never waits, allocates or copies. */
+int  b32_render_sky(b32_ctx* ctx, b32_sky* sky, const B32Camera* camera);
+/* stage tap: the projected (x, y) per vertex for a w x h framebuffer (1 .. 16384 each), a NaN pair (0x7FC00000) behind the camera
+ * (render.rs:99-103); blocking; needs no framebuffer */
+int  b32_sky_project_batch(b32_ctx* ctx, b32_sky* sky, const B32Camera* camera, uint32_t w, uint32_t h, float* xy /* 2 * nv */);
 /* The Framebuffer's line family (render.rs:684-872), drawn after the meshes by every caller (the player's cylinder, the editor's
  * outlines and gizmos, the modeler's edge overlay).  Lines never write the z-buffer; they read it (f32::MAX everywhere while it is not
  * valid, as in painter's mode).  Colour = Color{r, g, b, blend} (blend: BlendMode, B32_BLEND_ERASE -> alpha byte 0 in set_pixel,
@@ -981,6 +1007,24 @@ typedef struct B32Prim {
  * -> B32_E_UNSUPPORTED; for circles |radius| > 32767 or |x0|, |y0| >= 2^30 (r*r, dx*dx + dy*dy or cy +- r overflow i32 in the
  * reference) -> B32_E_UNSUPPORTED.  B32_PRIM_FILLED_RECT takes any i32.  n == 0: no-op. */
 int b32_draw_prims(b32_ctx* ctx, const B32Prim* prims, uint32_t n);
+
+/* Stars through the ordered tile pass.  The star's direction, its visibility test and the twinkle stay with the caller: the reference's
+ * LCG draws the phase only for a visible star (render.rs:184-191), so star i's direction depends on how many earlier stars the camera
+ * sees.  A star is what draw_star_diamond is called with: */
+typedef struct B32Star { int32_t cx, cy; uint8_t r, g, b, _pad; } B32Star;   /* 12 bytes: (screen.x as i32, screen.y as i32), the twinkled colour */
+/* draw_star_diamond (render.rs:206-237) for stars[0..n) in order: 1, 5 or 9 set_pixel_safe calls per star with s = size.max(1.0) as i32
+ * (NaN -> 1, the cast saturates) -- the centre, the four points at distance 1 when s >= 2 (colour channels (c as f32 * 0.7) as u8), the
+ * four at distance 2 when s >= 3 ((c as f32 * 0.4) as u8); cx + dx wraps.  Each call becomes a 1x1 B32_PRIM_FILLED_RECT record ON THE
+ * DEVICE (draw_filled_rect clamps to an empty range for anything outside, render.rs:954-971), and the records go through the ordered
+ * tile pass with b32_draw_prims's contract: every pixel and byte equal, only rows of the band written, the z-buffer read (f32::MAX
+ * while it is not valid) and never written, enqueued on the context's stream with no host synchronisation (a deferred clear is flushed
+ * first), `stars` reusable as soon as the call returns.  n > (2^31 - 1) / 9 -> B32_E_UNSUPPORTED.  n == 0: no-op. */
+int b32_draw_stars(b32_ctx* ctx, const B32Star* stars, uint32_t n, float size);
+/* host only: *records = n * (1, 5 or 9) */
+int b32_star_record_count(uint32_t n, float size, uint64_t* records);
+/* stage tap: the records of b32_draw_stars, star i's at [i * per, (i + 1) * per) in the order centre, (-1,0), (+1,0), (0,-1), (0,+1),
+ * (-2,0), (+2,0), (0,-2), (0,+2); blocking; needs no framebuffer.  More than `cap` records -> B32_E_ARG. */
+int b32_star_records_batch(b32_ctx* ctx, const B32Star* stars, uint32_t n, float size, B32Prim* out, uint32_t cap, uint32_t* n_records);
 
 /* World-space overlays (rasterizer/draw.rs:12-135, math.rs:503-652).  Every caller of the drawing methods above starts from world positions:
  * it projects both ends with one of the world_to_screen functions, casts with `as i32` and calls fb.draw_*.  An item is one such call:
